@@ -23,6 +23,11 @@ Workloads (BASELINE.json `configs`):
 
 metric value = read-vs-haplotype alignments (2 per scored read) of all ranks per step /
 max-over-ranks wall time per step.
+
+A plain run does only what that figure needs: generate, submit, warm up, time the K steps, print the line.
+Everything else it can measure (the hand-over timings, `sustained`, the other aligner, `sensitivity`, the CPU
+baseline) runs with --full only.  --dump-outputs DIR writes what the last timed step computed as .npy files;
+the inputs come from fixed seeds, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -132,6 +137,37 @@ def cpu_baseline(batch, cfg, target_seconds=12.0):
                                                       "full" if cfg.aligner == 1 else "banded", cores)}
 
 
+DUMP_SEED = 20261016
+DUMP_SCORES_MAX = 1 << 20      # per-record scores kept per array (2 arrays)
+DUMP_COO_MAX = 1 << 19         # triplets kept per field (7 fields): 2 x 8 MiB + 7 x 4 MiB of float64 at most
+
+
+def dump_sample(n: int, k: int) -> np.ndarray:
+    """Sorted indices of a fixed, seeded sample of k out of n (all of them when n <= k): the same n, the same indices."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, ctx, coo_t):
+    """What the last timed step computed, as a caller of vtx_run receives it: the per-record scores (vtx_fetch_scores, in the
+    library's record order) and the COO matrix (row, col, the three counts, value, ref_value; the gathered one at N > 1), as
+    float64 .npy files (every field is exact in float64).  Arrays longer than the caps above are sampled at fixed, seeded indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    ref, alt = ctx.fetch_scores()
+    idx = dump_sample(len(ref), DUMP_SCORES_MAX)
+    for name, a in (("scores_ref", ref), ("scores_alt", alt)):
+        np.save(os.path.join(out_dir, name + ".npy"), a[idx].astype(np.float64))
+    if coo_t is None:
+        return
+    n = int(coo_t["row"].shape[0])
+    idx_t = torch.from_numpy(dump_sample(n, DUMP_COO_MAX)).to(coo_t["row"].device)
+    for k, dt in shard.COO_FIELDS:
+        t = coo_t[k].index_select(0, idx_t)
+        t = (t.to(torch.int64) & 0xffffffff) if dt is np.uint32 else t      # uint32 fields travel as int32 tensors
+        np.save(os.path.join(out_dir, "coo_%s.npy" % k), t.to(torch.float64).cpu().numpy())
+
+
 def band_cells_sample(batch, cfg, n_loci=32):
     """DP cells bio's banded aligner would evaluate (oracle.batch_cells), per alignment, on a sample."""
     from oracle import oracle
@@ -164,6 +200,13 @@ def main():
     ap.add_argument("--sub-error", type=float, default=0.005)
     ap.add_argument("--genome", default="", help="FASTA: draw the loci from this sequence instead of an iid genome (sensitivity runs, "
                     "e.g. tests/golden/test_dna.fa: 181 kb of real sequence; the headline workload is the iid one)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the steady-state and nibble hand-overs (timing.submit_*), "
+                         "`sustained`, `other_aligner` / `banded_vs_full`, `sensitivity`, `cpu_baseline` / `work_avoided_equivalent`; "
+                         "the --no-* options and --sustain-seconds below act inside --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64): the per-record "
+                         "scores and the COO matrix (rank 0's; the gathered matrix at N > 1), each a fixed, seeded sample when larger")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sensitivity", action="store_true",
                     help="skip the `sensitivity` object (N = 1, default workload): the same 100 k x 10 k job with its loci drawn from real "
@@ -175,6 +218,8 @@ def main():
                     help="after the K timed steps (the contract's measurement: value / ms_per_step), keep stepping until this much wall "
                          "time has passed and report it as `sustained` (steps, seconds, value): a cross-check of a short timed region; 0: off")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -234,28 +279,29 @@ def main():
                          n_barcodes=n_barcodes, device=local_rank)
     ctx = lib.Context(cfg)
     ctx.submit(batch)                                      # H2D: outside the timed region (first submit of the context: + buffer allocation)
-    t_sub = time.perf_counter()
-    ctx.submit(batch)                                      # the steady-state hand-over of a batch: validation, H2D, work lists
-    t_sub = time.perf_counter() - t_sub
-    # the same hand-over with the bases two per byte, as a BAM record holds them and as the drop-in CLI ships them (vtx_set_read_format:
-    # the device unpacks): half the bytes through the pinned buffers and over PCIe.  The conversion is not timed — the packer copies
-    # the nibbles out of the BAM, it never has the bytes.  The timed steps below run on the byte-submitted batch.
-    t_sub_nib = None
-    nib_attempted = False
-    try:
-        nib = batch.to_nibbles()                               # (ValueError: a generator that lays reads out at odd offsets)
-        nib_attempted = True
-        ctx.submit(nib)
-        t_sub_nib = time.perf_counter()
-        ctx.submit(nib)
-        t_sub_nib = time.perf_counter() - t_sub_nib
-        del nib
-    except Exception as e:                                     # a side figure: it must never take the bench line down
-        t_sub_nib = None
-        if rank == 0:
-            print("bench: nibble hand-over not measured: %s" % e, file=sys.stderr)
-    if nib_attempted:
-        ctx.submit(batch)                                      # the byte-submitted batch is what the timed steps run on
+    t_sub, t_sub_nib = None, None
+    if args.full:
+        t_sub = time.perf_counter()
+        ctx.submit(batch)                                  # the steady-state hand-over of a batch: validation, H2D, work lists
+        t_sub = time.perf_counter() - t_sub
+        # the same hand-over with the bases two per byte, as a BAM record holds them and as the drop-in CLI ships them (vtx_set_read_format:
+        # the device unpacks): half the bytes through the pinned buffers and over PCIe.  The conversion is not timed — the packer copies
+        # the nibbles out of the BAM, it never has the bytes.  The timed steps below run on the byte-submitted batch.
+        nib_attempted = False
+        try:
+            nib = batch.to_nibbles()                           # (ValueError: a generator that lays reads out at odd offsets)
+            nib_attempted = True
+            ctx.submit(nib)
+            t_sub_nib = time.perf_counter()
+            ctx.submit(nib)
+            t_sub_nib = time.perf_counter() - t_sub_nib
+            del nib
+        except Exception as e:                                 # a side figure: it must never take the bench line down
+            t_sub_nib = None
+            if rank == 0:
+                print("bench: nibble hand-over not measured: %s" % e, file=sys.stderr)
+        if nib_attempted:
+            ctx.submit(batch)                                  # the byte-submitted batch is what the timed steps run on
 
     # Row gather.  Default: the PRODUCT's own exchange behind the C-ABI (vtx_comm_init / vtx_gather_coo: one ncclAllGather of
     # (count, status), then grouped ncclSend / ncclRecv of exact-size blocks to their final offsets on rank 0 — what a Rust host would
@@ -359,7 +405,7 @@ def main():
         et = torch.tensor([elapsed], dtype=torch.float64, device=ddev)
         dist.all_reduce(et, op=dist.ReduceOp.MAX)
         elapsed_all = float(et.item())
-    if args.sustain_seconds > 0 and elapsed_all < args.sustain_seconds:
+    if args.full and args.sustain_seconds > 0 and elapsed_all < args.sustain_seconds:
         more = int(min(10000, max(1, (args.sustain_seconds - elapsed_all) / max(elapsed_all / args.steps, 1e-6))))
         fence()
         t1 = time.perf_counter()
@@ -373,14 +419,17 @@ def main():
     nnz = ctx.device_coo()["nnz"]
 
     # result summary: the gathered matrix on rank 0 (N > 1) / the device triplets (N = 1)
-    summary = None
+    coo_t = None
     if use_gather:
         if rank == 0 and native and native_last[0] is not None:
-            summary = coo_summary(shard.device_coo_tensors(ctx, device, native_last[0]))
+            coo_t = shard.device_coo_tensors(ctx, device, native_last[0])
         elif rank == 0 and pipe is not None and pipe.last is not None:
-            summary = coo_summary(pipe.last)
+            coo_t = pipe.last
     else:
-        summary = coo_summary(shard.device_coo_tensors(ctx, device))
+        coo_t = shard.device_coo_tensors(ctx, device)
+    summary = None if coo_t is None else coo_summary(coo_t)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, coo_t)
 
     if world > 1:
         tt = torch.tensor([elapsed, sustained["seconds"] if sustained else 0.0], dtype=torch.float64, device=ddev)
@@ -396,7 +445,7 @@ def main():
 
     # secondary (N = 1): the other aligner flavour on the same resident-size batch, and how the two differ
     other, versus = None, None
-    if rank == 0 and world == 1 and not args.no_other_aligner:
+    if args.full and rank == 0 and world == 1 and not args.no_other_aligner:
         oname = "full" if args.aligner == "banded" else "banded"
         ocfg = default_config(aligner=oname, scoring_mode=args.mode, use_umi=args.umi, n_barcodes=n_barcodes, device=local_rank)
         octx = lib.Context(ocfg)
@@ -423,7 +472,7 @@ def main():
     # on noisy reads, measured in this process.  The headline's iid genome with 0.5 % errors is what BASELINE.json names; a
     # production BAM looks like something between these.
     sensitivity = None
-    if rank == 0 and world == 1 and workload == "config3" and args.aligner == "banded" and not args.no_sensitivity:
+    if args.full and rank == 0 and world == 1 and workload == "config3" and args.aligner == "banded" and not args.no_sensitivity:
         sensitivity = {}
         cases = [("real_sequence_loci", dict(genome_fasta=os.path.join(ROOT, "tests", "golden", "test_dna.fa"))),
                  ("sub_error_3pct", dict(sub_error=0.03)), ("sub_error_8pct", dict(sub_error=0.08)),
@@ -532,7 +581,7 @@ def main():
                        "diag_left_tasks": int(ctx.timing().diag_left), "reduce_ms": float(np.mean(red_ms)), "submit_h2d_s": t_sub,
                        "generate_s": t_gen, "hard_tasks": int(ctx.timing().hard_tasks),
                        "overflow_tasks": int(ctx.timing().overflow_tasks),
-                       "pcie_inclusive_alignments_per_s": n_aln / (t_sub + elapsed / args.steps),
+                       "pcie_inclusive_alignments_per_s": (n_aln / (t_sub + elapsed / args.steps)) if t_sub is not None else None,
                        "submit_h2d_nibbles_s": t_sub_nib,
                        "pcie_inclusive_nibbles_alignments_per_s": (n_aln / (t_sub_nib + elapsed / args.steps)) if t_sub_nib else None},
         }
@@ -631,7 +680,7 @@ def main():
             out["other_aligner"] = other
         if versus is not None:
             out["banded_vs_full"] = versus
-        if not args.no_cpu_baseline and world == 1:                  # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:    # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(batch, cfg, args.cpu_seconds)
             if banded:
                 # what the reference's own algorithm would have had to compute: its in-band DP cells (sampled with the

@@ -4,13 +4,32 @@ vtx_fetch_coo; and bench.py's own gather path (VTX_FORCE_GATHER=1) against its p
 exchange itself is covered by the world_size-2 gloo tests (tests/test_shard.py), which drive the same objects."""
 import json
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SUN_PATH_MAX = 107                 # bytes of a Unix socket path (sockaddr_un.sun_path, 108 with the NUL)
+SOCKET_NAME_LEN = len("/vtxcomm-") + 32 + len(".") + 3      # what the test transport appends (vtx_comm_test.hip: sock_path)
+
+
+@pytest.fixture
+def comm_dir():
+    """Directory for the test transport's sockets (VTX_COMM_TEST_TRANSPORT).  Not tmp_path: under a long user name, TMPDIR or
+    session number that path leaves no room for the socket name, the library's snprintf cuts off the rank suffix and every rank
+    binds the same socket.  A directory of its own under the temp root, or /tmp when that root is long too."""
+    root = tempfile.gettempdir()
+    if len(root) + len("/vtxc-xxxxxxxx") + SOCKET_NAME_LEN > SUN_PATH_MAX:
+        root = "/tmp"
+    d = tempfile.mkdtemp(prefix="vtxc-", dir=root)
+    assert len(d) + SOCKET_NAME_LEN <= SUN_PATH_MAX, d
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
 
 _CODE = r'''
 import os, sys
@@ -138,18 +157,19 @@ def test_bench_torch_gather_matches_plain_run():
     assert "VTX_BENCH_TEST_COMM_FAIL" in fb["gather"]["fallback_from_vtx_gather_coo"]
 
 
-def test_two_rank_launch_rehearsal_on_one_device(tmp_path):
+def test_two_rank_launch_rehearsal_on_one_device(comm_dir):
     """`python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 ...` exactly as the driver launches the scaling bench,
     on ONE device: the ranks share it, the library's exchange (vtx_comm_init, vtx_gather_coo in every step) runs over the test
     transport of libvtx_dev.so, torch.distributed falls back to gloo for the barriers.  The line must parse, say n_gpus 2 and the
     library's gather, and carry the matrix of the unsharded run."""
     args = ["--loci", "4000", "--barcodes", "50000", "--reads-per-locus", "32"]
     plain = _bench({}, args)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", VTX_LIB_VARIANT="dev", VTX_COMM_TEST_TRANSPORT=str(tmp_path))
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", VTX_LIB_VARIANT="dev", VTX_COMM_TEST_TRANSPORT=comm_dir)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29641", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"] + args,
+                        "--master-port", "29641", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+                        "--full"] + args,
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -162,14 +182,14 @@ def test_two_rank_launch_rehearsal_on_one_device(tmp_path):
     assert j["value"] > 0 and j["ms_per_step"] > 0 and j["sustained"]["steps"] >= 1
 
 
-def test_eight_rank_launch_rehearsal_on_one_device(tmp_path):
+def test_eight_rank_launch_rehearsal_on_one_device(comm_dir):
     """The driver's 8-GPU command — `torchrun --nproc-per-node 8 bench.py --gpus 8` — on ONE device over the test transport (round 6:
     8 is what the scaling run launches; 2 and 4 were the rehearsed worlds).  Eight contexts share the device (a reduced config 4:
     50 000 barcodes, sharded by partition_loci), every step ends in the library's gather with seven senders, the communicator
     reports 8 ranks, and the gathered matrix equals the unsharded run's."""
     args = ["--loci", "6000", "--barcodes", "50000", "--reads-per-locus", "24", "--no-sensitivity", "--no-cpu-baseline", "--no-other-aligner"]
     plain = _bench({}, args)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", VTX_LIB_VARIANT="dev", VTX_COMM_TEST_TRANSPORT=str(tmp_path))
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", VTX_LIB_VARIANT="dev", VTX_COMM_TEST_TRANSPORT=comm_dir)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
@@ -252,11 +272,11 @@ def _run_world(world, scenario, tmp):
 
 
 @pytest.mark.parametrize("world,scenario", [(2, "consensus"), (2, "alt_frac"), (4, "alt_frac"), (4, "empty")])
-def test_gather_coo_between_processes_equals_the_unsharded_matrix(tmp_path, world, scenario):
+def test_gather_coo_between_processes_equals_the_unsharded_matrix(comm_dir, world, scenario):
     import numpy as np
     from vartrix_amd import lib, synth
     from vartrix_amd.abi import default_config
-    outs = _run_world(world, scenario, tmp_path)
+    outs = _run_world(world, scenario, comm_dir)
     assert all(o.startswith("ok") for o in outs), outs
     assert [int(o.split()[1]) for o in outs[1:]] == [0] * (world - 1)                  # nnz = 0 away from the destination
     mode, umi = ("alt_frac", 1) if scenario != "consensus" else ("consensus", 0)
@@ -265,14 +285,14 @@ def test_gather_coo_between_processes_equals_the_unsharded_matrix(tmp_path, worl
         ctx.submit(synth.make_batch(spec))
         ctx.run()
         want = ctx.fetch_coo()
-    got = np.load(tmp_path / "gathered.npz")
+    got = np.load(os.path.join(comm_dir, "gathered.npz"))
     assert int(outs[0].split()[1]) == len(want["row"]) > 1000
     for k in want:
         assert np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), (world, scenario, k)
 
 
-def test_a_failing_rank_makes_every_gather_return_peer_error(tmp_path):
+def test_a_failing_rank_makes_every_gather_return_peer_error(comm_dir):
     from vartrix_amd import abi
-    outs = _run_world(4, "fail", tmp_path)
+    outs = _run_world(4, "fail", comm_dir)
     assert outs[3] == "aborted"
     assert outs[:3] == ["error %d" % abi.VTX_E_PEER] * 3, outs

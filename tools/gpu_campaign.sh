@@ -92,7 +92,7 @@ case $CMD in
     bash tools/pmc_collect.sh /tmp/pmc --no-sensitivity --sustain-seconds 0 > $OUT/pmc_collect.log 2>&1
     python tools/pmc_summarize.py /tmp/pmc $OUT/pmc_counters.json 24320920 $OUT/pmc_traffic.json > $OUT/pmc_summary.txt 2>&1
     [ -s $OUT/pmc_traffic.json ] && cp $OUT/pmc_traffic.json profiles/pmc_traffic.json
-    python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
+    python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
     bash $0 stats $OUT head genome e3 e8 c5 d16 d4 e1 r250 p150
     bash $0 lines $OUT d128 d64 d32 d16 d4 ln8 c4
     # end to end through the drop-in CLI at config-3 scale (device ingest against the host packer), and the kernels of one such run
