@@ -10,6 +10,8 @@ and by tools/certify_stress.py / tools/gpu_parity_stress.py, which run the same 
                       matches of iid bases, satellite repeats in the tail)
   real_shape_batches  what real 10x reads add to `150M`: soft-clipped ends (the clip is random sequence), adapter tails, spliced
                       reads (the read skips an intron of the reference: CIGAR N), lower-case / N bases
+  adversarial_batches shapes aimed at the certificate bounds (excursions over far pieces, tandem repeats, indel errors in reads, edge
+                      bytes and lengths), built as numpy arrays: the GPU audit (tests/audit_util.py) runs 10 M alignments of them
 """
 import numpy as np
 
@@ -217,3 +219,221 @@ def real_shape_batches(trials=4, loci=80, reads=40, seed=77):
                 rl.append((int(rng.integers(0, 30)), int(rng.integers(0, 5)), bytes(rd)))
             rds.append(rl)
         yield ("real-read shapes (clips, adapters, splices, poly-A, N), trial %d" % trial, manual_batch(haps, rds, 30), 30)
+
+
+# ---- adversarial batches: shapes aimed at the certificate bounds (vtx_fast_core.h, vtx_band_trim.h), built as arrays ----
+#   excursion    a read copies its haplotype; inside a gap of D = 12 - 21 bases 6 - 9 bases are overwritten with haplotype bases taken
+#                1 - 6 diagonals away (an exact off-diagonal run between two main runs: the shape of the round-6 join_gap3 bug), plus
+#                0 - 3 more errors in the gap and 0 - 3 % substitutions elsewhere
+#   repeats      tandem repeats (unit 1 - 12 bases) and homopolymers in haplotype and read, one across the variant (an indel there
+#                is a unit expansion / contraction), others where read ends fall
+#   read_indels  indel ERRORS in the reads, 1 - 4 bases at 0.2 - 2 % per base, with substitutions: the read leaves its diagonal part-way
+#   edges        N runs in reads and flanks, lower-case and IUPAC bytes in REF / ALT, a few haplotypes with a byte >= 0x80 (the
+#                kernel's `hib` path, no twin lists), reads longer than the window overhanging both ends, read lengths at the
+#                mask-word edges (63/64/65 ... 255/256) and shorter than a k-mer
+ADV_FAMILIES = ("excursion", "repeats", "read_indels", "edges")
+_ACGT = np.frombuffer(b"ACGT", np.uint8)
+_IUPAC = np.frombuffer(b"RYKMSWBDHVNacgtn", np.uint8)
+_EDGE_LENS = np.array([63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256])
+_ADV_OV, _ADV_MAXIND, _ADV_LMAX = 300, 20, 300
+
+
+def _pieces(M, lo, hi):
+    """M[i, lo[i]:hi[i]] of every row, concatenated."""
+    cols = np.arange(M.shape[1])[None, :]
+    return M[(cols >= lo[:, None]) & (cols < hi[:, None])]
+
+
+def _plant_repeats(rng, g, rows, starts, lens, max_unit=12):
+    """Overwrite g[rows, starts:starts + lens] with a tandem repeat of a random unit of 1 - max_unit bases; returns (unit, u)."""
+    n = len(rows)
+    u = rng.integers(1, max_unit + 1, n)
+    u = np.where(rng.random(n) < 0.3, 1, u)                      # homopolymers
+    unit = _ACGT[rng.integers(0, 4, (n, max_unit))]
+    j = np.arange(g.shape[1])[None, :] - starts[:, None]
+    inr = (j >= 0) & (j < lens[:, None])
+    rep = np.take_along_axis(unit, np.mod(np.maximum(j, 0), u[:, None]), axis=1)
+    g[rows] = np.where(inr, rep, g[rows])
+    return unit, u
+
+
+def _adversarial_chunk(rng, fam, reads, pads):
+    """One chunk of loci (fam[i]: index into ADV_FAMILIES): haplotype bytes (REF, ALT of each locus in turn), their lengths, read
+    bytes, read lengths."""
+    nl = len(fam)
+    pmax = pads[1]
+    C = _ADV_OV + pmax                                            # molecule column of the variant
+    GW = C + pmax + 1 + 2 * _ADV_MAXIND + _ADV_OV + 8
+    ex, rp, ri, ed = (fam == k for k in range(4))
+    g = _ACGT[rng.integers(0, 4, (nl, GW), dtype=np.uint8)]
+    pad = rng.integers(pads[0], pmax + 1, nl)
+    pad = np.where(ex | ri, np.maximum(pad, 60), pad)
+    # repeats: one across the variant, two more anywhere in the window or just outside it
+    unit, u = np.zeros((nl, 12), np.uint8), np.ones(nl, np.int64)
+    r = np.nonzero(rp)[0]
+    if len(r):
+        ln = rng.integers(8, 60, len(r))
+        unit[r], u[r] = _plant_repeats(rng, g, r, C - rng.integers(0, ln), ln)
+        for _ in range(2):
+            ln = rng.integers(6, 40, len(r))
+            _plant_repeats(rng, g, r, C + rng.integers(-pmax - 150, pmax + 150, len(r)), ln)
+    # edges: N runs in the flanks (reads copy them)
+    e = np.nonzero(ed & (rng.random(nl) < 0.4))[0]
+    if len(e):
+        s = C + rng.integers(-pmax, pmax, len(e))
+        j = np.arange(GW)[None, :] - s[:, None]
+        g[e] = np.where((j >= 0) & (j < rng.integers(1, 13, len(e))[:, None]), ord("N"), g[e])
+    # the variant: SNV, insertion or deletion of 1 - 20 bases (the alt molecule through an index map)
+    kind = rng.choice(3, nl, p=[0.5, 0.25, 0.25])
+    k = rng.integers(1, _ADV_MAXIND + 1, nl)
+    k = np.where(kind == 0, 0, k)
+    cols = np.arange(GW)[None, :]
+    src = np.where(cols <= C, cols, np.where((kind == 1)[:, None], cols - k[:, None], cols + k[:, None]))
+    alt = np.take_along_axis(g, np.clip(src, 0, GW - 1), axis=1)
+    ins = (kind == 1)[:, None] & (cols > C) & (cols <= C + k[:, None])
+    ins_base = np.where(rp[:, None], np.take_along_axis(unit, np.mod(cols - C - 1, u[:, None]), axis=1),
+                        _ACGT[rng.integers(0, 4, (nl, GW), dtype=np.uint8)])
+    alt = np.where(ins, ins_base, alt)
+    snv = np.nonzero(kind == 0)[0]
+    alt[snv, C] = _ACGT[(np.searchsorted(_ACGT, g[snv, C]) % 4 + rng.integers(1, 4, len(snv))) % 4]
+    mol = np.stack([g, alt], axis=1).reshape(2 * nl, GW)
+    ref_len = 2 * pad + 1
+    alt_len = ref_len + np.where(kind == 1, k, -k)
+    # reads
+    n = nl * reads
+    loc = np.repeat(np.arange(nl), reads)
+    a = rng.integers(0, 2, n)
+    hl = np.where(a == 1, alt_len[loc], ref_len[loc])
+    L = 150 - rng.integers(0, 51, n)
+    red = ed[loc]
+    pick = rng.random(n)
+    L = np.where(red & (pick < 0.6), _EDGE_LENS[rng.integers(0, len(_EDGE_LENS), n)], L)
+    L = np.where(red & (pick >= 0.6) & (pick < 0.7), rng.integers(1, 6, n), L)                     # shorter than a k-mer
+    over = red & (pick >= 0.7)                                                                     # longer than the window
+    L = np.where(over, np.minimum(hl + rng.integers(2, 60, n), _ADV_LMAX), L)
+    s = C - rng.integers(0, np.maximum(L, 1))
+    s = np.where(over, C - pad[loc] - rng.integers(1, np.maximum(L - hl, 2)), s)
+    s = np.clip(s, 0, GW - _ADV_LMAX - 2 * _ADV_MAXIND - 8)
+    # the reads as one flat array: base t of read r at roff[r] + t
+    roff = np.cumsum(L) - L
+    rec = np.repeat(np.arange(n), L)
+    tpos = (np.arange(len(rec)) - roff[rec]).astype(np.int32)
+    src = s[rec].astype(np.int32) + tpos
+    # read indels: the source position of base t shifts by the indels before it; inserted bases are random
+    rir = np.nonzero(ri[loc])[0]
+    insm = None
+    if len(rir):
+        lmax = int(L[rir].max())
+        valid = np.arange(lmax)[None, :] < L[rir, None]
+        rate = rng.uniform(0.002, 0.02, len(rir))
+        ev = (rng.random((len(rir), lmax), dtype=np.float32) < rate[:, None]) & valid
+        elen = rng.integers(1, 5, (len(rir), lmax), dtype=np.int32)
+        eins = rng.random((len(rir), lmax), dtype=np.float32) < 0.5
+        shift = np.cumsum(np.where(ev, np.where(eins, -elen, elen), 0), axis=1, dtype=np.int32)
+        insm = np.zeros((len(rir), lmax), bool)
+        for q in range(4):
+            m = ev & eins & (elen > q)
+            insm[:, q:] |= m[:, :lmax - q]
+        at = (roff[rir, None] + np.arange(lmax)[None, :])[valid]
+        src[at] += shift[valid]
+        insm = at[insm[valid]]
+    np.clip(src, 0, GW - 1, out=src)
+    molrow = (2 * loc + a) * GW
+    rd = mol.reshape(-1)[molrow[rec] + src]
+    if insm is not None:
+        rd[insm] = _ACGT[rng.integers(0, 4, len(insm))]
+    # excursions: 6 - 9 bases of a D = 12 - 21 gap taken from 1 - 6 diagonals away, 0 - 3 more errors in the gap.  A quarter of them
+    # over D = 23 - 30 (join_gap3's floor of 11 above D = 22); half of the reads get a second one anywhere
+    xr = np.nonzero(ex[loc] & (L >= 60))[0]
+    for second in (False, True):
+        if second:
+            xr = xr[rng.random(len(xr)) < 0.5]
+        if not len(xr):
+            break
+        D = np.where(rng.random(len(xr)) < 0.25, rng.integers(23, 31, len(xr)), rng.integers(12, 22, len(xr)))
+        gs = rng.integers(5, L[xr] - D - 4)
+        if not second:
+            # half of them leave a run of 8 - 20 bases between the gap and a read end: joined, that run is worth about a join (the
+            # round-6 task: the longer run alone was the certificate, the join priced one too high cost the excursion's score)
+            near = rng.random(len(xr)) < 0.5
+            endrun = rng.integers(8, 21, len(xr))
+            gs = np.where(near, np.where(rng.random(len(xr)) < 0.5, endrun, L[xr] - D - endrun), gs)
+        ne = rng.integers(6, 10, len(xr))
+        o = rng.integers(0, D - ne + 1)
+        # (4 - 6 diagonals, 70 %: far pieces that condition (*) still admits; 1 - 3: the corridor and the edge of the far-piece condition)
+        dl = np.where(rng.random(len(xr)) < 0.7, rng.integers(4, 7, len(xr)), rng.integers(1, 4, len(xr))) * rng.choice([-1, 1], len(xr))
+        for q in range(9):
+            on = q < ne
+            p = gs[on] + o[on] + q
+            rd[roff[xr[on]] + p] = mol.reshape(-1)[molrow[xr[on]] + s[xr[on]] + p + dl[on]]
+        for q in range(3):
+            on = rng.integers(0, 4, len(xr)) > q
+            rd[roff[xr[on]] + (gs + rng.integers(0, D))[on]] = _ACGT[rng.integers(0, 4, int(on.sum()))]
+    # background substitutions (a random base: the same one now and then)
+    bg = np.select([ex[loc], rp[loc], ri[loc]], [rng.choice([0.0, 0.005, 0.01, 0.03], n), rng.choice([0.0, 0.005, 0.02], n), rng.uniform(0, 0.01, n)], 0.005)
+    ns = rng.binomial(L, bg)
+    rows = np.repeat(np.arange(n), ns)
+    rd[roff[rows] + (rng.random(len(rows)) * L[rows]).astype(np.int64)] = _ACGT[rng.integers(0, 4, len(rows))]
+    # edges: N runs of 1 - 8 bases in reads
+    nr = np.nonzero(red & (rng.random(n) < 0.2) & (L > 0))[0]
+    if len(nr):
+        st = rng.integers(0, L[nr])
+        nl_ = rng.integers(1, 9, len(nr))
+        for q in range(8):
+            on = (q < nl_) & (st + q < L[nr])
+            rd[roff[nr[on]] + st[on] + q] = ord("N")
+    # edges: lower-case / IUPAC bytes in REF and ALT (after the reads were copied), bytes >= 0x80 in a few haplotypes
+    eh = np.nonzero(ed)[0]
+    if len(eh):
+        w = np.abs(cols - C) <= pad[eh, None] + _ADV_MAXIND
+        sub = mol[2 * eh[:, None] + np.arange(2)[None, :]]                       # (ne, 2, GW)
+        hit = (rng.random(sub.shape) < 0.02) & w[:, None, :] & (rng.random(len(eh))[:, None, None] < 0.5)
+        lowc = np.where(np.isin(sub, _ACGT), sub | 0x20, sub)
+        sub = np.where(hit, np.where(rng.random(sub.shape) < 0.5, lowc, _IUPAC[rng.integers(0, len(_IUPAC), sub.shape)]), sub)
+        hb = rng.random(len(eh)) < 0.05
+        pos = C + rng.integers(-20, 21, len(eh))
+        sub[hb, rng.integers(0, 2, len(eh))[hb], pos[hb]] = rng.integers(0x80, 0x100, int(hb.sum()))
+        mol[2 * eh[:, None] + np.arange(2)[None, :]] = sub
+    hap_lo = np.repeat(C - pad, 2)
+    hap_len = np.stack([ref_len, alt_len], axis=1).reshape(-1)
+    return _pieces(mol, hap_lo, hap_lo + hap_len), hap_len, rd, L
+
+
+def adversarial_batch(n_loci, reads, seed, families=ADV_FAMILIES, n_barcodes=500, chunk_loci=2048, pads=(20, 110)):
+    """One batch, each locus of one of `families` (names of ADV_FAMILIES), chosen at random per locus; paddings drawn from `pads`
+    (the default keeps every haplotype within 255 bases; above, the device scores the batch on round 3's path: band_refine_kernel)."""
+    rng = np.random.default_rng(seed)
+    fam_ids = np.array([ADV_FAMILIES.index(f) for f in families])
+    loci = np.zeros(n_loci, LOCUS_DTYPE)
+    recs = np.zeros(n_loci * reads, RECORD_DTYPE)
+    hap_parts, read_parts = [], []
+    hoff = roff = 0
+    for c0 in range(0, n_loci, chunk_loci):
+        nl = min(chunk_loci, n_loci - c0)
+        hb, hl, rd, L = _adversarial_chunk(rng, fam_ids[rng.integers(0, len(fam_ids), nl)], reads, pads)
+        lc = loci[c0:c0 + nl]
+        lc["row"] = np.arange(c0, c0 + nl)
+        lc["rec_begin"] = (c0 + np.arange(nl)) * reads
+        lc["rec_count"] = reads
+        off = hoff + np.cumsum(hl) - hl
+        lc["ref_off"], lc["alt_off"] = off[0::2], off[1::2]
+        lc["ref_len"], lc["alt_len"] = hl[0::2], hl[1::2]
+        hoff += len(hb)
+        hap_parts.append(hb)
+        rc = recs[c0 * reads:(c0 + nl) * reads]
+        rc["read_off"] = roff + np.cumsum(L) - L
+        rc["read_len"] = L
+        rc["cell_index"] = np.sort(rng.integers(0, n_barcodes, (nl, reads)), axis=1).reshape(-1)
+        roff += len(rd)
+        read_parts.append(rd)
+    read_parts.append(np.zeros(16, np.uint8))                    # (a kernel may load a word past the last read)
+    return PackedBatch(loci, recs, np.concatenate(hap_parts), np.concatenate(read_parts))
+
+
+def adversarial_batches(n_loci=60, reads=32, seed=31337, families=ADV_FAMILIES, mixed=False, n_barcodes=500, pads=(20, 110)):
+    """(label, batch, n_barcodes): one batch per family, or (mixed=True) one batch of all of them mixed."""
+    if mixed:
+        yield ("adversarial, %s mixed" % "/".join(families), adversarial_batch(n_loci, reads, seed, families, n_barcodes, pads=pads), n_barcodes)
+        return
+    for i, f in enumerate(families):
+        yield ("adversarial, %s" % f, adversarial_batch(n_loci, reads, seed + i, (f,), n_barcodes, pads=pads), n_barcodes)

@@ -45,3 +45,12 @@ def test_real_read_shapes():
     for label, batch, nb in SB.real_shape_batches(trials=2, loci=40, reads=24):
         r = cs.certify(batch, cfg, os.cpu_count() or 8, exact=False)
         assert _violations(r, False) == 0, label
+
+
+def test_adversarial_families():
+    """cert <= banded <= full <= ub on every family of the adversarial generator (tests/stress_batches.py)."""
+    cfg = default_config(aligner="banded", n_barcodes=500)
+    for label, batch, nb in SB.adversarial_batches(n_loci=150, reads=32, seed=707):
+        r = cs.certify(batch, cfg, os.cpu_count() or 8, exact=False)
+        assert _violations(r, False) == 0, label
+        assert (r["cert"] >= 0).mean() > 0.2, label

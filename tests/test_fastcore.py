@@ -657,3 +657,13 @@ def test_twin_list_mode_decides_what_the_probes_decided(core):
         tot += len(s0)
     check(core, cases[0][1], cases[0][2], cases[0][0], 1024 | (1 << 29) | (1 << 28))
     assert tot > 30000, tot
+
+
+@pytest.mark.parametrize("family", SB.ADV_FAMILIES)
+def test_adversarial_families(core, family):
+    """The adversarial generator of tests/stress_batches.py (shapes aimed at the bounds: excursions over far pieces, tandem repeats,
+    indel errors in reads, N / IUPAC / high bytes and mask-word read lengths) through the mirror — plain, with the corridor refinement,
+    and with the corridor certificate — against the oracle's banded and full scores (check())."""
+    for label, batch, nb in SB.adversarial_batches(n_loci=250, reads=32, seed=606, families=(family,)):
+        fr = [check(core, batch, nb, label, flags)[0] for flags in (1024, 1024 | (1 << 30), 1024 | (1 << 29))]
+        assert min(fr) > 0.15, (label, fr)

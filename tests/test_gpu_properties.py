@@ -250,38 +250,78 @@ def test_config5_full_size_properties():
         assert (oracle.sw_banded(read, rh), oracle.sw_banded(read, ah)) == (int(ref[k]), int(alt[k])), k
 
 
-def test_config3_full_size_stage_audit():
-    """BASELINE.json configs[2] at full size, every alignment audited: the banded and the full flavour run on the
-    device, the stage byte of every one of the 48.6 M banded alignments is fetched, and
-      * every alignment whose banded score differs from its full-matrix score was decided by a DP stage — never by a certificate
-        (cert <= banded <= full: a certificate that equals the upper bound of the FULL score cannot coexist with banded < full);
-      * ALL of those alignments, ALL alignments the certificate stages did not decide, and a 1 % random sample of the records
-        are compared with the oracle (reference call site src/main.rs:898-901; the scores of Scores.ref_score / alt_score, :926-927)."""
+def test_config3_full_size_stage_audit(tmp_path):
+    """BASELINE.json configs[2] at full size, every alignment audited (tests/audit_util.py full_size_audit): the
+    banded and the full flavour run on the device, the stage byte of every one of the 48.6 M banded alignments is fetched, and
+      * every alignment whose banded score differs from its full-matrix score was decided by a DP stage or a certificate of the banded
+        score (cert <= banded <= full: a certificate that equals the upper bound of the FULL score cannot coexist with banded < full);
+      * the no-diag run (band_run_kernel on every task) gives the same scores on every alignment;
+      * ALL alignments whose two scores differ, ALL alignments the first certificate stages did not decide, a sample of every stage and a
+        1 % random sample of the records are compared with the oracle (reference call site src/main.rs:898-901; the scores of
+        Scores.ref_score / alt_score, :926-927)."""
     from vartrix_amd import abi
-    from audit_util import assert_stage_invariant, oracle_scores_of, stage_report
-    spec = synth.config3()
-    batch = synth.make_batch(spec)
-    out = {}
-    for aligner in ("banded", "full"):
-        with lib.Context(default_config(aligner=aligner, scoring_mode="consensus", n_barcodes=spec.n_barcodes)) as ctx:
-            ctx.submit(batch)
-            if aligner == "banded":
-                ctx.set_stage_trace(True)
-                ctx.set_poison(-4242)
-            ctx.run()
-            out[aligner] = ctx.fetch_scores() + ((ctx.fetch_stage(),) if aligner == "banded" else ())
-    rb, ab, stage = out["banded"]
-    rf, af = out["full"]
-    assert not (rb == -4242).any() and not (ab == -4242).any()
-    differ = assert_stage_invariant(stage, (rb, ab), (rf, af), "config 3")
-    by_cert = np.isin(stage, (abi.STAGE_DIAG_CERT, abi.STAGE_REFINE_CERT, abi.STAGE_UNKNOWN))
-    print("config 3: %d alignments, banded != full on %d; stages %s" % (len(stage), int(differ.sum()), stage_report(stage)))
-    assert by_cert.mean() > 0.99                                                  # the headline's premise
-    rng = np.random.default_rng(7)
-    recs = np.unique(np.concatenate([np.nonzero(differ)[0] >> 1, np.nonzero(~by_cert)[0] >> 1,
-                                     rng.choice(batch.n_records, batch.n_records // 100, replace=False)]))
-    ids, oref, oalt = oracle_scores_of(batch, recs, "banded", spec.n_barcodes)
-    bad = np.nonzero((rb[ids] != oref) | (ab[ids] != oalt))[0]
-    assert bad.size == 0, "record %d: device (%d, %d) oracle (%d, %d), stages %s" % (
-        ids[bad[0]], rb[ids[bad[0]]], ab[ids[bad[0]]], oref[bad[0]], oalt[bad[0]], stage[2 * ids[bad[0]]:2 * ids[bad[0]] + 2])
-    print("config 3: %d records (%d alignments) compared with the oracle: all equal" % (len(ids), 2 * len(ids)))
+    from audit_util import full_size_audit
+    by_cert_stages = (abi.STAGE_DIAG_CERT, abi.STAGE_REFINE_CERT, abi.STAGE_UNKNOWN)
+    res = full_size_audit("config3", tmp_path, oracle_records=lambda stage, differ: np.concatenate(
+        [np.nonzero(differ)[0] >> 1, np.nonzero(~np.isin(stage, by_cert_stages))[0] >> 1]))
+    assert np.isin(res["stage"], by_cert_stages).mean() > 0.99                   # the headline's premise
+
+
+def _share(res, *stages):
+    return float(np.isin(res["stage"], stages).mean())
+
+
+def _premise_e8(res):           # round 6: 39 % and 5.7 %
+    from vartrix_amd import abi
+    assert _share(res, abi.STAGE_CORRIDOR_CERT) > 0.20 and _share(res, abi.STAGE_UNKNOWN) > 0.02, res["stages"]
+
+
+def _premise_e3(res):           # round 6: 5.8 %
+    from vartrix_amd import abi
+    assert _share(res, abi.STAGE_CORRIDOR_CERT) > 0.02, res["stages"]
+
+
+def _premise_real(res):
+    from vartrix_amd import abi
+    assert _share(res, abi.STAGE_FULL_CHECK) > 0 and res["timing"].diag2_tasks > 0, (res["stages"], res["timing"].diag2_tasks)
+
+
+def _premise_config5(res):
+    b = res["batch"]
+    assert len(np.unique(b.loci["ref_len"].astype(np.int64) - b.loci["alt_len"])) > 30
+
+
+def _premise_reads250(res):
+    assert res["batch"].records["read_len"].min() > 192                          # the fourth mask word of every read
+
+
+def _premise_padding150(res):
+    b = res["batch"]
+    assert min(b.loci["ref_len"].min(), b.loci["alt_len"].min()) > 255
+
+
+def _premise_adversarial(res):
+    import stress_batches as SB
+    from audit_util import BANDED_BOUND_CERTS
+    b = res["batch"]
+    L = b.records["read_len"]
+    assert np.isin(SB._EDGE_LENS, L).all() and (L < 6).any() and (L > b.loci["ref_len"].max()).any()
+    assert (b.hap_arena >= 0x80).any() and (b.read_arena == ord("N")).any()
+    assert res["differ"] > 0 and _share(res, *BANDED_BOUND_CERTS) > 0.001, res["stages"]
+
+
+def _premise_adversarial_long(res):
+    from vartrix_amd import abi
+    b = res["batch"]
+    assert min(b.loci["ref_len"].min(), b.loci["alt_len"].min()) > 255                          # round 3's path for the whole batch
+    assert _share(res, abi.STAGE_REFINE_CERT) > 0.001, res["stages"]                           # band_refine_kernel decided some
+
+
+@pytest.mark.parametrize("name", ["e8", "e3", "real", "config5", "reads250", "padding150", "adversarial", "adversarial_long"])
+def test_full_size_stage_audit(tmp_path, name):
+    """The audit of test_config3_full_size_stage_audit on the noisy, real-sequence, shape and adversarial workloads of
+    tests/audit_util.py (AUDIT_WORKLOADS; bench.py's sensitivity cases, seed 20260926) — where the certificates of the BANDED score
+    decide most of what they decide, and where round 6's unsound join bound lived — each with the premise it exists for."""
+    from audit_util import full_size_audit
+    res = full_size_audit(name, tmp_path)
+    globals()["_premise_" + name](res)

@@ -37,7 +37,11 @@ namespace vtxf {
 
 // rows of the read whose main-diagonal cell lies inside the band of a one-diagonal task (band_pack(fr))
 VTXF_FN void band_rows(const Front& fr, int m, int& lo, int& hi) {
+#if VTXF_MUTANT == 4
+    lo = imax(0, fr.ca - W - fr.d);               // (mutant: one row narrower.  One row WIDER is sound: more in-band runs only raise the bound)
+#else
     lo = imax(0, fr.ca - W - 1 - fr.d);
+#endif
     hi = imin(m - 1, fr.cb + W - 1 - fr.d);
 }
 

@@ -86,6 +86,11 @@ constexpr int LAZY = VTX_BAND_LAZY_EXT(6);
 #ifndef VTXF_NW
 #define VTXF_NW 4
 #endif
+// Mutation testing (tests/test_mutants.py, tests/fastcore/Makefile): VTXF_MUTANT = n > 0 makes ONE bound of the certificate stages
+// unsound on purpose, so that the tests can show they catch it.  Only the host mirror's mutant builds define it; libvtx.so never does.
+#ifndef VTXF_MUTANT
+#define VTXF_MUTANT 0
+#endif
 constexpr int NW = VTXF_NW;     // 64-bit words of a diagonal's match mask (3: rounds 3 - 5; the A/B build of tools/gpu_campaign.sh)
 static_assert(NW == 3 || NW == 4, "rows, columns and piece ends are bytes: 256 bases at most");
 constexpr int MAX_READ = 64 * NW;   // mask capacity
@@ -269,9 +274,17 @@ VTXF_FN uint32_t eq8(uint64_t a, uint64_t b) {
 //                    below the true count only loosens the bound), a stretch with gaps at least J_gap(D) = {7, 9, 11, 10, 9, 8}
 //                    [D mod 6] (J_gap(1) = 12 > 6 e - D = 5)
 VTXF_FN int div6(int D) { return (D * 10923) >> 16; }                // D / 6 for 0 <= D < 30000 ((D * 43) >> 8, first version, is off from D = 131: found by tests/test_fastcore.py::test_join_closed_forms_of_the_kernel_header)
+#if VTXF_MUTANT == 3
+VTXF_FN int join_free(int D) { return 6 * div6(D + 11) - D; }           // (mutant: one base too many before rounding up)
+#else
 VTXF_FN int join_free(int D) { return 6 * div6(D + 10) - D; }
+#endif
 VTXF_FN int join_same(int D, int e) {
+#if VTXF_MUTANT == 7
+    const int jg = (int)((0x89ab98u >> (4 * (D - 6 * div6(D)))) & 15u);   // (mutant: J_gap(6 i) = 8)
+#else
     const int jg = (int)((0x89ab97u >> (4 * (D - 6 * div6(D)))) & 15u);
+#endif
     return imin(6 * e - D, jg);
 }
 
@@ -284,7 +297,11 @@ VTXF_FN int join_same(int D, int e) {
 //      proof as for J_gap: oracle/vtx_certify.c, tests/test_certify.py).  The join costs the smaller of the two. ----
 constexpr int CORR = 2;
 VTXF_FN int join_gap3(int D) {                    // J_gap for G >= 3, D >= 3 (a lower bound of it above D = 22: 11 or 12)
+#if VTXF_MUTANT == 2
+    if (D > 22) return 12;                        // (mutant: the floor one higher)
+#else
     if (D > 22) return 11;
+#endif
     const uint64_t lo = 0x0122001232012345ull;    // D = 3 .. 18: value - 11, a nibble each
     const uint32_t hi = 0x1200u;                  // D = 19 .. 22
     return 11 + (int)(D <= 18 ? (lo >> (4 * (D - 3))) & 15u : (hi >> (4 * (D - 19))) & 15u);
@@ -297,6 +314,9 @@ VTXF_FN int join_gap3(int D) {                    // J_gap for G >= 3, D >= 3 (a
 // far pieces costs >= 11.  Round 6: found by the first full audit of the 8 % workload — the plain join_gap3 priced a join at 13 that a
 // 7-base run four diagonals out made for 12 (ub 36 < full 37; the banded score happened to be 36 too).
 VTXF_FN int join_gap3_far(int D, int far_e) {
+#if VTXF_MUTANT == 1
+    return join_gap3(D);                          // (mutant: round 6's bound, blind to the far pieces)
+#endif
     int j = join_gap3(D);
     if (far_e > 0) {
         VTXF_UNROLL
@@ -778,7 +798,11 @@ template <class PL> VTXF_FN uint32_t harmless_item(const PL& pl, int r, int d, i
         if (t0 <= lm1) minH = imin(minH, dpf + 3 * t0 + 2 * pu);
     }
     const int A = bv > -1000000 ? imin(imax(bv - q + 1, 0), 255) : 0;
+#if VTXF_MUTANT == 5
+    const int T = imin(imax(imin(best_dp, minH - q - 2 * K), 0), 255);        // (mutant: one closer still counts as harmless)
+#else
     const int T = imin(imax(imin(best_dp, minH - q - 2 * K - 1), 0), 255);
+#endif
     return (uint32_t)A | ((uint32_t)T << 8);
 }
 // the same against up to four main pieces held in registers (a piece word of 0 is no piece: it ends before it starts) — the usual task
@@ -798,7 +822,11 @@ VTXF_FN uint32_t harmless_item4(const uint32_t (&pw4)[4], int d, int best_dp, in
         if (t0 <= lm1) minH = imin(minH, dpf + 3 * t0 + 2 * pu);
     }
     const int A = bv > -1000000 ? imin(imax(bv - q + 1, 0), 255) : 0;
+#if VTXF_MUTANT == 5
+    const int T = imin(imax(imin(best_dp, minH - q - 2 * K), 0), 255);        // (mutant: one closer still counts as harmless)
+#else
     const int T = imin(imax(imin(best_dp, minH - q - 2 * K - 1), 0), 255);
+#endif
     return (uint32_t)A | ((uint32_t)T << 8);
 }
 VTXF_FN bool harmless_step(uint32_t at, int& runmax) {
@@ -919,7 +947,11 @@ template <class LN> VTXF_FN int32_t back_rest(const Front& fr, int ns, const LN&
                 }
             }
             if (near_k < 0) break;                                        // nothing is far
+#if VTXF_MUTANT == 6
+            bool ok = near_d >= 3;                                         // (mutant: a far piece three diagonals out)
+#else
             bool ok = near_d >= 4;                                         // bound(t) <= 0 for t <= 3
+#endif
             if (ok) {
                 const uint64_t lim = 0x002018100c080602ull;                // bound(4, 6, 8, 12, 16, 24, 32), one byte each
                 // every byte of cum <= its byte of lim: byte-wise (0x80 + lim) - cum keeps bit 7 (no borrow crosses a byte: cum <= SM < 128)
