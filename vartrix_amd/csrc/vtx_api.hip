@@ -115,7 +115,7 @@ struct vtx_ctx {
     int read_format = VTX_READS_BYTES;     // vtx_set_read_format
     DevBuf d_read_packed;                  // VTX_READS_NIBBLES: the arena as uploaded, unpacked into d_read
     uint64_t gt_used = 0;      // bytes of d_gtables the last banded run's table kernel wrote (vtx_debug_tables)
-    DevBuf d_band_ws, d_band_ws2, d_band, d_poly, d_gtables, d_hard, d_over, d_over2, d_pend, d_pend_buf, d_cnt, d_band2, d_hard2, d_fail, d_fail_tmp, d_refine;   // banded flavour
+    DevBuf d_band_ws, d_band_ws2, d_band, d_poly, d_gtables, d_hard, d_over, d_over2, d_pend, d_pend_buf, d_cnt, d_band2, d_hard2, d_fail, d_fail_tmp, d_refine, d_tail;   // banded flavour
     DevBuf d_tight2, d_tight2_pack;                                          // band_diag2_kernel: tasks whose band is one diagonal stretch after all
     DevBuf d_recheck2, d_recheck2_pack;                                      // ... of which the full-matrix check did not settle (full != certificate); first they hold band_stream_kernel's task list and diagonals
     DevBuf d_sweep_log;                                                      // band_sweep_kernel: the section logs of the resident workgroups (48 MB: 1 536 x 8 x 1 024 words)
@@ -665,7 +665,7 @@ void vtx_destroy(vtx_ctx* c) {
                       &c->d_cnt, &c->d_redo, &c->d_redo_cnt, &c->d_bc_slots, &c->d_bc_hash, &c->d_bc_off, &c->d_bc_bytes,
                       &c->d_raw, &c->d_tags, &c->d_raw_locus, &c->d_key_lc, &c->d_key_lc2, &c->d_key_umi, &c->d_key_umi2,
                       &c->d_idx, &c->d_idx2, &c->d_shape, &c->d_shape2, &c->d_seq, &c->d_locus_cnt, &c->d_locus_scan,
-                      &c->d_prep_cnt, &c->d_sort_tmp, &c->d_fail, &c->d_fail_tmp, &c->d_refine, &c->d_tight, &c->d_tight_pack, &c->d_dband, &c->d_dband_pack, &c->d_dense, &c->d_stage, &c->d_sweep_log, &c->d_tight2, &c->d_tight2_pack, &c->d_recheck2, &c->d_recheck2_pack};
+                      &c->d_prep_cnt, &c->d_sort_tmp, &c->d_fail, &c->d_fail_tmp, &c->d_refine, &c->d_tail, &c->d_tight, &c->d_tight_pack, &c->d_dband, &c->d_dband_pack, &c->d_dense, &c->d_stage, &c->d_sweep_log, &c->d_tight2, &c->d_tight2_pack, &c->d_recheck2, &c->d_recheck2_pack};
     for (DevBuf* b : bufs) b->release();
     c->d_slow_ws.release(); c->d_slow_retry.release(); c->d_read_packed.release();
     DevBuf* ib[] = {&c->d_bam_comp, &c->d_bam_data, &c->d_bam_blocks, &c->d_bam_seeds, &c->d_bam_seed_cnt, &c->d_bam_seed_scan, &c->d_bam_iv, &c->d_bam_cnt,
@@ -708,6 +708,9 @@ static void note_long_loci(vtx_ctx* c, const vtx_locus* loci, uint32_t nl) {
 // (round 6: with a tight list EVERY task that leaves band_diag_kernel with a certificate leaves a record, for band_corridor_kernel: 24 - 30 %
 // of the tasks at 8 % errors (39 % measured: 19.1 M of 48.6 M) — half; a task that does not fit takes the masked DP over its band, as all of them did before)
 static uint32_t band_refine_cap(uint32_t chunk) { return std::max(65536u, chunk / 2); }
+// records band_diag_kernel may leave for band_tail_kernel per chunk (tasks whose generic set grows: 8 % of a clean workload's tasks; a
+// task that does not fit finishes in its wavefront).  128 bytes each; no room for them (the buffer is optional): every task stays.
+static uint32_t band_tail_cap(uint32_t chunk) { return std::max(65536u, chunk / 4); }
 struct BandPlan {
     uint64_t n_tasks = 0;
     uint32_t chunk = 0, band_stride = 0, hard_cap = 0, pend_cap = 0, slots = 0, poly_stride = 0, tasks_per_locus = 0;
@@ -763,6 +766,10 @@ static int band_reserve(vtx_ctx* c, BandPlan& p, bool quiet) {
     RES(d_cnt, 64 * sizeof(uint32_t));
     if (p.gt_bytes) RES(d_fail, 2 * (size_t)p.chunk * sizeof(uint32_t));  // tasks band_diag_kernel leaves to band_run_kernel (as listed, then sorted)
     if (p.gt_bytes) RES(d_refine, (size_t)band_refine_cap(p.chunk) * vtxk_band_refine_words() * sizeof(uint32_t));   // records for band_refine_kernel
+    if (p.gt_bytes && c->d_tail.reserve((size_t)band_tail_cap(p.chunk) * vtxk_band_tail_words() * sizeof(uint32_t)) != hipSuccess) {
+        (void)hipGetLastError();                                                                          // records for band_tail_kernel
+        c->d_tail.release();
+    }
     if (p.gt_bytes) RES(d_tight, (size_t)p.chunk * sizeof(uint32_t));       // tasks with a certificate but no verdict ...
     if (p.gt_bytes) RES(d_tight_pack, (size_t)p.chunk * sizeof(uint32_t));  // ... and their bands (one diagonal stretch each: one word)
     if (p.gt_bytes) RES(d_dense, 2 * (size_t)p.chunk * sizeof(uint32_t));   // tasks for band_sweep_kernel (repeats: as listed, then sorted)
@@ -1728,12 +1735,15 @@ int vtx_run(vtx_ctx* c) {
                     static const bool no_refine = VTX_DEV_ENV("VTX_BAND_NO_REFINE") != nullptr;        // experiment / test hook
                     const uint32_t refine_cap = band_refine_cap(chunk);
                     uint32_t* refine_list = no_refine ? nullptr : c->d_refine.as<uint32_t>();
+                    const uint32_t tail_cap = (uint32_t)std::min<size_t>(band_tail_cap(chunk), c->d_tail.cap / (vtxk_band_tail_words() * sizeof(uint32_t)));
+                    const uint32_t tail_cap_hook = VTX_DEV_ENV("VTX_DIAG_TAIL_CAP") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_TAIL_CAP")) : 0xffffffffu;   // test hook: a small buffer (read per run)
+                    const uint32_t tail_n = std::min(tail_cap, tail_cap_hook);
                     const hipError_t e = vtxk_launch_band_diag(nt, (uint32_t)base, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
                                                                c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(),
                                                                mh, mh_min, c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(),
                                                                c->d_fail.as<uint32_t>(), refine_list, refine_cap, d_cnt, tasks_per_locus, gt_l0, gt_n,
                                                                c->d_gtables.as<uint8_t>(), gt_bytes, diag_stats, tight_list, tight_pack, stage,
-                                                               dense_list, dense_mask, c->max_read_len, s);
+                                                               dense_list, dense_mask, c->max_read_len, c->d_tail.as<uint32_t>(), tail_n, s);
                     if (e == hipSuccess && sweep_path) {
                         diag = true; swept = true; sweep_used = true;
                         HIP_TRY(c, hipEventRecord(c->ev[6], s));

@@ -2109,6 +2109,92 @@ extern "C" hipError_t vtxk_diag_phases(unsigned long long* out) {
 }
 #define REFINE_WORDS 12u       // record of band_refine_kernel: task, d, r | cert << 4 | far matches << 16, zc, RM piece words
 extern "C" uint32_t vtxk_band_refine_words(void) { return REFINE_WORDS; }
+// record of band_tail_kernel (vtx_fast_core.h: tail_pack), word-major: word i of record p at i * cap + p — the ballot-compacted positions
+// of a wavefront are consecutive, so the stores here and the loads there coalesce
+extern "C" uint32_t vtxk_band_tail_words(void) { return (uint32_t)vtxf::TAIL_WORDS; }
+#define TAIL_DECIDED 0x80000000u   // (band_tail_kernel, word 3 after its first pass: decided; else why | TAIL_TIGHT)
+#define TAIL_TIGHT 0x10u
+
+// Where a task goes once the last phase of the certificate is over — band_diag_kernel's lanes and band_tail_kernel's (the tasks the
+// former left in the middle of that phase) alike; every lane of the wavefront calls it.  fail: no verdict (why, aux: back_rest's);
+// tight: the task holds its certificate (harmless matches only).  The lists, each reserved with one atomic per wavefront:
+//   refine_rec (counters[14])  with a tight list a record for band_corridor_kernel (every task that keeps its certificate), else round 3's
+//                              record for band_refine_kernel (main pieces only, bounds apart); the buffer full: on to the lists below
+//   tight_list (counters[15])  the certificate's band (pack), the certificate as a provisional score
+//   dense_list (counters[13])  the reasons in dense_mask (W_MATCHES: only when spread) — band_sweep_kernel
+//   fail_list  (counters[12])  the rest — band_run_kernel
+// Round 6, the sweep path (a tight list): EVERY task that leaves the last phase with its certificate — harmless matches only, bounds
+// apart or the generic set full — leaves a record for band_corridor_kernel (the task, its one-diagonal band, the rows of its
+// matches far out: vtx_fast_core.h, "the corridor certificate") instead of taking the masked DP; what that kernel does not decide
+// goes on to the tight list.  (stats bit 16 — libvtx_dev.so, VTX_BAND_NO_CORRIDOR=1 — and batches with haplotypes above 255 bases:
+// round 3's records for band_refine_kernel, main pieces only.)
+// far_of(): vtxf::far_rows of the task (asked only for a corridor record); ln: its main piece words (round 3's records).
+template <class LaneT, class FarOf>
+__device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t why, bool tight, uint32_t aux, bool spread, FarOf far_of, const LaneT& ln,
+                                           int r, int cert, uint32_t zc, uint32_t pack, int32_t* __restrict__ ref_score,
+                                           int32_t* __restrict__ alt_score, uint32_t* __restrict__ fail_list, uint32_t* __restrict__ refine_rec,
+                                           uint32_t refine_cap, uint32_t* __restrict__ counters, uint32_t stats, uint32_t* __restrict__ tight_list,
+                                           uint32_t* __restrict__ tight_pack, uint32_t* __restrict__ dense_list, uint32_t dense_mask) {
+    const int tid = threadIdx.x & 63;
+    const bool corr_mode = tight_list != nullptr && refine_rec != nullptr && !(stats & 0x10000u);
+    bool again = corr_mode ? (fail && tight) : (fail && why == vtxf::W_NOT_TIGHT && refine_rec != nullptr && aux != 0xffffffffu);
+    const uint64_t am = __ballot(again);
+    if (am) {
+        uint32_t base = 0;
+        const int leader = __ffsll((long long)am) - 1;
+        if (tid == leader) base = atomicAdd(&counters[14], (uint32_t)__popcll(am));
+        base = (uint32_t)__shfl((int)base, leader);
+        const uint32_t pos = base + (uint32_t)__popcll(am & ((1ull << tid) - 1ull));
+        if (again && pos >= refine_cap) again = false;              // (the record buffer is full: band_run_kernel takes it)
+        if (again && corr_mode) {
+            static_assert(REFINE_WORDS >= 4 + 2 * vtxf::NW, "the far rows fit the record");
+            const vtxf::M192 far = far_of();
+            uint32_t* rec = refine_rec + (size_t)pos * REFINE_WORDS;
+            rec[0] = task; rec[1] = pack;
+            rec[2] = (uint32_t)cert; rec[3] = 0;
+#pragma unroll
+            for (int i = 0; i < vtxf::NW; ++i) { rec[4 + 2 * i] = (uint32_t)far.w[i]; rec[5 + 2 * i] = (uint32_t)(far.w[i] >> 32); }
+        } else if (again) {
+            uint32_t* rec = refine_rec + (size_t)pos * REFINE_WORDS;
+            rec[0] = task; rec[1] = pack;                              // (the diagonal is its upper half)
+            rec[2] = (uint32_t)r | ((uint32_t)cert << 4) | (aux << 16);
+            rec[3] = zc;
+            for (int i = 0; i < vtxf::RM; ++i) rec[4 + i] = i < r ? ln.at(i) : 0u;
+        }
+    }
+    tight = tight && fail && !again;
+    const uint64_t tm = __ballot(tight);
+    if (tm) {
+        uint32_t base = 0;
+        const int leader = __ffsll((long long)tm) - 1;
+        if (tid == leader) base = atomicAdd(&counters[15], (uint32_t)__popcll(tm));
+        base = (uint32_t)__shfl((int)base, leader);
+        if (tight) {
+            const uint32_t pos = base + (uint32_t)__popcll(tm & ((1ull << tid) - 1ull));
+            tight_list[pos] = task;
+            tight_pack[pos] = pack;
+            (((task & 1u) ? alt_score : ref_score) + (task >> 1))[0] = cert;     // provisional: a lower bound of the banded score
+        }
+    }
+    const bool dense = fail && !again && !tight && dense_list != nullptr && ((dense_mask >> why) & 1u) && (why != vtxf::W_MATCHES || spread);
+    const uint64_t dm = __ballot(dense);
+    if (dm) {
+        uint32_t base = 0;
+        const int leader = __ffsll((long long)dm) - 1;
+        if (tid == leader) base = atomicAdd(&counters[13], (uint32_t)__popcll(dm));
+        base = (uint32_t)__shfl((int)base, leader);
+        if (dense) dense_list[base + (uint32_t)__popcll(dm & ((1ull << tid) - 1ull))] = task;
+    }
+    const uint64_t fm = __ballot(fail && !again && !tight && !dense);
+    if (fm) {
+        uint32_t base = 0;
+        const int leader = __ffsll((long long)fm) - 1;
+        if (tid == leader) base = atomicAdd(&counters[12], (uint32_t)__popcll(fm));
+        base = (uint32_t)__shfl((int)base, leader);
+        if (fail && !again && !tight && !dense) fail_list[base + (uint32_t)__popcll(fm & ((1ull << tid) - 1ull))] = task;
+    }
+    if (fail && !again && (stats & 0xffu)) atomicAdd(&counters[32 + why], 1u);
+}
 // ST: type of an off-diagonal match entry — uint16_t (x << 8 | y: 40 entries per task in the same LDS) when every haplotype of
 // the batch has <= 255 bases, else uint32_t (20 entries).
 // A: mask words in use — 3 when no read of the batch exceeds 192 bases (the instruction count of rounds 3 - 5), else vtxf::NW = 4.
@@ -2120,7 +2206,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     const uint8_t* __restrict__ gtables, uint32_t gt_l0, int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score,
     uint32_t* __restrict__ fail_list, uint32_t* __restrict__ refine_rec, uint32_t refine_cap, uint32_t* __restrict__ counters,
     uint32_t stats, uint32_t* __restrict__ tight_list, uint32_t* __restrict__ tight_pack, uint8_t* __restrict__ stage,
-    uint32_t* __restrict__ dense_list, uint32_t dense_mask, uint32_t min_hap) {
+    uint32_t* __restrict__ dense_list, uint32_t dense_mask, uint32_t min_hap, uint32_t* __restrict__ tail_rec, uint32_t tail_cap) {
     // min_hap: tasks of loci whose longer haplotype has <= min_hap bases are left alone (vtx_run's second pass over a batch that mixes
     // haplotypes of <= 255 bases with a few longer ones: the first pass, with two-byte entries and the sweep behind it, scored them).
     // dense_list != nullptr (round 4): a task left for a reason in dense_mask (bit = vtxf::Why; by default W_MATCHES: more than 40
@@ -2577,78 +2663,112 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     if (VTX_ABLATE((stats >> 8) & 0xffu) == 7) { if (live && ns == 0x7fffffff) counters[40] = 1; return; }            // (profiling aid) ... + the sort
     if (live && !vtxf::back_harmless(fr, ns, ln)) { live = false; fail = true; why = vtxf::W_NOT_HARMLESS; }
     PH(9);                                                              // harmless tests
+    // The closure's first scan decides whether the generic set stays empty (92 % of the live tasks: one scan and the main-only run bound
+    // on piece words in registers).  A task whose set must grow — closure rescans, a fixpoint over (r + ng)^2 piece pairs — costs what
+    // its whole wavefront waits for: it leaves a record for band_tail_kernel instead (tail_rec, counters[44]; vtxf::tail_pack) and writes
+    // nothing else here.  The buffer full: it goes on here, as without the record.  (Headline: closure + bound 19.4 -> 9.9 k cycles per
+    // wavefront, the kernel 10.64 -> 9.44 ms, band_tail_kernel 0.68 ms; DESIGN 4.3.2, "where the kernel's time goes".)
+    int first = -2;
+    if (live && tail_rec) first = vtxf::closure_first(fr, ns, ln);
+    bool defer = first >= 0;
+    const uint64_t xm = __ballot(defer);
+    if (xm) {
+        uint32_t base = 0;
+        const int leader = __ffsll((long long)xm) - 1;
+        if (tid == leader) base = atomicAdd(&counters[44], (uint32_t)__popcll(xm));
+        base = (uint32_t)__shfl((int)base, leader);
+        const uint32_t pos = base + (uint32_t)__popcll(xm & ((1ull << tid) - 1ull));
+        if (defer && pos >= tail_cap) defer = false;
+        if (defer) {
+            vtxf::tail_pack(tail_rec + pos, tail_cap, task, fr, ns, ln);
+            live = false;
+        }
+    }
     if (live) {
         const vtxf::Lane gl{(uint32_t*)q_ent + tid, 64};                 // (the queue is dead by now)
-        const int32_t sc = vtxf::back_rest(fr, ns, ln, gl, &why, (int)VTX_ABLATE((stats >> 8) & 0xffu), nullptr, &aux);
+        const int32_t sc = vtxf::back_rest(fr, ns, ln, gl, &why, (int)VTX_ABLATE((stats >> 8) & 0xffu), nullptr, &aux, first);
         if (sc >= 0) { *my_score() = sc; if (stage) stage[task] = 1; }
         else { fail = true; tight = tight_list != nullptr; }
     }
-    // Round 6, the sweep path (a tight list): EVERY task that leaves the last phase with its certificate — harmless matches only, bounds
-    // apart or the generic set full — leaves a record for band_corridor_kernel (the task, its one-diagonal band, the rows of its
-    // matches far out: vtx_fast_core.h, "the corridor certificate") instead of taking the masked DP; what that kernel does not decide
-    // goes on to the tight list.  (stats bit 16 — libvtx_dev.so, VTX_BAND_NO_CORRIDOR=1 — and batches with haplotypes above 255 bases:
-    // round 3's records for band_refine_kernel, main pieces only.)
     PH(10);                                                             // closure, run bound
-    const bool corr_mode = tight_list != nullptr && refine_rec != nullptr && !(stats & 0x10000u);
-    bool again = corr_mode ? (fail && tight) : (fail && why == vtxf::W_NOT_TIGHT && refine_rec != nullptr && aux != 0xffffffffu);
-    const uint64_t am = __ballot(again);
-    if (am) {
-        uint32_t base = 0;
-        const int leader = __ffsll((long long)am) - 1;
-        if (tid == leader) base = atomicAdd(&counters[14], (uint32_t)__popcll(am));
-        base = (uint32_t)__shfl((int)base, leader);
-        const uint32_t pos = base + (uint32_t)__popcll(am & ((1ull << tid) - 1ull));
-        if (again && pos >= refine_cap) again = false;              // (the record buffer is full: band_run_kernel takes it)
-        if (again && corr_mode) {
-            static_assert(REFINE_WORDS >= 4 + 2 * vtxf::NW, "the far rows fit the record");
-            const vtxf::M192 far = vtxf::far_rows(fr.d, ns, ln);
-            uint32_t* rec = refine_rec + (size_t)pos * REFINE_WORDS;
-            rec[0] = task; rec[1] = vtxf::band_pack(fr);
-            rec[2] = (uint32_t)fr.cert; rec[3] = 0;
-#pragma unroll
-            for (int i = 0; i < vtxf::NW; ++i) { rec[4 + 2 * i] = (uint32_t)far.w[i]; rec[5 + 2 * i] = (uint32_t)(far.w[i] >> 32); }
-        } else if (again) {
-            uint32_t* rec = refine_rec + (size_t)pos * REFINE_WORDS;
-            rec[0] = task; rec[1] = vtxf::band_pack(fr);               // (the diagonal is its upper half)
-            rec[2] = (uint32_t)fr.r | ((uint32_t)fr.cert << 4) | (aux << 16);
-            rec[3] = fr.zc;
-            for (int i = 0; i < vtxf::RM; ++i) rec[4 + i] = i < fr.r ? ln.at(i) : 0u;
-        }
-    }
-    tight = tight && fail && !again;
-    const uint64_t tm = __ballot(tight);
-    if (tm) {
-        uint32_t base = 0;
-        const int leader = __ffsll((long long)tm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[15], (uint32_t)__popcll(tm));
-        base = (uint32_t)__shfl((int)base, leader);
-        if (tight) {
-            const uint32_t pos = base + (uint32_t)__popcll(tm & ((1ull << tid) - 1ull));
-            tight_list[pos] = task;
-            tight_pack[pos] = vtxf::band_pack(fr);
-            *my_score() = fr.cert;                                    // provisional: a lower bound of the banded score
-        }
-    }
-    const bool dense = fail && !again && !tight && dense_list != nullptr && ((dense_mask >> why) & 1u) && (why != vtxf::W_MATCHES || spread);
-    const uint64_t dm = __ballot(dense);
-    if (dm) {
-        uint32_t base = 0;
-        const int leader = __ffsll((long long)dm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[13], (uint32_t)__popcll(dm));
-        base = (uint32_t)__shfl((int)base, leader);
-        if (dense) dense_list[base + (uint32_t)__popcll(dm & ((1ull << tid) - 1ull))] = task;
-    }
-    const uint64_t fm = __ballot(fail && !again && !tight && !dense);
-    if (fm) {
-        uint32_t base = 0;
-        const int leader = __ffsll((long long)fm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[12], (uint32_t)__popcll(fm));
-        base = (uint32_t)__shfl((int)base, leader);
-        if (fail && !again && !tight && !dense) fail_list[base + (uint32_t)__popcll(fm & ((1ull << tid) - 1ull))] = task;
-    }
-    if (fail && !again && (stats & 0xffu)) atomicAdd(&counters[32 + why], 1u);
+    diag_route(task, fail, why, tight, aux, spread, [&]() { return vtxf::far_rows(fr.d, ns, ln); }, ln, fr.r, fr.cert, fr.zc, vtxf::band_pack(fr),
+               ref_score, alt_score, fail_list,
+               refine_rec, refine_cap, counters, stats, tight_list, tight_pack, dense_list, dense_mask);
     PH(11);                                                             // lists
     if (VTX_DEVTOOLS_ON && ph_on && tid == 0) atomicAdd(&g_diag_phase[blockIdx.x & 255u][15], 1ull);
+}
+
+// =============================================================================================
+// band_tail_kernel — the rest of the last phase for the tasks band_diag_kernel deferred: those whose closure must take an off-diagonal
+// piece into the generic set (7.4 % of the headline's tasks).  One lane per record, over the device's record count (counters[44]); the
+// record goes back into band_diag_kernel's LDS layout and the same vtxf::back_rest runs on it, then the same routing (diag_route):
+// every task ends with the score, stage and lists it had when decided in its wavefront.  Launched with up to 65 536 one-wavefront
+// workgroups: a wavefront that finishes early makes room for the next (4 608 resident ones looping over the records: 0.87 ms, 0.68 ms
+// so; without back_rest the kernel takes 67 us — its time is the rare path's own work).
+// 60 - 62 VGPRs and no probe queue (band_diag_kernel: 128): LDS — the lane's words and the GM generic piece words, 8.7 KB a wavefront —
+// bounds it at 18 wavefronts per CU, 4.5 per SIMD, against 4 of band_diag_kernel's that hide the fixpoint's LDS round trips.
+// =============================================================================================
+template <class ST, int A>
+__global__ __launch_bounds__(64) void band_tail_kernel(
+    uint32_t* __restrict__ tail_rec, uint32_t tail_cap, const uint32_t* __restrict__ n_dev,
+    int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score, uint32_t* __restrict__ fail_list, uint32_t* __restrict__ refine_rec,
+    uint32_t refine_cap, uint32_t* __restrict__ counters, uint32_t stats, uint32_t* __restrict__ tight_list, uint32_t* __restrict__ tight_pack,
+    uint8_t* __restrict__ stage, uint32_t* __restrict__ dense_list, uint32_t dense_mask) {
+    __shared__ uint32_t lane_mem[vtxf::LANE_WORDS * 64];
+    __shared__ uint32_t gen_mem[vtxf::GM * 64];
+    typedef vtxf::LaneS<ST, vtxf::S_WORDS, (A <= 3)> LaneT;
+    const int tid = threadIdx.x & 63;
+    const LaneT ln{lane_mem + vtxf::S_WORDS * 64 + tid, 64, (ST*)lane_mem + tid, 64};
+    const vtxf::Lane gl{gen_mem + tid, 64};
+    const uint32_t nd = *n_dev, n_recs = nd < tail_cap ? nd : tail_cap;
+    const uint32_t lanes = gridDim.x * 64u;
+    // 1. every lane through its own records, p = its lane number + k * lanes, without waiting for the others: a wavefront takes what its
+    //    slowest LANE's records cost together, not the sum over the records of the slowest one's (the costs are a long tail: generic sets
+    //    of one to six pieces, fixpoint passes of one to six).  What the routing needs goes back into the record: word 3 the outcome,
+    //    words 4 .. 4 + 2 NW the far rows of a task that keeps its certificate (the main piece words are not needed again: round 3's
+    //    records take tasks whose generic set is empty only — aux is 0xffffffff for every task deferred here).
+    for (uint32_t p = blockIdx.x * 64u + (uint32_t)tid; p < n_recs; p += lanes) {
+        uint32_t* rec = tail_rec + p;
+        vtxf::Front fr;
+        int ns = 0;
+        uint32_t pack = 0, why = 0, aux = 0xffffffffu;
+        const uint32_t task = vtxf::tail_unpack(rec, tail_cap, fr, ns, ln, &pack);
+        const int32_t sc = vtxf::back_rest(fr, ns, ln, gl, &why, 0, nullptr, &aux);
+        uint32_t out = TAIL_DECIDED;
+        if (sc >= 0) { (((task & 1u) ? alt_score : ref_score) + (task >> 1))[0] = sc; if (stage) stage[task] = 1; }
+        else {
+            out = why | (tight_list ? TAIL_TIGHT : 0u);
+            if (tight_list) {
+                static_assert(4 + 2 * vtxf::NW <= 4 + vtxf::RM, "the far rows fit where the main pieces were");
+                const vtxf::M192 far = vtxf::far_rows(fr.d, ns, ln);
+#pragma unroll
+                for (int i = 0; i < vtxf::NW; ++i) {
+                    rec[(size_t)(4 + 2 * i) * tail_cap] = (uint32_t)far.w[i];
+                    rec[(size_t)(5 + 2 * i) * tail_cap] = (uint32_t)(far.w[i] >> 32);
+                }
+            }
+        }
+        rec[3 * (size_t)tail_cap] = out;
+    }
+    // 2. the routing, wavefront-uniform (its ballots see every lane): the same lane, the same records
+    for (uint32_t p0 = blockIdx.x * 64u; p0 < n_recs; p0 += lanes) {
+        const uint32_t p = p0 + (uint32_t)tid;
+        uint32_t task = 0, pack = 0, w2 = 0, out = TAIL_DECIDED;
+        vtxf::M192 far = vtxf::m_zero();
+        if (p < n_recs) {
+            const uint32_t* rec = tail_rec + p;
+            task = rec[0]; pack = rec[(size_t)tail_cap]; w2 = rec[2 * (size_t)tail_cap]; out = rec[3 * (size_t)tail_cap];
+        }
+        const bool fail = !(out & TAIL_DECIDED), tight = (out & TAIL_TIGHT) != 0;
+        if (fail && tight) {
+            const uint32_t* rec = tail_rec + p;
+#pragma unroll
+            for (int i = 0; i < vtxf::NW; ++i)
+                far.w[i] = (uint64_t)rec[(size_t)(4 + 2 * i) * tail_cap] | ((uint64_t)rec[(size_t)(5 + 2 * i) * tail_cap] << 32);
+        }
+        diag_route(task, fail, out & 15u, tight, 0xffffffffu, false, [&]() { return far; }, ln, 0, (int)(w2 >> 18), 0u, pack, ref_score,
+                   alt_score, fail_list, refine_rec, refine_cap, counters, stats, tight_list, tight_pack, dense_list, dense_mask);
+    }
 }
 
 // =============================================================================================
@@ -2952,9 +3072,14 @@ extern "C" hipError_t vtxk_launch_band_diag(uint32_t n_tasks, uint32_t task_base
                                             uint32_t* fail_list, uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters,
                                             uint32_t tasks_per_locus, uint32_t gt_l0, uint32_t n_loci, uint8_t* gtables,
                                             size_t gtables_bytes, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage,
-                                            uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, hipStream_t s) {
+                                            uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, uint32_t* tail_rec, uint32_t tail_cap,
+                                            hipStream_t s) {
     // max_read: the longest read of the batch (the fast kernels' records) — up to 192 bases the kernel is built with three mask words
+    // tail_rec != nullptr: room for tail_cap records of band_tail_kernel (TAIL_WORDS words each, word-major), launched here behind
+    // band_diag_kernel on the same stream; counters[44] counts them.  (libvtx_dev.so: VTX_DIAG_NO_TAIL=1 — and the profiling aids of
+    // VTX_DIAG_ABLATE — keep every task in its wavefront, the path of rounds 3 - 6.)
     if (!n_tasks) return hipSuccess;
+    if (VTX_DEV_ENV("VTX_DIAG_NO_TAIL") || VTX_DEV_ENV("VTX_DIAG_ABLATE") || !tail_cap) tail_rec = nullptr;
     const uint32_t n_heads = pick_heads(tasks_per_locus, true);
     const size_t tstride = band_table_stride(max_hap, n_heads);
     if (!gtables || (size_t)n_loci * 2 * tstride > gtables_bytes) return hipErrorInvalidValue;
@@ -2969,10 +3094,18 @@ extern "C" hipError_t vtxk_launch_band_diag(uint32_t n_tasks, uint32_t task_base
     // two-byte match entries (40 per task) whenever a haplotype position fits a byte; VTX_DIAG_WIDE=1 forces the four-byte variant (tests)
     static const bool force_wide = VTX_DEV_ENV("VTX_DIAG_WIDE") != nullptr;
     static const bool force_four = VTX_DEV_ENV("VTX_DIAG_FOUR_WORDS") != nullptr;      // (tests: the four-word build on short reads)
-#define LAUNCH_DIAG(STV, AV)                                                                                                             \
-    hipLaunchKernelGGL((band_diag_kernel<4, STV, AV>), dim3(((n_blocks + 7) / 8) * 8), dim3(256), 0, s, n_tasks, task_base, n_blocks, records, \
-                       rec_locus, loci, read_arena, max_hap, (uint32_t)tstride, n_heads, (const uint8_t*)gtables, gt_l0, ref_score,        \
-                       alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list, tight_pack, stage, dense_list, dense_mask, min_hap)
+#define LAUNCH_DIAG(STV, AV)                                                                                                              \
+    do {                                                                                                                                  \
+        hipLaunchKernelGGL((band_diag_kernel<4, STV, AV>), dim3(((n_blocks + 7) / 8) * 8), dim3(256), 0, s, n_tasks, task_base, n_blocks,   \
+                           records, rec_locus, loci, read_arena, max_hap, (uint32_t)tstride, n_heads, (const uint8_t*)gtables, gt_l0,       \
+                           ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list, tight_pack, stage, dense_list, \
+                           dense_mask, min_hap, tail_rec, tail_cap);                                                                      \
+        if (tail_rec)                                                                                                                     \
+            hipLaunchKernelGGL((band_tail_kernel<STV, AV>), dim3(std::min((tail_cap + 63u) / 64u, 65536u)), dim3(64), 0, s, tail_rec,  \
+                               tail_cap, counters + 44, ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list, \
+                               tight_pack, stage, dense_list, dense_mask);                                                                \
+    } while (0)
+    if (tail_rec) { const hipError_t e = hipMemsetAsync(counters + 44, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
     const bool three = max_read <= 192 && !force_four && vtxf::NW >= 3;
     if (max_hap <= 255 && !force_wide) { if (three) LAUNCH_DIAG(uint16_t, 3); else LAUNCH_DIAG(uint16_t, vtxf::NW); }
     else { if (three) LAUNCH_DIAG(uint32_t, 3); else LAUNCH_DIAG(uint32_t, vtxf::NW); }

@@ -896,7 +896,7 @@ template <class LN> VTXF_FN bool back_harmless(const Front& fr, int ns, const LN
     }
 }
 template <class LN> VTXF_FN int32_t back_rest(const Front& fr, int ns, const LN& ln, const Lane& gl, uint32_t* why, int ablate,
-                                              const Refine* rf, uint32_t* aux);
+                                              const Refine* rf, uint32_t* aux, int first = -2);
 template <class LN> VTXF_FN int32_t back(const Front& fr, int ns, const LN& ln, const Lane& gl, uint32_t* why, int ablate = 0,
                                          const Refine* rf = nullptr, uint32_t* aux = nullptr) {
     if (aux) *aux = 0xffffffffu;
@@ -905,9 +905,54 @@ template <class LN> VTXF_FN int32_t back(const Front& fr, int ns, const LN& ln, 
     if (!back_harmless(fr, ns, ln)) { *why = W_NOT_HARMLESS; return -1; }
     return back_rest(fr, ns, ln, gl, why, ablate, rf, aux);
 }
-// closure, run bound, verdict (the matches sorted and found harmless)
+// One scan of the closure (below): the far match nearest to the hull [hull_lo, hull_hi] of the generic diagonals when the far matches
+// (those not in `used`) violate condition (*) — the piece the generic set must take in next —, -1 when the set is complete.
+// Far matches are binned by their distance D from the hull; the cumulative count up to a bin's upper edge must stay within
+// bound(lower edge), bound(t) = min(t, 2t - 6) — conservative for (*), which asks cnt(D' <= D) <= bound(D) at every far match.
+template <class LN> VTXF_FN int closure_scan(int d, int nc, const LN& ln, uint64_t used, int hull_lo, int hull_hi) {
+    constexpr int XS = LN::XS;
+    constexpr uint32_t YM = LN::YM;
+    // cumulative counters, one byte each: D <= 5, 7, 11, 15, 23, 31, 39 (a match at D >= 40 > ns can never be in the way)
+    uint64_t cum = 0;
+    int near_k = -1, near_d = 1 << 20;
+    for (int k0 = 0; k0 < nc; k0 += 4) {               // (four words per trip, loaded together)
+        uint32_t w4[4];
+        VTXF_UNROLL
+        for (int j = 0; j < 4; ++j) w4[j] = ln.s(imin(k0 + j, nc - 1));
+        VTXF_UNROLL
+        for (int j = 0; j < 4; ++j) {
+            const int k = k0 + j;
+            if (k >= nc || ((used >> k) & 1ull)) continue;
+            const uint32_t w = w4[j];
+            const int delta = (int)(w & YM) - (int)(w >> XS) - d;
+            const int D = delta > hull_hi ? delta - hull_hi : (delta < hull_lo ? hull_lo - delta : 0);
+            if (D < near_d) { near_d = D; near_k = k; }
+            if (D < 40) {
+                const int bin = (D >= 6) + (D >= 8) + (D >= 12) + (D >= 16) + (D >= 24) + (D >= 32);
+                cum += 0x0001010101010101ull << (8 * bin);
+            }
+        }
+    }
+    if (near_k < 0) return -1;                                    // nothing is far
+#if VTXF_MUTANT == 6
+    bool ok = near_d >= 3;                                         // (mutant: a far piece three diagonals out)
+#else
+    bool ok = near_d >= 4;                                         // bound(t) <= 0 for t <= 3
+#endif
+    if (ok) {
+        const uint64_t lim = 0x002018100c080602ull;                // bound(4, 6, 8, 12, 16, 24, 32), one byte each
+        // every byte of cum <= its byte of lim: byte-wise (0x80 + lim) - cum keeps bit 7 (no borrow crosses a byte: cum <= SM < 128)
+        ok = (((lim | 0x8080808080808080ull) - cum) & 0x0080808080808080ull) == 0x0080808080808080ull;
+    }
+    return ok ? -1 : near_k;
+}
+// The closure's first scan (the generic set still empty): >= 0 when the set must grow — the task takes the rare path of back_rest
+// (closure rescans, the fixpoint over the generic pieces); band_diag_kernel leaves those tasks to band_tail_kernel.  back_rest(..,
+// first) with first = this value goes on from there; back_rest without it scans itself — the same verdict either way.
+template <class LN> VTXF_FN int closure_first(const Front& fr, int ns, const LN& ln) { return closure_scan(fr.d, ns, ln, 0ull, 0, 0); }
+// closure, run bound, verdict (the matches sorted and found harmless).  first: closure_first's answer when the caller has it (-2: not)
 template <class LN> VTXF_FN int32_t back_rest(const Front& fr, int ns, const LN& ln, const Lane& gl, uint32_t* why, int ablate,
-                                              const Refine* rf, uint32_t* aux) {
+                                              const Refine* rf, uint32_t* aux, int first) {
     if (aux) *aux = 0xffffffffu;
     constexpr int XS = LN::XS;
     constexpr uint32_t YM = LN::YM, ONE = LN::ONE;
@@ -916,48 +961,14 @@ template <class LN> VTXF_FN int32_t back_rest(const Front& fr, int ns, const LN&
     const int nc = ns;
     if (ablate == 5) { *why = W_NOT_TIGHT; return -1; }                   // (profiling aid) sort + harmless tests only
     // ---- generic set: the main pieces plus the off-diagonal pieces that may not be left out as FAR (header: condition (*)).
-    //      Far matches are binned by their distance D from the hull of the generic diagonals; the cumulative count up to a
-    //      bin's upper edge must stay within bound(lower edge), bound(t) = min(t, 2t - 6) — conservative for (*), which asks
-    //      cnt(D' <= D) <= bound(D) at every far match.  On a violation the nearest far piece joins the generic set (the hull
-    //      grows, every distance is taken again). ----
+    //      closure_scan bins the far matches; on a violation the nearest far piece joins the generic set (the hull grows, every
+    //      distance is taken again). ----
     int ng = 0;
     {
         int hull_lo = 0, hull_hi = 0;
         uint64_t used = 0;
-        for (;;) {
-            // cumulative counters, one byte each: D <= 5, 7, 11, 15, 23, 31, 39 (a match at D >= 40 > ns can never be in the way)
-            uint64_t cum = 0;
-            int near_k = -1, near_d = 1 << 20;
-            for (int k0 = 0; k0 < nc; k0 += 4) {               // (four words per trip, loaded together)
-                uint32_t w4[4];
-                VTXF_UNROLL
-                for (int j = 0; j < 4; ++j) w4[j] = ln.s(imin(k0 + j, nc - 1));
-                VTXF_UNROLL
-                for (int j = 0; j < 4; ++j) {
-                    const int k = k0 + j;
-                    if (k >= nc || ((used >> k) & 1ull)) continue;
-                    const uint32_t w = w4[j];
-                    const int delta = (int)(w & YM) - (int)(w >> XS) - d;
-                    const int D = delta > hull_hi ? delta - hull_hi : (delta < hull_lo ? hull_lo - delta : 0);
-                    if (D < near_d) { near_d = D; near_k = k; }
-                    if (D < 40) {
-                        const int bin = (D >= 6) + (D >= 8) + (D >= 12) + (D >= 16) + (D >= 24) + (D >= 32);
-                        cum += 0x0001010101010101ull << (8 * bin);
-                    }
-                }
-            }
-            if (near_k < 0) break;                                        // nothing is far
-#if VTXF_MUTANT == 6
-            bool ok = near_d >= 3;                                         // (mutant: a far piece three diagonals out)
-#else
-            bool ok = near_d >= 4;                                         // bound(t) <= 0 for t <= 3
-#endif
-            if (ok) {
-                const uint64_t lim = 0x002018100c080602ull;                // bound(4, 6, 8, 12, 16, 24, 32), one byte each
-                // every byte of cum <= its byte of lim: byte-wise (0x80 + lim) - cum keeps bit 7 (no borrow crosses a byte: cum <= SM < 128)
-                ok = (((lim | 0x8080808080808080ull) - cum) & 0x0080808080808080ull) == 0x0080808080808080ull;
-            }
-            if (ok) break;
+        int near_k = first >= -1 ? first : closure_first(fr, nc, ln);
+        while (near_k >= 0) {
             // the nearest far match: its piece (head = the match no other match continues into; members = its continuations)
             int k = near_k;
             for (int j = k - 1; j >= 0; --j) {
@@ -980,6 +991,7 @@ template <class LN> VTXF_FN int32_t back_rest(const Front& fr, int ns, const LN&
             ++ng;
             used |= members;
             hull_lo = imin(hull_lo, delta); hull_hi = imax(hull_hi, delta);
+            near_k = closure_scan(d, nc, ln, used, hull_lo, hull_hi);
         }
         // what is left is far.  E = their k-mer matches
         far_e = nc - __builtin_popcountll(used);
@@ -1063,6 +1075,53 @@ template <class LN> VTXF_FN int32_t back_rest(const Front& fr, int ns, const LN&
     if (fr.cert != ub) { *why = W_NOT_TIGHT; if (aux && ng == 0) *aux = (uint32_t)far_e; return -1; }
     *why = W_OK;
     return fr.cert;
+}
+
+// ---- the record of a task deferred at closure_first (band_diag_kernel -> band_tail_kernel): everything back_rest and the routing
+//      behind it read.  Word i at rec[i * stride] (the device: word-major over the buffer's records).
+//   0 task   1 band_pack(fr)   2 r | ns << 4 | best_dp << 10 | cert << 18   3 zc   4 .. 4 + RM  main piece words (i < r)
+//   4 + RM ..  the ns sorted, harmless matches: TAIL_SW words (two two-byte entries per word, or one four-byte entry)
+constexpr int TAIL_SW = S_WORDS;
+constexpr int TAIL_WORDS = 4 + RM + TAIL_SW;
+template <class LN> VTXF_FN void tail_pack(uint32_t* rec, size_t stride, uint32_t task, const Front& fr, int ns, const LN& ln) {
+    static_assert(LN::SMAX <= 2 * TAIL_SW, "the matches fit the record");
+    rec[0] = task;
+    rec[stride] = band_pack(fr);
+    rec[2 * stride] = (uint32_t)fr.r | ((uint32_t)ns << 4) | ((uint32_t)imin(fr.best_dp, 255) << 10) | ((uint32_t)fr.cert << 18);
+    rec[3 * stride] = fr.zc;
+    for (int i = 0; i < fr.r; ++i) rec[(size_t)(4 + i) * stride] = ln.at(i);
+    if constexpr (sizeof(typename LN::SType) == 2) {
+        for (int i = 0; 2 * i < ns; ++i) rec[(size_t)(4 + RM + i) * stride] = (uint32_t)ln.s(2 * i) | ((uint32_t)ln.s(2 * i + 1) << 16);
+    } else {
+        for (int i = 0; i < ns; ++i) rec[(size_t)(4 + RM + i) * stride] = (uint32_t)ln.s(i);
+    }
+}
+// back into the lane's layout; returns the task (fr: d, r, best_dp, cert, zc, and ca / cb as far as band_pack holds them; *pack: word 1)
+template <class LN> VTXF_FN uint32_t tail_unpack(const uint32_t* rec, size_t stride, Front& fr, int& ns, const LN& ln, uint32_t* pack) {
+    const uint32_t task = rec[0], pk = rec[stride], w2 = rec[2 * stride];
+    fr.why = W_OK; fr.need = m_zero();
+    fr.zc = rec[3 * stride];
+    fr.d = (int)(pk >> 16) - 256; fr.ca = (int)((pk >> 8) & 0xffu); fr.cb = (int)(pk & 0xffu);
+    fr.r = (int)(w2 & 15u); ns = (int)((w2 >> 4) & 63u); fr.best_dp = (int)((w2 >> 10) & 255u); fr.cert = (int)(w2 >> 18);
+    *pack = pk;
+    const int nw = sizeof(typename LN::SType) == 2 ? (ns + 1) >> 1 : ns;
+    uint32_t pw[RM], sw[TAIL_SW];
+    VTXF_UNROLL
+    for (int i = 0; i < RM; ++i) pw[i] = i < fr.r ? rec[(size_t)(4 + i) * stride] : 0u;              // (the loads go out together)
+    VTXF_UNROLL
+    for (int i = 0; i < TAIL_SW; ++i) sw[i] = i < nw ? rec[(size_t)(4 + RM + i) * stride] : 0u;
+    VTXF_UNROLL
+    for (int i = 0; i < RM; ++i) if (i < fr.r) ln.at(i) = pw[i];
+    VTXF_UNROLL
+    for (int i = 0; i < TAIL_SW; ++i) {
+        if (i >= nw) continue;
+        if constexpr (sizeof(typename LN::SType) == 2) {
+            ln.s(2 * i) = (typename LN::SType)(sw[i] & 0xffffu); ln.s(2 * i + 1) = (typename LN::SType)(sw[i] >> 16);
+        } else {
+            ln.s(i) = (typename LN::SType)sw[i];
+        }
+    }
+    return task;
 }
 
 // ======== the corridor certificate (round 6; band_corridor_kernel; proof below, brute-force check in tests/test_fastcore.py) ========
