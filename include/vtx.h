@@ -365,9 +365,17 @@ int vtx_device_scores(vtx_ctx* ctx, const int32_t** d_ref, const int32_t** d_alt
  * per triplet in insertion order) — formatted on the device and streamed into `path` by the copy workers; the triplets never become
  * host arrays.  which: 0 = `value` (the matrix), 1 = `ref_value` (coverage mode's ref matrix, :385-389).  Integral values only
  * (consensus 1 / 2 / 3, coverage counts: Rust's `{}` of such an f64 is its digits); alt_frac's fractions / NaN return
- * VTX_E_UNSUPPORTED and leave nothing at `path` — format those on the host (vtx_fetch_coo + vtxh_write_mtx: shortest round-trip
- * digits).  *sum (optional): the sum of the values written (the reference's "sum of 0" warning, :410-415).                      */
+ * VTX_E_UNSUPPORTED and leave nothing at `path` — use vtx_write_mtx_f64, or format those on the host (vtx_fetch_coo +
+ * vtxh_write_mtx).  *sum (optional): the sum of the values written (the reference's "sum of 0" warning, :410-415).                      */
 int vtx_write_mtx(vtx_ctx* ctx, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum);
+
+/* vtx_write_mtx for ANY value vtx_run produces — alt_frac's fractions and NaN included: Rust's `{}` of an f64, the shortest digits
+ * that round-trip, positional (0.3333333333333333, 0.000033333333333333335, NaN), formatted per lane on the device; byte-identical to
+ * vtx_fetch_coo + vtxh_write_mtx.  Integral matrices come out as from vtx_write_mtx.  Domain: NaN, +-0 and 2^-40 <= |v| < 2^53; a
+ * value outside it (infinite, subnormal, larger, smaller — nothing a scoring mode computes) returns VTX_E_UNSUPPORTED and leaves
+ * nothing at `path`.  *sum (optional): the sum of the values, added up in no fixed order; NaN when a value is NaN (what the host's
+ * `sum += v` gives: the "sum of 0" warning stays silent).  (A second name because vtx_write_mtx's refusal of fractions is pinned.)  */
+int vtx_write_mtx_f64(vtx_ctx* ctx, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum);
 
 /* Device pointers of the last vtx_run's triplets (same layout as vtx_coo, all
  * arrays resident in HBM) — the payload of the multi-GPU row gather.          */

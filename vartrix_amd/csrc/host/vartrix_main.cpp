@@ -132,7 +132,7 @@ struct Shard {
     bool keep_ctx = false;
     vtx_coo kept{};
     vtx_ctx* ctx_pre = nullptr;                 // a context created at launch (its vtx_prefetch_file is bringing the BAM's bytes): used instead of vtx_create
-    vtx_ctx* ctx_kept = nullptr;                // keep_ctx with defer_fetch: the triplets stay on the device — vtx_write_mtx formats them there
+    vtx_ctx* ctx_kept = nullptr;                // keep_ctx with defer_fetch: the triplets stay on the device — vtx_write_mtx / vtx_write_mtx_f64 formats them there
     bool defer_fetch = false;
     std::string err;
     int rc = 0;
@@ -448,7 +448,7 @@ int main(int argc, char** argv) {
     const uint32_t *out_row = nullptr, *out_col = nullptr;
     const double *out_v = nullptr, *out_rv = nullptr;
     std::vector<double> v, rv;
-    vtx_ctx* kept_ctx = nullptr;                           // one range, one batch, one device: the matrix is written from the device (vtx_write_mtx)
+    vtx_ctx* kept_ctx = nullptr;                           // one range, one batch, one device: the matrix is written from the device (vtx_write_mtx, alt_frac: vtx_write_mtx_f64)
     vtx_raw_stats raw_total{};
     vtxh_metrics m{};
     double t_device = 0;
@@ -464,7 +464,7 @@ int main(int argc, char** argv) {
         Shard s;
         s.ingest = &g; s.bc_bytes = bc_bytes; s.bc_offsets = bc_offsets; s.n_bcs = bc_n; s.raw = true;
         s.keep_ctx = range_idx == 0 && cur.last;
-        s.defer_fetch = s.keep_ctx && mode != "alt_frac";
+        s.defer_fetch = s.keep_ctx;
         if (early.joinable()) early.join();
         if (early_ctx) { s.ctx_pre = early_ctx; early_ctx = nullptr; }
         const auto t_shard = std::chrono::steady_clock::now();
@@ -537,7 +537,7 @@ int main(int argc, char** argv) {
                 const uint32_t r1 = s.loci.empty() ? 0 : s.loci.back().rec_begin + s.loci.back().rec_count;
                 s.n_records = r1 - r0;
                 s.keep_ctx = n_batches == 1 && ndev == 1 && range_idx == 0 && cur.last;
-                s.defer_fetch = s.keep_ctx && mode != "alt_frac" && val["gather"] != "library";
+                s.defer_fetch = s.keep_ctx && val["gather"] != "library";
                 if (raw) {
                     s.raw = true;
                     s.raw_records = full_raw.records + r0;
@@ -627,9 +627,11 @@ int main(int argc, char** argv) {
     if (kept_ctx) {
         // the matrix straight from the device: Matrix-Market text formatted there, streamed into the file by the copy workers
         double s0 = 0;
-        int rc = vtx_write_mtx(kept_ctx, out_matrix.c_str(), n_vars, n_bcs, 0, &s0);
+        // (alt_frac: fractions and NaN, shortest round-trip digits per lane — vtx_write_mtx_f64; s0 is NaN when a value is, like the sum below)
+        const bool real = mode == "alt_frac";
+        int rc = real ? vtx_write_mtx_f64(kept_ctx, out_matrix.c_str(), n_vars, n_bcs, 0, &s0) : vtx_write_mtx(kept_ctx, out_matrix.c_str(), n_vars, n_bcs, 0, &s0);
         if (rc == VTX_OK && mode == "coverage") rc = vtx_write_mtx(kept_ctx, ref_matrix.c_str(), n_vars, n_bcs, 1, nullptr);    // :385-389 (see below)
-        if (rc == VTX_OK) { written = true; sum = s0; }
+        if (rc == VTX_OK) { written = true; sum = s0; LOG_INFO("Matrix written from the device (%s)", real ? "vtx_write_mtx_f64" : "vtx_write_mtx"); }
         else if (rc != VTX_E_UNSUPPORTED) { printf("Vartrix error.\nError: Error writing out-matrix\nInfo: caused by %s\n", vtx_strerror(kept_ctx)); return 1; }
         else {
             vtx_coo coo{};
@@ -638,6 +640,7 @@ int main(int argc, char** argv) {
         }
     }
     if (!written) {
+    LOG_INFO("Matrix written by the host formatter (vtxh_write_mtx)");
     if (!out_row) { out_nnz = row.size(); out_row = row.data(); out_col = col.data(); out_v = v.data(); out_rv = rv.data(); }
     if (vtxh_write_mtx(out_matrix.c_str(), n_vars, n_bcs, out_nnz, out_row, out_col, out_v) != 0) {
         printf("Vartrix error.\nError: Error writing out-matrix\nInfo: caused by %s\n", vtxh_last_error());

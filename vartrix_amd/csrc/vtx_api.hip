@@ -2289,21 +2289,26 @@ int vtx_fetch_coo(vtx_ctx* c, vtx_coo* out) {
 
 // sprs::io::write_matrix_market of the last vtx_run's triplets (src/main.rs:381-389: three header lines, then "row+1 col+1 value"
 // in insertion order), formatted ON THE DEVICE and streamed into the file by the copy workers: the triplets never become host arrays.
-// which: 0 = `value` (the matrix), 1 = `ref_value` (coverage mode's ref matrix).  Only for integral values — consensus 1 / 2 / 3,
-// coverage counts — whose Rust `{}` text is their digits; alt_frac's fractions / NaN need shortest-round-trip digits: VTX_E_UNSUPPORTED,
-// nothing is left at `path`, the caller formats on the host (vtx_fetch_coo + vtxh_write_mtx).  *sum (optional) = the sum of the values
-// (the reference's "matrix has a sum of 0" warning, :410-415).
-int vtx_write_mtx(vtx_ctx* c, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum) {
+// which: 0 = `value` (the matrix), 1 = `ref_value` (coverage mode's ref matrix).
+// vtx_write_mtx: only for integral values — consensus 1 / 2 / 3, coverage counts — whose Rust `{}` text is their digits; alt_frac's
+// fractions / NaN: VTX_E_UNSUPPORTED, nothing is left at `path`.
+// vtx_write_mtx_f64 (real): those too — shortest round-trip digits per lane (vtx_f64_text.h); VTX_E_UNSUPPORTED only for a value outside
+// that formatter's domain (nothing vtx_run produces), and then the caller formats on the host (vtx_fetch_coo + vtxh_write_mtx).
+// *sum (optional) = the sum of the values (the reference's "matrix has a sum of 0" warning, :410-415), added up in no fixed order; NaN
+// when a value is NaN, as the host's `sum += v` gives.
+static int write_mtx_text(vtx_ctx* c, const char* fn, bool real, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum) {
     if (!c) return VTX_E_INVAL;
-    if (!path || (which != 0 && which != 1)) return fail(c, VTX_E_INVAL, "vtx_write_mtx: bad argument");
-    if (!c->ran) return fail(c, VTX_E_STATE, "vtx_write_mtx: no completed vtx_run");
+    if (!path || (which != 0 && which != 1)) return fail(c, VTX_E_INVAL, "%s: bad argument", fn);
+    if (!c->ran) return fail(c, VTX_E_STATE, "%s: no completed vtx_run", fn);
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
     const uint64_t nnz = c->nnz;
     const uint32_t* d_row = c->d_o_row.as<uint32_t>();
     const uint32_t* d_col = c->d_o_col.as<uint32_t>();
     const double* d_val = which ? c->d_o_refval.as<double>() : c->d_o_val.as<double>();
-    const uint32_t kSlab = 48u << 20;                     // lines per pass: <= 33 bytes each, 32-bit text offsets
+    uint32_t kSlab = 48u << 20;                           // lines per pass: <= 33 bytes each (real: <= 54), 32-bit text offsets
+    static_assert((uint64_t)(48u << 20) * VTXG_MTX_LINE_MAX < (1ull << 32), "a pass's text has 32-bit offsets");
+    if (VTX_DEV_ENV("VTX_MTX_SLAB")) kSlab = std::min(kSlab, (uint32_t)std::max(1, atoi(VTX_DEV_ENV("VTX_MTX_SLAB"))));   // test hook: several passes
     HIP_TRY(c, c->d_bam_cnt.reserve(VTXG_N_COUNTERS * sizeof(uint64_t) + 4 * sizeof(uint32_t)));
     double* d_sum = (double*)c->d_bam_cnt.p;
     uint32_t* d_flag = (uint32_t*)(c->d_bam_cnt.as<unsigned long long>() + VTXG_N_COUNTERS);
@@ -2318,32 +2323,43 @@ int vtx_write_mtx(vtx_ctx* c, const char* path, uint32_t n_rows, uint32_t n_cols
     uint64_t file_off = (uint64_t)hl;
     for (uint64_t base = 0; base < nnz; base += kSlab) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(kSlab, nnz - base);
-        if (hipError_t e = c->d_bam_nhit.reserve((size_t)n * sizeof(uint32_t) + 16)) return bail(fail(c, VTX_E_NOMEM, "vtx_write_mtx: %s", hipGetErrorString(e)));
-        if (hipError_t e = c->d_bam_hscan.reserve((size_t)n * sizeof(uint32_t) + 16)) return bail(fail(c, VTX_E_NOMEM, "vtx_write_mtx: %s", hipGetErrorString(e)));
-        if (hipError_t e = c->d_scan_tmp.reserve(vtxk_scan_temp_bytes(n))) return bail(fail(c, VTX_E_NOMEM, "vtx_write_mtx: %s", hipGetErrorString(e)));
+        if (hipError_t e = c->d_bam_nhit.reserve((size_t)n * sizeof(uint32_t) + 16)) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
+        if (hipError_t e = c->d_bam_hscan.reserve((size_t)n * sizeof(uint32_t) + 16)) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
+        if (hipError_t e = c->d_scan_tmp.reserve(vtxk_scan_temp_bytes(n))) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
         uint32_t* d_len = c->d_bam_nhit.as<uint32_t>();
         uint32_t* d_end = c->d_bam_hscan.as<uint32_t>();
-        hipError_t e = vtxg_mtx_len(d_row + base, d_col + base, d_val + base, n, d_len, d_sum, d_flag, s);
+        hipError_t e = vtxg_mtx_len(d_row + base, d_col + base, d_val + base, n, d_len, d_sum, d_flag, real ? 1 : 0, s);
         if (e == hipSuccess) e = vtxk_inclusive_scan_u32(d_len, d_end, n, c->d_scan_tmp.p, vtxk_scan_temp_bytes(n), s);
         uint32_t total = 0, flag = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&total, d_end + (n - 1), sizeof total, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return bail(fail(c, VTX_E_HIP, "vtx_write_mtx: %s", hipGetErrorString(e)));
-        if (flag) return bail(fail(c, VTX_E_UNSUPPORTED, "vtx_write_mtx: a value that is not a non-negative integer (alt_frac): format on the host (vtx_fetch_coo + vtxh_write_mtx)"));
-        if ((e = c->d_bam_data.reserve((size_t)total + 64)) != hipSuccess) return bail(fail(c, VTX_E_NOMEM, "vtx_write_mtx: %s", hipGetErrorString(e)));
-        e = vtxg_mtx_text(d_row + base, d_col + base, d_val + base, n, d_end, c->d_bam_data.as<uint8_t>(), s);
+        if (e != hipSuccess) return bail(fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e)));
+        if (flag)
+            return bail(real ? fail(c, VTX_E_UNSUPPORTED, "%s: a value outside the device formatter's domain (infinite, subnormal, |v| >= 2^53 or 0 < |v| < 2^-40): format on the host (vtx_fetch_coo + vtxh_write_mtx)", fn)
+                             : fail(c, VTX_E_UNSUPPORTED, "%s: a value that is not a non-negative integer (alt_frac): format on the host (vtx_fetch_coo + vtxh_write_mtx)", fn));
+        if ((e = c->d_bam_data.reserve((size_t)total + 64)) != hipSuccess) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
+        e = vtxg_mtx_text(d_row + base, d_col + base, d_val + base, n, d_end, c->d_bam_data.as<uint8_t>(), real ? 1 : 0, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return bail(fail(c, VTX_E_HIP, "vtx_write_mtx: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return bail(fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e)));
         if (int rc = download_to_fd(c, fd, file_off, c->d_bam_data.p, total)) return bail(rc);
         file_off += total;
     }
     if (sum) {
         *sum = 0.0;
-        if (nnz) HIP_TRY(c, hipMemcpy(sum, d_sum, sizeof(double), hipMemcpyDeviceToHost));
+        if (nnz)
+            if (hipError_t e = hipMemcpy(sum, d_sum, sizeof(double), hipMemcpyDeviceToHost)) return bail(fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e)));
     }
     if (close(fd) != 0) { unlink(path); return fail(c, VTX_E_INVAL, "error writing %s", path); }
     return VTX_OK;
+}
+
+int vtx_write_mtx(vtx_ctx* c, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum) {
+    return write_mtx_text(c, "vtx_write_mtx", false, path, n_rows, n_cols, which, sum);
+}
+
+int vtx_write_mtx_f64(vtx_ctx* c, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum) {
+    return write_mtx_text(c, "vtx_write_mtx_f64", true, path, n_rows, n_cols, which, sum);
 }
 
 int vtx_device_coo(vtx_ctx* c, vtx_coo* out) {

@@ -25,6 +25,7 @@
 #include "vtx_device.h"
 #include "vtx_ingest.h"
 #include "vtx_inflate_core.h"
+#include "vtx_f64_text.h"
 
 namespace {
 
@@ -323,6 +324,9 @@ __global__ __launch_bounds__(256) void bam_scan_kernel(const uint8_t* __restrict
 // Matrix-Market text of resident triplets (sprs::io::write_matrix_market, src/main.rs:381-389): "row+1 col+1 value\n" per triplet,
 // Rust `{}` of an f64 that holds a non-negative integer = its decimal digits (consensus 1 / 2 / 3, coverage counts).  Any other
 // value (alt_frac's fractions, NaN) sets the flag: the host formatter (shortest round-trip digits, vtxh_write_mtx) takes over.
+// REAL (vtx_write_mtx_f64): such a value is formatted too, by vtx_f64_text.h (shortest round-trip digits, positional; its domain covers
+// everything alt_frac produces), and only a value outside that domain sets the flag.  The integral test comes first and keeps its
+// digits; -0 ("-0" in Rust) is not integral there.  The sum takes every value of the domain as it is: one NaN makes it NaN.
 // ---------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t ndigits(uint32_t v) {
     return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u : v < 10000000u ? 7u
@@ -332,6 +336,8 @@ __device__ __forceinline__ uint8_t* put_u32(uint8_t* p, uint32_t v, uint32_t nd)
     for (uint32_t i = nd; i-- > 0;) { p[i] = (uint8_t)('0' + v % 10u); v /= 10u; }
     return p + nd;
 }
+static_assert(10 + 1 + 10 + 1 + vtxt::MAX_LEN + 1 == VTXG_MTX_LINE_MAX, "longest Matrix-Market line");
+template <bool REAL>
 __global__ __launch_bounds__(256) void mtx_len_kernel(const uint32_t* __restrict__ row, const uint32_t* __restrict__ col,
                                                       const double* __restrict__ val, uint32_t n, uint32_t* __restrict__ len,
                                                       double* __restrict__ sum, uint32_t* __restrict__ flag) {
@@ -341,7 +347,12 @@ __global__ __launch_bounds__(256) void mtx_len_kernel(const uint32_t* __restrict
     if (k < n) {
         v = val[k];
         const bool integral = v >= 0.0 && v < 4294967296.0 && v == (double)(uint32_t)v;      // (false for NaN)
-        if (!integral) { atomicOr(flag, 1u); v = 0.0; len[k] = 0; }
+        if (REAL) {
+            const uint32_t nv = integral && !__builtin_signbit(v) ? ndigits((uint32_t)v) : vtxt::f64_len(v);
+            if (!nv) { atomicOr(flag, 1u); v = 0.0; len[k] = 0; }
+            else len[k] = ndigits(row[k] + 1u) + ndigits(col[k] + 1u) + nv + 3u;
+        }
+        else if (!integral) { atomicOr(flag, 1u); v = 0.0; len[k] = 0; }
         else len[k] = ndigits(row[k] + 1u) + ndigits(col[k] + 1u) + ndigits((uint32_t)v) + 3u;
     }
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
@@ -349,16 +360,30 @@ __global__ __launch_bounds__(256) void mtx_len_kernel(const uint32_t* __restrict
     __syncthreads();
     if (threadIdx.x == 0) { const double t = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]; if (t != 0.0) atomicAdd(sum, t); }
 }
+template <bool REAL>
 __global__ __launch_bounds__(256) void mtx_text_kernel(const uint32_t* __restrict__ row, const uint32_t* __restrict__ col,
                                                        const double* __restrict__ val, uint32_t n, const uint32_t* __restrict__ end,
                                                        uint8_t* __restrict__ text) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    const uint32_t r = row[k] + 1u, c = col[k] + 1u, v = (uint32_t)val[k];
-    uint8_t* p = text + (k ? end[k - 1] : 0u);
-    p = put_u32(p, r, ndigits(r)); *p++ = ' ';
-    p = put_u32(p, c, ndigits(c)); *p++ = ' ';
-    p = put_u32(p, v, ndigits(v)); *p = '\n';
+    if (!REAL) {
+        const uint32_t r = row[k] + 1u, c = col[k] + 1u, v = (uint32_t)val[k];
+        uint8_t* p = text + (k ? end[k - 1] : 0u);
+        p = put_u32(p, r, ndigits(r)); *p++ = ' ';
+        p = put_u32(p, c, ndigits(c)); *p++ = ' ';
+        p = put_u32(p, v, ndigits(v)); *p = '\n';
+    } else {
+        const uint32_t beg = k ? end[k - 1] : 0u;
+        if (end[k] == beg) return;                          // outside the formatter's domain: no line (the caller has seen the flag)
+        const uint32_t r = row[k] + 1u, c = col[k] + 1u;
+        const double d = val[k];
+        uint8_t* p = text + beg;
+        p = put_u32(p, r, ndigits(r)); *p++ = ' ';
+        p = put_u32(p, c, ndigits(c)); *p++ = ' ';
+        if (d >= 0.0 && d < 4294967296.0 && d == (double)(uint32_t)d && !__builtin_signbit(d)) p = put_u32(p, (uint32_t)d, ndigits((uint32_t)d));
+        else p = vtxt::f64_put(p, d);
+        *p = '\n';
+    }
 }
 
 }  // namespace
@@ -395,14 +420,16 @@ hipError_t vtxg_scan(int emit, const uint8_t* data, const uint64_t* rec_upos, ui
     return hipGetLastError();
 }
 
-hipError_t vtxg_mtx_len(const uint32_t* row, const uint32_t* col, const double* val, uint32_t n, uint32_t* len, double* sum, uint32_t* flag, hipStream_t s) {
+hipError_t vtxg_mtx_len(const uint32_t* row, const uint32_t* col, const double* val, uint32_t n, uint32_t* len, double* sum, uint32_t* flag, int real, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(mtx_len_kernel, dim3((n + 255) / 256), dim3(256), 0, s, row, col, val, n, len, sum, flag);
+    if (real) hipLaunchKernelGGL(mtx_len_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, row, col, val, n, len, sum, flag);
+    else hipLaunchKernelGGL(mtx_len_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, s, row, col, val, n, len, sum, flag);
     return hipGetLastError();
 }
-hipError_t vtxg_mtx_text(const uint32_t* row, const uint32_t* col, const double* val, uint32_t n, const uint32_t* end, uint8_t* text, hipStream_t s) {
+hipError_t vtxg_mtx_text(const uint32_t* row, const uint32_t* col, const double* val, uint32_t n, const uint32_t* end, uint8_t* text, int real, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(mtx_text_kernel, dim3((n + 255) / 256), dim3(256), 0, s, row, col, val, n, end, text);
+    if (real) hipLaunchKernelGGL(mtx_text_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, row, col, val, n, end, text);
+    else hipLaunchKernelGGL(mtx_text_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, s, row, col, val, n, end, text);
     return hipGetLastError();
 }
 

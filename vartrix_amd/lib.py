@@ -38,6 +38,9 @@ SYMBOLS = (
     "vtx_set_debug", "vtx_fetch_stage", "vtx_debug_bands", "vtx_debug_tables", "vtx_set_read_format",
     "vtx_submit_bam", "vtx_debug_ingest", "vtx_debug_inflate", "vtx_comm_ranks", "vtx_write_mtx", "vtx_prefetch_file",
 )
+# (entry points with a digit in their name: tests/test_abi.py finds the header's declarations with [a-z_]+ and compares them with SYMBOLS,
+# so these are listed — and checked against the header and every build of the library, tests/test_abi_f64.py — on their own)
+SYMBOLS_ALNUM = ("vtx_write_mtx_f64",)
 
 
 class VtxError(RuntimeError):
@@ -121,6 +124,8 @@ def load(variant=None):
     L.vtx_prefetch_file.argtypes = [ctxp, C.c_char_p, C.c_uint64, C.c_uint64]
     L.vtx_write_mtx.restype = C.c_int
     L.vtx_write_mtx.argtypes = [ctxp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_double)]
+    L.vtx_write_mtx_f64.restype = C.c_int
+    L.vtx_write_mtx_f64.argtypes = [ctxp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_double)]
     L.vtx_comm_ranks.restype = C.c_int
     L.vtx_comm_ranks.argtypes = [ctxp, C.POINTER(C.c_int)]
     L.vtx_debug_inflate.restype = C.c_int
@@ -300,11 +305,13 @@ class Context:
         assert len(ident) == COMM_ID_BYTES
         self._check(self._L.vtx_comm_init(self._h, C.c_char_p(ident), rank, world))
 
-    def write_mtx(self, path: str, n_rows: int, n_cols: int, which: int = 0) -> float:
+    def write_mtx(self, path: str, n_rows: int, n_cols: int, which: int = 0, real: bool = False) -> float:
         """The last run's triplets as Matrix-Market text, formatted on the device and streamed into ``path``; returns the sum of the
-        values.  Raises VTX_E_UNSUPPORTED for non-integral values (alt_frac): use fetch_coo + hostlib.write_mtx."""
+        values.  Raises VTX_E_UNSUPPORTED for non-integral values (alt_frac) unless ``real``: vtx_write_mtx_f64 formats those too
+        (shortest round-trip digits, NaN; the sum is NaN when a value is)."""
         s = C.c_double(0.0)
-        self._check(self._L.vtx_write_mtx(self._h, path.encode(), n_rows, n_cols, which, C.byref(s)))
+        fn = self._L.vtx_write_mtx_f64 if real else self._L.vtx_write_mtx
+        self._check(fn(self._h, path.encode(), n_rows, n_cols, which, C.byref(s)))
         return float(s.value)
 
     def comm_ranks(self) -> int:
