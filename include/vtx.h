@@ -328,7 +328,44 @@ typedef struct vtx_ingest_stats {
 int vtx_prefetch_file(vtx_ctx* ctx, const char* path, uint64_t file_off, uint64_t n);
 int vtx_submit_bam(vtx_ctx* ctx, const vtx_bam_ingest* ingest, vtx_ingest_stats* stats);
 
-/* Test / audit hook: intermediate arrays of the last vtx_submit_bam.  *bytes = the array's size, min(cap, *bytes) bytes go to dst. */
+/* ---- vtx_submit_bam_segments: the same ingest for SPARSE loci (round 9) -------------------------------------------------------
+ * A few thousand loci on a BAM of tens of GB: one contiguous stretch from the first locus to the last would be the whole file.  The
+ * plan is a list of SEGMENTS instead, each a run of consecutive BGZF blocks with the record starts inside it — what the reference's
+ * indexed fetch per locus reads (src/main.rs:822-826), merged where two fetches touch.  `base` is a vtx_bam_ingest whose arrays are the
+ * segments' back to back: base.blocks ascending in the file and consecutive only INSIDE a segment (only those byte ranges travel, into
+ * one compact device buffer); base.seeds and segment.end_upos are offsets into the CONCATENATION of the segments' inflated bytes;
+ * base.end_upos is ignored.  Segment k owns blocks [block_begin, block_end) and seeds [seed_begin, seed_end), both tiling the arrays
+ * in order.  A chain stops at the next seed of its segment; the segment's last chain must land on end_upos — a record start the
+ * index names a few windows behind the segment's last locus (or, VTX_SEGMENT_TO_EOF, the end of the file's records).  No record at
+ * or behind end_upos is looked at, so the end has to be PROVEN: the record at end_upos must lie on a contig behind end_tid or start
+ * at / behind end_pos (the end of the segment's last locus; coordinate-sorted file: nothing later can overlap the segment's loci).
+ * The 12 bytes that hold its (tid, pos) are part of the segment's blocks.  A segment that cannot prove its end (a read spliced over
+ * all those windows) is never used: VTX_E_UNSUPPORTED, nothing submitted, the caller packs on the host.  Segments are disjoint in
+ * the file, so every BAM record is looked at once and the (read, locus) pairs come in BAM order, as from vtx_submit_bam.
+ * Afterwards: the state vtx_submit_raw leaves; stats.compressed_bytes / inflated_bytes = the bytes that travelled / were inflated.
+ * A vtx_prefetch_file still in flight is cancelled, not waited for: its bytes are of no use here.                                 */
+#define VTX_SEGMENT_TO_EOF 1u
+typedef struct vtx_bam_segment {
+    uint32_t block_begin, block_end;     /* base.blocks[block_begin .. block_end): consecutive in the file                        */
+    uint32_t seed_begin, seed_end;       /* base.seeds[seed_begin .. seed_end): ascending, inside this segment's inflated bytes   */
+    uint64_t end_upos;                   /* where the last chain lands (offset into the concatenated inflated stream)             */
+    int32_t end_tid, end_pos;            /* the record at end_upos must be beyond (end_tid, end_pos)                              */
+    uint32_t flags;                      /* VTX_SEGMENT_TO_EOF: end_upos is the end of the file's records, nothing to prove       */
+    uint32_t reserved;
+} vtx_bam_segment;
+
+typedef struct vtx_bam_segments {
+    vtx_bam_ingest base;
+    const vtx_bam_segment* segments;
+    uint32_t n_segments;
+    uint32_t contiguous_blocks;          /* for the log: what ONE stretch from the first locus to the last would have been */
+    uint64_t contiguous_compressed, contiguous_inflated;
+} vtx_bam_segments;
+
+int vtx_submit_bam_segments(vtx_ctx* ctx, const vtx_bam_segments* plan, vtx_ingest_stats* stats);
+
+/* Test / audit hook: intermediate arrays of the last vtx_submit_bam / vtx_submit_bam_segments (there: the concatenated stream and
+ * offsets into it).  *bytes = the array's size, min(cap, *bytes) bytes go to dst. */
 #define VTX_INGEST_INFLATED 0        /* the inflated stream of the submitted blocks                           */
 #define VTX_INGEST_RECORD_OFFSETS 1  /* uint64 per BAM record: where its block_size word lies in that stream */
 #define VTX_INGEST_RAW_RECORDS 2     /* vtx_raw_record per surviving (read, locus) pair, BAM order            */
@@ -462,8 +499,8 @@ const char* vtx_status_name(int status);
 
 /* sizeof() of {vtx_config, vtx_locus, vtx_record, vtx_batch, vtx_coo,
  * vtx_timing, vtx_raw_record, vtx_raw_batch, vtx_raw_stats, vtx_bgzf_block, vtx_bam_interval,
- * vtx_bam_ingest, vtx_ingest_stats} as compiled into the library, for binding self-checks.
- * Writes min(n, 13) entries; returns VTX_ABI_VERSION.                        */
+ * vtx_bam_ingest, vtx_ingest_stats, vtx_bam_segment, vtx_bam_segments} as compiled into the library,
+ * for binding self-checks.  Writes min(n, 15) entries; returns VTX_ABI_VERSION.             */
 int vtx_abi_sizes(uint32_t* out, uint32_t n);
 
 #ifdef __cplusplus

@@ -89,11 +89,22 @@ int vtxh_pack_files_range(const vtxh_args* args, int raw, uint32_t row_begin, ui
  * rows [row_begin, row_end), haplotypes, loci — plus an index of the BAM for the device: the BGZF blocks that can hold reads of those
  * loci (a header walk; the file stays mapped, nothing but its header is inflated), the record starts the .bai's linear index names
  * inside them, and the offset of the first record that lies beyond the last locus.  vtxh_get_ingest fills the struct vtx_submit_bam
- * takes (pointers valid until vtxh_free); VTX_E_UNSUPPORTED — no usable .bai, loci so sparse that an index-guided sweep inflates far
- * less, an index that does not match the file — means: pack on the host (vtxh_pack_files_range), as before.  The returned pack
- * carries the loci, names, barcode table and the two VCF-level Metrics like any raw pack; it has no batches.                    */
+ * takes (pointers valid until vtxh_free); VTX_E_UNSUPPORTED — no usable .bai, an index that does not match the file — means: pack
+ * on the host (vtxh_pack_files_range), as before.  The returned pack carries the loci, names, barcode table and the two VCF-level
+ * Metrics like any raw pack; it has no batches.
+ * Loci so sparse that one stretch would inflate far more than an index-guided sweep (more than 64 MiB inflated AND more than 1 MiB
+ * per locus) get a SEGMENTED plan instead (vtxh_plan_kind == VTXH_PLAN_SEGMENTED): per locus the stretch from its linear-index
+ * offset to the index's record start four windows behind its end, stretches that touch or lie within 4 MiB of each other merged —
+ * ascending and disjoint in the file.  vtxh_get_ingest_segments fills the struct vtx_submit_bam_segments takes; vtxh_get_ingest
+ * answers VTX_E_STATE for such a plan (and vtxh_get_ingest_segments for a contiguous one).  vtxh_get_ingest_stats: blocks the
+ * device will inflate / blocks of the file / segments.                                                                          */
+#define VTXH_PLAN_NONE 0
+#define VTXH_PLAN_CONTIGUOUS 1
+#define VTXH_PLAN_SEGMENTED 2
 int vtxh_plan_ingest(const vtxh_args* args, uint32_t row_begin, uint32_t row_end, vtxh_pack** out);
 int vtxh_get_ingest(const vtxh_pack* p, vtx_bam_ingest* out);
+int vtxh_get_ingest_segments(const vtxh_pack* p, vtx_bam_segments* out);
+int vtxh_plan_kind(const vtxh_pack* p);      /* VTXH_PLAN_NONE: not a plan, or a plan that declined (the reason: vtxh_get_ingest) */
 int vtxh_is_plan(const vtxh_pack* p);
 
 /* A pack holds one or more BATCHES: consecutive loci whose reads span less than 4 GiB of the arenas, so that the

@@ -188,6 +188,73 @@ def run_cli_timed(out_dir, fa, vcf, bam, bcs, threads, extra, label, env=None):
 run_cli_timed.totals = []
 
 
+def sparse_runs(args, fa, vcf, bam, bcs):
+    """VCFs of N evenly spaced loci of the authored BAM: this build's --ingest device (the segmented plan) against a baseline binary's
+    --ingest auto (the commit before the segmented plan packs such inputs on the host), alternating, one process at a time."""
+    import hashlib
+    import json
+    import re
+    import statistics
+    lines = open(vcf).read().splitlines()
+    head, rows = [ln for ln in lines if ln.startswith("#")], [ln for ln in lines if not ln.startswith("#")]
+    result = {"what": "sparse loci on the authored config-3-scale BAM (tools/e2e_cli_bench.py --fast --sparse-loci): seconds from main() to "
+                      "exit ('Total since launch') and process wall, alternating runs, %.0f s pause in front of each" % args.gap_seconds,
+              "baseline_commit": args.baseline_commit, "baseline": "--ingest auto", "candidate": "--ingest device", "bam_bytes": os.path.getsize(bam),
+              "runs_per_side": args.runs, "cases": []}
+    pat = {"segments": r"segmented plan: (\d+) segments", "plan_s": r"Plan of range 0: ([\d.]+) s",
+           "compressed_mb": r"segments moved ([\d.]+) MB compressed", "inflated_mb": r"compressed / ([\d.]+) MB inflated of",
+           "contiguous_inflated_mb": r"MB / ([\d.]+) MB$", "h2d_ms": r"upload ([\d.]+) ms", "inflate_ms": r"inflate ([\d.]+) ms",
+           "index_ms": r"record index ([\d.]+) ms", "filter_ms": r"filters ([\d.]+) ms", "host_pack_s": r"Ingest \+ filter \+ pack, all ranges: ([\d.]+) s"}
+    for n in args.sparse_loci:
+        pick = rows[len(rows) // (2 * n)::max(1, len(rows) // n)][:n]
+        sv = os.path.join(args.out, "sparse_%d.vcf" % n)
+        open(sv, "w").write("\n".join(head + pick) + "\n")
+        sides = {"baseline": [], "candidate": []}
+        for k in range(args.runs):
+            for side in ("baseline", "candidate"):
+                if side == "baseline" and not args.baseline_cli:
+                    continue
+                out = os.path.join(args.out, "out.mtx")
+                for f in (out, os.path.join(args.out, "ref_matrix.mtx")):
+                    if os.path.exists(f):
+                        os.remove(f)
+                time.sleep(args.gap_seconds)
+                t0 = time.time()
+                r = subprocess.run([args.baseline_cli if side == "baseline" else hostlib.CLI_PATH, "-v", sv, "-b", bam, "-f", fa, "-c", bcs, "-o", out,
+                                    "--threads", str(args.threads), "--log-level", "info", "--ingest", "auto" if side == "baseline" else "device"],
+                                   cwd=args.out, capture_output=True, text=True)
+                wall = time.time() - t0
+                assert r.returncode == 0, r.stdout + r.stderr
+                run = {"wall_s": round(wall, 4), "mtx_sha256_16": hashlib.sha256(open(out, "rb").read()).hexdigest()[:16],
+                       "packed_on_host": "packing on the host" in r.stderr}
+                m = re.search(r"Total since launch: ([\d.]+) s", r.stderr)
+                run["main_to_exit_s"] = float(m.group(1)) if m else None
+                for key, rx in pat.items():
+                    m = re.search(rx, r.stderr, re.M)
+                    if m:
+                        run[key] = float(m.group(1))
+                sides[side].append(run)
+                print("%d loci, %s run %d: %s" % (n, side, k, json.dumps(run)), flush=True)
+        case = {"loci": len(pick)}
+        for side, runs in sides.items():
+            if not runs:
+                continue
+            t = [x["main_to_exit_s"] for x in runs if x["main_to_exit_s"] is not None]
+            w = [x["wall_s"] for x in runs]
+            case[side] = {"runs": runs, "main_to_exit_median_s": statistics.median(t) if t else None, "main_to_exit_range_s": [min(t), max(t)] if t else None,
+                          "wall_median_s": statistics.median(w), "wall_range_s": [min(w), max(w)]}
+        shas = {x["mtx_sha256_16"] for runs in sides.values() for x in runs}
+        assert len(shas) == 1, "the two sides wrote different matrices for %d loci" % n
+        assert not any(x["packed_on_host"] for x in sides["candidate"]), "--ingest device fell back"
+        case["mtx_sha256_equal"] = True
+        result["cases"].append(case)
+    text = json.dumps(result, indent=1)
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        open(args.json, "w").write(text + "\n")
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fast", action="store_true", help="vectorised authoring (config-3 scale); timing runs only, with an "
@@ -202,12 +269,22 @@ def main():
     ap.add_argument("--gap-seconds", type=float, default=3.0, help="pause in front of every timed CLI run: a process that starts while the driver "
                     "still clears the ~20 GB of device memory the run before it released waits for that inside its first allocations "
                     "(round 6: submit 0.25 s or 1.2 - 1.7 s, alternating, on back-to-back runs; the timed quantity is one run on an idle device)")
+    ap.add_argument("--sparse-loci", type=int, nargs="*", default=[], help="--fast: instead of the runs above, VCFs of N evenly spaced loci of "
+                    "the authored BAM each (sparse loci: the segmented device ingest), --ingest device of this build against "
+                    "--baseline-cli's --ingest auto, alternating, --runs per side; the figures go to --json")
+    ap.add_argument("--baseline-cli", default=None, help="--sparse-loci: the bin/vartrix of the commit to compare with (next to its libraries)")
+    ap.add_argument("--baseline-commit", default=None, help="--sparse-loci: that commit's name, for the record")
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--json", default=None)
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     if args.fast:
         t0 = time.time()
         fa, vcf, bam, bcs, n_reads = author_fast(args.out, args.loci, args.reads, args.barcodes, procs=args.procs)
         print("authored %d reads over %d loci in %.1f s (%.1f MB BAM)" % (n_reads, args.loci, time.time() - t0, os.path.getsize(bam) / 1e6), flush=True)
+        if args.sparse_loci:
+            sparse_runs(args, fa, vcf, bam, bcs)
+            return
         texts = []
         runs = [(["--ingest", "device"], "--ingest device (BGZF inflate, record split, filters on the GPU)", args.threads),
                 (["--ingest", "device"], "--ingest device (second run, page cache warm)", args.threads),

@@ -197,6 +197,19 @@ class VtxBamIngest(C.Structure):
     ]
 
 
+# vtx_submit_bam_segments (sparse loci): segment k owns blocks[block_begin:block_end] and seeds[seed_begin:seed_end] of the base plan
+BAM_SEGMENT_DTYPE = np.dtype([("block_begin", "<u4"), ("block_end", "<u4"), ("seed_begin", "<u4"), ("seed_end", "<u4"), ("end_upos", "<u8"),
+                              ("end_tid", "<i4"), ("end_pos", "<i4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert BAM_SEGMENT_DTYPE.itemsize == 40
+SEGMENT_TO_EOF = 1
+PLAN_NONE, PLAN_CONTIGUOUS, PLAN_SEGMENTED = 0, 1, 2
+
+
+class VtxBamSegments(C.Structure):
+    _fields_ = [("base", VtxBamIngest), ("segments", C.c_void_p), ("n_segments", C.c_uint32), ("contiguous_blocks", C.c_uint32),
+                ("contiguous_compressed", C.c_uint64), ("contiguous_inflated", C.c_uint64)]
+
+
 class VtxIngestStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("num_reads", "num_low_mapq", "num_non_primary", "num_duplicates", "num_not_useful",
                                           "num_no_barcode_tag", "bam_records", "raw_records", "compressed_bytes", "inflated_bytes")] + \

@@ -144,6 +144,7 @@ struct Shard {
     int read_format = VTX_READS_BYTES;          // of the pack's read arenas (vtxh_read_format)
     // --ingest device: the range's reads never exist on the host — the device gets the file's bytes and the plan (vtx_submit_bam)
     const vtx_bam_ingest* ingest = nullptr;
+    const vtx_bam_segments* segments = nullptr; // ... or the segmented plan of sparse loci (vtx_submit_bam_segments); ingest = &segments->base then
     vtx_ingest_stats istats{};
     bool declined = false;                      // vtx_submit_bam said VTX_E_UNSUPPORTED: the caller packs this range on the host
 };
@@ -183,7 +184,7 @@ void run_shard(Shard* s, vtx_config cfg) {
                 s->hap_bytes, s->reads, s->read_bytes};
     vtx_coo coo{};
     if (s->ingest) {
-        if ((s->rc = vtx_set_barcodes(ctx, s->bc_bytes, s->bc_offsets, s->n_bcs)) || (s->rc = vtx_submit_bam(ctx, s->ingest, &s->istats))) {
+        if ((s->rc = vtx_set_barcodes(ctx, s->bc_bytes, s->bc_offsets, s->n_bcs)) || (s->rc = s->segments ? vtx_submit_bam_segments(ctx, s->segments, &s->istats) : vtx_submit_bam(ctx, s->ingest, &s->istats))) {
             s->err = vtx_strerror(ctx);
             s->declined = s->rc == VTX_E_UNSUPPORTED || s->rc == VTX_E_NOMEM;      // (the inflated stream did not fit the device: the host packer needs far less of it)
             vtx_destroy(ctx);
@@ -385,7 +386,7 @@ int main(int argc, char** argv) {
             if (try_device_ingest) {
                 pc.rc = vtxh_plan_ingest(&ha, begin, end, &pc.pk);
                 vtx_bam_ingest probe;
-                if (!pc.rc && vtxh_get_ingest(pc.pk, &probe) != VTX_OK) {        // no plan for this input: pack on the host (here, beside the device)
+                if (!pc.rc && vtxh_plan_kind(pc.pk) == VTXH_PLAN_NONE && vtxh_get_ingest(pc.pk, &probe) != VTX_OK) {        // no plan for this input: pack on the host (here, beside the device)
                     pc.why_host = vtxh_last_error();
                     vtxh_free(pc.pk); pc.pk = nullptr;
                     if (must_device_ingest) { pc.rc = VTX_E_UNSUPPORTED; pc.err = pc.why_host; }
@@ -458,16 +459,24 @@ int main(int argc, char** argv) {
     if (!cur.why_host.empty()) LOG_INFO("Range %u: %s — packing on the host", range_idx, cur.why_host.c_str());
     if (vtxh_is_plan(pk)) {
         // ---- --ingest device: the BAM's bytes and the plan go to the device; the reads never exist on the host ----
-        vtx_bam_ingest g;
-        (void)vtxh_get_ingest(pk, &g);
+        vtx_bam_segments gs{};
+        const bool segmented = vtxh_plan_kind(pk) == VTXH_PLAN_SEGMENTED;
+        if (segmented) (void)vtxh_get_ingest_segments(pk, &gs);
+        else (void)vtxh_get_ingest(pk, &gs.base);
+        const vtx_bam_ingest& g = gs.base;
         vtxh_get_barcode_table(pk, &bc_bytes, &bc_offsets, &bc_n);
         Shard s;
+        if (segmented) s.segments = &gs;
         s.ingest = &g; s.bc_bytes = bc_bytes; s.bc_offsets = bc_offsets; s.n_bcs = bc_n; s.raw = true;
         s.keep_ctx = range_idx == 0 && cur.last;
         s.defer_fetch = s.keep_ctx;
         if (early.joinable()) early.join();
         if (early_ctx) { s.ctx_pre = early_ctx; early_ctx = nullptr; }
         const auto t_shard = std::chrono::steady_clock::now();
+        if (segmented)
+            LOG_INFO("Plan of range %u: %.3f s (%u loci, segmented plan: %u segments, %u BGZF blocks, %u record-start seeds from the .bai; one contiguous stretch would be %u blocks, %.1f MB compressed, %.1f MB inflated); ingest on the device",
+                     range_idx, cur.secs, g.n_loci, gs.n_segments, g.n_blocks, g.n_seeds, gs.contiguous_blocks, gs.contiguous_compressed / 1e6, gs.contiguous_inflated / 1e6);
+        else
         LOG_INFO("Plan of range %u: %.3f s (%u loci, %u BGZF blocks, %u record-start seeds from the .bai); ingest on the device", range_idx, cur.secs,
                  g.n_loci, g.n_blocks, g.n_seeds);
         run_shard(&s, cfg);
@@ -483,6 +492,9 @@ int main(int argc, char** argv) {
             if (s.rc) { printf("Vartrix error.\nError: %s: %s\n", vtx_status_name(s.rc), s.err.c_str()); return 1; }
             t_device += since(t_shard);
             const vtx_ingest_stats& is = s.istats;
+            if (segmented)
+                LOG_INFO("  segmented plan ran: %u segments moved %.1f MB compressed / %.1f MB inflated of the contiguous stretch's %.1f MB / %.1f MB",
+                         gs.n_segments, is.compressed_bytes / 1e6, is.inflated_bytes / 1e6, gs.contiguous_compressed / 1e6, gs.contiguous_inflated / 1e6);
             LOG_INFO("  device ingest: %llu BAM records, %llu (read, locus) pairs; upload %.1f ms (%.1f MB compressed; prefetch %.1f ms, waited %.1f ms for it), inflate %.1f ms (%.1f MB), record index %.1f ms, filters %.1f ms",
                      (unsigned long long)is.bam_records, (unsigned long long)is.raw_records, (double)is.h2d_ms, is.compressed_bytes / 1e6, (double)is.prefetch_ms,
                      (double)is.prefetch_wait_ms, (double)is.inflate_ms, is.inflated_bytes / 1e6, (double)is.index_ms, (double)is.filter_ms);

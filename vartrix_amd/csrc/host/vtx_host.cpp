@@ -681,6 +681,10 @@ struct vtxh_pack {
     std::vector<vtx_bgzf_block> pl_blocks;
     std::vector<uint64_t> pl_seeds;
     uint64_t pl_end = 0;
+    bool segmented = false;        // the plan is a list of segments (vtxh_get_ingest_segments): pl_blocks / pl_seeds hold them back to back
+    std::vector<vtx_bam_segment> pl_segs;
+    uint32_t pl_contig_blocks = 0;
+    uint64_t pl_contig_inflated = 0, pl_contig_compressed = 0;
     std::vector<vtx_bam_interval> pl_iv;
     std::vector<uint32_t> pl_tid_begin;
     std::vector<int32_t> pl_span;
@@ -819,11 +823,28 @@ int vtxh_plan_ingest(const vtxh_args* a, uint32_t row_begin, uint32_t row_end, v
     if (row_begin > row_end) return fail(VTX_E_INVAL, "vtxh_plan_ingest: row_begin > row_end");
     return pack_impl(a, true, row_begin, row_end, out, true);
 }
+static int fill_ingest(const vtxh_pack* p, vtx_bam_ingest* out);
 int vtxh_get_ingest(const vtxh_pack* p, vtx_bam_ingest* out) {
     if (!p || !out) return fail(VTX_E_INVAL, "vtxh_get_ingest: null argument");
     memset(out, 0, sizeof *out);
     if (!p->is_plan) return fail(VTX_E_STATE, "vtxh_get_ingest: not a plan (vtxh_plan_ingest)");
     if (!p->planned) return fail(VTX_E_UNSUPPORTED, "no device-side ingest for this input: %s", p->plan_reason.c_str());
+    if (p->segmented) return fail(VTX_E_STATE, "vtxh_get_ingest: the plan is segmented (vtxh_get_ingest_segments)");
+    return fill_ingest(p, out);
+}
+int vtxh_get_ingest_segments(const vtxh_pack* p, vtx_bam_segments* out) {
+    if (!p || !out) return fail(VTX_E_INVAL, "vtxh_get_ingest_segments: null argument");
+    memset(out, 0, sizeof *out);
+    if (!p->is_plan) return fail(VTX_E_STATE, "vtxh_get_ingest_segments: not a plan (vtxh_plan_ingest)");
+    if (!p->planned) return fail(VTX_E_UNSUPPORTED, "no device-side ingest for this input: %s", p->plan_reason.c_str());
+    if (!p->segmented) return fail(VTX_E_STATE, "vtxh_get_ingest_segments: the plan is contiguous (vtxh_get_ingest)");
+    (void)fill_ingest(p, &out->base);
+    out->segments = p->pl_segs.data(); out->n_segments = (uint32_t)p->pl_segs.size();
+    out->contiguous_blocks = p->pl_contig_blocks; out->contiguous_compressed = p->pl_contig_compressed; out->contiguous_inflated = p->pl_contig_inflated;
+    return VTX_OK;
+}
+int vtxh_plan_kind(const vtxh_pack* p) { return !p || !p->is_plan || !p->planned ? VTXH_PLAN_NONE : (p->segmented ? VTXH_PLAN_SEGMENTED : VTXH_PLAN_CONTIGUOUS); }
+static int fill_ingest(const vtxh_pack* p, vtx_bam_ingest* out) {
     out->file = p->bam_map->data(); out->file_bytes = p->bam_map->size();
     out->blocks = p->pl_blocks.data(); out->n_blocks = (uint32_t)p->pl_blocks.size();
     out->n_ref = (uint32_t)p->pl_span.size();
@@ -1274,8 +1295,104 @@ static int pack_impl(const vtxh_args* a, bool raw, uint32_t row_begin, uint32_t 
         const size_t b1 = (size_t)(std::lower_bound(ustart.begin(), ustart.end(), end_upos) - ustart.begin());
         // sparse loci far apart: the host's index-guided sweep inflates a few blocks per locus; one contiguous range would inflate
         // everything between the first and the last
-        if (ustart[b1] - ustart[b0] > ((uint64_t)64 << 20) && (ustart[b1] - ustart[b0]) >> 20 > targets.size())       // (> 1 MiB of BAM per locus)
-            return done("sparse loci (an index-guided sweep on the host inflates less)");
+        // (developer build: VTXH_SPARSE_KIB = the first threshold in KiB, the second and the merge distance below scale with it, so
+        //  that small authored BAMs take the segmented plan in tests)
+        uint64_t sparse_min = (uint64_t)64 << 20;
+        if (const char* e = VTXH_DEV_ENV("VTXH_SPARSE_KIB")) sparse_min = std::max<uint64_t>(1, strtoull(e, nullptr, 10)) << 10;
+        const uint64_t sparse_per_locus = std::max<uint64_t>(1, sparse_min >> 6);                                       // (1 MiB of BAM per locus)
+        if (ustart[b1] - ustart[b0] > sparse_min && (ustart[b1] - ustart[b0]) / sparse_per_locus > targets.size()) {
+            // ---- the SEGMENTED plan (vtx_submit_bam_segments): per target the stretch an indexed fetch would read, merged where
+            //      two stretches touch or lie closer together than a restart is worth.  Where a stretch ENDS is the index's record
+            //      start kStopWindows windows behind the locus' last window (else the first indexed record of a later contig, else
+            //      the end of the file).  That record may be a read spliced from in front of the locus' end — the index cannot tell
+            //      — so the device proves every end ((tid, pos) of the record there lies behind the segment's last locus) and declines
+            //      the whole ingest if one does not hold: no host probe per segment (10^4 - 10^5 segments at ~0.1 ms each). ----
+            const size_t kStopWindows = 4;
+            const uint64_t merge_gap = sparse_min >> 4;                                                                // (4 MiB inflated)
+            const uint64_t file_end = ustart[blocks.size()];
+            // every record start the index names, as an offset into the file's inflated stream
+            std::vector<uint64_t> named;
+            for (const auto& li : lin) {
+                uint64_t prev = 0;
+                for (const uint64_t v : li) {
+                    if (!v || v == prev) continue;
+                    prev = v;
+                    uint64_t up;
+                    if (!upos_of(v, &up)) return done("the .bai names an offset that is not in the BAM");
+                    if (up >= first_rec) named.push_back(up);
+                }
+            }
+            std::sort(named.begin(), named.end());
+            named.erase(std::unique(named.begin(), named.end()), named.end());
+            struct Stretch { uint64_t s, e; int32_t tid; int64_t end; };
+            std::vector<Stretch> st;
+            st.reserve(targets.size());
+            for (const Target& t : targets) {
+                uint64_t s0 = first_rec, e0 = file_end;
+                if (t.voff) {
+                    if (!upos_of(t.voff, &s0)) return done("the .bai names an offset that is not in the BAM");
+                    if (s0 < first_rec) return done("the .bai names an offset inside the BAM header");
+                }
+                bool found = false;
+                const auto& li = lin[(size_t)t.tid];
+                for (size_t w = (size_t)((std::max<int64_t>(t.end, 1) - 1) >> lin_shift) + kStopWindows; w < li.size() && !found; ++w) {
+                    uint64_t up;
+                    if (!li[w]) continue;
+                    if (!upos_of(li[w], &up)) return done("the .bai names an offset that is not in the BAM");
+                    if (up > s0) { e0 = up; found = true; }
+                }
+                for (size_t c = (size_t)t.tid + 1; c < lin.size() && !found; ++c)
+                    for (const uint64_t v : lin[c])
+                        if (v) { if (!upos_of(v, &e0)) return done("the .bai names an offset that is not in the BAM"); found = true; break; }
+                if (e0 > s0) st.push_back(Stretch{s0, e0, t.tid, t.end});
+            }
+            if (st.empty()) return done(nullptr);
+            std::stable_sort(st.begin(), st.end(), [](const Stretch& x, const Stretch& y) { return x.s < y.s; });
+            auto block_holding = [&](uint64_t up) { return (size_t)(std::upper_bound(ustart.begin(), ustart.end(), up) - ustart.begin()) - 1; };
+            // a segment's blocks: from the one that holds its first record to the one that holds (tid, pos) of the record at its end
+            auto last_block = [&](const Stretch& x) { return x.e >= file_end ? blocks.size() : std::min(blocks.size(), block_holding(std::min(x.e + 11, file_end - 1)) + 1); };
+            std::vector<Stretch> merged;
+            for (const Stretch& x : st) {
+                if (!merged.empty() && (x.s <= merged.back().e + merge_gap || block_holding(x.s) < last_block(merged.back()))) {
+                    Stretch& m = merged.back();
+                    m.e = std::max(m.e, x.e);
+                    if (x.tid > m.tid || (x.tid == m.tid && x.end > m.end)) { m.tid = x.tid; m.end = x.end; }
+                } else merged.push_back(x);
+            }
+            uint64_t cat = 0;                        // bytes of the concatenated inflated stream so far
+            for (const Stretch& x : merged) {
+                const size_t sb0 = block_holding(x.s), sb1 = last_block(x);
+                if (x.end > INT32_MAX) return done("a locus beyond 2^31 on its contig");
+                vtx_bam_segment sg{};
+                sg.block_begin = (uint32_t)P->pl_blocks.size(); sg.seed_begin = (uint32_t)P->pl_seeds.size();
+                for (size_t b = sb0; b < sb1; ++b) P->pl_blocks.push_back(vtx_bgzf_block{(uint64_t)blocks[b].coff, blocks[b].clen, blocks[b].isize});
+                const uint64_t rebase = cat - ustart[sb0];
+                P->pl_seeds.push_back(x.s + rebase);
+                for (auto it = std::upper_bound(named.begin(), named.end(), x.s); it != named.end() && *it < x.e; ++it) P->pl_seeds.push_back(*it + rebase);
+                sg.block_end = (uint32_t)P->pl_blocks.size(); sg.seed_end = (uint32_t)P->pl_seeds.size();
+                sg.end_upos = x.e + rebase; sg.end_tid = x.tid; sg.end_pos = (int32_t)x.end;
+                sg.flags = x.e >= file_end ? VTX_SEGMENT_TO_EOF : 0u;
+                for (size_t i = sg.seed_begin; i < sg.seed_end; ++i) {
+                    const uint64_t stop = i + 1 < sg.seed_end ? P->pl_seeds[i + 1] : sg.end_upos;
+                    if (stop - P->pl_seeds[i] > ((uint64_t)256 << 20)) { P->pl_blocks.clear(); P->pl_seeds.clear(); return done("more than 256 MiB of BAM between two indexed record starts"); }
+                }
+                cat += ustart[sb1] - ustart[sb0];
+                P->pl_segs.push_back(sg);
+                if (cat > ((uint64_t)48 << 30) || P->pl_blocks.size() > 0xfffffff0ull || P->pl_seeds.size() > 0xfffffff0ull) {
+                    P->pl_blocks.clear(); P->pl_seeds.clear(); P->pl_segs.clear();
+                    return done("more than 48 GiB of inflated BAM in one range: stream ranges of loci");
+                }
+            }
+            P->pl_end = cat;
+            P->pl_contig_blocks = (uint32_t)std::min<size_t>(b1 - b0, 0xffffffffu);
+            P->pl_contig_inflated = ustart[b1] - ustart[b0];
+            P->pl_contig_compressed = (uint64_t)blocks[b1 - 1].coff + blocks[b1 - 1].clen - (uint64_t)blocks[b0].coff;
+            P->blocks_inflated = P->pl_blocks.size();
+            P->index_jumps = P->pl_segs.size();
+            P->segmented = true;
+            ph.mark("plan");
+            return done(nullptr);
+        }
         if (ustart[b1] - ustart[b0] > ((uint64_t)48 << 30)) return done("more than 48 GiB of inflated BAM in one range: stream ranges of loci");
         for (size_t b = b0; b < b1; ++b) P->pl_blocks.push_back(vtx_bgzf_block{(uint64_t)blocks[b].coff, blocks[b].clen, blocks[b].isize});
         const uint64_t base = ustart[b0];

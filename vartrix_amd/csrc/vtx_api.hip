@@ -131,7 +131,7 @@ struct vtx_ctx {
         d_locus_cnt, d_locus_scan, d_prep_cnt, d_sort_tmp;
     // device-side BAM ingest (vtx_submit_bam, vtx_ingest.hip): compressed range, inflated stream, record offsets, per-record counts / scans
     DevBuf d_bam_comp, d_bam_data, d_bam_blocks, d_bam_seeds, d_bam_seed_cnt, d_bam_seed_scan, d_bam_iv, d_bam_cnt, d_bam_rec, d_bam_nhit,
-        d_bam_rsz, d_bam_tsz, d_bam_hscan, d_bam_rscan, d_bam_tscan, d_bam_info;
+        d_bam_rsz, d_bam_tsz, d_bam_hscan, d_bam_rscan, d_bam_tscan, d_bam_info, d_bam_segs;
     // vtx_prefetch_file: bytes [pf_off, pf_off + pf_n) of the BAM on their way into d_bam_comp (a library thread drives the copy workers)
     std::thread pf_thread;
     uint64_t pf_off = 0, pf_n = 0;
@@ -140,6 +140,7 @@ struct vtx_ctx {
     size_t pf_map_bytes = 0;
     float pf_ms = 0;                  // how long the prefetch's copy took
     bool pf_valid = false;
+    std::atomic<bool> pf_cancel{false};      // vtx_submit_bam_segments: the prefetch still in flight stops at its next chunk
     uint32_t bam_n_rec = 0, bam_n_raw = 0;
     uint64_t bam_utotal = 0, bam_read_bases = 0, bam_tag_bytes = 0;
     uint32_t max_read_len = 0, fast_overflow = 0;
@@ -213,7 +214,7 @@ void upload_release(vtx_ctx* c) {
 }
 
 // Copies every job to the device and returns when all bytes have landed.
-int upload(vtx_ctx* c, const std::vector<UploadJob>& jobs) {
+int upload(vtx_ctx* c, const std::vector<UploadJob>& jobs, const std::atomic<bool>* cancel = nullptr) {
     struct Chunk { char* dst; const char* src; size_t bytes; };
     std::vector<Chunk> chunks;
     size_t total = 0;
@@ -239,6 +240,7 @@ int upload(vtx_ctx* c, const std::vector<UploadJob>& jobs) {
         for (;;) {
             const size_t i = next.fetch_add(1);
             if (i >= chunks.size() || err.load() != (int)hipSuccess) break;
+            if (cancel && cancel->load()) { err = (int)hipErrorNotReady; break; }           // (vtx_prefetch_file: nobody wants the rest)
             hipError_t e = used[slot] ? hipEventSynchronize(c->up_ev[w][slot]) : hipSuccess;   // the DMA out of this buffer is done
             if (e == hipSuccess) {
                 memcpy(c->up_pin[w][slot], chunks[i].src, chunks[i].bytes);
@@ -253,6 +255,56 @@ int upload(vtx_ctx* c, const std::vector<UploadJob>& jobs) {
         if (e != hipSuccess) err = (int)e;
     };
     const int nw = (int)std::min<size_t>(vtx_ctx::kUpWorkers, chunks.size());
+    std::vector<std::thread> th;
+    for (int w = 1; w < nw; ++w) th.emplace_back(worker, w);
+    worker(0);
+    for (auto& t : th) t.join();
+    if (err.load() != (int)hipSuccess)
+        return fail(c, VTX_E_HIP, "upload: %s", hipGetErrorString((hipError_t)err.load()));
+    return VTX_OK;
+}
+
+// Gathers byte ranges of one host mapping into ONE compact device buffer: piece k lands at dst + off[k] (off ascending, pieces back
+// to back).  The destination is cut into kUpChunk chunks; a worker copies whatever pieces (or parts of them) fall into its chunk
+// into its pinned buffer and pushes the chunk with one DMA — ten thousand segments of a sparse plan cost ten thousand memcpys on the
+// host, not ten thousand DMAs.
+struct GatherPiece { const char* src; size_t off, bytes; };
+int upload_gather(vtx_ctx* c, void* dst, const std::vector<GatherPiece>& pieces) {
+    if (pieces.empty()) return VTX_OK;
+    const size_t total = pieces.back().off + pieces.back().bytes;
+    const size_t n_chunks = (total + vtx_ctx::kUpChunk - 1) / vtx_ctx::kUpChunk;
+    if (!n_chunks) return VTX_OK;
+    if (int rc = upload_init(c)) return rc;
+    std::atomic<size_t> next{0};
+    std::atomic<int> err{(int)hipSuccess};
+    const int device = c->cfg.device;
+    auto worker = [&](int w) {
+        if (hipSetDevice(device) != hipSuccess) { err = (int)hipErrorInvalidDevice; return; }
+        bool used[vtx_ctx::kUpSlots] = {};
+        int slot = 0;
+        for (;;) {
+            const size_t i = next.fetch_add(1);
+            if (i >= n_chunks || err.load() != (int)hipSuccess) break;
+            const size_t lo = i * vtx_ctx::kUpChunk, hi = std::min(total, lo + vtx_ctx::kUpChunk);
+            hipError_t e = used[slot] ? hipEventSynchronize(c->up_ev[w][slot]) : hipSuccess;   // the DMA out of this buffer is done
+            if (e == hipSuccess) {
+                // first piece that ends behind lo
+                size_t k = (size_t)(std::upper_bound(pieces.begin(), pieces.end(), lo, [](size_t v, const GatherPiece& g) { return v < g.off + g.bytes; }) - pieces.begin());
+                for (; k < pieces.size() && pieces[k].off < hi; ++k) {
+                    const size_t a = std::max(lo, pieces[k].off), b = std::min(hi, pieces[k].off + pieces[k].bytes);
+                    memcpy((char*)c->up_pin[w][slot] + (a - lo), pieces[k].src + (a - pieces[k].off), b - a);
+                }
+                e = hipMemcpyAsync((char*)dst + lo, c->up_pin[w][slot], hi - lo, hipMemcpyHostToDevice, c->up_stream[w]);
+            }
+            if (e == hipSuccess) e = hipEventRecord(c->up_ev[w][slot], c->up_stream[w]);
+            if (e != hipSuccess) { err = (int)e; break; }
+            used[slot] = true;
+            slot = (slot + 1) % vtx_ctx::kUpSlots;
+        }
+        const hipError_t e = hipStreamSynchronize(c->up_stream[w]);
+        if (e != hipSuccess) err = (int)e;
+    };
+    const int nw = (int)std::min<size_t>(vtx_ctx::kUpWorkers, n_chunks);
     std::vector<std::thread> th;
     for (int w = 1; w < nw; ++w) th.emplace_back(worker, w);
     worker(0);
@@ -584,12 +636,12 @@ void vtx_config_default(vtx_config* cfg) {
 }
 
 int vtx_abi_sizes(uint32_t* out, uint32_t n) {
-    const uint32_t s[13] = {(uint32_t)sizeof(vtx_config), (uint32_t)sizeof(vtx_locus), (uint32_t)sizeof(vtx_record),
+    const uint32_t s[15] = {(uint32_t)sizeof(vtx_config), (uint32_t)sizeof(vtx_locus), (uint32_t)sizeof(vtx_record),
                             (uint32_t)sizeof(vtx_batch), (uint32_t)sizeof(vtx_coo), (uint32_t)sizeof(vtx_timing),
                             (uint32_t)sizeof(vtx_raw_record), (uint32_t)sizeof(vtx_raw_batch), (uint32_t)sizeof(vtx_raw_stats),
                             (uint32_t)sizeof(vtx_bgzf_block), (uint32_t)sizeof(vtx_bam_interval), (uint32_t)sizeof(vtx_bam_ingest),
-                            (uint32_t)sizeof(vtx_ingest_stats)};
-    for (uint32_t i = 0; i < n && i < 13; ++i) out[i] = s[i];
+                            (uint32_t)sizeof(vtx_ingest_stats), (uint32_t)sizeof(vtx_bam_segment), (uint32_t)sizeof(vtx_bam_segments)};
+    for (uint32_t i = 0; i < n && i < 15; ++i) out[i] = s[i];
     return VTX_ABI_VERSION;
 }
 
@@ -669,7 +721,7 @@ void vtx_destroy(vtx_ctx* c) {
     for (DevBuf* b : bufs) b->release();
     c->d_slow_ws.release(); c->d_slow_retry.release(); c->d_read_packed.release();
     DevBuf* ib[] = {&c->d_bam_comp, &c->d_bam_data, &c->d_bam_blocks, &c->d_bam_seeds, &c->d_bam_seed_cnt, &c->d_bam_seed_scan, &c->d_bam_iv, &c->d_bam_cnt,
-                    &c->d_bam_rec, &c->d_bam_nhit, &c->d_bam_rsz, &c->d_bam_tsz, &c->d_bam_hscan, &c->d_bam_rscan, &c->d_bam_tscan, &c->d_bam_info};
+                    &c->d_bam_rec, &c->d_bam_nhit, &c->d_bam_rsz, &c->d_bam_tsz, &c->d_bam_hscan, &c->d_bam_rscan, &c->d_bam_tscan, &c->d_bam_info, &c->d_bam_segs};
     for (DevBuf* b : ib) b->release();
     DevBuf* gb[] = {&c->d_g_cnt, &c->d_g_row, &c->d_g_col, &c->d_g_alt, &c->d_g_ref, &c->d_g_unk, &c->d_g_val, &c->d_g_refval};
     for (DevBuf* b : gb) b->release();
@@ -1135,16 +1187,16 @@ int vtx_prefetch_file(vtx_ctx* c, const char* path, uint64_t file_off, uint64_t 
     c->pf_thread = std::thread([c, dst, src, n] {
         if (hipSetDevice(c->cfg.device) != hipSuccess) { c->pf_rc = VTX_E_HIP; return; }
         const auto t0 = std::chrono::steady_clock::now();
-        c->pf_rc = upload(c, {{dst, src, (size_t)n}});
+        c->pf_rc = upload(c, {{dst, src, (size_t)n}}, &c->pf_cancel);
         c->pf_ms = (float)(1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     });
     return VTX_OK;
 }
 
 // ---- vtx_submit_bam: the ingest itself on the device (vtx_ingest.hip) ----
-int vtx_submit_bam(vtx_ctx* c, const vtx_bam_ingest* g, vtx_ingest_stats* st) {
-    if (!c) return VTX_E_INVAL;
-    if (!g) return fail(c, VTX_E_INVAL, "vtx_submit_bam: null argument");
+// sg == nullptr: one contiguous stretch (vtx_submit_bam).  Else the segmented plan of vtx_submit_bam_segments: g = &sg->base holds the
+// segments' blocks and seeds back to back; only the segments' byte ranges travel, and the record chains end per segment.
+static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_segments* sg, vtx_ingest_stats* st) {
     c->submitted = false; c->ran = false;
     if (st) memset(st, 0, sizeof *st);
     if (!c->bc_ready) return fail(c, VTX_E_STATE, "vtx_submit_bam: no barcode list (vtx_set_barcodes)");
@@ -1176,8 +1228,42 @@ int vtx_submit_bam(vtx_ctx* c, const vtx_bam_ingest* g, vtx_ingest_stats* st) {
         hi = B.coff + B.clen;
         utotal += B.isize;
     }
+    // segmented: blocks[].coff is rebased to the compact buffer the segments' byte ranges are gathered into; the segment table
+    // tiles the blocks and the seeds in order; every seed and every end lies inside its segment's inflated bytes
+    std::vector<vtxg_segment> segs;
+    std::vector<uint32_t> seed_seg;
+    std::vector<GatherPiece> pieces;
+    uint64_t comp_bytes = hi - lo;
+    if (sg) {
+        const uint32_t nseg = sg->n_segments;
+        if ((nseg && !sg->segments) || (!nseg && (nb || g->n_seeds))) return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: blocks or seeds without segments");
+        segs.resize(nseg); seed_seg.resize(g->n_seeds); pieces.reserve(nseg);
+        uint32_t nbk = 0, nsd = 0;
+        uint64_t ub = 0, cb = 0;
+        for (uint32_t k = 0; k < nseg; ++k) {
+            const vtx_bam_segment& S = sg->segments[k];
+            if (S.block_begin != nbk || S.block_end <= S.block_begin || S.block_end > nb || S.seed_begin != nsd || S.seed_end <= S.seed_begin || S.seed_end > g->n_seeds)
+                return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: segment %u: its blocks / seeds do not follow the segment before, or are empty", k);
+            const uint64_t first = g->blocks[S.block_begin].coff, end = g->blocks[S.block_end - 1].coff + g->blocks[S.block_end - 1].clen;
+            uint64_t ul = ub;
+            for (uint32_t i = S.block_begin; i < S.block_end; ++i) { blocks[i].coff = cb + (g->blocks[i].coff - first); ul += g->blocks[i].isize; }
+            const bool to_eof = (S.flags & VTX_SEGMENT_TO_EOF) != 0;
+            if (S.end_upos > ul || (!to_eof && S.end_upos + 12 > ul) || S.end_upos <= ub)
+                return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: segment %u: its end (and the 12 bytes of the record there) lies outside its blocks", k);
+            for (uint32_t i = S.seed_begin; i < S.seed_end; ++i) {
+                if (g->seeds[i] < ub || g->seeds[i] >= S.end_upos || (i > S.seed_begin && g->seeds[i] <= g->seeds[i - 1]))
+                    return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: seed %u: not ascending or outside segment %u", i, k);
+                seed_seg[i] = k;
+            }
+            segs[k] = vtxg_segment{ub, ul, S.end_upos, S.seed_end, S.end_tid, S.end_pos, S.flags};
+            pieces.push_back(GatherPiece{(const char*)g->file + first, (size_t)cb, (size_t)(end - first)});
+            nbk = S.block_end; nsd = S.seed_end; ub = ul; cb += end - first;
+        }
+        if (nbk != nb || nsd != g->n_seeds) return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: blocks or seeds behind the last segment");
+        comp_bytes = cb;
+    }
     const uint64_t end_upos = std::min<uint64_t>(g->end_upos, utotal);
-    for (uint32_t i = 0; i < g->n_seeds; ++i)
+    for (uint32_t i = 0; !sg && i < g->n_seeds; ++i)
         if (g->seeds[i] >= end_upos || (i && g->seeds[i] <= g->seeds[i - 1])) return fail(c, VTX_E_INVAL, "vtx_submit_bam: seed %u: not ascending or beyond the end", i);
 
     HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -1189,11 +1275,15 @@ int vtx_submit_bam(vtx_ctx* c, const vtx_bam_ingest* g, vtx_ingest_stats* st) {
     //  the latency-bound inflate kernel takes its full ~35 ms whatever the block count, and the copies still in flight queued behind
     //  the kernels: inflate 94 -> 250 ms, the copy 0.09 -> 1.4 s.  The copy is waited for as a whole.)
     const auto t_pf = std::chrono::steady_clock::now();
+    // (a segmented plan has no use for the file as a whole: the prefetch stops at its next chunk and its bytes are dropped)
+    if (sg) c->pf_cancel = true;
     if (c->pf_thread.joinable()) c->pf_thread.join();
+    c->pf_cancel = false;
     const float pf_wait_ms = (float)(1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_pf).count());
-    const bool prefetched = c->pf_valid && c->pf_rc == VTX_OK && nb && c->pf_off <= lo && hi <= c->pf_off + c->pf_n;
+    const bool prefetched = !sg && c->pf_valid && c->pf_rc == VTX_OK && nb && c->pf_off <= lo && hi <= c->pf_off + c->pf_n;
     if (prefetched) { const uint64_t shift = lo - c->pf_off; for (auto& B : blocks) B.coff += shift; }
-    else { c->pf_valid = false; HIP_TRY(c, c->d_bam_comp.reserve((size_t)(hi - lo) + 64)); }
+    else { c->pf_valid = false; HIP_TRY(c, c->d_bam_comp.reserve((size_t)comp_bytes + 64)); }
+    if (sg) HIP_TRY(c, c->d_bam_segs.reserve(segs.size() * sizeof(vtxg_segment) + (size_t)g->n_seeds * sizeof(uint32_t) + 64));
     HIP_TRY(c, c->d_bam_data.reserve((size_t)utotal + 64));
     HIP_TRY(c, c->d_bam_blocks.reserve((size_t)nb * sizeof(vtxg_block)));
     HIP_TRY(c, c->d_bam_seeds.reserve((size_t)ns * u64));
@@ -1221,7 +1311,15 @@ int vtx_submit_bam(vtx_ctx* c, const vtx_bam_ingest* g, vtx_ingest_stats* st) {
     auto since = [&](std::chrono::steady_clock::time_point t) { return (float)(1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count()); };
     HIP_TRY(c, hipMemsetAsync(d_counters, 0, VTXG_N_COUNTERS * u64 + 4 * u32, s));
     HIP_TRY(c, hipMemsetAsync(d_err + 1, 0xff, u32, s));
-    if (int rc = upload(c, {{c->d_bam_comp.p, g->file + lo, prefetched ? (size_t)0 : (size_t)(hi - lo)},
+    // segment table, then the seeds' segment numbers (8-byte aligned: the table's entries are 40 bytes)
+    const vtxg_segment* d_segs = c->d_bam_segs.as<vtxg_segment>();
+    const uint32_t* d_seed_seg = (const uint32_t*)(d_segs + segs.size());
+    if (sg) {
+        if (int rc = upload_gather(c, c->d_bam_comp.p, pieces)) return rc;
+        if (int rc = upload(c, {{c->d_bam_segs.p, segs.data(), segs.size() * sizeof(vtxg_segment)},
+                                {(void*)d_seed_seg, seed_seg.data(), seed_seg.size() * sizeof(uint32_t)}})) return rc;
+    }
+    if (int rc = upload(c, {{c->d_bam_comp.p, g->file + lo, prefetched || sg ? (size_t)0 : (size_t)(hi - lo)},
                             {c->d_bam_blocks.p, blocks.data(), (size_t)nb * sizeof(vtxg_block)},
                             {c->d_bam_seeds.p, g->seeds, (size_t)ns * u64},
                             {c->d_bam_iv.p, ivh.data(), ivh.size() * u32},
@@ -1235,14 +1333,17 @@ int vtx_submit_bam(vtx_ctx* c, const vtx_bam_ingest* g, vtx_ingest_stats* st) {
     HIP_TRY(c, hipEventRecord(c->ev[1], s));
     uint32_t n_rec = 0;
     if (ns) {
-        HIP_TRY(c, vtxg_chain(c->d_bam_data.as<uint8_t>(), utotal, c->d_bam_seeds.as<uint64_t>(), ns, end_upos, c->d_bam_seed_cnt.as<uint32_t>(), nullptr, nullptr, d_err, s));
+        if (sg) HIP_TRY(c, vtxg_chain_segments(c->d_bam_data.as<uint8_t>(), c->d_bam_seeds.as<uint64_t>(), ns, d_seed_seg, d_segs, c->d_bam_seed_cnt.as<uint32_t>(), nullptr, nullptr, d_err, s));
+        else HIP_TRY(c, vtxg_chain(c->d_bam_data.as<uint8_t>(), utotal, c->d_bam_seeds.as<uint64_t>(), ns, end_upos, c->d_bam_seed_cnt.as<uint32_t>(), nullptr, nullptr, d_err, s));
         HIP_TRY(c, vtxk_inclusive_scan_u32(c->d_bam_seed_cnt.as<uint32_t>(), c->d_bam_seed_scan.as<uint32_t>(), ns, c->d_scan_tmp.p, vtxk_scan_temp_bytes(ns), s));
         HIP_TRY(c, hipMemcpyAsync(&n_rec, c->d_bam_seed_scan.as<uint32_t>() + (ns - 1), u32, hipMemcpyDeviceToHost, s));
     }
-    uint32_t err[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(err, d_err, 2 * u32, hipMemcpyDeviceToHost, s));
+    uint32_t err[3] = {0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(err, d_err, 3 * u32, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     auto ingest_error = [&](uint32_t e0, uint32_t e1) -> int {
+        if (!(e0 & (0x1ffu | VTXG_ERR_CHAIN)) && (e0 & VTXG_ERR_SEG_END))
+            return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam_segments: %u of %u segments cannot prove their end (the record the index names there starts in front of the segment's last locus: a read spliced over four windows): the host packer decides", err[2], sg ? sg->n_segments : 0u);
         if (e0 & 0x1ffu) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: BGZF block %u does not inflate on the device (status bits 0x%x): the host packer decides", e1, e0 & 0x1ffu);
         if (e0 & VTXG_ERR_CHAIN) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: a record chain does not end on the index's next record start (index and file disagree, or a malformed record)");
         return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: malformed BAM record");
@@ -1254,7 +1355,9 @@ int vtx_submit_bam(vtx_ctx* c, const vtx_bam_ingest* g, vtx_ingest_stats* st) {
     for (DevBuf* d : per_rec) HIP_TRY(c, d->reserve((size_t)n_rec * u32 + 16));
     HIP_TRY(c, c->d_bam_info.reserve((size_t)n_rec * sizeof(vtxg_recinfo) + 16));
     HIP_TRY(c, c->d_scan_tmp.reserve(vtxk_scan_temp_bytes(std::max(n_rec, 1u))));
-    if (ns) HIP_TRY(c, vtxg_chain(c->d_bam_data.as<uint8_t>(), utotal, c->d_bam_seeds.as<uint64_t>(), ns, end_upos, c->d_bam_seed_cnt.as<uint32_t>(),
+    if (ns && sg) HIP_TRY(c, vtxg_chain_segments(c->d_bam_data.as<uint8_t>(), c->d_bam_seeds.as<uint64_t>(), ns, d_seed_seg, d_segs, c->d_bam_seed_cnt.as<uint32_t>(),
+                                                 c->d_bam_seed_scan.as<uint32_t>(), c->d_bam_rec.as<uint64_t>(), d_err, s));
+    else if (ns) HIP_TRY(c, vtxg_chain(c->d_bam_data.as<uint8_t>(), utotal, c->d_bam_seeds.as<uint64_t>(), ns, end_upos, c->d_bam_seed_cnt.as<uint32_t>(),
                                    c->d_bam_seed_scan.as<uint32_t>(), c->d_bam_rec.as<uint64_t>(), d_err, s));
     HIP_TRY(c, hipEventRecord(c->ev[2], s));
     // ---- fetch + filters per (read, locus) pair: counts, then offsets, then the raw records ----
@@ -1296,11 +1399,24 @@ int vtx_submit_bam(vtx_ctx* c, const vtx_bam_ingest* g, vtx_ingest_stats* st) {
     if (st) {
         st->num_reads = cnt[0]; st->num_low_mapq = cnt[1]; st->num_non_primary = cnt[2]; st->num_duplicates = cnt[3];
         st->num_not_useful = cnt[4]; st->num_no_barcode_tag = cnt[5];
-        st->bam_records = n_rec; st->raw_records = nr; st->inflated_bytes = utotal; st->compressed_bytes = hi - lo;
+        st->bam_records = n_rec; st->raw_records = nr; st->inflated_bytes = utotal; st->compressed_bytes = comp_bytes;
         st->raw = rs; st->h2d_ms = h2d_ms; st->inflate_ms = inflate_ms; st->index_ms = index_ms; st->filter_ms = filter_ms;
         st->prefetch_ms = prefetched ? c->pf_ms : 0.f; st->prefetch_wait_ms = prefetched ? pf_wait_ms : 0.f;
     }
     return VTX_OK;
+}
+
+int vtx_submit_bam(vtx_ctx* c, const vtx_bam_ingest* g, vtx_ingest_stats* st) {
+    if (!c) return VTX_E_INVAL;
+    if (!g) return fail(c, VTX_E_INVAL, "vtx_submit_bam: null argument");
+    return submit_bam_impl(c, g, nullptr, st);
+}
+
+// ---- vtx_submit_bam_segments: the same ingest for a plan of several stretches of the file (sparse loci) ----
+int vtx_submit_bam_segments(vtx_ctx* c, const vtx_bam_segments* sg, vtx_ingest_stats* st) {
+    if (!c) return VTX_E_INVAL;
+    if (!sg) return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: null argument");
+    return submit_bam_impl(c, &sg->base, sg, st);
 }
 
 // Test hook: bgzf_inflate_kernel on arbitrary raw-DEFLATE payloads — block i is file[blocks[i].coff .. + clen) and must inflate to

@@ -20,11 +20,17 @@ struct vtxg_recinfo { uint32_t bc_rel, umi_rel, lens; };
 // err[0] bits: 1 << vtxi::Status of a block that did not inflate (bits 1..8); err[1]: the first such block
 #define VTXG_ERR_CHAIN (1u << 16)      // a record chain did not land on the next seed / ran off the data
 #define VTXG_ERR_RECORD (1u << 17)     // a record whose fields run past its block_size
+#define VTXG_ERR_SEG_END (1u << 18)    // a segment's end is not proven: the record there may still overlap its loci (err[2]: how many)
+// a segment of a segmented plan on the device: its stretch [ubegin, ulimit) of the concatenated inflated stream, where its last chain
+// lands, one past its last seed, and what the record at end_upos must lie beyond (vtx_bam_segment)
+struct vtxg_segment { uint64_t ubegin, ulimit, end_upos; uint32_t seed_end; int32_t end_tid, end_pos; uint32_t flags; };
 
 extern "C" {
 hipError_t vtxg_inflate(const uint8_t* comp, const vtxg_block* blocks, uint32_t n_blocks, uint8_t* out, uint32_t* err, uint32_t* status, uint32_t b_base, hipStream_t s);
 hipError_t vtxg_chain(const uint8_t* data, uint64_t total, const uint64_t* seeds, uint32_t n_seeds, uint64_t end_upos, uint32_t* cnt,
                       const uint32_t* off, uint64_t* rec_upos, uint32_t* err, hipStream_t s);
+hipError_t vtxg_chain_segments(const uint8_t* data, const uint64_t* seeds, uint32_t n_seeds, const uint32_t* seed_seg, const vtxg_segment* segs,
+                               uint32_t* cnt, const uint32_t* off, uint64_t* rec_upos, uint32_t* err, hipStream_t s);
 hipError_t vtxg_scan(int emit, const uint8_t* data, const uint64_t* rec_upos, uint32_t n_rec, vtxg_filter f, const int32_t* iv_start,
                      const int32_t* iv_end, const uint32_t* iv_locus, const uint32_t* tid_begin, const int32_t* tid_span,
                      uint32_t* n_hit, uint32_t* read_sz, uint32_t* tag_sz, vtxg_recinfo* info, const uint32_t* hit_scan,

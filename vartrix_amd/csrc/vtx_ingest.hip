@@ -82,6 +82,49 @@ __global__ __launch_bounds__(64) void bam_chain_kernel(const uint8_t* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// Record boundaries of a SEGMENTED plan (sparse loci: the inflated stream is the concatenation of several stretches of the file).
+// The same walk, but a lane knows its segment: it stops at the next seed of ITS segment or, as the segment's last lane, at the
+// segment's stated end, and reads nothing outside [S.ubegin, S.ulimit) — a record cut by the end of the segment's blocks is an error
+// of the plan (VTXG_ERR_CHAIN), not something to skip.  The last lane then PROVES the end: nothing at or behind it is looked at, so
+// the record that starts there must lie behind every locus of the segment ((tid, pos) beyond (end_tid, end_pos); the file is
+// coordinate-sorted; tid -1, the unplaced reads at the end of a file, compares as the largest).  Its 12 bytes are inside the
+// segment's blocks (the plan adds the block that holds them).  err[2] counts the segments whose end does not hold.
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void bam_chain_seg_kernel(const uint8_t* __restrict__ data, const uint64_t* __restrict__ seeds,
+                                                           uint32_t n_seeds, const uint32_t* __restrict__ seed_seg,
+                                                           const vtxg_segment* __restrict__ segs, uint32_t* __restrict__ cnt,
+                                                           const uint32_t* __restrict__ off, uint64_t* __restrict__ rec_upos,
+                                                           uint32_t* __restrict__ err) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n_seeds) return;
+    const vtxg_segment S = segs[seed_seg[i]];
+    const bool last = i + 1 == S.seed_end;
+    uint64_t p = seeds[i];
+    const uint64_t stop = last ? S.end_upos : seeds[i + 1];
+    uint32_t k = 0;
+    const uint32_t base = off ? (i ? off[i - 1] : 0u) : 0u;      // (off: INCLUSIVE scan of the counts)
+    bool bad = p < S.ubegin || stop > S.ulimit;
+    while (!bad && p < stop) {
+        if (p + 36 > S.ulimit) { bad = true; break; }
+        const uint32_t bs = ld32(data + p);
+        if (bs < 32 || p + 4 + (uint64_t)bs > S.ulimit) { bad = true; break; }
+        if (off) rec_upos[base + k] = p;
+        ++k;
+        p += 4 + (uint64_t)bs;
+    }
+    if (bad || p != stop) atomicOr(&err[0], VTXG_ERR_CHAIN);
+    else if (last && !off && !(S.flags & VTX_SEGMENT_TO_EOF)) {
+        bool proven = false;
+        if (stop + 12 <= S.ulimit) {
+            const int32_t tid = (int32_t)ld32(data + stop + 4), pos = (int32_t)ld32(data + stop + 8);
+            proven = (uint32_t)tid > (uint32_t)S.end_tid || (tid == S.end_tid && pos >= S.end_pos);
+        }
+        if (!proven) { atomicOr(&err[0], VTXG_ERR_SEG_END); atomicAdd(&err[2], 1u); }
+    }
+    if (!off) cnt[i] = k;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // rust-htslib 0.36 CigarStringView::read_pos(ref_pos, include_softclips = false, include_dels = true) as called from
 // useful_alignment (src/main.rs:796): 1 = Some, 0 = None, -1 = Err.  Same restatement as host/vtx_host.cpp: cigar_read_pos and
 // oracle/vtx_oracle.c: vtxo_cigar_read_pos.
@@ -394,6 +437,13 @@ hipError_t vtxg_inflate(const uint8_t* comp, const vtxg_block* blocks, uint32_t 
     if (!n_blocks) return hipSuccess;
     const uint32_t wgs = std::min<uint32_t>((n_blocks + 63) / 64, 256u * 5u);
     hipLaunchKernelGGL(bgzf_inflate_kernel, dim3(wgs), dim3(64), 0, s, comp, blocks, n_blocks, out, err, status, b_base);
+    return hipGetLastError();
+}
+
+hipError_t vtxg_chain_segments(const uint8_t* data, const uint64_t* seeds, uint32_t n_seeds, const uint32_t* seed_seg, const vtxg_segment* segs,
+                               uint32_t* cnt, const uint32_t* off, uint64_t* rec_upos, uint32_t* err, hipStream_t s) {
+    if (!n_seeds) return hipSuccess;
+    hipLaunchKernelGGL(bam_chain_seg_kernel, dim3((n_seeds + 63) / 64), dim3(64), 0, s, data, seeds, n_seeds, seed_seg, segs, cnt, off, rec_upos, err);
     return hipGetLastError();
 }
 

@@ -33,7 +33,7 @@ SYMBOLS = ("vtxh_pack_files", "vtxh_free", "vtxh_last_error", "vtxh_get_batch", 
            "vtxh_num_variants", "vtxh_num_barcodes", "vtxh_variant_name", "vtxh_barcode", "vtxh_write_mtx",
            "vtxh_format_f64", "vtxh_pack_files_raw", "vtxh_get_raw_batch", "vtxh_get_barcode_table", "vtxh_num_batches",
            "vtxh_get_batch_at", "vtxh_get_raw_batch_at", "vtxh_pack_files_range", "vtxh_test_inflate", "vtxh_read_format",
-           "vtxh_trim", "vtxh_plan_ingest", "vtxh_get_ingest", "vtxh_is_plan")
+           "vtxh_trim", "vtxh_plan_ingest", "vtxh_get_ingest", "vtxh_is_plan", "vtxh_get_ingest_segments", "vtxh_plan_kind")
 METRIC_NAMES = ("num_reads", "num_low_mapq", "num_non_primary", "num_duplicates", "num_not_cell_bc",
                 "num_not_useful", "num_non_umi", "num_invalid_recs", "num_multiallelic_recs")
 
@@ -95,6 +95,10 @@ def load():
         L.vtxh_plan_ingest.argtypes = [C.POINTER(VtxhArgs), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
         L.vtxh_get_ingest.restype = C.c_int
         L.vtxh_get_ingest.argtypes = [C.c_void_p, C.POINTER(abi.VtxBamIngest)]
+        L.vtxh_get_ingest_segments.restype = C.c_int
+        L.vtxh_get_ingest_segments.argtypes = [C.c_void_p, C.POINTER(abi.VtxBamSegments)]
+        L.vtxh_plan_kind.restype = C.c_int
+        L.vtxh_plan_kind.argtypes = [C.c_void_p]
         L.vtxh_is_plan.restype = C.c_int
         L.vtxh_is_plan.argtypes = [C.c_void_p]
         L.vtxh_get_ingest_stats.restype = None
@@ -169,15 +173,24 @@ def pack_files(vcf, bam, fasta, cell_barcodes, padding=100, mapq=0, primary_only
 
 class IngestPlan:
     """The plan of a device-side ingest (vtxh_plan_ingest): ``ingest`` is the struct ``Context.submit_bam`` takes (its pointers live as
-    long as this object), ``reason`` says why there is none.  Also the loci, the VCF-level metrics, the barcode list and the names."""
+    long as this object), ``reason`` says why there is none.  Also the loci, the VCF-level metrics, the barcode list and the names.
+    ``kind``: "contiguous" (one stretch of the file), "segmented" (sparse loci: ``segments`` is the struct ``Context.submit_bam_segments``
+    takes and ``ingest`` its base — blocks and seeds of all segments back to back) or None."""
 
     def __init__(self, h, L):
         self._h, self._L = h, L
         self.ingest = abi.VtxBamIngest()
-        rc = L.vtxh_get_ingest(h, C.byref(self.ingest))
+        self.segments = None
+        self.kind = {abi.PLAN_CONTIGUOUS: "contiguous", abi.PLAN_SEGMENTED: "segmented"}.get(L.vtxh_plan_kind(h))
+        if self.kind == "segmented":
+            self.segments = abi.VtxBamSegments()
+            rc = L.vtxh_get_ingest_segments(h, C.byref(self.segments))
+            self.ingest = self.segments.base
+        else:
+            rc = L.vtxh_get_ingest(h, C.byref(self.ingest))
         self.reason = None if rc == 0 else L.vtxh_last_error().decode()
         if rc != 0:
-            self.ingest = None
+            self.ingest = self.segments = None
         m = VtxhMetrics()
         L.vtxh_get_metrics(h, C.byref(m))
         self.metrics = {n: int(getattr(m, n)) for n in METRIC_NAMES}
@@ -198,7 +211,10 @@ class IngestPlan:
 
         def arr(ptr, n, dt):
             return np.frombuffer(C.string_at(ptr, n * np.dtype(dt).itemsize), dtype=dt).copy() if n else np.zeros(0, dt)
-        return dict(blocks=arr(g.blocks, g.n_blocks, abi.BGZF_BLOCK_DTYPE), seeds=arr(g.seeds, g.n_seeds, np.uint64),
+        sg = self.segments
+        extra = dict(segments=arr(sg.segments, sg.n_segments, abi.BAM_SEGMENT_DTYPE), contiguous_blocks=int(sg.contiguous_blocks),
+                     contiguous_compressed=int(sg.contiguous_compressed), contiguous_inflated=int(sg.contiguous_inflated)) if sg is not None else {}
+        return dict(**extra, blocks=arr(g.blocks, g.n_blocks, abi.BGZF_BLOCK_DTYPE), seeds=arr(g.seeds, g.n_seeds, np.uint64),
                     intervals=arr(g.intervals, g.n_intervals, abi.BAM_INTERVAL_DTYPE), tid_begin=arr(g.tid_begin, g.n_ref + 1, np.uint32),
                     tid_max_span=arr(g.tid_max_span, g.n_ref, np.int32), loci=arr(g.loci, g.n_loci, abi.LOCUS_DTYPE),
                     hap_arena=arr(g.hap_arena, g.hap_bytes, np.uint8), end_upos=int(g.end_upos))

@@ -36,7 +36,7 @@ SYMBOLS = (
     "vtx_status_name", "vtx_abi_sizes", "vtx_set_barcodes", "vtx_submit_raw", "vtx_fetch_records",
     "vtx_comm_id", "vtx_comm_init", "vtx_gather_coo", "vtx_fetch_gathered", "vtx_gather_abort", "vtx_gather_plan",
     "vtx_set_debug", "vtx_fetch_stage", "vtx_debug_bands", "vtx_debug_tables", "vtx_set_read_format",
-    "vtx_submit_bam", "vtx_debug_ingest", "vtx_debug_inflate", "vtx_comm_ranks", "vtx_write_mtx", "vtx_prefetch_file",
+    "vtx_submit_bam", "vtx_submit_bam_segments", "vtx_debug_ingest", "vtx_debug_inflate", "vtx_comm_ranks", "vtx_write_mtx", "vtx_prefetch_file",
 )
 # (entry points with a digit in their name: tests/test_abi.py finds the header's declarations with [a-z_]+ and compares them with SYMBOLS,
 # so these are listed — and checked against the header and every build of the library, tests/test_abi_f64.py — on their own)
@@ -120,6 +120,8 @@ def load(variant=None):
     L.vtx_debug_bands.argtypes = [ctxp, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vtx_submit_bam.restype = C.c_int
     L.vtx_submit_bam.argtypes = [ctxp, C.POINTER(abi.VtxBamIngest), C.POINTER(abi.VtxIngestStats)]
+    L.vtx_submit_bam_segments.restype = C.c_int
+    L.vtx_submit_bam_segments.argtypes = [ctxp, C.POINTER(abi.VtxBamSegments), C.POINTER(abi.VtxIngestStats)]
     L.vtx_prefetch_file.restype = C.c_int
     L.vtx_prefetch_file.argtypes = [ctxp, C.c_char_p, C.c_uint64, C.c_uint64]
     L.vtx_write_mtx.restype = C.c_int
@@ -234,6 +236,15 @@ class Context:
         tests); the barcode list must be set.  Afterwards the context is in the state ``submit_raw`` leaves."""
         stats = abi.VtxIngestStats()
         self._check(self._L.vtx_submit_bam(self._h, C.byref(ingest), C.byref(stats)))
+        self.n_records = int(stats.raw.kept)
+        self._n_loci = n_loci
+        return stats
+
+    def submit_bam_segments(self, plan: abi.VtxBamSegments, n_loci: int) -> abi.VtxIngestStats:
+        """Device-side ingest of a SEGMENTED plan (vtx_submit_bam_segments; sparse loci: ``hostlib.plan_ingest(..).segments``): only the
+        segments' bytes travel, record chains end where their segment ends.  The same state afterwards as ``submit_bam``."""
+        stats = abi.VtxIngestStats()
+        self._check(self._L.vtx_submit_bam_segments(self._h, C.byref(plan), C.byref(stats)))
         self.n_records = int(stats.raw.kept)
         self._n_loci = n_loci
         return stats
