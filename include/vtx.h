@@ -271,8 +271,10 @@ int vtx_fetch_records(vtx_ctx* ctx, vtx_record* records, uint32_t* rec_begin, ui
  *   loci / hap_arena   as in vtx_raw_batch; rec_begin / rec_count are ignored (the device fills them).
  * The same resident state afterwards as after vtx_submit_raw (vtx_run / vtx_fetch_* unchanged); stats carries the Metrics
  * counters the filters produce.  VTX_E_UNSUPPORTED (with the reason in vtx_strerror) when the device declines — a block its
- * inflater does not accept, reads above one batch's 4 GiB arena: the caller then packs on the host (libvtxhost), where zlib and the
- * multi-batch logic live.  Nothing is read from the file but [blocks[0].coff, blocks[n - 1].coff + clen).                         */
+ * inflater does not accept, a block whose inflated bytes do not have the CRC32 of its trailer (htslib's check in bgzf_read_block;
+ * always on), a block whose 8-byte trailer would lie beyond file_bytes, reads above one batch's 4 GiB arena: the caller then packs
+ * on the host (libvtxhost), where zlib and the multi-batch logic live.  Nothing is read from the file but
+ * [blocks[0].coff, blocks[n - 1].coff + clen + 8): the blocks' payloads and the trailer (CRC32, ISIZE) behind each.                 */
 typedef struct vtx_bgzf_block {
     uint64_t coff;       /* file offset of the block's raw-DEFLATE payload (behind the gzip header and its extra field) */
     uint32_t clen;       /* payload bytes (BSIZE + 1 - header - 8)                                                      */
@@ -378,6 +380,12 @@ int vtx_debug_ingest(vtx_ctx* ctx, int what, void* dst, uint64_t cap, uint64_t* 
  * path (vtx_submit_bam) treats any non-zero status as "the host packer decides".                                              */
 int vtx_debug_inflate(vtx_ctx* ctx, const uint8_t* file, uint64_t file_bytes, const vtx_bgzf_block* blocks, uint32_t n_blocks,
                       uint8_t* out, uint64_t out_cap, uint32_t* status);
+/* Test hook: the device's CRC-32 (bgzf_crc32_kernel: gzip's, bit for bit zlib's) of arbitrary byte ranges: range i is
+ * data[offsets[i] .. offsets[i + 1]) (n + 1 offsets, ascending, each range at most 65536 bytes), crc_out[i] its value.           */
+int vtx_debug_crc32(vtx_ctx* ctx, const uint8_t* data, uint64_t n_bytes, const uint64_t* offsets, uint32_t n, uint32_t* crc_out);
+/* Device time of the context's last CRC32 check in milliseconds (the last vtx_submit_bam / vtx_submit_bam_segments that succeeded,
+ * or vtx_debug_crc32; vtx_ingest_stats.inflate_ms does not contain it).                                                            */
+int vtx_last_crc_ms(vtx_ctx* ctx, float* ms);
 
 /* Run the hot path on the resident batch: Smith-Waterman of every record
  * against both haplotypes (src/main.rs:898-901), per-read call

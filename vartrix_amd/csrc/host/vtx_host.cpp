@@ -377,12 +377,25 @@ bool index_bgzf(const MappedFile& file, std::vector<BgzfBlock>& blocks) {
 
 // the packer's own decoder first (vtx_inflate.h: one-shot, table driven, ~2.5 x zlib on BAM data); whatever it does not accept
 // — malformed or merely unusual — goes to zlib, which decides.  VTXH_ZLIB_INFLATE=1: zlib only (A/B timing, tests).
-bool inflate_block(const MappedFile& file, const BgzfBlock& b, unsigned char* dst) {
-    if (b.isize == 0) return true;
+// Whichever decoder produced the bytes, they must have the CRC32 of the block's trailer (htslib's check in bgzf_read_block; the
+// trailer lies inside the file: index_bgzf): a mismatch records the block's file offset (the smallest, when several threads find one).
+struct BadCrc {
+    std::atomic<size_t> at{SIZE_MAX};
+    void note(size_t start) { size_t cur = at.load(); while (start < cur && !at.compare_exchange_weak(cur, start)) {} }
+};
+bool inflate_block(const MappedFile& file, const BgzfBlock& b, unsigned char* dst, BadCrc& bad_crc) {
+    const unsigned char* trailer = (const unsigned char*)file.data() + b.coff + b.clen;
+    const uint32_t want = trailer[0] | (trailer[1] << 8) | (trailer[2] << 16) | ((uint32_t)trailer[3] << 24);
+    auto crc_ok = [&] {
+        if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), dst, b.isize) == want) return true;
+        bad_crc.note(b.start);
+        return false;
+    };
+    if (b.isize == 0) return crc_ok();
     const bool zlib_only = VTXH_DEV_ENV("VTXH_ZLIB_INFLATE") != nullptr;      // (per block: a test switches it between two packs of one process)
     if (!zlib_only) {
         vtxinf::Tables T;
-        if (vtxinf::inflate_raw((const uint8_t*)file.data() + b.coff, b.clen, dst, b.isize, T)) return true;
+        if (vtxinf::inflate_raw((const uint8_t*)file.data() + b.coff, b.clen, dst, b.isize, T)) return crc_ok();
     }
     z_stream zs;
     memset(&zs, 0, sizeof zs);
@@ -393,7 +406,7 @@ bool inflate_block(const MappedFile& file, const BgzfBlock& b, unsigned char* ds
     zs.avail_out = b.isize;
     int rc = inflate(&zs, Z_FINISH);
     inflateEnd(&zs);
-    return rc == Z_STREAM_END && zs.avail_out == 0;
+    return rc == Z_STREAM_END && zs.avail_out == 0 && crc_ok();
 }
 
 // Linear index of a .bai (SAM spec 5.2): per reference, for every 16 kb window the smallest virtual file offset of an
@@ -1019,6 +1032,12 @@ static int pack_impl(const vtxh_args* a, bool raw, uint32_t row_begin, uint32_t 
     bool pend_detached = false;
     ByteBuf pend_store;
     bool refill_failed = false;           // a block did not inflate / the buffer could not grow (as opposed to: the file has no more)
+    BadCrc bad_crc;                       // ... or inflated to bytes that do not have its trailer's CRC32
+    auto inflate_failure = [&] {
+        const size_t at = bad_crc.at.load();
+        if (at != SIZE_MAX) return fail(VTX_E_INVAL, "%s: BGZF block at file offset %zu: the CRC32 of its inflated bytes does not match its trailer", a->bam, at);
+        return fail(VTX_E_INVAL, "%s: a BGZF block does not inflate (or out of memory)", a->bam);
+    };
     auto refill = [&](size_t need) -> bool {   // ensure buf has >= need bytes from buf_pos, if the file has them
         while (buf.size() - buf_pos < need && next_block < blocks.size()) {
             size_t chunk = std::min(blocks.size() - next_block, chunk_blocks);
@@ -1047,7 +1066,7 @@ static int pack_impl(const vtxh_args* a, bool raw, uint32_t row_begin, uint32_t 
             std::atomic<bool> ok{true};
             pool.run([&](size_t) {
                 for (size_t k; (k = nextk.fetch_add(1)) < chunk;)
-                    if (!inflate_block(bam_file, blocks[next_block + k], buf.data() + base + off[k])) ok = false;
+                    if (!inflate_block(bam_file, blocks[next_block + k], buf.data() + base + off[k], bad_crc)) ok = false;
             });
             if (!ok) { buf.len = base; refill_failed = true; return false; }     // nothing half-inflated is ever indexed as records
             next_block += chunk;
@@ -1055,7 +1074,7 @@ static int pack_impl(const vtxh_args* a, bool raw, uint32_t row_begin, uint32_t 
         }
         return buf.size() - buf_pos >= need;
     };
-    if (!refill(12) && refill_failed) return fail(VTX_E_INVAL, "%s: a BGZF block does not inflate (or out of memory)", a->bam);
+    if (!refill(12) && refill_failed) return inflate_failure();
     if (buf.size() - buf_pos < 12 || memcmp(buf.data() + buf_pos, "BAM\1", 4) != 0) return fail(VTX_E_INVAL, "%s: bad BAM magic", a->bam);
     uint32_t l_text = rd32(buf.data() + buf_pos + 4);
     if (!refill(12 + (size_t)l_text)) return fail(VTX_E_INVAL, "%s: truncated BAM header", a->bam);
@@ -1247,7 +1266,7 @@ static int pack_impl(const vtxh_args* a, bool raw, uint32_t row_begin, uint32_t 
             while (tmp.size() < within + 12 && b < blocks.size()) {
                 const size_t o = tmp.size();
                 tmp.resize(o + blocks[b].isize + 8);
-                if (!inflate_block(bam_file, blocks[b], tmp.data() + o)) return false;
+                if (!inflate_block(bam_file, blocks[b], tmp.data() + o, bad_crc)) return false;
                 tmp.resize(o + blocks[b].isize);
                 ++b;
             }
@@ -1278,7 +1297,10 @@ static int pack_impl(const vtxh_args* a, bool raw, uint32_t row_begin, uint32_t 
                 if (!v || v == prev || v <= start_voff) continue;
                 prev = v;
                 int32_t rt; int64_t rp;
-                if (!record_at(v, &rt, &rp)) return done("the .bai names an offset that is not a record of the BAM");
+                if (!record_at(v, &rt, &rp)) {
+                    if (bad_crc.at.load() != SIZE_MAX) return inflate_failure();       // damaged data is an error, not a reason to plan differently
+                    return done("the .bai names an offset that is not a record of the BAM");
+                }
                 if (rt < 0 || rt > tl || (rt == tl && rp >= seg_end)) {
                     if (!upos_of(v, &end_upos)) return done("the .bai names an offset that is not in the BAM");
                     found_end = true;
@@ -1657,13 +1679,13 @@ static int pack_impl(const vtxh_args* a, bool raw, uint32_t row_begin, uint32_t 
             buf_pos = 0;
             next_block = b; chunk_blocks = std::min<size_t>(32, max_chunk_blocks);
             refill((size_t)(jump_voff & 0xffff) + 1);
-            if (refill_failed) return fail(VTX_E_INVAL, "%s: a BGZF block does not inflate (or out of memory)", a->bam);
+            if (refill_failed) return inflate_failure();
             buf_pos = (size_t)(jump_voff & 0xffff);
             if (buf_pos > buf.size()) return fail(VTX_E_INVAL, "%s.bai: offset outside its block", a->bam);
         }
         if (use_index) update_read_ahead();
         refill(buf.size() - buf_pos + 1);             // one more chunk of blocks, if the file has one
-        if (refill_failed) return fail(VTX_E_INVAL, "%s: a BGZF block does not inflate (or out of memory)", a->bam);
+        if (refill_failed) return inflate_failure();
         ph.mark("inflate");
         if (!pend_offs.empty()) parse_thread = std::thread(parse_pending);      // ... beside the indexing below
         const auto t_idx0 = std::chrono::steady_clock::now();

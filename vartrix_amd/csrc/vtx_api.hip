@@ -101,6 +101,8 @@ struct vtx_ctx {
     uint32_t* h_pin = nullptr;               // pinned words for counters read back asynchronously (a D2H copy into pageable
                                              // memory blocks the host until the stream reaches it)
     hipEvent_t ev[12] = {};
+    hipEvent_t ev_crc[2] = {};               // around bgzf_crc32_kernel (vtx_submit_bam, vtx_debug_crc32)
+    float crc_ms = 0;                        // vtx_last_crc_ms
     std::string err;
     bool submitted = false, ran = false;
     uint32_t n_loci = 0, n_records = 0, n_cell_groups = 0, n_umi_groups = 0, max_hap_len = 0;
@@ -699,6 +701,8 @@ int vtx_create(const vtx_config* cfg, vtx_ctx** out) {
     }
     for (auto& ev : c->ev)
         if (hipEventCreate(&ev) != hipSuccess) { vtx_destroy(c); return fail(nullptr, VTX_E_HIP, "vtx_create: event creation failed"); }
+    for (auto& ev : c->ev_crc)
+        if (hipEventCreate(&ev) != hipSuccess) { vtx_destroy(c); return fail(nullptr, VTX_E_HIP, "vtx_create: event creation failed"); }
     *out = c;
     return VTX_OK;
 }
@@ -728,6 +732,7 @@ void vtx_destroy(vtx_ctx* c) {
     comm_release(c);
     upload_release(c);
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : c->ev_crc) if (ev) (void)hipEventDestroy(ev);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -1217,13 +1222,17 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
                 return fail(c, VTX_E_INVAL, "vtx_submit_bam: interval %u: bad locus / order / span", k);
         }
     }
-    // blocks: consecutive in the file; the compressed range [lo, hi) travels as it is
+    // blocks: consecutive in the file; the compressed range [lo, hi) travels as it is, and the 8 bytes behind it: a block's trailer
+    // (CRC32, ISIZE) follows its payload, and bgzf_crc32_kernel reads the CRC32 of every block
+    const uint64_t kTrailer = 8;
     std::vector<vtxg_block> blocks(nb);
     uint64_t lo = nb ? g->blocks[0].coff : 0, hi = lo, utotal = 0;
     for (uint32_t i = 0; i < nb; ++i) {
         const vtx_bgzf_block& B = g->blocks[i];
         if (B.coff < hi || B.coff + B.clen > g->file_bytes || B.isize > 65536u)
             return fail(c, VTX_E_INVAL, "vtx_submit_bam: block %u: out of order, outside the file or above 64 KiB", i);
+        if (B.coff + B.clen + kTrailer > g->file_bytes)
+            return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: BGZF block %u: its trailer (CRC32, ISIZE) lies beyond the end of the file: the host packer decides", i);
         blocks[i] = vtxg_block{B.coff - lo, utotal, B.clen, B.isize};
         hi = B.coff + B.clen;
         utotal += B.isize;
@@ -1233,7 +1242,7 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
     std::vector<vtxg_segment> segs;
     std::vector<uint32_t> seed_seg;
     std::vector<GatherPiece> pieces;
-    uint64_t comp_bytes = hi - lo;
+    uint64_t comp_bytes = nb ? hi - lo + kTrailer : 0;
     if (sg) {
         const uint32_t nseg = sg->n_segments;
         if ((nseg && !sg->segments) || (!nseg && (nb || g->n_seeds))) return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: blocks or seeds without segments");
@@ -1256,8 +1265,8 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
                 seed_seg[i] = k;
             }
             segs[k] = vtxg_segment{ub, ul, S.end_upos, S.seed_end, S.end_tid, S.end_pos, S.flags};
-            pieces.push_back(GatherPiece{(const char*)g->file + first, (size_t)cb, (size_t)(end - first)});
-            nbk = S.block_end; nsd = S.seed_end; ub = ul; cb += end - first;
+            pieces.push_back(GatherPiece{(const char*)g->file + first, (size_t)cb, (size_t)(end - first + kTrailer)});      // (with its last block's trailer)
+            nbk = S.block_end; nsd = S.seed_end; ub = ul; cb += end - first + kTrailer;
         }
         if (nbk != nb || nsd != g->n_seeds) return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: blocks or seeds behind the last segment");
         comp_bytes = cb;
@@ -1280,7 +1289,7 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
     if (c->pf_thread.joinable()) c->pf_thread.join();
     c->pf_cancel = false;
     const float pf_wait_ms = (float)(1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_pf).count());
-    const bool prefetched = !sg && c->pf_valid && c->pf_rc == VTX_OK && nb && c->pf_off <= lo && hi <= c->pf_off + c->pf_n;
+    const bool prefetched = !sg && c->pf_valid && c->pf_rc == VTX_OK && nb && c->pf_off <= lo && hi + kTrailer <= c->pf_off + c->pf_n;
     if (prefetched) { const uint64_t shift = lo - c->pf_off; for (auto& B : blocks) B.coff += shift; }
     else { c->pf_valid = false; HIP_TRY(c, c->d_bam_comp.reserve((size_t)comp_bytes + 64)); }
     if (sg) HIP_TRY(c, c->d_bam_segs.reserve(segs.size() * sizeof(vtxg_segment) + (size_t)g->n_seeds * sizeof(uint32_t) + 64));
@@ -1319,7 +1328,7 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
         if (int rc = upload(c, {{c->d_bam_segs.p, segs.data(), segs.size() * sizeof(vtxg_segment)},
                                 {(void*)d_seed_seg, seed_seg.data(), seed_seg.size() * sizeof(uint32_t)}})) return rc;
     }
-    if (int rc = upload(c, {{c->d_bam_comp.p, g->file + lo, prefetched || sg ? (size_t)0 : (size_t)(hi - lo)},
+    if (int rc = upload(c, {{c->d_bam_comp.p, g->file + lo, prefetched || sg ? (size_t)0 : (size_t)comp_bytes},
                             {c->d_bam_blocks.p, blocks.data(), (size_t)nb * sizeof(vtxg_block)},
                             {c->d_bam_seeds.p, g->seeds, (size_t)ns * u64},
                             {c->d_bam_iv.p, ivh.data(), ivh.size() * u32},
@@ -1331,6 +1340,14 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
     HIP_TRY(c, hipEventRecord(c->ev[0], s));
     HIP_TRY(c, vtxg_inflate(c->d_bam_comp.as<uint8_t>(), c->d_bam_blocks.as<vtxg_block>(), nb, c->d_bam_data.as<uint8_t>(), d_err, nullptr, 0, s));
     HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    // ---- the CRC32 of every block's inflated bytes against its trailer (htslib's check in bgzf_read_block): in front of the first
+    //      reader of those bytes, on the same stream, its verdict in the same err words ----
+    static const bool no_crc = VTX_DEV_ENV("VTX_NO_CRC") != nullptr;                                   // A/B timing only: the check off
+    static const int crc_width = VTX_DEV_ENV("VTX_CRC_WIDTH") ? atoi(VTX_DEV_ENV("VTX_CRC_WIDTH")) : VTXG_CRC_WIDTH;   // experiment knob: 4 / 8 / 16
+    HIP_TRY(c, hipEventRecord(c->ev_crc[0], s));
+    if (!no_crc) HIP_TRY(c, vtxg_crc32(c->d_bam_comp.as<uint8_t>(), c->d_bam_blocks.as<vtxg_block>(), nb, c->d_bam_data.as<uint8_t>(), d_err, nullptr, 0, crc_width, s));
+    HIP_TRY(c, hipEventRecord(c->ev_crc[1], s));
+    c->crc_ms = 0;
     uint32_t n_rec = 0;
     if (ns) {
         if (sg) HIP_TRY(c, vtxg_chain_segments(c->d_bam_data.as<uint8_t>(), c->d_bam_seeds.as<uint64_t>(), ns, d_seed_seg, d_segs, c->d_bam_seed_cnt.as<uint32_t>(), nullptr, nullptr, d_err, s));
@@ -1342,9 +1359,10 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
     HIP_TRY(c, hipMemcpyAsync(err, d_err, 3 * u32, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     auto ingest_error = [&](uint32_t e0, uint32_t e1) -> int {
-        if (!(e0 & (0x1ffu | VTXG_ERR_CHAIN)) && (e0 & VTXG_ERR_SEG_END))
+        if (!(e0 & (0x1ffu | VTXG_ERR_CRC | VTXG_ERR_CHAIN)) && (e0 & VTXG_ERR_SEG_END))
             return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam_segments: %u of %u segments cannot prove their end (the record the index names there starts in front of the segment's last locus: a read spliced over four windows): the host packer decides", err[2], sg ? sg->n_segments : 0u);
         if (e0 & 0x1ffu) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: BGZF block %u does not inflate on the device (status bits 0x%x): the host packer decides", e1, e0 & 0x1ffu);
+        if (e0 & VTXG_ERR_CRC) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: BGZF block %u: the CRC32 of its inflated bytes does not match its trailer: the host packer decides", e1);
         if (e0 & VTXG_ERR_CHAIN) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: a record chain does not end on the index's next record start (index and file disagree, or a malformed record)");
         return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: malformed BAM record");
     };
@@ -1391,7 +1409,8 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
     HIP_TRY(c, hipStreamSynchronize(s));
     float inflate_ms = 0, index_ms = 0, filter_ms = 0;
     HIP_TRY(c, hipEventElapsedTime(&inflate_ms, c->ev[0], c->ev[1]));
-    HIP_TRY(c, hipEventElapsedTime(&index_ms, c->ev[1], c->ev[2]));
+    HIP_TRY(c, hipEventElapsedTime(&c->crc_ms, c->ev_crc[0], c->ev_crc[1]));
+    HIP_TRY(c, hipEventElapsedTime(&index_ms, c->ev_crc[1], c->ev[2]));
     HIP_TRY(c, hipEventElapsedTime(&filter_ms, c->ev[2], c->ev[3]));
     c->bam_n_rec = n_rec; c->bam_n_raw = nr; c->bam_utotal = utotal; c->bam_read_bases = read_bases; c->bam_tag_bytes = tag_bytes;
     vtx_raw_stats rs{};
@@ -1450,6 +1469,45 @@ int vtx_debug_inflate(vtx_ctx* c, const uint8_t* file, uint64_t file_bytes, cons
     if (n) HIP_TRY(c, hipMemcpyAsync(status, c->d_bam_seed_cnt.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (utotal && out) HIP_TRY(c, hipMemcpyAsync(out, c->d_bam_data.p, (size_t)utotal, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
+    return VTX_OK;
+}
+
+// Test hook: bgzf_crc32_kernel on arbitrary byte ranges — range i is data[offsets[i] .. offsets[i + 1]), at most 64 KiB each; crc_out[i]
+// = its CRC-32 as the device computes it (no trailer to compare with).  vtx_last_crc_ms then gives the kernel's time.
+int vtx_debug_crc32(vtx_ctx* c, const uint8_t* data, uint64_t n_bytes, const uint64_t* offsets, uint32_t n, uint32_t* crc_out) {
+    if (!c || !offsets || (n && !crc_out) || (n_bytes && !data)) return VTX_E_INVAL;
+    std::vector<vtxg_block> blocks(n);
+    if (offsets[n] > n_bytes) return fail(c, VTX_E_INVAL, "vtx_debug_crc32: the last offset lies outside the data");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 65536u) return fail(c, VTX_E_INVAL, "vtx_debug_crc32: range %u: not ascending or above 64 KiB", i);
+        blocks[i] = vtxg_block{0, offsets[i], 0, (uint32_t)(offsets[i + 1] - offsets[i])};
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    if (c->pf_thread.joinable()) c->pf_thread.join();
+    static const int crc_width = VTX_DEV_ENV("VTX_CRC_WIDTH") ? atoi(VTX_DEV_ENV("VTX_CRC_WIDTH")) : VTXG_CRC_WIDTH;
+    HIP_TRY(c, c->d_bam_data.reserve((size_t)n_bytes + 64));
+    HIP_TRY(c, c->d_bam_blocks.reserve((size_t)n * sizeof(vtxg_block) + 16));
+    HIP_TRY(c, c->d_bam_cnt.reserve(VTXG_N_COUNTERS * sizeof(uint64_t) + 4 * sizeof(uint32_t)));
+    HIP_TRY(c, c->d_bam_seed_cnt.reserve((size_t)n * sizeof(uint32_t) + 16));
+    uint32_t* d_err = (uint32_t*)(c->d_bam_cnt.as<unsigned long long>() + VTXG_N_COUNTERS);
+    HIP_TRY(c, hipMemsetAsync(d_err, 0, 4 * sizeof(uint32_t), s));
+    if (int rc = upload(c, {{c->d_bam_data.p, data, (size_t)n_bytes}, {c->d_bam_blocks.p, blocks.data(), (size_t)n * sizeof(vtxg_block)}})) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipEventRecord(c->ev_crc[0], s));
+    HIP_TRY(c, vtxg_crc32(nullptr, c->d_bam_blocks.as<vtxg_block>(), n, c->d_bam_data.as<uint8_t>(), d_err, c->d_bam_seed_cnt.as<uint32_t>(), 0, crc_width, s));
+    HIP_TRY(c, hipEventRecord(c->ev_crc[1], s));
+    if (n) HIP_TRY(c, hipMemcpyAsync(crc_out, c->d_bam_seed_cnt.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipEventElapsedTime(&c->crc_ms, c->ev_crc[0], c->ev_crc[1]));
+    return VTX_OK;
+}
+
+// Device time of the last bgzf_crc32_kernel launch of this context (vtx_submit_bam / vtx_submit_bam_segments that got as far as the
+// raw records, or vtx_debug_crc32), in milliseconds; 0 before any.
+int vtx_last_crc_ms(vtx_ctx* c, float* ms) {
+    if (!c || !ms) return VTX_E_INVAL;
+    *ms = c->crc_ms;
     return VTX_OK;
 }
 

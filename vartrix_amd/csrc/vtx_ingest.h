@@ -21,12 +21,18 @@ struct vtxg_recinfo { uint32_t bc_rel, umi_rel, lens; };
 #define VTXG_ERR_CHAIN (1u << 16)      // a record chain did not land on the next seed / ran off the data
 #define VTXG_ERR_RECORD (1u << 17)     // a record whose fields run past its block_size
 #define VTXG_ERR_SEG_END (1u << 18)    // a segment's end is not proven: the record there may still overlap its loci (err[2]: how many)
+#define VTXG_ERR_CRC (1u << 19)        // a block whose inflated bytes do not have the CRC32 of its trailer (err[1]: the first; only when every block inflated)
 // a segment of a segmented plan on the device: its stretch [ubegin, ulimit) of the concatenated inflated stream, where its last chain
 // lands, one past its last seed, and what the record at end_upos must lie beyond (vtx_bam_segment)
 struct vtxg_segment { uint64_t ubegin, ulimit, end_upos; uint32_t seed_end; int32_t end_tid, end_pos; uint32_t flags; };
 
 extern "C" {
 hipError_t vtxg_inflate(const uint8_t* comp, const vtxg_block* blocks, uint32_t n_blocks, uint8_t* out, uint32_t* err, uint32_t* status, uint32_t b_base, hipStream_t s);
+// CRC32 of the inflated bytes of every block (data + uoff, isize) against the four bytes at comp + coff + clen; comp == nullptr: no
+// comparison.  crc_out (optional): the computed values.  width: the slicing width, 4 / 8 / 16 (VTXG_CRC_WIDTH).  data: 16-byte aligned.
+#define VTXG_CRC_WIDTH 16
+hipError_t vtxg_crc32(const uint8_t* comp, const vtxg_block* blocks, uint32_t n_blocks, const uint8_t* data, uint32_t* err, uint32_t* crc_out,
+                      uint32_t b_base, int width, hipStream_t s);
 hipError_t vtxg_chain(const uint8_t* data, uint64_t total, const uint64_t* seeds, uint32_t n_seeds, uint64_t end_upos, uint32_t* cnt,
                       const uint32_t* off, uint64_t* rec_upos, uint32_t* err, hipStream_t s);
 hipError_t vtxg_chain_segments(const uint8_t* data, const uint64_t* seeds, uint32_t n_seeds, const uint32_t* seed_seg, const vtxg_segment* segs,

@@ -25,6 +25,7 @@
 #include "vtx_device.h"
 #include "vtx_ingest.h"
 #include "vtx_inflate_core.h"
+#include "vtx_crc32_core.h"
 #include "vtx_f64_text.h"
 
 namespace {
@@ -52,6 +53,41 @@ __global__ __launch_bounds__(64) void bgzf_inflate_kernel(const uint8_t* __restr
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 __device__ __forceinline__ uint32_t ld16(const uint8_t* p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
 __device__ __forceinline__ uint64_t ld64(const uint8_t* p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// BGZF CRC32: one wavefront per block, four per workgroup, grid-stride over the blocks.  The workgroup fills the W slicing tables in
+// LDS once (W KiB); a lane then needs W aligned bytes and W table reads per step, and a load instruction of the wavefront covers 64 W
+// consecutive bytes (vtx_crc32_core.h has the cut of a block and why the pieces are interleaved).  The expected value is the four
+// bytes behind the block's payload in the compressed buffer (comp == nullptr: vtx_debug_crc32, nothing to compare with).  Blocks of
+// an ingest in which some block did not inflate are not looked at: err[1] then names that block, and its message comes first.
+// `data` is 16-byte aligned (a device allocation's start) and readable from (uoff & ~15) on.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <int W>
+__global__ __launch_bounds__(256) void bgzf_crc32_kernel(const uint8_t* __restrict__ comp, const vtxg_block* __restrict__ blocks, uint32_t n_blocks,
+                                                         const uint8_t* __restrict__ data, uint32_t* __restrict__ err,
+                                                         uint32_t* __restrict__ crc_out, uint32_t b_base) {
+    __shared__ uint32_t s_tab[vtxc::TABLE_WORDS(W)];
+    if (comp && (err[0] & 0x1ffu)) return;                  // (written by the inflate kernel in front of this one: the same for every lane)
+    for (uint32_t i = threadIdx.x; i < (uint32_t)vtxc::TABLE_WORDS(W); i += 256) s_tab[i] = vtxc::table_entry<W>(i);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6); b < n_blocks; b += gridDim.x * 4) {
+        const vtxg_block B = blocks[b];
+        const uint64_t s = B.uoff, e = B.uoff + B.isize;
+        const vtxc::Cut c = vtxc::cut_block<W>(s, e);
+        uint32_t v = vtxc::lane_pieces<W>(data, c, lane, s_tab);
+        VTXI_UNROLL
+        for (int k = 0; k < 6; ++k) {
+            const uint32_t partner = __shfl_xor(v, 1 << k);
+            if (lane & (1u << k)) v = vtxc::lane_join<W>(partner, v, k);
+        }
+        const uint32_t crc = vtxc::finish_block<W>(__shfl(v, 63), data, c, s, e);      // (wavefront-uniform: every lane holds it)
+        if (lane == 0) {
+            if (crc_out) crc_out[b] = crc;
+            if (comp && crc != ld32(comp + B.coff + B.clen)) { atomicMin(&err[1], b_base + b); atomicOr(&err[0], VTXG_ERR_CRC); }
+        }
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Record boundaries.  Seed i (a record start the .bai names) .. seed i + 1: one lane hops from block_size to block_size.
@@ -437,6 +473,21 @@ hipError_t vtxg_inflate(const uint8_t* comp, const vtxg_block* blocks, uint32_t 
     if (!n_blocks) return hipSuccess;
     const uint32_t wgs = std::min<uint32_t>((n_blocks + 63) / 64, 256u * 5u);
     hipLaunchKernelGGL(bgzf_inflate_kernel, dim3(wgs), dim3(64), 0, s, comp, blocks, n_blocks, out, err, status, b_base);
+    return hipGetLastError();
+}
+
+hipError_t vtxg_crc32(const uint8_t* comp, const vtxg_block* blocks, uint32_t n_blocks, const uint8_t* data, uint32_t* err, uint32_t* crc_out,
+                      uint32_t b_base, int width, hipStream_t s) {
+    if (!n_blocks) return hipSuccess;
+    if ((uintptr_t)data & 15u) return hipErrorInvalidValue;
+    // workgroups: all blocks at once up to what 256 CUs hold (the tables cost W KiB of a CU's 160: eight workgroups of four wavefronts fit beside them)
+    const dim3 wgs(std::min<uint32_t>((n_blocks + 3) / 4, 256u * 8u)), wg(256);
+    switch (width) {
+    case 4: hipLaunchKernelGGL(bgzf_crc32_kernel<4>, wgs, wg, 0, s, comp, blocks, n_blocks, data, err, crc_out, b_base); break;
+    case 8: hipLaunchKernelGGL(bgzf_crc32_kernel<8>, wgs, wg, 0, s, comp, blocks, n_blocks, data, err, crc_out, b_base); break;
+    case 16: hipLaunchKernelGGL(bgzf_crc32_kernel<16>, wgs, wg, 0, s, comp, blocks, n_blocks, data, err, crc_out, b_base); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -37,10 +37,11 @@ SYMBOLS = (
     "vtx_comm_id", "vtx_comm_init", "vtx_gather_coo", "vtx_fetch_gathered", "vtx_gather_abort", "vtx_gather_plan",
     "vtx_set_debug", "vtx_fetch_stage", "vtx_debug_bands", "vtx_debug_tables", "vtx_set_read_format",
     "vtx_submit_bam", "vtx_submit_bam_segments", "vtx_debug_ingest", "vtx_debug_inflate", "vtx_comm_ranks", "vtx_write_mtx", "vtx_prefetch_file",
+    "vtx_last_crc_ms",
 )
 # (entry points with a digit in their name: tests/test_abi.py finds the header's declarations with [a-z_]+ and compares them with SYMBOLS,
 # so these are listed — and checked against the header and every build of the library, tests/test_abi_f64.py — on their own)
-SYMBOLS_ALNUM = ("vtx_write_mtx_f64",)
+SYMBOLS_ALNUM = ("vtx_write_mtx_f64", "vtx_debug_crc32")
 
 
 class VtxError(RuntimeError):
@@ -134,6 +135,10 @@ def load(variant=None):
     L.vtx_debug_inflate.argtypes = [ctxp, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
     L.vtx_debug_ingest.restype = C.c_int
     L.vtx_debug_ingest.argtypes = [ctxp, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.vtx_debug_crc32.restype = C.c_int
+    L.vtx_debug_crc32.argtypes = [ctxp, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.vtx_last_crc_ms.restype = C.c_int
+    L.vtx_last_crc_ms.argtypes = [ctxp, C.POINTER(C.c_float)]
     _libs[path] = L
     return L
 
@@ -259,6 +264,22 @@ class Context:
                                               out.ctypes.data, total, status.ctypes.data))
         offs = np.concatenate([[0], np.cumsum(blk["isize"])]).astype(np.int64)
         return status[:len(blk)], [bytes(out[offs[i]:offs[i + 1]]) for i in range(len(blk))]
+
+    def debug_crc32(self, data: bytes, offsets) -> np.ndarray:
+        """bgzf_crc32_kernel on byte ranges of ``data``: range i = data[offsets[i]:offsets[i + 1]] (ascending, each at most 64 KiB).
+        -> uint32 array of their CRC-32s (zlib.crc32's values)."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(off) - 1
+        buf = np.frombuffer(data, np.uint8) if len(data) else np.zeros(1, np.uint8)
+        out = np.zeros(max(n, 1), np.uint32)
+        self._check(self._L.vtx_debug_crc32(self._h, buf.ctypes.data, len(data), off.ctypes.data, n, out.ctypes.data))
+        return out[:n]
+
+    def crc_ms(self) -> float:
+        """Device time of the last CRC32 check (submit_bam / submit_bam_segments / debug_crc32), milliseconds."""
+        ms = C.c_float(0)
+        self._check(self._L.vtx_last_crc_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def debug_ingest(self, what: int, dtype=np.uint8) -> np.ndarray:
         """An intermediate array of the last submit_bam (abi.INGEST_*)."""
