@@ -140,6 +140,14 @@ int vtxh_read_format(const vtxh_pack* p);
  * decoder declined (the packer then gives the block to zlib).  Nothing is written outside [out, out + out_len).               */
 int vtxh_test_inflate(const uint8_t* in, uint64_t in_len, uint8_t* out, uint64_t out_len);
 
+#ifdef VTX_DEVTOOLS
+/* Test hooks of the developer build only: the packer's aux lookup (rec.aux(tag) matched against Aux::String, src/main.rs:742-748;
+ * 1 and the value's offset / length when the tag's first occurrence is a Z string, else 0) and its CIGAR walk (1 Some, 0 None,
+ * -1 Err) on raw bytes.                                                                                                        */
+int vtxh_test_aux_string(const uint8_t* aux, uint64_t n, const char* tag, uint64_t* off, uint64_t* len);
+int vtxh_test_cigar_read_pos(const uint8_t* cig, uint32_t n_ops, int64_t pos, int64_t ref_pos);
+#endif
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ def _bgzf_block(data: bytes) -> bytes:
 
 def parse_cigar(s: str) -> list:
     out, num = [], ""
-    for ch in s:
+    for ch in ("" if s == "*" else s):
         if ch.isdigit():
             num += ch
         else:
@@ -34,33 +34,52 @@ def parse_cigar(s: str) -> list:
     return out
 
 
+_INT_FMT = {"c": "<b", "C": "<B", "s": "<h", "S": "<H", "i": "<i", "I": "<I"}
+
+
+def aux_bytes(tags) -> bytes:
+    """tags: iterable of (tag, type, value) with type 'Z' / 'H' (bytes/str), 'A' (char), 'c' 'C' 's' 'S' 'i' 'I' (int), 'd' / 'f'
+    (float), 'B' ((subtype, values), subtypes c C s S i I f) or 'raw' (the tag is ignored; the value's bytes go in as they are)."""
+    aux = b""
+    for tag, ty, val in tags:
+        if ty == "raw":
+            aux += bytes(val)
+            continue
+        t = tag.encode() if isinstance(tag, str) else tag
+        if ty in "ZH":
+            v = val.encode() if isinstance(val, str) else val
+            aux += t + ty.encode() + v + b"\x00"
+        elif ty in _INT_FMT:
+            aux += t + ty.encode() + struct.pack(_INT_FMT[ty], val)
+        elif ty == "A":
+            aux += t + b"A" + (val.encode() if isinstance(val, str) else val)
+        elif ty == "d":
+            aux += t + b"d" + struct.pack("<d", val)
+        elif ty == "f":
+            aux += t + b"f" + struct.pack("<f", val)
+        elif ty == "B":         # val = (subtype char, list of values)
+            sub, vals = val
+            fmt = "<f" if sub == "f" else _INT_FMT[sub]
+            aux += t + b"B" + sub.encode() + struct.pack("<i", len(vals)) + b"".join(struct.pack(fmt, v) for v in vals)
+        else:
+            raise ValueError("aux type %r" % ty)
+    return aux
+
+
 def record(tid, pos, qname, seq, cigar, flag=0, mapq=60, tags=()):
-    """tags: iterable of (tag, type, value) with type 'Z' (bytes/str), 'i' (int), 'A' (char), 'd' / 'f' (float) or
-    'B' ((subtype, [ints]))."""
-    qn = qname.encode() + b"\x00"
+    """qname: str or bytes of any length up to 254 (l_read_name counts the NUL: 1 .. 255); seq: the bases, "*" or "" for none
+    (l_seq 0); cigar: text or a list of BAM uint32 ops; tags: see aux_bytes."""
+    qn = (qname.encode() if isinstance(qname, str) else bytes(qname)) + b"\x00"
+    assert 1 <= len(qn) <= 255
     cig = parse_cigar(cigar) if isinstance(cigar, str) else list(cigar)
+    if seq == "*":
+        seq = ""
     l_seq = len(seq)
     packed = bytearray((l_seq + 1) // 2)
     for i, ch in enumerate(seq):
         code = _NT16.get(ch, 15)
         packed[i >> 1] |= code << (4 if i % 2 == 0 else 0)
-    aux = b""
-    for tag, ty, val in tags:
-        if ty == "Z":
-            v = val.encode() if isinstance(val, str) else val
-            aux += tag.encode() + b"Z" + v + b"\x00"
-        elif ty == "i":
-            aux += tag.encode() + b"i" + struct.pack("<i", val)
-        elif ty == "A":
-            aux += tag.encode() + b"A" + val.encode()
-        elif ty == "d":
-            aux += tag.encode() + b"d" + struct.pack("<d", val)
-        elif ty == "f":
-            aux += tag.encode() + b"f" + struct.pack("<f", val)
-        elif ty == "B":         # val = (subtype char, list of ints)
-            sub, vals = val
-            aux += tag.encode() + b"B" + sub.encode() + struct.pack("<i", len(vals)) + b"".join(
-                struct.pack({"c": "<b", "C": "<B", "s": "<h", "S": "<H", "i": "<i", "I": "<I"}[sub], v) for v in vals)
+    aux = aux_bytes(tags)
     body = struct.pack("<iiBBHHHiiii", tid, pos, len(qn), mapq, 4680, len(cig), flag, l_seq, -1, -1, 0)
     body += qn + b"".join(struct.pack("<I", c) for c in cig) + bytes(packed) + b"\xff" * l_seq + aux
     return struct.pack("<i", len(body)) + body

@@ -132,7 +132,9 @@ def read_bam(path: str) -> Bam:
         seq = _NT16_PAIR[packed].reshape(-1)[:l_seq].tobytes()
         p += (l_seq + 1) // 2 + l_seq
         aux = d[p:o + 4 + bs]
-        rlen = sum(int(c >> 4) for c in cigar if int(c & 15) in _REF_CONSUME)
+        # htslib bam_endpos: an unmapped record (BAM_FUNMAP) ends at pos + 1 whatever its CIGAR says; so does one without a
+        # reference-consuming op
+        rlen = 0 if flag & FLAG_UNMAP else sum(int(c >> 4) for c in cigar if int(c & 15) in _REF_CONSUME)
         end = pos + (rlen if rlen > 0 else 1)
         bam.recs.append(BamRec(tid, pos, mapq, flag, cigar, seq, qname, aux, end))
         o += 4 + bs

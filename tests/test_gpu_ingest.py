@@ -215,8 +215,10 @@ def test_reference_fixture_through_the_device_ingest(umi):
 @pytest.mark.parametrize("opts", [dict(), dict(mapq=30), dict(primary_only=True, no_duplicates=True), dict(use_umi=True, mapq=10),
                                   dict(bam_tag="CR"), dict(padding=30)])
 def test_authored_bam_with_every_filter(tmp_path, opts):
-    """tests/test_host.py's authored BAM over test_dna.fa — indels, soft / hard clips, N skips, secondary / supplementary / duplicate
-    flags, missing and non-Z tags, reads that overlap several loci — with each filter option: the device's pairs ARE the host's."""
+    """tests/test_host.py's authored BAM over test_dna.fa — CIGARs of M, I, D and a leading S (make_dna_bam emits no hard clip, no N
+    skip and no P, = or X: those are tests/test_gpu_bam_grammar.py's), secondary / supplementary / duplicate flags, missing and non-Z
+    (i) barcode tags, d / f / B:S fields in front of the barcode, reads that overlap several loci — with each filter option: the
+    device's pairs ARE the host's."""
     from test_host import make_dna_bam
     bam = make_dna_bam(tmp_path, seed=3, n_reads=2500)
     inputs = dict(vcf=os.path.join(G, "test_dna.vcf"), bam=bam, fasta=os.path.join(G, "test_dna.fa"),

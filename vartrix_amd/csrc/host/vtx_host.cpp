@@ -522,6 +522,7 @@ int aux_string(const unsigned char* aux, size_t n, const char* tag, const unsign
         case 'Z': case 'H': {
             size_t e = o;
             while (e < n && aux[e]) ++e;
+            if (e >= n) return 0;                     // no NUL inside the record: htslib's bam_aux_get gives NULL on corrupt aux data
             size = e - o + 1;
             is_z = ty == 'Z';
             break;
@@ -530,7 +531,8 @@ int aux_string(const unsigned char* aux, size_t n, const char* tag, const unsign
             if (o + 5 > n) return 0;
             char sub = (char)aux[o];
             uint32_t cnt = rd32(aux + o + 1);
-            size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+            size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+            if (!es) return 0;                        // (an unknown subtype has no size: corrupt, as for htslib's skip_aux)
             size = 5 + (size_t)cnt * es;
             break;
         }
@@ -1924,5 +1926,16 @@ int vtxh_test_inflate(const uint8_t* in, uint64_t in_len, uint8_t* out, uint64_t
     vtxinf::Tables T;
     return vtxinf::inflate_raw(in, (size_t)in_len, out, (size_t)out_len, T) ? 1 : 0;
 }
+
+#ifdef VTX_DEVTOOLS
+// Test hooks (libvtxhost_dev.so only): the packer's own aux lookup and CIGAR walk on raw bytes, for tests/test_scan_core.py.
+int vtxh_test_aux_string(const uint8_t* aux, uint64_t n, const char* tag, uint64_t* off, uint64_t* len) {
+    const unsigned char* val = nullptr; size_t vlen = 0;
+    if (!aux_string(aux, (size_t)n, tag, &val, &vlen)) return 0;
+    *off = (uint64_t)(val - aux); *len = vlen;
+    return 1;
+}
+int vtxh_test_cigar_read_pos(const uint8_t* cig, uint32_t n_ops, int64_t pos, int64_t ref_pos) { return cigar_read_pos(cig, n_ops, pos, ref_pos); }
+#endif
 
 }  // extern "C"

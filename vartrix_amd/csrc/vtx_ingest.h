@@ -6,11 +6,12 @@
 #include <stdint.h>
 
 #include "../../include/vtx.h"
+#include "vtx_scan_core.h"
 
 // a BGZF block on the device: offsets into the uploaded compressed range / the inflated buffer
 struct vtxg_block { uint64_t coff, uoff; uint32_t clen, isize; };
 // the read filters of evaluate_alns that need no dictionary (src/main.rs:833-864) + the tag to look for (--bam-tag, :126-129)
-struct vtxg_filter { uint32_t n_ref, min_mapq, primary_only, no_duplicates, bam_tag; };
+typedef vtxs::Filter vtxg_filter;      // { n_ref, min_mapq, primary_only, no_duplicates, bam_tag }: vtx_scan_core.h, where the scan reads it
 // per BAM record with at least one surviving pair: where its tags lie (relative to the record body) and their lengths
 struct vtxg_recinfo { uint32_t bc_rel, umi_rel, lens; };
 

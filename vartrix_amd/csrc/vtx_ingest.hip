@@ -27,6 +27,7 @@
 #include "vtx_inflate_core.h"
 #include "vtx_crc32_core.h"
 #include "vtx_f64_text.h"
+#include "vtx_scan_core.h"
 
 namespace {
 
@@ -50,9 +51,8 @@ __global__ __launch_bounds__(64) void bgzf_inflate_kernel(const uint8_t* __restr
     }
 }
 
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint32_t ld16(const uint8_t* p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
-__device__ __forceinline__ uint64_t ld64(const uint8_t* p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
+using vtxs::ld32;
+using vtxs::ld64;
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // BGZF CRC32: one wavefront per block, four per workgroup, grid-stride over the blocks.  The workgroup fills the W slicing tables in
@@ -160,138 +160,6 @@ __global__ __launch_bounds__(64) void bam_chain_seg_kernel(const uint8_t* __rest
     if (!off) cnt[i] = k;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// rust-htslib 0.36 CigarStringView::read_pos(ref_pos, include_softclips = false, include_dels = true) as called from
-// useful_alignment (src/main.rs:796): 1 = Some, 0 = None, -1 = Err.  Same restatement as host/vtx_host.cpp: cigar_read_pos and
-// oracle/vtx_oracle.c: vtxo_cigar_read_pos.
-// ---------------------------------------------------------------------------------------------------------------------------
-__device__ int cigar_read_pos(const uint8_t* cig, uint32_t n_ops, int64_t pos, int64_t ref_pos) {
-    int64_t rpos = pos;
-    uint32_t j = 0;
-    for (uint32_t i = 0; i < n_ops; ++i) {
-        const uint32_t op = ld32(cig + 4 * i) & 15u;
-        if (op == 0 || op == 7 || op == 8 || op == 1) { j = i; break; }
-        if (op == 4) { j = i; break; }
-        if (op == 2 || op == 3) return -1;
-        if (op == 5 && i > 0 && i + 1 < n_ops) return -1;
-        if ((op == 6 || op == 5) && i + 1 == n_ops) return 0;
-    }
-    while (rpos <= ref_pos && j < n_ops) {
-        const uint32_t c = ld32(cig + 4 * j), op = c & 15u;
-        const int64_t l = c >> 4;
-        const bool contains = rpos <= ref_pos && rpos + l > ref_pos;
-        switch (op) {
-        case 0: case 7: case 8: if (contains) return 1; rpos += l; ++j; break;
-        case 4: ++j; break;
-        case 2: if (contains) return 1; rpos += l; ++j; break;
-        case 3: rpos += l; ++j; break;
-        case 1: case 6: ++j; break;
-        case 5: if (j + 1 < n_ops) return -1; return 0;
-        default: return -1;
-        }
-    }
-    return 0;
-}
-// useful_alignment, src/main.rs:790-806 (probes start..=end, inclusive; an invalid CIGAR drops the read, :799-802)
-__device__ bool useful_alignment(const uint8_t* cig, uint32_t n_ops, int64_t pos, int64_t start, int64_t end) {
-    for (int64_t i = start; i <= end; ++i) {
-        const int r = cigar_read_pos(cig, n_ops, pos, i);
-        if (r == 1) return true;
-        if (r < 0) return false;
-    }
-    return false;
-}
-// rec.aux(tag) matched against Aux::String (src/main.rs:742-748, :753-755): type 'Z' only.  Returns the value's offset from aux
-// (0xffffffff: no such Z tag) and *len.
-__device__ uint32_t aux_string(const uint8_t* aux, uint32_t n, uint32_t tag2, uint32_t* len) {
-    uint32_t o = 0;
-    while (o + 3 <= n) {
-        const uint32_t t2 = ld16(aux + o);
-        const uint32_t ty = aux[o + 2];
-        o += 3;
-        uint32_t size;
-        bool is_z = false;
-        switch (ty) {
-        case 'A': case 'c': case 'C': size = 1; break;
-        case 's': case 'S': size = 2; break;
-        case 'i': case 'I': case 'f': size = 4; break;
-        case 'd': size = 8; break;
-        case 'Z': case 'H': {
-            uint32_t e = o;
-            while (e < n && aux[e]) ++e;
-            size = e - o + 1;
-            is_z = ty == 'Z';
-            break;
-        }
-        case 'B': {
-            if (o + 5 > n) return 0xffffffffu;
-            const uint32_t sub = aux[o];
-            const uint32_t cnt = ld32(aux + o + 1);
-            const uint32_t es = (sub == 'c' || sub == 'C') ? 1u : (sub == 's' || sub == 'S') ? 2u : 4u;
-            const uint64_t sz = 5ull + (uint64_t)cnt * es;
-            if (sz > n) return 0xffffffffu;
-            size = (uint32_t)sz;
-            break;
-        }
-        default: return 0xffffffffu;
-        }
-        if (t2 == tag2) {
-            if (!is_z) return 0xffffffffu;
-            *len = size - 1;
-            return o;
-        }
-        o += size;
-    }
-    return 0xffffffffu;
-}
-
-struct RecView {
-    const uint8_t* r;          // behind block_size
-    uint32_t bs;
-    int32_t tid;
-    int64_t pos, endpos;
-    uint32_t mapq, flag, n_cig, l_seq;
-    const uint8_t* cig;
-    const uint8_t* sq;
-    const uint8_t* aux;
-    bool malformed;
-};
-__device__ __forceinline__ RecView view_record(const uint8_t* data, uint64_t p) {
-    RecView v;
-    v.bs = ld32(data + p);
-    v.r = data + p + 4;
-    v.tid = (int32_t)ld32(v.r);
-    v.pos = (int32_t)ld32(v.r + 4);
-    const uint32_t w2 = ld32(v.r + 8), w3 = ld32(v.r + 12);
-    const uint32_t l_rn = w2 & 0xffu;
-    v.mapq = (w2 >> 8) & 0xffu;
-    v.n_cig = w3 & 0xffffu;
-    v.flag = w3 >> 16;
-    v.l_seq = ld32(v.r + 16);
-    v.cig = v.r + 32 + l_rn;
-    v.sq = v.cig + 4 * (size_t)v.n_cig;
-    const uint64_t aux_off = 32ull + l_rn + 4ull * v.n_cig + ((uint64_t)v.l_seq + 1) / 2 + v.l_seq;
-    v.malformed = aux_off > v.bs;
-    v.aux = v.r + (v.malformed ? v.bs : aux_off);
-    int64_t rlen = 0;                                     // bam_endpos: unmapped or no reference-consuming op => pos + 1
-    if (!v.malformed && !(v.flag & 0x4u))
-        for (uint32_t k = 0; k < v.n_cig; ++k) {
-            const uint32_t c = ld32(v.cig + 4 * k), op = c & 15u;
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += c >> 4;
-        }
-    v.endpos = v.pos + (rlen > 0 ? rlen : 1);
-    return v;
-}
-
-// hi = first interval of the contig with start >= endpos (the loci that can overlap lie below it)
-__device__ __forceinline__ uint32_t first_not_below(const int32_t* __restrict__ iv_start, uint32_t lo, uint32_t hi, int64_t endpos) {
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if ((int64_t)iv_start[mid] < endpos) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // One lane per BAM record.  EMIT = false: counts (pairs that survive, metrics, the bytes to keep); EMIT = true: the raw records.
 template <bool EMIT>
 __global__ __launch_bounds__(256) void bam_scan_kernel(const uint8_t* __restrict__ data, const uint64_t* __restrict__ rec_upos,
@@ -313,57 +181,30 @@ __global__ __launch_bounds__(256) void bam_scan_kernel(const uint8_t* __restrict
     for (uint32_t rix = blockIdx.x * 256 + threadIdx.x; rix < n_rec; rix += gridDim.x * 256) {
         if (EMIT && n_hit[rix] == 0) continue;
         const uint64_t p = rec_upos[rix];
-        const RecView v = view_record(data, p);
-        uint32_t hits = 0, m_reads = 0, m_mapq = 0, m_prim = 0, m_dup = 0, m_useful = 0, m_nobc = 0;
-        uint32_t bc_rel = 0, umi_rel = 0, bc_len = VTX_TAG_MISSING, umi_len = VTX_TAG_MISSING;
-        bool tags_ready = false;
+        const vtxs::RecView v = vtxs::view_record(data, p);
+        vtxs::Verdict V;
         uint32_t h_base = 0, roff = 0, toff = 0;
         if (EMIT) {
             h_base = rix ? hit_scan[rix - 1] : 0u;
             roff = rix ? read_scan[rix - 1] : 0u;
             toff = rix ? tag_scan[rix - 1] : 0u;
             const vtxg_recinfo I = info[rix];
-            bc_rel = I.bc_rel; umi_rel = I.umi_rel; bc_len = I.lens & 0xffffu; umi_len = I.lens >> 16;
+            V.bc_rel = I.bc_rel; V.umi_rel = I.umi_rel; V.bc_len = I.lens & 0xffffu; V.umi_len = I.lens >> 16;
         }
         if (v.malformed) { if (!EMIT) atomicOr(&err[0], VTXG_ERR_RECORD); }
-        else if (v.tid >= 0 && (uint32_t)v.tid < f.n_ref) {
-            const uint32_t i0 = tid_begin[v.tid], i1 = tid_begin[v.tid + 1];
-            if (i1 > i0) {
-                const int64_t span = tid_span[v.tid];
-                uint32_t k = first_not_below(iv_start, i0, i1, v.endpos);
-                // loci of this contig with start < endpos && end > pos (htslib's overlap on [start, end), src/main.rs:822-826)
-                while (k-- > i0) {
-                    if ((int64_t)iv_start[k] + span <= v.pos) break;
-                    if ((int64_t)iv_end[k] <= v.pos) continue;
-                    ++m_reads;                                                              // :831
-                    if (v.mapq < f.min_mapq) { ++m_mapq; continue; }                        // :833
-                    if (f.primary_only && (v.flag & (0x100u | 0x800u))) { ++m_prim; continue; }   // :841
-                    if (f.no_duplicates && (v.flag & 0x400u)) { ++m_dup; continue; }        // :849
-                    if (!useful_alignment(v.cig, v.n_cig, v.pos, iv_start[k], iv_end[k])) { ++m_useful; continue; }   // :857
-                    if (!EMIT && !tags_ready) {
-                        tags_ready = true;
-                        const uint32_t n_aux = (uint32_t)(v.r + v.bs - v.aux);
-                        uint32_t len = 0;
-                        uint32_t o = aux_string(v.aux, n_aux, f.bam_tag, &len);            // :867 (the in-list test: vtx_prep.hip)
-                        if (o != 0xffffffffu && len < VTX_TAG_MISSING) {
-                            bc_rel = (uint32_t)(v.aux - v.r) + o; bc_len = len;
-                            o = aux_string(v.aux, n_aux, (uint32_t)'U' | ((uint32_t)'B' << 8), &len);   // :879 (the test itself: vtx_prep.hip)
-                            if (o != 0xffffffffu && len < VTX_TAG_MISSING) { umi_rel = (uint32_t)(v.aux - v.r) + o; umi_len = len; }
-                        }
-                    }
-                    if (bc_len == VTX_TAG_MISSING) { ++m_nobc; continue; }
-                    if (EMIT) {
-                        vtx_raw_record rr;
-                        rr.read_off = roff; rr.read_len = v.l_seq;
-                        rr.bc_off = toff; rr.umi_off = umi_len != VTX_TAG_MISSING ? toff + bc_len : 0u;
-                        rr.bc_len = (uint16_t)bc_len; rr.umi_len = (uint16_t)umi_len;
-                        raw[h_base + hits] = rr;
-                        raw_locus[h_base + hits] = iv_locus[k];
-                    }
-                    ++hits;
+        else
+            vtxs::scan_pairs<!EMIT>(v, f, iv_start, iv_end, tid_begin, tid_span, V, [&](uint32_t k, uint32_t outcome, uint32_t hit) {
+                if (EMIT && outcome == vtxs::PAIR_KEPT) {
+                    vtx_raw_record rr;
+                    rr.read_off = roff; rr.read_len = v.l_seq;
+                    rr.bc_off = toff; rr.umi_off = V.umi_len != VTX_TAG_MISSING ? toff + V.bc_len : 0u;
+                    rr.bc_len = (uint16_t)V.bc_len; rr.umi_len = (uint16_t)V.umi_len;
+                    raw[h_base + hit] = rr;
+                    raw_locus[h_base + hit] = iv_locus[k];
                 }
-            }
-        }
+            });
+        const uint32_t hits = V.hits, bc_len = V.bc_len, umi_len = V.umi_len, bc_rel = V.bc_rel, umi_rel = V.umi_rel;
+        const uint32_t m_reads = V.reads, m_mapq = V.low_mapq, m_prim = V.non_primary, m_dup = V.duplicate, m_useful = V.not_useful, m_nobc = V.no_barcode;
         if (!EMIT) {
             n_hit[rix] = hits;
             read_sz[rix] = hits ? (v.l_seq + 1u) & ~1u : 0u;           // bases; every read starts at an even one (two per byte)

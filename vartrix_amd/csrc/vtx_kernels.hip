@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "vtx_device.h"
+#include "vtx_scan_core.h"
 
 typedef short v2s __attribute__((ext_vector_type(2)));
 typedef unsigned short v2u __attribute__((ext_vector_type(2)));
@@ -379,8 +380,7 @@ extern "C" hipError_t vtxk_emit_coo(const uint32_t* cell_cnt, uint32_t n_grp, in
 __global__ __launch_bounds__(256) void unpack_nibbles_kernel(const uint8_t* __restrict__ in, uint64_t n_in, uint8_t* __restrict__ out) {
     const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16u;
     if (i >= n_in) return;
-    const uint64_t lut_lo = 0x565352474d43413dull, lut_hi = 0x4e42444b48595754ull;      // "=ACMGRSV", "TWYHKDBN" (little endian)
-    auto dec = [&](uint32_t nib) -> uint32_t { return (uint32_t)(((nib & 8u) ? lut_hi : lut_lo) >> (8u * (nib & 7u))) & 0xffu; };
+    auto dec = [&](uint32_t nib) -> uint32_t { return vtxs::nt16_char(nib); };      // (vtx_scan_core.h: the 16 codes as two 64-bit constants)
     if (i + 16 <= n_in) {
         uint4 v;
         __builtin_memcpy(&v, in + i, 16);
