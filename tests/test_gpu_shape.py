@@ -16,30 +16,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-ROUND3_STAGES = (abi.STAGE_UNKNOWN, abi.STAGE_RUN_DP, abi.STAGE_GENERAL_DP)      # (0 = decided by band_run_kernel's certificate)
-
-
-def long_loci_batch(n, seed, reads=64, max_indel=90):
-    """n loci whose REF or ALT haplotype exceeds 255 bases: indels of 56 .. max_indel bases at padding 100."""
-    spec = synth.SynthSpec(n_loci=4 * n + 8, n_barcodes=5000, reads_per_locus=reads, indel_frac=1.0, max_indel=max_indel, seed=seed)
-    b = synth.make_batch(spec)
-    long_ = np.nonzero(np.maximum(b.loci["ref_len"], b.loci["alt_len"]) > 255)[0][:n]
-    assert len(long_) == n
-    return [b.slice_loci(int(l), int(l) + 1) for l in long_]
-
-
-def mixed_batch(n_loci, positions, reads=64, seed=11):
-    base = synth.make_batch(synth.SynthSpec(n_loci=n_loci, n_barcodes=5000, reads_per_locus=reads, seed=seed))
-    longs = long_loci_batch(len(positions), seed + 1, reads)
-    parts, prev = [], 0
-    for pos, lb in zip(positions, longs):
-        parts += [base.slice_loci(prev, pos), lb]
-        prev = pos
-    parts.append(base.slice_loci(prev, n_loci))
-    out = PackedBatch.concat(parts)
-    is_long = np.maximum(out.loci["ref_len"], out.loci["alt_len"]) > 255
-    assert int(is_long.sum()) == len(positions)
-    return out, is_long
+from reuse_util import ROUND3_STAGES, long_loci_batch, mixed_batch  # noqa: E402  (the generators live in tests/reuse_util.py, shared with tests/test_gpu_context_reuse.py)
 
 
 def run_banded(batch, n_barcodes=5000):

@@ -1557,6 +1557,11 @@ int vtx_run(vtx_ctx* c) {
     const uint32_t nr = c->n_records;
     c->ran = false;
     c->fast_overflow = 0;
+    // the banded stages ADD their times and task counts per pass (band_pass below): zeroed here, for every run — a run that does not
+    // enter them (an empty batch, a batch of slow records only) must not report the previous batch's
+    c->timing.diag_ms = c->timing.check_ms = c->timing.sweep_ms = 0;
+    c->timing.diag_left = c->timing.checked_tasks = c->timing.swept_tasks = c->timing.resweep_tasks = 0;
+    c->timing.diag2_tasks = c->timing.diag2_scored = c->timing.diag2_streamed = 0;
     // test / audit hooks (vtx_set_debug): poison the score arrays so that a stage that fails to write a task's score cannot hide
     // behind the previous run's value; one byte per task saying which stage decided it (vtx_fetch_stage)
     uint8_t* stage = nullptr;
@@ -2217,10 +2222,6 @@ int vtx_run(vtx_ctx* c) {
             if (getenv("VTX_DEBUG")) fprintf(stderr, "[vtx] banded: %llu tasks, %u overflowed band_run_kernel, %u bounded by the pending kernel, %u hard\n", (unsigned long long)n_tasks, fast_overflow, pending_total, hard_total);
             return VTX_OK;
         };
-        c->fast_overflow = 0;
-        c->timing.diag_ms = c->timing.check_ms = c->timing.sweep_ms = 0;
-        c->timing.diag_left = c->timing.checked_tasks = c->timing.swept_tasks = c->timing.resweep_tasks = 0;
-        c->timing.diag2_tasks = c->timing.diag2_scored = c->timing.diag2_streamed = 0;
         // Shape per task (round 6).  A haplotype above 255 bases (a long deletion or insertion, a larger --padding) does not fit the
         // two-byte match entries of band_diag_kernel<., uint16_t> nor band_sweep_kernel's 256 columns; ONE such locus used to put the
         // whole batch on round 3's path (config 3: 18.9 instead of 15.9 ms; repeat-rich loci lose the sweep and the second stage, 2x).
