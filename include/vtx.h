@@ -113,7 +113,8 @@ typedef struct vtx_locus {
  * (src/main.rs:923-930) before alignment.  Within a locus, records MUST be
  * ordered by (cell_index, umi_id) ascending — the reference's stable sort by
  * cell_index (src/main.rs:932) followed by the per-cell UMI HashMap
- * (src/main.rs:1047-1057), whose iteration order never reaches the output.   */
+ * (src/main.rs:1047-1057), whose iteration order never reaches the output.
+ * Without cfg.use_umi the order is by cell_index alone: umi_id is not read.   */
 typedef struct vtx_record {
     uint32_t read_off;   /* read bases in read_arena (rec.seq().as_bytes(), :896) */
     uint32_t read_len;

@@ -900,7 +900,7 @@ int vtx_submit(vtx_ctx* c, const vtx_batch* b) {
     if (nr) {
         HIP_TRY(c, vtxk_prep_rec_locus(c->d_loci.as<vtx_locus>(), nl, c->d_rec_locus.as<uint32_t>(), s));
         HIP_TRY(c, vtxk_prep_check(c->d_records.as<vtx_record>(), nr, c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(),
-                                   b->read_bytes, kMaxReadLen | (nibbles ? 0x80000000u : 0u), c->cfg.n_barcodes, kNumShapes, c->d_shape.as<uint8_t>(),
+                                   b->read_bytes, kMaxReadLen | (nibbles ? 0x80000000u : 0u), c->cfg.n_barcodes, c->cfg.use_umi ? 1 : 0, kNumShapes, c->d_shape.as<uint8_t>(),
                                    c->d_seq.as<uint32_t>(), d_shape_cnt, d_counters, s));
         // work lists per kernel shape: stable sort of the record numbers by shape
         HIP_TRY(c, vtxk_prep_sort_u8(c->d_shape.as<uint8_t>(), c->d_shape2.as<uint8_t>(), c->d_seq.as<uint32_t>(),
@@ -920,7 +920,7 @@ int vtx_submit(vtx_ctx* c, const vtx_batch* b) {
         if (code == 2) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit: record %u: read length %u above %u", r, R.read_len, kMaxReadLen);
         if (code == 3) return fail(c, VTX_E_INVAL, "vtx_submit: record %u: cell_index %u >= n_barcodes %u", r, R.cell_index, c->cfg.n_barcodes);
         if (code == 5) return fail(c, VTX_E_INVAL, "vtx_submit: record %u: read_off %u is odd (VTX_READS_NIBBLES: every read starts at an even base)", r, R.read_off);
-        return fail(c, VTX_E_INVAL, "vtx_submit: record %u: not sorted by (cell_index, umi_id) within its locus", r);
+        return fail(c, VTX_E_INVAL, "vtx_submit: record %u: not sorted by %s within its locus", r, c->cfg.use_umi ? "(cell_index, umi_id)" : "cell_index");
     }
     if (int rc = make_buckets(c, shape_cnt, max_hap, d_shape_cnt + 16)) return rc;
     if (int rc = build_groups(c, nr)) return rc;

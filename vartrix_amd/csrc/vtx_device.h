@@ -211,7 +211,7 @@ hipError_t vtxk_prep_lut_check(const uint32_t* work, uint32_t count, const uint3
                                uint32_t* flag, hipStream_t s);
 hipError_t vtxk_unpack_nibbles(const uint8_t* in, uint64_t n_in, uint8_t* out, hipStream_t s);
 hipError_t vtxk_prep_check(const vtx_record* records, uint32_t n, const uint32_t* rec_locus, const vtx_locus* loci,
-                           uint64_t read_bytes, uint32_t max_read_len, uint32_t n_barcodes, uint32_t n_shapes, uint8_t* shape,
+                           uint64_t read_bytes, uint32_t max_read_len, uint32_t n_barcodes, int use_umi, uint32_t n_shapes, uint8_t* shape,
                            uint32_t* seq, uint32_t* shape_cnt, unsigned long long* counters, hipStream_t s);
 }
 #endif

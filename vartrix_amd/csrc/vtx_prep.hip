@@ -178,12 +178,13 @@ __global__ __launch_bounds__(256) void prep_locus_ranges_kernel(vtx_locus* __res
 }
 
 // Per-record half of vtx_submit's validation, on the device (the host only checks the loci): bounds of the read,
-// length limit, cell index range, order (cell_index, umi_id) inside the locus; plus what the host loop used to derive —
+// length limit, cell index range, order (cell_index, umi_id) inside the locus (cell_index alone when !use_umi: umi_id may then hold
+// any value, include/vtx.h, and nothing reads it); plus what the host loop used to derive —
 // kernel shape per record, shape histogram, DP-cell count, longest read.  counters[6] = min over offending records of
 // (record << 3 | code): 1 read outside the arena, 2 read too long, 3 cell_index >= n_barcodes, 4 order.
 __global__ __launch_bounds__(256) void prep_check_kernel(
     const vtx_record* __restrict__ records, uint32_t n, const uint32_t* __restrict__ rec_locus,
-    const vtx_locus* __restrict__ loci, uint64_t read_bytes, uint32_t max_read_len_fmt, uint32_t n_barcodes, uint32_t n_shapes,
+    const vtx_locus* __restrict__ loci, uint64_t read_bytes, uint32_t max_read_len_fmt, uint32_t n_barcodes, int use_umi, uint32_t n_shapes,
     uint8_t* __restrict__ shape, uint32_t* __restrict__ seq, uint32_t* __restrict__ shape_cnt,
     unsigned long long* __restrict__ counters) {
     const uint32_t max_read_len = max_read_len_fmt & 0x7fffffffu, odd_mask = max_read_len_fmt >> 31;   // (bit 31: VTX_READS_NIBBLES, as in prep_resolve_kernel)
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(256) void prep_check_kernel(
         else if (r.read_off & odd_mask) code = 5;
         else if (j > 0 && rec_locus[j - 1] == locus) {
             const vtx_record q = records[j - 1];
-            if (q.cell_index > r.cell_index || (q.cell_index == r.cell_index && q.umi_id > r.umi_id)) code = 4;
+            if (q.cell_index > r.cell_index || (use_umi && q.cell_index == r.cell_index && q.umi_id > r.umi_id)) code = 4;
         }
         if (code) bad = min(bad, ((unsigned long long)j << 3) | code);
         const uint32_t rl = min(r.read_len, max_read_len);
@@ -351,12 +352,12 @@ hipError_t vtxk_prep_lut_check(const uint32_t* work, uint32_t count, const uint3
 }
 
 hipError_t vtxk_prep_check(const vtx_record* records, uint32_t n, const uint32_t* rec_locus, const vtx_locus* loci,
-                           uint64_t read_bytes, uint32_t max_read_len, uint32_t n_barcodes, uint32_t n_shapes, uint8_t* shape,
+                           uint64_t read_bytes, uint32_t max_read_len, uint32_t n_barcodes, int use_umi, uint32_t n_shapes, uint8_t* shape,
                            uint32_t* seq, uint32_t* shape_cnt, unsigned long long* counters, hipStream_t s) {
     if (!n) return hipSuccess;
     const uint32_t blocks = std::min<uint32_t>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(prep_check_kernel, dim3(blocks), dim3(256), 0, s, records, n, rec_locus, loci, read_bytes, max_read_len,
-                       n_barcodes, n_shapes, shape, seq, shape_cnt, counters);
+                       n_barcodes, use_umi, n_shapes, shape, seq, shape_cnt, counters);
     return hipGetLastError();
 }
 
