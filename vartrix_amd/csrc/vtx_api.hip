@@ -71,6 +71,9 @@ const uint32_t kFastHapLen = VTX_FAST_HAP_LEN;     // 16 record slots x (len + 3
 // set the hard limits.
 const uint32_t kMaxReadLen = 30000;
 const uint32_t kMaxHapLen = 30000;
+// The call reduction runs one thread per (row, cell) group when the batch's mean group is at most this many records, and the
+// histogram kernels (one thread per record, atomics) above it.  4 is the starting value: the crossing has not been measured yet.
+const uint32_t kReduceMeanGroupMax = 4;
 
 thread_local std::string g_create_err;
 
@@ -111,6 +114,8 @@ struct vtx_ctx {
     vtx_timing timing{};
     DevBuf d_loci, d_records, d_rec_locus, d_hap, d_read, d_work, d_ref, d_alt;
     DevBuf d_head_cell, d_head_umi, d_cell_scan, d_umi_scan, d_grp_row, d_grp_col, d_umi_cellgrp;
+    DevBuf d_grp_start;                      // first record of every (row, cell) group + one last entry, n_records (build_groups)
+    int reduce_path = 0;                     // the last vtx_run's call reduction: 1 = histogram kernels (atomics), 2 = one pass per group
     DevBuf d_cell_cnt, d_umi_cnt, d_keep, d_keep_scan, d_scan_tmp;
     DevBuf d_o_row, d_o_col, d_o_alt, d_o_ref, d_o_unk, d_o_val, d_o_refval;
     bool band_long_lists = false;      // (performance feedback between runs: see vtx_run)
@@ -526,6 +531,7 @@ int reserve_record_buffers(vtx_ctx* c, uint32_t nr) {
                          &c->d_umi_cellgrp, &c->d_keep, &c->d_keep_scan, &c->d_o_row, &c->d_o_col, &c->d_o_alt,
                          &c->d_o_ref, &c->d_o_unk};
     for (DevBuf* d : per_rec) HIP_TRY(c, d->reserve(nr * u32));
+    HIP_TRY(c, c->d_grp_start.reserve(((size_t)nr + 1) * u32));
     HIP_TRY(c, c->d_cell_cnt.reserve(3 * (size_t)nr * u32));
     HIP_TRY(c, c->d_umi_cnt.reserve(3 * (size_t)nr * u32));
     HIP_TRY(c, c->d_o_val.reserve(nr * sizeof(double)));
@@ -548,7 +554,7 @@ int build_groups(vtx_ctx* c, uint32_t nr) {
     HIP_TRY(c, vtxk_group_table(c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), nr,
                                 c->d_head_cell.as<uint32_t>(), c->d_head_umi.as<uint32_t>(), c->d_cell_scan.as<uint32_t>(),
                                 c->d_umi_scan.as<uint32_t>(), c->d_grp_row.as<uint32_t>(), c->d_grp_col.as<uint32_t>(),
-                                c->d_umi_cellgrp.as<uint32_t>(), s));
+                                c->d_umi_cellgrp.as<uint32_t>(), c->d_grp_start.as<uint32_t>(), s));
     HIP_TRY(c, hipMemcpyAsync(&c->n_cell_groups, c->d_cell_scan.as<uint32_t>() + (nr - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(&c->n_umi_groups, c->d_umi_scan.as<uint32_t>() + (nr - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     return VTX_OK;
@@ -715,7 +721,7 @@ void vtx_destroy(vtx_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     DevBuf* bufs[] = {&c->d_loci, &c->d_records, &c->d_rec_locus, &c->d_hap, &c->d_read, &c->d_work, &c->d_ref,
                       &c->d_alt, &c->d_head_cell, &c->d_head_umi, &c->d_cell_scan, &c->d_umi_scan, &c->d_grp_row,
-                      &c->d_grp_col, &c->d_umi_cellgrp, &c->d_cell_cnt, &c->d_umi_cnt, &c->d_keep, &c->d_keep_scan,
+                      &c->d_grp_col, &c->d_umi_cellgrp, &c->d_grp_start, &c->d_cell_cnt, &c->d_umi_cnt, &c->d_keep, &c->d_keep_scan,
                       &c->d_scan_tmp, &c->d_o_row, &c->d_o_col, &c->d_o_alt, &c->d_o_ref, &c->d_o_unk, &c->d_o_val,
                       &c->d_o_refval, &c->d_band_ws, &c->d_band_ws2, &c->d_band, &c->d_poly, &c->d_gtables, &c->d_hard, &c->d_over, &c->d_over2, &c->d_pend, &c->d_pend_buf, &c->d_band2, &c->d_hard2,
                       &c->d_cnt, &c->d_redo, &c->d_redo_cnt, &c->d_bc_slots, &c->d_bc_hash, &c->d_bc_off, &c->d_bc_bytes,
@@ -2278,7 +2284,26 @@ int vtx_run(vtx_ctx* c) {
     HIP_TRY(c, hipEventRecord(c->ev[1], s));
     uint32_t nnz32 = 0;
     const uint32_t ng = c->n_cell_groups, nu = c->n_umi_groups;
-    if (nr) {
+    // Short groups (the mean at most kReduceMeanGroupMax records): one thread per group counts its records in registers, twice —
+    // once for the kept groups per block, once to emit behind the scanned block counts (d_keep / d_keep_scan hold one word per
+    // block of groups then).  Deep groups: a histogram with atomics, one thread per record.
+    uint32_t mean_max = kReduceMeanGroupMax;
+    if (VTX_DEV_ENV("VTX_REDUCE_THRESHOLD")) mean_max = (uint32_t)strtoul(VTX_DEV_ENV("VTX_REDUCE_THRESHOLD"), nullptr, 10);   // test hook (read per run)
+    const bool legacy = VTX_DEV_ENV("VTX_REDUCE_LEGACY") && atoi(VTX_DEV_ENV("VTX_REDUCE_LEGACY"));                            // A/B and test hook (read per run)
+    const bool onepass = !legacy && (uint64_t)nr <= (uint64_t)mean_max * ng;
+    c->reduce_path = nr ? (onepass ? 2 : 1) : 0;
+    if (nr && onepass) {
+        const uint32_t nb = vtxk_reduce_blocks(ng);
+        HIP_TRY(c, vtxk_reduce_count(c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), c->d_head_umi.as<uint32_t>(), c->d_grp_start.as<uint32_t>(),
+                                     ng, c->cfg.min_score, c->cfg.use_umi, c->cfg.scoring_mode, c->d_keep.as<uint32_t>(), s));
+        HIP_TRY(c, vtxk_inclusive_scan_u32(c->d_keep.as<uint32_t>(), c->d_keep_scan.as<uint32_t>(), nb, c->d_scan_tmp.p, vtxk_scan_temp_bytes(nr), s));
+        HIP_TRY(c, vtxk_reduce_emit(c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), c->d_head_umi.as<uint32_t>(), c->d_grp_start.as<uint32_t>(),
+                                    ng, c->cfg.min_score, c->cfg.use_umi, c->cfg.scoring_mode, c->d_keep_scan.as<uint32_t>(),
+                                    c->d_grp_row.as<uint32_t>(), c->d_grp_col.as<uint32_t>(), c->d_o_row.as<uint32_t>(),
+                                    c->d_o_col.as<uint32_t>(), c->d_o_alt.as<uint32_t>(), c->d_o_ref.as<uint32_t>(),
+                                    c->d_o_unk.as<uint32_t>(), c->d_o_val.as<double>(), c->d_o_refval.as<double>(), s));
+        if (nb) HIP_TRY(c, hipMemcpyAsync(&nnz32, c->d_keep_scan.as<uint32_t>() + (nb - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    } else if (nr) {
         const size_t tmp_bytes = vtxk_scan_temp_bytes(nr);
         HIP_TRY(c, hipMemsetAsync(c->d_cell_cnt.p, 0, 3 * (size_t)ng * sizeof(uint32_t), s));
         if (c->cfg.use_umi) {
@@ -2326,6 +2351,12 @@ int vtx_fetch_scores(vtx_ctx* c, int32_t* ref_score, int32_t* alt_score) {
     }
     return VTX_OK;
 }
+
+#ifdef VTX_DEVTOOLS
+// developer library only (not part of include/vtx.h): which call reduction the last vtx_run took — 0 none (no records),
+// 1 the histogram kernels, 2 one pass per group
+extern "C" int vtx_dev_reduce_path(vtx_ctx* c) { return c ? c->reduce_path : -1; }
+#endif
 
 int vtx_set_debug(vtx_ctx* c, int key, int64_t value) {
     if (!c) return VTX_E_INVAL;

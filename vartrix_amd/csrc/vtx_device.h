@@ -170,7 +170,17 @@ hipError_t vtxk_group_heads(const vtx_record* records, const uint32_t* rec_locus
 hipError_t vtxk_group_table(const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci, uint32_t n,
                             const uint32_t* head_cell, const uint32_t* head_umi, const uint32_t* cell_scan,
                             const uint32_t* umi_scan, uint32_t* grp_row, uint32_t* grp_col, uint32_t* umi_cellgrp,
-                            hipStream_t s);
+                            uint32_t* grp_start, hipStream_t s);
+// the call reduction of short groups in one pass over the scores (one thread per group, vtx_call_core.h)
+uint32_t vtxk_reduce_blocks(uint32_t n_grp);     // words reduce_count_kernel writes: one per block of groups
+hipError_t vtxk_reduce_count(const int32_t* ref_score, const int32_t* alt_score, const uint32_t* head_umi,
+                             const uint32_t* grp_start, uint32_t n_grp, int32_t min_score, int use_umi, int mode,
+                             uint32_t* blk_keep, hipStream_t s);
+hipError_t vtxk_reduce_emit(const int32_t* ref_score, const int32_t* alt_score, const uint32_t* head_umi,
+                            const uint32_t* grp_start, uint32_t n_grp, int32_t min_score, int use_umi, int mode,
+                            const uint32_t* blk_keep_scan, const uint32_t* grp_row, const uint32_t* grp_col, uint32_t* o_row,
+                            uint32_t* o_col, uint32_t* o_alt, uint32_t* o_ref, uint32_t* o_unk, double* o_val,
+                            double* o_refval, hipStream_t s);
 hipError_t vtxk_count_calls(const int32_t* ref_score, const int32_t* alt_score, uint32_t n, int32_t min_score,
                             const uint32_t* gscan, uint32_t* cnt, hipStream_t s);
 hipError_t vtxk_umi_collapse(const uint32_t* umi_cnt, uint32_t n_umi, const uint32_t* umi_cellgrp,

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "vtx_device.h"
+#include "vtx_call_core.h"
 #include "vtx_scan_core.h"
 
 typedef short v2s __attribute__((ext_vector_type(2)));
@@ -259,17 +260,19 @@ __global__ void group_heads_kernel(const vtx_record* __restrict__ records, const
     head_umi[r] = hu;
 }
 
-// After the inclusive scans: gid = scan - 1.  Head records publish their group's (row, col).
+// After the inclusive scans: gid = scan - 1.  Head records publish their group's (row, col) and its first record
+// (grp_start: one entry per group and a last one, n, so that group g is the records [grp_start[g], grp_start[g + 1])).
 __global__ void group_table_kernel(const vtx_record* __restrict__ records, const uint32_t* __restrict__ rec_locus,
                                    const vtx_locus* __restrict__ loci, uint32_t n,
                                    const uint32_t* __restrict__ head_cell, const uint32_t* __restrict__ head_umi,
                                    const uint32_t* __restrict__ cell_scan, const uint32_t* __restrict__ umi_scan,
                                    uint32_t* __restrict__ grp_row, uint32_t* __restrict__ grp_col,
-                                   uint32_t* __restrict__ umi_cellgrp) {
+                                   uint32_t* __restrict__ umi_cellgrp, uint32_t* __restrict__ grp_start) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const uint32_t cg = cell_scan[r] - 1;
-    if (head_cell[r]) { grp_row[cg] = loci[rec_locus[r]].row; grp_col[cg] = records[r].cell_index; }
+    if (head_cell[r]) { grp_row[cg] = loci[rec_locus[r]].row; grp_col[cg] = records[r].cell_index; grp_start[cg] = r; }
+    if (r == n - 1) grp_start[cg + 1] = n;
     if (head_umi[r]) umi_cellgrp[umi_scan[r] - 1] = cg;
 }
 
@@ -330,7 +333,94 @@ __global__ void emit_coo_kernel(const uint32_t* __restrict__ cell_cnt, uint32_t 
     o_val[o] = v; o_refval[o] = rv;
 }
 
+// ---------------------------------------------------------------------------
+// The call reduction in one pass over the scores, for batches of short groups (vtx_run picks it when the mean group is at most
+// kReduceMeanGroupMax records; the five kernels above remain the path for deep groups).  One thread per (row, cell) group walks
+// its records [grp_start[g], grp_start[g + 1]) and counts them in registers (vtx_call_core.h): no counters in memory, no zeroing,
+// no atomics.  reduce_count_kernel leaves ONE word per 256 groups, the number it keeps; after an inclusive scan of those words
+// reduce_emit_kernel counts its group again (the scores are still in L2 / MALL) and writes the triplet at the block's base plus
+// the prefix of the keep flags inside the block.  No block waits for another.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kReduceBlock = 256;
+
+// exclusive prefix of `flag` over the 256 threads of the block, and the block's total
+__device__ __forceinline__ uint32_t block_prefix_flags(bool flag, uint32_t* total) {
+    __shared__ uint32_t wave_cnt[kReduceBlock / 64];
+    const uint64_t mask = __ballot(flag);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    uint32_t before = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)), sum = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kReduceBlock / 64; ++w) { before += w < wave ? wave_cnt[w] : 0u; sum += wave_cnt[w]; }
+    *total = sum;
+    return before;
+}
+
+__device__ __forceinline__ vtxcall::Counts reduce_group(const int32_t* __restrict__ ref_score, const int32_t* __restrict__ alt_score,
+                                                        const uint32_t* __restrict__ head_umi, const uint32_t* __restrict__ grp_start,
+                                                        uint32_t g, int32_t min_score, int use_umi) {
+    return vtxcall::count_group(ref_score, alt_score, head_umi, grp_start[g], grp_start[g + 1], min_score, use_umi != 0);
+}
+
+__global__ __launch_bounds__(kReduceBlock) void reduce_count_kernel(
+    const int32_t* __restrict__ ref_score, const int32_t* __restrict__ alt_score, const uint32_t* __restrict__ head_umi,
+    const uint32_t* __restrict__ grp_start, uint32_t n_grp, int32_t min_score, int use_umi, int mode, uint32_t* __restrict__ blk_keep) {
+    const uint32_t g = blockIdx.x * kReduceBlock + threadIdx.x;
+    bool keep = false;
+    if (g < n_grp)      // (alt_frac / coverage keep every group: nothing to count yet)
+        keep = mode != VTX_MODE_CONSENSUS || vtxcall::keep_of(reduce_group(ref_score, alt_score, head_umi, grp_start, g, min_score, use_umi), mode);
+    uint32_t total;
+    (void)block_prefix_flags(keep, &total);
+    if (threadIdx.x == 0) blk_keep[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kReduceBlock) void reduce_emit_kernel(
+    const int32_t* __restrict__ ref_score, const int32_t* __restrict__ alt_score, const uint32_t* __restrict__ head_umi,
+    const uint32_t* __restrict__ grp_start, uint32_t n_grp, int32_t min_score, int use_umi, int mode,
+    const uint32_t* __restrict__ blk_keep_scan, const uint32_t* __restrict__ grp_row, const uint32_t* __restrict__ grp_col,
+    uint32_t* __restrict__ o_row, uint32_t* __restrict__ o_col, uint32_t* __restrict__ o_alt, uint32_t* __restrict__ o_ref,
+    uint32_t* __restrict__ o_unk, double* __restrict__ o_val, double* __restrict__ o_refval) {
+    const uint32_t g = blockIdx.x * kReduceBlock + threadIdx.x;
+    vtxcall::Counts c = {0, 0, 0};
+    bool keep = false;
+    if (g < n_grp) {
+        c = reduce_group(ref_score, alt_score, head_umi, grp_start, g, min_score, use_umi);
+        keep = vtxcall::keep_of(c, mode);
+    }
+    uint32_t total;
+    const uint32_t before = block_prefix_flags(keep, &total);
+    if (!keep) return;
+    const uint32_t o = (blockIdx.x ? blk_keep_scan[blockIdx.x - 1] : 0u) + before;
+    double v, rv;
+    vtxcall::values_of(c, mode, &v, &rv);
+    o_row[o] = grp_row[g]; o_col[o] = grp_col[g];
+    o_alt[o] = c.a; o_ref[o] = c.r; o_unk[o] = c.k;
+    o_val[o] = v; o_refval[o] = rv;
+}
+
 static inline dim3 grid1d(uint32_t n, uint32_t b) { return dim3((n + b - 1) / b); }
+
+extern "C" uint32_t vtxk_reduce_blocks(uint32_t n_grp) { return (n_grp + kReduceBlock - 1) / kReduceBlock; }
+extern "C" hipError_t vtxk_reduce_count(const int32_t* ref_score, const int32_t* alt_score, const uint32_t* head_umi,
+                                        const uint32_t* grp_start, uint32_t n_grp, int32_t min_score, int use_umi, int mode,
+                                        uint32_t* blk_keep, hipStream_t s) {
+    if (!n_grp) return hipSuccess;
+    hipLaunchKernelGGL(reduce_count_kernel, grid1d(n_grp, kReduceBlock), dim3(kReduceBlock), 0, s, ref_score, alt_score, head_umi,
+                       grp_start, n_grp, min_score, use_umi, mode, blk_keep);
+    return hipGetLastError();
+}
+extern "C" hipError_t vtxk_reduce_emit(const int32_t* ref_score, const int32_t* alt_score, const uint32_t* head_umi,
+                                       const uint32_t* grp_start, uint32_t n_grp, int32_t min_score, int use_umi, int mode,
+                                       const uint32_t* blk_keep_scan, const uint32_t* grp_row, const uint32_t* grp_col,
+                                       uint32_t* o_row, uint32_t* o_col, uint32_t* o_alt, uint32_t* o_ref, uint32_t* o_unk,
+                                       double* o_val, double* o_refval, hipStream_t s) {
+    if (!n_grp) return hipSuccess;
+    hipLaunchKernelGGL(reduce_emit_kernel, grid1d(n_grp, kReduceBlock), dim3(kReduceBlock), 0, s, ref_score, alt_score, head_umi,
+                       grp_start, n_grp, min_score, use_umi, mode, blk_keep_scan, grp_row, grp_col, o_row, o_col, o_alt, o_ref,
+                       o_unk, o_val, o_refval);
+    return hipGetLastError();
+}
 
 extern "C" hipError_t vtxk_group_heads(const vtx_record* records, const uint32_t* rec_locus, uint32_t n,
                                        uint32_t* head_cell, uint32_t* head_umi, hipStream_t s) {
@@ -341,10 +431,10 @@ extern "C" hipError_t vtxk_group_heads(const vtx_record* records, const uint32_t
 extern "C" hipError_t vtxk_group_table(const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci,
                                        uint32_t n, const uint32_t* head_cell, const uint32_t* head_umi,
                                        const uint32_t* cell_scan, const uint32_t* umi_scan, uint32_t* grp_row,
-                                       uint32_t* grp_col, uint32_t* umi_cellgrp, hipStream_t s) {
+                                       uint32_t* grp_col, uint32_t* umi_cellgrp, uint32_t* grp_start, hipStream_t s) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(group_table_kernel, grid1d(n, 256), dim3(256), 0, s, records, rec_locus, loci, n, head_cell,
-                       head_umi, cell_scan, umi_scan, grp_row, grp_col, umi_cellgrp);
+                       head_umi, cell_scan, umi_scan, grp_row, grp_col, umi_cellgrp, grp_start);
     return hipGetLastError();
 }
 extern "C" hipError_t vtxk_count_calls(const int32_t* ref_score, const int32_t* alt_score, uint32_t n,
