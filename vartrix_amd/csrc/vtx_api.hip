@@ -75,6 +75,35 @@ const uint32_t kMaxHapLen = 30000;
 // histogram kernels (one thread per record, atomics) above it.  4 is the starting value: the crossing has not been measured yet.
 const uint32_t kReduceMeanGroupMax = 4;
 
+// vtx_ctx::ev.  vtx_run's slots; the entry points that prepare a batch run at other times and reuse the first four.
+enum EvSlot {
+    EV_START = 0,           // run_prologue records; run_epilogue reads (full_ms, sw_ms)
+    EV_DP_END = 1,          // vtx_run records after the slow path; run_epilogue reads (sw_ms, reduce_ms)
+    EV_REDUCE_END = 2,      // run_reduce records; run_epilogue reads (reduce_ms)
+    EV_FULL_END = 3,        // run_full_dp records; run_epilogue reads (full_ms)
+    EV_CHUNK_START = 4,     // BandPass::resident_tables records; run_stage reads (diag_ms, band_run_ms of a chunk without a sweep)
+    EV_BAND_RUN_END = 5,    // run_stage / second_chance record behind band_run_kernel; run_stage reads (band_run_ms)
+    EV_DIAG_END = 6,        // diag_sweep_path / diag_round3_path record; run_stage reads (diag_ms); the side stream waits for it
+    EV_BRANCH_START = 7,    // diag_sweep_path records on the one-diagonal branch's stream; collect_sweep_times reads (check_ms)
+    EV_SWEEP_END = 8,       // diag_sweep_path records after the join; collect_sweep_times waits for it and reads (sweep_ms)
+    EV_BRANCH_END = 9,      // diag_sweep_path records on the branch's stream; the main stream joins on it; collect_sweep_times reads
+    EV_BAND_RUN_START = 10, // run_stage records in front of band_run_kernel; run_stage reads (band_run_ms of a swept chunk)
+    EV_FORK_START = 11,     // diag_sweep_path records where the main stream's branch starts (forked); collect_sweep_times reads
+    EV_COUNT = 12
+};
+enum PrepEv { EV_PREP_START = 0, EV_PREP_END = 1 };                                                // the same array in vtx_submit_raw: around the preparation
+enum IngestEv { EV_INGEST_START = 0, EV_INFLATE_END = 1, EV_INDEX_END = 2, EV_FILTER_END = 3 };    // ... and in vtx_submit_bam: its phases
+// vtx_ctx::h_pin: counter words copied back asynchronously.
+enum PinWord {
+    PIN_GENERAL_HARD = 0, PIN_GENERAL_AGAIN = 1,                        // fallback_launch copies VTX_CNT_GENERAL_HARD, _AGAIN here (side stream); fallback_finish reads both
+    PIN_RUN_LEFT = 8, PIN_DENSE = 9, PIN_REFINE = 10, PIN_TIGHT = 11,   // diag_sweep_path copies VTX_CNT_RUN_LEFT .. VTX_CNT_TIGHT here and reads them
+    PIN_R3_REFINE = 9,      // diag_round3_path copies and reads PIN_RUN_LEFT, and VTX_CNT_REFINE here: no dense list on that path, PIN_DENSE's word is free
+    PIN_FORK_TIGHT = 12,    // diag_sweep_path copies VTX_CNT_TIGHT on the side stream (forked); collect_sweep_times reads
+    PIN_DIAG2_LEFT = 14, PIN_DIAG2_TIGHT = 15,                          // second_stage copies VTX_CNT_DIAG2_LEFT, _TIGHT here and reads both
+    PIN_STREAMED = 16,      // second_stage copies VTX_CNT_STREAMED here and reads it
+    PIN_WORDS = 64
+};
+
 thread_local std::string g_create_err;
 
 }  // namespace
@@ -103,7 +132,7 @@ struct vtx_ctx {
     uint64_t g_nnz = 0;
     uint32_t* h_pin = nullptr;               // pinned words for counters read back asynchronously (a D2H copy into pageable
                                              // memory blocks the host until the stream reaches it)
-    hipEvent_t ev[12] = {};
+    hipEvent_t ev[EV_COUNT] = {};
     hipEvent_t ev_crc[2] = {};               // around bgzf_crc32_kernel (vtx_submit_bam, vtx_debug_crc32)
     float crc_ms = 0;                        // vtx_last_crc_ms
     std::string err;
@@ -1029,7 +1058,7 @@ static int raw_prepare(vtx_ctx* c, uint32_t nl, uint32_t nr, uint64_t read_bytes
     unsigned long long* d_counters = c->d_prep_cnt.as<unsigned long long>();
     uint32_t* d_shape_cnt = (uint32_t*)(d_counters + 8);
     uint32_t* d_lut_flag = d_shape_cnt + 16;
-    HIP_TRY(c, hipEventRecord(c->ev[0], s));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_PREP_START], s));
     const uint32_t cell_bits = bits_for(c->cfg.n_barcodes ? c->cfg.n_barcodes - 1 : 0);
     const int end_bit = (int)(cell_bits + bits_for(nl));
     if (end_bit > 64) return fail(c, VTX_E_UNSUPPORTED, "raw batch: loci x barcodes exceed a 64-bit sort key");
@@ -1097,10 +1126,10 @@ static int raw_prepare(vtx_ctx* c, uint32_t nl, uint32_t nr, uint64_t read_bytes
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = make_buckets(c, shape_cnt, max_hap, d_lut_flag)) return rc;
     if (int rc = build_groups(c, n_kept)) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_PREP_END], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     float ms = 0;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_PREP_START], c->ev[EV_PREP_END]));
     c->n_loci = nl; c->n_records = n_kept; c->max_hap_len = max_hap; c->max_read_len = (uint32_t)cnt[5]; c->cells = cnt[3];
     c->max_hap_all = max_hap_all; c->max_read_all = std::max<uint32_t>((uint32_t)cnt[7], std::max<uint32_t>((uint32_t)cnt[5], 1u));
     c->submitted = true;
@@ -1343,9 +1372,9 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
     HIP_TRY(c, hipStreamSynchronize(s));
     const float h2d_ms = since(t0);
     // ---- inflate, record boundaries ----
-    HIP_TRY(c, hipEventRecord(c->ev[0], s));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_INGEST_START], s));
     HIP_TRY(c, vtxg_inflate(c->d_bam_comp.as<uint8_t>(), c->d_bam_blocks.as<vtxg_block>(), nb, c->d_bam_data.as<uint8_t>(), d_err, nullptr, 0, s));
-    HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_INFLATE_END], s));
     // ---- the CRC32 of every block's inflated bytes against its trailer (htslib's check in bgzf_read_block): in front of the first
     //      reader of those bytes, on the same stream, its verdict in the same err words ----
     static const bool no_crc = VTX_DEV_ENV("VTX_NO_CRC") != nullptr;                                   // A/B timing only: the check off
@@ -1383,7 +1412,7 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
                                                  c->d_bam_seed_scan.as<uint32_t>(), c->d_bam_rec.as<uint64_t>(), d_err, s));
     else if (ns) HIP_TRY(c, vtxg_chain(c->d_bam_data.as<uint8_t>(), utotal, c->d_bam_seeds.as<uint64_t>(), ns, end_upos, c->d_bam_seed_cnt.as<uint32_t>(),
                                    c->d_bam_seed_scan.as<uint32_t>(), c->d_bam_rec.as<uint64_t>(), d_err, s));
-    HIP_TRY(c, hipEventRecord(c->ev[2], s));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_INDEX_END], s));
     // ---- fetch + filters per (read, locus) pair: counts, then offsets, then the raw records ----
     const vtxg_filter f{nref, g->min_mapq, g->primary_only ? 1u : 0u, g->no_duplicates ? 1u : 0u, (uint32_t)(uint8_t)g->bam_tag[0] | ((uint32_t)(uint8_t)g->bam_tag[1] << 8)};
     HIP_TRY(c, vtxg_scan(0, c->d_bam_data.as<uint8_t>(), c->d_bam_rec.as<uint64_t>(), n_rec, f, d_iv_start, d_iv_end, d_iv_locus, d_tid_begin, d_tid_span,
@@ -1411,13 +1440,13 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
                              c->d_raw_locus.as<uint32_t>(), c->d_tags.as<uint8_t>(), c->d_read_packed.as<uint8_t>(), d_counters, d_err, s));
     }
     HIP_TRY(c, vtxk_unpack_nibbles(c->d_read_packed.as<uint8_t>(), read_bases / 2, c->d_read.as<uint8_t>(), s));
-    HIP_TRY(c, hipEventRecord(c->ev[3], s));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_FILTER_END], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     float inflate_ms = 0, index_ms = 0, filter_ms = 0;
-    HIP_TRY(c, hipEventElapsedTime(&inflate_ms, c->ev[0], c->ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(&inflate_ms, c->ev[EV_INGEST_START], c->ev[EV_INFLATE_END]));
     HIP_TRY(c, hipEventElapsedTime(&c->crc_ms, c->ev_crc[0], c->ev_crc[1]));
-    HIP_TRY(c, hipEventElapsedTime(&index_ms, c->ev_crc[1], c->ev[2]));
-    HIP_TRY(c, hipEventElapsedTime(&filter_ms, c->ev[2], c->ev[3]));
+    HIP_TRY(c, hipEventElapsedTime(&index_ms, c->ev_crc[1], c->ev[EV_INDEX_END]));
+    HIP_TRY(c, hipEventElapsedTime(&filter_ms, c->ev[EV_INDEX_END], c->ev[EV_FILTER_END]));
     c->bam_n_rec = n_rec; c->bam_n_raw = nr; c->bam_utotal = utotal; c->bam_read_bases = read_bases; c->bam_tag_bytes = tag_bytes;
     vtx_raw_stats rs{};
     if (int rc = raw_prepare(c, nl, nr, read_bases, tag_bytes, true, max_hap, max_hap_all, false, &rs)) return rc;
@@ -1555,787 +1584,759 @@ int vtx_fetch_records(vtx_ctx* c, vtx_record* records, uint32_t* rec_begin, uint
     return VTX_OK;
 }
 
-int vtx_run(vtx_ctx* c) {
-    if (!c) return VTX_E_INVAL;
-    if (!c->submitted) return fail(c, VTX_E_STATE, "vtx_run: no batch submitted");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
+}  // extern "C": the run path's helpers are C++
+
+namespace {
+
+// ---- vtx_run: the hooks, the arrays every launch takes, the launchers' short forms --------------------------------------------
+// The developer hooks of vtx_run that hold for the life of the process (libvtx_dev.so; in libvtx.so every VTX_DEV_ENV is the constant
+// nullptr and the members are their defaults), and whether VTX_DEBUG asked for the kernels' statistics.  Read once, by band_knobs().
+inline bool env_is(const char* v, const char* what) { return v && !strcmp(v, what); }
+inline uint32_t env_atoi(const char* v, uint32_t dflt) { return v ? (uint32_t)atoi(v) : dflt; }
+inline uint32_t env_u32(const char* v, int base, uint32_t dflt) { return v ? (uint32_t)strtoul(v, nullptr, base) : dflt; }
+struct BandKnobs {
+    bool no_duo = env_is(VTX_DEV_ENV("VTX_DP_KERNEL"), "lut"), no_pair = env_is(VTX_DEV_ENV("VTX_DP_KERNEL"), "duo2");   // (duo2: two-lookup prefix phase)
+    uint32_t lds_tasks = env_atoi(VTX_DEV_ENV("VTX_BAND_LDS_TASKS"), 4096u);    // experiment knob
+    bool no_coop = VTX_DEV_ENV("VTX_BAND_NO_COOP") != nullptr;                  // experiment / test hook
+    bool sweep_v1 = VTX_DEV_ENV("VTX_SWEEP_V1") != nullptr;                     // round 4's band_sweep_kernel: the A/B reference of tests/test_gpu_sweep.py and tools/gpu_campaign.sh
+    bool no_diag2 = VTX_DEV_ENV("VTX_BAND_NO_DIAG2") != nullptr;                // everything to the sweep, as round 4 did
+    uint32_t diag2_min = env_u32(VTX_DEV_ENV("VTX_BAND_DIAG2_MIN"), 10, 700000u);   // the shortest list the second stage takes (see second_stage_on)
+    bool no_stream = VTX_DEV_ENV("VTX_BAND_NO_STREAM") != nullptr;              // what exceeds the second stage's list goes to the sweep
+    bool no_diag = VTX_DEV_ENV("VTX_BAND_NO_DIAG") != nullptr;                  // experiment / test hook: stage 1 off
+    bool legacy = VTX_DEV_ENV("VTX_BAND_LEGACY") != nullptr;                    // round 3's band_run_kernel / pending / general path (kept for A/B tests)
+    bool no_tight = VTX_DEV_ENV("VTX_BAND_NO_TIGHT") != nullptr;                // test hook: tasks with a certificate go to the sweep like the others
+    bool use_check = VTX_DEV_ENV("VTX_BAND_CHECK") != nullptr;                  // experiment hook: full-matrix check in front of their DP
+    uint32_t dense_mask = env_u32(VTX_DEV_ENV("VTX_BAND_DENSE_MASK"), 0, 1u << 4);   // experiment knob (0x3be: everything but shape; 0: nothing — band_run_kernel sees every task first)
+    bool no_refine = VTX_DEV_ENV("VTX_BAND_NO_REFINE") != nullptr;              // experiment / test hook
+    bool no_fork = VTX_DEV_ENV("VTX_BAND_NO_FORK") != nullptr;                  // experiment / test hook
+    bool no_corridor = VTX_DEV_ENV("VTX_BAND_NO_CORRIDOR") != nullptr;          // round 3's band_refine_kernel instead of band_corridor_kernel
+    uint32_t run_min = env_u32(VTX_DEV_ENV("VTX_BAND_RUN_MIN"), 10, 65536u);    // the shortest list worth band_run_kernel's launch (see repeats)
+    bool no_split = VTX_DEV_ENV("VTX_BAND_NO_SPLIT") != nullptr;                // test hook: the single pass of rounds 3 - 5
+    bool sweep_stats = getenv("VTX_DEBUG") != nullptr;                          // band_sweep_kernel counts its reasons
+    int diag_stats = getenv("VTX_DEBUG") ? 1 : 0;                               // band_diag_kernel and its followers count theirs
+};
+const BandKnobs& band_knobs() { static const BandKnobs k; return k; }
+// The batch's arrays that nearly every kernel launch takes; filled once per run from the context.
+struct TaskArrays { const vtx_record* records; const uint32_t* rec_locus; const vtx_locus* loci; const uint8_t* read; const uint8_t* hap; int32_t* ref; int32_t* alt; };
+// What the stages of one vtx_run share.  stage: one byte per task saying which stage decided it (vtx_fetch_stage), or nullptr
+struct RunState { TaskArrays a{}; uint8_t* stage = nullptr; uint32_t launches = 0, hard_total = 0; float band_run_ms = 0; };
+// vtxk_launch_*(...) with the arrays taken from the bundle: a call shows what distinguishes it.
+inline hipError_t launch_sw_full(const TaskArrays& a, int R, int GL, uint32_t n, const uint32_t* work, uint32_t mh, hipStream_t s) {
+    return vtxk_launch_sw_full(R, GL, n, work, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, mh, s); }
+inline hipError_t launch_sw_full_lut(const TaskArrays& a, int R, uint32_t n, const uint32_t* work, uint32_t mh, uint32_t loci_cap, uint32_t* redo, uint32_t* redo_count, hipStream_t s) {
+    return vtxk_launch_sw_full_lut(R, n, work, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, mh, loci_cap, redo, redo_count, s); }
+inline hipError_t launch_sw_full_duo(const TaskArrays& a, int R, uint32_t n, const uint32_t* work, uint32_t mh, uint32_t loci_cap, uint32_t* redo, uint32_t* redo_count, uint32_t pair_cols, hipStream_t s) {
+    return vtxk_launch_sw_full_duo(R, n, work, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, mh, loci_cap, redo, redo_count, pair_cols, s); }
+inline hipError_t launch_sw_banded(const TaskArrays& a, const int* shape, uint32_t n, const uint32_t* hard, const uint16_t* band, uint32_t band_stride, uint32_t mh, hipStream_t s) {
+    return vtxk_launch_sw_banded(shape[0], shape[1], n, hard, a.records, a.rec_locus, a.loci, a.read, a.hap, band, band_stride, a.ref, a.alt, mh, s); }
+inline hipError_t launch_sw_banded_dev(const TaskArrays& a, const int* shape, uint32_t n_cap, const uint32_t* hard, const uint32_t* n_dev, const uint16_t* band, uint32_t band_stride, uint32_t mh, hipStream_t s) {
+    return vtxk_launch_sw_banded_dev(shape[0], shape[1], n_cap, hard, n_dev, a.records, a.rec_locus, a.loci, a.read, a.hap, band, band_stride, a.ref, a.alt, mh, s); }
+inline hipError_t launch_sw_check(const TaskArrays& a, const int* shape, uint32_t n_cap, const uint32_t* list, const uint32_t* packs, const uint32_t* n_dev, uint32_t mh, uint32_t* recheck_list, uint32_t* recheck_pack,
+        uint32_t* recheck_count, uint8_t* stage, hipStream_t s) {
+    return vtxk_launch_sw_check(shape[0], shape[1], n_cap, list, packs, n_dev, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, mh, recheck_list, recheck_pack, recheck_count, stage, s); }
+inline hipError_t launch_sw_diag_band(const TaskArrays& a, const int* shape, uint32_t n_cap, const uint32_t* list, const uint32_t* packs, const uint32_t* n_dev, uint32_t mh, uint8_t* stage, hipStream_t s) {
+    return vtxk_launch_sw_diag_band(shape[0], shape[1], n_cap, list, packs, n_dev, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, mh, stage, s); }
+inline hipError_t launch_band_expand(const TaskArrays& a, const uint32_t* hard, uint32_t n, const uint16_t* src, uint32_t src_stride, uint16_t* band, uint32_t band_stride, hipStream_t s) {
+    return vtxk_launch_band_expand(hard, n, a.records, a.rec_locus, a.loci, src, src_stride, band, band_stride, s); }
+inline hipError_t launch_band(const TaskArrays& a, const uint32_t* tasks, uint32_t n, uint8_t* ws, uint64_t ws_stride, uint32_t m_cap, uint32_t mh, uint16_t* band, uint32_t band_stride, uint32_t* hard, uint32_t* over,
+        uint32_t* counters, int in_lds, uint32_t max_read, hipStream_t s) {
+    return vtxk_launch_band(tasks, n, 0, a.records, a.rec_locus, a.loci, a.read, a.hap, ws, ws_stride, m_cap, mh, a.ref, a.alt, band, band_stride, hard, over, counters, in_lds, max_read, s); }
+inline hipError_t launch_band_coop(const TaskArrays& a, int tier, const uint32_t* tasks, uint32_t n, uint32_t mh, uint16_t* band, uint32_t band_stride, uint32_t* hard, uint32_t* over, uint32_t* counters, hipStream_t s) {
+    return vtxk_launch_band_coop(tier, tasks, n, a.records, a.rec_locus, a.loci, a.read, a.hap, mh, a.ref, a.alt, band, band_stride, hard, over, counters, s); }
+inline hipError_t launch_band_sweep(const TaskArrays& a, const uint32_t* tasks, uint32_t n, uint16_t* band, uint32_t band_stride, uint32_t* hard, uint32_t* over, uint32_t* counters, uint32_t* stat_counters, uint8_t* stage,
+        uint32_t* glog, hipStream_t s) {
+    return vtxk_launch_band_sweep(tasks, n, nullptr, a.records, a.rec_locus, a.loci, a.read, a.hap, band, band_stride, hard, over, counters, stat_counters, stage, nullptr, glog, s); }
+#ifdef VTX_DEVTOOLS
+inline hipError_t launch_band_sweep_v1(const TaskArrays& a, int tier, const uint32_t* tasks, uint32_t n, uint16_t* band, uint32_t band_stride, uint32_t* hard, uint32_t* over, uint32_t* counters, uint32_t* stat_counters, uint8_t* stage,
+        hipStream_t s) {
+    return vtxk_launch_band_sweep_v1(tier, tasks, n, nullptr, a.records, a.rec_locus, a.loci, a.read, a.hap, band, band_stride, hard, over, counters, stat_counters, stage, nullptr, s); }
+#endif
+inline hipError_t launch_slow_align(const TaskArrays& a, const uint32_t* recs, const uint32_t* tasks, uint32_t n, int banded, uint8_t* ws, uint64_t ws_stride, uint32_t m_cap, uint32_t mh, uint32_t max_read, uint32_t* retry,
+        uint32_t* counters, hipStream_t s) {
+    return vtxk_launch_slow_align(recs, tasks, n, banded, a.records, a.rec_locus, a.loci, a.read, a.hap, ws, ws_stride, m_cap, mh, max_read, a.ref, a.alt, retry, counters, s); }
+inline hipError_t launch_band_run(const TaskArrays& a, uint32_t n, uint32_t task_base, uint32_t mh, uint32_t mh_min, uint32_t* logbuf, uint16_t* poly, uint32_t poly_stride, uint32_t* hard, uint32_t* over, uint32_t* pend,
+        uint32_t* pend_buf, uint32_t hard_cap, uint32_t pend_cap, uint32_t* counters, uint32_t tasks_per_locus, uint32_t gt_l0, uint32_t gt_n, uint8_t* gtables, size_t gt_bytes, const uint32_t* task_list, int long_lists,
+        hipStream_t s) {
+    return vtxk_launch_band_run(n, task_base, a.records, a.rec_locus, a.loci, a.read, a.hap, mh, mh_min, a.ref, a.alt, logbuf, poly, poly_stride, hard, over, pend, pend_buf, hard_cap, pend_cap, counters, tasks_per_locus, gt_l0, gt_n,
+            gtables, gt_bytes, task_list, long_lists, s); }
+inline hipError_t launch_band_diag(const TaskArrays& a, uint32_t n, uint32_t task_base, uint32_t mh, uint32_t mh_min, uint32_t* fail_list, uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus,
+        uint32_t gt_l0, uint32_t gt_n, uint8_t* gtables, size_t gt_bytes, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, uint32_t* tail_rec,
+        uint32_t tail_cap, hipStream_t s) {
+    return vtxk_launch_band_diag(n, task_base, a.records, a.rec_locus, a.loci, a.read, a.hap, mh, mh_min, a.ref, a.alt, fail_list, refine_rec, refine_cap, counters, tasks_per_locus, gt_l0, gt_n, gtables, gt_bytes, stats, tight_list,
+            tight_pack, stage, dense_list, dense_mask, max_read, tail_rec, tail_cap, s); }
+inline hipError_t launch_band_refine(const TaskArrays& a, const uint32_t* recs, uint32_t n, uint32_t mh, uint32_t* fail_list, uint32_t* counters, uint32_t tasks_per_locus, uint32_t gt_l0, const uint8_t* gtables, int stats,
+        uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, const uint32_t* n_dev, hipStream_t s) {
+    return vtxk_launch_band_refine(recs, n, a.records, a.rec_locus, a.loci, a.read, mh, a.ref, a.alt, fail_list, counters, tasks_per_locus, gt_l0, gtables, stats, tight_list, tight_pack, stage, n_dev, s); }
+inline hipError_t launch_band_diag2(const TaskArrays& a, const uint32_t* tasks, uint32_t n, uint32_t mh, uint32_t tasks_per_locus, uint32_t gt_l0, const uint8_t* gtables, uint32_t* sweep_list, uint32_t* tight_list, uint32_t* tight_pack,
+        uint32_t* counters, uint32_t* stream_list, uint32_t* stream_diag, uint32_t* stream_cnt, uint8_t* stage, hipStream_t s) {
+    return vtxk_launch_band_diag2(tasks, n, a.records, a.rec_locus, a.loci, a.read, mh, a.ref, a.alt, tasks_per_locus, gt_l0, gtables, sweep_list, tight_list, tight_pack, counters, stream_list, stream_diag, stream_cnt, stage, s); }
+inline hipError_t launch_band_corridor(const TaskArrays& a, const uint32_t* recs, uint32_t n, uint32_t* counters, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, const uint32_t* n_dev, hipStream_t s) {
+    return vtxk_launch_band_corridor(recs, n, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, counters, stats, tight_list, tight_pack, stage, n_dev, s); }
+
+// ---- vtx_run: one pass of the banded stages ---------------------------------------------------------------------------------------
+// Tasks [t_begin, t_end) whose locus has its longer haplotype in (mh_min, mh] (the others are left alone); chunk_tables: the tables are built per chunk for the loci the chunk spans, whatever the
+// buffer would hold. Per chunk of tasks (task = 2*record + hap), round 4 (the stages are described in vtx_band.hip's header): tables -> band_diag_kernel (+ band_refine_kernel): scores of the
+// certified tasks, and three lists — tasks whose band is one diagonal stretch (masked DP straight from one word), repeats (band_sweep_kernel + masked DP), the others (band_run_kernel: seeds,
+// chain, general certificate; its hard list -> expand -> masked DP).  What overflows band_run_kernel's lists joins the repeats after the last chunk; what band_sweep_kernel declines twice takes
+// the general band kernel (side stream). The counters are VtxBandCnt (vtx_device.h), the words read back through pinned memory PinWord, the events EvSlot.
+struct BandPass {
+    vtx_ctx* const c;
+    RunState& rs;
+    const uint32_t mh, mh_min;
+    const uint64_t t_begin, t_end;
+    const bool chunk_tables;
+    const BandKnobs& kn = band_knobs();
+    const TaskArrays& a = rs.a;
+    hipStream_t s = c->stream, s2 = nullptr;
+    BandPlan bp;
+    bool gt_chunked = false, sweep_path = false;
+    uint32_t* d_cnt = nullptr;
+    const int* shape = kShapes[0];              // the masked DP's (rows per lane, lanes per record) for the batch's longest read
+    uint32_t *tight_list = nullptr, *tight_pack = nullptr, *dense_list = nullptr, *refine_list = nullptr, refine_cap = 0;   // band_diag_kernel's other outputs
+    // The general band kernel (tasks band_run_kernel could not hold) is a handful of serial lanes: ~4.5 ms of latency for 0.1 % of config 3.  It runs on a side
+    // stream, with its own hard list; started once the overflow list is complete, finished (slabs grow until every task fits) after the main path's launches are queued.
+    struct { uint32_t n_over = 0, cap2 = 0, todo = 0, off = 0, total = 0; const uint32_t* tasks = nullptr; bool active = false; uint32_t n_hard = 0, n_again = 0; } fb;
+    uint32_t cnt[VTX_CNT_PENDING + 1] = {0};    // host copy of the block's first words
+    uint32_t pending_total = 0, over_before = 0, resweep_total = 0;
+    uint64_t diag_total = 0, diag_left = 0, refined_total = 0, checked_total = 0, swept_total = 0, diag2_total = 0, diag2_scored = 0, tight2_total = 0, stream_total = 0;
+    float diag_ms = 0, check_ms = 0, sweep_ms = 0;
+    bool sweep_used = false;                    // some chunk took the round-4 path
+    bool sweep_pending = false;                 // the events of a swept chunk have not been read yet
+    bool sweep_forked = false;                  // ... and that chunk ran its two branches side by side
+    uint32_t fork_nt = 0;
+    // one chunk of tasks [base, base + nt): the loci whose tables are resident, and what band_diag_kernel left for band_run_kernel
+    struct Chunk { uint64_t base; uint32_t nt; bool last; uint32_t gt_l0 = 0, gt_n = 0; bool diag = false, swept = false; uint32_t n_fail = 0; const uint32_t* fail_list = nullptr; };
+    BandPass(vtx_ctx* c_, RunState& rs_, uint32_t mh_, uint32_t mh_min_, uint64_t t_begin_, uint64_t t_end_, bool chunk_tables_) : c(c_), rs(rs_), mh(mh_), mh_min(mh_min_), t_begin(t_begin_), t_end(t_end_),
+             chunk_tables(chunk_tables_) {}
+    int run() {
+        bp = band_plan(c->n_records, c->n_loci, mh);
+        if (int rc = band_reserve(c, bp, false)) return rc;
+        gt_chunked = bp.gt_bytes && (bp.gt_loci < c->n_loci || chunk_tables);
+        d_cnt = c->d_cnt.as<uint32_t>();
+        int sh = 0;
+        while ((uint32_t)(kShapes[sh][0] * kShapes[sh][1]) < c->max_read_len) ++sh;
+        shape = kShapes[sh];
+        if (!c->stream2) {
+            HIP_TRY(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
+            HIP_TRY(c, hipEventCreateWithFlags(&c->ev2, hipEventDisableTiming));
+            HIP_TRY(c, hipHostMalloc((void**)&c->h_pin, PIN_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+        }
+        s2 = c->stream2;
+        // Round 4's path (sweep + masked DP for what the certificate stages leave), or round 3's (VTX_BAND_LEGACY=1; a haplotype above 255 bases)
+        sweep_path = !kn.legacy && mh <= vtxk_band_sweep_max_len() && mh > 0;
+        tight_list = (sweep_path && !kn.no_tight) ? c->d_tight.as<uint32_t>() : nullptr;
+        tight_pack = tight_list ? c->d_tight_pack.as<uint32_t>() : nullptr;
+        // dense list: the tasks whose vtxf::Why is in kn.dense_mask (default W_MATCHES: repeats) skip band_run_kernel and take band_sweep_kernel at once
+        dense_list = sweep_path ? c->d_dense.as<uint32_t>() : nullptr;
+        refine_cap = band_refine_cap(bp.chunk);
+        refine_list = kn.no_refine ? nullptr : c->d_refine.as<uint32_t>();
+        HIP_TRY(c, hipMemsetAsync(d_cnt, 0, VTX_CNT_WORDS * sizeof(uint32_t), s));
+        for (uint64_t base = t_begin; base < t_end; base += bp.chunk) {
+            Chunk ch{base, (uint32_t)std::min<uint64_t>(bp.chunk, t_end - base), base + bp.chunk >= t_end};
+            ch.fail_list = c->d_fail.as<uint32_t>();
+            if (int rc = resident_tables(ch)) return rc;
+            if (ch.gt_n && !kn.no_diag) { if (int rc = diag_stage(ch)) return rc; }
+            if (int rc = run_stage(ch)) return rc;
+            if (sweep_used && ch.last) { if (int rc = last_chunk()) return rc; }
+        }
+        return publish();
+    }
+    // src == nullptr: the band slots already hold arrays (or the full-matrix marker), one slot per task
+    int masked_dp(uint32_t n_hard, uint32_t* hard, const uint16_t* src, uint16_t* band, uint32_t n_slots, hipStream_t st, uint8_t code) {
+        if (rs.stage) HIP_TRY(c, vtxk_mark_stage(hard, n_hard, nullptr, code, rs.stage, st));
+        for (uint32_t off = 0; off < n_hard; off += n_slots) {
+            const uint32_t cnt_s = std::min(n_slots, n_hard - off);
+            HIP_TRY(c, launch_band_expand(a, hard + off, cnt_s, src ? src + (size_t)off * bp.poly_stride : band, src ? bp.poly_stride : 2 * bp.band_stride, band, bp.band_stride, st));
+            HIP_TRY(c, launch_sw_banded(a, shape, cnt_s, hard + off, band, bp.band_stride, mh, st));
+            rs.launches += 2;
+        }
+        return VTX_OK;
+    }
+    // the half of d_over2 the general kernel's current list is not in: where it writes the tasks that need a larger slab
+    uint32_t* fallback_other() const { return c->d_over2.as<uint32_t>() + ((fb.tasks == c->d_over2.as<uint32_t>()) ? fb.n_over : 0); }
+    int fallback_launch() {
+        // A few overflow tasks (shallow data: some hundreds per run) first try the in-LDS variant of the general kernel
+        // with a slab for kLdsMatches k-mer matches: their ~2 ms of serial HBM latency were a third of a shallow step.
+        const uint32_t kLdsMatches = 512;
+        const uint64_t worst = (uint64_t)c->max_read_len * mh;
+        if (fb.cap2 >= worst && fb.cap2 >= 512) return fail(c, VTX_E_STATE, "vtx_run: band kernel overflow with a worst-case slab");
+        // first three rounds: the cooperative kernel, everything in LDS (band_coop_kernel: a wavefront per task, up to 512 matches,
+        // then 1024, then 4096; reads up to 256 bases); what that cannot hold takes the serial kernel below
+        const int tier = fb.cap2 < 512 ? 0 : (fb.cap2 == 512 ? 1 : (fb.cap2 == 1024 ? 2 : -1));
+        const uint32_t tier_cap = tier == 0 ? 512u : (tier == 1 ? 1024u : 4096u);
+        // (haplotypes up to 1000 bases: the kernel walks its Fenwick tree in ten unrolled steps, tn = n + 8 < 1024)
+        const bool coop = tier >= 0 && !kn.no_coop && c->max_read_len <= 256 && mh <= 1000 && vtxk_band_coop_lds(mh, tier_cap) <= 64u * 1024;
+        if (coop) {
+            fb.cap2 = tier_cap;
+            HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_GENERAL_AGAIN, 0, sizeof(uint32_t), s2));
+            HIP_TRY(c, launch_band_coop(a, tier, fb.tasks, fb.todo, mh, c->d_band2.as<uint16_t>(), bp.band_stride, c->d_hard2.as<uint32_t>(), fallback_other(), d_cnt + VTX_CNT_GENERAL_HARD, s2));
+        } else {
+            const bool in_lds = fb.cap2 < 512 && fb.todo <= kn.lds_tasks && !VTX_DEV_ENV("VTX_BAND_NO_LDS_FALLBACK") && vtxk_band_lds_stride(kLdsMatches, mh, c->max_read_len) <= 160 * 1024 - 512;
+            fb.cap2 = in_lds ? kLdsMatches : (uint32_t)std::max<uint64_t>(std::min<uint64_t>((uint64_t)fb.cap2 * 16, worst), 512);
+            const size_t stride2 = vtxk_band_ws_stride(fb.cap2, mh);
+            if (!in_lds) {                                                  // whole wavefronts: the 64 slabs are interleaved, vtxk_band_lanes() of them in use
+                const size_t lanes = vtxk_band_lanes(fb.todo);
+                HIP_TRY(c, c->d_band_ws2.reserve(lanes < 64 ? (size_t)fb.todo * stride2 : ((size_t)fb.todo + 63) / 64 * 64 * stride2));   // (sparse lanes: a contiguous slab per task)
+            }
+            HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_GENERAL_AGAIN, 0, sizeof(uint32_t), s2));
+            HIP_TRY(c, launch_band(a, fb.tasks, fb.todo, c->d_band_ws2.as<uint8_t>(), stride2, fb.cap2, mh, c->d_band2.as<uint16_t>(), bp.band_stride, c->d_hard2.as<uint32_t>(), fallback_other(), d_cnt + VTX_CNT_GENERAL_HARD,
+                    in_lds ? 1 : 0, c->max_read_len, s2));
+        }
+        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_GENERAL_HARD, d_cnt + VTX_CNT_GENERAL_HARD, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s2));   // pinned: does not block
+        ++rs.launches;
+        return VTX_OK;
+    }
+    int fallback_start(uint32_t off, uint32_t total) {   // the overflow list d_over[0, total) is complete and visible
+        const uint32_t n_over = std::min(std::max(bp.slots, 1024u), total - off);   // slices (bounds d_band2)
+        fb.off = off; fb.total = total; fb.n_over = n_over; fb.todo = n_over; fb.cap2 = 512 / 16; fb.tasks = c->d_over.as<uint32_t>() + off; fb.active = true;
+        HIP_TRY(c, c->d_over2.reserve(2 * (size_t)n_over * sizeof(uint32_t)));
+        HIP_TRY(c, c->d_hard2.reserve((size_t)n_over * sizeof(uint32_t)));
+        HIP_TRY(c, c->d_band2.reserve((size_t)n_over * 2 * bp.band_stride * sizeof(uint16_t)));
+        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_GENERAL_HARD, 0, 2 * sizeof(uint32_t), s2));
+        return fallback_launch();
+    }
+    int fallback_finish() {
+        if (!fb.active) return VTX_OK;
+        for (;;) {
+            for (;;) {
+                HIP_TRY(c, hipStreamSynchronize(s2));
+                fb.n_hard = c->h_pin[PIN_GENERAL_HARD]; fb.n_again = c->h_pin[PIN_GENERAL_AGAIN];
+                // tasks that still do not fit were written to the other half of d_over2: rerun them with a larger slab
+                fb.tasks = fallback_other();
+                fb.todo = fb.n_again;
+                if (!fb.todo) break;
+                if (int rc = fallback_launch()) return rc;
+            }
+            if (int rc = masked_dp(fb.n_hard, c->d_hard2.as<uint32_t>(), nullptr, c->d_band2.as<uint16_t>(), std::max(fb.n_hard, 1u), s2, VTX_STAGE_GENERAL_DP)) return rc;
+            rs.hard_total += fb.n_hard;
+            if (fb.off + fb.n_over >= fb.total) break;
+            if (int rc = fallback_start(fb.off + fb.n_over, fb.total)) return rc;      // next slice (same stream: in order)
+        }
+        HIP_TRY(c, hipEventRecord(c->ev2, s2));
+        HIP_TRY(c, hipStreamWaitEvent(s, c->ev2, 0));             // the reduction kernels read every score
+        return VTX_OK;
+    }
+    // the band of every listed task (band_sweep_kernel), one slice of band slots at a time, then the masked DP over the slice (its length — the tasks the sweep did not decline — is read on the
+    // device: counters[0]; declined: counters[1]) (libvtx_dev.so, VTX_SWEEP_V1=1: round 4's kernel instead — 256 sections per task (tier 0), then a second pass with 1 024 (tier 1) over what the
+    // first declined.  tier means nothing to band_sweep_kernel: the production build ignores it; the parameter stays so that the callers read the same in both builds.)
+    int sweep_slices([[maybe_unused]] int tier, const uint32_t* list, uint32_t n, uint32_t* over_out, uint32_t* counters) {
+        uint32_t* why = kn.sweep_stats ? d_cnt + VTX_CNT_SWEEP_WHY : nullptr;
+        HIP_TRY(c, c->d_sweep_log.reserve(vtxk_band_sweep_log_bytes()));
+        for (uint32_t off = 0; off < n; off += bp.slots) {
+            const uint32_t cnt_s = std::min(bp.slots, n - off);
+            HIP_TRY(c, hipMemsetAsync(counters, 0, sizeof(uint32_t), s));
+#ifdef VTX_DEVTOOLS
+            if (kn.sweep_v1) HIP_TRY(c, launch_band_sweep_v1(a, tier, list + off, cnt_s, c->d_band.as<uint16_t>(), bp.band_stride, c->d_hard.as<uint32_t>(), over_out, counters, why, rs.stage, s));
+            else
+#endif
+            HIP_TRY(c, launch_band_sweep(a, list + off, cnt_s, c->d_band.as<uint16_t>(), bp.band_stride, c->d_hard.as<uint32_t>(), over_out, counters, why, rs.stage, c->d_sweep_log.as<uint32_t>(), s));
+            HIP_TRY(c, launch_sw_banded_dev(a, shape, cnt_s, c->d_hard.as<uint32_t>(), counters, c->d_band.as<uint16_t>(), bp.band_stride, mh, s));
+            rs.launches += 2;
+        }
+        return VTX_OK;
+    }
+    // Second stage (round 5; DESIGN.md 4.3.3b, where its threshold of 700 k tasks is measured): band_diag2_kernel, band_stream_kernel for what exceeds its list, the full-matrix check + masked DP
+    // over the one-diagonal bands they prove; what they leave — out[0, *n_out) — takes the sweep.  One host round trip for the counts. The tables of the tasks' loci have to be resident (gt_l0:
+    // first locus of the table buffer).
+    bool second_stage_on(uint32_t n) const { return !kn.no_diag2 && n >= kn.diag2_min && mh <= 255; }
+    int second_stage(const uint32_t* list, uint32_t n, uint32_t gt_l0, uint32_t* out, uint32_t* n_out) {
+        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_DIAG2_LEFT, 0, 2 * sizeof(uint32_t), s));
+        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_STREAMED, 0, sizeof(uint32_t), s));
+        HIP_TRY(c, launch_band_diag2(a, list, n, mh, bp.tasks_per_locus, gt_l0, c->d_gtables.as<uint8_t>(), out, c->d_tight2.as<uint32_t>(), c->d_tight2_pack.as<uint32_t>(), d_cnt + VTX_CNT_DIAG2_LEFT,
+                kn.no_stream ? nullptr : c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), d_cnt + VTX_CNT_STREAMED, rs.stage, s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_DIAG2_LEFT, d_cnt + VTX_CNT_DIAG2_LEFT, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_STREAMED, d_cnt + VTX_CNT_STREAMED, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        stream_total += std::min(c->h_pin[PIN_STREAMED], n);
+        const uint32_t n_sweep = std::min(c->h_pin[PIN_DIAG2_LEFT], n);
+        const uint32_t n_tight2 = std::min(c->h_pin[PIN_DIAG2_TIGHT], n - n_sweep);
+        ++rs.launches;
+        diag2_total += n; diag2_scored += n - n_sweep - n_tight2;
+        if (n_tight2) {
+            // certificate == full-matrix score decides practically all of them (cert <= banded <= full); the masked DP for the rest (count on the device)
+            HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_CHECK2, 0, sizeof(uint32_t), s));
+            HIP_TRY(c, launch_sw_check(a, shape, n_tight2, c->d_tight2.as<uint32_t>(), c->d_tight2_pack.as<uint32_t>(), nullptr, mh, c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), d_cnt + VTX_CNT_CHECK2, rs.stage, s));
+            HIP_TRY(c, launch_sw_diag_band(a, shape, n_tight2, c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), d_cnt + VTX_CNT_CHECK2, mh, rs.stage, s));
+            // (its grid is sized for n_tight2 although a few hundred tasks remain: the workgroups past the device count leave at once)
+            rs.launches += 2;
+            tight2_total += n_tight2;
+        }
+        *n_out = n_sweep; return 0;
+    }
+    int collect_sweep_times() {
+        if (!sweep_pending) return VTX_OK;
+        sweep_pending = false;
+        HIP_TRY(c, hipEventSynchronize(c->ev[EV_SWEEP_END]));
+        float ms = 0;
+        // BRANCH_START .. BRANCH_END: band_refine_kernel (forked only) + the one-diagonal bands' masked DP; then band_sweep_kernel + its
+        // masked DP (the chunk's repeats) — forked: FORK_START .. SWEEP_END on the main stream, BESIDE the first interval, not after it
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_BRANCH_START], c->ev[EV_BRANCH_END])); check_ms += ms;
+        HIP_TRY(c, hipEventElapsedTime(&ms, sweep_forked ? c->ev[EV_FORK_START] : c->ev[EV_BRANCH_END], c->ev[EV_SWEEP_END])); sweep_ms += ms;
+        if (sweep_forked) checked_total += std::min(c->h_pin[PIN_FORK_TIGHT], fork_nt);          // (copied before BRANCH_END, which SWEEP_END waited for)
+        sweep_forked = false;
+        return VTX_OK;
+    }
+    // Sorts list[0, n) by task into `sorted` when it has more than 64 entries and the temporary buffer can be had; *at = where the list then is.  (Lists come out in the order the wavefronts
+    // finished: eight XCD ranges interleaved.  Sorted, neighbours share their loci's tables, haplotypes and reads again — 12.7 -> GB of L2 misses for 2 % of the tasks otherwise — and the hard
+    // list comes out in a fixed order.)
+    int sort_by_task(uint32_t* list, uint32_t* sorted, uint32_t n, const uint32_t** at) {
+        *at = list;
+        if (n <= 64) return VTX_OK;
+        const size_t tb = vtxk_sort_keys_u32_temp_bytes(n);
+        if (c->d_fail_tmp.reserve(tb) != hipSuccess) { (void)hipGetLastError(); return VTX_OK; }
+        HIP_TRY(c, vtxk_sort_keys_u32(list, sorted, n, c->d_fail_tmp.p, tb, s));
+        *at = sorted;
+        return VTX_OK;
+    }
+    // the chunk's counters, and the loci of this range of tasks (tables in global memory are built per range)
+    int resident_tables(Chunk& ch) {
+        if (int rc = collect_sweep_times()) return rc;                              // (a chunk re-records the events)
+        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_HARD, 0, sizeof(uint32_t), s));
+        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_PENDING, 0, sizeof(uint32_t), s));
+        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_BLOCK, 0, 8 * sizeof(uint32_t), s));
+        ch.gt_l0 = 0; ch.gt_n = bp.gt_bytes ? c->n_loci : 0;
+        if (gt_chunked) {
+            uint32_t ends[2];
+            HIP_TRY(c, hipMemcpyAsync(&ends[0], a.rec_locus + ch.base / 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(&ends[1], a.rec_locus + (ch.base + ch.nt - 1) / 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            ch.gt_l0 = ends[0]; ch.gt_n = ends[1] - ends[0] + 1;
+            if (ch.gt_n > bp.gt_loci) ch.gt_n = 0;              // does not fit after all: tables in LDS for this chunk
+        }
+        c->gt_used = (ch.gt_n && bp.gt_loci) ? (uint64_t)ch.gt_n * (bp.gt_bytes / bp.gt_loci) : 0;     // (gt_bytes = gt_loci x bytes per locus)
+        HIP_TRY(c, hipEventRecord(c->ev[EV_CHUNK_START], s));
+        return VTX_OK;
+    }
+    // Stage 1 (tables in global memory): band_diag_kernel decides the tasks whose alignment lives on one diagonal
+    // (vtx_fast_core.h) and lists the others; band_run_kernel then takes that LIST instead of the whole range.
+    int diag_stage(Chunk& ch) {
+        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_RUN_LEFT, 0, 4 * sizeof(uint32_t), s));   // RUN_LEFT, DENSE, REFINE, TIGHT
+        const uint32_t tail_cap = (uint32_t)std::min<size_t>(band_tail_cap(bp.chunk), c->d_tail.cap / (vtxk_band_tail_words() * sizeof(uint32_t)));
+        const uint32_t tail_cap_hook = VTX_DEV_ENV("VTX_DIAG_TAIL_CAP") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_TAIL_CAP")) : 0xffffffffu;   // test hook: a small buffer (read per run)
+        const hipError_t e = launch_band_diag(a, ch.nt, (uint32_t)ch.base, mh, mh_min, c->d_fail.as<uint32_t>(), refine_list, refine_cap, d_cnt, bp.tasks_per_locus, ch.gt_l0, ch.gt_n, c->d_gtables.as<uint8_t>(), bp.gt_bytes,
+                                              kn.diag_stats, tight_list, tight_pack, rs.stage, dense_list, kn.dense_mask, c->max_read_len, c->d_tail.as<uint32_t>(), std::min(tail_cap, tail_cap_hook), s);
+        if (e != hipSuccess) {
+            // (the tables do not fit the buffer for this chunk: band_run_kernel alone, tables in LDS)
+            if (getenv("VTX_DEBUG")) fprintf(stderr, "[vtx] band_diag_kernel not launched for tasks [%llu, +%u): %s\n", (unsigned long long)ch.base, ch.nt, hipGetErrorString(e));
+            (void)hipGetLastError(); return VTX_OK;
+        }
+        return sweep_path ? diag_sweep_path(ch) : diag_round3_path(ch);
+    }
+    // the records band_diag_kernel left: with a tight list (round 6) every task that holds a certificate and a one-diagonal
+    // band, for band_corridor_kernel; else (VTX_BAND_NO_TIGHT, libvtx_dev.so's VTX_BAND_NO_CORRIDOR) round 3's, for band_refine_kernel
+    hipError_t second_look(const Chunk& ch, uint32_t n_rec, hipStream_t st) {
+        if (tight_list && !kn.no_corridor) return launch_band_corridor(a, refine_list, n_rec, d_cnt, kn.diag_stats, tight_list, tight_pack, rs.stage, d_cnt + VTX_CNT_REFINE, st);
+        return launch_band_refine(a, refine_list, n_rec, mh, c->d_fail.as<uint32_t>(), d_cnt, bp.tasks_per_locus, ch.gt_l0, c->d_gtables.as<uint8_t>(), kn.diag_stats, tight_list, tight_pack, rs.stage, d_cnt + VTX_CNT_REFINE, st);
+    }
+    // What the stage left, in two branches over disjoint tasks: side stream — band_refine_kernel / band_corridor_kernel over its records, then the masked DP over the
+    // one-diagonal bands; this stream — band_sweep_kernel + masked DP over the repeats and the short fail list.  One host round trip, right after band_diag_kernel.  (VTX_BAND_NO_TIGHT: the
+    // refinement's leftovers go to the fail list, so everything stays in order on this stream.)
+    int diag_sweep_path(Chunk& ch) {
+        ch.diag = true; ch.swept = true; sweep_used = true;
+        HIP_TRY(c, hipEventRecord(c->ev[EV_DIAG_END], s));
+        const bool fork = tight_list != nullptr && !kn.no_fork;
+        hipStream_t sb = fork ? s2 : s;                                             // the refine / one-diagonal branch
+        if (!fork && refine_list) HIP_TRY(c, second_look(ch, std::min(refine_cap, ch.nt), s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_RUN_LEFT, d_cnt + VTX_CNT_RUN_LEFT, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // RUN_LEFT, DENSE, REFINE, TIGHT
+        HIP_TRY(c, hipStreamSynchronize(s));
+        const uint32_t n_refine = std::min(c->h_pin[PIN_REFINE], refine_cap);
+        // (forked: the tight list still grows by what the refinement leaves — at most its records)
+        const uint32_t n_tight = (uint32_t)std::min<uint64_t>((uint64_t)c->h_pin[PIN_TIGHT] + (fork && refine_list ? n_refine : 0u), ch.nt);
+        refined_total += n_refine;
+        rs.launches += 2;
+        if (fork) HIP_TRY(c, hipStreamWaitEvent(s2, c->ev[EV_DIAG_END], 0));
+        HIP_TRY(c, hipEventRecord(c->ev[EV_BRANCH_START], sb));
+        if (fork && refine_list && n_refine) HIP_TRY(c, second_look(ch, n_refine, sb));
+        if (n_tight) { if (int rc = one_diagonal_dp(n_tight, fork, sb)) return rc; }
+        if (fork) HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_FORK_TIGHT, d_cnt + VTX_CNT_TIGHT, sizeof(uint32_t), hipMemcpyDeviceToHost, sb));   // the list's final length (read in collect_sweep_times)
+        HIP_TRY(c, hipEventRecord(c->ev[EV_BRANCH_END], sb));
+        if (fork) HIP_TRY(c, hipEventRecord(c->ev[EV_FORK_START], s));                          // (this stream's branch starts here)
+        ch.n_fail = c->h_pin[PIN_RUN_LEFT];
+        const uint32_t n_dense = std::min(c->h_pin[PIN_DENSE], ch.nt);
+        if (!fork) checked_total += n_tight;                                    // (forked: the exact count arrives with the events)
+        diag_total += ch.nt; diag_left += (uint64_t)ch.n_fail + n_dense;
+        if (int rc = repeats(ch, n_dense)) return rc;
+        // the others: band_run_kernel (task-list mode) in run_stage — seeds, chain and the general certificate (a read against the
+        // other allele of an indel lies on TWO diagonals: cert == ub decides nearly all of those without a DP cell)
+        if (int rc = sort_by_task(c->d_fail.as<uint32_t>(), c->d_fail.as<uint32_t>() + ch.nt, ch.n_fail, &ch.fail_list)) return rc;
+        if (fork) HIP_TRY(c, hipStreamWaitEvent(s, c->ev[EV_BRANCH_END], 0));                    // join: what follows reads every score
+        HIP_TRY(c, hipEventRecord(c->ev[EV_SWEEP_END], s));
+        sweep_pending = true; sweep_forked = fork; fork_nt = ch.nt;
+        return VTX_OK;
+    }
+    // tasks with a certificate but no verdict: their band is one diagonal stretch (tight_pack): the masked DP expands it itself.  (VTX_BAND_CHECK=1: the full-matrix check first — full == cert
+    // decides a task, cert <= banded <= full; measured: 5.6 ns per task against 10 for the DP it saves on 20 - 30 % of noisy reads.)
+    int one_diagonal_dp(uint32_t n_tight, bool fork, hipStream_t sb) {
+        const uint32_t *dp_list = tight_list, *dp_pack = tight_pack, *dp_cnt = fork ? d_cnt + VTX_CNT_TIGHT : nullptr;
+        if (kn.use_check) {
+            HIP_TRY(c, c->d_dband.reserve((size_t)bp.chunk * sizeof(uint32_t)));
+            HIP_TRY(c, c->d_dband_pack.reserve((size_t)bp.chunk * sizeof(uint32_t)));
+            HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_CHECK, 0, sizeof(uint32_t), sb));
+            HIP_TRY(c, launch_sw_check(a, shape, n_tight, tight_list, tight_pack, dp_cnt, mh, c->d_dband.as<uint32_t>(), c->d_dband_pack.as<uint32_t>(), d_cnt + VTX_CNT_CHECK, rs.stage, sb));
+            dp_list = c->d_dband.as<uint32_t>(); dp_pack = c->d_dband_pack.as<uint32_t>(); dp_cnt = d_cnt + VTX_CNT_CHECK;
+            ++rs.launches;
+        }
+        HIP_TRY(c, launch_sw_diag_band(a, shape, n_tight, dp_list, dp_pack, dp_cnt, mh, rs.stage, sb));
+        ++rs.launches;
+        return VTX_OK;
+    }
+    // repeats: band_sweep_kernel (the band of ANY task) + masked DP, sorted by task; what it declines waits in d_over[2 n_tasks ..) for the second pass after the last chunk (a short list of the
+    // other tasks is not worth band_run_kernel's launch — a persistent grid: ~1 ms whatever the count — and the two host round trips behind it: it joins the repeats, ~25 ns per task)
+    int repeats(Chunk& ch, uint32_t n_dense) {
+        if (ch.n_fail && ch.n_fail < kn.run_min && (uint64_t)n_dense + ch.n_fail <= ch.nt) {
+            HIP_TRY(c, hipMemcpyAsync(dense_list + n_dense, c->d_fail.as<uint32_t>(), (size_t)ch.n_fail * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+            n_dense += ch.n_fail;
+            ch.n_fail = 0;
+        }
+        if (!n_dense) return VTX_OK;
+        const uint32_t* dl = nullptr;
+        if (int rc = sort_by_task(dense_list, dense_list + ch.nt, n_dense, &dl)) return rc;
+        // Second stage (round 5): band_diag2_kernel + band_stream_kernel + the full-matrix check
+        const uint32_t* sl = dl;
+        uint32_t n_sweep = n_dense;
+        if (second_stage_on(n_dense)) {
+            uint32_t* sweep2 = (dl == dense_list) ? dense_list + ch.nt : dense_list;          // (the half of d_dense the list is not in)
+            if (int rc = second_stage(dl, n_dense, ch.gt_l0, sweep2, &n_sweep)) return rc;
+            sl = sweep2;
+        }
+        if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, c->d_over.as<uint32_t>() + 2 * bp.n_tasks, d_cnt + VTX_CNT_SWEEP_HARD)) return rc; }
+        swept_total += n_sweep;
+        return VTX_OK;
+    }
+    // round 3's path (VTX_BAND_LEGACY, or a haplotype above band_sweep_kernel's 255 bases): band_refine_kernel, then band_run_kernel over the fail list
+    int diag_round3_path(Chunk& ch) {
+        ch.diag = true;
+        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_RUN_LEFT, d_cnt + VTX_CNT_RUN_LEFT, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_R3_REFINE, d_cnt + VTX_CNT_REFINE, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipEventRecord(c->ev[EV_DIAG_END], s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        ch.n_fail = c->h_pin[PIN_RUN_LEFT];
+        const uint32_t n_refine = std::min(c->h_pin[PIN_R3_REFINE], refine_cap);
+        if (n_refine) {
+            HIP_TRY(c, launch_band_refine(a, refine_list, n_refine, mh, c->d_fail.as<uint32_t>(), d_cnt, bp.tasks_per_locus, ch.gt_l0, c->d_gtables.as<uint8_t>(), kn.diag_stats, nullptr, nullptr, rs.stage, nullptr, s));
+            HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_RUN_LEFT, d_cnt + VTX_CNT_RUN_LEFT, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            ch.n_fail = c->h_pin[PIN_RUN_LEFT];
+            refined_total += n_refine;
+            ++rs.launches;
+        }
+        diag_total += ch.nt; diag_left += ch.n_fail;
+        ++rs.launches;
+        return sort_by_task(c->d_fail.as<uint32_t>(), c->d_fail.as<uint32_t>() + ch.nt, ch.n_fail, &ch.fail_list);
+    }
+    // band_run_kernel over what is left (the whole range when band_diag_kernel did not run), its second chance and pending records,
+    // the masked DP over its hard list; after the last chunk of a pass without a sweep, the general kernel's start
+    int run_stage(Chunk& ch) {
+        HIP_TRY(c, hipEventRecord(c->ev[EV_BAND_RUN_START], s));
+        if (!ch.diag || ch.n_fail) HIP_TRY(c, launch_band_run(a, ch.diag ? ch.n_fail : ch.nt, ch.diag ? 0u : (uint32_t)ch.base, mh, mh_min, c->d_band_ws.as<uint32_t>(), c->d_poly.as<uint16_t>(), bp.poly_stride / 2,
+            c->d_hard.as<uint32_t>(), c->d_over.as<uint32_t>(), c->d_pend.as<uint32_t>(), c->d_pend_buf.as<uint32_t>(), bp.hard_cap, bp.pend_cap, d_cnt, bp.tasks_per_locus, ch.gt_l0, ch.gt_n,
+            ch.gt_n ? c->d_gtables.as<uint8_t>() : nullptr, bp.gt_bytes, ch.diag ? ch.fail_list : nullptr, c->band_long_lists ? 1 : 0, s));
+        HIP_TRY(c, hipEventRecord(c->ev[EV_BAND_RUN_END], s));                  // (complete once the read-back below is: no synchronisation of its own)
+        const bool run_skipped = ch.swept && ch.n_fail == 0;             // nothing went to band_run_kernel: its counters are what they were
+        if (run_skipped) {
+            cnt[VTX_CNT_HARD] = 0; cnt[VTX_CNT_PENDING] = 0; cnt[VTX_CNT_OVERFLOW] = over_before;
+        } else {
+            HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+        }
+        if (int rc = second_chance(ch)) return rc;
+        over_before = cnt[VTX_CNT_OVERFLOW];
+        float ms = 0;
+        if (!run_skipped) {
+            HIP_TRY(c, hipEventElapsedTime(&ms, ch.swept ? c->ev[EV_BAND_RUN_START] : c->ev[EV_CHUNK_START], c->ev[EV_BAND_RUN_END]));
+            rs.band_run_ms += ms;
+            if (int rc = collect_sweep_times()) return rc;
+        }
+        if (ch.diag) { HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_CHUNK_START], c->ev[EV_DIAG_END])); diag_ms += ms; }
+        if (!sweep_used && ch.last && cnt[VTX_CNT_OVERFLOW])      // last chunk: the overflow list is complete
+            if (int rc = fallback_start(0, cnt[VTX_CNT_OVERFLOW])) return rc;
+        if (cnt[VTX_CNT_HARD] > bp.hard_cap) {               // the excess went to the general kernel's list: slots in use = hard_cap
+            cnt[VTX_CNT_HARD] = bp.hard_cap;
+            HIP_TRY(c, hipMemcpyAsync(d_cnt + VTX_CNT_HARD, cnt + VTX_CNT_HARD, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        }
+        cnt[VTX_CNT_PENDING] = std::min(cnt[VTX_CNT_PENDING], bp.pend_cap);
+        if (cnt[VTX_CNT_PENDING]) {
+            // tasks whose piece list overflowed its LDS slots: the same certificate, from their pending records
+            HIP_TRY(c, vtxk_launch_band_pending(c->d_pend.as<uint32_t>(), cnt[VTX_CNT_PENDING], c->d_pend_buf.as<uint32_t>(), a.ref, a.alt, c->d_poly.as<uint16_t>(), bp.poly_stride / 2, c->d_hard.as<uint32_t>(), d_cnt, s));
+            HIP_TRY(c, hipMemcpyAsync(cnt + VTX_CNT_HARD, d_cnt + VTX_CNT_HARD, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            pending_total += cnt[VTX_CNT_PENDING];
+            ++rs.launches;
+        }
+        if (int rc = masked_dp(cnt[VTX_CNT_HARD], c->d_hard.as<uint32_t>(), c->d_poly.as<uint16_t>(), c->d_band.as<uint16_t>(), bp.slots, s, VTX_STAGE_RUN_DP)) return rc;
+        rs.hard_total += cnt[VTX_CNT_HARD];
+        ++rs.launches;
+        return VTX_OK;
+    }
+    // The six-wavefront variant of band_run_kernel keeps 12-entry lists: the tasks that overflowed them ([a0, a1) of the overflow list) get a second chance in the 15-entry variant before the
+    // general kernel — what overflows again is appended behind a1 and then moved down to a0. (task-list mode runs the 15-entry variant: nothing to give a second chance to)
+    int second_chance(const Chunk& ch) {
+        const bool short_lists = !ch.diag && ch.gt_n && vtxk_band_second_chance(bp.tasks_per_locus, c->band_long_lists ? 1 : 0);
+        if (short_lists && ch.nt >= (1u << 20)) {
+            // feedback for the next run of this context: many overflows of the 12-entry lists (noisy reads: 3.3 % of the
+            // tasks at 3 % substitution errors, 0.2 % at 0.5 %) make the 15-entry variant the better first pass
+            if ((uint64_t)(cnt[VTX_CNT_OVERFLOW] - over_before) * 50 > ch.nt) c->band_long_lists = true;
+        }
+        if (!short_lists || cnt[VTX_CNT_OVERFLOW] <= over_before) return VTX_OK;
+        const uint32_t a0 = over_before, a1 = cnt[VTX_CNT_OVERFLOW];
+        uint32_t* over = c->d_over.as<uint32_t>();
+        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_BLOCK, 0, 8 * sizeof(uint32_t), s));
+        HIP_TRY(c, launch_band_run(a, a1 - a0, 0, mh, mh_min, c->d_band_ws.as<uint32_t>(), c->d_poly.as<uint16_t>(), bp.poly_stride / 2, c->d_hard.as<uint32_t>(), over, c->d_pend.as<uint32_t>(), c->d_pend_buf.as<uint32_t>(),
+                bp.hard_cap, bp.pend_cap, d_cnt, bp.tasks_per_locus, ch.gt_l0, ch.gt_n, c->d_gtables.as<uint8_t>(), bp.gt_bytes, over + a0, 0, s));
+        HIP_TRY(c, hipEventRecord(c->ev[EV_BAND_RUN_END], s));
+        HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        const uint32_t again = cnt[VTX_CNT_OVERFLOW] - a1;          // <= a1 - a0: source and destination do not overlap
+        if (again) HIP_TRY(c, hipMemcpyAsync(over + a0, over + a1, (size_t)again * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        cnt[VTX_CNT_OVERFLOW] = a0 + again;
+        HIP_TRY(c, hipMemcpyAsync(d_cnt + VTX_CNT_OVERFLOW, cnt + VTX_CNT_OVERFLOW, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        ++rs.launches;
+        return VTX_OK;
+    }
+    // After the last chunk of a pass with a sweep.  What overflowed band_run_kernel's lists (d_over[0, nA)) takes band_sweep_kernel too; then everything the sweep declined — here and in the
+    // chunks' own sweeps: d_over[2 n_tasks, + nB), counted on the device — takes the general band kernel (round 4's kernel, libvtx_dev.so: first its second pass, [2 n_tasks + nB, + nC) is what
+    // is left).
+    int last_chunk() {
+        uint32_t *over = c->d_over.as<uint32_t>(), *declined = over + 2 * bp.n_tasks;
+        const uint32_t nA = cnt[VTX_CNT_OVERFLOW];
+        if (nA) {
+            // (these tasks left band_diag_kernel for another reason than their number of matches, and then overflowed band_run_kernel's piece lists: repeats as well — on real-sequence loci 0.9 M
+            // tasks.  The second stage first, when the tables of every locus are still resident.)
+            const uint32_t* sl = over;
+            uint32_t n_sweep = nA;
+            if (second_stage_on(nA) && bp.gt_bytes && !gt_chunked && nA <= bp.chunk && c->d_dense.cap >= (size_t)nA * sizeof(uint32_t)) {
+                if (int rc = second_stage(over, nA, 0, c->d_dense.as<uint32_t>(), &n_sweep)) return rc;
+                sl = c->d_dense.as<uint32_t>();
+            }
+            if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, declined, d_cnt + VTX_CNT_SWEEP_HARD)) return rc; }
+            swept_total += n_sweep;
+        }
+        uint32_t nB = 0, nC = 0;
+        HIP_TRY(c, hipMemcpyAsync(&nB, d_cnt + VTX_CNT_SWEEP_DECLINED, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (int rc = collect_sweep_times()) return rc;
+        if (nB && kn.sweep_v1) {                    // (round 4's kernel only: its second pass with the larger log)
+            resweep_total = nB;
+            if (int rc = sweep_slices(1, declined, nB, declined + nB, d_cnt + VTX_CNT_SWEEP2_HARD)) return rc;
+            HIP_TRY(c, hipMemcpyAsync(&nC, d_cnt + VTX_CNT_SWEEP2_DECLINED, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+        } else if (nB) {                            // what band_sweep_kernel declines (bytes outside ACGTN, > 255 bases, > 1 024 sections, a
+            nC = nB; nB = 0;                        // full stash bucket) takes the general band kernel
+        }
+        cnt[VTX_CNT_OVERFLOW] = nC;
+        if (nC) { if (int rc = fallback_start((uint32_t)(2 * bp.n_tasks) + nB, (uint32_t)(2 * bp.n_tasks) + nB + nC)) return rc; }
+        return VTX_OK;
+    }
+    // the general kernel's end; the pass's times and task counts ADDED to the run's; the VTX_DEBUG lines
+    int publish() {
+        const uint32_t fast_overflow = cnt[VTX_CNT_OVERFLOW];
+        if (getenv("VTX_DEBUG")) {
+            uint32_t why[VTX_CNT_DROPPED + 1], *run_why = why + VTX_CNT_RUN_WHY;
+            HIP_TRY(c, hipMemcpy(why, d_cnt, sizeof why, hipMemcpyDeviceToHost));
+            fprintf(stderr, "[vtx] band_run_kernel: %u tasks hard only because pieces were dropped from a full list\n", why[VTX_CNT_DROPPED]);
+            fprintf(stderr, "[vtx] band_run_kernel overflow reasons: bound=%u parked-full=%u log-full=%u other=%u traceback=%u\n", run_why[1], run_why[2], run_why[3], run_why[4], run_why[5]);
+        }
+        if (int rc = fallback_finish()) return rc;
+        c->fast_overflow += fast_overflow;
+        c->timing.diag_ms += diag_ms; c->timing.diag_left += (uint32_t)std::min<uint64_t>(diag_left, 0xffffffffull);
+        c->timing.check_ms += check_ms; c->timing.sweep_ms += sweep_ms;
+        c->timing.swept_tasks += (uint32_t)std::min<uint64_t>(swept_total, 0xffffffffull);
+        c->timing.resweep_tasks += resweep_total;
+        c->timing.diag2_tasks += (uint32_t)std::min<uint64_t>(diag2_total, 0xffffffffull);
+        c->timing.diag2_scored += (uint32_t)std::min<uint64_t>(diag2_scored, 0xffffffffull);
+        c->timing.diag2_streamed += (uint32_t)std::min<uint64_t>(stream_total, 0xffffffffull);
+        checked_total += tight2_total;                     // (one-diagonal bands of the second stage: the same masked DP)
+        c->timing.checked_tasks += (uint32_t)std::min<uint64_t>(checked_total, 0xffffffffull);
+        if (swept_total) rs.hard_total += (uint32_t)std::min<uint64_t>(swept_total - std::min<uint64_t>(swept_total, fast_overflow), 0xffffffffull);
+        rs.hard_total += (uint32_t)std::min<uint64_t>(checked_total, 0xffffffffull);      // (tasks with a certificate: masked DP over their diagonal band; with VTX_BAND_CHECK an upper bound)
+        if (getenv("VTX_DEBUG") && diag_total) {
+            uint32_t why[16];
+            HIP_TRY(c, hipMemcpy(why, d_cnt + VTX_CNT_DIAG_WHY, sizeof why, hipMemcpyDeviceToHost));
+            fprintf(stderr, "[vtx] band_refine_kernel: %llu tasks listed\n", (unsigned long long)refined_total);
+            fprintf(stderr, "[vtx] band_diag_kernel: %llu of %llu tasks left to band_run_kernel (%.2f %%), %.2f ms: shape=%u no-diagonal=%u pieces=%u matches=%u not-harmless=%u generic=%u not-tight=%u no-main=%u\n",
+                    (unsigned long long)diag_left, (unsigned long long)diag_total, 100.0 * (double)diag_left / (double)diag_total, (double)diag_ms, why[1], why[2], why[3], why[4], why[5], why[7], why[8], why[9]);
+        }
+        if (getenv("VTX_DEBUG") && diag2_total) fprintf(stderr, "[vtx] band_diag2_kernel: %llu tasks looked at, %llu scored, %llu left with a one-diagonal band, %llu to band_sweep_kernel (%llu through band_stream_kernel)\n",
+            (unsigned long long)diag2_total, (unsigned long long)diag2_scored, (unsigned long long)tight2_total, (unsigned long long)(diag2_total - diag2_scored - tight2_total), (unsigned long long)stream_total);
+        if (getenv("VTX_DEBUG")) fprintf(stderr, "[vtx] banded: %llu tasks, %u overflowed band_run_kernel, %u bounded by the pending kernel, %u hard\n", (unsigned long long)bp.n_tasks, fast_overflow, pending_total, rs.hard_total);
+        return VTX_OK;
+    }
+};
+
+// ---- vtx_run: its stages ----------------------------------------------------------------------------------------------------------
+// The banded stages ADD their times and task counts per pass (BandPass::publish): zeroed here, for every run — a run that does not enter them (an empty batch, a batch of slow records only) must
+// not report the previous batch's.  Then the test / audit hooks (vtx_set_debug): poison the score arrays so that a stage that fails to write a task's score cannot hide behind the previous run's
+// value; one byte per task saying which stage decided it (vtx_fetch_stage).
+int run_prologue(vtx_ctx* c, RunState& rs) {
     hipStream_t s = c->stream;
     const uint32_t nr = c->n_records;
     c->ran = false;
     c->fast_overflow = 0;
-    // the banded stages ADD their times and task counts per pass (band_pass below): zeroed here, for every run — a run that does not
-    // enter them (an empty batch, a batch of slow records only) must not report the previous batch's
     c->timing.diag_ms = c->timing.check_ms = c->timing.sweep_ms = 0;
     c->timing.diag_left = c->timing.checked_tasks = c->timing.swept_tasks = c->timing.resweep_tasks = 0;
     c->timing.diag2_tasks = c->timing.diag2_scored = c->timing.diag2_streamed = 0;
-    // test / audit hooks (vtx_set_debug): poison the score arrays so that a stage that fails to write a task's score cannot hide
-    // behind the previous run's value; one byte per task saying which stage decided it (vtx_fetch_stage)
-    uint8_t* stage = nullptr;
+    rs.a = TaskArrays{c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>()};
     if (c->stage_trace && nr) {
         HIP_TRY(c, c->d_stage.reserve(2 * (size_t)nr));
-        stage = c->d_stage.as<uint8_t>();
-        HIP_TRY(c, hipMemsetAsync(stage, c->cfg.aligner == VTX_ALIGNER_BANDED ? VTX_STAGE_UNKNOWN : VTX_STAGE_FULL_DP, 2 * (size_t)nr, s));
+        rs.stage = c->d_stage.as<uint8_t>();
+        HIP_TRY(c, hipMemsetAsync(rs.stage, c->cfg.aligner == VTX_ALIGNER_BANDED ? VTX_STAGE_UNKNOWN : VTX_STAGE_FULL_DP, 2 * (size_t)nr, s));
     }
     if (c->poison && nr) {
-        HIP_TRY(c, vtxk_fill_i32(c->d_ref.as<int32_t>(), nr, c->poison_value, s));
-        HIP_TRY(c, vtxk_fill_i32(c->d_alt.as<int32_t>(), nr, c->poison_value, s));
+        HIP_TRY(c, vtxk_fill_i32(rs.a.ref, nr, c->poison_value, s));
+        HIP_TRY(c, vtxk_fill_i32(rs.a.alt, nr, c->poison_value, s));
     }
-    HIP_TRY(c, hipEventRecord(c->ev[0], s));
-    uint32_t launches = 0;
-    bool any_lut = false;
-    const bool full_dp = c->cfg.aligner != VTX_ALIGNER_BANDED;      // the banded flavour never runs the full-matrix DP
+    HIP_TRY(c, hipEventRecord(c->ev[EV_START], s));
+    return VTX_OK;
+}
+// The full-matrix DP, one launch per bucket of records (the banded flavour never runs it), and the generic (byte-equality) kernel
+// again over the records with bytes outside ACGTN that the table kernels listed.
+int run_full_dp(vtx_ctx* c, RunState& rs) {
+    hipStream_t s = c->stream;
+    const BandKnobs& kn = band_knobs();
+    const TaskArrays& a = rs.a;
+    const uint32_t mh = c->max_hap_len;
+    uint32_t *work = c->d_work.as<uint32_t>(), *d_redo = c->d_redo.as<uint32_t>();
+    bool any_lut = false; const bool full_dp = c->cfg.aligner != VTX_ALIGNER_BANDED;
     for (const Bucket& bk : c->buckets) any_lut |= bk.lut || bk.duo;
     any_lut &= full_dp;
     if (any_lut) HIP_TRY(c, hipMemsetAsync(c->d_redo_cnt.p, 0, 16 * sizeof(uint32_t), s));
     for (size_t b = 0; full_dp && b < c->buckets.size(); ++b) {
         const Bucket& bk = c->buckets[b];
-        static const bool no_duo = VTX_DEV_ENV("VTX_DP_KERNEL") && !strcmp(VTX_DEV_ENV("VTX_DP_KERNEL"), "lut");
-        static const bool no_pair = VTX_DEV_ENV("VTX_DP_KERNEL") && !strcmp(VTX_DEV_ENV("VTX_DP_KERNEL"), "duo2");   // two-lookup prefix phase
-        const bool use_pair = bk.pair && !no_pair;
-        if (bk.duo && !no_duo) {
-            HIP_TRY(c, vtxk_launch_sw_full_duo(bk.R, bk.count, c->d_work.as<uint32_t>() + bk.offset, c->d_records.as<vtx_record>(),
-                                               c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(),
-                                               c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(),
-                                               c->max_hap_len, use_pair ? kPairLociCap : duo_loci_cap(c->max_hap_len),
-                                               c->d_redo.as<uint32_t>() + bk.offset, c->d_redo_cnt.as<uint32_t>() + b,
-                                               use_pair ? duo_pair_cols(c->max_hap_len) : 0u, s));
-        } else if (bk.lut) {
-            HIP_TRY(c, vtxk_launch_sw_full_lut(bk.R, bk.count, c->d_work.as<uint32_t>() + bk.offset, c->d_records.as<vtx_record>(),
-                                               c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(),
-                                               c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(),
-                                               c->max_hap_len, kLutLociCap, c->d_redo.as<uint32_t>() + bk.offset,
-                                               c->d_redo_cnt.as<uint32_t>() + b, s));
-        } else {
-            HIP_TRY(c, vtxk_launch_sw_full(bk.R, bk.GL, bk.count, c->d_work.as<uint32_t>() + bk.offset,
-                                           c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(),
-                                           c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(),
-                                           c->d_alt.as<int32_t>(), c->max_hap_len, s));
-        }
-        ++launches;
+        const bool use_pair = bk.pair && !kn.no_pair;
+        uint32_t* redo_cnt = c->d_redo_cnt.as<uint32_t>() + b;
+        if (bk.duo && !kn.no_duo) HIP_TRY(c, launch_sw_full_duo(a, bk.R, bk.count, work + bk.offset, mh, use_pair ? kPairLociCap : duo_loci_cap(mh), d_redo + bk.offset, redo_cnt, use_pair ? duo_pair_cols(mh) : 0u, s));
+        else if (bk.lut) HIP_TRY(c, launch_sw_full_lut(a, bk.R, bk.count, work + bk.offset, mh, kLutLociCap, d_redo + bk.offset, redo_cnt, s));
+        else HIP_TRY(c, launch_sw_full(a, bk.R, bk.GL, bk.count, work + bk.offset, mh, s));
+        ++rs.launches;
     }
     if (any_lut) {
-        // records with bytes outside ACGTN: the generic (byte-equality) kernel scores them
         uint32_t redo[16] = {0};
         HIP_TRY(c, hipMemcpyAsync(redo, c->d_redo_cnt.p, sizeof redo, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         for (size_t b = 0; b < c->buckets.size(); ++b) {
             const Bucket& bk = c->buckets[b];
             if (!(bk.lut || bk.duo) || !redo[b]) continue;
-            HIP_TRY(c, vtxk_launch_sw_full(bk.R, bk.GL, redo[b], c->d_redo.as<uint32_t>() + bk.offset, c->d_records.as<vtx_record>(),
-                                           c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(),
-                                           c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), c->max_hap_len, s));
-            ++launches;
+            HIP_TRY(c, launch_sw_full(a, bk.R, bk.GL, redo[b], d_redo + bk.offset, mh, s));
+            ++rs.launches;
         }
     }
-    uint32_t hard_total = 0;
-    float band_run_ms = 0;
-    HIP_TRY(c, hipEventRecord(c->ev[3], s));
-    if (c->cfg.aligner == VTX_ALIGNER_BANDED && nr) {
-        // One pass of the banded stages over tasks [t_begin, t_end) whose locus has its longer haplotype in (mh_min, mh] (the others
-        // are left alone); chunk_tables: the tables are built per chunk for the loci the chunk spans, whatever the buffer would hold.
-        auto band_pass = [&](const uint32_t mh, const uint32_t mh_min, const uint64_t t_begin, const uint64_t t_end, const bool chunk_tables) -> int {
-            // Banded flavour.  Per chunk of tasks (task = 2*record + hap), round 4 (the stages are described in vtx_band.hip's header):
-            // tables -> band_diag_kernel (+ band_refine_kernel): scores of the certified tasks, and three lists — tasks whose band is one
-            // diagonal stretch (masked DP straight from one word), repeats (band_sweep_kernel + masked DP), the others (band_run_kernel:
-            // seeds, chain, general certificate; its hard list -> expand -> masked DP).  What overflows band_run_kernel's lists joins the
-            // repeats after the last chunk; what band_sweep_kernel declines twice takes the general band kernel (side stream).
-            // Counters (d_cnt, 64 words, zeroed once per run unless noted): [0] hard / [1] overflow / [2..7] reasons / [10] / [11] pending of
-            // band_run_kernel (0 and 11 per chunk); [8], [9] general kernel; [12] tasks for band_run_kernel, [13] for band_sweep_kernel,
-            // [14] refine records, [15] one-diagonal bands (12..15 per chunk); [16..23] band_run_kernel's block counters; [24] full-matrix
-            // check; [26] / [27] hard (per slice) / declined of the sweep's first pass, [28] / [29] of its second; [32..47] reasons of
-            // band_diag_kernel; [56..63] reasons of band_sweep_kernel.
-            BandPlan bp = band_plan(nr, c->n_loci, mh);
-            if (int rc = band_reserve(c, bp, false)) return rc;
-            const uint64_t n_tasks = bp.n_tasks;
-            const uint32_t chunk = bp.chunk, band_stride = bp.band_stride, hard_cap = bp.hard_cap, pend_cap = bp.pend_cap;
-            const uint32_t slots = bp.slots, poly_stride = bp.poly_stride, tasks_per_locus = bp.tasks_per_locus;
-            const size_t gt_bytes = bp.gt_bytes;
-            const bool gt_chunked = gt_bytes && (bp.gt_loci < c->n_loci || chunk_tables);
-            uint32_t fast_overflow = 0;
-            uint32_t* d_cnt = c->d_cnt.as<uint32_t>();
-            int shape = 0;
-            while ((uint32_t)(kShapes[shape][0] * kShapes[shape][1]) < c->max_read_len) ++shape;
-            // src == nullptr: the band slots already hold arrays (or the full-matrix marker), one slot per task
-            auto masked_dp = [&](uint32_t n_hard, uint32_t* hard, const uint16_t* src, uint16_t* band, uint32_t n_slots, hipStream_t st, uint8_t code) -> int {
-                if (stage) HIP_TRY(c, vtxk_mark_stage(hard, n_hard, nullptr, code, stage, st));
-                for (uint32_t off = 0; off < n_hard; off += n_slots) {
-                    const uint32_t cnt_s = std::min(n_slots, n_hard - off);
-                    HIP_TRY(c, vtxk_launch_band_expand(hard + off, cnt_s, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                                       c->d_loci.as<vtx_locus>(), src ? src + (size_t)off * poly_stride : band,
-                                                       src ? poly_stride : 2 * band_stride, band, band_stride, st));
-                    HIP_TRY(c, vtxk_launch_sw_banded(kShapes[shape][0], kShapes[shape][1], cnt_s, hard + off, c->d_records.as<vtx_record>(),
-                                                     c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(),
-                                                     c->d_hap.as<uint8_t>(), band, band_stride, c->d_ref.as<int32_t>(),
-                                                     c->d_alt.as<int32_t>(), mh, st));
-                    launches += 2;
-                }
-                return VTX_OK;
-            };
-            // The general band kernel (tasks band_run_kernel could not hold) is a handful of serial lanes: ~4.5 ms of latency
-            // for 0.1 % of config 3.  It runs on a side stream, with its own hard list, beside the pending kernel and the
-            // masked DP of the last chunk.  Started once the overflow list is complete; finished (host loop: slabs grow
-            // until every task fits) after the main path's launches are queued.
-            if (!c->stream2) {
-                HIP_TRY(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-                HIP_TRY(c, hipEventCreateWithFlags(&c->ev2, hipEventDisableTiming));
-                HIP_TRY(c, hipHostMalloc((void**)&c->h_pin, 64 * sizeof(uint32_t), hipHostMallocDefault));
-            }
-            hipStream_t s2 = c->stream2;
-            struct { uint32_t n_over = 0, cap2 = 0, todo = 0, off = 0, total = 0; const uint32_t* tasks = nullptr; bool active = false; uint32_t gcnt[2] = {0, 0}; } fb;
-            // A few overflow tasks (shallow data: some hundreds per run) first try the in-LDS variant of the general kernel
-            // with a slab for kLdsMatches k-mer matches: their ~2 ms of serial HBM latency were a third of a shallow step.
-            const uint32_t kLdsMatches = 512;
-            static const uint32_t kLdsTasks = VTX_DEV_ENV("VTX_BAND_LDS_TASKS") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_BAND_LDS_TASKS")) : 4096u;   // experiment knob
-            auto fallback_launch = [&]() -> int {
-                const uint64_t worst = (uint64_t)c->max_read_len * mh;
-                if (fb.cap2 >= worst && fb.cap2 >= 512) return fail(c, VTX_E_STATE, "vtx_run: band kernel overflow with a worst-case slab");
-                // first three rounds: the cooperative kernel, everything in LDS (band_coop_kernel: a wavefront per task, up to 512 matches,
-                // then 1024, then 4096; reads up to 256 bases); what that cannot hold takes the serial kernel below
-                static const bool no_coop = VTX_DEV_ENV("VTX_BAND_NO_COOP") != nullptr;             // experiment / test hook
-                const int tier = fb.cap2 < 512 ? 0 : (fb.cap2 == 512 ? 1 : (fb.cap2 == 1024 ? 2 : -1));
-                const uint32_t tier_cap = tier == 0 ? 512u : (tier == 1 ? 1024u : 4096u);
-                // (haplotypes up to 1000 bases: the kernel walks its Fenwick tree in ten unrolled steps, tn = n + 8 < 1024)
-                if (tier >= 0 && !no_coop && c->max_read_len <= 256 && mh <= 1000 &&
-                    vtxk_band_coop_lds(mh, tier_cap) <= 64u * 1024) {
-                    fb.cap2 = tier_cap;
-                    HIP_TRY(c, hipMemsetAsync(d_cnt + 9, 0, sizeof(uint32_t), s2));
-                    uint32_t* other = c->d_over2.as<uint32_t>() + ((fb.tasks == c->d_over2.as<uint32_t>()) ? fb.n_over : 0);
-                    HIP_TRY(c, vtxk_launch_band_coop(tier, fb.tasks, fb.todo, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                                     c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), mh,
-                                                     c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), c->d_band2.as<uint16_t>(), band_stride,
-                                                     c->d_hard2.as<uint32_t>(), other, d_cnt + 8, s2));
-                    HIP_TRY(c, hipMemcpyAsync(c->h_pin, d_cnt + 8, sizeof fb.gcnt, hipMemcpyDeviceToHost, s2));
-                    ++launches;
-                    return VTX_OK;
-                }
-                const bool in_lds = fb.cap2 < 512 && fb.todo <= kLdsTasks && !VTX_DEV_ENV("VTX_BAND_NO_LDS_FALLBACK") &&
-                                    vtxk_band_lds_stride(kLdsMatches, mh, c->max_read_len) <= 160 * 1024 - 512;
-                fb.cap2 = in_lds ? kLdsMatches : (uint32_t)std::max<uint64_t>(std::min<uint64_t>((uint64_t)fb.cap2 * 16, worst), 512);
-                const size_t stride2 = vtxk_band_ws_stride(fb.cap2, mh);
-                if (!in_lds) {                                                  // whole wavefronts: the 64 slabs are interleaved, vtxk_band_lanes() of them in use
-                    const size_t lanes = vtxk_band_lanes(fb.todo);
-                    HIP_TRY(c, c->d_band_ws2.reserve(lanes < 64 ? (size_t)fb.todo * stride2 : ((size_t)fb.todo + 63) / 64 * 64 * stride2));   // (sparse lanes: a contiguous slab per task)
-                }
-                HIP_TRY(c, hipMemsetAsync(d_cnt + 9, 0, sizeof(uint32_t), s2));
-                uint32_t* other = c->d_over2.as<uint32_t>() + ((fb.tasks == c->d_over2.as<uint32_t>()) ? fb.n_over : 0);
-                HIP_TRY(c, vtxk_launch_band(fb.tasks, fb.todo, 0, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                            c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(),
-                                            c->d_band_ws2.as<uint8_t>(), stride2, fb.cap2, mh, c->d_ref.as<int32_t>(),
-                                            c->d_alt.as<int32_t>(), c->d_band2.as<uint16_t>(), band_stride, c->d_hard2.as<uint32_t>(),
-                                            other, d_cnt + 8, in_lds ? 1 : 0, c->max_read_len, s2));
-                HIP_TRY(c, hipMemcpyAsync(c->h_pin, d_cnt + 8, sizeof fb.gcnt, hipMemcpyDeviceToHost, s2));   // pinned: does not block
-                ++launches;
-                return VTX_OK;
-            };
-            auto fallback_start = [&](uint32_t off, uint32_t total) -> int {   // the overflow list d_over[0, total) is complete and visible
-                const uint32_t n_over = std::min(std::max(slots, 1024u), total - off);   // slices (bounds d_band2)
-                fb.off = off; fb.total = total;
-                fb.n_over = n_over; fb.todo = n_over; fb.cap2 = 512 / 16; fb.tasks = c->d_over.as<uint32_t>() + off; fb.active = true;
-                HIP_TRY(c, c->d_over2.reserve(2 * (size_t)n_over * sizeof(uint32_t)));
-                HIP_TRY(c, c->d_hard2.reserve((size_t)n_over * sizeof(uint32_t)));
-                HIP_TRY(c, c->d_band2.reserve((size_t)n_over * 2 * band_stride * sizeof(uint16_t)));
-                HIP_TRY(c, hipMemsetAsync(d_cnt + 8, 0, 2 * sizeof(uint32_t), s2));
-                return fallback_launch();
-            };
-            auto fallback_finish = [&]() -> int {
-                if (!fb.active) return VTX_OK;
-                for (;;) {
-                    for (;;) {
-                        HIP_TRY(c, hipStreamSynchronize(s2));
-                        fb.gcnt[0] = c->h_pin[0]; fb.gcnt[1] = c->h_pin[1];
-                        // tasks that still do not fit were written to the other half of d_over2: rerun them with a larger slab
-                        fb.tasks = c->d_over2.as<uint32_t>() + ((fb.tasks == c->d_over2.as<uint32_t>()) ? fb.n_over : 0);
-                        fb.todo = fb.gcnt[1];
-                        if (!fb.todo) break;
-                        if (int rc = fallback_launch()) return rc;
-                    }
-                    if (int rc = masked_dp(fb.gcnt[0], c->d_hard2.as<uint32_t>(), nullptr, c->d_band2.as<uint16_t>(), std::max(fb.gcnt[0], 1u), s2, VTX_STAGE_GENERAL_DP)) return rc;
-                    hard_total += fb.gcnt[0];
-                    if (fb.off + fb.n_over >= fb.total) break;
-                    if (int rc = fallback_start(fb.off + fb.n_over, fb.total)) return rc;      // next slice (same stream: in order)
-                }
-                HIP_TRY(c, hipEventRecord(c->ev2, s2));
-                HIP_TRY(c, hipStreamWaitEvent(s, c->ev2, 0));             // the reduction kernels read every score
-                return VTX_OK;
-            };
-            HIP_TRY(c, hipMemsetAsync(d_cnt, 0, 64 * sizeof(uint32_t), s));
-            uint32_t cnt[12] = {0};
-            uint32_t pending_total = 0, over_before = 0;
-            uint64_t diag_total = 0, diag_left = 0, refined_total = 0, checked_total = 0, swept_total = 0, diag2_total = 0, diag2_scored = 0, tight2_total = 0, stream_total = 0;
-            float diag_ms = 0, check_ms = 0, sweep_ms = 0;
-            // the band of every listed task (band_sweep_kernel, tier 0 / 1), one slice of band slots at a time, then the masked DP over
-            // the slice (its length — the tasks the sweep did not decline — is read on the device: counters[0]; declined: counters[1])
-            // (libvtx_dev.so, VTX_SWEEP_V1=1: round 4's kernel instead — 256 sections per task, then a second pass with 1 024 over what the
-            // first declined; the A/B reference of tests/test_gpu_sweep.py and tools/gpu_campaign.sh)
-            static const bool sweep_v1 = VTX_DEV_ENV("VTX_SWEEP_V1") != nullptr;
-            auto sweep_slices = [&](int tier, const uint32_t* list, uint32_t n, uint32_t* over_out, uint32_t* counters) -> int {
-                static const bool sweep_stats = getenv("VTX_DEBUG") != nullptr;
-                HIP_TRY(c, c->d_sweep_log.reserve(vtxk_band_sweep_log_bytes()));
-                for (uint32_t off = 0; off < n; off += slots) {
-                    const uint32_t cnt_s = std::min(slots, n - off);
-                    HIP_TRY(c, hipMemsetAsync(counters, 0, sizeof(uint32_t), s));
-    #ifdef VTX_DEVTOOLS
-                    if (sweep_v1)
-                        HIP_TRY(c, vtxk_launch_band_sweep_v1(tier, list + off, cnt_s, nullptr, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                                             c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(),
-                                                             c->d_band.as<uint16_t>(), band_stride, c->d_hard.as<uint32_t>(), over_out,
-                                                             counters, sweep_stats ? d_cnt + 56 : nullptr, stage, nullptr, s));
-                    else
-    #endif
-                    HIP_TRY(c, vtxk_launch_band_sweep(list + off, cnt_s, nullptr, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                                      c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(),
-                                                      c->d_band.as<uint16_t>(), band_stride, c->d_hard.as<uint32_t>(), over_out,
-                                                      counters, sweep_stats ? d_cnt + 56 : nullptr, stage, nullptr, c->d_sweep_log.as<uint32_t>(), s));
-                    (void)tier;
-                    HIP_TRY(c, vtxk_launch_sw_banded_dev(kShapes[shape][0], kShapes[shape][1], cnt_s, c->d_hard.as<uint32_t>(), counters,
-                                                         c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(),
-                                                         c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), c->d_band.as<uint16_t>(), band_stride,
-                                                         c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), mh, s));
-                    launches += 2;
-                }
-                return VTX_OK;
-            };
-            uint32_t resweep_total = 0;
-            // Second stage (round 5): the same single-diagonal logic with a list of 64 entries and the harmless bound from
-            // the matches that can really precede a match (band_diag2_kernel), the harmless test alone over a two-row window for what
-            // exceeds the list (band_stream_kernel).  They score most of these tasks or prove that their band is one diagonal stretch
-            // (full-matrix check, masked DP for what it does not settle; no sweep); what they leave — out[0, *n_out) — takes the sweep.
-            // One host round trip for the counts.  (libvtx_dev.so: VTX_BAND_NO_DIAG2=1 sends everything to the sweep, as round 4 did;
-            // VTX_BAND_NO_STREAM=1 — what exceeds the second stage's list goes to the sweep.)
-            // A short list skips it: one lane per task, a few hundred dependent loads each — the kernels are latency chains with a fixed
-            // cost of several milliseconds that the sweep + its DP beat below ~0.65 M tasks.  Measured in round 6 on loci from real sequence
-            // (profiles/r06_second_stage_threshold.txt; stage on / off): 33 k tasks 7.9 / 3.4 ms per step, 145 k 12.8 / 8.6, 319 k 28.9 / 19.9,
-            // 638 k 36.8 / 36.0, 1.28 M 52.2 / 64.3 — round 5's threshold of 200 k made mid-size batches a third slower.
-            // The tables of the tasks' loci have to be resident (gt_l0: first locus of the table buffer).
-            auto second_stage_on = [&](uint32_t n) -> bool {
-                static const bool no_diag2 = VTX_DEV_ENV("VTX_BAND_NO_DIAG2") != nullptr;
-                static const uint32_t diag2_min = VTX_DEV_ENV("VTX_BAND_DIAG2_MIN") ? (uint32_t)strtoul(VTX_DEV_ENV("VTX_BAND_DIAG2_MIN"), nullptr, 10) : 700000u;
-                return !no_diag2 && n >= diag2_min && mh <= 255;
-            };
-            auto second_stage = [&](const uint32_t* list, uint32_t n, uint32_t gt_l0, uint32_t* out, uint32_t* n_out) -> int {
-                static const bool no_stream = VTX_DEV_ENV("VTX_BAND_NO_STREAM") != nullptr;
-                HIP_TRY(c, hipMemsetAsync(d_cnt + 30, 0, 2 * sizeof(uint32_t), s));
-                HIP_TRY(c, hipMemsetAsync(d_cnt + 48, 0, sizeof(uint32_t), s));
-                HIP_TRY(c, vtxk_launch_band_diag2(list, n, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                                  c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), mh,
-                                                  c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), bp.tasks_per_locus, gt_l0,
-                                                  c->d_gtables.as<uint8_t>(), out, c->d_tight2.as<uint32_t>(),
-                                                  c->d_tight2_pack.as<uint32_t>(), d_cnt + 30,
-                                                  no_stream ? nullptr : c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), d_cnt + 48, stage, s));
-                HIP_TRY(c, hipMemcpyAsync(c->h_pin + 14, d_cnt + 30, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                HIP_TRY(c, hipMemcpyAsync(c->h_pin + 16, d_cnt + 48, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                HIP_TRY(c, hipStreamSynchronize(s));
-                stream_total += std::min(c->h_pin[16], n);
-                const uint32_t n_sweep = std::min(c->h_pin[14], n);
-                const uint32_t n_tight2 = std::min(c->h_pin[15], n - n_sweep);
-                ++launches;
-                diag2_total += n; diag2_scored += n - n_sweep - n_tight2;
-                if (n_tight2) {
-                    // These tasks hold a certificate (a lower bound of the banded score) and sit in repeat-rich sequence on
-                    // clean reads: the full-matrix score equals it for practically all of them (4 223 of 4 223 in the CPU
-                    // sample), and cert <= banded <= full then decides the task for 5.9 ns where the masked DP takes 10.
-                    // What the check does not settle takes the masked DP over its one-diagonal band (count on the device).
-                    HIP_TRY(c, hipMemsetAsync(d_cnt + 25, 0, sizeof(uint32_t), s));
-                    HIP_TRY(c, vtxk_launch_sw_check(kShapes[shape][0], kShapes[shape][1], n_tight2, c->d_tight2.as<uint32_t>(),
-                                                    c->d_tight2_pack.as<uint32_t>(), nullptr, c->d_records.as<vtx_record>(),
-                                                    c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(),
-                                                    c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), mh,
-                                                    c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), d_cnt + 25, stage, s));
-                    HIP_TRY(c, vtxk_launch_sw_diag_band(kShapes[shape][0], kShapes[shape][1], n_tight2, c->d_recheck2.as<uint32_t>(),
-                                                        c->d_recheck2_pack.as<uint32_t>(), d_cnt + 25, c->d_records.as<vtx_record>(),
-                                                        c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(),
-                                                        c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(),
-                                                        mh, stage, s));
-                    // (its grid is sized for n_tight2 although a few hundred tasks remain: the workgroups past the device count leave at once —
-                    //  measured in round 6 with an exact-size launch behind a host round trip: no difference.  The 3 x 13 ms of
-                    //  sw_banded_kernel<.., 2> in the real-sequence kernel table are ONE launch of 39 ms — the first stage's 0.5 M one-diagonal
-                    //  bands on the side stream, stretched by the kernels it runs beside — and two of microseconds.)
-                    launches += 2;
-                    tight2_total += n_tight2;
-                }
-                *n_out = n_sweep;
-                return 0;
-            };
-            bool sweep_used = false;                    // some chunk took the round-4 path
-            bool sweep_pending = false;                 // the events of a swept chunk have not been read yet
-            bool sweep_forked = false;                  // ... and that chunk ran its two branches side by side
-            uint32_t fork_nt = 0;
-            auto collect_sweep_times = [&]() -> int {
-                if (!sweep_pending) return VTX_OK;
-                sweep_pending = false;
-                HIP_TRY(c, hipEventSynchronize(c->ev[8]));
-                float ms = 0;
-                // ev[7] .. ev[9]: band_refine_kernel (forked only) + the one-diagonal bands' masked DP; then band_sweep_kernel + its masked
-                // DP (the chunk's repeats) — forked: ev[11] .. ev[8] on the main stream, BESIDE the first interval, not after it
-                HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[7], c->ev[9])); check_ms += ms;
-                HIP_TRY(c, hipEventElapsedTime(&ms, sweep_forked ? c->ev[11] : c->ev[9], c->ev[8])); sweep_ms += ms;
-                if (sweep_forked) checked_total += std::min(c->h_pin[12], fork_nt);          // (copied before ev[9], which ev[8] waited for)
-                sweep_forked = false;
-                return VTX_OK;
-            };
-            for (uint64_t base = t_begin; base < t_end; base += chunk) {
-                const uint32_t nt = (uint32_t)std::min<uint64_t>(chunk, t_end - base);
-                if (int rc = collect_sweep_times()) return rc;                              // (a chunk re-records the events)
-                HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), s));                 // hard count of this chunk
-                HIP_TRY(c, hipMemsetAsync(d_cnt + 11, 0, sizeof(uint32_t), s));            // pending count of this chunk
-                HIP_TRY(c, hipMemsetAsync(d_cnt + 16, 0, 8 * sizeof(uint32_t), s));        // block counters (one per XCD)
-                // the loci of this range of tasks (tables in global memory are built per range)
-                uint32_t gt_l0 = 0, gt_n = gt_bytes ? c->n_loci : 0;
-                if (gt_chunked) {
-                    uint32_t ends[2];
-                    HIP_TRY(c, hipMemcpyAsync(&ends[0], c->d_rec_locus.as<uint32_t>() + base / 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    HIP_TRY(c, hipMemcpyAsync(&ends[1], c->d_rec_locus.as<uint32_t>() + (base + nt - 1) / 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    HIP_TRY(c, hipStreamSynchronize(s));
-                    gt_l0 = ends[0];
-                    gt_n = ends[1] - ends[0] + 1;
-                    if (gt_n > bp.gt_loci) gt_n = 0;              // does not fit after all: tables in LDS for this chunk
-                }
-                c->gt_used = (gt_n && bp.gt_loci) ? (uint64_t)gt_n * (gt_bytes / bp.gt_loci) : 0;     // (gt_bytes = gt_loci x bytes per locus)
-                HIP_TRY(c, hipEventRecord(c->ev[4], s));
-                // Stage 1 (tables in global memory): band_diag_kernel decides the tasks whose alignment lives on one diagonal
-                // (vtx_fast_core.h) and lists the others; band_run_kernel then takes that LIST instead of the whole range.
-                static const bool no_diag = VTX_DEV_ENV("VTX_BAND_NO_DIAG") != nullptr;          // experiment / test hook: stage 1 off
-                static const int diag_stats = getenv("VTX_DEBUG") ? 1 : 0;
-                bool diag = false, swept = false;
-                uint32_t n_fail = 0;
-                const uint32_t* fail_list = c->d_fail.as<uint32_t>();
-                // Round 4: what band_diag_kernel / band_refine_kernel leave goes (a) with a certificate: through the full-matrix CHECK
-                // (full == cert decides it: cert <= banded <= full), (b) otherwise, or when the check fails: through band_sweep_kernel
-                // (the band of ANY task, vtx_sweep.hip) and the masked DP.  VTX_BAND_LEGACY=1: round 3's band_run_kernel / pending /
-                // general path instead (kept for A/B tests; also what takes over when a haplotype of the batch exceeds 255 bases).
-                static const bool legacy = VTX_DEV_ENV("VTX_BAND_LEGACY") != nullptr;
-                static const bool no_tight = VTX_DEV_ENV("VTX_BAND_NO_TIGHT") != nullptr;          // test hook: tasks with a certificate go to the sweep like the others
-                static const bool use_check = VTX_DEV_ENV("VTX_BAND_CHECK") != nullptr;            // experiment hook: full-matrix check in front of their DP
-                const bool sweep_path = !legacy && mh <= vtxk_band_sweep_max_len() && mh > 0;
-                uint32_t* tight_list = (sweep_path && !no_tight) ? c->d_tight.as<uint32_t>() : nullptr;
-                uint32_t* tight_pack = tight_list ? c->d_tight_pack.as<uint32_t>() : nullptr;
-                // which of the tasks the certificate stages leave skip band_run_kernel (whose piece lists they would overflow) and take
-                // band_sweep_kernel at once: bit = vtxf::Why.  Default: W_MATCHES (4: more than 40 off-diagonal k-mer matches — repeats).
-                // VTX_BAND_DENSE_MASK: experiment knob (0x3be: everything but shape; 0: nothing — band_run_kernel sees every task first).
-                static const uint32_t dense_mask = VTX_DEV_ENV("VTX_BAND_DENSE_MASK") ? (uint32_t)strtoul(VTX_DEV_ENV("VTX_BAND_DENSE_MASK"), nullptr, 0) : (1u << 4);
-                uint32_t* dense_list = sweep_path ? c->d_dense.as<uint32_t>() : nullptr;
-                if (gt_n && !no_diag) {
-                    HIP_TRY(c, hipMemsetAsync(d_cnt + 12, 0, 4 * sizeof(uint32_t), s));   // [12] left for band_run_kernel, [13] for band_sweep_kernel, [14] refine records, [15] tasks with a one-diagonal band
-                    // tasks with main pieces only whose bounds do not meet leave a record for band_refine_kernel
-                    static const bool no_refine = VTX_DEV_ENV("VTX_BAND_NO_REFINE") != nullptr;        // experiment / test hook
-                    const uint32_t refine_cap = band_refine_cap(chunk);
-                    uint32_t* refine_list = no_refine ? nullptr : c->d_refine.as<uint32_t>();
-                    const uint32_t tail_cap = (uint32_t)std::min<size_t>(band_tail_cap(chunk), c->d_tail.cap / (vtxk_band_tail_words() * sizeof(uint32_t)));
-                    const uint32_t tail_cap_hook = VTX_DEV_ENV("VTX_DIAG_TAIL_CAP") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_TAIL_CAP")) : 0xffffffffu;   // test hook: a small buffer (read per run)
-                    const uint32_t tail_n = std::min(tail_cap, tail_cap_hook);
-                    const hipError_t e = vtxk_launch_band_diag(nt, (uint32_t)base, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                                               c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(),
-                                                               mh, mh_min, c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(),
-                                                               c->d_fail.as<uint32_t>(), refine_list, refine_cap, d_cnt, tasks_per_locus, gt_l0, gt_n,
-                                                               c->d_gtables.as<uint8_t>(), gt_bytes, diag_stats, tight_list, tight_pack, stage,
-                                                               dense_list, dense_mask, c->max_read_len, c->d_tail.as<uint32_t>(), tail_n, s);
-                    if (e == hipSuccess && sweep_path) {
-                        diag = true; swept = true; sweep_used = true;
-                        HIP_TRY(c, hipEventRecord(c->ev[6], s));
-                        // What the stage left, in two branches that share nothing but the score arrays (disjoint tasks):
-                        //   side stream   band_refine_kernel over its records, then the masked DP over the one-diagonal bands (tight list:
-                        //                 band_diag_kernel's entries + what the refinement leaves; counted on the device, the grid is
-                        //                 sized for the bound known here);
-                        //   this stream   band_sweep_kernel + masked DP over the repeats and the short fail list (both final once
-                        //                 band_diag_kernel is done: with a tight list the refinement adds nothing to them).
-                        // At 16 reads per locus these are five latency-bound launches of 0.1 - 0.2 ms each: side by side 0.31 instead
-                        // of 0.55 ms.  One host round trip, right after band_diag_kernel.  (VTX_BAND_NO_TIGHT: the refinement's leftovers
-                        // go to the fail list, so everything stays in order on this stream.)
-                        static const bool no_fork = VTX_DEV_ENV("VTX_BAND_NO_FORK") != nullptr;          // experiment / test hook
-                        const bool fork = tight_list != nullptr && !no_fork;
-                        hipStream_t sb = fork ? s2 : s;                                             // the refine / one-diagonal branch
-                        // the records band_diag_kernel left: with a tight list (round 6) every task that holds a certificate and a one-diagonal
-                        // band, for band_corridor_kernel; else (VTX_BAND_NO_TIGHT, libvtx_dev.so's VTX_BAND_NO_CORRIDOR) round 3's, for band_refine_kernel
-                        static const bool no_corridor = VTX_DEV_ENV("VTX_BAND_NO_CORRIDOR") != nullptr;
-                        auto second_look = [&](uint32_t n_rec, hipStream_t st) -> hipError_t {
-                            if (tight_list && !no_corridor)
-                                return vtxk_launch_band_corridor(refine_list, n_rec, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                                                 c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(),
-                                                                 c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), d_cnt, diag_stats, tight_list, tight_pack,
-                                                                 stage, d_cnt + 14, st);
-                            return vtxk_launch_band_refine(refine_list, n_rec, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                                           c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), mh,
-                                                           c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), c->d_fail.as<uint32_t>(), d_cnt,
-                                                           tasks_per_locus, gt_l0, c->d_gtables.as<uint8_t>(), diag_stats, tight_list, tight_pack, stage, d_cnt + 14, st);
-                        };
-                        if (!fork && refine_list) HIP_TRY(c, second_look(std::min(refine_cap, nt), s));
-                        HIP_TRY(c, hipMemcpyAsync(c->h_pin + 8, d_cnt + 12, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // [12] fail, [13] dense, [14] refine, [15] tight
-                        HIP_TRY(c, hipStreamSynchronize(s));
-                        const uint32_t n_refine = std::min(c->h_pin[10], refine_cap);
-                        // (forked: the tight list still grows by what the refinement leaves — at most its records)
-                        const uint32_t n_tight = (uint32_t)std::min<uint64_t>((uint64_t)c->h_pin[11] + (fork && refine_list ? n_refine : 0u), nt);
-                        refined_total += n_refine;
-                        launches += 2;
-                        if (fork) HIP_TRY(c, hipStreamWaitEvent(s2, c->ev[6], 0));
-                        HIP_TRY(c, hipEventRecord(c->ev[7], sb));
-                        if (fork && refine_list && n_refine) HIP_TRY(c, second_look(n_refine, sb));
-                        if (n_tight) {
-                            // tasks with a certificate but no verdict: their band is one diagonal stretch (tight_pack): the masked DP
-                            // expands it itself.  (VTX_BAND_CHECK=1: the full-matrix check first — full == cert decides a task, cert <=
-                            // banded <= full; measured: 5.6 ns per task against 10 for the DP it saves on 20 - 30 % of noisy reads.)
-                            const uint32_t* dp_list = tight_list;
-                            const uint32_t* dp_pack = tight_pack;
-                            const uint32_t* dp_cnt = fork ? d_cnt + 15 : nullptr;
-                            if (use_check) {
-                                HIP_TRY(c, c->d_dband.reserve((size_t)chunk * sizeof(uint32_t)));
-                                HIP_TRY(c, c->d_dband_pack.reserve((size_t)chunk * sizeof(uint32_t)));
-                                HIP_TRY(c, hipMemsetAsync(d_cnt + 24, 0, sizeof(uint32_t), sb));
-                                HIP_TRY(c, vtxk_launch_sw_check(kShapes[shape][0], kShapes[shape][1], n_tight, tight_list, tight_pack, dp_cnt,
-                                                                c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(),
-                                                                c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(),
-                                                                c->d_alt.as<int32_t>(), mh, c->d_dband.as<uint32_t>(),
-                                                                c->d_dband_pack.as<uint32_t>(), d_cnt + 24, stage, sb));
-                                dp_list = c->d_dband.as<uint32_t>(); dp_pack = c->d_dband_pack.as<uint32_t>(); dp_cnt = d_cnt + 24;
-                                ++launches;
-                            }
-                            HIP_TRY(c, vtxk_launch_sw_diag_band(kShapes[shape][0], kShapes[shape][1], n_tight, dp_list, dp_pack, dp_cnt,
-                                                                c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(),
-                                                                c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(),
-                                                                c->d_alt.as<int32_t>(), mh, stage, sb));
-                            ++launches;
-                        }
-                        if (fork) HIP_TRY(c, hipMemcpyAsync(c->h_pin + 12, d_cnt + 15, sizeof(uint32_t), hipMemcpyDeviceToHost, sb));   // the list's final length (read in collect_sweep_times)
-                        HIP_TRY(c, hipEventRecord(c->ev[9], sb));
-                        if (fork) HIP_TRY(c, hipEventRecord(c->ev[11], s));                          // (this stream's branch starts here)
-                        n_fail = c->h_pin[8];
-                        uint32_t n_dense = std::min(c->h_pin[9], nt);
-                        if (!fork) checked_total += n_tight;                                    // (forked: the exact count arrives with the events)
-                        diag_total += nt; diag_left += (uint64_t)n_fail + n_dense;
-                        // repeats: band_sweep_kernel (the band of ANY task) + masked DP, sorted by task (neighbours share their locus'
-                        // haplotypes, and the hard list comes out in a fixed order); what it declines waits in d_over[2 n_tasks ..) for the
-                        // second pass after the last chunk
-                        // (a short list of the other tasks is not worth band_run_kernel's launch — a persistent grid: ~1 ms whatever the
-                        // count — and the two host round trips behind it: it joins the repeats, ~25 ns per task)
-                        static const uint32_t run_min = VTX_DEV_ENV("VTX_BAND_RUN_MIN") ? (uint32_t)strtoul(VTX_DEV_ENV("VTX_BAND_RUN_MIN"), nullptr, 10) : 65536u;
-                        if (n_fail && n_fail < run_min && (uint64_t)n_dense + n_fail <= nt) {
-                            HIP_TRY(c, hipMemcpyAsync(dense_list + n_dense, c->d_fail.as<uint32_t>(), (size_t)n_fail * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-                            n_dense += n_fail;
-                            n_fail = 0;
-                        }
-                        if (n_dense) {
-                            const uint32_t* dl = dense_list;
-                            if (n_dense > 64) {
-                                const size_t tb = vtxk_sort_keys_u32_temp_bytes(n_dense);
-                                if (c->d_fail_tmp.reserve(tb) == hipSuccess) {
-                                    HIP_TRY(c, vtxk_sort_keys_u32(dense_list, dense_list + nt, n_dense, c->d_fail_tmp.p, tb, s));
-                                    dl = dense_list + nt;
-                                } else (void)hipGetLastError();
-                            }
-                            // Second stage (round 5): band_diag2_kernel + band_stream_kernel + the full-matrix check (second_stage above)
-                            const uint32_t* sl = dl;
-                            uint32_t n_sweep = n_dense;
-                            if (second_stage_on(n_dense)) {
-                                uint32_t* sweep2 = (dl == dense_list) ? dense_list + nt : dense_list;          // (the half of d_dense the list is not in)
-                                if (int rc = second_stage(dl, n_dense, gt_l0, sweep2, &n_sweep)) return rc;
-                                sl = sweep2;
-                            }
-                            if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, c->d_over.as<uint32_t>() + 2 * n_tasks, d_cnt + 26)) return rc; }
-                            swept_total += n_sweep;
-                        }
-                        if (n_fail > 64) {
-                            const size_t tb = vtxk_sort_keys_u32_temp_bytes(n_fail);
-                            if (c->d_fail_tmp.reserve(tb) == hipSuccess) {
-                                HIP_TRY(c, vtxk_sort_keys_u32(c->d_fail.as<uint32_t>(), c->d_fail.as<uint32_t>() + nt, n_fail, c->d_fail_tmp.p, tb, s));
-                                fail_list = c->d_fail.as<uint32_t>() + nt;
-                            } else (void)hipGetLastError();
-                        }
-                        if (fork) HIP_TRY(c, hipStreamWaitEvent(s, c->ev[9], 0));                    // join: what follows reads every score
-                        HIP_TRY(c, hipEventRecord(c->ev[8], s));
-                        sweep_pending = true; sweep_forked = fork; fork_nt = nt;
-                        // the others: band_run_kernel (task-list mode) below — seeds, chain and the general certificate (a read against the
-                        // other allele of an indel lies on TWO diagonals: cert == ub decides nearly all of those without a DP cell)
-                    } else if (e == hipSuccess) {
-                        diag = true;
-                        HIP_TRY(c, hipMemcpyAsync(c->h_pin + 8, d_cnt + 12, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                        HIP_TRY(c, hipMemcpyAsync(c->h_pin + 9, d_cnt + 14, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                        HIP_TRY(c, hipEventRecord(c->ev[6], s));
-                        HIP_TRY(c, hipStreamSynchronize(s));
-                        n_fail = c->h_pin[8];
-                        const uint32_t n_refine = std::min(c->h_pin[9], refine_cap);
-                        if (n_refine) {
-                            HIP_TRY(c, vtxk_launch_band_refine(refine_list, n_refine, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                                               c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), mh,
-                                                               c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), c->d_fail.as<uint32_t>(), d_cnt,
-                                                               tasks_per_locus, gt_l0, c->d_gtables.as<uint8_t>(), diag_stats, nullptr, nullptr, stage, nullptr, s));
-                            HIP_TRY(c, hipMemcpyAsync(c->h_pin + 8, d_cnt + 12, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                            HIP_TRY(c, hipStreamSynchronize(s));
-                            n_fail = c->h_pin[8];
-                            refined_total += n_refine;
-                            ++launches;
-                        }
-                        diag_total += nt; diag_left += n_fail;
-                        ++launches;
-                        if (n_fail > 64) {
-                            // the list comes out in the order the wavefronts finished: eight XCD ranges interleaved.  Sorted by task, the
-                            // 64 tasks of a band_run_kernel wavefront share their loci's tables and reads again (12.7 -> GB of L2 misses
-                            // for 2 % of the tasks otherwise)
-                            const size_t tb = vtxk_sort_keys_u32_temp_bytes(n_fail);
-                            if (c->d_fail_tmp.reserve(tb) == hipSuccess) {
-                                HIP_TRY(c, vtxk_sort_keys_u32(c->d_fail.as<uint32_t>(), c->d_fail.as<uint32_t>() + nt, n_fail, c->d_fail_tmp.p, tb, s));
-                                fail_list = c->d_fail.as<uint32_t>() + nt;
-                            } else (void)hipGetLastError();
-                        }
-                    } else {
-                        // (the tables do not fit the buffer for this chunk: band_run_kernel alone, tables in LDS)
-                        if (getenv("VTX_DEBUG")) fprintf(stderr, "[vtx] band_diag_kernel not launched for tasks [%llu, +%u): %s\n", (unsigned long long)base, nt, hipGetErrorString(e));
-                        (void)hipGetLastError();
-                    }
-                }
-                HIP_TRY(c, hipEventRecord(c->ev[10], s));
-                if (!diag || n_fail)
-                    HIP_TRY(c, vtxk_launch_band_run(diag ? n_fail : nt, diag ? 0u : (uint32_t)base, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                                     c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(),
-                                                     mh, mh_min, c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(),
-                                                     c->d_band_ws.as<uint32_t>(), c->d_poly.as<uint16_t>(), poly_stride / 2,
-                                                     c->d_hard.as<uint32_t>(), c->d_over.as<uint32_t>(), c->d_pend.as<uint32_t>(),
-                                                     c->d_pend_buf.as<uint32_t>(), hard_cap, pend_cap, d_cnt,
-                                                     tasks_per_locus, gt_l0, gt_n, gt_n ? c->d_gtables.as<uint8_t>() : nullptr, gt_bytes,
-                                                     diag ? fail_list : nullptr, c->band_long_lists ? 1 : 0, s));
-                HIP_TRY(c, hipEventRecord(c->ev[5], s));                  // (complete once the read-back below is: no synchronisation of its own)
-                const bool run_skipped = swept && n_fail == 0;             // nothing went to band_run_kernel: its counters are what they were
-                if (run_skipped) {
-                    cnt[0] = 0; cnt[11] = 0; cnt[1] = over_before;
-                } else {
-                    HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
-                    HIP_TRY(c, hipStreamSynchronize(s));
-                }
-                // (task-list mode runs the 15-entry variant: nothing to give a second chance to)
-                const bool short_lists = !diag && gt_n && vtxk_band_second_chance(tasks_per_locus, c->band_long_lists ? 1 : 0);
-                if (short_lists && nt >= (1u << 20)) {
-                    // feedback for the next run of this context: many overflows of the 12-entry lists (noisy reads: 3.3 % of the
-                    // tasks at 3 % substitution errors, 0.2 % at 0.5 %) make the 15-entry variant the better first pass
-                    if ((uint64_t)(cnt[1] - over_before) * 50 > nt) c->band_long_lists = true;
-                }
-                if (short_lists && cnt[1] > over_before) {
-                    // The six-wavefront variant keeps 12-entry lists: the tasks that overflowed them ([a0, a1) of the overflow
-                    // list) get a second chance in the 15-entry variant before the general kernel — what overflows again is
-                    // appended behind a1 and then moved down to a0.
-                    const uint32_t a0 = over_before, a1 = cnt[1];
-                    HIP_TRY(c, hipMemsetAsync(d_cnt + 16, 0, 8 * sizeof(uint32_t), s));
-                    HIP_TRY(c, vtxk_launch_band_run(a1 - a0, 0, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                                     c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(),
-                                                     mh, mh_min, c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(),
-                                                     c->d_band_ws.as<uint32_t>(), c->d_poly.as<uint16_t>(), poly_stride / 2,
-                                                     c->d_hard.as<uint32_t>(), c->d_over.as<uint32_t>(), c->d_pend.as<uint32_t>(),
-                                                     c->d_pend_buf.as<uint32_t>(), hard_cap, pend_cap, d_cnt, tasks_per_locus, gt_l0,
-                                                     gt_n, c->d_gtables.as<uint8_t>(), gt_bytes, c->d_over.as<uint32_t>() + a0, 0, s));
-                    HIP_TRY(c, hipEventRecord(c->ev[5], s));
-                    HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
-                    HIP_TRY(c, hipStreamSynchronize(s));
-                    const uint32_t again = cnt[1] - a1;          // <= a1 - a0: source and destination do not overlap
-                    if (again) HIP_TRY(c, hipMemcpyAsync(c->d_over.as<uint32_t>() + a0, c->d_over.as<uint32_t>() + a1, (size_t)again * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-                    cnt[1] = a0 + again;
-                    HIP_TRY(c, hipMemcpyAsync(d_cnt + 1, cnt + 1, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-                    ++launches;
-                }
-                over_before = cnt[1];
-                {
-                    float ms = 0;
-                    if (!run_skipped) {
-                        HIP_TRY(c, hipEventElapsedTime(&ms, swept ? c->ev[10] : c->ev[4], c->ev[5]));
-                        band_run_ms += ms;
-                        if (int rc = collect_sweep_times()) return rc;
-                    }
-                    if (diag) { HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[4], c->ev[6])); diag_ms += ms; }
-                }
-                if (!sweep_used && base + chunk >= t_end && cnt[1])      // last chunk: the overflow list is complete
-                    if (int rc = fallback_start(0, cnt[1])) return rc;
-                if (cnt[0] > hard_cap) {               // the excess went to the general kernel's list: slots in use = hard_cap
-                    cnt[0] = hard_cap;
-                    HIP_TRY(c, hipMemcpyAsync(d_cnt, cnt, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-                }
-                cnt[11] = std::min(cnt[11], pend_cap);
-                if (cnt[11]) {
-                    // tasks whose piece list overflowed its LDS slots: the same certificate, from their pending records
-                    HIP_TRY(c, vtxk_launch_band_pending(c->d_pend.as<uint32_t>(), cnt[11], c->d_pend_buf.as<uint32_t>(),
-                                                        c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), c->d_poly.as<uint16_t>(),
-                                                        poly_stride / 2, c->d_hard.as<uint32_t>(), d_cnt, s));
-                    HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    HIP_TRY(c, hipStreamSynchronize(s));
-                    pending_total += cnt[11];
-                    ++launches;
-                }
-                if (int rc = masked_dp(cnt[0], c->d_hard.as<uint32_t>(), c->d_poly.as<uint16_t>(), c->d_band.as<uint16_t>(), slots, s, VTX_STAGE_RUN_DP)) return rc;
-                hard_total += cnt[0];
-                ++launches;
-                if (sweep_used && base + chunk >= t_end) {
-                    // last chunk.  What overflowed band_run_kernel's lists (d_over[0, nA)) takes band_sweep_kernel too; then everything
-                    // the sweep declined — here and in the chunks' own sweeps: d_over[2 n_tasks, + nB), counted on the device — takes the
-                    // general band kernel (round 4's kernel, libvtx_dev.so: first its second pass, [2 n_tasks + nB, + nC) is what is left).
-                    uint32_t* over = c->d_over.as<uint32_t>();
-                    const uint32_t nA = cnt[1];
-                    if (nA) {
-                        // (these tasks left band_diag_kernel for another reason than their number of matches, and then overflowed
-                        // band_run_kernel's piece lists: repeats as well — on real-sequence loci 0.9 M tasks.  The second stage first, when
-                        // the tables of every locus are still resident.)
-                        const uint32_t* sl = over;
-                        uint32_t n_sweep = nA;
-                        if (second_stage_on(nA) && gt_bytes && !gt_chunked && nA <= chunk && c->d_dense.cap >= (size_t)nA * sizeof(uint32_t)) {
-                            if (int rc = second_stage(over, nA, 0, c->d_dense.as<uint32_t>(), &n_sweep)) return rc;
-                            sl = c->d_dense.as<uint32_t>();
-                        }
-                        if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, over + 2 * n_tasks, d_cnt + 26)) return rc; }
-                        swept_total += n_sweep;
-                    }
-                    uint32_t nB = 0, nC = 0;
-                    HIP_TRY(c, hipMemcpyAsync(&nB, d_cnt + 27, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    HIP_TRY(c, hipStreamSynchronize(s));
-                    if (int rc = collect_sweep_times()) return rc;
-                    if (nB && sweep_v1) {                       // (round 4's kernel only: its second pass with the larger log)
-                        resweep_total = nB;
-                        if (int rc = sweep_slices(1, over + 2 * n_tasks, nB, over + 2 * n_tasks + nB, d_cnt + 28)) return rc;
-                        HIP_TRY(c, hipMemcpyAsync(&nC, d_cnt + 29, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                        HIP_TRY(c, hipStreamSynchronize(s));
-                    } else if (nB) {                            // what band_sweep_kernel declines (bytes outside ACGTN, > 255 bases, > 1 024 sections, a
-                        nC = nB; nB = 0;                        // full stash bucket) takes the general band kernel
-                    }
-                    cnt[1] = nC;
-                    if (nC) { if (int rc = fallback_start((uint32_t)(2 * n_tasks) + nB, (uint32_t)(2 * n_tasks) + nB + nC)) return rc; }
-                }
-            }
-            fast_overflow = cnt[1];
-            if (getenv("VTX_DEBUG")) {
-                uint32_t why[11];
-                HIP_TRY(c, hipMemcpy(why, d_cnt, sizeof why, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[vtx] band_run_kernel: %u tasks hard only because pieces were dropped from a full list\n", why[10]);
-                fprintf(stderr, "[vtx] band_run_kernel overflow reasons: bound=%u parked-full=%u log-full=%u other=%u traceback=%u\n", why[3], why[4], why[5], why[6], why[7]);
-            }
-            if (int rc = fallback_finish()) return rc;
-            c->fast_overflow += fast_overflow;
-            c->timing.diag_ms += diag_ms; c->timing.diag_left += (uint32_t)std::min<uint64_t>(diag_left, 0xffffffffull);
-            c->timing.check_ms += check_ms; c->timing.sweep_ms += sweep_ms;
-            c->timing.swept_tasks += (uint32_t)std::min<uint64_t>(swept_total, 0xffffffffull);
-            c->timing.resweep_tasks += resweep_total;
-            c->timing.diag2_tasks += (uint32_t)std::min<uint64_t>(diag2_total, 0xffffffffull);
-            c->timing.diag2_scored += (uint32_t)std::min<uint64_t>(diag2_scored, 0xffffffffull);
-            c->timing.diag2_streamed += (uint32_t)std::min<uint64_t>(stream_total, 0xffffffffull);
-            checked_total += tight2_total;                     // (one-diagonal bands of the second stage: the same masked DP)
-            c->timing.checked_tasks += (uint32_t)std::min<uint64_t>(checked_total, 0xffffffffull);
-            if (swept_total) hard_total += (uint32_t)std::min<uint64_t>(swept_total - std::min<uint64_t>(swept_total, fast_overflow), 0xffffffffull);
-            hard_total += (uint32_t)std::min<uint64_t>(checked_total, 0xffffffffull);      // (tasks with a certificate: masked DP over their diagonal band; with VTX_BAND_CHECK an upper bound)
-            if (getenv("VTX_DEBUG") && diag_total) {
-                uint32_t why[16];
-                HIP_TRY(c, hipMemcpy(why, d_cnt + 32, sizeof why, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[vtx] band_refine_kernel: %llu tasks listed\n", (unsigned long long)refined_total);
-                fprintf(stderr, "[vtx] band_diag_kernel: %llu of %llu tasks left to band_run_kernel (%.2f %%), %.2f ms: shape=%u no-diagonal=%u pieces=%u matches=%u not-harmless=%u generic=%u not-tight=%u no-main=%u\n",
-                        (unsigned long long)diag_left, (unsigned long long)diag_total, 100.0 * (double)diag_left / (double)diag_total, (double)diag_ms,
-                        why[1], why[2], why[3], why[4], why[5], why[7], why[8], why[9]);
-            }
-            if (getenv("VTX_DEBUG") && diag2_total)
-                fprintf(stderr, "[vtx] band_diag2_kernel: %llu tasks looked at, %llu scored, %llu left with a one-diagonal band, %llu to band_sweep_kernel (%llu through band_stream_kernel)\n",
-                        (unsigned long long)diag2_total, (unsigned long long)diag2_scored, (unsigned long long)tight2_total,
-                        (unsigned long long)(diag2_total - diag2_scored - tight2_total), (unsigned long long)stream_total);
-            if (getenv("VTX_DEBUG")) fprintf(stderr, "[vtx] banded: %llu tasks, %u overflowed band_run_kernel, %u bounded by the pending kernel, %u hard\n", (unsigned long long)n_tasks, fast_overflow, pending_total, hard_total);
-            return VTX_OK;
-        };
-        // Shape per task (round 6).  A haplotype above 255 bases (a long deletion or insertion, a larger --padding) does not fit the
-        // two-byte match entries of band_diag_kernel<., uint16_t> nor band_sweep_kernel's 256 columns; ONE such locus used to put the
-        // whole batch on round 3's path (config 3: 18.9 instead of 15.9 ms; repeat-rich loci lose the sweep and the second stage, 2x).
-        // When they are few, two passes: every locus up to 255 bases as if the others were not there, then the stretch of tasks from
-        // the first to the last long locus with round 3's kernels, the short loci skipped (measured, config 3 + 1 long locus: 16.45 ms;
-        // + 20 spread over the batch: 17.6 ms — the second pass walks the whole stretch: 0.6 ms of skipping, 1 ms of launches).
-        // (Many long loci — a batch at --padding 150 — : one pass as before; two would walk the batch twice for nothing.)
-        static const bool no_split = VTX_DEV_ENV("VTX_BAND_NO_SPLIT") != nullptr;          // test hook: the single pass of rounds 3 - 5
-        const bool split = !no_split && c->max_hap_len > 255 && c->hap_short_max > 0 && c->n_long_loci > 0 &&
-                           (uint64_t)c->n_long_loci * 8 <= c->n_loci;
-        if (!split) {
-            if (int rc = band_pass(c->max_hap_len, 0, 0, 2ull * nr, false)) return rc;
-        } else {
-            if (int rc = band_pass(c->hap_short_max, 0, 0, 2ull * nr, false)) return rc;
-            vtx_locus ends[2];
-            HIP_TRY(c, hipMemcpyAsync(&ends[0], c->d_loci.as<vtx_locus>() + c->long_first, sizeof(vtx_locus), hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(&ends[1], c->d_loci.as<vtx_locus>() + c->long_last, sizeof(vtx_locus), hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            const uint64_t t0 = 2ull * std::min(ends[0].rec_begin, nr), t1 = 2ull * std::min<uint64_t>((uint64_t)ends[1].rec_begin + ends[1].rec_count, nr);
-            if (t1 > t0) { if (int rc = band_pass(c->max_hap_len, 255, t0, t1, true)) return rc; }
-        }
+    HIP_TRY(c, hipEventRecord(c->ev[EV_FULL_END], s));
+    return VTX_OK;
+}
+// One pass, or two when a few loci have haplotypes above 255 bases (the shape per task of round 6: DESIGN.md 4.3.1, "Host orchestration"): every locus up
+// to 255 bases as if the others were not there, then the stretch of tasks from the first to the last long locus with round 3's kernels.
+int run_banded(vtx_ctx* c, RunState& rs) {
+    hipStream_t s = c->stream; const uint32_t nr = c->n_records;
+    const bool split = !band_knobs().no_split && c->max_hap_len > 255 && c->hap_short_max > 0 && c->n_long_loci > 0 && (uint64_t)c->n_long_loci * 8 <= c->n_loci;
+    if (!split) return BandPass(c, rs, c->max_hap_len, 0, 0, 2ull * nr, false).run();
+    if (int rc = BandPass(c, rs, c->hap_short_max, 0, 0, 2ull * nr, false).run()) return rc;
+    vtx_locus ends[2];
+    HIP_TRY(c, hipMemcpyAsync(&ends[0], rs.a.loci + c->long_first, sizeof(vtx_locus), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&ends[1], rs.a.loci + c->long_last, sizeof(vtx_locus), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const uint64_t t0 = 2ull * std::min(ends[0].rec_begin, nr), t1 = 2ull * std::min<uint64_t>((uint64_t)ends[1].rec_begin + ends[1].rec_count, nr);
+    if (t1 > t0) return BandPass(c, rs, c->max_hap_len, 255, t0, t1, true).run();
+    return VTX_OK;
+}
+// records beyond the fast kernels' limits: exact slow path, both flavours (slabs grow until every chain fits)
+int run_slow(vtx_ctx* c, RunState& rs) {
+    hipStream_t s = c->stream;
+    const uint32_t n_slow = 2 * c->slow_cnt;
+    const int banded = c->cfg.aligner == VTX_ALIGNER_BANDED;
+    if (rs.stage) HIP_TRY(c, vtxk_mark_stage_records(c->d_work.as<uint32_t>() + c->slow_off, c->slow_cnt, VTX_STAGE_SLOW, rs.stage, s));
+    HIP_TRY(c, c->d_cnt.reserve(VTX_CNT_WORDS * sizeof(uint32_t)));
+    uint32_t* d_scnt = c->d_cnt.as<uint32_t>() + VTX_CNT_SLOW;
+    HIP_TRY(c, c->d_slow_retry.reserve(2 * (size_t)n_slow * sizeof(uint32_t)));
+    const uint32_t* tasks = nullptr; uint32_t todo = n_slow, cap = 1024;
+    const uint32_t mh = std::max(c->max_hap_all, 1u);
+    for (;;) {
+        const uint64_t worst = (uint64_t)c->max_read_all * mh;
+        const size_t stride = vtxk_slow_ws_stride(cap, mh, c->max_read_all);
+        HIP_TRY(c, c->d_slow_ws.reserve((size_t)todo * stride));
+        HIP_TRY(c, hipMemsetAsync(d_scnt, 0, sizeof(uint32_t), s));
+        uint32_t* retry = c->d_slow_retry.as<uint32_t>() + ((tasks == c->d_slow_retry.as<uint32_t>()) ? n_slow : 0);
+        HIP_TRY(c, launch_slow_align(rs.a, c->d_work.as<uint32_t>() + c->slow_off, tasks, todo, banded, c->d_slow_ws.as<uint8_t>(), stride, cap, mh, c->max_read_all, retry, d_scnt, s));
+        uint32_t left = 0;
+        HIP_TRY(c, hipMemcpyAsync(&left, d_scnt, sizeof left, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        ++rs.launches;
+        if (!left) return VTX_OK;
+        if (cap >= worst) return fail(c, VTX_E_STATE, "vtx_run: slow path overflow with a worst-case slab");
+        cap = (uint32_t)std::min<uint64_t>((uint64_t)cap * 16, std::max<uint64_t>(worst, 1024));
+        tasks = retry; todo = left;
     }
-    if (c->slow_cnt) {
-        // records beyond the fast kernels' limits: exact slow path, both flavours (slabs grow until every chain fits)
-        const uint32_t n_slow = 2 * c->slow_cnt;
-        const int banded = c->cfg.aligner == VTX_ALIGNER_BANDED;
-        if (stage) HIP_TRY(c, vtxk_mark_stage_records(c->d_work.as<uint32_t>() + c->slow_off, c->slow_cnt, VTX_STAGE_SLOW, stage, s));
-        HIP_TRY(c, c->d_cnt.reserve(64 * sizeof(uint32_t)));
-        uint32_t* d_scnt = c->d_cnt.as<uint32_t>() + 13;
-        HIP_TRY(c, c->d_slow_retry.reserve(2 * (size_t)n_slow * sizeof(uint32_t)));
-        const uint32_t* tasks = nullptr;
-        uint32_t todo = n_slow, cap = 1024;
-        const uint32_t mh = std::max(c->max_hap_all, 1u);
-        for (;;) {
-            const uint64_t worst = (uint64_t)c->max_read_all * mh;
-            const size_t stride = vtxk_slow_ws_stride(cap, mh, c->max_read_all);
-            HIP_TRY(c, c->d_slow_ws.reserve((size_t)todo * stride));
-            HIP_TRY(c, hipMemsetAsync(d_scnt, 0, sizeof(uint32_t), s));
-            uint32_t* retry = c->d_slow_retry.as<uint32_t>() + ((tasks == c->d_slow_retry.as<uint32_t>()) ? n_slow : 0);
-            HIP_TRY(c, vtxk_launch_slow_align(c->d_work.as<uint32_t>() + c->slow_off, tasks, todo, banded, c->d_records.as<vtx_record>(),
-                                              c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(),
-                                              c->d_hap.as<uint8_t>(), c->d_slow_ws.as<uint8_t>(), stride, cap, mh, c->max_read_all,
-                                              c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), retry, d_scnt, s));
-            uint32_t left = 0;
-            HIP_TRY(c, hipMemcpyAsync(&left, d_scnt, sizeof left, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            ++launches;
-            if (!left) break;
-            if (cap >= worst) return fail(c, VTX_E_STATE, "vtx_run: slow path overflow with a worst-case slab");
-            cap = (uint32_t)std::min<uint64_t>((uint64_t)cap * 16, std::max<uint64_t>(worst, 1024));
-            tasks = retry; todo = left;
-        }
-    }
-    HIP_TRY(c, hipEventRecord(c->ev[1], s));
-    uint32_t nnz32 = 0;
-    const uint32_t ng = c->n_cell_groups, nu = c->n_umi_groups;
-    // Short groups (the mean at most kReduceMeanGroupMax records): one thread per group counts its records in registers, twice —
-    // once for the kept groups per block, once to emit behind the scanned block counts (d_keep / d_keep_scan hold one word per
-    // block of groups then).  Deep groups: a histogram with atomics, one thread per record.
+}
+// The call reduction: scores -> triplets; *nnz32 arrives with the stream's next synchronisation. Short groups (the mean at most kReduceMeanGroupMax records): one thread per group counts its
+// records in registers, twice — once for the kept groups per block, once to emit behind the scanned block counts (d_keep / d_keep_scan hold one word per block of groups then).  Deep groups: a
+// histogram with atomics, one thread per record.
+int run_reduce(vtx_ctx* c, const RunState& rs, uint32_t* nnz32) {
+    hipStream_t s = c->stream;
+    const uint32_t nr = c->n_records, ng = c->n_cell_groups, nu = c->n_umi_groups;
+    const int32_t *ref = rs.a.ref, *alt = rs.a.alt;
     uint32_t mean_max = kReduceMeanGroupMax;
     if (VTX_DEV_ENV("VTX_REDUCE_THRESHOLD")) mean_max = (uint32_t)strtoul(VTX_DEV_ENV("VTX_REDUCE_THRESHOLD"), nullptr, 10);   // test hook (read per run)
     const bool legacy = VTX_DEV_ENV("VTX_REDUCE_LEGACY") && atoi(VTX_DEV_ENV("VTX_REDUCE_LEGACY"));                            // A/B and test hook (read per run)
     const bool onepass = !legacy && (uint64_t)nr <= (uint64_t)mean_max * ng;
     c->reduce_path = nr ? (onepass ? 2 : 1) : 0;
+    uint32_t *keep = c->d_keep.as<uint32_t>(), *keep_scan = c->d_keep_scan.as<uint32_t>();
     if (nr && onepass) {
         const uint32_t nb = vtxk_reduce_blocks(ng);
-        HIP_TRY(c, vtxk_reduce_count(c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), c->d_head_umi.as<uint32_t>(), c->d_grp_start.as<uint32_t>(),
-                                     ng, c->cfg.min_score, c->cfg.use_umi, c->cfg.scoring_mode, c->d_keep.as<uint32_t>(), s));
-        HIP_TRY(c, vtxk_inclusive_scan_u32(c->d_keep.as<uint32_t>(), c->d_keep_scan.as<uint32_t>(), nb, c->d_scan_tmp.p, vtxk_scan_temp_bytes(nr), s));
-        HIP_TRY(c, vtxk_reduce_emit(c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), c->d_head_umi.as<uint32_t>(), c->d_grp_start.as<uint32_t>(),
-                                    ng, c->cfg.min_score, c->cfg.use_umi, c->cfg.scoring_mode, c->d_keep_scan.as<uint32_t>(),
-                                    c->d_grp_row.as<uint32_t>(), c->d_grp_col.as<uint32_t>(), c->d_o_row.as<uint32_t>(),
-                                    c->d_o_col.as<uint32_t>(), c->d_o_alt.as<uint32_t>(), c->d_o_ref.as<uint32_t>(),
-                                    c->d_o_unk.as<uint32_t>(), c->d_o_val.as<double>(), c->d_o_refval.as<double>(), s));
-        if (nb) HIP_TRY(c, hipMemcpyAsync(&nnz32, c->d_keep_scan.as<uint32_t>() + (nb - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, vtxk_reduce_count(ref, alt, c->d_head_umi.as<uint32_t>(), c->d_grp_start.as<uint32_t>(), ng, c->cfg.min_score, c->cfg.use_umi, c->cfg.scoring_mode, keep, s));
+        HIP_TRY(c, vtxk_inclusive_scan_u32(keep, keep_scan, nb, c->d_scan_tmp.p, vtxk_scan_temp_bytes(nr), s));
+        HIP_TRY(c, vtxk_reduce_emit(ref, alt, c->d_head_umi.as<uint32_t>(), c->d_grp_start.as<uint32_t>(), ng, c->cfg.min_score, c->cfg.use_umi, c->cfg.scoring_mode, keep_scan, c->d_grp_row.as<uint32_t>(), c->d_grp_col.as<uint32_t>(),
+                c->d_o_row.as<uint32_t>(), c->d_o_col.as<uint32_t>(), c->d_o_alt.as<uint32_t>(), c->d_o_ref.as<uint32_t>(), c->d_o_unk.as<uint32_t>(), c->d_o_val.as<double>(), c->d_o_refval.as<double>(), s));
+        if (nb) HIP_TRY(c, hipMemcpyAsync(nnz32, keep_scan + (nb - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     } else if (nr) {
         const size_t tmp_bytes = vtxk_scan_temp_bytes(nr);
-        HIP_TRY(c, hipMemsetAsync(c->d_cell_cnt.p, 0, 3 * (size_t)ng * sizeof(uint32_t), s));
+        uint32_t* cell_cnt = c->d_cell_cnt.as<uint32_t>();
+        HIP_TRY(c, hipMemsetAsync(cell_cnt, 0, 3 * (size_t)ng * sizeof(uint32_t), s));
         if (c->cfg.use_umi) {
             HIP_TRY(c, hipMemsetAsync(c->d_umi_cnt.p, 0, 3 * (size_t)nu * sizeof(uint32_t), s));
-            HIP_TRY(c, vtxk_count_calls(c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), nr, c->cfg.min_score,
-                                        c->d_umi_scan.as<uint32_t>(), c->d_umi_cnt.as<uint32_t>(), s));
-            HIP_TRY(c, vtxk_umi_collapse(c->d_umi_cnt.as<uint32_t>(), nu, c->d_umi_cellgrp.as<uint32_t>(), c->d_cell_cnt.as<uint32_t>(), s));
+            HIP_TRY(c, vtxk_count_calls(ref, alt, nr, c->cfg.min_score, c->d_umi_scan.as<uint32_t>(), c->d_umi_cnt.as<uint32_t>(), s));
+            HIP_TRY(c, vtxk_umi_collapse(c->d_umi_cnt.as<uint32_t>(), nu, c->d_umi_cellgrp.as<uint32_t>(), cell_cnt, s));
         } else {
-            HIP_TRY(c, vtxk_count_calls(c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>(), nr, c->cfg.min_score,
-                                        c->d_cell_scan.as<uint32_t>(), c->d_cell_cnt.as<uint32_t>(), s));
+            HIP_TRY(c, vtxk_count_calls(ref, alt, nr, c->cfg.min_score, c->d_cell_scan.as<uint32_t>(), cell_cnt, s));
         }
-        HIP_TRY(c, vtxk_keep_flags(c->d_cell_cnt.as<uint32_t>(), ng, c->cfg.scoring_mode, c->d_keep.as<uint32_t>(), s));
-        HIP_TRY(c, vtxk_inclusive_scan_u32(c->d_keep.as<uint32_t>(), c->d_keep_scan.as<uint32_t>(), ng, c->d_scan_tmp.p, tmp_bytes, s));
-        HIP_TRY(c, vtxk_emit_coo(c->d_cell_cnt.as<uint32_t>(), ng, c->cfg.scoring_mode, c->d_keep.as<uint32_t>(),
-                                 c->d_keep_scan.as<uint32_t>(), c->d_grp_row.as<uint32_t>(), c->d_grp_col.as<uint32_t>(),
-                                 c->d_o_row.as<uint32_t>(), c->d_o_col.as<uint32_t>(), c->d_o_alt.as<uint32_t>(),
-                                 c->d_o_ref.as<uint32_t>(), c->d_o_unk.as<uint32_t>(), c->d_o_val.as<double>(),
-                                 c->d_o_refval.as<double>(), s));
-        if (ng) HIP_TRY(c, hipMemcpyAsync(&nnz32, c->d_keep_scan.as<uint32_t>() + (ng - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, vtxk_keep_flags(cell_cnt, ng, c->cfg.scoring_mode, keep, s));
+        HIP_TRY(c, vtxk_inclusive_scan_u32(keep, keep_scan, ng, c->d_scan_tmp.p, tmp_bytes, s));
+        HIP_TRY(c, vtxk_emit_coo(cell_cnt, ng, c->cfg.scoring_mode, keep, keep_scan, c->d_grp_row.as<uint32_t>(), c->d_grp_col.as<uint32_t>(), c->d_o_row.as<uint32_t>(), c->d_o_col.as<uint32_t>(), c->d_o_alt.as<uint32_t>(),
+                c->d_o_ref.as<uint32_t>(), c->d_o_unk.as<uint32_t>(), c->d_o_val.as<double>(), c->d_o_refval.as<double>(), s));
+        if (ng) HIP_TRY(c, hipMemcpyAsync(nnz32, keep_scan + (ng - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     }
-    HIP_TRY(c, hipEventRecord(c->ev[2], s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    c->nnz = nnz32;
+    HIP_TRY(c, hipEventRecord(c->ev[EV_REDUCE_END], s));
+    return VTX_OK;
+}
+
+int run_epilogue(vtx_ctx* c, const RunState& rs) {
     float t01 = 0, t12 = 0, t03 = 0;
-    HIP_TRY(c, hipEventElapsedTime(&t03, c->ev[0], c->ev[3]));
-    c->timing.full_ms = t03;
-    HIP_TRY(c, hipEventElapsedTime(&t01, c->ev[0], c->ev[1]));
-    c->timing.band_ms = t01 - t03;
-    HIP_TRY(c, hipEventElapsedTime(&t12, c->ev[1], c->ev[2]));
+    HIP_TRY(c, hipEventElapsedTime(&t03, c->ev[EV_START], c->ev[EV_FULL_END])); c->timing.full_ms = t03;
+    HIP_TRY(c, hipEventElapsedTime(&t01, c->ev[EV_START], c->ev[EV_DP_END])); c->timing.band_ms = t01 - t03;
+    HIP_TRY(c, hipEventElapsedTime(&t12, c->ev[EV_DP_END], c->ev[EV_REDUCE_END]));
     c->timing.sw_ms = t01; c->timing.reduce_ms = t12; c->timing.total_ms = t01 + t12;
-    c->timing.sw_launches = launches; c->timing.hard_tasks = hard_total;
-    c->timing.band_run_ms = band_run_ms; c->timing.overflow_tasks = c->fast_overflow;
+    c->timing.sw_launches = rs.launches; c->timing.hard_tasks = rs.hard_total;
+    c->timing.band_run_ms = rs.band_run_ms; c->timing.overflow_tasks = c->fast_overflow;
+    return VTX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vtx_run(vtx_ctx* c) {
+    if (!c) return VTX_E_INVAL;
+    if (!c->submitted) return fail(c, VTX_E_STATE, "vtx_run: no batch submitted");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    RunState rs;
+    if (int rc = run_prologue(c, rs)) return rc;
+    if (int rc = run_full_dp(c, rs)) return rc;
+    if (c->cfg.aligner == VTX_ALIGNER_BANDED && c->n_records) { if (int rc = run_banded(c, rs)) return rc; }
+    if (c->slow_cnt) { if (int rc = run_slow(c, rs)) return rc; }
+    HIP_TRY(c, hipEventRecord(c->ev[EV_DP_END], c->stream));
+    uint32_t nnz32 = 0;
+    if (int rc = run_reduce(c, rs, &nnz32)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->nnz = nnz32;
+    if (int rc = run_epilogue(c, rs)) return rc;
     c->ran = true;
     return VTX_OK;
 }
@@ -2416,32 +2417,30 @@ int vtx_debug_bands(vtx_ctx* c, const uint32_t* tasks, uint32_t n_tasks, uint32_
     auto done = [&](int rc) { d_t.release(); d_h.release(); d_o.release(); d_c.release(); d_b.release(); d_d.release(); return rc; };
 #define DBG_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return done(fail(c, VTX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_))); } while (0)
     DBG_TRY(d_t.reserve((size_t)n_tasks * 4)); DBG_TRY(d_h.reserve((size_t)n_tasks * 4)); DBG_TRY(d_o.reserve((size_t)n_tasks * 4));
-    DBG_TRY(d_c.reserve(64 * 4)); DBG_TRY(d_b.reserve((size_t)n_tasks * 2 * bs * sizeof(uint16_t)));
+    DBG_TRY(d_c.reserve(VTX_CNT_WORDS * 4)); DBG_TRY(d_b.reserve((size_t)n_tasks * 2 * bs * sizeof(uint16_t)));
     const bool dbg_on = VTX_DEV_ENV("VTX_SWEEP_DBG") != nullptr;        // developer aid: the kernel's per-task intermediate state on stderr
     if (dbg_on) DBG_TRY(d_d.reserve((size_t)n_tasks * 64 * 4));
     DBG_TRY(hipMemcpyAsync(d_t.p, tasks, (size_t)n_tasks * 4, hipMemcpyHostToDevice, s));
-    DBG_TRY(hipMemsetAsync(d_c.p, 0, 64 * 4, s));
+    DBG_TRY(hipMemsetAsync(d_c.p, 0, VTX_CNT_WORDS * 4, s));
     DBG_TRY(c->d_sweep_log.reserve(vtxk_band_sweep_log_bytes()));
+    const TaskArrays a{c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), nullptr, nullptr};
+    uint32_t* dbg = dbg_on ? d_d.as<uint32_t>() : nullptr;
 #ifdef VTX_DEVTOOLS
     // (libvtx_dev.so: VTX_SWEEP_V1=1 asks round 4's kernel instead; VTX_SWEEP_TIER=1 its 1024-section variant)
     if (VTX_DEV_ENV("VTX_SWEEP_V1"))
-        DBG_TRY(vtxk_launch_band_sweep_v1(VTX_DEV_ENV("VTX_SWEEP_TIER") ? atoi(VTX_DEV_ENV("VTX_SWEEP_TIER")) : 0, d_t.as<uint32_t>(), n_tasks, nullptr,
-                                          c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(),
-                                          c->d_hap.as<uint8_t>(), d_b.as<uint16_t>(), bs, d_h.as<uint32_t>(), d_o.as<uint32_t>(), d_c.as<uint32_t>(), nullptr,
-                                          nullptr, dbg_on ? d_d.as<uint32_t>() : nullptr, s));
+        DBG_TRY(vtxk_launch_band_sweep_v1(VTX_DEV_ENV("VTX_SWEEP_TIER") ? atoi(VTX_DEV_ENV("VTX_SWEEP_TIER")) : 0, d_t.as<uint32_t>(), n_tasks, nullptr, a.records, a.rec_locus, a.loci, a.read, a.hap,
+                                          d_b.as<uint16_t>(), bs, d_h.as<uint32_t>(), d_o.as<uint32_t>(), d_c.as<uint32_t>(), nullptr, nullptr, dbg, s));
     else
 #endif
-    DBG_TRY(vtxk_launch_band_sweep(d_t.as<uint32_t>(), n_tasks, nullptr, c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(),
-                                   c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), d_b.as<uint16_t>(), bs,
-                                   d_h.as<uint32_t>(), d_o.as<uint32_t>(), d_c.as<uint32_t>(), nullptr, nullptr, dbg_on ? d_d.as<uint32_t>() : nullptr,
-                                   c->d_sweep_log.as<uint32_t>(), s));
-    uint32_t cnt[2] = {0, 0};
-    DBG_TRY(hipMemcpyAsync(cnt, d_c.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+    DBG_TRY(vtxk_launch_band_sweep(d_t.as<uint32_t>(), n_tasks, nullptr, a.records, a.rec_locus, a.loci, a.read, a.hap, d_b.as<uint16_t>(), bs, d_h.as<uint32_t>(), d_o.as<uint32_t>(), d_c.as<uint32_t>(),
+                                   nullptr, nullptr, dbg, c->d_sweep_log.as<uint32_t>(), s));
+    struct { uint32_t hard = 0, declined = 0; } swept;   // band_sweep_kernel's two counters
+    DBG_TRY(hipMemcpyAsync(&swept, d_c.p, sizeof swept, hipMemcpyDeviceToHost, s));
     DBG_TRY(hipStreamSynchronize(s));
-    std::vector<uint32_t> hard(cnt[0]);
-    std::vector<uint16_t> bands((size_t)cnt[0] * 2 * bs);
-    if (cnt[0]) {
-        DBG_TRY(hipMemcpy(hard.data(), d_h.p, (size_t)cnt[0] * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> hard(swept.hard);
+    std::vector<uint16_t> bands((size_t)swept.hard * 2 * bs);
+    if (swept.hard) {
+        DBG_TRY(hipMemcpy(hard.data(), d_h.p, (size_t)swept.hard * 4, hipMemcpyDeviceToHost));
         DBG_TRY(hipMemcpy(bands.data(), d_b.p, bands.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
     }
     if (dbg_on) {
@@ -2463,8 +2462,8 @@ int vtx_debug_bands(vtx_ctx* c, const uint32_t* tasks, uint32_t n_tasks, uint32_
     }
 #undef DBG_TRY
     // slots come out in any order, and a task may be listed more than once: every occurrence of a task gets the band of one of its slots
-    std::vector<std::pair<uint32_t, uint32_t>> by_task(cnt[0]);
-    for (uint32_t h = 0; h < cnt[0]; ++h) by_task[h] = {hard[h], h};
+    std::vector<std::pair<uint32_t, uint32_t>> by_task(swept.hard);
+    for (uint32_t h = 0; h < swept.hard; ++h) by_task[h] = {hard[h], h};
     std::sort(by_task.begin(), by_task.end());
     for (uint32_t i = 0; i < n_tasks; ++i) {
         auto it = std::lower_bound(by_task.begin(), by_task.end(), std::make_pair(tasks[i], 0u));

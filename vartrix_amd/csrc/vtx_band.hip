@@ -1381,7 +1381,7 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
     uint32_t* mylog = logbuf + (size_t)blockIdx.x * NT * TASK_WORDS + tid * 2;
     const uint32_t n_blocks = (n_tasks + NT - 1) / NT;
     // Workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8); each XCD claims blocks from its own eighth of the
-    // batch first (counters[16 + xcd]), so the ~8 wavefronts that share a locus' tables and reads meet in one L2, and
+    // batch first (counters[VTX_CNT_BLOCK + xcd]), so the ~8 wavefronts that share a locus' tables and reads meet in one L2, and
     // helps the other eighths out when its own is done.
     // (xcd_claim == 0: one range for all)
     const bool by_xcd = xcd_claim != 0;
@@ -1395,7 +1395,7 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
         while (turn < 8) {
             const uint32_t r = (xcd + turn) & 7u;
             const uint32_t lo = r * per_xcd, hi = min(n_blocks, lo + per_xcd);
-            const uint32_t k = lo + atomicAdd(&counters[16 + r], 1u);
+            const uint32_t k = lo + atomicAdd(&counters[VTX_CNT_BLOCK + r], 1u);
             if (lo < hi && k < hi) { b = k; break; }
             ++turn;
         }
@@ -1431,9 +1431,9 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
                  max(loci[my_locus].ref_len, loci[my_locus].alt_len) <= min_hap)) done = true;
     // a task without any k-mer match has the whole matrix in band (Band::full_matrix): hard list, marker slot
     // (hard slots beyond the capacity of the band buffer go to the general kernel's list, which makes them hard in slices)
-#define PUSH_FULL_MATRIX() { const uint32_t h_ = atomicAdd(&counters[0], 1u);                                    \
+#define PUSH_FULL_MATRIX() { const uint32_t h_ = atomicAdd(&counters[VTX_CNT_HARD], 1u);                                    \
                              if (h_ < hard_cap) { hard_list[h_] = task; band[(size_t)h_ * 2 * band_stride] = BAND_FULL_MATRIX; } \
-                             else overflow_list[atomicAdd(&counters[1], 1u)] = task; }
+                             else overflow_list[atomicAdd(&counters[VTX_CNT_OVERFLOW], 1u)] = task; }
 
     for (uint32_t lbase = GT ? 0u : l_first; lbase <= (GT ? 0u : l_last); lbase += loci_per_pass) {     // GT: one pass over every locus
         const uint32_t n_tab = GT ? 0u : min(loci_per_pass, l_last - lbase + 1) * 2;
@@ -1472,7 +1472,7 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
                 const uint32_t nb = (xr + KMER < m) ? x[xr + KMER] : 0;
                 wl = (wl >> 8) | (wh << 24); wh = ((wh >> 8) & 0xff) | (nb << 8);
             }
-            if (cntm == 0xffffffffu) counters[7] = cntm;
+            if (cntm == 0xffffffffu) counters[VTX_CNT_RUN_WHY_LAST] = cntm;
             continue;
         }
 
@@ -1609,7 +1609,7 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
         bool overflow = st.overflow;
         uint32_t why = st.why;
         if (!overflow && st.n_ent == 0 && st.best_v < 0) { PUSH_FULL_MATRIX() continue; }   // no k-mer match
-        if (VTX_ABLATE(ablate) == 3) { if (st.n_ent == 0xffffu) counters[7] = st.n_ent; continue; }   // (profiling aid) phase 1 only
+        if (VTX_ABLATE(ablate) == 3) { if (st.n_ent == 0xffffu) counters[VTX_CNT_RUN_WHY_LAST] = st.n_ent; continue; }   // (profiling aid) phase 1 only
         // ================= phase 2: the rest of the chain DP =================
         if (!overflow) {
             uint32_t no_a = NONE_ID, no_b = NONE_ID;
@@ -1625,25 +1625,25 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
         }
         const uint32_t lg_n = st.lg_n;
         const uint32_t best_id = st.best_id;
-        if (overflow) { overflow_list[atomicAdd(&counters[1], 1u)] = task; atomicAdd(&counters[2 + why], 1u); continue; }
+        if (overflow) { overflow_list[atomicAdd(&counters[VTX_CNT_OVERFLOW], 1u)] = task; atomicAdd(&counters[VTX_CNT_RUN_WHY + why], 1u); continue; }
         // ================= certificate: chain-of-runs upper bound vs the staircase's own score =================
         // Tasks whose list lost pieces to run_compact cannot bound here: their pieces (list + spill area) go to
         // band_pending_kernel, which computes the same bound with a wavefront's lanes over up to 32 pieces.
         const bool pending = st.ub_ok && st.n_sp > 0;
         const int32_t ub = (st.ub_ok && !pending) ? run_ub<NT>(pm_a, pm_id, tid, st.n_ent) : INT32_MAX;
-        if (VTX_ABLATE(ablate) == 4) { if (ub == -1) counters[7] = 1; continue; }   // (profiling aid) everything but the staircase walk
+        if (VTX_ABLATE(ablate) == 4) { if (ub == -1) counters[VTX_CNT_RUN_WHY_LAST] = 1; continue; }   // (profiling aid) everything but the staircase walk
         uint32_t verts[4 * SG + 6];
         uint32_t nv = 0;
         int32_t cert = 0;
         {
             const int fr = band_finish(mylog, 2 * NT, lg_n, best_id, x, yb, m, n, ub, verts, &nv, &cert);
             if (fr == 0) { *my_score = ub; continue; }
-            if (fr == 2) { overflow_list[atomicAdd(&counters[1], 1u)] = task; atomicAdd(&counters[7], 1u); continue; }
+            if (fr == 2) { overflow_list[atomicAdd(&counters[VTX_CNT_OVERFLOW], 1u)] = task; atomicAdd(&counters[VTX_CNT_RUN_WHY_LAST], 1u); continue; }
         }
         if (pending) {
             // a record for band_pending_kernel: header, certificate, list entries, staircase, spilled pieces
-            const uint32_t pi = atomicAdd(&counters[11], 1u);
-            if (pi >= pend_cap) { overflow_list[atomicAdd(&counters[1], 1u)] = task; continue; }
+            const uint32_t pi = atomicAdd(&counters[VTX_CNT_PENDING], 1u);
+            if (pi >= pend_cap) { overflow_list[atomicAdd(&counters[VTX_CNT_OVERFLOW], 1u)] = task; continue; }
             uint32_t* prec = pend_buf + (size_t)pi * PEND_WORDS;
             prec[0] = st.n_ent | (st.n_sp << 8) | (nv << 16);
             prec[1] = (uint32_t)cert;
@@ -1656,9 +1656,9 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
             pending_list[pi] = task;
             continue;
         }
-        if (!st.ub_ok) atomicAdd(&counters[10], 1u);         // statistics: hard only because too many pieces were dropped
-        const uint32_t h = atomicAdd(&counters[0], 1u);
-        if (h >= hard_cap) { overflow_list[atomicAdd(&counters[1], 1u)] = task; continue; }
+        if (!st.ub_ok) atomicAdd(&counters[VTX_CNT_DROPPED], 1u);         // statistics: hard only because too many pieces were dropped
+        const uint32_t h = atomicAdd(&counters[VTX_CNT_HARD], 1u);
+        if (h >= hard_cap) { overflow_list[atomicAdd(&counters[VTX_CNT_OVERFLOW], 1u)] = task; continue; }
         hard_list[h] = task;
         uint16_t* lo = band + (size_t)h * 2 * band_stride;
         lo[0] = BAND_POLYLINE; lo[1] = (uint16_t)nv;
@@ -1749,7 +1749,7 @@ __global__ __launch_bounds__(256) void band_pending_kernel(
         return;
     }
     uint32_t h = 0;
-    if (l == 0) { h = atomicAdd(&counters[0], 1u); hard_list[h] = task; }
+    if (l == 0) { h = atomicAdd(&counters[VTX_CNT_HARD], 1u); hard_list[h] = task; }
     h = (uint32_t)__shfl((int)h, 0, 32);
     uint16_t* lo = band + (size_t)h * 2 * band_stride;
     if (l == 0) { lo[0] = BAND_POLYLINE; lo[1] = (uint16_t)nv; }
@@ -1940,7 +1940,7 @@ __global__ __launch_bounds__(256) void band_expand_kernel(const uint32_t* __rest
 // haplotypes of one record: their read loads coalesce); the blocks are dealt so that each XCD works through one
 // contiguous eighth of the batch (workgroups go to the XCDs round-robin): the ~8 wavefronts that share a locus' tables
 // and reads meet in one L2.
-// counters[12] = tasks left to band_run_kernel; counters[32 + why] = reasons (stats != 0).
+// counters[VTX_CNT_RUN_LEFT] = tasks left to band_run_kernel; counters[VTX_CNT_DIAG_WHY + why] = reasons (stats != 0).
 // =============================================================================================
 
 // =============================================================================================
@@ -2118,11 +2118,11 @@ extern "C" uint32_t vtxk_band_tail_words(void) { return (uint32_t)vtxf::TAIL_WOR
 // Where a task goes once the last phase of the certificate is over — band_diag_kernel's lanes and band_tail_kernel's (the tasks the
 // former left in the middle of that phase) alike; every lane of the wavefront calls it.  fail: no verdict (why, aux: back_rest's);
 // tight: the task holds its certificate (harmless matches only).  The lists, each reserved with one atomic per wavefront:
-//   refine_rec (counters[14])  with a tight list a record for band_corridor_kernel (every task that keeps its certificate), else round 3's
+//   refine_rec (counters[VTX_CNT_REFINE])  with a tight list a record for band_corridor_kernel (every task that keeps its certificate), else round 3's
 //                              record for band_refine_kernel (main pieces only, bounds apart); the buffer full: on to the lists below
-//   tight_list (counters[15])  the certificate's band (pack), the certificate as a provisional score
-//   dense_list (counters[13])  the reasons in dense_mask (W_MATCHES: only when spread) — band_sweep_kernel
-//   fail_list  (counters[12])  the rest — band_run_kernel
+//   tight_list (counters[VTX_CNT_TIGHT])  the certificate's band (pack), the certificate as a provisional score
+//   dense_list (counters[VTX_CNT_DENSE])  the reasons in dense_mask (W_MATCHES: only when spread) — band_sweep_kernel
+//   fail_list  (counters[VTX_CNT_RUN_LEFT])  the rest — band_run_kernel
 // Round 6, the sweep path (a tight list): EVERY task that leaves the last phase with its certificate — harmless matches only, bounds
 // apart or the generic set full — leaves a record for band_corridor_kernel (the task, its one-diagonal band, the rows of its
 // matches far out: vtx_fast_core.h, "the corridor certificate") instead of taking the masked DP; what that kernel does not decide
@@ -2142,7 +2142,7 @@ __device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t wh
     if (am) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)am) - 1;
-        if (tid == leader) base = atomicAdd(&counters[14], (uint32_t)__popcll(am));
+        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_REFINE], (uint32_t)__popcll(am));
         base = (uint32_t)__shfl((int)base, leader);
         const uint32_t pos = base + (uint32_t)__popcll(am & ((1ull << tid) - 1ull));
         if (again && pos >= refine_cap) again = false;              // (the record buffer is full: band_run_kernel takes it)
@@ -2167,7 +2167,7 @@ __device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t wh
     if (tm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)tm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[15], (uint32_t)__popcll(tm));
+        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_TIGHT], (uint32_t)__popcll(tm));
         base = (uint32_t)__shfl((int)base, leader);
         if (tight) {
             const uint32_t pos = base + (uint32_t)__popcll(tm & ((1ull << tid) - 1ull));
@@ -2181,7 +2181,7 @@ __device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t wh
     if (dm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)dm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[13], (uint32_t)__popcll(dm));
+        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_DENSE], (uint32_t)__popcll(dm));
         base = (uint32_t)__shfl((int)base, leader);
         if (dense) dense_list[base + (uint32_t)__popcll(dm & ((1ull << tid) - 1ull))] = task;
     }
@@ -2189,11 +2189,11 @@ __device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t wh
     if (fm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)fm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[12], (uint32_t)__popcll(fm));
+        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_RUN_LEFT], (uint32_t)__popcll(fm));
         base = (uint32_t)__shfl((int)base, leader);
         if (fail && !again && !tight && !dense) fail_list[base + (uint32_t)__popcll(fm & ((1ull << tid) - 1ull))] = task;
     }
-    if (fail && !again && (stats & 0xffu)) atomicAdd(&counters[32 + why], 1u);
+    if (fail && !again && (stats & 0xffu)) atomicAdd(&counters[VTX_CNT_DIAG_WHY + why], 1u);
 }
 // ST: type of an off-diagonal match entry — uint16_t (x << 8 | y: 40 entries per task in the same LDS) when every haplotype of
 // the batch has <= 255 bases, else uint32_t (20 entries).
@@ -2210,15 +2210,15 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     // min_hap: tasks of loci whose longer haplotype has <= min_hap bases are left alone (vtx_run's second pass over a batch that mixes
     // haplotypes of <= 255 bases with a few longer ones: the first pass, with two-byte entries and the sweep behind it, scored them).
     // dense_list != nullptr (round 4): a task left for a reason in dense_mask (bit = vtxf::Why; by default W_MATCHES: more than 40
-    // off-diagonal k-mer matches — repeats) goes there (counters[13]): band_run_kernel's piece lists would overflow on it, it takes
+    // off-diagonal k-mer matches — repeats) goes there (counters[VTX_CNT_DENSE]): band_run_kernel's piece lists would overflow on it, it takes
     // band_sweep_kernel directly.
     // tight_list != nullptr (round 4): a task whose off-diagonal matches are all harmless but whose bounds do not meet (or whose
     // generic set overflows) HAS a certificate — the chain is the closed form's, cert <= banded — so it leaves with
-    // its band (the (2w + 1)-squares along ONE diagonal stretch: tight_pack[i] = vtxf::band_pack) on tight_list (counters[15]):
+    // its band (the (2w + 1)-squares along ONE diagonal stretch: tight_pack[i] = vtxf::band_pack) on tight_list (counters[VTX_CNT_TIGHT]):
     // the band-masked DP scores it from that word, without band_sweep_kernel; score = cert meanwhile, a PROVISIONAL score
     // (the optional full-matrix check sw_banded_kernel<.., 1> decides it where full == cert).  Not on fail_list.  stage != nullptr: stage[task] = 1 for every task decided here (vtx_fetch_stage).
     // refine_rec != nullptr: a task with main pieces only whose bounds do not meet leaves a 12-word record for band_refine_kernel
-    // (counters[14]; REFINE_WORDS) instead of going to band_run_kernel's list: that kernel prices the stretches of >= 3 errors
+    // (counters[VTX_CNT_REFINE]; REFINE_WORDS) instead of going to band_run_kernel's list: that kernel prices the stretches of >= 3 errors
     // within a few bases from the real neighbour diagonals and needs nothing else of what this one found.
     // Four wavefronts per workgroup, each on its own 64 consecutive tasks and its own slice of the LDS (no workgroup barrier
     // anywhere): the four share their loci's tables in the CU's L1.
@@ -2294,7 +2294,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
             if constexpr (sizeof(ST) == 2) twins = !(stats & 0x20000u) && vtxf::tab_has_twins(tb);
         }
     }
-    if (VTX_ABLATE((stats >> 8) & 0xffu) == 4) { if (live && m == 0x7fffffff) counters[40] = 1; return; }           // (profiling aid) task set-up only
+    if (VTX_ABLATE((stats >> 8) & 0xffu) == 4) { if (live && m == 0x7fffffff) counters[VTX_CNT_DIAG_DUMMY] = 1; return; }           // (profiling aid) task set-up only
     // ---- the read, once: lanes 2i / 2i + 1 hold the two haplotypes of ONE record, so each loads half of its 8-byte words (16-byte
     //      loads) and the two swap halves — a quarter of the load instructions and of the L2 lines 8-byte loads per lane cost ----
     PH(0);                                                              // task set-up
@@ -2351,7 +2351,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
         }
         if (live && !have_d) { live = false; fail = true; why = vtxf::W_NO_DIAG; }
         PH(3);                                                          // the mask
-        if (VTX_ABLATE((stats >> 8) & 0xffu) == 3) { if (live && d == 0x7fffffff) counters[40] = 1; return; }       // (profiling aid) up to the diagonal and its mask
+        if (VTX_ABLATE((stats >> 8) & 0xffu) == 3) { if (live && d == 0x7fffffff) counters[VTX_CNT_DIAG_DUMMY] = 1; return; }       // (profiling aid) up to the diagonal and its mask
         if (live) {
             vtxf::TwinHead th;
             if (twins) th = vtxf::twin_head(tb);
@@ -2418,7 +2418,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
         }
     }
     vtxf::MIter need_it = vtxf::m_iter(nd);
-    if (VTX_ABLATE((stats >> 8) & 0xffu) == 1) { if (live && fr.cert == 0x7fffffff) counters[40] = 1; return; }      // (profiling aid) front only
+    if (VTX_ABLATE((stats >> 8) & 0xffu) == 1) { if (live && fr.cert == 0x7fffffff) counters[VTX_CNT_DIAG_DUMMY] = 1; return; }      // (profiling aid) front only
     const uint32_t pb_rel = vtxf::tab_pb_off(max_hap, n_heads), head_rel = max_hap * 8u, bytes_rel = vtxf::tab_bytes_off(max_hap, n_heads);
     const uint32_t t3_rel = vtxf::tab_t3_off(max_hap, n_heads);
     // pass 2 over the first n_walk entries of the walk list (every lane calls it; 0xffff: a slot reserved by a lane that did not fit)
@@ -2629,7 +2629,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     walk_list(q_count[1]);
     wave_sync();
     PH(7);                                                              // the walks
-    if (VTX_ABLATE((stats >> 8) & 0xffu) == 2) { if (live && s_cnt[tid] == 0x7fffffffu) counters[40] = 1; return; }   // (profiling aid) front + probes
+    if (VTX_ABLATE((stats >> 8) & 0xffu) == 2) { if (live && s_cnt[tid] == 0x7fffffffu) counters[VTX_CNT_DIAG_DUMMY] = 1; return; }   // (profiling aid) front + probes
     uint32_t aux = 0xffffffffu;
     bool tight = false;
     // ---- the last phase, every lane for itself: sort, harmless tests, closure, run bound (vtx_fast_core.h).  (Pooling the harmless
@@ -2660,12 +2660,12 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     }
     if (live) vtxf::back_sort(ns, ln, (int)(s_cnt[tid] >> 16));
     PH(8);                                                              // sort
-    if (VTX_ABLATE((stats >> 8) & 0xffu) == 7) { if (live && ns == 0x7fffffff) counters[40] = 1; return; }            // (profiling aid) ... + the sort
+    if (VTX_ABLATE((stats >> 8) & 0xffu) == 7) { if (live && ns == 0x7fffffff) counters[VTX_CNT_DIAG_DUMMY] = 1; return; }            // (profiling aid) ... + the sort
     if (live && !vtxf::back_harmless(fr, ns, ln)) { live = false; fail = true; why = vtxf::W_NOT_HARMLESS; }
     PH(9);                                                              // harmless tests
     // The closure's first scan decides whether the generic set stays empty (92 % of the live tasks: one scan and the main-only run bound
     // on piece words in registers).  A task whose set must grow — closure rescans, a fixpoint over (r + ng)^2 piece pairs — costs what
-    // its whole wavefront waits for: it leaves a record for band_tail_kernel instead (tail_rec, counters[44]; vtxf::tail_pack) and writes
+    // its whole wavefront waits for: it leaves a record for band_tail_kernel instead (tail_rec, counters[VTX_CNT_TAIL]; vtxf::tail_pack) and writes
     // nothing else here.  The buffer full: it goes on here, as without the record.  (Headline: closure + bound 19.4 -> 9.9 k cycles per
     // wavefront, the kernel 10.64 -> 9.44 ms, band_tail_kernel 0.68 ms; DESIGN 4.3.2, "where the kernel's time goes".)
     int first = -2;
@@ -2675,7 +2675,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     if (xm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)xm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[44], (uint32_t)__popcll(xm));
+        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_TAIL], (uint32_t)__popcll(xm));
         base = (uint32_t)__shfl((int)base, leader);
         const uint32_t pos = base + (uint32_t)__popcll(xm & ((1ull << tid) - 1ull));
         if (defer && pos >= tail_cap) defer = false;
@@ -2700,7 +2700,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
 
 // =============================================================================================
 // band_tail_kernel — the rest of the last phase for the tasks band_diag_kernel deferred: those whose closure must take an off-diagonal
-// piece into the generic set (7.4 % of the headline's tasks).  One lane per record, over the device's record count (counters[44]); the
+// piece into the generic set (7.4 % of the headline's tasks).  One lane per record, over the device's record count (counters[VTX_CNT_TAIL]); the
 // record goes back into band_diag_kernel's LDS layout and the same vtxf::back_rest runs on it, then the same routing (diag_route):
 // every task ends with the score, stage and lists it had when decided in its wavefront.  Launched with up to 65 536 one-wavefront
 // workgroups: a wavefront that finishes early makes room for the next (4 608 resident ones looping over the records: 0.87 ms, 0.68 ms
@@ -2788,7 +2788,7 @@ __global__ __launch_bounds__(256) void band_refine_kernel(
     const uint8_t* __restrict__ gtables, uint32_t gt_l0, int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score,
     uint32_t* __restrict__ fail_list, uint32_t* __restrict__ counters, uint32_t stats, uint32_t* __restrict__ tight_list,
     uint32_t* __restrict__ tight_pack, uint8_t* __restrict__ stage, const uint32_t* __restrict__ n_dev) {
-    // tight_list != nullptr (round 4): an undecided record still has its certificate: provisional score + tight_list (counters[15])
+    // tight_list != nullptr (round 4): an undecided record still has its certificate: provisional score + tight_list (counters[VTX_CNT_TIGHT])
     // instead of fail_list (see band_diag_kernel).  n_dev: the record count lives on the device (min(*n_dev, n_recs)).
     __shared__ uint32_t piece_mem_[4][vtxf::RM * 64];
     if (n_dev) { const uint32_t nd = *n_dev; n_recs = nd < n_recs ? nd : n_recs; }
@@ -2834,13 +2834,13 @@ __global__ __launch_bounds__(256) void band_refine_kernel(
     if (fm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)fm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[tight_list ? 15 : 12], (uint32_t)__popcll(fm));
+        if (tid == leader) base = atomicAdd(&counters[tight_list ? VTX_CNT_TIGHT : VTX_CNT_RUN_LEFT], (uint32_t)__popcll(fm));
         base = (uint32_t)__shfl((int)base, leader);
         if (fail) {
             const uint32_t pos = base + (uint32_t)__popcll(fm & ((1ull << tid) - 1ull));
             (tight_list ? tight_list : fail_list)[pos] = task;
             if (tight_list) tight_pack[pos] = pack;
-            if (stats & 0xffu) atomicAdd(&counters[32 + vtxf::W_NOT_TIGHT], 1u);
+            if (stats & 0xffu) atomicAdd(&counters[VTX_CNT_DIAG_WHY + vtxf::W_NOT_TIGHT], 1u);
         }
     }
 }
@@ -2888,13 +2888,13 @@ __global__ __launch_bounds__(256) void band_corridor_kernel(
     if (fm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)fm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[15], (uint32_t)__popcll(fm));
+        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_TIGHT], (uint32_t)__popcll(fm));
         base = (uint32_t)__shfl((int)base, leader);
         if (fail) {
             const uint32_t pos = base + (uint32_t)__popcll(fm & ((1ull << tid) - 1ull));
             tight_list[pos] = task;
             tight_pack[pos] = pack;
-            if (stats & 0xffu) atomicAdd(&counters[32 + vtxf::W_NOT_TIGHT], 1u);
+            if (stats & 0xffu) atomicAdd(&counters[VTX_CNT_DIAG_WHY + vtxf::W_NOT_TIGHT], 1u);
         }
     }
 }
@@ -3076,7 +3076,7 @@ extern "C" hipError_t vtxk_launch_band_diag(uint32_t n_tasks, uint32_t task_base
                                             hipStream_t s) {
     // max_read: the longest read of the batch (the fast kernels' records) — up to 192 bases the kernel is built with three mask words
     // tail_rec != nullptr: room for tail_cap records of band_tail_kernel (TAIL_WORDS words each, word-major), launched here behind
-    // band_diag_kernel on the same stream; counters[44] counts them.  (libvtx_dev.so: VTX_DIAG_NO_TAIL=1 — and the profiling aids of
+    // band_diag_kernel on the same stream; counters[VTX_CNT_TAIL] counts them.  (libvtx_dev.so: VTX_DIAG_NO_TAIL=1 — and the profiling aids of
     // VTX_DIAG_ABLATE — keep every task in its wavefront, the path of rounds 3 - 6.)
     if (!n_tasks) return hipSuccess;
     if (VTX_DEV_ENV("VTX_DIAG_NO_TAIL") || VTX_DEV_ENV("VTX_DIAG_ABLATE") || !tail_cap) tail_rec = nullptr;
@@ -3102,10 +3102,10 @@ extern "C" hipError_t vtxk_launch_band_diag(uint32_t n_tasks, uint32_t task_base
                            dense_mask, min_hap, tail_rec, tail_cap);                                                                      \
         if (tail_rec)                                                                                                                     \
             hipLaunchKernelGGL((band_tail_kernel<STV, AV>), dim3(std::min((tail_cap + 63u) / 64u, 65536u)), dim3(64), 0, s, tail_rec,  \
-                               tail_cap, counters + 44, ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list, \
+                               tail_cap, counters + VTX_CNT_TAIL, ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list, \
                                tight_pack, stage, dense_list, dense_mask);                                                                \
     } while (0)
-    if (tail_rec) { const hipError_t e = hipMemsetAsync(counters + 44, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
+    if (tail_rec) { const hipError_t e = hipMemsetAsync(counters + VTX_CNT_TAIL, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
     const bool three = max_read <= 192 && !force_four && vtxf::NW >= 3;
     if (max_hap <= 255 && !force_wide) { if (three) LAUNCH_DIAG(uint16_t, 3); else LAUNCH_DIAG(uint16_t, vtxf::NW); }
     else { if (three) LAUNCH_DIAG(uint32_t, 3); else LAUNCH_DIAG(uint32_t, vtxf::NW); }

@@ -44,6 +44,41 @@ static __host__ __device__ inline bool vtx_bytes_equal(const uint8_t* a, const u
     return eq;
 }
 
+// The banded stage's counter block (vtx_ctx::d_cnt): VTX_CNT_WORDS words, zeroed once per pass of the stage unless noted.  The host
+// (vtx_api.hip) and every kernel or launcher that is handed the BASE of the block index it through these names; a kernel that is
+// handed a pointer INTO the block (band_kernel / band_coop_kernel: GENERAL_HARD; the sweeps: SWEEP_HARD / SWEEP2_HARD and SWEEP_WHY;
+// band_diag2_kernel: DIAG2_LEFT, STREAMED; the full-matrix check: CHECK / CHECK2; slow_align_kernel: SLOW) counts from that word.
+enum VtxBandCnt {
+    VTX_CNT_HARD = 0,             // band_run_kernel / band_pending_kernel: entries of the hard list (zeroed per chunk)
+    VTX_CNT_OVERFLOW = 1,         // band_run_kernel: entries of the overflow list (grows over the chunks)
+    VTX_CNT_RUN_WHY = 2,          // [2, 8): band_run_kernel's overflow reasons ...
+    VTX_CNT_RUN_WHY_LAST = 7,     //   ... the last one: traceback (also where that kernel's profiling aids leave their dummy store)
+    VTX_CNT_GENERAL_HARD = 8,     // the general band kernel (side stream): hard tasks ...
+    VTX_CNT_GENERAL_AGAIN = 9,    //   ... and tasks that need a larger slab (zeroed per launch)
+    VTX_CNT_DROPPED = 10,         // band_run_kernel, statistics: hard only because pieces were dropped from a full list
+    VTX_CNT_PENDING = 11,         // band_run_kernel: pending records (zeroed per chunk)
+    VTX_CNT_RUN_LEFT = 12,        // band_diag_kernel / band_refine_kernel: tasks left for band_run_kernel (12 .. 15 zeroed per chunk)
+    VTX_CNT_DENSE = 13,           // band_diag_kernel: tasks for band_sweep_kernel
+    VTX_CNT_REFINE = 14,          // band_diag_kernel: records for band_refine_kernel / band_corridor_kernel
+    VTX_CNT_TIGHT = 15,           // band_diag_kernel and those two: tasks with a one-diagonal band
+    VTX_CNT_BLOCK = 16,           // [16, 24): band_run_kernel's block counters, one per XCD (zeroed per launch)
+    VTX_CNT_CHECK = 24,           // the full-matrix check in front of the first stage's one-diagonal bands: what it leaves
+    VTX_CNT_CHECK2 = 25,          // ... of the second stage's
+    VTX_CNT_SWEEP_HARD = 26,      // band_sweep_kernel, first pass: band slots of the slice (zeroed per slice) ...
+    VTX_CNT_SWEEP_DECLINED = 27,  //   ... and declined tasks
+    VTX_CNT_SWEEP2_HARD = 28,     // round 4's second pass (libvtx_dev.so): the same two
+    VTX_CNT_SWEEP2_DECLINED = 29,
+    VTX_CNT_DIAG2_LEFT = 30,      // band_diag2_kernel / band_stream_kernel: tasks left for the sweep ...
+    VTX_CNT_DIAG2_TIGHT = 31,     //   ... and with a one-diagonal band (both zeroed per call of the second stage)
+    VTX_CNT_DIAG_WHY = 32,        // [32, 48): band_diag_kernel's reasons, by vtxf::Why (statistics); two words past W_COUNT are in use:
+    VTX_CNT_DIAG_DUMMY = 40,      //   where band_diag_kernel's profiling aids leave their dummy store (W_NOT_TIGHT's word: results are wrong anyway)
+    VTX_CNT_TAIL = 44,            //   records band_diag_kernel leaves for band_tail_kernel (zeroed per launch)
+    VTX_CNT_STREAMED = 48,        // band_diag2_kernel: tasks handed to band_stream_kernel (zeroed per call of the second stage)
+    VTX_CNT_SWEEP_WHY = 56,       // [56, 64): band_sweep_kernel's reasons (statistics)
+    VTX_CNT_SLOW = 13,            // slow_align_kernel: tasks to retry.  Aliases VTX_CNT_DENSE: the slow path runs after the banded stage
+    VTX_CNT_WORDS = 64
+};
+
 extern "C" {
 hipError_t vtxk_launch_sw_full(int R, int GL, uint32_t n_work, const uint32_t* work, const vtx_record* records,
                                const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
