@@ -423,6 +423,21 @@ int vtx_write_mtx(vtx_ctx* ctx, const char* path, uint32_t n_rows, uint32_t n_co
  * `sum += v` gives: the "sum of 0" warning stays silent).  (A second name because vtx_write_mtx's refusal of fractions is pinned.)  */
 int vtx_write_mtx_f64(vtx_ctx* ctx, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum);
 
+/* The same text gzip-compressed ON THE DEVICE: `path` (used exactly as given) becomes a BGZF file — a series of gzip members of at
+ * most 65 280 text bytes each, then BGZF's 28-byte empty member — that zcat, Python's gzip, scanpy.read_10x_mtx and Seurat Read10X
+ * read as matrix.mtx.gz; decompressed it is byte for byte what vtx_write_mtx (real = 0) or vtx_write_mtx_f64 (real != 0) writes, the
+ * three header lines included.  One wavefront deflates one chunk (LZ77 inside the chunk, the cheapest of a stored, a fixed-Huffman and a
+ * dynamic-Huffman block; vartrix_amd/csrc/vtx_deflate_core.h), and only the compressed bytes leave the card.  The bytes are a
+ * function of the text alone: every run and the host build of the encoder give the same file.  Preconditions, which, the decline
+ * rule (VTX_E_UNSUPPORTED, nothing left at `path`) and *sum as for the two calls above.  *text_bytes (optional): the uncompressed size.
+ * Like vtx_write_mtx this call works in the buffers of the device ingest: what vtx_debug_ingest returned before it is no longer
+ * there afterwards.  Unlike it, it also takes the buffer of vtx_prefetch_file: it waits for a prefetch in flight and DROPS the
+ * prefetched bytes (a later vtx_submit_bam of that file uploads them again).  Device memory while it runs, beyond the text of a
+ * pass (T bytes): 2 T for the members' slots and their compacted copy, and 261 120 bytes of token work space per resident workgroup
+ * (at most 1 536: 401 MB) — about 1 GB at 306 MB of text; the buffers stay with the context like the ingest's.                     */
+int vtx_write_mtx_gz(vtx_ctx* ctx, const char* path, uint32_t n_rows, uint32_t n_cols, int which, int real, double* sum,
+                     uint64_t* text_bytes);
+
 /* Device pointers of the last vtx_run's triplets (same layout as vtx_coo, all
  * arrays resident in HBM) — the payload of the multi-GPU row gather.          */
 int vtx_device_coo(vtx_ctx* ctx, vtx_coo* out);

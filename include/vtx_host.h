@@ -131,6 +131,11 @@ const char* vtxh_barcode(const vtxh_pack* p, uint32_t j);
  * "row+1 col+1 value" in the given order with Rust `{}` float text.           */
 int vtxh_write_mtx(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t nnz,
                    const uint32_t* row, const uint32_t* col, const double* value);
+/* vtxh_write_mtx's text gzip-compressed, `path` used exactly as given: chunks of 65 280 text bytes, each a gzip member in BGZF
+ * framing (zlib raw deflate, level 1, on the formatter's threads), then BGZF's empty end-of-file member.  Decompressed it equals
+ * vtxh_write_mtx's file; its bytes are NOT those of the device's encoder (vtx_write_mtx_gz).                                    */
+int vtxh_write_mtx_gz(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t nnz,
+                      const uint32_t* row, const uint32_t* col, const double* value);
 int vtxh_format_f64(double v, char* buf32);
 /* the format of the pack's read arenas (vtxh_args.read_format as honoured) */
 int vtxh_read_format(const vtxh_pack* p);

@@ -71,6 +71,7 @@ const Opt kOpts[] = {
     {"bam-tag", 0, false, "CB"}, {"valid-chars", 0, false, "ATGCatgc"},
     {"devices", 0, false, "1"}, {"aligner", 0, false, "banded"}, {"prep", 0, false, "host"},
     {"stream-loci", 0, false, "auto"}, {"reads", 0, false, "nibbles"}, {"gather", 0, false, "auto"}, {"ingest", 0, false, "auto"},
+    {"gzip", 0, true, nullptr},
 };
 
 void usage() {
@@ -91,7 +92,10 @@ void usage() {
             "  --reads nibbles|bytes [nibbles]  read bases on their way to the device: two per byte as the BAM holds them (the device\n"
             "                               unpacks), or one ASCII byte per base\n"
             "  --gather auto|library [auto]  how the shards' rows meet: auto = through the library's RCCL gather when --devices > 1;\n"
-            "                               library = through it even with one device (the same bytes either way)\n");
+            "                               library = through it even with one device (the same bytes either way)\n"
+            "  --gzip                       write --out-matrix (and, in coverage mode, --ref-matrix) gzip-compressed, at exactly the paths\n"
+            "                               given (name them .mtx.gz): deflated on the GPU when the matrix is written from there\n"
+            "                               (vtx_write_mtx_gz), else by the host formatter's threads; variants and barcodes stay text\n");
 }
 
 // The shard threads of one batch meet here before each RCCL collective, carrying their status: if any shard has failed,
@@ -273,6 +277,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     const std::string out_matrix = val["out-matrix"], ref_matrix = val["ref-matrix"];
+    const bool gzip = present.count("gzip") != 0;         // the matrices as .gz, at exactly the paths given
 
     // check_inputs_exist, :493-542
     for (const char* k : {"fasta", "vcf", "bam", "cell-barcodes"})
@@ -641,9 +646,12 @@ int main(int argc, char** argv) {
         double s0 = 0;
         // (alt_frac: fractions and NaN, shortest round-trip digits per lane — vtx_write_mtx_f64; s0 is NaN when a value is, like the sum below)
         const bool real = mode == "alt_frac";
-        int rc = real ? vtx_write_mtx_f64(kept_ctx, out_matrix.c_str(), n_vars, n_bcs, 0, &s0) : vtx_write_mtx(kept_ctx, out_matrix.c_str(), n_vars, n_bcs, 0, &s0);
-        if (rc == VTX_OK && mode == "coverage") rc = vtx_write_mtx(kept_ctx, ref_matrix.c_str(), n_vars, n_bcs, 1, nullptr);    // :385-389 (see below)
-        if (rc == VTX_OK) { written = true; sum = s0; LOG_INFO("Matrix written from the device (%s)", real ? "vtx_write_mtx_f64" : "vtx_write_mtx"); }
+        // (--gzip: the same text deflated on the device, vtx_write_mtx_gz — only the compressed bytes come back)
+        int rc = gzip ? vtx_write_mtx_gz(kept_ctx, out_matrix.c_str(), n_vars, n_bcs, 0, real ? 1 : 0, &s0, nullptr)
+               : real ? vtx_write_mtx_f64(kept_ctx, out_matrix.c_str(), n_vars, n_bcs, 0, &s0) : vtx_write_mtx(kept_ctx, out_matrix.c_str(), n_vars, n_bcs, 0, &s0);
+        if (rc == VTX_OK && mode == "coverage")                                                                                // :385-389 (see below)
+            rc = gzip ? vtx_write_mtx_gz(kept_ctx, ref_matrix.c_str(), n_vars, n_bcs, 1, 0, nullptr, nullptr) : vtx_write_mtx(kept_ctx, ref_matrix.c_str(), n_vars, n_bcs, 1, nullptr);
+        if (rc == VTX_OK) { written = true; sum = s0; LOG_INFO("Matrix written from the device (%s)", gzip ? "vtx_write_mtx_gz" : real ? "vtx_write_mtx_f64" : "vtx_write_mtx"); }
         else if (rc != VTX_E_UNSUPPORTED) { printf("Vartrix error.\nError: Error writing out-matrix\nInfo: caused by %s\n", vtx_strerror(kept_ctx)); return 1; }
         else {
             vtx_coo coo{};
@@ -652,16 +660,17 @@ int main(int argc, char** argv) {
         }
     }
     if (!written) {
-    LOG_INFO("Matrix written by the host formatter (vtxh_write_mtx)");
+    LOG_INFO("Matrix written by the host formatter (%s)", gzip ? "vtxh_write_mtx_gz" : "vtxh_write_mtx");
+    const auto host_write = gzip ? vtxh_write_mtx_gz : vtxh_write_mtx;
     if (!out_row) { out_nnz = row.size(); out_row = row.data(); out_col = col.data(); out_v = v.data(); out_rv = rv.data(); }
-    if (vtxh_write_mtx(out_matrix.c_str(), n_vars, n_bcs, out_nnz, out_row, out_col, out_v) != 0) {
+    if (host_write(out_matrix.c_str(), n_vars, n_bcs, out_nnz, out_row, out_col, out_v) != 0) {
         printf("Vartrix error.\nError: Error writing out-matrix\nInfo: caused by %s\n", vtxh_last_error());
         return 1;
     }
     // :385-389 `args.is_present("ref_matrix")` is true even without the flag: clap 2.33 reports an argument with a
     // default_value (:100) as present, so coverage mode always writes the REF-count matrix (default ref_matrix.mtx)
     if (mode == "coverage") {
-        if (vtxh_write_mtx(ref_matrix.c_str(), n_vars, n_bcs, out_nnz, out_row, out_col, out_rv) != 0) {
+        if (host_write(ref_matrix.c_str(), n_vars, n_bcs, out_nnz, out_row, out_col, out_rv) != 0) {
             printf("Vartrix error.\nError: Error writing ref-matrix\nInfo: caused by %s\n", vtxh_last_error());
             return 1;
         }

@@ -728,7 +728,36 @@ int vtxh_format_f64(double v, char* buf) {
     return (int)n;
 }
 
-int vtxh_write_mtx(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t nnz, const uint32_t* row,
+}  // extern "C"
+
+namespace {
+// text -> BGZF members appended to out: chunks of 65 280 bytes, raw deflate at level 1 (zlib), the framing of vtx_deflate_core.h
+bool bgzf_append(z_stream& zs, const char* text, size_t n, std::string& out) {
+    const size_t kChunk = 65280;
+    for (size_t off = 0; off < n || (n == 0 && off == 0); off += kChunk) {
+        const size_t m = std::min(kChunk, n - off);
+        if (deflateReset(&zs) != Z_OK) return false;
+        const size_t at = out.size(), cap = deflateBound(&zs, (uLong)m);
+        out.resize(at + 18 + cap + 8);
+        zs.next_in = (Bytef*)(text + off); zs.avail_in = (uInt)m;
+        zs.next_out = (Bytef*)&out[at + 18]; zs.avail_out = (uInt)cap;
+        if (deflate(&zs, Z_FINISH) != Z_STREAM_END) return false;
+        const size_t clen = cap - zs.avail_out, bsize = 18 + clen + 8;
+        if (bsize > 65536) return false;
+        static const uint8_t kHead[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0};
+        memcpy(&out[at], kHead, 16);
+        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef*)(text + off), (uInt)m), isize = (uint32_t)m;
+        const uint16_t b1 = (uint16_t)(bsize - 1);
+        memcpy(&out[at + 16], &b1, 2);
+        memcpy(&out[at + 18 + clen], &crc, 4);
+        memcpy(&out[at + 18 + clen + 4], &isize, 4);
+        out.resize(at + bsize);
+        if (n == 0) break;
+    }
+    return true;
+}
+
+int write_mtx_impl(bool gz, const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t nnz, const uint32_t* row,
                    const uint32_t* col, const double* value) {
     const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (fd < 0) return fail(VTX_E_INVAL, "cannot open %s for writing", path);
@@ -743,23 +772,30 @@ int vtxh_write_mtx(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t 
         }
         return true;
     };
-    bool ok = write_at(head, (size_t)hl, 0);
-    uint64_t file_off = (uint64_t)hl;
+    bool ok = gz || write_at(head, (size_t)hl, 0);
+    uint64_t file_off = gz ? 0 : (uint64_t)hl;
+    // (gz: the header lines go in front of the first thread's first lines, and every thread deflates what it has formatted)
     // lines are formatted by several threads into private buffers (rounds of bounded size); every thread then writes its
     // buffer at its own offset (the copy into the page cache is most of the time of a 300 MB file)
     const uint64_t kRound = 8u << 20;
     const unsigned hw = std::thread::hardware_concurrency();
     const size_t T = nnz < (1u << 16) ? 1 : std::min<size_t>(hw ? hw : 1, 16);
-    std::vector<std::string> parts(T);
+    std::vector<std::string> parts(T), zparts(gz ? T : 0);
     std::vector<uint64_t> offs(T);
     std::vector<uint8_t> wok(T, 1);
-    for (uint64_t base = 0; base < nnz && ok; base += kRound) {
+    std::vector<z_stream> zs(gz ? T : 0);
+    for (auto& z : zs) { memset(&z, 0, sizeof z); if (deflateInit2(&z, 1, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) ok = false; }
+    bool first = true;
+    for (uint64_t base = 0; (base < nnz || (gz && first)) && ok; base += kRound) {
         const uint64_t n = std::min<uint64_t>(kRound, nnz - base);
+        const bool with_head = gz && first;
+        first = false;
         auto fmt = [&](size_t t) {
             std::string& out = parts[t];
             out.clear();
             const uint64_t k0 = base + n * t / T, k1 = base + n * (t + 1) / T;
-            out.reserve((size_t)(k1 - k0) * 16);
+            out.reserve((size_t)(k1 - k0) * 16 + 160);
+            if (with_head && t == 0) out.append(head, (size_t)hl);
             char line[96], num[40];
             for (uint64_t k = k0; k < k1; ++k) {
                 char* p = line;
@@ -769,8 +805,13 @@ int vtxh_write_mtx(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t 
                 memcpy(p, num, (size_t)m); p += m; *p++ = '\n';
                 out.append(line, (size_t)(p - line));
             }
+            if (gz) {
+                zparts[t].clear();
+                if (!out.empty() && !bgzf_append(zs[t], out.data(), out.size(), zparts[t])) wok[t] = 0;
+                out.swap(zparts[t]);
+            }
         };
-        auto put = [&](size_t t) { wok[t] = write_at(parts[t].data(), parts[t].size(), offs[t]) ? 1 : 0; };
+        auto put = [&](size_t t) { wok[t] = wok[t] && write_at(parts[t].data(), parts[t].size(), offs[t]) ? 1 : 0; };
         {
             std::vector<std::thread> th;
             for (size_t t = 1; t < T; ++t) th.emplace_back(fmt, t);
@@ -786,8 +827,26 @@ int vtxh_write_mtx(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t 
         }
         for (size_t t = 0; t < T; ++t) ok = ok && wok[t];
     }
+    for (auto& z : zs) deflateEnd(&z);
+    if (gz && ok) {
+        static const char kEof[28] = {0x1f, (char)0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, (char)0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        ok = write_at(kEof, sizeof kEof, file_off);
+    }
     ok = (close(fd) == 0) && ok;
     return ok ? VTX_OK : fail(VTX_E_INVAL, "error writing %s", path);
+}
+}  // namespace
+
+extern "C" {
+
+int vtxh_write_mtx(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t nnz, const uint32_t* row,
+                   const uint32_t* col, const double* value) {
+    return write_mtx_impl(false, path, n_rows, n_cols, nnz, row, col, value);
+}
+
+int vtxh_write_mtx_gz(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t nnz, const uint32_t* row,
+                      const uint32_t* col, const double* value) {
+    return write_mtx_impl(true, path, n_rows, n_cols, nnz, row, col, value);
 }
 
 void vtxh_free(vtxh_pack* p) { delete p; }

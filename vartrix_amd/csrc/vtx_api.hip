@@ -28,6 +28,7 @@
 
 #include "vtx_device.h"
 #include "vtx_ingest.h"
+#include "vtx_deflate_core.h"
 #include "../../include/vtx_band_semantics.h"
 
 extern "C" hipError_t vtxk_inclusive_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, void* temp,
@@ -2501,7 +2502,12 @@ int vtx_fetch_coo(vtx_ctx* c, vtx_coo* out) {
 // that formatter's domain (nothing vtx_run produces), and then the caller formats on the host (vtx_fetch_coo + vtxh_write_mtx).
 // *sum (optional) = the sum of the values (the reference's "matrix has a sum of 0" warning, :410-415), added up in no fixed order; NaN
 // when a value is NaN, as the host's `sum += v` gives.
-static int write_mtx_text(vtx_ctx* c, const char* fn, bool real, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum) {
+// vtx_write_mtx_gz (gz): the same text, header lines included, as a BGZF file — per pass the text is cut into chunks of vtxd::CHUNK bytes
+// (the chunking restarts with every pass; a pass's last chunk may be short), mtx_deflate_kernel makes a gzip member of each, the members
+// are compacted and only they are downloaded; the 28-byte empty member ends the file.  real = the values' formatter as above, and the
+// same decline rule.  *text_bytes (optional) = the uncompressed size.
+static int write_mtx_text(vtx_ctx* c, const char* fn, bool real, bool gz, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum,
+                          uint64_t* text_bytes) {
     if (!c) return VTX_E_INVAL;
     if (!path || (which != 0 && which != 1)) return fail(c, VTX_E_INVAL, "%s: bad argument", fn);
     if (!c->ran) return fail(c, VTX_E_STATE, "%s: no completed vtx_run", fn);
@@ -2524,10 +2530,13 @@ static int write_mtx_text(vtx_ctx* c, const char* fn, bool real, const char* pat
     char head[160];
     const int hl = snprintf(head, sizeof head, "%%%%MatrixMarket matrix coordinate real general\n%% written by sprs\n%u %u %llu\n", n_rows, n_cols,
                             (unsigned long long)nnz);
-    if (pwrite(fd, head, (size_t)hl, 0) != hl) return bail(fail(c, VTX_E_INVAL, "error writing %s", path));
-    uint64_t file_off = (uint64_t)hl;
-    for (uint64_t base = 0; base < nnz; base += kSlab) {
+    if (!gz && pwrite(fd, head, (size_t)hl, 0) != hl) return bail(fail(c, VTX_E_INVAL, "error writing %s", path));
+    uint64_t file_off = gz ? 0 : (uint64_t)hl, text_total = (uint64_t)hl;
+    bool first = true;
+    for (uint64_t base = 0; base < nnz || (gz && first); base += kSlab) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(kSlab, nnz - base);
+        const uint32_t pre = gz && first ? (uint32_t)hl : 0u;      // gz: the header lines lie in front of the first pass's text — every byte of the file goes through the encoder
+        first = false;
         if (hipError_t e = c->d_bam_nhit.reserve((size_t)n * sizeof(uint32_t) + 16)) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
         if (hipError_t e = c->d_bam_hscan.reserve((size_t)n * sizeof(uint32_t) + 16)) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
         if (hipError_t e = c->d_scan_tmp.reserve(vtxk_scan_temp_bytes(n))) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
@@ -2536,20 +2545,53 @@ static int write_mtx_text(vtx_ctx* c, const char* fn, bool real, const char* pat
         hipError_t e = vtxg_mtx_len(d_row + base, d_col + base, d_val + base, n, d_len, d_sum, d_flag, real ? 1 : 0, s);
         if (e == hipSuccess) e = vtxk_inclusive_scan_u32(d_len, d_end, n, c->d_scan_tmp.p, vtxk_scan_temp_bytes(n), s);
         uint32_t total = 0, flag = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&total, d_end + (n - 1), sizeof total, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && n) e = hipMemcpyAsync(&total, d_end + (n - 1), sizeof total, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return bail(fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e)));
+        const char* host_fn = gz ? "vtxh_write_mtx_gz" : "vtxh_write_mtx";
         if (flag)
-            return bail(real ? fail(c, VTX_E_UNSUPPORTED, "%s: a value outside the device formatter's domain (infinite, subnormal, |v| >= 2^53 or 0 < |v| < 2^-40): format on the host (vtx_fetch_coo + vtxh_write_mtx)", fn)
-                             : fail(c, VTX_E_UNSUPPORTED, "%s: a value that is not a non-negative integer (alt_frac): format on the host (vtx_fetch_coo + vtxh_write_mtx)", fn));
-        if ((e = c->d_bam_data.reserve((size_t)total + 64)) != hipSuccess) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
-        e = vtxg_mtx_text(d_row + base, d_col + base, d_val + base, n, d_end, c->d_bam_data.as<uint8_t>(), real ? 1 : 0, s);
+            return bail(real ? fail(c, VTX_E_UNSUPPORTED, "%s: a value outside the device formatter's domain (infinite, subnormal, |v| >= 2^53 or 0 < |v| < 2^-40): format on the host (vtx_fetch_coo + %s)", fn, host_fn)
+                             : fail(c, VTX_E_UNSUPPORTED, "%s: a value that is not a non-negative integer (alt_frac): format on the host (vtx_fetch_coo + %s)", fn, host_fn));
+        if ((e = c->d_bam_data.reserve((size_t)pre + total + 64)) != hipSuccess) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
+        if (pre) e = hipMemcpyAsync(c->d_bam_data.p, head, pre, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = vtxg_mtx_text(d_row + base, d_col + base, d_val + base, n, d_end, c->d_bam_data.as<uint8_t>() + pre, real ? 1 : 0, s);
+        text_total += total;
+        if (!gz) {
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) return bail(fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e)));
+            if (int rc = download_to_fd(c, fd, file_off, c->d_bam_data.p, total)) return bail(rc);
+            file_off += total;
+            continue;
+        }
+        const uint64_t t_bytes = (uint64_t)pre + total;             // > 0: a pass has the header lines or at least one line
+        const uint32_t n_chunks = (uint32_t)((t_bytes + vtxd::CHUNK - 1) / vtxd::CHUNK);
+        // d_bam_comp is where vtx_prefetch_file's thread copies a BAM: like every other user of it, wait for that thread and drop the
+        // prefetch before the encoder's slots take the buffer (a later vtx_submit_bam uploads its bytes again)
+        if (c->pf_thread.joinable()) c->pf_thread.join();
+        c->pf_valid = false;
+        DevBuf &slots = c->d_bam_comp, &packed = c->d_bam_rec, &sizes = c->d_bam_rsz, &ends = c->d_bam_rscan, &tok = c->d_bam_info;
+        if (e == hipSuccess) e = slots.reserve((size_t)n_chunks * vtxd::SLOT);
+        if (e == hipSuccess) e = packed.reserve((size_t)n_chunks * vtxd::SLOT);
+        if (e == hipSuccess) e = sizes.reserve((size_t)n_chunks * sizeof(uint32_t));
+        if (e == hipSuccess) e = ends.reserve((size_t)n_chunks * sizeof(uint32_t));
+        if (e == hipSuccess) e = tok.reserve((size_t)vtxg_deflate_grid(n_chunks) * vtxd::CHUNK * sizeof(uint32_t));
+        if (e == hipSuccess) e = c->d_scan_tmp.reserve(vtxk_scan_temp_bytes(std::max(n, n_chunks)));
+        if (e != hipSuccess) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
+        e = vtxg_mtx_deflate(c->d_bam_data.as<uint8_t>(), t_bytes, n_chunks, slots.as<uint8_t>(), sizes.as<uint32_t>(), tok.as<uint32_t>(), s);
+        if (e == hipSuccess) e = vtxk_inclusive_scan_u32(sizes.as<uint32_t>(), ends.as<uint32_t>(), n_chunks, c->d_scan_tmp.p, vtxk_scan_temp_bytes(n_chunks), s);
+        if (e == hipSuccess) e = vtxg_mtx_gz_compact(slots.as<uint8_t>(), sizes.as<uint32_t>(), ends.as<uint32_t>(), n_chunks, packed.as<uint8_t>(), s);
+        uint32_t gz_bytes = 0;
+        if (e == hipSuccess) e = hipMemcpyAsync(&gz_bytes, ends.as<uint32_t>() + (n_chunks - 1), sizeof gz_bytes, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return bail(fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e)));
-        if (int rc = download_to_fd(c, fd, file_off, c->d_bam_data.p, total)) return bail(rc);
-        file_off += total;
+        if (gz_bytes > (uint64_t)n_chunks * vtxd::SLOT) return bail(fail(c, VTX_E_HIP, "%s: the encoder's sizes do not fit its slots", fn));
+        if (int rc = download_to_fd(c, fd, file_off, packed.p, gz_bytes)) return bail(rc);
+        file_off += gz_bytes;
     }
+    if (gz && pwrite(fd, vtxd::EOF_BLOCK, sizeof vtxd::EOF_BLOCK, (off_t)file_off) != (ssize_t)sizeof vtxd::EOF_BLOCK)
+        return bail(fail(c, VTX_E_INVAL, "error writing %s", path));
+    if (text_bytes) *text_bytes = text_total;
     if (sum) {
         *sum = 0.0;
         if (nnz)
@@ -2560,11 +2602,15 @@ static int write_mtx_text(vtx_ctx* c, const char* fn, bool real, const char* pat
 }
 
 int vtx_write_mtx(vtx_ctx* c, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum) {
-    return write_mtx_text(c, "vtx_write_mtx", false, path, n_rows, n_cols, which, sum);
+    return write_mtx_text(c, "vtx_write_mtx", false, false, path, n_rows, n_cols, which, sum, nullptr);
 }
 
 int vtx_write_mtx_f64(vtx_ctx* c, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum) {
-    return write_mtx_text(c, "vtx_write_mtx_f64", true, path, n_rows, n_cols, which, sum);
+    return write_mtx_text(c, "vtx_write_mtx_f64", true, false, path, n_rows, n_cols, which, sum, nullptr);
+}
+
+int vtx_write_mtx_gz(vtx_ctx* c, const char* path, uint32_t n_rows, uint32_t n_cols, int which, int real, double* sum, uint64_t* text_bytes) {
+    return write_mtx_text(c, "vtx_write_mtx_gz", real != 0, true, path, n_rows, n_cols, which, sum, text_bytes);
 }
 
 int vtx_device_coo(vtx_ctx* c, vtx_coo* out) {

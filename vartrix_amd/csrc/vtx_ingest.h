@@ -49,5 +49,11 @@ hipError_t vtxg_scan(int emit, const uint8_t* data, const uint64_t* rec_upos, ui
 #define VTXG_MTX_LINE_MAX 54u      /* "4294967296 4294967296 " + vtxt::MAX_LEN + "\n" (static_assert in vtx_ingest.hip) */
 hipError_t vtxg_mtx_len(const uint32_t* row, const uint32_t* col, const double* val, uint32_t n, uint32_t* len, double* sum, uint32_t* flag, int real, hipStream_t s);
 hipError_t vtxg_mtx_text(const uint32_t* row, const uint32_t* col, const double* val, uint32_t n, const uint32_t* end, uint8_t* text, int real, hipStream_t s);
+// vtx_deflate.hip: `total` bytes of text (4-byte aligned) in n_chunks = ceil(total / vtxd::CHUNK) chunks -> one BGZF member per chunk at
+// slots + ch * vtxd::SLOT (4-byte aligned), its size in sizes[ch]; tok: vtxg_deflate_grid(n_chunks) * vtxd::CHUNK words of work space.
+// Then, with `end` the inclusive scan of the sizes, the members back to back at out (end[n_chunks - 1] bytes).
+uint32_t vtxg_deflate_grid(uint32_t n_chunks);
+hipError_t vtxg_mtx_deflate(const uint8_t* text, uint64_t total, uint32_t n_chunks, uint8_t* slots, uint32_t* sizes, uint32_t* tok, hipStream_t s);
+hipError_t vtxg_mtx_gz_compact(const uint8_t* slots, const uint32_t* sizes, const uint32_t* end, uint32_t n_chunks, uint8_t* out, hipStream_t s);
 }
 #endif

@@ -33,7 +33,8 @@ SYMBOLS = ("vtxh_pack_files", "vtxh_free", "vtxh_last_error", "vtxh_get_batch", 
            "vtxh_num_variants", "vtxh_num_barcodes", "vtxh_variant_name", "vtxh_barcode", "vtxh_write_mtx",
            "vtxh_format_f64", "vtxh_pack_files_raw", "vtxh_get_raw_batch", "vtxh_get_barcode_table", "vtxh_num_batches",
            "vtxh_get_batch_at", "vtxh_get_raw_batch_at", "vtxh_pack_files_range", "vtxh_test_inflate", "vtxh_read_format",
-           "vtxh_trim", "vtxh_plan_ingest", "vtxh_get_ingest", "vtxh_is_plan", "vtxh_get_ingest_segments", "vtxh_plan_kind")
+           "vtxh_trim", "vtxh_plan_ingest", "vtxh_get_ingest", "vtxh_is_plan", "vtxh_get_ingest_segments", "vtxh_plan_kind",
+           "vtxh_write_mtx_gz")
 METRIC_NAMES = ("num_reads", "num_low_mapq", "num_non_primary", "num_duplicates", "num_not_cell_bc",
                 "num_not_useful", "num_non_umi", "num_invalid_recs", "num_multiallelic_recs")
 
@@ -89,6 +90,8 @@ def load():
         L.vtxh_barcode.argtypes = [C.c_void_p, C.c_uint32]
         L.vtxh_write_mtx.restype = C.c_int
         L.vtxh_write_mtx.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vtxh_write_mtx_gz.restype = C.c_int
+        L.vtxh_write_mtx_gz.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vtxh_format_f64.restype = C.c_int
         L.vtxh_format_f64.argtypes = [C.c_double, C.c_char_p]
         L.vtxh_plan_ingest.restype = C.c_int
@@ -249,13 +252,22 @@ def plan_ingest(vcf, bam, fasta, cell_barcodes, padding=100, mapq=0, primary_onl
     return IngestPlan(h, L)
 
 
-def write_mtx(path, n_rows, n_cols, row, col, value):
+def _write_mtx(fn, path, n_rows, n_cols, row, col, value):
     row = np.ascontiguousarray(row, np.uint32)
     col = np.ascontiguousarray(col, np.uint32)
     value = np.ascontiguousarray(value, np.float64)
-    rc = load().vtxh_write_mtx(path.encode(), n_rows, n_cols, len(row), row.ctypes.data, col.ctypes.data, value.ctypes.data)
+    rc = fn(path.encode(), n_rows, n_cols, len(row), row.ctypes.data, col.ctypes.data, value.ctypes.data)
     if rc != 0:
         raise HostError(load().vtxh_last_error().decode())
+
+
+def write_mtx(path, n_rows, n_cols, row, col, value):
+    _write_mtx(load().vtxh_write_mtx, path, n_rows, n_cols, row, col, value)
+
+
+def write_mtx_gz(path, n_rows, n_cols, row, col, value):
+    """``write_mtx``'s text gzip-compressed into ``path`` (vtxh_write_mtx_gz: zlib level 1 per 65 280-byte chunk, BGZF framing)."""
+    _write_mtx(load().vtxh_write_mtx_gz, path, n_rows, n_cols, row, col, value)
 
 
 def format_f64(v: float) -> str:

@@ -37,7 +37,7 @@ SYMBOLS = (
     "vtx_comm_id", "vtx_comm_init", "vtx_gather_coo", "vtx_fetch_gathered", "vtx_gather_abort", "vtx_gather_plan",
     "vtx_set_debug", "vtx_fetch_stage", "vtx_debug_bands", "vtx_debug_tables", "vtx_set_read_format",
     "vtx_submit_bam", "vtx_submit_bam_segments", "vtx_debug_ingest", "vtx_debug_inflate", "vtx_comm_ranks", "vtx_write_mtx", "vtx_prefetch_file",
-    "vtx_last_crc_ms",
+    "vtx_last_crc_ms", "vtx_write_mtx_gz",
 )
 # (entry points with a digit in their name: tests/test_abi.py finds the header's declarations with [a-z_]+ and compares them with SYMBOLS,
 # so these are listed — and checked against the header and every build of the library, tests/test_abi_f64.py — on their own)
@@ -129,6 +129,8 @@ def load(variant=None):
     L.vtx_write_mtx.argtypes = [ctxp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_double)]
     L.vtx_write_mtx_f64.restype = C.c_int
     L.vtx_write_mtx_f64.argtypes = [ctxp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_double)]
+    L.vtx_write_mtx_gz.restype = C.c_int
+    L.vtx_write_mtx_gz.argtypes = [ctxp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.vtx_comm_ranks.restype = C.c_int
     L.vtx_comm_ranks.argtypes = [ctxp, C.POINTER(C.c_int)]
     L.vtx_debug_inflate.restype = C.c_int
@@ -345,6 +347,14 @@ class Context:
         fn = self._L.vtx_write_mtx_f64 if real else self._L.vtx_write_mtx
         self._check(fn(self._h, path.encode(), n_rows, n_cols, which, C.byref(s)))
         return float(s.value)
+
+    def write_mtx_gz(self, path: str, n_rows: int, n_cols: int, which: int = 0, real: bool = False):
+        """``write_mtx`` gzip-compressed on the device (vtx_write_mtx_gz): ``path``, used as given, becomes a BGZF file whose
+        decompressed bytes are ``write_mtx``'s; only the compressed bytes leave the card.  Returns (sum, text_bytes): the sum of the
+        values and the uncompressed size."""
+        s, t = C.c_double(0.0), C.c_uint64(0)
+        self._check(self._L.vtx_write_mtx_gz(self._h, path.encode(), n_rows, n_cols, which, int(bool(real)), C.byref(s), C.byref(t)))
+        return float(s.value), int(t.value)
 
     def comm_ranks(self) -> int:
         n = C.c_int(0)
