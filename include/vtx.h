@@ -438,6 +438,44 @@ int vtx_write_mtx_f64(vtx_ctx* ctx, const char* path, uint32_t n_rows, uint32_t 
 int vtx_write_mtx_gz(vtx_ctx* ctx, const char* path, uint32_t n_rows, uint32_t n_cols, int which, int real, double* sum,
                      uint64_t* text_bytes);
 
+/* ---- the matrix in PARTS: for callers that run several batches (streamed ranges of loci, batches of one pack) ----------------------
+ * The three calls above write a whole file from ONE vtx_run.  A caller that feeds the loci in several runs — rows ascending from run
+ * to run, as vtxh_pack_files_range and the batches of a pack give them — takes a PART after each run instead and joins the parts at
+ * the end; nothing stays on the device between the runs, and the context may be destroyed or reused as soon as the call returns.
+ *   vtx_mtx_part       the last vtx_run's triplets as a finished piece of the file in host memory: the lines "row+1 col+1 value" and
+ *                      nothing else (gz = 0), or those lines as BGZF members (gz != 0: chunks of at most 65 280 text bytes counted from
+ *                      the part's first byte, deflated on the device; no header lines, no end-of-file member).  which and real as for
+ *                      vtx_write_mtx (real = 0) / vtx_write_mtx_f64 (real != 0), and the same decline rule: VTX_E_UNSUPPORTED, *out
+ *                      zeroed, the context usable — format that run on the host (vtx_fetch_coo + vtxh_mtx_part of vtx_host.h; such a
+ *                      part joins like any other).  VTX_E_STATE before a completed vtx_run, VTX_E_INVAL for a bad argument.  A run
+ *                      without triplets gives nnz = 0, n_bytes = 0, bytes = NULL (no member).  The engine is vtx_write_mtx's: the
+ *                      text is the same bytes, the call is synchronous on the context's stream and, like vtx_write_mtx, works in the
+ *                      buffers of the device ingest (what vtx_debug_ingest returned before is gone).  It waits for a
+ *                      vtx_prefetch_file in flight (the part comes back through the copy workers the prefetch uses); with gz it
+ *                      also drops the prefetched bytes, like vtx_write_mtx_gz.  `bytes` belongs to the library: vtx_mtx_part_free.
+ *   vtx_mtx_part_free  releases `bytes` and zeroes the struct; nothing to do on a zeroed struct.
+ *   vtx_mtx_join       no context, no device: writes `path` = the three header lines with nnz = the sum of the parts' nnz, then the
+ *                      parts in the order given.  gz != 0: the header lines are a BGZF member of their own (a stored block) in front,
+ *                      BGZF's 28-byte empty member ends the file.  Reads only bytes, n_bytes, text_bytes, nnz and gz of a part.  A
+ *                      part whose gz differs from the argument: VTX_E_INVAL.  On any error nothing is left at `path`; the message is
+ *                      vtx_strerror(NULL).  No parts, or only empty ones: a valid file with the header alone.  *text_bytes
+ *                      (optional): the uncompressed size of the file.
+ * Joined, the plain file is byte for byte what vtx_write_mtx / vtx_write_mtx_f64 / vtxh_write_mtx write for all the triplets at once;
+ * the gz file decompresses to it (its members are cut differently from vtx_write_mtx_gz's: per part, the header apart).             */
+struct vtx_mtx_part {
+    uint8_t* bytes;      /* the part: text lines, or BGZF members (no header lines, no EOF member) */
+    uint64_t n_bytes;
+    uint64_t text_bytes; /* uncompressed size (== n_bytes when gz == 0) */
+    uint64_t nnz;        /* lines in this part */
+    double   sum;        /* as vtx_write_mtx's *sum: NaN when a value is NaN */
+    uint32_t gz;         /* 0 text, 1 BGZF members */
+    uint32_t reserved;
+};   /* (a struct tag only, no typedef: the call that fills it has the same name, so the type is always written `struct vtx_mtx_part`) */
+int vtx_mtx_part(vtx_ctx* ctx, int which, int real, int gz, struct vtx_mtx_part* out);
+void vtx_mtx_part_free(struct vtx_mtx_part* part);
+int vtx_mtx_join(const char* path, uint32_t n_rows, uint32_t n_cols, int gz, const struct vtx_mtx_part* parts, uint32_t n_parts,
+                 uint64_t* text_bytes);
+
 /* Device pointers of the last vtx_run's triplets (same layout as vtx_coo, all
  * arrays resident in HBM) — the payload of the multi-GPU row gather.          */
 int vtx_device_coo(vtx_ctx* ctx, vtx_coo* out);
@@ -523,8 +561,8 @@ const char* vtx_status_name(int status);
 
 /* sizeof() of {vtx_config, vtx_locus, vtx_record, vtx_batch, vtx_coo,
  * vtx_timing, vtx_raw_record, vtx_raw_batch, vtx_raw_stats, vtx_bgzf_block, vtx_bam_interval,
- * vtx_bam_ingest, vtx_ingest_stats, vtx_bam_segment, vtx_bam_segments} as compiled into the library,
- * for binding self-checks.  Writes min(n, 15) entries; returns VTX_ABI_VERSION.             */
+ * vtx_bam_ingest, vtx_ingest_stats, vtx_bam_segment, vtx_bam_segments, vtx_mtx_part} as compiled into the library,
+ * for binding self-checks.  Writes min(n, 16) entries; returns VTX_ABI_VERSION.             */
 int vtx_abi_sizes(uint32_t* out, uint32_t n);
 
 #ifdef __cplusplus

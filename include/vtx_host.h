@@ -136,6 +136,13 @@ int vtxh_write_mtx(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t 
  * vtxh_write_mtx's file; its bytes are NOT those of the device's encoder (vtx_write_mtx_gz).                                    */
 int vtxh_write_mtx_gz(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t nnz,
                       const uint32_t* row, const uint32_t* col, const double* value);
+/* One PART of a matrix written in several runs (vtx_mtx_part / vtx_mtx_join in vtx.h) formatted on the host: exactly the lines
+ * vtxh_write_mtx writes for these triplets (gz = 0), or vtxh_write_mtx_gz's members for that text (gz != 0) — no header lines, no
+ * end-of-file member; out->sum = the sum of the values (NaN when one is).  For the run whose vtx_mtx_part declined: vtx_fetch_coo,
+ * then this; vtx_mtx_join takes the part like a device-made one.  out->bytes is released by vtxh_mtx_part_free (no-op on a zeroed
+ * struct).  The two writers above and this call share one formatter.                                                            */
+int vtxh_mtx_part(uint64_t nnz, const uint32_t* row, const uint32_t* col, const double* value, int gz, struct vtx_mtx_part* out);
+void vtxh_mtx_part_free(struct vtx_mtx_part* part);
 int vtxh_format_f64(double v, char* buf32);
 /* the format of the pack's read arenas (vtxh_args.read_format as honoured) */
 int vtxh_read_format(const vtxh_pack* p);

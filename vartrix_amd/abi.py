@@ -216,6 +216,27 @@ class VtxIngestStats(C.Structure):
                [("raw", VtxRawStats)] + [(n, C.c_float) for n in ("h2d_ms", "inflate_ms", "index_ms", "filter_ms", "prefetch_ms", "prefetch_wait_ms")]
 
 
+class VtxMtxPart(C.Structure):
+    _fields_ = [("bytes", C.c_void_p), ("n_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("nnz", C.c_uint64), ("sum", C.c_double),
+                ("gz", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MtxPart:
+    """One part of a matrix written in several runs (vtx_mtx_part / vtxh_mtx_part), copied out of the library: ``bytes`` are the
+    Matrix-Market lines of one run, or their BGZF members (``gz``); ``text_bytes`` the uncompressed size, ``nnz`` the lines, ``sum`` the
+    sum of the values (NaN when one is).  ``lib.mtx_join`` writes a list of them behind a header."""
+
+    def __init__(self, data: bytes = b"", text_bytes: int = 0, nnz: int = 0, sum: float = 0.0, gz: bool = False):
+        self.bytes, self.text_bytes, self.nnz, self.sum, self.gz = data, int(text_bytes), int(nnz), float(sum), bool(gz)
+
+    @classmethod
+    def from_struct(cls, st: "VtxMtxPart"):
+        return cls(C.string_at(st.bytes, st.n_bytes) if st.n_bytes else b"", st.text_bytes, st.nnz, st.sum, bool(st.gz))
+
+    def __repr__(self):
+        return "MtxPart(%d bytes, text_bytes=%d, nnz=%d, sum=%r, gz=%r)" % (len(self.bytes), self.text_bytes, self.nnz, self.sum, self.gz)
+
+
 def pack_nibbles(arena: np.ndarray) -> np.ndarray:
     """One ASCII byte per base -> two bases per byte, high nibble first, the BAM's code "=ACMGRSVTWYHKDBN" (SAM spec 4.2.3)."""
     code = np.full(256, 255, np.uint8)

@@ -95,7 +95,8 @@ void usage() {
             "                               library = through it even with one device (the same bytes either way)\n"
             "  --gzip                       write --out-matrix (and, in coverage mode, --ref-matrix) gzip-compressed, at exactly the paths\n"
             "                               given (name them .mtx.gz): deflated on the GPU when the matrix is written from there\n"
-            "                               (vtx_write_mtx_gz), else by the host formatter's threads; variants and barcodes stay text\n");
+            "                               (vtx_write_mtx_gz; in parts over several ranges or batches: vtx_mtx_part), else by the host\n"
+            "                               formatter's threads; variants and barcodes stay text\n");
 }
 
 // The shard threads of one batch meet here before each RCCL collective, carrying their status: if any shard has failed,
@@ -115,6 +116,10 @@ struct ShardGate {
         return verdict;
     }
 };
+
+typedef struct vtx_mtx_part MtxPart;           // (the struct shares its name with the call that fills it)
+// what a run's parts look like — constants of the run: the values' formatter (alt_frac), --gzip, and coverage mode's second matrix
+struct PartOpts { bool real = false, gz = false, coverage = false; };
 
 struct Shard {
     std::vector<vtx_locus> loci;                 // rec_begin rebased to the shard's first record
@@ -138,6 +143,11 @@ struct Shard {
     vtx_ctx* ctx_pre = nullptr;                 // a context created at launch (its vtx_prefetch_file is bringing the BAM's bytes): used instead of vtx_create
     vtx_ctx* ctx_kept = nullptr;                // keep_ctx with defer_fetch: the triplets stay on the device — vtx_write_mtx / vtx_write_mtx_f64 formats them there
     bool defer_fetch = false;
+    // one device, several ranges and / or batches: the run's triplets leave the context as a finished PART of the file (vtx_mtx_part; two in
+    // coverage mode: the matrix and the ref matrix), joined behind a header at the end — the four vectors above stay empty
+    bool want_parts = false;
+    MtxPart part[2] = {};
+    bool part_host = false;                     // vtx_mtx_part declined: this run's triplets were fetched and vtxh_mtx_part formatted them
     std::string err;
     int rc = 0;
     double t_create = 0, t_submit = 0, t_run = 0, t_fetch = 0;
@@ -159,7 +169,7 @@ double since(std::chrono::steady_clock::time_point t0) {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-void run_shard(Shard* s, vtx_config cfg) {
+void run_shard(Shard* s, vtx_config cfg, PartOpts po) {
     vtx_ctx* ctx = s->ctx_pre;
     double t0 = now_s();
     if (!ctx) {
@@ -218,6 +228,25 @@ void run_shard(Shard* s, vtx_config cfg) {
         if (s->rank != 0) { s->t_fetch = now_s() - t0; vtx_destroy(ctx); return; }
         if ((s->rc = vtx_fetch_gathered(ctx, &coo))) { s->err = vtx_strerror(ctx); vtx_destroy(ctx); return; }
     } else if (s->keep_ctx && s->defer_fetch) { s->ctx_kept = ctx; return; }
+    else if (s->want_parts) {
+        const int n_which = po.coverage ? 2 : 1;
+        for (int w = 0; w < n_which && !s->rc; ++w) s->rc = vtx_mtx_part(ctx, w, po.real ? 1 : 0, po.gz ? 1 : 0, &s->part[w]);
+        if (s->rc == VTX_E_UNSUPPORTED) {
+            // declined (a value outside the device formatter's domain): this one run is formatted on the host, the others stay device-made
+            for (int w = 0; w < n_which; ++w) vtx_mtx_part_free(&s->part[w]);
+            s->part_host = true;
+            if ((s->rc = vtx_fetch_coo(ctx, &coo))) s->err = vtx_strerror(ctx);
+            for (int w = 0; w < n_which && !s->rc; ++w)
+                if ((s->rc = vtxh_mtx_part(coo.nnz, coo.row, coo.col, w ? coo.ref_value : coo.value, po.gz ? 1 : 0, &s->part[w]))) s->err = vtxh_last_error();
+            if (s->rc) for (int w = 0; w < n_which; ++w) vtxh_mtx_part_free(&s->part[w]);
+        } else if (s->rc) {
+            s->err = vtx_strerror(ctx);
+            for (int w = 0; w < n_which; ++w) vtx_mtx_part_free(&s->part[w]);
+        }
+        s->t_fetch = now_s() - t0;
+        vtx_destroy(ctx);
+        return;
+    }
     else if ((s->rc = vtx_fetch_coo(ctx, &coo))) { s->err = vtx_strerror(ctx); vtx_destroy(ctx); return; }
     if (s->keep_ctx) { s->kept = coo; s->ctx_kept = ctx; s->t_fetch = now_s() - t0; return; }
     s->row.assign(coo.row, coo.row + coo.nnz);
@@ -455,6 +484,19 @@ int main(int argc, char** argv) {
     const double *out_v = nullptr, *out_rv = nullptr;
     std::vector<double> v, rv;
     vtx_ctx* kept_ctx = nullptr;                           // one range, one batch, one device: the matrix is written from the device (vtx_write_mtx, alt_frac: vtx_write_mtx_f64)
+    // one device, more than one range and / or batch: the parts of the file, in row order (run_shard: vtx_mtx_part), until vtx_mtx_join
+    const bool parts_ok = ndev == 1 && val["gather"] != "library";
+    PartOpts part_opts;
+    part_opts.real = mode == "alt_frac"; part_opts.gz = gzip; part_opts.coverage = mode == "coverage";
+    struct MtxParts {
+        std::vector<MtxPart> mat, ref;
+        std::vector<uint8_t> host;
+        void take(Shard& s) { mat.push_back(s.part[0]); ref.push_back(s.part[1]); host.push_back(s.part_host ? 1 : 0); s.part[0] = s.part[1] = MtxPart{}; }
+        ~MtxParts() {
+            for (size_t i = 0; i < mat.size(); ++i)
+                for (MtxPart* p : {&mat[i], &ref[i]}) { if (host[i]) vtxh_mtx_part_free(p); else vtx_mtx_part_free(p); }
+        }
+    } mparts;
     vtx_raw_stats raw_total{};
     vtxh_metrics m{};
     double t_device = 0;
@@ -475,6 +517,7 @@ int main(int argc, char** argv) {
         s.ingest = &g; s.bc_bytes = bc_bytes; s.bc_offsets = bc_offsets; s.n_bcs = bc_n; s.raw = true;
         s.keep_ctx = range_idx == 0 && cur.last;
         s.defer_fetch = s.keep_ctx;
+        s.want_parts = parts_ok && !s.keep_ctx;
         if (early.joinable()) early.join();
         if (early_ctx) { s.ctx_pre = early_ctx; early_ctx = nullptr; }
         const auto t_shard = std::chrono::steady_clock::now();
@@ -484,7 +527,7 @@ int main(int argc, char** argv) {
         else
         LOG_INFO("Plan of range %u: %.3f s (%u loci, %u BGZF blocks, %u record-start seeds from the .bai); ingest on the device", range_idx, cur.secs,
                  g.n_loci, g.n_blocks, g.n_seeds);
-        run_shard(&s, cfg);
+        run_shard(&s, cfg, part_opts);
         if (s.rc && s.declined && !must_device_ingest) {
             LOG_INFO("Range %u: the device declined (%s) — packing on the host", range_idx, s.err.c_str());
             vtxh_pack* hp = nullptr;
@@ -507,6 +550,7 @@ int main(int argc, char** argv) {
             LOG_INFO("  device preparation: %llu reads kept, %.3f ms, %u hash round(s)", (unsigned long long)s.stats.kept, (double)s.stats.prep_ms, s.stats.hash_rounds);
             if (s.keep_ctx && s.ctx_kept && s.defer_fetch) kept_ctx = s.ctx_kept;
             else if (s.keep_ctx) { out_nnz = s.kept.nnz; out_row = s.kept.row; out_col = s.kept.col; out_v = s.kept.value; out_rv = s.kept.ref_value; }
+            if (s.want_parts) mparts.take(s);
             row.insert(row.end(), s.row.begin(), s.row.end());
             col.insert(col.end(), s.col.begin(), s.col.end());
             v.insert(v.end(), s.val.begin(), s.val.end());
@@ -555,6 +599,7 @@ int main(int argc, char** argv) {
                 s.n_records = r1 - r0;
                 s.keep_ctx = n_batches == 1 && ndev == 1 && range_idx == 0 && cur.last;
                 s.defer_fetch = s.keep_ctx && val["gather"] != "library";
+                s.want_parts = parts_ok && !s.keep_ctx;
                 if (raw) {
                     s.raw = true;
                     s.raw_records = full_raw.records + r0;
@@ -585,7 +630,7 @@ int main(int argc, char** argv) {
         for (int d = 0; d < ndev; ++d) {
             vtx_config c = cfg;
             c.device = d;
-            th.emplace_back(run_shard, &shards[(size_t)d], c);
+            th.emplace_back(run_shard, &shards[(size_t)d], c, part_opts);
         }
         for (auto& t : th) t.join();
         t_device += since(t_shards);                      // (the shards' work only: not the packer, not the release of a range's reads)
@@ -597,6 +642,7 @@ int main(int argc, char** argv) {
                      s.raw ? " + device preparation" : "", s.t_submit, s.t_run, s.t_fetch);
             if (s.keep_ctx && s.ctx_kept && s.defer_fetch) kept_ctx = s.ctx_kept;
             else if (s.keep_ctx) { out_nnz = s.kept.nnz; out_row = s.kept.row; out_col = s.kept.col; out_v = s.kept.value; out_rv = s.kept.ref_value; }
+            if (s.want_parts) mparts.take(s);
             row.insert(row.end(), s.row.begin(), s.row.end());       // shard (= row) order: the triplet order of the merge loop :320-348
             col.insert(col.end(), s.col.begin(), s.col.end());
             v.insert(v.end(), s.val.begin(), s.val.end());
@@ -658,6 +704,24 @@ int main(int argc, char** argv) {
             if (vtx_fetch_coo(kept_ctx, &coo)) { printf("Vartrix error.\nError: %s\n", vtx_strerror(kept_ctx)); return 1; }
             out_nnz = coo.nnz; out_row = coo.row; out_col = coo.col; out_v = coo.value; out_rv = coo.ref_value;
         }
+    }
+    if (!mparts.mat.empty()) {
+        // the parts of the file, made run by run, behind a header: nothing is formatted here
+        const uint32_t n_parts = (uint32_t)mparts.mat.size();
+        uint32_t n_host = 0;
+        for (uint32_t i = 0; i < n_parts; ++i) { sum += mparts.mat[i].sum; n_host += mparts.host[i]; }
+        if (vtx_mtx_join(out_matrix.c_str(), n_vars, n_bcs, gzip ? 1 : 0, mparts.mat.data(), n_parts, nullptr) != VTX_OK) {
+            printf("Vartrix error.\nError: Error writing out-matrix\nInfo: caused by %s\n", vtx_strerror(nullptr));
+            return 1;
+        }
+        if (mode == "coverage" && vtx_mtx_join(ref_matrix.c_str(), n_vars, n_bcs, gzip ? 1 : 0, mparts.ref.data(), n_parts, nullptr) != VTX_OK) {      // :385-389 (see below)
+            unlink(out_matrix.c_str());
+            printf("Vartrix error.\nError: Error writing ref-matrix\nInfo: caused by %s\n", vtx_strerror(nullptr));
+            return 1;
+        }
+        written = true;
+        if (n_host) LOG_INFO("Matrix written from the device in %u parts (vtx_mtx_part), %u formatted on the host", n_parts, n_host);
+        else LOG_INFO("Matrix written from the device in %u parts (vtx_mtx_part)", n_parts);
     }
     if (!written) {
     LOG_INFO("Matrix written by the host formatter (%s)", gzip ? "vtxh_write_mtx_gz" : "vtxh_write_mtx");

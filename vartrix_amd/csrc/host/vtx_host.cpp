@@ -757,6 +757,68 @@ bool bgzf_append(z_stream& zs, const char* text, size_t n, std::string& out) {
     return true;
 }
 
+// The formatter, once: the lines "row+1 col+1 value" of the triplets, formatted by several threads into private buffers in rounds of
+// bounded size; with gz every thread deflates what it has formatted (bgzf_append).  head / hl: text in front of the first thread's
+// first lines (the gz FILE's header lines: they share its first member; then there is a round even without a triplet).  After each
+// round `sink` takes the threads' buffers, in order; *text_bytes = the uncompressed bytes handed over, *sum = the sum of the values.
+template <class Sink>
+bool mtx_rounds(bool gz, const char* head, size_t hl, uint64_t nnz, const uint32_t* row, const uint32_t* col, const double* value,
+                Sink&& sink, uint64_t* text_bytes, double* sum) {
+    const uint64_t kRound = 8u << 20;
+    const unsigned hw = std::thread::hardware_concurrency();
+    const size_t T = nnz < (1u << 16) ? 1 : std::min<size_t>(hw ? hw : 1, 16);
+    std::vector<std::string> parts(T), zparts(gz ? T : 0);
+    std::vector<uint64_t> tbytes(T, 0);
+    std::vector<double> tsum(T, 0.0);
+    std::vector<uint8_t> wok(T, 1);
+    std::vector<z_stream> zs(gz ? T : 0);
+    bool ok = true;
+    for (auto& z : zs) { memset(&z, 0, sizeof z); if (deflateInit2(&z, 1, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) ok = false; }
+    bool first = true;
+    for (uint64_t base = 0; (base < nnz || (hl && first)) && ok; base += kRound) {
+        const uint64_t n = std::min<uint64_t>(kRound, nnz - base);
+        const bool with_head = hl && first;
+        first = false;
+        auto fmt = [&](size_t t) {
+            std::string& out = parts[t];
+            out.clear();
+            const uint64_t k0 = base + n * t / T, k1 = base + n * (t + 1) / T;
+            out.reserve((size_t)(k1 - k0) * 16 + 160);
+            if (with_head && t == 0) out.append(head, hl);
+            char line[96], num[40];
+            double acc = 0.0;
+            for (uint64_t k = k0; k < k1; ++k) {
+                char* p = line;
+                p = std::to_chars(p, p + 12, row[k] + 1u).ptr; *p++ = ' ';
+                p = std::to_chars(p, p + 12, col[k] + 1u).ptr; *p++ = ' ';
+                const int m = vtxh_format_f64(value[k], num);
+                memcpy(p, num, (size_t)m); p += m; *p++ = '\n';
+                out.append(line, (size_t)(p - line));
+                acc += value[k];
+            }
+            tsum[t] += acc;
+            tbytes[t] += out.size();
+            if (gz) {
+                zparts[t].clear();
+                if (!out.empty() && !bgzf_append(zs[t], out.data(), out.size(), zparts[t])) wok[t] = 0;
+                out.swap(zparts[t]);
+            }
+        };
+        {
+            std::vector<std::thread> th;
+            for (size_t t = 1; t < T; ++t) th.emplace_back(fmt, t);
+            fmt(0);
+            for (auto& t : th) t.join();
+        }
+        for (size_t t = 0; t < T; ++t) ok = ok && wok[t];
+        ok = ok && sink(parts);
+    }
+    for (auto& z : zs) deflateEnd(&z);
+    *text_bytes = 0; *sum = 0.0;
+    for (size_t t = 0; t < T; ++t) { *text_bytes += tbytes[t]; *sum += tsum[t]; }
+    return ok;
+}
+
 int write_mtx_impl(bool gz, const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t nnz, const uint32_t* row,
                    const uint32_t* col, const double* value) {
     const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
@@ -775,59 +837,22 @@ int write_mtx_impl(bool gz, const char* path, uint32_t n_rows, uint32_t n_cols, 
     bool ok = gz || write_at(head, (size_t)hl, 0);
     uint64_t file_off = gz ? 0 : (uint64_t)hl;
     // (gz: the header lines go in front of the first thread's first lines, and every thread deflates what it has formatted)
-    // lines are formatted by several threads into private buffers (rounds of bounded size); every thread then writes its
-    // buffer at its own offset (the copy into the page cache is most of the time of a 300 MB file)
-    const uint64_t kRound = 8u << 20;
-    const unsigned hw = std::thread::hardware_concurrency();
-    const size_t T = nnz < (1u << 16) ? 1 : std::min<size_t>(hw ? hw : 1, 16);
-    std::vector<std::string> parts(T), zparts(gz ? T : 0);
-    std::vector<uint64_t> offs(T);
-    std::vector<uint8_t> wok(T, 1);
-    std::vector<z_stream> zs(gz ? T : 0);
-    for (auto& z : zs) { memset(&z, 0, sizeof z); if (deflateInit2(&z, 1, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) ok = false; }
-    bool first = true;
-    for (uint64_t base = 0; (base < nnz || (gz && first)) && ok; base += kRound) {
-        const uint64_t n = std::min<uint64_t>(kRound, nnz - base);
-        const bool with_head = gz && first;
-        first = false;
-        auto fmt = [&](size_t t) {
-            std::string& out = parts[t];
-            out.clear();
-            const uint64_t k0 = base + n * t / T, k1 = base + n * (t + 1) / T;
-            out.reserve((size_t)(k1 - k0) * 16 + 160);
-            if (with_head && t == 0) out.append(head, (size_t)hl);
-            char line[96], num[40];
-            for (uint64_t k = k0; k < k1; ++k) {
-                char* p = line;
-                p = std::to_chars(p, p + 12, row[k] + 1u).ptr; *p++ = ' ';
-                p = std::to_chars(p, p + 12, col[k] + 1u).ptr; *p++ = ' ';
-                const int m = vtxh_format_f64(value[k], num);
-                memcpy(p, num, (size_t)m); p += m; *p++ = '\n';
-                out.append(line, (size_t)(p - line));
-            }
-            if (gz) {
-                zparts[t].clear();
-                if (!out.empty() && !bgzf_append(zs[t], out.data(), out.size(), zparts[t])) wok[t] = 0;
-                out.swap(zparts[t]);
-            }
-        };
-        auto put = [&](size_t t) { wok[t] = wok[t] && write_at(parts[t].data(), parts[t].size(), offs[t]) ? 1 : 0; };
-        {
-            std::vector<std::thread> th;
-            for (size_t t = 1; t < T; ++t) th.emplace_back(fmt, t);
-            fmt(0);
-            for (auto& t : th) t.join();
-        }
+    // every thread writes its buffer at its own offset (the copy into the page cache is most of the time of a 300 MB file)
+    auto to_file = [&](std::vector<std::string>& parts) {
+        const size_t T = parts.size();
+        std::vector<uint64_t> offs(T);
+        std::vector<uint8_t> wok(T, 1);
         for (size_t t = 0; t < T; ++t) { offs[t] = file_off; file_off += parts[t].size(); }
-        {
-            std::vector<std::thread> th;
-            for (size_t t = 1; t < T; ++t) th.emplace_back(put, t);
-            put(0);
-            for (auto& t : th) t.join();
-        }
-        for (size_t t = 0; t < T; ++t) ok = ok && wok[t];
-    }
-    for (auto& z : zs) deflateEnd(&z);
+        auto put = [&](size_t t) { wok[t] = write_at(parts[t].data(), parts[t].size(), offs[t]) ? 1 : 0; };
+        std::vector<std::thread> th;
+        for (size_t t = 1; t < T; ++t) th.emplace_back(put, t);
+        put(0);
+        for (auto& t : th) t.join();
+        return std::all_of(wok.begin(), wok.end(), [](uint8_t w) { return w != 0; });
+    };
+    uint64_t text_bytes = 0;
+    double sum = 0.0;
+    ok = ok && mtx_rounds(gz, head, gz ? (size_t)hl : 0, nnz, row, col, value, to_file, &text_bytes, &sum);
     if (gz && ok) {
         static const char kEof[28] = {0x1f, (char)0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, (char)0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         ok = write_at(kEof, sizeof kEof, file_off);
@@ -847,6 +872,40 @@ int vtxh_write_mtx(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t 
 int vtxh_write_mtx_gz(const char* path, uint32_t n_rows, uint32_t n_cols, uint64_t nnz, const uint32_t* row,
                       const uint32_t* col, const double* value) {
     return write_mtx_impl(true, path, n_rows, n_cols, nnz, row, col, value);
+}
+
+int vtxh_mtx_part(uint64_t nnz, const uint32_t* row, const uint32_t* col, const double* value, int gz, struct vtx_mtx_part* out) {
+    if (!out) return fail(VTX_E_INVAL, "vtxh_mtx_part: null output");
+    memset(out, 0, sizeof *out);
+    if (nnz && (!row || !col || !value)) return fail(VTX_E_INVAL, "vtxh_mtx_part: null array");
+    uint8_t* buf = nullptr;
+    uint64_t len = 0, cap = 0;
+    auto to_buffer = [&](std::vector<std::string>& parts) {
+        uint64_t add = 0;
+        for (const std::string& s : parts) add += s.size();
+        if (len + add > cap) {
+            const uint64_t want = std::max<uint64_t>(len + add, cap + cap / 2);
+            uint8_t* p = (uint8_t*)realloc(buf, (size_t)want);
+            if (!p) return false;
+            buf = p; cap = want;
+        }
+        for (const std::string& s : parts) { memcpy(buf + len, s.data(), s.size()); len += s.size(); }
+        return true;
+    };
+    uint64_t text_bytes = 0;
+    double sum = 0.0;
+    if (!mtx_rounds(gz != 0, nullptr, 0, nnz, row, col, value, to_buffer, &text_bytes, &sum)) {
+        free(buf);
+        return fail(VTX_E_NOMEM, "vtxh_mtx_part: out of memory, or the encoder failed");
+    }
+    out->bytes = buf; out->n_bytes = len; out->text_bytes = text_bytes; out->nnz = nnz; out->sum = sum; out->gz = gz ? 1u : 0u;
+    return VTX_OK;
+}
+
+void vtxh_mtx_part_free(struct vtx_mtx_part* part) {
+    if (!part) return;
+    free(part->bytes);
+    memset(part, 0, sizeof *part);
 }
 
 void vtxh_free(vtxh_pack* p) { delete p; }

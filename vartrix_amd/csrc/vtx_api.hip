@@ -29,6 +29,7 @@
 #include "vtx_device.h"
 #include "vtx_ingest.h"
 #include "vtx_deflate_core.h"
+#include "vtx_mtx_join.h"
 #include "../../include/vtx_band_semantics.h"
 
 extern "C" hipError_t vtxk_inclusive_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, void* temp,
@@ -674,12 +675,13 @@ void vtx_config_default(vtx_config* cfg) {
 }
 
 int vtx_abi_sizes(uint32_t* out, uint32_t n) {
-    const uint32_t s[15] = {(uint32_t)sizeof(vtx_config), (uint32_t)sizeof(vtx_locus), (uint32_t)sizeof(vtx_record),
+    const uint32_t s[16] = {(uint32_t)sizeof(vtx_config), (uint32_t)sizeof(vtx_locus), (uint32_t)sizeof(vtx_record),
                             (uint32_t)sizeof(vtx_batch), (uint32_t)sizeof(vtx_coo), (uint32_t)sizeof(vtx_timing),
                             (uint32_t)sizeof(vtx_raw_record), (uint32_t)sizeof(vtx_raw_batch), (uint32_t)sizeof(vtx_raw_stats),
                             (uint32_t)sizeof(vtx_bgzf_block), (uint32_t)sizeof(vtx_bam_interval), (uint32_t)sizeof(vtx_bam_ingest),
-                            (uint32_t)sizeof(vtx_ingest_stats), (uint32_t)sizeof(vtx_bam_segment), (uint32_t)sizeof(vtx_bam_segments)};
-    for (uint32_t i = 0; i < n && i < 15; ++i) out[i] = s[i];
+                            (uint32_t)sizeof(vtx_ingest_stats), (uint32_t)sizeof(vtx_bam_segment), (uint32_t)sizeof(vtx_bam_segments),
+                            (uint32_t)sizeof(struct vtx_mtx_part)};
+    for (uint32_t i = 0; i < n && i < 16; ++i) out[i] = s[i];
     return VTX_ABI_VERSION;
 }
 
@@ -2506,12 +2508,38 @@ int vtx_fetch_coo(vtx_ctx* c, vtx_coo* out) {
 // (the chunking restarts with every pass; a pass's last chunk may be short), mtx_deflate_kernel makes a gzip member of each, the members
 // are compacted and only they are downloaded; the 28-byte empty member ends the file.  real = the values' formatter as above, and the
 // same decline rule.  *text_bytes (optional) = the uncompressed size.
-static int write_mtx_text(vtx_ctx* c, const char* fn, bool real, bool gz, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum,
-                          uint64_t* text_bytes) {
-    if (!c) return VTX_E_INVAL;
-    if (!path || (which != 0 && which != 1)) return fail(c, VTX_E_INVAL, "%s: bad argument", fn);
-    if (!c->ran) return fail(c, VTX_E_STATE, "%s: no completed vtx_run", fn);
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
+// The slab loop is ONE engine with two sinks: a file (vtx_write_mtx*: the copy workers pwrite their pinned buffers) or a host buffer
+// (vtx_mtx_part: the same bytes through download(), without header lines and without the end-of-file member).
+struct MtxSink {
+    int fd = -1;                 // >= 0: the file, written at file_off
+    uint64_t file_off = 0;
+    uint8_t* buf = nullptr;      // fd < 0: malloc'ed, `len` bytes used of `cap`
+    uint64_t len = 0, cap = 0;
+};
+
+static int mtx_sink_put(vtx_ctx* c, const char* fn, MtxSink& k, const void* d_src, size_t bytes) {
+    if (k.fd >= 0) {
+        if (int rc = download_to_fd(c, k.fd, k.file_off, d_src, bytes)) return rc;
+        k.file_off += bytes;
+        return VTX_OK;
+    }
+    if (!bytes) return VTX_OK;
+    if (k.len + bytes > k.cap) {                          // one pass is the rule: the first allocation is exact
+        const uint64_t cap = std::max<uint64_t>(k.len + bytes, k.cap + k.cap / 2);
+        uint8_t* p = (uint8_t*)realloc(k.buf, (size_t)cap);
+        if (!p) return fail(c, VTX_E_NOMEM, "%s: out of host memory for %llu bytes", fn, (unsigned long long)cap);
+        k.buf = p; k.cap = cap;
+    }
+    if (int rc = download(c, {{k.buf + k.len, d_src, bytes}})) return rc;
+    k.len += bytes;
+    return VTX_OK;
+}
+
+// The lines of the last vtx_run's triplets into `sink`, pass by pass.  head / hl: text that lies in front of the first pass's lines and
+// goes through the encoder with them (gz files: the header lines; such a call has a pass even without a triplet); hl = 0: the lines
+// alone.  *text_total = the bytes of text that went to the sink, *sum as documented above.  On an error the sink is the caller's to undo.
+static int mtx_text_engine(vtx_ctx* c, const char* fn, bool real, bool gz, int which, const char* head, uint32_t hl, MtxSink& sink,
+                           uint64_t* text_total, double* sum) {
     hipStream_t s = c->stream;
     const uint64_t nnz = c->nnz;
     const uint32_t* d_row = c->d_o_row.as<uint32_t>();
@@ -2524,22 +2552,15 @@ static int write_mtx_text(vtx_ctx* c, const char* fn, bool real, bool gz, const 
     double* d_sum = (double*)c->d_bam_cnt.p;
     uint32_t* d_flag = (uint32_t*)(c->d_bam_cnt.as<unsigned long long>() + VTXG_N_COUNTERS);
     HIP_TRY(c, hipMemsetAsync(c->d_bam_cnt.p, 0, VTXG_N_COUNTERS * sizeof(uint64_t) + 4 * sizeof(uint32_t), s));
-    const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (fd < 0) return fail(c, VTX_E_INVAL, "cannot open %s for writing", path);
-    auto bail = [&](int rc) { close(fd); unlink(path); return rc; };
-    char head[160];
-    const int hl = snprintf(head, sizeof head, "%%%%MatrixMarket matrix coordinate real general\n%% written by sprs\n%u %u %llu\n", n_rows, n_cols,
-                            (unsigned long long)nnz);
-    if (!gz && pwrite(fd, head, (size_t)hl, 0) != hl) return bail(fail(c, VTX_E_INVAL, "error writing %s", path));
-    uint64_t file_off = gz ? 0 : (uint64_t)hl, text_total = (uint64_t)hl;
+    *text_total = 0;
     bool first = true;
-    for (uint64_t base = 0; base < nnz || (gz && first); base += kSlab) {
+    for (uint64_t base = 0; base < nnz || (hl && first); base += kSlab) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(kSlab, nnz - base);
-        const uint32_t pre = gz && first ? (uint32_t)hl : 0u;      // gz: the header lines lie in front of the first pass's text — every byte of the file goes through the encoder
+        const uint32_t pre = first ? hl : 0u;                      // gz: the header lines lie in front of the first pass's text — every byte of the file goes through the encoder
         first = false;
-        if (hipError_t e = c->d_bam_nhit.reserve((size_t)n * sizeof(uint32_t) + 16)) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
-        if (hipError_t e = c->d_bam_hscan.reserve((size_t)n * sizeof(uint32_t) + 16)) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
-        if (hipError_t e = c->d_scan_tmp.reserve(vtxk_scan_temp_bytes(n))) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
+        if (hipError_t e = c->d_bam_nhit.reserve((size_t)n * sizeof(uint32_t) + 16)) return fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e));
+        if (hipError_t e = c->d_bam_hscan.reserve((size_t)n * sizeof(uint32_t) + 16)) return fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e));
+        if (hipError_t e = c->d_scan_tmp.reserve(vtxk_scan_temp_bytes(n))) return fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e));
         uint32_t* d_len = c->d_bam_nhit.as<uint32_t>();
         uint32_t* d_end = c->d_bam_hscan.as<uint32_t>();
         hipError_t e = vtxg_mtx_len(d_row + base, d_col + base, d_val + base, n, d_len, d_sum, d_flag, real ? 1 : 0, s);
@@ -2548,20 +2569,19 @@ static int write_mtx_text(vtx_ctx* c, const char* fn, bool real, bool gz, const 
         if (e == hipSuccess && n) e = hipMemcpyAsync(&total, d_end + (n - 1), sizeof total, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return bail(fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e)));
-        const char* host_fn = gz ? "vtxh_write_mtx_gz" : "vtxh_write_mtx";
+        if (e != hipSuccess) return fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+        const char* host_fn = sink.fd < 0 ? "vtxh_mtx_part" : gz ? "vtxh_write_mtx_gz" : "vtxh_write_mtx";
         if (flag)
-            return bail(real ? fail(c, VTX_E_UNSUPPORTED, "%s: a value outside the device formatter's domain (infinite, subnormal, |v| >= 2^53 or 0 < |v| < 2^-40): format on the host (vtx_fetch_coo + %s)", fn, host_fn)
-                             : fail(c, VTX_E_UNSUPPORTED, "%s: a value that is not a non-negative integer (alt_frac): format on the host (vtx_fetch_coo + %s)", fn, host_fn));
-        if ((e = c->d_bam_data.reserve((size_t)pre + total + 64)) != hipSuccess) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
+            return real ? fail(c, VTX_E_UNSUPPORTED, "%s: a value outside the device formatter's domain (infinite, subnormal, |v| >= 2^53 or 0 < |v| < 2^-40): format on the host (vtx_fetch_coo + %s)", fn, host_fn)
+                        : fail(c, VTX_E_UNSUPPORTED, "%s: a value that is not a non-negative integer (alt_frac): format on the host (vtx_fetch_coo + %s)", fn, host_fn);
+        if ((e = c->d_bam_data.reserve((size_t)pre + total + 64)) != hipSuccess) return fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e));
         if (pre) e = hipMemcpyAsync(c->d_bam_data.p, head, pre, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = vtxg_mtx_text(d_row + base, d_col + base, d_val + base, n, d_end, c->d_bam_data.as<uint8_t>() + pre, real ? 1 : 0, s);
-        text_total += total;
+        *text_total += (uint64_t)pre + total;
         if (!gz) {
             if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) return bail(fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e)));
-            if (int rc = download_to_fd(c, fd, file_off, c->d_bam_data.p, total)) return bail(rc);
-            file_off += total;
+            if (e != hipSuccess) return fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+            if (int rc = mtx_sink_put(c, fn, sink, c->d_bam_data.p, total)) return rc;
             continue;
         }
         const uint64_t t_bytes = (uint64_t)pre + total;             // > 0: a pass has the header lines or at least one line
@@ -2577,27 +2597,47 @@ static int write_mtx_text(vtx_ctx* c, const char* fn, bool real, bool gz, const 
         if (e == hipSuccess) e = ends.reserve((size_t)n_chunks * sizeof(uint32_t));
         if (e == hipSuccess) e = tok.reserve((size_t)vtxg_deflate_grid(n_chunks) * vtxd::CHUNK * sizeof(uint32_t));
         if (e == hipSuccess) e = c->d_scan_tmp.reserve(vtxk_scan_temp_bytes(std::max(n, n_chunks)));
-        if (e != hipSuccess) return bail(fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(c, VTX_E_NOMEM, "%s: %s", fn, hipGetErrorString(e));
         e = vtxg_mtx_deflate(c->d_bam_data.as<uint8_t>(), t_bytes, n_chunks, slots.as<uint8_t>(), sizes.as<uint32_t>(), tok.as<uint32_t>(), s);
         if (e == hipSuccess) e = vtxk_inclusive_scan_u32(sizes.as<uint32_t>(), ends.as<uint32_t>(), n_chunks, c->d_scan_tmp.p, vtxk_scan_temp_bytes(n_chunks), s);
         if (e == hipSuccess) e = vtxg_mtx_gz_compact(slots.as<uint8_t>(), sizes.as<uint32_t>(), ends.as<uint32_t>(), n_chunks, packed.as<uint8_t>(), s);
         uint32_t gz_bytes = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&gz_bytes, ends.as<uint32_t>() + (n_chunks - 1), sizeof gz_bytes, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return bail(fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e)));
-        if (gz_bytes > (uint64_t)n_chunks * vtxd::SLOT) return bail(fail(c, VTX_E_HIP, "%s: the encoder's sizes do not fit its slots", fn));
-        if (int rc = download_to_fd(c, fd, file_off, packed.p, gz_bytes)) return bail(rc);
-        file_off += gz_bytes;
+        if (e != hipSuccess) return fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+        if (gz_bytes > (uint64_t)n_chunks * vtxd::SLOT) return fail(c, VTX_E_HIP, "%s: the encoder's sizes do not fit its slots", fn);
+        if (int rc = mtx_sink_put(c, fn, sink, packed.p, gz_bytes)) return rc;
     }
-    if (gz && pwrite(fd, vtxd::EOF_BLOCK, sizeof vtxd::EOF_BLOCK, (off_t)file_off) != (ssize_t)sizeof vtxd::EOF_BLOCK)
-        return bail(fail(c, VTX_E_INVAL, "error writing %s", path));
-    if (text_bytes) *text_bytes = text_total;
     if (sum) {
         *sum = 0.0;
         if (nnz)
-            if (hipError_t e = hipMemcpy(sum, d_sum, sizeof(double), hipMemcpyDeviceToHost)) return bail(fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e)));
+            if (hipError_t e = hipMemcpy(sum, d_sum, sizeof(double), hipMemcpyDeviceToHost)) return fail(c, VTX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     }
-    if (close(fd) != 0) { unlink(path); return fail(c, VTX_E_INVAL, "error writing %s", path); }
+    return VTX_OK;
+}
+
+static int write_mtx_text(vtx_ctx* c, const char* fn, bool real, bool gz, const char* path, uint32_t n_rows, uint32_t n_cols, int which, double* sum,
+                          uint64_t* text_bytes) {
+    if (!c) return VTX_E_INVAL;
+    if (!path || (which != 0 && which != 1)) return fail(c, VTX_E_INVAL, "%s: bad argument", fn);
+    if (!c->ran) return fail(c, VTX_E_STATE, "%s: no completed vtx_run", fn);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    char head[160];
+    const int hl = vtxj::header(head, sizeof head, n_rows, n_cols, c->nnz);
+    MtxSink sink;
+    sink.fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (sink.fd < 0) return fail(c, VTX_E_INVAL, "cannot open %s for writing", path);
+    auto bail = [&](int rc) { close(sink.fd); unlink(path); return rc; };
+    if (!gz) {                                            // plain: the header lines straight into the file, the passes behind them
+        if (pwrite(sink.fd, head, (size_t)hl, 0) != hl) return bail(fail(c, VTX_E_INVAL, "error writing %s", path));
+        sink.file_off = (uint64_t)hl;
+    }
+    uint64_t text_total = 0;
+    if (int rc = mtx_text_engine(c, fn, real, gz, which, head, gz ? (uint32_t)hl : 0u, sink, &text_total, sum)) return bail(rc);
+    if (gz && pwrite(sink.fd, vtxd::EOF_BLOCK, sizeof vtxd::EOF_BLOCK, (off_t)sink.file_off) != (ssize_t)sizeof vtxd::EOF_BLOCK)
+        return bail(fail(c, VTX_E_INVAL, "error writing %s", path));
+    if (text_bytes) *text_bytes = text_total + (gz ? 0u : (uint64_t)hl);
+    if (close(sink.fd) != 0) { unlink(path); return fail(c, VTX_E_INVAL, "error writing %s", path); }
     return VTX_OK;
 }
 
@@ -2611,6 +2651,40 @@ int vtx_write_mtx_f64(vtx_ctx* c, const char* path, uint32_t n_rows, uint32_t n_
 
 int vtx_write_mtx_gz(vtx_ctx* c, const char* path, uint32_t n_rows, uint32_t n_cols, int which, int real, double* sum, uint64_t* text_bytes) {
     return write_mtx_text(c, "vtx_write_mtx_gz", real != 0, true, path, n_rows, n_cols, which, sum, text_bytes);
+}
+
+// ---- the matrix in parts (include/vtx.h): one part per vtx_run, joined behind a header at the end; no device state between the runs ----
+int vtx_mtx_part(vtx_ctx* c, int which, int real, int gz, struct vtx_mtx_part* out) {
+    if (!c) return VTX_E_INVAL;
+    if (out) memset(out, 0, sizeof *out);                 // before any return: vtx_mtx_part_free on it is always safe
+    if (!out || (which != 0 && which != 1)) return fail(c, VTX_E_INVAL, "vtx_mtx_part: bad argument");
+    if (!c->ran) return fail(c, VTX_E_STATE, "vtx_mtx_part: no completed vtx_run");
+    if (const char* k = VTX_DEV_ENV("VTX_MTX_PART_DECLINE")) {     // test hook: the k-th call of the process declines, as a value outside the formatter's domain would
+        static std::atomic<int> calls{0};
+        if (++calls == atoi(k)) return fail(c, VTX_E_UNSUPPORTED, "vtx_mtx_part: declined by the developer hook: format on the host (vtx_fetch_coo + vtxh_mtx_part)");
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    // the part comes back through download(): the copy workers' pinned buffers and streams, which a vtx_prefetch_file in flight is using
+    // for its upload — wait for it (plain parts too; a gz part drops the prefetched bytes as well, in the engine)
+    if (c->pf_thread.joinable()) c->pf_thread.join();
+    MtxSink sink;
+    uint64_t text_total = 0;
+    double sum = 0.0;
+    if (int rc = mtx_text_engine(c, "vtx_mtx_part", real != 0, gz != 0, which, nullptr, 0, sink, &text_total, &sum)) { free(sink.buf); return rc; }
+    out->bytes = sink.buf; out->n_bytes = sink.len; out->text_bytes = text_total; out->nnz = c->nnz; out->sum = sum; out->gz = gz ? 1u : 0u;
+    return VTX_OK;
+}
+
+void vtx_mtx_part_free(struct vtx_mtx_part* part) {
+    if (!part) return;
+    free(part->bytes);
+    memset(part, 0, sizeof *part);
+}
+
+int vtx_mtx_join(const char* path, uint32_t n_rows, uint32_t n_cols, int gz, const struct vtx_mtx_part* parts, uint32_t n_parts, uint64_t* text_bytes) {
+    char why[512];
+    const int rc = vtxj::join(path, n_rows, n_cols, gz, parts, n_parts, text_bytes, why, sizeof why);      // host code only (vtx_mtx_join.h)
+    return rc ? fail(nullptr, rc, "%s", why) : VTX_OK;
 }
 
 int vtx_device_coo(vtx_ctx* c, vtx_coo* out) {

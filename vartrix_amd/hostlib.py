@@ -34,7 +34,7 @@ SYMBOLS = ("vtxh_pack_files", "vtxh_free", "vtxh_last_error", "vtxh_get_batch", 
            "vtxh_format_f64", "vtxh_pack_files_raw", "vtxh_get_raw_batch", "vtxh_get_barcode_table", "vtxh_num_batches",
            "vtxh_get_batch_at", "vtxh_get_raw_batch_at", "vtxh_pack_files_range", "vtxh_test_inflate", "vtxh_read_format",
            "vtxh_trim", "vtxh_plan_ingest", "vtxh_get_ingest", "vtxh_is_plan", "vtxh_get_ingest_segments", "vtxh_plan_kind",
-           "vtxh_write_mtx_gz")
+           "vtxh_write_mtx_gz", "vtxh_mtx_part", "vtxh_mtx_part_free")
 METRIC_NAMES = ("num_reads", "num_low_mapq", "num_non_primary", "num_duplicates", "num_not_cell_bc",
                 "num_not_useful", "num_non_umi", "num_invalid_recs", "num_multiallelic_recs")
 
@@ -92,6 +92,10 @@ def load():
         L.vtxh_write_mtx.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vtxh_write_mtx_gz.restype = C.c_int
         L.vtxh_write_mtx_gz.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vtxh_mtx_part.restype = C.c_int
+        L.vtxh_mtx_part.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(abi.VtxMtxPart)]
+        L.vtxh_mtx_part_free.restype = None
+        L.vtxh_mtx_part_free.argtypes = [C.POINTER(abi.VtxMtxPart)]
         L.vtxh_format_f64.restype = C.c_int
         L.vtxh_format_f64.argtypes = [C.c_double, C.c_char_p]
         L.vtxh_plan_ingest.restype = C.c_int
@@ -268,6 +272,22 @@ def write_mtx(path, n_rows, n_cols, row, col, value):
 def write_mtx_gz(path, n_rows, n_cols, row, col, value):
     """``write_mtx``'s text gzip-compressed into ``path`` (vtxh_write_mtx_gz: zlib level 1 per 65 280-byte chunk, BGZF framing)."""
     _write_mtx(load().vtxh_write_mtx_gz, path, n_rows, n_cols, row, col, value)
+
+
+def mtx_part(row, col, value, gz=False) -> abi.MtxPart:
+    """vtxh_mtx_part: the host formatter's lines for these triplets (``gz``: vtxh_write_mtx_gz's members for them), without header
+    lines and without the end-of-file member — a part ``lib.mtx_join`` takes like one from ``Context.mtx_part``."""
+    L = load()
+    row = np.ascontiguousarray(row, np.uint32)
+    col = np.ascontiguousarray(col, np.uint32)
+    value = np.ascontiguousarray(value, np.float64)
+    st = abi.VtxMtxPart()
+    if L.vtxh_mtx_part(len(row), row.ctypes.data, col.ctypes.data, value.ctypes.data, int(bool(gz)), C.byref(st)) != 0:
+        raise HostError(L.vtxh_last_error().decode())
+    try:
+        return abi.MtxPart.from_struct(st)
+    finally:
+        L.vtxh_mtx_part_free(C.byref(st))
 
 
 def format_f64(v: float) -> str:

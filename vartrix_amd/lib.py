@@ -37,7 +37,7 @@ SYMBOLS = (
     "vtx_comm_id", "vtx_comm_init", "vtx_gather_coo", "vtx_fetch_gathered", "vtx_gather_abort", "vtx_gather_plan",
     "vtx_set_debug", "vtx_fetch_stage", "vtx_debug_bands", "vtx_debug_tables", "vtx_set_read_format",
     "vtx_submit_bam", "vtx_submit_bam_segments", "vtx_debug_ingest", "vtx_debug_inflate", "vtx_comm_ranks", "vtx_write_mtx", "vtx_prefetch_file",
-    "vtx_last_crc_ms", "vtx_write_mtx_gz",
+    "vtx_last_crc_ms", "vtx_write_mtx_gz", "vtx_mtx_part", "vtx_mtx_part_free", "vtx_mtx_join",
 )
 # (entry points with a digit in their name: tests/test_abi.py finds the header's declarations with [a-z_]+ and compares them with SYMBOLS,
 # so these are listed — and checked against the header and every build of the library, tests/test_abi_f64.py — on their own)
@@ -131,6 +131,12 @@ def load(variant=None):
     L.vtx_write_mtx_f64.argtypes = [ctxp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_double)]
     L.vtx_write_mtx_gz.restype = C.c_int
     L.vtx_write_mtx_gz.argtypes = [ctxp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.vtx_mtx_part.restype = C.c_int
+    L.vtx_mtx_part.argtypes = [ctxp, C.c_int, C.c_int, C.c_int, C.POINTER(abi.VtxMtxPart)]
+    L.vtx_mtx_part_free.restype = None
+    L.vtx_mtx_part_free.argtypes = [C.POINTER(abi.VtxMtxPart)]
+    L.vtx_mtx_join.restype = C.c_int
+    L.vtx_mtx_join.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(abi.VtxMtxPart), C.c_uint32, C.POINTER(C.c_uint64)]
     L.vtx_comm_ranks.restype = C.c_int
     L.vtx_comm_ranks.argtypes = [ctxp, C.POINTER(C.c_int)]
     L.vtx_debug_inflate.restype = C.c_int
@@ -171,6 +177,24 @@ def comm_id() -> bytes:
     if rc != abi.VTX_OK:
         raise VtxError(rc, L.vtx_strerror(None).decode())
     return buf.raw
+
+
+def mtx_join(path: str, n_rows: int, n_cols: int, parts, gz: bool = False, variant=None) -> int:
+    """vtx_mtx_join: ``path`` = the three Matrix-Market header lines (nnz = the parts' total), then the parts (``abi.MtxPart``, from
+    ``Context.mtx_part`` or ``hostlib.mtx_part``) in order; with ``gz`` a BGZF file (the header a member of its own, the empty member at
+    the end).  Needs no GPU.  Returns the uncompressed size of the file."""
+    L = load(variant)
+    arr = (abi.VtxMtxPart * max(len(parts), 1))()
+    keep = []
+    for i, p in enumerate(parts):
+        buf = C.create_string_buffer(p.bytes, len(p.bytes)) if p.bytes else None
+        keep.append(buf)
+        arr[i] = abi.VtxMtxPart(C.cast(buf, C.c_void_p) if buf is not None else None, len(p.bytes), p.text_bytes, p.nnz, p.sum, int(p.gz), 0)
+    t = C.c_uint64(0)
+    rc = L.vtx_mtx_join(path.encode(), n_rows, n_cols, int(bool(gz)), arr if parts else None, len(parts), C.byref(t))
+    if rc != abi.VTX_OK:
+        raise VtxError(rc, L.vtx_strerror(None).decode())
+    return int(t.value)
 
 
 class Context:
@@ -355,6 +379,17 @@ class Context:
         s, t = C.c_double(0.0), C.c_uint64(0)
         self._check(self._L.vtx_write_mtx_gz(self._h, path.encode(), n_rows, n_cols, which, int(bool(real)), C.byref(s), C.byref(t)))
         return float(s.value), int(t.value)
+
+    def mtx_part(self, which: int = 0, real: bool = False, gz: bool = False) -> abi.MtxPart:
+        """The last run's triplets as a finished PART of a Matrix-Market file (vtx_mtx_part): the lines alone, formatted on the device
+        (``gz``: deflated there into BGZF members) — for a matrix that several runs make; ``lib.mtx_join`` writes the parts behind a
+        header.  ``which`` / ``real`` and the decline rule (VTX_E_UNSUPPORTED) as for ``write_mtx``."""
+        st = abi.VtxMtxPart()
+        self._check(self._L.vtx_mtx_part(self._h, which, int(bool(real)), int(bool(gz)), C.byref(st)))
+        try:
+            return abi.MtxPart.from_struct(st)
+        finally:
+            self._L.vtx_mtx_part_free(C.byref(st))
 
     def comm_ranks(self) -> int:
         n = C.c_int(0)
