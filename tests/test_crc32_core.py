@@ -2,10 +2,12 @@
 every inflated BGZF block against its trailer: htslib's check in bgzf_read_block behind src/main.rs:822-830) — built for the host by
 tests/crc32core/Makefile, against zlib.crc32: the GF(2) helpers, and the whole 64-lane decomposition (interleaved pieces, head mask,
 front padding, butterfly, un-skip, tail) for each slicing width.  The device runs the same grid through the kernel in
-tests/test_gpu_crc32.py."""
+tests/test_gpu_crc32.py.  What the wavefront TOUCHES is checked by a stand-alone program (tests/crc32core/main.cpp) in allocations of
+exactly the device's size, plain and under AddressSanitizer and UBSan; nothing sanitized is loaded into Python."""
 import ctypes as C
 import os
 import random
+import struct
 import subprocess
 import zlib
 
@@ -117,3 +119,44 @@ def test_combine_against_zlib_on_random_splits(core):
         cut = rng.randrange(0, n + 1)
         a, b = data[:cut], data[cut:]
         assert core.vtxt_combine(zlib.crc32(a), zlib.crc32(b), len(b)) == zlib.crc32(data), (n, cut)
+
+
+def run_program(cases, tmp, san):
+    """cases: [(W, s, data, total, fill)] through tests/crc32core/main.cpp in ONE process -> [crc]."""
+    name = "crc32_host_san" if san else "crc32_host"
+    subprocess.check_call(["make", "-C", os.path.join(HERE, "crc32core"), "-s", name])
+    src, dst = os.path.join(tmp, name + ".in"), os.path.join(tmp, name + ".out")
+    with open(src, "wb") as f:
+        f.write(struct.pack("<I", len(cases)))
+        for w, s, data, total, fill in cases:
+            f.write(struct.pack("<IIIII", w, s, len(data), total, fill) + data)
+    r = subprocess.run([os.path.join(HERE, "crc32core", name), src, dst], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr, "exit %d\n%s" % (r.returncode, r.stderr[-4000:])
+    out = open(dst, "rb").read()
+    assert len(out) == 4 * len(cases)
+    return list(struct.unpack("<%dI" % len(cases), out))
+
+
+def test_the_wavefront_reads_nothing_outside_the_inflated_buffer(tmp_path):
+    """Every length 0..300 and the edge lengths at every misalignment 0..15, each width, the block FIRST in its buffer (its head
+    read, down to start & ~(W - 1), starts at the allocation's base; other bytes follow) and LAST (other bytes in front; it ends
+    at total, the allocation at total + 64, as d_bam_data's does), the other bytes 00, FF or A5: the stand-alone program gives
+    zlib.crc32, and its build under AddressSanitizer and UBSan exits 0 without a report and gives the same."""
+    rng = random.Random(12)
+    blobs = {n: rng.randbytes(n) for n in list(range(301)) + [65280, 65535, 65536]}
+    cases, want = [], []
+    for w in WIDTHS:
+        edges = [65280, 65536, 65535, 64 * w - 1, 64 * w, 64 * w + 1, 128 * w - 1, 128 * w + 1, 63 * w, 65 * w]
+        for n in list(range(301)) + edges:
+            data = blobs.setdefault(n, rng.randbytes(n))
+            for m in (range(16) if n <= 300 else (0, 1, w - 1, 15)):
+                fill = (0x00, 0xFF, 0xA5)[(n + m) % 3]
+                cases.append((w, m, data, m + n + 37, fill))               # first
+                cases.append((w, 32 + m, data, 32 + m + n, fill))          # last
+                if n % 50 == 0:
+                    cases.append((w, m, data, m + n, fill))                # alone: first and last
+                want += [zlib.crc32(data)] * (len(cases) - len(want))
+    assert len(cases) > 28000
+    plain = run_program(cases, str(tmp_path), san=False)
+    assert plain == want, next((c[:2] + (len(c[2]),) + c[3:]) for c, g, e in zip(cases, plain, want) if g != e)
+    assert run_program(cases, str(tmp_path), san=True) == want

@@ -127,6 +127,58 @@ def test_inflate_kernel_never_accepts_what_zlib_rejects(ctx):
     assert 100 < accepted < 1400
 
 
+def test_inflate_kernel_verdicts_do_not_depend_on_what_follows_a_block(ctx):
+    """The hostile corpus of tests/test_inflate_bounds.py (every prefix of valid streams, 15-bit-code streams cut short, blocks
+    without an end-of-block, headers cut at each field) through ONE launch.  Each hostile block is there twice, followed by 16
+    bytes of 00 and by 16 bytes of FF, and a valid block sits between any two of them, so hostile and valid lanes share
+    wavefronts.  Per block the kernel's status is the CPU build's of the same header (tests/inflatecore/libinflate_host.so), the
+    same in both copies, and every valid neighbour comes out as zlib's bytes.  No hostile block is last: 128 KiB of filler end
+    the blob, more than 65 280 literals of 15 bits can read, so no decoder — bounded or not — leaves the upload."""
+    import ctypes as C
+    import subprocess
+    import inflate_bounds_util as U
+    subprocess.check_call(["make", "-C", os.path.join(HERE, "inflatecore"), "-s"])
+    L = C.CDLL(os.path.join(HERE, "inflatecore", "libinflate_host.so"))
+    L.vtxt_inflate.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
+    L.vtxt_inflate.restype = C.c_uint32
+    cases = U.corpus()
+    valid = [(c, U.zlib_verdict(c.raw, c.out_len)) for c in cases if c.expect == U.ST_OK]
+    small = [v for v in valid if len(v[0].raw) < 1000]
+    hostile = [c for c in cases if c.expect != U.ST_OK]
+    assert len(hostile) > 500 and len(small) >= 8 and len(valid) - len(small) >= 18
+    blob, blocks, what = bytearray(), [], []           # what: ("valid", bytes) or ("hostile", case)
+
+    def add(raw, n, tail, tag):
+        blocks.append((len(blob), len(raw), n))
+        blob.extend(raw + tail)
+        what.append(tag)
+
+    neighbours = [v for v in valid if v not in small] + small * (2 * len(hostile) // len(small) + 1)       # each long stream once, then the small ones in turn
+    k = 0
+    for c in hostile:
+        for tail in (b"\x00" * 16, b"\xff" * 16):
+            add(c.raw, c.out_len, tail, ("hostile", c))
+            v, z = neighbours[k]
+            k += 1
+            add(v.raw, v.out_len, b"", ("valid", z))
+    blob.extend(b"\xa5" * (128 << 10))
+    assert what[-1][0] == "valid" and blocks[-1][0] + blocks[-1][1] + (128 << 10) == len(blob)
+    status, outs = ctx.debug_inflate(bytes(blob), blocks)
+    cpu = {}
+    for c in hostile:
+        out = (C.c_uint8 * (c.out_len + 64))()
+        cpu[c.name] = L.vtxt_inflate(c.raw, len(c.raw), C.addressof(out), c.out_len, 64, None)
+        assert cpu[c.name] != 0 and (c.expect is None or cpu[c.name] == c.expect), c.name
+    seen = {}
+    for st, o, (kind, x) in zip(status, outs, what):
+        if kind == "valid":
+            assert st == 0 and o == x
+        else:
+            assert st == cpu[x.name], (x.name, int(st), cpu[x.name])
+            assert seen.setdefault(x.name, int(st)) == st, x.name          # (both copies)
+    assert len(seen) == len(hostile)
+
+
 def test_inflate_kernel_on_the_reference_bam(ctx):
     """Every BGZF block of the reference's test.bam (multi-member gzip: one member per block), CRC32 of each trailer."""
     f = open(os.path.join(G, "test.bam"), "rb").read()

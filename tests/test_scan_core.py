@@ -3,7 +3,9 @@ bam_endpos rule, the CIGAR walk behind useful_alignment, the aux lookup, the ove
 the host by tests/scancore/Makefile, against the independently written model in tests/bam_grammar_util.py.  The oracle's
 vtxo_cigar_read_pos / vtxo_useful_alignment, oracle/refpipe.py's aux_string and the host packer's own copies (test hooks of
 libvtxhost_dev.so) are compared with the same model on the same cases.  The device runs the same grammar through the kernel in
-tests/test_gpu_bam_grammar.py."""
+tests/test_gpu_bam_grammar.py.  What the record logic and the record-chain step TOUCH is checked by a stand-alone program
+(tests/scancore/main.cpp) in allocations of exactly the device's sizes, plain and under AddressSanitizer and UBSan; nothing sanitized
+is loaded into Python."""
 import bisect
 import ctypes as C
 import itertools
@@ -464,3 +466,151 @@ def test_overlap_and_filter_loop(core):
     for tid in (1, 2, 7, -1):
         rec = bamwriter.record(tid, 100, "r", "ACGT", "10M", tags=[("CB", "Z", "ACGT-1")])
         assert scan(core, rec, {}, iv)[:2] == (0, [])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# what the record logic touches: the stand-alone program, plain and sanitized
+# ---------------------------------------------------------------------------------------------------------------------------
+def run_program(cases, tmp, san):
+    """cases: [(kind, payload)] through tests/scancore/main.cpp in ONE process -> [bytes]."""
+    name = "scan_host_san" if san else "scan_host"
+    subprocess.check_call(["make", "-C", os.path.join(HERE, "scancore"), "-s", name])
+    src, dst = os.path.join(tmp, name + ".in"), os.path.join(tmp, name + ".out")
+    with open(src, "wb") as f:
+        f.write(struct.pack("<I", len(cases)))
+        for kind, payload in cases:
+            f.write(struct.pack("<II", kind, len(payload)) + payload)
+    r = subprocess.run([os.path.join(HERE, "scancore", name), src, dst], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr, "exit %d\n%s" % (r.returncode, r.stderr[-4000:])
+    blob, q, out = open(dst, "rb").read(), 0, []
+    for _ in cases:
+        m, = struct.unpack_from("<I", blob, q)
+        out.append(blob[q + 4:q + 4 + m])
+        q += 4 + m
+    assert q == len(blob)
+    return out
+
+
+def with_raw_aux(rec, aux):
+    """A record of bamwriter's with `aux` as its aux block, whatever the bytes are."""
+    return struct.pack("<I", len(rec) - 4 + len(aux)) + rec[4:] + aux
+
+
+def chain_model(data, p, stop):
+    """The walk of bam_chain_kernel / bam_chain_seg_kernel as they were written before the step moved into vtx_scan_core.h:
+    (records, bad, p at the end, highest byte offset read + 1)."""
+    limit, k, bad, read_to = len(data), 0, False, 0
+    while p < stop:
+        if p + 36 > limit:
+            bad = True
+            break
+        bs, = struct.unpack_from("<I", data, p)
+        read_to = max(read_to, p + 4)
+        if bs < 32 or p + 4 + bs > limit:
+            bad = True
+            break
+        k += 1
+        p += 4 + bs
+    return k, int(bad or p != stop), p, read_to
+
+
+def chain_corpus():
+    """[(name, data, p, stop)]: block_size 0, 31, 32 and 0xFFFFFFFF in the first, a middle and the last record; the last record
+    ending exactly at the limit, one byte past it, and with fewer than 36 bytes left in front of the limit."""
+    def rec(bs, body=None):
+        return struct.pack("<I", bs) + b"\x5a" * (bs if body is None else body)
+    good = [rec(32), rec(40), rec(33), rec(100)]
+    out = []
+    whole = b"".join(good)
+    out.append(("four records, the last ends exactly at the limit", whole, 0, len(whole)))
+    out.append(("the last record ends one byte past the limit", whole[:-1], 0, len(whole)))
+    out.append(("the last record ends one byte past the limit, stop at the limit", whole[:-1], 0, len(whole) - 1))
+    out.append(("a record of 36 bytes is all there is", rec(32), 0, 36))
+    out.append(("35 bytes left in front of the limit", whole + rec(32)[:35], 0, len(whole) + 36))
+    out.append(("4 bytes left in front of the limit", whole + rec(32)[:4], 0, len(whole) + 36))
+    out.append(("nothing left in front of the limit, stop behind it", whole, 0, len(whole) + 36))
+    out.append(("the chain steps over the stop", whole, 0, len(whole) - 50))
+    out.append(("starts at the stop", whole, 36, 36))
+    out.append(("starts behind the limit", whole, len(whole) + 8, len(whole) + 80))
+    for bs in (0, 31, 32, 0xFFFFFFFF, 0x7FFFFFFF, 0xFFFFFFFC):
+        for where in range(4):
+            recs = list(good)
+            recs[where] = rec(bs, body=bs if bs <= 32 else 32)
+            data = b"".join(recs)
+            out.append(("block_size %#x in record %d" % (bs, where), data, 0, len(data)))
+    return out
+
+
+def test_the_record_logic_reads_nothing_outside_the_inflated_buffer(core, tmp_path):
+    """view_record, aux_string and scan_pairs on the record-layout extremes, the malformed records and the aux corpus (each aux
+    block also as the aux block of a record that gets as far as the tag lookup), every record or block the LAST thing of a buffer
+    of exactly its size + 64; the chain walk over buffers of exactly `limit` bytes.  The stand-alone program answers what the
+    shared object answers in the tests above (and, for aux blocks and chains, what the models say), and its build under
+    AddressSanitizer and UBSan exits 0 without a report and answers the same."""
+    cases, want = [], []
+    fills = (0x00, 0xFF, 0xA5)
+    # view_record
+    recs = []
+    for qlen, l_seq, cigar, flag in itertools.product((0, 1, 3, 254), (0, 1, 7, 150), ("*", "3S", "2H3M1D2=1X4N1I2P3S"), (0, 0x4)):
+        seq = "".join(M.NT16[(i * 7 + qlen) % 16] for i in range(l_seq))
+        recs.append(bamwriter.record(3, 123456, "n" * qlen, seq, cigar, flag=flag, tags=[("CB", "Z", "AC-1")] if l_seq % 2 else []))
+    malformed = []
+    for off, fmt, val in ((20, "<i", 4000), (16, "<H", 60000), (20, "<i", 0x7FFFFFFF), (12, "<B", 255)):
+        r = bytearray(bamwriter.record(0, 10, "name", "ACGT", "4M"))
+        struct.pack_into(fmt, r, off, val)                   # l_seq, n_cigar_op, l_seq, l_read_name beyond block_size
+        malformed.append(bytes(r))
+    for i, r in enumerate(recs + malformed):
+        pre = (0, 1, 2, 3, 5)[i % 5]
+        cases.append((0, struct.pack("<II", pre, fills[i % 3]) + r))
+        v = view(core, b"\xa5" * pre + r + b"\xa5" * 8, pre)
+        want.append(struct.pack("<12q", *v.values()))
+    for r in malformed:
+        v = view(core, r + b"\xa5" * 8)
+        assert v["malformed"] == 1 and v["aux"] == v["bs"] and v["endpos"] == 11
+    # aux_string
+    for i, (name, aux, _) in enumerate(aux_corpus()):
+        for tag in (b"CB", b"UB", b"XZ", b"Bg", b"ZZ"):
+            cases.append((1, struct.pack("<III", i % 7, fills[i % 3], struct.unpack("<H", tag)[0]) + aux))
+            got = M.aux_lookup(aux, tag)
+            # (the offset of the value: behind the first occurrence of tag + 'Z' that the model's tokens name)
+            want.append(("aux", aux, got))
+    # scan_pairs: the aux corpus as the aux block of a record that overlaps loci, and the filters
+    iv = sorted({(s, s + w) for s in range(90, 140, 3) for w in (1, 2, 9)})
+    st = np.array([s for s, _ in iv], dtype=np.int32)
+    en = np.array([e for _, e in iv], dtype=np.int32)
+    tables = st.tobytes() + en.tobytes() + struct.pack("<3I", 0, len(iv), len(iv)) + struct.pack("<2i", 9, 0)
+    scans = [(with_raw_aux(bamwriter.record(0, 100, "r", "ACGTN", "10M"), aux), {}) for _, aux, _ in aux_corpus()]
+    for cigar, flag, flt in itertools.product(("10M", "*", "3S4M2D4M", "5M2H5M", "3H", "6M3S2H"), (0, 0x4, 0x100, 0x400), (dict(), dict(mapq=30), dict(primary_only=True, no_duplicates=True))):
+        scans.append((bamwriter.record(0, 118, "r", "ACG", cigar, flag=flag, mapq=40, tags=[("UB", "Z", "UMI1"), ("Xi", "i", 3), ("CB", "Z", "ACGT-1")]), flt))
+    scans.append((bamwriter.record(-1, 100, "r", "ACGT", "10M", tags=[("CB", "Z", "ACGT-1")]), {}))
+    scans.append((malformed[0], {}))
+    for i, (r, flt) in enumerate(scans):
+        f = struct.pack("<5I", 2, flt.get("mapq", 0), int(flt.get("primary_only", False)), int(flt.get("no_duplicates", False)), struct.unpack("<H", b"CB")[0])
+        cases.append((2, struct.pack("<II", i % 5, fills[i % 3]) + f + struct.pack("<II", 2, len(iv)) + tables + r))
+        n, pairs, V = scan(core, r, flt, iv)
+        assert n >= -1
+        want.append(struct.pack("<i11I", n, *V.values()) + b"".join(struct.pack("<II", k, o) for k, o in pairs))
+    assert sum(w[:4] != b"\0\0\0\0" and w[:4] != b"\xff\xff\xff\xff" for w in want[-len(scans):]) > 100      # most records meet loci
+    # the record-chain walk
+    chains = chain_corpus()
+    verdicts = set()
+    for name, data, p, stop in chains:
+        cases.append((3, struct.pack("<QQ", p, stop) + data))
+        k, bad, end, read_to = chain_model(data, p, stop)
+        assert read_to <= len(data), name                   # the kernels as they were read nothing at or beyond the limit
+        verdicts.add((bad, k > 0))
+        want.append(struct.pack("<IIQ", k, bad, end))
+    assert verdicts == {(0, True), (0, False), (1, True), (1, False)}
+    assert chain_model(chains[0][1], 0, len(chains[0][1]))[:2] == (4, 0) and chain_model(chains[1][1], 0, len(chains[1][1]) + 1)[:2] == (3, 1)
+
+    for san in (False, True):
+        got = run_program(cases, str(tmp_path), san)
+        for (kind, _), g, w in zip(cases, got, want):
+            if kind == 1:
+                _, aux, val = w
+                o, ln = struct.unpack("<II", g)
+                assert (None if o == 0xFFFFFFFF else aux[o:o + ln]) == val, (san, aux[:40], val)
+            elif kind == 2 and w[:4] == b"\xff\xff\xff\xff":
+                assert g[:4] == w[:4], san                   # a malformed record is not scanned: there is no verdict to compare
+            else:
+                assert g == w, (san, kind)

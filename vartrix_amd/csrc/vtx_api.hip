@@ -29,6 +29,7 @@
 #include "vtx_device.h"
 #include "vtx_ingest.h"
 #include "vtx_deflate_core.h"
+#include "vtx_inflate_core.h"
 #include "vtx_mtx_join.h"
 #include "../../include/vtx_band_semantics.h"
 
@@ -71,6 +72,11 @@ const uint32_t kFastReadLen = VTX_FAST_READ_LEN;   // 16 rows x 64 lanes
 const uint32_t kFastHapLen = VTX_FAST_HAP_LEN;     // 16 record slots x (len + 35) words must fit 160 KiB of LDS
 // Beyond the fast limits a record is scored by slow_align_kernel (exact, one lane per alignment); its 16-bit coordinates
 // set the hard limits.
+// Slack behind the compressed BAM bytes (d_bam_comp) and behind the inflated ones (d_bam_data): bgzf_inflate_kernel loads whole
+// words, up to IN_PAD bytes behind a block's payload and OUT_PAD bytes behind its output (vtx_inflate_core.h), and the last block
+// of an upload has nothing else behind it.
+const size_t kBamPad = 64;
+static_assert(kBamPad >= vtxi::IN_PAD && kBamPad >= vtxi::OUT_PAD, "the inflater's loads must stay inside d_bam_comp / d_bam_data");
 const uint32_t kMaxReadLen = 30000;
 const uint32_t kMaxHapLen = 30000;
 // The call reduction runs one thread per (row, cell) group when the batch's mean group is at most this many records, and the
@@ -1216,7 +1222,7 @@ int vtx_prefetch_file(vtx_ctx* c, const char* path, uint64_t file_off, uint64_t 
     if (file_off > (uint64_t)st.st_size) file_off = (uint64_t)st.st_size;
     if (n == 0 || file_off + n > (uint64_t)st.st_size) n = (uint64_t)st.st_size - file_off;
     if (!n) { close(fd); return VTX_OK; }
-    if (hipSetDevice(c->cfg.device) != hipSuccess || c->d_bam_comp.reserve((size_t)n + 64) != hipSuccess) { close(fd); return fail(c, VTX_E_NOMEM, "vtx_prefetch_file: no device memory for %llu bytes", (unsigned long long)n); }
+    if (hipSetDevice(c->cfg.device) != hipSuccess || c->d_bam_comp.reserve((size_t)n + kBamPad) != hipSuccess) { close(fd); return fail(c, VTX_E_NOMEM, "vtx_prefetch_file: no device memory for %llu bytes", (unsigned long long)n); }
     // the copy workers read the file through a mapping of their own (measured against pread() into the pinned buffers at config-3 scale:
     // the same 80 - 200 ms beside the host's planning threads, and the mapping showed no multi-second outliers)
     const uint64_t map_off = file_off & ~(uint64_t)4095;
@@ -1329,9 +1335,9 @@ static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_se
     const float pf_wait_ms = (float)(1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_pf).count());
     const bool prefetched = !sg && c->pf_valid && c->pf_rc == VTX_OK && nb && c->pf_off <= lo && hi + kTrailer <= c->pf_off + c->pf_n;
     if (prefetched) { const uint64_t shift = lo - c->pf_off; for (auto& B : blocks) B.coff += shift; }
-    else { c->pf_valid = false; HIP_TRY(c, c->d_bam_comp.reserve((size_t)comp_bytes + 64)); }
+    else { c->pf_valid = false; HIP_TRY(c, c->d_bam_comp.reserve((size_t)comp_bytes + kBamPad)); }
     if (sg) HIP_TRY(c, c->d_bam_segs.reserve(segs.size() * sizeof(vtxg_segment) + (size_t)g->n_seeds * sizeof(uint32_t) + 64));
-    HIP_TRY(c, c->d_bam_data.reserve((size_t)utotal + 64));
+    HIP_TRY(c, c->d_bam_data.reserve((size_t)utotal + kBamPad));
     HIP_TRY(c, c->d_bam_blocks.reserve((size_t)nb * sizeof(vtxg_block)));
     HIP_TRY(c, c->d_bam_seeds.reserve((size_t)ns * u64));
     HIP_TRY(c, c->d_bam_seed_cnt.reserve((size_t)ns * u32 + 16));
@@ -1493,14 +1499,14 @@ int vtx_debug_inflate(vtx_ctx* c, const uint8_t* file, uint64_t file_bytes, cons
     hipStream_t s = c->stream;
     if (c->pf_thread.joinable()) c->pf_thread.join();
     c->pf_valid = false;
-    HIP_TRY(c, c->d_bam_comp.reserve((size_t)file_bytes + 64));
-    HIP_TRY(c, c->d_bam_data.reserve((size_t)utotal + 64));
+    HIP_TRY(c, c->d_bam_comp.reserve((size_t)file_bytes + kBamPad));
+    HIP_TRY(c, c->d_bam_data.reserve((size_t)utotal + kBamPad));
     HIP_TRY(c, c->d_bam_blocks.reserve((size_t)n * sizeof(vtxg_block) + 16));
     HIP_TRY(c, c->d_bam_cnt.reserve(VTXG_N_COUNTERS * sizeof(uint64_t) + 4 * sizeof(uint32_t)));
     HIP_TRY(c, c->d_bam_seed_cnt.reserve((size_t)n * sizeof(uint32_t) + 16));
     uint32_t* d_err = (uint32_t*)(c->d_bam_cnt.as<unsigned long long>() + VTXG_N_COUNTERS);
     HIP_TRY(c, hipMemsetAsync(d_err, 0, 4 * sizeof(uint32_t), s));
-    HIP_TRY(c, hipMemsetAsync(c->d_bam_data.p, 0xEE, (size_t)utotal + 64, s));
+    HIP_TRY(c, hipMemsetAsync(c->d_bam_data.p, 0xEE, (size_t)utotal + kBamPad, s));
     if (file_bytes) HIP_TRY(c, hipMemcpyAsync(c->d_bam_comp.p, file, (size_t)file_bytes, hipMemcpyHostToDevice, s));
     if (n) HIP_TRY(c, hipMemcpyAsync(c->d_bam_blocks.p, blocks.data(), (size_t)n * sizeof(vtxg_block), hipMemcpyHostToDevice, s));
     HIP_TRY(c, vtxg_inflate(c->d_bam_comp.as<uint8_t>(), c->d_bam_blocks.as<vtxg_block>(), n, c->d_bam_data.as<uint8_t>(), d_err, c->d_bam_seed_cnt.as<uint32_t>(), 0, s));

@@ -19,6 +19,15 @@
 // rejected block makes the whole ingest fall back to the host packer, where zlib stays the authority (vtx_host.cpp: inflate_block).
 // Nothing is written outside [out, out + out_len): the neighbouring block belongs to another lane.
 //
+// Input that runs out: a decode step (a Huffman symbol, its extra bits, a header field) that has consumed a bit at or beyond
+// 8 * in_len ends the block with ST_INPUT BEFORE what it decoded is acted on — the bits behind the block never decide anything.  So
+// the status and the trip count are functions of in[0 .. in_len) and out_len alone, a proper prefix of a valid stream is ST_INPUT,
+// and no load from `in` lies outside [in, in + in_len + IN_PAD): a refill happens with fewer than 8 bits of overshoot (at most the
+// 5 extra bits of a length symbol are taken unchecked), so its four bytes end at in_len + 8 at the latest.  The symbol loop asks
+// only near the end: while 8 or more bytes of the block lie in front of the next load, a trip (two refills at most) cannot starve,
+// and runs without the questions — one compare per trip is what the bound costs.  S_COPY reads whole 8-byte words of the output
+// written so far: no load from `out` lies outside [out, out + out_len + OUT_PAD).
+//
 // Compiles for the host too (tests/inflatecore/: every accepted stream equals zlib's output byte for byte; CPU suite, no GPU needed).
 #ifndef VTX_INFLATE_CORE_H
 #define VTX_INFLATE_CORE_H
@@ -55,6 +64,10 @@ struct Scratch {
 constexpr int CUR = 0;         // 16: per-length counters / cursors (code-length code, literal / length table)
 constexpr int CUR_D = 16;      // 16: the same for the distance table (both tables of a dynamic block are counted in one pass)
 constexpr int BYTES = 344, HI_WORDS = 9, CNT_WORDS = 32;           // per lane: 344 + 36 + 64 = 444 bytes
+
+// Bytes behind in[in_len) and out[out_len) that the decoder may LOAD (never use, never write): the buffers are allocated with at least
+// this much slack behind their last block (vtx_api.hip: static_assert on its reserves).
+constexpr uint32_t IN_PAD = 8, OUT_PAD = 8;
 
 enum Status : uint32_t { ST_OK = 0, ST_BAD_TYPE = 1, ST_BAD_STORED = 2, ST_BAD_CODE = 3, ST_BAD_SYMBOL = 4, ST_BAD_DIST = 5,
                          ST_OVERRUN = 6, ST_SHORT = 7, ST_INPUT = 8 };
@@ -113,16 +126,21 @@ VTXI_FN int make_code(Code& c, const Scratch& sc, int cur, int max_len) {
 }
 
 struct Bits {
-    const uint8_t* in;       // compressed bytes of the block (readable for 8 bytes past in_len: the buffer is padded)
+    const uint8_t* in;       // compressed bytes of the block (readable for IN_PAD bytes past in_len: the buffer is padded)
+    uint32_t in_len;
     uint32_t ip;             // next byte to load
     uint32_t cnt;            // valid bits in buf
     uint64_t buf;
-    VTXI_MEM void refill() {  // >= 33 valid bits afterwards (the input may be exhausted: the bits beyond are whatever follows, and
-        if (cnt <= 32) {     // `consumed() > in_len * 8` is checked where a block ends)
+    // >= 33 valid bits afterwards.  The callers keep consumed() < 8 * in_len + 8 here, so ip <= in_len + 4: the load ends inside the
+    // padding.  Bits from beyond in_len may enter buf; starved() is asked before anything decoded from them is acted on.
+    VTXI_MEM void refill() {
+        if (cnt <= 32) {
             buf |= (uint64_t)ld4(in + ip) << cnt;
             ip += 4; cnt += 32;
         }
     }
+    // consumed() > 8 * in_len: a bit from beyond the block has been taken (32-bit arithmetic: ip - in_len is at most IN_PAD here)
+    VTXI_MEM bool starved() const { return ip > in_len && ((ip - in_len) << 3) > cnt; }
     VTXI_MEM uint32_t peek15() const { return (uint32_t)buf & 0x7fffu; }
     VTXI_MEM uint32_t take(uint32_t n) { const uint32_t v = (uint32_t)buf & ((1u << n) - 1u); buf >>= n; cnt -= n; return v; }
     VTXI_MEM void drop(uint32_t n) { buf >>= n; cnt -= n; }
@@ -144,10 +162,55 @@ VTXI_FN uint32_t dist_base_extra(uint32_t s) {           // 0..29
     return (1 + ((2 + (s & 1)) << e)) | (e << 16);
 }
 
+// One S_SYM trip: a literal, an end-of-block, or a length / distance pair up to the start of its copy.  CHECKED: the trip may reach
+// the end of the input — starved() is asked before anything decoded is acted on (a bit pattern that is no code comes back with 15
+// bits, more than a starved input has left, so ST_INPUT wins over ST_BAD_CODE there).  Unchecked: the caller saw b.ip + 8 <= in_len
+// — a trip refills at most twice, so every bit it can take is inside the block — and the two forms do the same.
+template <bool CHECKED>
+VTXI_FN void sym_trip(Bits& b, const Code& ll, const Code& dc, const Scratch& sc, uint8_t* out, uint32_t out_len, bool last,
+                      uint32_t& op, uint32_t& st, uint32_t& err, uint32_t& rem, uint32_t& src, uint32_t& dist) {
+    b.refill();
+    uint32_t idx, len;
+    decode(ll, b.peek15(), idx, len);
+    b.drop(len);
+    if (CHECKED && b.starved()) { err = ST_INPUT; st = S_DONE; }
+    else if (idx >= ll.n) { err = ST_BAD_CODE; st = S_DONE; }
+    else {
+        const uint32_t sym = sc.ll(idx);
+        if (sym < 256) {
+            if (op >= out_len) { err = ST_OVERRUN; st = S_DONE; }
+            else out[op++] = (uint8_t)sym;
+        } else if (sym == 256) st = last ? S_DONE : S_HEADER;
+        else if (sym > 285) { err = ST_BAD_SYMBOL; st = S_DONE; }
+        else {
+            const uint32_t lb = len_base_extra(sym - 257);
+            const uint32_t mlen = (lb & 0xffffu) + b.take(lb >> 16);      // (at most 5 bits unchecked in front of the refill)
+            b.refill();
+            uint32_t didx, dlen;
+            decode(dc, b.peek15(), didx, dlen);
+            b.drop(dlen);
+            if (didx >= dc.n) { err = CHECKED && b.starved() ? ST_INPUT : ST_BAD_CODE; st = S_DONE; }
+            else {
+                const uint32_t dsym = sc.d(didx);
+                if (dsym > 29) { err = CHECKED && b.starved() ? ST_INPUT : ST_BAD_SYMBOL; st = S_DONE; }
+                else {
+                    const uint32_t db = dist_base_extra(dsym);
+                    dist = (db & 0xffffu) + b.take(db >> 16);
+                    if (CHECKED && b.starved()) { err = ST_INPUT; st = S_DONE; }     // (covers the length's extra bits and the distance code too)
+                    else if (dist > op) { err = ST_BAD_DIST; st = S_DONE; }
+                    else if (mlen > out_len - op) { err = ST_OVERRUN; st = S_DONE; }
+                    else { rem = mlen; src = op - dist; st = S_COPY; }
+                }
+            }
+        }
+    }
+}
+
 // Inflates in[0 .. in_len) into out[0 .. out_len); returns a Status.  sc: scratch private to this lane.
 // trips (optional statistics): state-machine trips taken.
 VTXI_FN uint32_t inflate_block(const uint8_t* in, uint32_t in_len, uint8_t* out, uint32_t out_len, const Scratch& sc, uint32_t* trips) {
-    Bits b{in, 0u, 0u, 0ull};
+    Bits b{in, in_len, 0u, 0u, 0ull};
+    const uint32_t fast_end = in_len >= 8u ? in_len - 7u : 0u;      // b.ip < fast_end: b.ip + 8 <= in_len, an S_SYM trip cannot starve
     Code ll, dc;
     for (int j = 0; j < 15; ++j) { ll.p[j] = 0; dc.p[j] = 0; }
     ll.n = dc.n = 0;
@@ -174,42 +237,10 @@ VTXI_FN uint32_t inflate_block(const uint8_t* in, uint32_t in_len, uint8_t* out,
             }
             op += n; src += n; rem -= n;
             if (rem == 0) st = S_SYM;
+        } else if (st == S_SYM && b.ip < fast_end) {
+            sym_trip<false>(b, ll, dc, sc, out, out_len, last, op, st, err, rem, src, dist);
         } else if (st == S_SYM) {
-            b.refill();
-            uint32_t idx, len;
-            decode(ll, b.peek15(), idx, len);
-            if (idx >= ll.n) { err = ST_BAD_CODE; st = S_DONE; }
-            else {
-                b.drop(len);
-                const uint32_t sym = sc.ll(idx);
-                if (sym < 256) {
-                    if (op >= out_len) { err = ST_OVERRUN; st = S_DONE; }
-                    else out[op++] = (uint8_t)sym;
-                } else if (sym == 256) {
-                    if (b.consumed() > (uint64_t)in_len * 8) { err = ST_INPUT; st = S_DONE; }
-                    else st = last ? S_DONE : S_HEADER;
-                } else if (sym > 285) { err = ST_BAD_SYMBOL; st = S_DONE; }
-                else {
-                    const uint32_t lb = len_base_extra(sym - 257);
-                    const uint32_t mlen = (lb & 0xffffu) + b.take(lb >> 16);
-                    b.refill();
-                    uint32_t didx, dlen;
-                    decode(dc, b.peek15(), didx, dlen);
-                    if (didx >= dc.n) { err = ST_BAD_CODE; st = S_DONE; }
-                    else {
-                        b.drop(dlen);
-                        const uint32_t dsym = sc.d(didx);
-                        if (dsym > 29) { err = ST_BAD_SYMBOL; st = S_DONE; }
-                        else {
-                            const uint32_t db = dist_base_extra(dsym);
-                            dist = (db & 0xffffu) + b.take(db >> 16);
-                            if (dist > op) { err = ST_BAD_DIST; st = S_DONE; }
-                            else if (mlen > out_len - op) { err = ST_OVERRUN; st = S_DONE; }
-                            else { rem = mlen; src = op - dist; st = S_COPY; }
-                        }
-                    }
-                }
-            }
+            sym_trip<true>(b, ll, dc, sc, out, out_len, last, op, st, err, rem, src, dist);
         } else if (st == S_STORED) {
             // byte-aligned input: 8 bytes a trip
             const uint32_t n = rem < 8u ? rem : 8u;
@@ -228,7 +259,8 @@ VTXI_FN uint32_t inflate_block(const uint8_t* in, uint32_t in_len, uint8_t* out,
             b.refill();
             last = b.take(1) != 0;
             const uint32_t type = b.take(2);
-            if (type == 0) {
+            if (b.starved()) { err = ST_INPUT; st = S_DONE; }
+            else if (type == 0) {
                 b.drop(b.cnt & 7u);                      // to the byte boundary; the whole bytes still buffered go back to the input
                 b.ip -= b.cnt >> 3;
                 b.cnt = 0; b.buf = 0;
@@ -261,13 +293,16 @@ VTXI_FN uint32_t inflate_block(const uint8_t* in, uint32_t in_len, uint8_t* out,
             } else {
                 b.refill();
                 const uint32_t nll = b.take(5) + 257, nd = b.take(5) + 1, ncl = b.take(4) + 4;
-                if (nll > 286 || nd > 30) { err = ST_BAD_CODE; st = S_DONE; }
+                bool starved = b.starved();
+                if (starved) { err = ST_INPUT; st = S_DONE; }
+                else if (nll > 286 || nd > 30) { err = ST_BAD_CODE; st = S_DONE; }
                 else {
                     // the code-length code: 3 bits per symbol in the RFC's order; lengths packed 3 bits per symbol in one word
                     uint64_t cl = 0;
-                    for (uint32_t i = 0; i < ncl; ++i) {
+                    for (uint32_t i = 0; i < ncl && !starved; ++i) {
                         b.refill();
                         const uint32_t v = b.take(3);
+                        starved = b.starved();
                         // order: 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15 (5 bits each, packed in two words)
                         const uint32_t s = i < 12 ? (uint32_t)((0x022caa324e804a30ull >> (5 * i)) & 31u)           // 16 17 18 0 8 7 9 6 10 5 11 4
                                                   : (uint32_t)((0x00000003c2e1346cull >> (5 * (i - 12))) & 31u);   // 12 3 13 2 14 1 15
@@ -277,7 +312,8 @@ VTXI_FN uint32_t inflate_block(const uint8_t* in, uint32_t in_len, uint8_t* out,
                     for (int s = 0; s < 19; ++s) { const int l = (int)((cl >> (3 * s)) & 7u); if (l) sc.at(CUR + l) = (uint16_t)(sc.at(CUR + l) + 1); }
                     Code cc;
                     const int vc = make_code(cc, sc, CUR, 7);
-                    if (vc != 0) { err = ST_BAD_CODE; st = S_DONE; }
+                    if (starved) { err = ST_INPUT; st = S_DONE; }
+                    else if (vc != 0) { err = ST_BAD_CODE; st = S_DONE; }
                     else {
                         for (int s = 0; s < 19; ++s) {
                             const int l = (int)((cl >> (3 * s)) & 7u);
@@ -297,13 +333,15 @@ VTXI_FN uint32_t inflate_block(const uint8_t* in, uint32_t in_len, uint8_t* out,
                                 b.refill();
                                 uint32_t ci, cn;
                                 decode(cc, b.peek15(), ci, cn);
-                                if (ci >= cc.n) { bad = true; break; }
                                 b.drop(cn);
+                                if (ci >= cc.n) { starved = b.starved(); bad = true; break; }
                                 const uint32_t cs = sc.cl(ci);
                                 uint32_t rep = 1, val = cs;
-                                if (cs == 16) { if (k == 0) { bad = true; break; } val = pv; rep = 3 + b.take(2); }
+                                if (cs == 16) { val = pv; rep = 3 + b.take(2); }
                                 else if (cs == 17) { val = 0; rep = 3 + b.take(3); }
                                 else if (cs == 18) { val = 0; rep = 11 + b.take(7); }
+                                if (b.starved()) { starved = bad = true; break; }
+                                if (cs == 16 && k == 0) { bad = true; break; }
                                 if (k + rep > total) { bad = true; break; }
                                 if (val) {
                                     for (uint32_t t = 0; t < rep; ++t) {
@@ -330,7 +368,7 @@ VTXI_FN uint32_t inflate_block(const uint8_t* in, uint32_t in_len, uint8_t* out,
                                 else if (v1 == 1 && !(d_used == 0 || (d_used == 1 && d_one_len == 1))) bad = true;   // RFC 1951 3.2.7
                             }
                         }
-                        if (bad) { err = ST_BAD_CODE; st = S_DONE; }
+                        if (bad) { err = starved ? ST_INPUT : ST_BAD_CODE; st = S_DONE; }
                         else st = S_SYM;
                     }
                 }

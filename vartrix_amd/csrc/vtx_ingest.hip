@@ -106,12 +106,10 @@ __global__ __launch_bounds__(64) void bam_chain_kernel(const uint8_t* __restrict
     const uint32_t base = off ? (i ? off[i - 1] : 0u) : 0u;      // (off: INCLUSIVE scan of the counts)
     bool bad = false;
     while (p < stop) {
-        if (p + 36 > total) { bad = true; break; }
-        const uint32_t bs = ld32(data + p);
-        if (bs < 32 || p + 4 + (uint64_t)bs > total) { bad = true; break; }
-        if (off) rec_upos[base + k] = p;
+        const uint64_t at = p;
+        if (!vtxs::chain_step(data, p, total)) { bad = true; break; }
+        if (off) rec_upos[base + k] = at;
         ++k;
-        p += 4 + (uint64_t)bs;
     }
     if (bad || p != stop) atomicOr(&err[0], VTXG_ERR_CHAIN);
     if (!off) cnt[i] = k;
@@ -141,12 +139,10 @@ __global__ __launch_bounds__(64) void bam_chain_seg_kernel(const uint8_t* __rest
     const uint32_t base = off ? (i ? off[i - 1] : 0u) : 0u;      // (off: INCLUSIVE scan of the counts)
     bool bad = p < S.ubegin || stop > S.ulimit;
     while (!bad && p < stop) {
-        if (p + 36 > S.ulimit) { bad = true; break; }
-        const uint32_t bs = ld32(data + p);
-        if (bs < 32 || p + 4 + (uint64_t)bs > S.ulimit) { bad = true; break; }
-        if (off) rec_upos[base + k] = p;
+        const uint64_t at = p;
+        if (!vtxs::chain_step(data, p, S.ulimit)) { bad = true; break; }
+        if (off) rec_upos[base + k] = at;
         ++k;
-        p += 4 + (uint64_t)bs;
     }
     if (bad || p != stop) atomicOr(&err[0], VTXG_ERR_CHAIN);
     else if (last && !off && !(S.flags & VTX_SEGMENT_TO_EOF)) {

@@ -155,6 +155,18 @@ VTXS_FN RecView view_record(const uint8_t* data, uint64_t p) {
     return v;
 }
 
+// One step of a record-chain walk (bam_chain_kernel, bam_chain_seg_kernel: block_size to block_size from a seed): the record at p
+// must have its block_size and fixed fields (36 bytes) and its whole body inside [.., limit); a block_size below the 32 fixed bytes
+// is no record.  true: p moves behind the record.  false: the chain is broken at p (left as it is).  Reads data[p .. p + 4) only,
+// and only when p + 36 <= limit.
+VTXS_FN bool chain_step(const uint8_t* data, uint64_t& p, uint64_t limit) {
+    if (p + 36 > limit) return false;
+    const uint32_t bs = ld32(data + p);
+    if (bs < 32 || p + 4 + (uint64_t)bs > limit) return false;
+    p += 4 + (uint64_t)bs;
+    return true;
+}
+
 // hi = first interval of the contig with start >= endpos (the loci that can overlap lie below it)
 VTXS_FN uint32_t first_not_below(const int32_t* __restrict__ iv_start, uint32_t lo, uint32_t hi, int64_t endpos) {
     while (lo < hi) {
