@@ -163,9 +163,12 @@ typedef struct vtx_timing {
     float band_ms;         /* band kernels + band-masked DP (banded flavour; part of sw_ms) */
     float band_run_ms;     /* band_run_kernel launches only (seeds, chain, certificate; part of band_ms) */
     uint32_t overflow_tasks; /* banded flavour: alignments handed to the general band kernel        */
-    float diag_ms;         /* band_tables_kernel + band_diag_kernel (single-diagonal stage; part of band_run_ms)   */
+    float diag_ms;         /* band_tables_kernel + band_diag_kernel (single-diagonal stage; part of band_run_ms).  band_tail_kernel is
+                              in here only where it runs behind band_diag_kernel on the same stream; where the stage's two branches run
+                              side by side (the default for haplotypes up to 255 bases) it runs on the side branch and counts in check_ms */
     uint32_t diag_left;    /* alignments the certificate stages left: band_sweep_kernel + masked DP take them       */
-    float check_ms;        /* band-masked DP (and, with VTX_BAND_CHECK, the full-matrix check) of the tasks that left with a certificate */
+    float check_ms;        /* the side branch: band_tail_kernel (see diag_ms), the second look at the tasks that left with a certificate, their
+                              band-masked DP (and, with VTX_BAND_CHECK, the full-matrix check); beside sweep_ms, not in front of it */
     float sweep_ms;        /* band_sweep_kernel + band-masked DP over what is left (part of band_ms)                 */
     uint32_t checked_tasks; /* alignments that left the certificate stages WITH a certificate: one-diagonal band + masked DP */
     uint32_t swept_tasks;  /* alignments handed to band_sweep_kernel                                                 */

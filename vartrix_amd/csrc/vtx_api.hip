@@ -91,8 +91,9 @@ enum EvSlot {
     EV_FULL_END = 3,        // run_full_dp records; run_epilogue reads (full_ms)
     EV_CHUNK_START = 4,     // BandPass::resident_tables records; run_stage reads (diag_ms, band_run_ms of a chunk without a sweep)
     EV_BAND_RUN_END = 5,    // run_stage / second_chance record behind band_run_kernel; run_stage reads (band_run_ms)
-    EV_DIAG_END = 6,        // diag_sweep_path / diag_round3_path record; run_stage reads (diag_ms); the side stream waits for it
-    EV_BRANCH_START = 7,    // diag_sweep_path records on the one-diagonal branch's stream; collect_sweep_times reads (check_ms)
+    EV_DIAG_END = 6,        // diag_sweep_path / diag_round3_path record; run_stage reads (diag_ms); the side stream waits for it (behind band_diag_kernel when
+                            // band_tail_kernel runs on the side stream, else behind band_tail_kernel)
+    EV_BRANCH_START = 7,    // diag_sweep_path records on the one-diagonal branch's stream, in front of band_tail_kernel when that runs there; collect_sweep_times reads (check_ms)
     EV_SWEEP_END = 8,       // diag_sweep_path records after the join; collect_sweep_times waits for it and reads (sweep_ms)
     EV_BRANCH_END = 9,      // diag_sweep_path records on the branch's stream; the main stream joins on it; collect_sweep_times reads
     EV_BAND_RUN_START = 10, // run_stage records in front of band_run_kernel; run_stage reads (band_run_ms of a swept chunk)
@@ -107,6 +108,8 @@ enum PinWord {
     PIN_RUN_LEFT = 8, PIN_DENSE = 9, PIN_REFINE = 10, PIN_TIGHT = 11,   // diag_sweep_path copies VTX_CNT_RUN_LEFT .. VTX_CNT_TIGHT here and reads them
     PIN_R3_REFINE = 9,      // diag_round3_path copies and reads PIN_RUN_LEFT, and VTX_CNT_REFINE here: no dense list on that path, PIN_DENSE's word is free
     PIN_FORK_TIGHT = 12,    // diag_sweep_path copies VTX_CNT_TIGHT on the side stream (forked); collect_sweep_times reads
+    PIN_TAIL = 13,          // diag_sweep_path copies VTX_CNT_TAIL here (band_tail_kernel on the side stream) and reads it: what that kernel may still append
+    PIN_FORK_REFINE = 17,   // diag_sweep_path copies VTX_CNT_REFINE on the side stream (band_tail_kernel there); collect_sweep_times reads
     PIN_DIAG2_LEFT = 14, PIN_DIAG2_TIGHT = 15,                          // second_stage copies VTX_CNT_DIAG2_LEFT, _TIGHT here and reads both
     PIN_STREAMED = 16,      // second_stage copies VTX_CNT_STREAMED here and reads it
     PIN_WORDS = 64
@@ -1618,6 +1621,7 @@ struct BandKnobs {
     uint32_t dense_mask = env_u32(VTX_DEV_ENV("VTX_BAND_DENSE_MASK"), 0, 1u << 4);   // experiment knob (0x3be: everything but shape; 0: nothing — band_run_kernel sees every task first)
     bool no_refine = VTX_DEV_ENV("VTX_BAND_NO_REFINE") != nullptr;              // experiment / test hook
     bool no_fork = VTX_DEV_ENV("VTX_BAND_NO_FORK") != nullptr;                  // experiment / test hook
+    bool tail_inline = VTX_DEV_ENV("VTX_BAND_TAIL_INLINE") != nullptr;          // A/B hook: band_tail_kernel behind band_diag_kernel on the main stream in fork mode too
     bool no_corridor = VTX_DEV_ENV("VTX_BAND_NO_CORRIDOR") != nullptr;          // round 3's band_refine_kernel instead of band_corridor_kernel
     uint32_t run_min = env_u32(VTX_DEV_ENV("VTX_BAND_RUN_MIN"), 10, 65536u);    // the shortest list worth band_run_kernel's launch (see repeats)
     bool no_split = VTX_DEV_ENV("VTX_BAND_NO_SPLIT") != nullptr;                // test hook: the single pass of rounds 3 - 5
@@ -1670,9 +1674,9 @@ inline hipError_t launch_band_run(const TaskArrays& a, uint32_t n, uint32_t task
             gtables, gt_bytes, task_list, long_lists, s); }
 inline hipError_t launch_band_diag(const TaskArrays& a, uint32_t n, uint32_t task_base, uint32_t mh, uint32_t mh_min, uint32_t* fail_list, uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus,
         uint32_t gt_l0, uint32_t gt_n, uint8_t* gtables, size_t gt_bytes, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, uint32_t* tail_rec,
-        uint32_t tail_cap, hipStream_t s) {
+        uint32_t tail_cap, bool tail_inline, hipStream_t s) {
     return vtxk_launch_band_diag(n, task_base, a.records, a.rec_locus, a.loci, a.read, a.hap, mh, mh_min, a.ref, a.alt, fail_list, refine_rec, refine_cap, counters, tasks_per_locus, gt_l0, gt_n, gtables, gt_bytes, stats, tight_list,
-            tight_pack, stage, dense_list, dense_mask, max_read, tail_rec, tail_cap, s); }
+            tight_pack, stage, dense_list, dense_mask, max_read, tail_rec, tail_cap, tail_inline ? 1 : 0, s); }
 inline hipError_t launch_band_refine(const TaskArrays& a, const uint32_t* recs, uint32_t n, uint32_t mh, uint32_t* fail_list, uint32_t* counters, uint32_t tasks_per_locus, uint32_t gt_l0, const uint8_t* gtables, int stats,
         uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, const uint32_t* n_dev, hipStream_t s) {
     return vtxk_launch_band_refine(recs, n, a.records, a.rec_locus, a.loci, a.read, mh, a.ref, a.alt, fail_list, counters, tasks_per_locus, gt_l0, gtables, stats, tight_list, tight_pack, stage, n_dev, s); }
@@ -1712,9 +1716,11 @@ struct BandPass {
     bool sweep_used = false;                    // some chunk took the round-4 path
     bool sweep_pending = false;                 // the events of a swept chunk have not been read yet
     bool sweep_forked = false;                  // ... and that chunk ran its two branches side by side
+    bool sweep_tail_side = false;               // ... with band_tail_kernel on the side one
     uint32_t fork_nt = 0;
     // one chunk of tasks [base, base + nt): the loci whose tables are resident, and what band_diag_kernel left for band_run_kernel
-    struct Chunk { uint64_t base; uint32_t nt; bool last; uint32_t gt_l0 = 0, gt_n = 0; bool diag = false, swept = false; uint32_t n_fail = 0; const uint32_t* fail_list = nullptr; };
+    struct Chunk { uint64_t base; uint32_t nt; bool last; uint32_t gt_l0 = 0, gt_n = 0; bool diag = false, swept = false; uint32_t n_fail = 0; const uint32_t* fail_list = nullptr;
+                   uint32_t tail_cap = 0; bool tail_side = false; };    // band_tail_kernel's record buffer; whether diag_sweep_path launches that kernel on the side stream
     BandPass(vtx_ctx* c_, RunState& rs_, uint32_t mh_, uint32_t mh_min_, uint64_t t_begin_, uint64_t t_end_, bool chunk_tables_) : c(c_), rs(rs_), mh(mh_), mh_min(mh_min_), t_begin(t_begin_), t_end(t_end_),
              chunk_tables(chunk_tables_) {}
     int run() {
@@ -1737,7 +1743,7 @@ struct BandPass {
         tight_pack = tight_list ? c->d_tight_pack.as<uint32_t>() : nullptr;
         // dense list: the tasks whose vtxf::Why is in kn.dense_mask (default W_MATCHES: repeats) skip band_run_kernel and take band_sweep_kernel at once
         dense_list = sweep_path ? c->d_dense.as<uint32_t>() : nullptr;
-        refine_cap = band_refine_cap(bp.chunk);
+        refine_cap = std::min(band_refine_cap(bp.chunk), env_u32(VTX_DEV_ENV("VTX_DIAG_REFINE_CAP"), 10, 0xffffffffu));   // (test hook: a small record buffer, read per run)
         refine_list = kn.no_refine ? nullptr : c->d_refine.as<uint32_t>();
         HIP_TRY(c, hipMemsetAsync(d_cnt, 0, VTX_CNT_WORDS * sizeof(uint32_t), s));
         for (uint64_t base = t_begin; base < t_end; base += bp.chunk) {
@@ -1877,12 +1883,13 @@ struct BandPass {
         sweep_pending = false;
         HIP_TRY(c, hipEventSynchronize(c->ev[EV_SWEEP_END]));
         float ms = 0;
-        // BRANCH_START .. BRANCH_END: band_refine_kernel (forked only) + the one-diagonal bands' masked DP; then band_sweep_kernel + its
+        // BRANCH_START .. BRANCH_END: band_tail_kernel (when it runs on the side stream) + band_refine_kernel (forked only) + the one-diagonal bands' masked DP; then band_sweep_kernel + its
         // masked DP (the chunk's repeats) — forked: FORK_START .. SWEEP_END on the main stream, BESIDE the first interval, not after it
         HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_BRANCH_START], c->ev[EV_BRANCH_END])); check_ms += ms;
         HIP_TRY(c, hipEventElapsedTime(&ms, sweep_forked ? c->ev[EV_FORK_START] : c->ev[EV_BRANCH_END], c->ev[EV_SWEEP_END])); sweep_ms += ms;
         if (sweep_forked) checked_total += std::min(c->h_pin[PIN_FORK_TIGHT], fork_nt);          // (copied before BRANCH_END, which SWEEP_END waited for)
-        sweep_forked = false;
+        if (sweep_tail_side) refined_total += std::min(c->h_pin[PIN_FORK_REFINE], refine_cap);   // (likewise; band_tail_kernel's records included)
+        sweep_forked = false; sweep_tail_side = false;
         return VTX_OK;
     }
     // Sorts list[0, n) by task into `sorted` when it has more than 64 entries and the temporary buffer can be had; *at = where the list then is.  (Lists come out in the order the wavefronts
@@ -1922,8 +1929,11 @@ struct BandPass {
         HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_RUN_LEFT, 0, 4 * sizeof(uint32_t), s));   // RUN_LEFT, DENSE, REFINE, TIGHT
         const uint32_t tail_cap = (uint32_t)std::min<size_t>(band_tail_cap(bp.chunk), c->d_tail.cap / (vtxk_band_tail_words() * sizeof(uint32_t)));
         const uint32_t tail_cap_hook = VTX_DEV_ENV("VTX_DIAG_TAIL_CAP") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_TAIL_CAP")) : 0xffffffffu;   // test hook: a small buffer (read per run)
+        ch.tail_cap = std::min(tail_cap, tail_cap_hook);
+        // The sweep path with its two branches: band_tail_kernel goes to the side one (diag_sweep_path).  Every other path keeps it behind band_diag_kernel on this stream.
+        ch.tail_side = sweep_path && fork_on() && !kn.tail_inline && vtxk_band_tail_on(c->d_tail.as<uint32_t>(), ch.tail_cap);
         const hipError_t e = launch_band_diag(a, ch.nt, (uint32_t)ch.base, mh, mh_min, c->d_fail.as<uint32_t>(), refine_list, refine_cap, d_cnt, bp.tasks_per_locus, ch.gt_l0, ch.gt_n, c->d_gtables.as<uint8_t>(), bp.gt_bytes,
-                                              kn.diag_stats, tight_list, tight_pack, rs.stage, dense_list, kn.dense_mask, c->max_read_len, c->d_tail.as<uint32_t>(), std::min(tail_cap, tail_cap_hook), s);
+                                              kn.diag_stats, tight_list, tight_pack, rs.stage, dense_list, kn.dense_mask, c->max_read_len, c->d_tail.as<uint32_t>(), ch.tail_cap, !ch.tail_side, s);
         if (e != hipSuccess) {
             // (the tables do not fit the buffer for this chunk: band_run_kernel alone, tables in LDS)
             if (getenv("VTX_DEBUG")) fprintf(stderr, "[vtx] band_diag_kernel not launched for tasks [%llu, +%u): %s\n", (unsigned long long)ch.base, ch.nt, hipGetErrorString(e));
@@ -1937,27 +1947,46 @@ struct BandPass {
         if (tight_list && !kn.no_corridor) return launch_band_corridor(a, refine_list, n_rec, d_cnt, kn.diag_stats, tight_list, tight_pack, rs.stage, d_cnt + VTX_CNT_REFINE, st);
         return launch_band_refine(a, refine_list, n_rec, mh, c->d_fail.as<uint32_t>(), d_cnt, bp.tasks_per_locus, ch.gt_l0, c->d_gtables.as<uint8_t>(), kn.diag_stats, tight_list, tight_pack, rs.stage, d_cnt + VTX_CNT_REFINE, st);
     }
-    // What the stage left, in two branches over disjoint tasks: side stream — band_refine_kernel / band_corridor_kernel over its records, then the masked DP over the
+    // What the stage left, in two branches over disjoint tasks: side stream — band_tail_kernel (tail_on_side), band_refine_kernel / band_corridor_kernel over its records, then the masked DP over the
     // one-diagonal bands; this stream — band_sweep_kernel + masked DP over the repeats and the short fail list.  One host round trip, right after band_diag_kernel.  (VTX_BAND_NO_TIGHT: the
     // refinement's leftovers go to the fail list, so everything stays in order on this stream.)
+    // (the two branches: a tight list to feed the side one, and no VTX_BAND_NO_FORK)
+    bool fork_on() const { return tight_list != nullptr && !kn.no_fork; }
+    // band_tail_kernel on the side stream, behind band_diag_kernel (EV_DIAG_END) and beside everything the main stream does from there on.  A task deferred to it passed back_harmless,
+    // so with a tight list it ends decided, as a refine / corridor record or as a tight entry (vtx_band.hip: band_tail_kernel): VTX_CNT_RUN_LEFT and VTX_CNT_DENSE, which the main branch
+    // starts from, are final when band_diag_kernel ends, and the side branch reads its own two counts on the device.  The kernel gets no fail_list and no dense_list: those are the main
+    // branch's.  d_tail is free again at EV_BRANCH_END, which the main stream joins before the next chunk.
+    int tail_on_side(const Chunk& ch) {
+        HIP_TRY(c, hipStreamWaitEvent(s2, c->ev[EV_DIAG_END], 0));
+        HIP_TRY(c, hipEventRecord(c->ev[EV_BRANCH_START], s2));
+        HIP_TRY(c, vtxk_launch_band_tail(mh, c->max_read_len, a.ref, a.alt, nullptr, refine_list, refine_cap, d_cnt, bp.tasks_per_locus, kn.diag_stats, tight_list, tight_pack, rs.stage, nullptr,
+                                         kn.dense_mask, c->d_tail.as<uint32_t>(), ch.tail_cap, 1, s2));
+        return VTX_OK;
+    }
     int diag_sweep_path(Chunk& ch) {
         ch.diag = true; ch.swept = true; sweep_used = true;
         HIP_TRY(c, hipEventRecord(c->ev[EV_DIAG_END], s));
-        const bool fork = tight_list != nullptr && !kn.no_fork;
+        const bool fork = fork_on();
         hipStream_t sb = fork ? s2 : s;                                             // the refine / one-diagonal branch
+        if (ch.tail_side) { if (int rc = tail_on_side(ch)) return rc; }             // (before the host waits: it starts while band_diag_kernel drains)
         if (!fork && refine_list) HIP_TRY(c, second_look(ch, std::min(refine_cap, ch.nt), s));
         HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_RUN_LEFT, d_cnt + VTX_CNT_RUN_LEFT, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // RUN_LEFT, DENSE, REFINE, TIGHT
+        if (ch.tail_side) HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_TAIL, d_cnt + VTX_CNT_TAIL, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        const uint32_t n_refine = std::min(c->h_pin[PIN_REFINE], refine_cap);
+        // band_tail_kernel on the side stream: REFINE and TIGHT are what that kernel had appended when the copy ran, and every one of its n_tail records may still become a record for the
+        // second look or, that buffer full, a tight entry.  These two are BOUNDS for the grids; the kernels read the final counts on the device, the figures of vtx_timing arrive with the events.
+        const uint32_t n_tail = ch.tail_side ? std::min(c->h_pin[PIN_TAIL], ch.tail_cap) : 0u;
+        const uint32_t n_refine = (uint32_t)std::min<uint64_t>((uint64_t)c->h_pin[PIN_REFINE] + n_tail, refine_cap);
         // (forked: the tight list still grows by what the refinement leaves — at most its records)
-        const uint32_t n_tight = (uint32_t)std::min<uint64_t>((uint64_t)c->h_pin[PIN_TIGHT] + (fork && refine_list ? n_refine : 0u), ch.nt);
-        refined_total += n_refine;
+        const uint32_t n_tight = (uint32_t)std::min<uint64_t>((uint64_t)c->h_pin[PIN_TIGHT] + (fork && refine_list ? n_refine : 0u) + n_tail, ch.nt);
+        if (!ch.tail_side) refined_total += n_refine;                               // (else: collect_sweep_times)
         rs.launches += 2;
-        if (fork) HIP_TRY(c, hipStreamWaitEvent(s2, c->ev[EV_DIAG_END], 0));
-        HIP_TRY(c, hipEventRecord(c->ev[EV_BRANCH_START], sb));
+        if (fork && !ch.tail_side) HIP_TRY(c, hipStreamWaitEvent(s2, c->ev[EV_DIAG_END], 0));
+        if (!ch.tail_side) HIP_TRY(c, hipEventRecord(c->ev[EV_BRANCH_START], sb));
         if (fork && refine_list && n_refine) HIP_TRY(c, second_look(ch, n_refine, sb));
         if (n_tight) { if (int rc = one_diagonal_dp(n_tight, fork, sb)) return rc; }
         if (fork) HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_FORK_TIGHT, d_cnt + VTX_CNT_TIGHT, sizeof(uint32_t), hipMemcpyDeviceToHost, sb));   // the list's final length (read in collect_sweep_times)
+        if (ch.tail_side) HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_FORK_REFINE, d_cnt + VTX_CNT_REFINE, sizeof(uint32_t), hipMemcpyDeviceToHost, sb));   // ... and the records' final count
         HIP_TRY(c, hipEventRecord(c->ev[EV_BRANCH_END], sb));
         if (fork) HIP_TRY(c, hipEventRecord(c->ev[EV_FORK_START], s));                          // (this stream's branch starts here)
         ch.n_fail = c->h_pin[PIN_RUN_LEFT];
@@ -1970,7 +1999,7 @@ struct BandPass {
         if (int rc = sort_by_task(c->d_fail.as<uint32_t>(), c->d_fail.as<uint32_t>() + ch.nt, ch.n_fail, &ch.fail_list)) return rc;
         if (fork) HIP_TRY(c, hipStreamWaitEvent(s, c->ev[EV_BRANCH_END], 0));                    // join: what follows reads every score
         HIP_TRY(c, hipEventRecord(c->ev[EV_SWEEP_END], s));
-        sweep_pending = true; sweep_forked = fork; fork_nt = ch.nt;
+        sweep_pending = true; sweep_forked = fork; sweep_tail_side = ch.tail_side; fork_nt = ch.nt;
         return VTX_OK;
     }
     // tasks with a certificate but no verdict: their band is one diagonal stretch (tight_pack): the masked DP expands it itself.  (VTX_BAND_CHECK=1: the full-matrix check first — full == cert
@@ -2164,6 +2193,7 @@ struct BandPass {
             fprintf(stderr, "[vtx] band_refine_kernel: %llu tasks listed\n", (unsigned long long)refined_total);
             fprintf(stderr, "[vtx] band_diag_kernel: %llu of %llu tasks left to band_run_kernel (%.2f %%), %.2f ms: shape=%u no-diagonal=%u pieces=%u matches=%u not-harmless=%u generic=%u not-tight=%u no-main=%u\n",
                     (unsigned long long)diag_left, (unsigned long long)diag_total, 100.0 * (double)diag_left / (double)diag_total, (double)diag_ms, why[1], why[2], why[3], why[4], why[5], why[7], why[8], why[9]);
+            if (VTX_DEVTOOLS_ON) fprintf(stderr, "[vtx] band_tail_kernel: %u records routed towards the dense or fail list beside a tight list\n", why[VTX_CNT_TAIL_STRAY - VTX_CNT_DIAG_WHY]);
         }
         if (getenv("VTX_DEBUG") && diag2_total) fprintf(stderr, "[vtx] band_diag2_kernel: %llu tasks looked at, %llu scored, %llu left with a one-diagonal band, %llu to band_sweep_kernel (%llu through band_stream_kernel)\n",
             (unsigned long long)diag2_total, (unsigned long long)diag2_scored, (unsigned long long)tight2_total, (unsigned long long)(diag2_total - diag2_scored - tight2_total), (unsigned long long)stream_total);

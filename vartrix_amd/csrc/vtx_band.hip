@@ -2702,7 +2702,9 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
 // band_tail_kernel — the rest of the last phase for the tasks band_diag_kernel deferred: those whose closure must take an off-diagonal
 // piece into the generic set (7.4 % of the headline's tasks).  One lane per record, over the device's record count (counters[VTX_CNT_TAIL]); the
 // record goes back into band_diag_kernel's LDS layout and the same vtxf::back_rest runs on it, then the same routing (diag_route):
-// every task ends with the score, stage and lists it had when decided in its wavefront.  Launched with up to 65 536 one-wavefront
+// every task ends with the score, stage and lists it had when decided in its wavefront.  With a tight list an undecided task holds its
+// certificate (it passed back_harmless before it was deferred): diag_route sends it to refine_rec or tight_list, never to dense_list or
+// fail_list, so the sweep path launches the kernel on its side branch, beside the sweep (vtx_api.hip: diag_sweep_path).  Launched with up to 65 536 one-wavefront
 // workgroups: a wavefront that finishes early makes room for the next (4 608 resident ones looping over the records: 0.87 ms, 0.68 ms
 // so; without back_rest the kernel takes 67 us — its time is the rare path's own work).
 // 60 - 62 VGPRs and no probe queue (band_diag_kernel: 128): LDS — the lane's words and the GM generic piece words, 8.7 KB a wavefront —
@@ -2760,6 +2762,9 @@ __global__ __launch_bounds__(64) void band_tail_kernel(
             task = rec[0]; pack = rec[(size_t)tail_cap]; w2 = rec[2 * (size_t)tail_cap]; out = rec[3 * (size_t)tail_cap];
         }
         const bool fail = !(out & TAIL_DECIDED), tight = (out & TAIL_TIGHT) != 0;
+        // (libvtx_dev.so: with a tight list every undecided record carries TAIL_TIGHT, so the routing below ends at refine_rec or
+        // tight_list — what lets this kernel run beside the readers of dense_list / fail_list.  A record that would take either: counted.)
+        if (VTX_DEVTOOLS_ON && tight_list && fail && !tight) atomicAdd(&counters[VTX_CNT_TAIL_STRAY], 1u);
         if (fail && tight) {
             const uint32_t* rec = tail_rec + p;
 #pragma unroll
@@ -3063,6 +3068,71 @@ extern "C" hipError_t vtxk_launch_band_run(uint32_t n_tasks, uint32_t task_base,
     return hipGetLastError();
 }
 
+// What band_diag_kernel and band_tail_kernel must agree on, whoever launches the latter: the template choice and the stats word.
+// two-byte match entries (40 per task) whenever a haplotype position fits a byte; VTX_DIAG_WIDE=1 forces the four-byte variant (tests)
+static bool diag_narrow(uint32_t max_hap) {
+    static const bool force_wide = VTX_DEV_ENV("VTX_DIAG_WIDE") != nullptr;
+    return max_hap <= 255 && !force_wide;
+}
+static bool diag_three_words(uint32_t max_read) {
+    static const bool force_four = VTX_DEV_ENV("VTX_DIAG_FOUR_WORDS") != nullptr;      // (tests: the four-word build on short reads)
+    return max_read <= 192 && !force_four && vtxf::NW >= 3;
+}
+static uint32_t diag_stats_word(int stats, uint32_t tasks_per_locus) {
+    return (uint32_t)stats | (VTX_DEV_ENV("VTX_DIAG_ABLATE") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_ABLATE")) << 8 : 0u) |
+           (VTX_DEV_ENV("VTX_BAND_NO_CORRIDOR") ? 0x10000u : 0u) |         // (A/B hook: round 5's records for band_refine_kernel)
+           (VTX_DEV_ENV("VTX_DIAG_NO_TWINS") ? 0x20000u : 0u) |            // (A/B hook: every row that is not intact and unique is probed, the twin lists unused)
+           (VTX_DEV_ENV("VTX_DIAG_PHASES") ? 0x80000u : 0u) |
+           (band_use_t3(tasks_per_locus) ? 0u : 0x40000u);                 // (a queue entry and a presence-bitmap word per row instead of t3[] and blocks of three rows)
+}
+// Whether band_diag_kernel leaves records for band_tail_kernel at all: a buffer with room, and (libvtx_dev.so) neither VTX_DIAG_NO_TAIL=1
+// nor the profiling aids of VTX_DIAG_ABLATE, which keep every task in its wavefront, the path of rounds 3 - 6.  The one place that decides
+// it: vtxk_launch_band_diag asks, and so does a caller that launches the tail itself.
+extern "C" int vtxk_band_tail_on(const uint32_t* tail_rec, uint32_t tail_cap) {
+    return tail_rec != nullptr && tail_cap != 0 && !VTX_DEV_ENV("VTX_DIAG_NO_TAIL") && !VTX_DEV_ENV("VTX_DIAG_ABLATE");
+}
+// band_tail_kernel over the records a vtxk_launch_band_diag with the same arguments (n_tasks > 0, hipSuccess, vtxk_band_tail_on) left in
+// tail_rec; s runs behind that band_diag_kernel.  The lists are diag_route's: a caller that runs the kernel beside the readers of
+// fail_list / dense_list passes nullptr for both — with a tight list no record is routed to either (see band_tail_kernel).
+// resident_grid != 0 (the kernel runs beside others): no more workgroups than the device holds at once, each looping over its share
+// of the records.  With the 65 536 of the launch that has the device to itself a workgroup that ends hands its 8.7 KB of LDS to the
+// next one of this kernel, and a neighbour's workgroup (band_sweep_kernel: 19.1 KB in one piece) finds no room until the last record
+// is taken (DESIGN.md 4.3.7 has the measurement).
+template <class ST, int A>
+static uint32_t tail_resident_grid() {
+    static const uint32_t n = [] {
+        int dev = 0, cus = 0, per_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, band_tail_kernel<ST, A>, 64, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
+            (void)hipGetLastError();
+            return 65536u;
+        }
+        return (uint32_t)cus * (uint32_t)per_cu;
+    }();
+    return n;
+}
+extern "C" hipError_t vtxk_launch_band_tail(uint32_t max_hap, uint32_t max_read, int32_t* ref_score, int32_t* alt_score, uint32_t* fail_list,
+                                            uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, int stats,
+                                            uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask,
+                                            uint32_t* tail_rec, uint32_t tail_cap, int resident_grid, hipStream_t s) {
+    if (!vtxk_band_tail_on(tail_rec, tail_cap)) return hipErrorInvalidValue;
+    if (!tight_list && !fail_list) return hipErrorInvalidValue;            // (without a tight list the undecided records go to fail_list)
+    const uint32_t st = diag_stats_word(stats, tasks_per_locus);
+    // (libvtx_dev.so, VTX_DIAG_TAIL_GRID: a small grid, so that a test's few thousand records make every lane loop)
+    const uint32_t grid_hook = VTX_DEV_ENV("VTX_DIAG_TAIL_GRID") ? std::max(1u, (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_TAIL_GRID"))) : 65536u;
+#define LAUNCH_TAIL(STV, AV)                                                                                                              \
+    hipLaunchKernelGGL((band_tail_kernel<STV, AV>),                                                                                         \
+                       dim3(std::min({(tail_cap + 63u) / 64u, 65536u, grid_hook, resident_grid ? tail_resident_grid<STV, AV>() : 65536u})), \
+                       dim3(64), 0, s, tail_rec, tail_cap,                                                                                  \
+                       counters + VTX_CNT_TAIL, ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list,          \
+                       tight_pack, stage, dense_list, dense_mask)
+    const bool three = diag_three_words(max_read);
+    if (diag_narrow(max_hap)) { if (three) LAUNCH_TAIL(uint16_t, 3); else LAUNCH_TAIL(uint16_t, vtxf::NW); }
+    else { if (three) LAUNCH_TAIL(uint32_t, 3); else LAUNCH_TAIL(uint32_t, vtxf::NW); }
+#undef LAUNCH_TAIL
+    return hipGetLastError();
+}
+
 // Tables of loci [gt_l0, gt_l0 + n_loci) into gtables (the same layout and bucket count vtxk_launch_band_run picks for this
 // shape of data), then band_diag_kernel over tasks [task_base, task_base + n_tasks).  Returns hipErrorInvalidValue when the
 // tables do not fit the buffer (the caller then runs band_run_kernel alone, which falls back to tables in LDS).
@@ -3073,44 +3143,34 @@ extern "C" hipError_t vtxk_launch_band_diag(uint32_t n_tasks, uint32_t task_base
                                             uint32_t tasks_per_locus, uint32_t gt_l0, uint32_t n_loci, uint8_t* gtables,
                                             size_t gtables_bytes, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage,
                                             uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, uint32_t* tail_rec, uint32_t tail_cap,
-                                            hipStream_t s) {
+                                            int tail_inline, hipStream_t s) {
     // max_read: the longest read of the batch (the fast kernels' records) — up to 192 bases the kernel is built with three mask words
-    // tail_rec != nullptr: room for tail_cap records of band_tail_kernel (TAIL_WORDS words each, word-major), launched here behind
-    // band_diag_kernel on the same stream; counters[VTX_CNT_TAIL] counts them.  (libvtx_dev.so: VTX_DIAG_NO_TAIL=1 — and the profiling aids of
-    // VTX_DIAG_ABLATE — keep every task in its wavefront, the path of rounds 3 - 6.)
+    // tail_rec != nullptr: room for tail_cap records of band_tail_kernel (TAIL_WORDS words each, word-major); counters[VTX_CNT_TAIL]
+    // counts them.  tail_inline != 0: band_tail_kernel is launched here, behind band_diag_kernel on the same stream; 0: the caller
+    // launches it (vtxk_launch_band_tail, when vtxk_band_tail_on says the records exist) on a stream that waits for this one.
     if (!n_tasks) return hipSuccess;
-    if (VTX_DEV_ENV("VTX_DIAG_NO_TAIL") || VTX_DEV_ENV("VTX_DIAG_ABLATE") || !tail_cap) tail_rec = nullptr;
+    if (!vtxk_band_tail_on(tail_rec, tail_cap)) tail_rec = nullptr;
     const uint32_t n_heads = pick_heads(tasks_per_locus, true);
     const size_t tstride = band_table_stride(max_hap, n_heads);
     if (!gtables || (size_t)n_loci * 2 * tstride > gtables_bytes) return hipErrorInvalidValue;
     const bool use_t3 = band_use_t3(tasks_per_locus);
     launch_band_tables(loci, gt_l0, n_loci, hap_arena, max_hap, min_hap, tstride, n_heads, gtables, use_t3, s);
     const uint32_t n_blocks = (n_tasks + 255) / 256;
-    const uint32_t st = (uint32_t)stats | (VTX_DEV_ENV("VTX_DIAG_ABLATE") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_ABLATE")) << 8 : 0u) |
-                        (VTX_DEV_ENV("VTX_BAND_NO_CORRIDOR") ? 0x10000u : 0u) |         // (A/B hook: round 5's records for band_refine_kernel)
-                        (VTX_DEV_ENV("VTX_DIAG_NO_TWINS") ? 0x20000u : 0u) |            // (A/B hook: every row that is not intact and unique is probed, the twin lists unused)
-                        (VTX_DEV_ENV("VTX_DIAG_PHASES") ? 0x80000u : 0u) |
-                        (use_t3 ? 0u : 0x40000u);                                       // (a queue entry and a presence-bitmap word per row instead of t3[] and blocks of three rows)
-    // two-byte match entries (40 per task) whenever a haplotype position fits a byte; VTX_DIAG_WIDE=1 forces the four-byte variant (tests)
-    static const bool force_wide = VTX_DEV_ENV("VTX_DIAG_WIDE") != nullptr;
-    static const bool force_four = VTX_DEV_ENV("VTX_DIAG_FOUR_WORDS") != nullptr;      // (tests: the four-word build on short reads)
+    const uint32_t st = diag_stats_word(stats, tasks_per_locus);
 #define LAUNCH_DIAG(STV, AV)                                                                                                              \
-    do {                                                                                                                                  \
-        hipLaunchKernelGGL((band_diag_kernel<4, STV, AV>), dim3(((n_blocks + 7) / 8) * 8), dim3(256), 0, s, n_tasks, task_base, n_blocks,   \
-                           records, rec_locus, loci, read_arena, max_hap, (uint32_t)tstride, n_heads, (const uint8_t*)gtables, gt_l0,       \
-                           ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list, tight_pack, stage, dense_list, \
-                           dense_mask, min_hap, tail_rec, tail_cap);                                                                      \
-        if (tail_rec)                                                                                                                     \
-            hipLaunchKernelGGL((band_tail_kernel<STV, AV>), dim3(std::min((tail_cap + 63u) / 64u, 65536u)), dim3(64), 0, s, tail_rec,  \
-                               tail_cap, counters + VTX_CNT_TAIL, ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list, \
-                               tight_pack, stage, dense_list, dense_mask);                                                                \
-    } while (0)
+    hipLaunchKernelGGL((band_diag_kernel<4, STV, AV>), dim3(((n_blocks + 7) / 8) * 8), dim3(256), 0, s, n_tasks, task_base, n_blocks,       \
+                       records, rec_locus, loci, read_arena, max_hap, (uint32_t)tstride, n_heads, (const uint8_t*)gtables, gt_l0,           \
+                       ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list, tight_pack, stage, dense_list,     \
+                       dense_mask, min_hap, tail_rec, tail_cap)
     if (tail_rec) { const hipError_t e = hipMemsetAsync(counters + VTX_CNT_TAIL, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
-    const bool three = max_read <= 192 && !force_four && vtxf::NW >= 3;
-    if (max_hap <= 255 && !force_wide) { if (three) LAUNCH_DIAG(uint16_t, 3); else LAUNCH_DIAG(uint16_t, vtxf::NW); }
+    const bool three = diag_three_words(max_read);
+    if (diag_narrow(max_hap)) { if (three) LAUNCH_DIAG(uint16_t, 3); else LAUNCH_DIAG(uint16_t, vtxf::NW); }
     else { if (three) LAUNCH_DIAG(uint32_t, 3); else LAUNCH_DIAG(uint32_t, vtxf::NW); }
 #undef LAUNCH_DIAG
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !tail_rec || !tail_inline) return e;
+    return vtxk_launch_band_tail(max_hap, max_read, ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, tasks_per_locus, stats, tight_list,
+                                 tight_pack, stage, dense_list, dense_mask, tail_rec, tail_cap, 0, s);
 }
 
 // band_refine_kernel over n_recs records of REFINE_WORDS words: the tables are the ones vtxk_launch_band_diag built

@@ -70,9 +70,10 @@ enum VtxBandCnt {
     VTX_CNT_SWEEP2_DECLINED = 29,
     VTX_CNT_DIAG2_LEFT = 30,      // band_diag2_kernel / band_stream_kernel: tasks left for the sweep ...
     VTX_CNT_DIAG2_TIGHT = 31,     //   ... and with a one-diagonal band (both zeroed per call of the second stage)
-    VTX_CNT_DIAG_WHY = 32,        // [32, 48): band_diag_kernel's reasons, by vtxf::Why (statistics); two words past W_COUNT are in use:
+    VTX_CNT_DIAG_WHY = 32,        // [32, 48): band_diag_kernel's reasons, by vtxf::Why (statistics); three words past W_COUNT are in use:
     VTX_CNT_DIAG_DUMMY = 40,      //   where band_diag_kernel's profiling aids leave their dummy store (W_NOT_TIGHT's word: results are wrong anyway)
     VTX_CNT_TAIL = 44,            //   records band_diag_kernel leaves for band_tail_kernel (zeroed per launch)
+    VTX_CNT_TAIL_STRAY = 45,      //   libvtx_dev.so: records band_tail_kernel routed towards dense_list / fail_list although a tight list exists (must stay 0)
     VTX_CNT_STREAMED = 48,        // band_diag2_kernel: tasks handed to band_stream_kernel (zeroed per call of the second stage)
     VTX_CNT_SWEEP_WHY = 56,       // [56, 64): band_sweep_kernel's reasons (statistics)
     VTX_CNT_SLOW = 13,            // slow_align_kernel: tasks to retry.  Aliases VTX_CNT_DENSE: the slow path runs after the banded stage
@@ -119,7 +120,12 @@ hipError_t vtxk_launch_band_diag(uint32_t n_tasks, uint32_t task_base, const vtx
                                  uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, uint32_t gt_l0, uint32_t n_loci,
                                  uint8_t* gtables, size_t gtables_bytes, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage,
                                  uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, uint32_t* tail_rec, uint32_t tail_cap,
-                                 hipStream_t s);
+                                 int tail_inline, hipStream_t s);
+int vtxk_band_tail_on(const uint32_t* tail_rec, uint32_t tail_cap);
+hipError_t vtxk_launch_band_tail(uint32_t max_hap, uint32_t max_read, int32_t* ref_score, int32_t* alt_score, uint32_t* fail_list,
+                                 uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, int stats,
+                                 uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask,
+                                 uint32_t* tail_rec, uint32_t tail_cap, int resident_grid, hipStream_t s);
 uint32_t vtxk_band_refine_words(void);
 uint32_t vtxk_band_tail_words(void);
 hipError_t vtxk_launch_band_corridor(const uint32_t* recs, uint32_t n_recs, const vtx_record* records, const uint32_t* rec_locus,
