@@ -483,6 +483,58 @@ int vtx_mtx_join(const char* path, uint32_t n_rows, uint32_t n_cols, int gz, con
  * arrays resident in HBM) — the payload of the multi-GPU row gather.          */
 int vtx_device_coo(vtx_ctx* ctx, vtx_coo* out);
 
+/* ---- the matrices as CSR on the device (vartrix_amd/csrc/vtx_csr.hip) --------------------------------------------------------------
+ * The triplets of a run are in merge-loop order (row ascending, column ascending inside a row), so they ARE a variant-major CSR but
+ * for the row offsets: `indices` is vtx_coo.col and every data array is the vtx_coo array of the same name — the same addresses
+ * vtx_device_coo reports, nothing is copied.  Only `indptr` is new: indptr[r - row_begin], r in [row_begin, row_end], is the offset of
+ * the first triplet whose row is >= r, so a row without triplets (a skipped record, a locus no read reached, the empty stretches at
+ * the ends of the window) has an empty range.                                                                                        */
+typedef struct vtx_csr {
+    const uint64_t* indptr;      /* row_end - row_begin + 1 offsets into the arrays below */
+    const uint32_t* indices;     /* == vtx_coo.col */
+    const uint32_t *alt, *ref, *unk;
+    const double *value, *ref_value;
+    uint64_t nnz;
+    uint32_t row_begin, row_end, n_cols, reserved;   /* n_cols = cfg.n_barcodes */
+} vtx_csr;
+
+/* Variant-major CSR of the last vtx_run's triplets over the rows [row_begin, row_end); DEVICE pointers.  VTX_E_STATE before a
+ * completed vtx_run; VTX_E_INVAL for row_begin > row_end or when a triplet's row lies outside the window (the window must hold every
+ * triplet of the run: the arrays are the run's, not a slice of them).  A run without triplets: nnz = 0 and indptr all zero.
+ * Lifetime: the data arrays live as vtx_device_coo's do, until the next vtx_run / vtx_destroy on the context; `indptr` lives in a
+ * buffer of its own until the next vtx_device_csr, vtx_run or vtx_destroy.  That buffer is none of the device ingest's: the calls
+ * that work in those (vtx_write_mtx, vtx_write_mtx_gz, vtx_mtx_part, and the f64 writer) neither disturb a vtx_csr taken before them nor
+ * are disturbed by this call, and it may be repeated after any of them.  It changes nothing vtx_device_coo / vtx_fetch_coo return.
+ * Synchronous on the context's stream.  The offsets take 8 (row_end - row_begin + 1) bytes of device memory (VTX_E_NOMEM when the
+ * device does not have them); their cost does not depend on how the triplets are spread over the window: a stretch of more than 256
+ * rows without triplets is written by one lane per row, not by one lane.                                                             */
+int vtx_device_csr(vtx_ctx* ctx, uint32_t row_begin, uint32_t row_end, vtx_csr* out);
+
+/* Stable transpose of ANY CSR in caller-owned DEVICE memory into caller-owned device memory; needs no run (the context gives the
+ * device, the stream and the work space).  In: d_indptr[n_major + 1], d_indices[nnz] (each < n_minor; inside a row in any order,
+ * duplicates allowed).  Out: d_indptr_t[n_minor + 1], d_indices_t[nnz] and (optional, may be NULL) d_perm[nnz] with
+ *     d_indices_t[k] = the major index of source entry perm[k],     perm == the STABLE argsort of d_indices:
+ * inside an output row the entries keep their source order (for the library's own triplets: ascending), so the result is a function
+ * of the input alone.  n_payload arrays of nnz elements of payload_elem_bytes[i] = 4 or 8 bytes move with the entries,
+ * d_payload_out[i][k] = d_payload_in[i][perm[k]], bit for bit (NaN payloads, -0.0, explicit zeros).  The three arrays of pointers and
+ * sizes are HOST arrays of device pointers.  Outputs must not overlap inputs.
+ * The inputs are checked on the device BEFORE anything is written through them: indptr[0] == 0, indptr non-decreasing,
+ * indptr[n_major] == nnz, every index < n_minor; a violation returns VTX_E_INVAL (the reason in vtx_strerror), no output byte is
+ * written and the context stays usable.  VTX_E_UNSUPPORTED for nnz >= 2^32; VTX_E_INVAL for a null array that is needed or an element
+ * size other than 4 / 8.  Synchronous on the context's stream.
+ * Work space (stays with the context, like the ingest's): 8 nnz bytes of sorted keys and positions (12 nnz when d_perm is NULL) plus
+ * the radix sort's own: about 8 nnz + 64 KiB more.  n_minor adds nothing: the offsets go straight into d_indptr_t.               */
+int vtx_csr_transpose(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
+                      const uint64_t* d_indptr, const uint32_t* d_indices,
+                      uint64_t* d_indptr_t, uint32_t* d_indices_t, uint32_t* d_perm,
+                      const void* const* d_payload_in, void* const* d_payload_out,
+                      const uint32_t* payload_elem_bytes, uint32_t n_payload);
+
+/* Device time of the context's last vtx_device_csr or vtx_csr_transpose that succeeded, in milliseconds, from events on the context's
+ * own stream: ms[0] the check of the inputs, ms[1] the sort of the positions by column, ms[2] the offsets, ms[3] the placement of the
+ * indices and payloads (vtx_device_csr: 1 and 3 are 0).  Writes the first n of the four, at most four.                               */
+int vtx_last_csr_ms(vtx_ctx* ctx, float* ms, uint32_t n);
+
 /* ---- Multi-GPU: one process (one ctx) per GPU, loci sharded over the ranks (src/main.rs:284-291: chunks of loci
  * are independent), and ONE exchange at the end — every rank's triplets travel to rank `dst` over RCCL (xGMI inside
  * a node), concatenated in rank order, which is row order when rank r holds the r-th contiguous range of loci
@@ -564,8 +616,8 @@ const char* vtx_status_name(int status);
 
 /* sizeof() of {vtx_config, vtx_locus, vtx_record, vtx_batch, vtx_coo,
  * vtx_timing, vtx_raw_record, vtx_raw_batch, vtx_raw_stats, vtx_bgzf_block, vtx_bam_interval,
- * vtx_bam_ingest, vtx_ingest_stats, vtx_bam_segment, vtx_bam_segments, vtx_mtx_part} as compiled into the library,
- * for binding self-checks.  Writes min(n, 16) entries; returns VTX_ABI_VERSION.             */
+ * vtx_bam_ingest, vtx_ingest_stats, vtx_bam_segment, vtx_bam_segments, vtx_mtx_part, vtx_csr} as compiled into the library,
+ * for binding self-checks.  Writes min(n, 17) entries; returns VTX_ABI_VERSION.             */
 int vtx_abi_sizes(uint32_t* out, uint32_t n);
 
 #ifdef __cplusplus

@@ -107,6 +107,24 @@ class VtxCoo(C.Structure):
     ]
 
 
+class VtxCsr(C.Structure):
+    """vtx_csr: the variant-major CSR of a run on the device (vtx_device_csr); ``indices`` is ``VtxCoo.col``."""
+    _fields_ = [
+        ("indptr", C.POINTER(C.c_uint64)),
+        ("indices", C.POINTER(C.c_uint32)),
+        ("alt", C.POINTER(C.c_uint32)),
+        ("ref", C.POINTER(C.c_uint32)),
+        ("unk", C.POINTER(C.c_uint32)),
+        ("value", C.POINTER(C.c_double)),
+        ("ref_value", C.POINTER(C.c_double)),
+        ("nnz", C.c_uint64),
+        ("row_begin", C.c_uint32),
+        ("row_end", C.c_uint32),
+        ("n_cols", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class VtxTiming(C.Structure):
     _fields_ = [
         ("total_ms", C.c_float),

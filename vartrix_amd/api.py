@@ -1,0 +1,246 @@
+"""The public Python entry point: the four input files in, the matrices out as scipy or torch CSR.
+
+``run()`` is what the command line does (ingest -> ``vtx_run`` per range of loci) without the Matrix-Market text at the end: after every
+run the variant-major CSR of its triplets is taken ON THE DEVICE (``vtx_device_csr``: only the row offsets are new, the other arrays
+are the run's own), the parts of several runs are stacked (``stack_parts``), and the cell-major orientation — the ``X`` of an AnnData —
+is one stable transpose of the stacked whole (``vtx_csr_transpose``).  Every array of the run comes back: the scoring mode's values
+(the reference's ``matrix`` / ``ref_matrix``, src/main.rs:323-346) and the alt / ref / unknown counts behind them
+(CellCounts, src/main.rs:1032-1039), which no file of the command line holds outside the coverage mode.
+
+There is no CPU path: the scores, the calls, the offsets and the transpose are computed on the GPU; torch carries the device arrays
+(``__cuda_array_interface__``) and, for ``to="scipy"``, copies the finished arrays to the host.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import abi, hostlib, lib
+
+DATA_FIELDS = ("value", "ref_value", "alt", "ref", "unk")          # the five data arrays of a part, vtx_coo's names
+_ELEM_BYTES = {"value": 8, "ref_value": 8, "alt": 4, "ref": 4, "unk": 4}
+
+
+@dataclass
+class Result:
+    matrix: object            # the scoring mode's values (consensus 1 / 2 / 3, alt_frac's fractions and NaN, coverage's alt counts)
+    ref_matrix: object        # coverage mode: the ref counts (the reference's --ref-matrix); None otherwise
+    alt_counts: object        # integer, same sparsity as ``matrix``
+    ref_counts: object
+    unknown_counts: object
+    variants: list            # "{chrom}_{pos0}" per VCF record, what --out-variants writes
+    barcodes: list
+    metrics: dict             # the nine counters of hostlib.METRIC_NAMES
+    shape: tuple
+
+
+def _is_torch(a) -> bool:
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def stack_parts(parts):
+    """Stack CSR parts over consecutive row ranges into one CSR (what ``scipy.sparse.vstack`` does), on numpy arrays or torch tensors.
+
+    A part is a dict with ``indptr`` (rows + 1 offsets starting at 0), ``indices`` and any number of further arrays of one element per
+    entry (the same keys in every part).  Rows ascend from part to part, so stacking is concatenation: the entry arrays back to back,
+    and each part's offsets (without its leading 0) shifted by the entries in front of it.  Pure: the parts are not changed.  No
+    parts: the CSR of a matrix without rows (numpy)."""
+    parts = list(parts)
+    if not parts:
+        return {"indptr": np.zeros(1, np.int64), "indices": np.zeros(0, np.int64)}
+    keys = [k for k in parts[0] if k != "indptr"]
+    if _is_torch(parts[0]["indptr"]):
+        import torch
+        cat = torch.cat
+    else:
+        cat = np.concatenate
+    ptrs, base = [parts[0]["indptr"][:1] * 0], 0
+    for p in parts:
+        ptrs.append(p["indptr"][1:] + base)
+        base += int(p["indptr"][-1])
+    out = {"indptr": cat(ptrs)}
+    for k in keys:
+        out[k] = cat([p[k] for p in parts])
+    return out
+
+
+class _DevArray:
+    """A raw device pointer as an object ``torch.as_tensor`` takes without a copy (``shard._DevArray``)."""
+
+    def __init__(self, ptr: int, n: int, typestr: str):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False), "version": 2}
+
+
+def _device_part(ctx, torch, dev, row_begin, row_end):
+    """The last run's variant-major CSR over [row_begin, row_end) as CLONED torch tensors.  The library has finished writing the
+    arrays when ``device_csr`` returns (it synchronises its own stream); the clones are copies torch queues on ITS current stream, so
+    that stream is synchronised before this returns: only then may the next submit / run, on the library's stream, overwrite the
+    source arrays.  After that the clones outlive the next run and the context."""
+    d = ctx.device_csr(row_begin, row_end)
+    n = d["nnz"]
+
+    def take(key, count, typestr, dtype):
+        if not count:
+            return torch.zeros(0, dtype=dtype, device=dev)
+        return torch.as_tensor(_DevArray(d[key], count, typestr), device=dev).clone()
+    part = {"indptr": take("indptr", row_end - row_begin + 1, "<i8", torch.int64), "indices": take("indices", n, "<i4", torch.int32)}
+    for k in DATA_FIELDS:
+        part[k] = take(k, n, "<f8", torch.float64) if _ELEM_BYTES[k] == 8 else take(k, n, "<i4", torch.int32)
+    torch.cuda.current_stream(dev).synchronize()     # the copies out of the context's arrays are complete (shard.gather_coo_async does the same)
+    return part
+
+
+def _empty_part(torch, dev, n_rows):
+    part = {"indptr": torch.zeros(n_rows + 1, dtype=torch.int64, device=dev), "indices": torch.zeros(0, dtype=torch.int32, device=dev)}
+    for k in DATA_FIELDS:
+        part[k] = torch.zeros(0, dtype=torch.float64 if _ELEM_BYTES[k] == 8 else torch.int32, device=dev)
+    return part
+
+
+def _transpose(ctx, torch, dev, csr, n_major, n_minor):
+    """One stable transpose of the stacked CSR on the device; ``perm`` is computed once and moves all five data arrays."""
+    nnz = int(csr["indices"].shape[0])
+    out = {"indptr": torch.empty(n_minor + 1, dtype=torch.int64, device=dev), "indices": torch.empty(nnz, dtype=torch.int32, device=dev)}
+    for k in DATA_FIELDS:
+        out[k] = torch.empty_like(csr[k])
+    src = {k: v.contiguous() for k, v in csr.items()}
+    torch.cuda.synchronize(dev)              # the library works on its own stream: torch's writes to these arrays have to be done
+    ctx.csr_transpose(n_major, n_minor, nnz, src["indptr"].data_ptr(), src["indices"].data_ptr(), out["indptr"].data_ptr(),
+                      out["indices"].data_ptr(), 0, [(src[k].data_ptr(), out[k].data_ptr(), _ELEM_BYTES[k]) for k in DATA_FIELDS])
+    return out
+
+
+def _finish(csr, field, shape, to, torch):
+    if to == "torch":
+        return torch.sparse_csr_tensor(csr["indptr"], csr["indices"].to(torch.int64), csr[field], size=shape)
+    import scipy.sparse as sp
+    data = csr[field].cpu().numpy()
+    if data.dtype == np.int32:
+        data = data.view(np.uint32)
+    # (data, indices, indptr) as given: explicit zeros and NaN stay, nothing is summed or sorted
+    return sp.csr_matrix((data, csr["indices"].cpu().numpy(), csr["indptr"].cpu().numpy()), shape=shape)
+
+
+def run(vcf, bam, fasta, cell_barcodes, *, scoring_method="consensus", padding=100, mapq=0, primary_alignments=False,
+        no_duplicates=False, umi=False, bam_tag="CB", valid_chars="ATGCatgc", aligner="banded", ingest="auto", stream_loci=None,
+        threads=1, device=0, orient="variants", to="scipy") -> Result:
+    """Genotype the cells of ``bam`` at the variants of ``vcf`` and return every matrix of the run as CSR.
+
+    The arguments up to ``valid_chars`` are the command line's (the reference's, src/main.rs:54-160).  ``ingest``: "host" packs the
+    reads on the CPU (``hostlib.pack_files``, every batch of a pack), "device" hands the BAM's bytes to the card
+    (``hostlib.plan_ingest`` + ``submit_bam`` / ``submit_bam_segments``) and fails with the plan's or the device's reason, "auto" takes
+    the plan where there is one and the host packer for a range the device declines (VTX_E_UNSUPPORTED), as the command line does.
+    ``stream_loci=N``: the VCF in ranges of N records, one context reused.  ``orient``: "variants" (variants x cells, the files'
+    orientation) or "cells" (cells x variants: AnnData's X).  ``to``: "scipy" (``scipy.sparse.csr_matrix`` on the host) or "torch"
+    (``torch.sparse_csr_tensor`` on ``device``; the values never pass through the host).  Explicit zeros and NaN are kept.  The
+    result does not depend on ``ingest``, ``stream_loci`` or ``to``."""
+    import torch
+    if scoring_method not in abi.MODES:
+        raise ValueError("scoring_method %r: one of %s" % (scoring_method, sorted(abi.MODES)))
+    if aligner not in abi.ALIGNERS:
+        raise ValueError("aligner %r: one of %s" % (aligner, sorted(abi.ALIGNERS)))
+    if ingest not in ("auto", "host", "device"):
+        raise ValueError("ingest %r: auto, host or device" % (ingest,))
+    if orient not in ("variants", "cells"):
+        raise ValueError("orient %r: variants or cells" % (orient,))
+    if to not in ("scipy", "torch"):
+        raise ValueError("to %r: scipy or torch" % (to,))
+    if stream_loci is not None and int(stream_loci) < 1:
+        raise ValueError("stream_loci %r: a positive number of VCF records, or None" % (stream_loci,))
+    dev = torch.device("cuda", int(device))
+    files = dict(vcf=str(vcf), bam=str(bam), fasta=str(fasta), cell_barcodes=str(cell_barcodes))
+    filt = dict(padding=int(padding), mapq=int(mapq), primary_only=bool(primary_alignments), no_duplicates=bool(no_duplicates),
+                use_umi=bool(umi), bam_tag=bam_tag, valid_chars=valid_chars, threads=int(threads))
+    metrics = dict.fromkeys(hostlib.METRIC_NAMES, 0)
+    state = {"ctx": None, "barcodes": None, "variants": None, "n_variants": None, "bc_set": False}
+    parts = []
+
+    def add(m):
+        for k, v in m.items():
+            metrics[k] += int(v)
+
+    def context(n_variants, barcodes, variants):
+        if state["ctx"] is None:
+            cfg = abi.default_config(aligner=aligner, scoring_mode=scoring_method, use_umi=int(bool(umi)), n_barcodes=len(barcodes),
+                                     device=int(device))
+            state.update(ctx=lib.Context(cfg), barcodes=barcodes, variants=variants, n_variants=n_variants)
+        return state["ctx"]
+
+    def take(ctx, lo, hi):
+        ctx.run()
+        parts.append(_device_part(ctx, torch, dev, lo, hi))
+
+    def window(lo, hi):
+        nv = int(state["n_variants"])
+        return min(lo, nv), (nv if hi is None else min(hi, nv))
+
+    def host_range(rows, lo, hi):
+        batches, m, nv, barcodes, variants = hostlib.pack_files(**files, **filt, all_batches=True, rows=rows)
+        ctx = context(nv, barcodes, variants)
+        lo, hi = window(lo, hi)
+        add(m)
+        batches = [b for b in batches if b.n_loci]
+        if not batches:
+            parts.append(_empty_part(torch, dev, hi - lo))
+        for i, b in enumerate(batches):      # consecutive loci: a batch's rows end where the next batch's begin
+            cut = int(batches[i + 1].loci["row"][0]) if i + 1 < len(batches) else hi
+            ctx.submit(b)
+            take(ctx, lo, cut)
+            lo = cut
+
+    def device_range(rows, lo, hi):
+        """True: done on the device.  False: declined and ``ingest`` is auto (the host packs this range)."""
+        with hostlib.plan_ingest(**files, **filt, rows=rows) as plan:
+            ctx = context(plan.n_variants, plan.barcodes, plan.variants)
+            lo, hi = window(lo, hi)
+            if plan.reason is not None:
+                if ingest == "device":
+                    raise hostlib.HostError("no device ingest for rows [%d, %d): %s" % (lo, hi, plan.reason))
+                return False
+            if not plan.n_loci:              # nothing to look at in this range (skipped records only): its rows are empty
+                add(plan.metrics)
+                parts.append(_empty_part(torch, dev, hi - lo))
+                return True
+            if not state["bc_set"]:
+                ctx.set_barcodes(plan.barcodes)
+                state["bc_set"] = True
+            try:
+                st = ctx.submit_bam_segments(plan.segments, plan.n_loci) if plan.kind == "segmented" else ctx.submit_bam(plan.ingest, plan.n_loci)
+            except lib.VtxError as e:
+                if e.status == abi.VTX_E_UNSUPPORTED and ingest == "auto":
+                    return False
+                raise
+            add(plan.metrics)
+            add(dict(num_reads=st.num_reads, num_low_mapq=st.num_low_mapq, num_non_primary=st.num_non_primary,
+                     num_duplicates=st.num_duplicates, num_not_useful=st.num_not_useful,
+                     num_not_cell_bc=st.num_no_barcode_tag + st.raw.num_not_cell_bc, num_non_umi=st.raw.num_non_umi))
+        take(ctx, lo, hi)
+        return True
+
+    try:
+        lo = 0
+        while True:                          # the number of VCF records is known once the first range is packed or planned
+            hi = None if stream_loci is None else lo + int(stream_loci)
+            rows = None if stream_loci is None else (lo, hi)
+            if ingest == "host" or not device_range(rows, lo, hi):
+                host_range(rows, lo, hi)
+            lo = window(lo, hi)[1]
+            if lo >= state["n_variants"]:
+                break
+        ctx = state["ctx"]
+        n_rows, n_cols = int(state["n_variants"]), len(state["barcodes"])
+        csr = stack_parts(parts)
+        shape = (n_rows, n_cols)
+        if orient == "cells":
+            csr = _transpose(ctx, torch, dev, csr, n_rows, n_cols)
+            shape = (n_cols, n_rows)
+        coverage = abi.MODES[scoring_method] == abi.MODE_COVERAGE
+        return Result(matrix=_finish(csr, "value", shape, to, torch),
+                      ref_matrix=_finish(csr, "ref_value", shape, to, torch) if coverage else None,
+                      alt_counts=_finish(csr, "alt", shape, to, torch), ref_counts=_finish(csr, "ref", shape, to, torch),
+                      unknown_counts=_finish(csr, "unk", shape, to, torch), variants=list(state["variants"]),
+                      barcodes=[b.decode() if isinstance(b, bytes) else b for b in state["barcodes"]], metrics=metrics, shape=shape)
+    finally:
+        if state["ctx"] is not None:
+            state["ctx"].close()

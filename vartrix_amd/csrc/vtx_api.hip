@@ -31,6 +31,7 @@
 #include "vtx_deflate_core.h"
 #include "vtx_inflate_core.h"
 #include "vtx_mtx_join.h"
+#include "vtx_csr_core.h"
 #include "../../include/vtx_band_semantics.h"
 
 extern "C" hipError_t vtxk_inclusive_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, void* temp,
@@ -146,6 +147,8 @@ struct vtx_ctx {
     hipEvent_t ev[EV_COUNT] = {};
     hipEvent_t ev_crc[2] = {};               // around bgzf_crc32_kernel (vtx_submit_bam, vtx_debug_crc32)
     float crc_ms = 0;                        // vtx_last_crc_ms
+    hipEvent_t ev_csr[6] = {};               // vtx_device_csr / vtx_csr_transpose: around the check, the sort, the offsets, the placement (created on first use)
+    float csr_ms[4] = {};                    // vtx_last_csr_ms
     std::string err;
     bool submitted = false, ran = false;
     uint32_t n_loci = 0, n_records = 0, n_cell_groups = 0, n_umi_groups = 0, max_hap_len = 0;
@@ -158,6 +161,8 @@ struct vtx_ctx {
     int reduce_path = 0;                     // the last vtx_run's call reduction: 1 = histogram kernels (atomics), 2 = one pass per group
     DevBuf d_cell_cnt, d_umi_cnt, d_keep, d_keep_scan, d_scan_tmp;
     DevBuf d_o_row, d_o_col, d_o_alt, d_o_ref, d_o_unk, d_o_val, d_o_refval;
+    DevBuf d_csr_indptr;                     // vtx_device_csr: the row offsets of d_o_row (a buffer of its own: no other call works in it)
+    DevBuf d_csr_flag, d_csr_keys, d_csr_iota, d_csr_perm, d_csr_tmp;   // vtx_csr_transpose: flag word, sorted columns, positions, perm (when the caller wants none), the sort's work space
     bool band_long_lists = false;      // (performance feedback between runs: see vtx_run)
     int read_format = VTX_READS_BYTES;     // vtx_set_read_format
     DevBuf d_read_packed;                  // VTX_READS_NIBBLES: the arena as uploaded, unpacked into d_read
@@ -684,13 +689,13 @@ void vtx_config_default(vtx_config* cfg) {
 }
 
 int vtx_abi_sizes(uint32_t* out, uint32_t n) {
-    const uint32_t s[16] = {(uint32_t)sizeof(vtx_config), (uint32_t)sizeof(vtx_locus), (uint32_t)sizeof(vtx_record),
+    const uint32_t s[17] = {(uint32_t)sizeof(vtx_config), (uint32_t)sizeof(vtx_locus), (uint32_t)sizeof(vtx_record),
                             (uint32_t)sizeof(vtx_batch), (uint32_t)sizeof(vtx_coo), (uint32_t)sizeof(vtx_timing),
                             (uint32_t)sizeof(vtx_raw_record), (uint32_t)sizeof(vtx_raw_batch), (uint32_t)sizeof(vtx_raw_stats),
                             (uint32_t)sizeof(vtx_bgzf_block), (uint32_t)sizeof(vtx_bam_interval), (uint32_t)sizeof(vtx_bam_ingest),
                             (uint32_t)sizeof(vtx_ingest_stats), (uint32_t)sizeof(vtx_bam_segment), (uint32_t)sizeof(vtx_bam_segments),
-                            (uint32_t)sizeof(struct vtx_mtx_part)};
-    for (uint32_t i = 0; i < n && i < 16; ++i) out[i] = s[i];
+                            (uint32_t)sizeof(struct vtx_mtx_part), (uint32_t)sizeof(vtx_csr)};
+    for (uint32_t i = 0; i < n && i < 17; ++i) out[i] = s[i];
     return VTX_ABI_VERSION;
 }
 
@@ -771,6 +776,7 @@ void vtx_destroy(vtx_ctx* c) {
                       &c->d_prep_cnt, &c->d_sort_tmp, &c->d_fail, &c->d_fail_tmp, &c->d_refine, &c->d_tail, &c->d_tight, &c->d_tight_pack, &c->d_dband, &c->d_dband_pack, &c->d_dense, &c->d_stage, &c->d_sweep_log, &c->d_tight2, &c->d_tight2_pack, &c->d_recheck2, &c->d_recheck2_pack};
     for (DevBuf* b : bufs) b->release();
     c->d_slow_ws.release(); c->d_slow_retry.release(); c->d_read_packed.release();
+    c->d_csr_indptr.release(); c->d_csr_flag.release(); c->d_csr_keys.release(); c->d_csr_iota.release(); c->d_csr_perm.release(); c->d_csr_tmp.release();
     DevBuf* ib[] = {&c->d_bam_comp, &c->d_bam_data, &c->d_bam_blocks, &c->d_bam_seeds, &c->d_bam_seed_cnt, &c->d_bam_seed_scan, &c->d_bam_iv, &c->d_bam_cnt,
                     &c->d_bam_rec, &c->d_bam_nhit, &c->d_bam_rsz, &c->d_bam_tsz, &c->d_bam_hscan, &c->d_bam_rscan, &c->d_bam_tscan, &c->d_bam_info, &c->d_bam_segs};
     for (DevBuf* b : ib) b->release();
@@ -780,6 +786,7 @@ void vtx_destroy(vtx_ctx* c) {
     upload_release(c);
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : c->ev_crc) if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : c->ev_csr) if (ev) (void)hipEventDestroy(ev);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -2731,6 +2738,129 @@ int vtx_device_coo(vtx_ctx* c, vtx_coo* out) {
     out->ref = c->d_o_ref.as<uint32_t>(); out->unk = c->d_o_unk.as<uint32_t>(); out->value = c->d_o_val.as<double>();
     out->ref_value = c->d_o_refval.as<double>();
     out->nnz = c->nnz;
+    return VTX_OK;
+}
+
+// ---- the matrices as CSR on the device (include/vtx.h, vtx_csr.hip) ----
+static const char* csr_bad_reason(uint32_t flag) {
+    if (flag & vtxr::BAD_FIRST) return "indptr[0] != 0";
+    if (flag & vtxr::BAD_ORDER) return "indptr decreases";
+    if (flag & vtxr::BAD_LAST) return "indptr[n_major] != nnz";
+    if (flag & vtxr::BAD_INDEX) return "an index >= n_minor";
+    return "a triplet's row outside [row_begin, row_end)";
+}
+
+// the flag word of a check: zeroed on the stream in front of the check, read back behind it
+static int csr_flag_zero(vtx_ctx* c) {
+    HIP_TRY(c, c->d_csr_flag.reserve(sizeof(uint32_t)));
+    HIP_TRY(c, hipMemsetAsync(c->d_csr_flag.p, 0, sizeof(uint32_t), c->stream));
+    return VTX_OK;
+}
+static int csr_flag_read(vtx_ctx* c, uint32_t* flag) {
+    HIP_TRY(c, hipMemcpyAsync(flag, c->d_csr_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return VTX_OK;
+}
+
+// Device times of the CSR calls: events on the context's stream.  enum CsrEv names what lies between two of them.
+enum CsrEv { EV_CSR_CHECK0 = 0, EV_CSR_CHECK1 = 1, EV_CSR_SORT0 = 2, EV_CSR_SORT1 = 3, EV_CSR_OFFSETS1 = 4, EV_CSR_PLACE1 = 5 };
+static int csr_events(vtx_ctx* c) {
+    for (auto& ev : c->ev_csr) if (!ev) HIP_TRY(c, hipEventCreate(&ev));
+    return VTX_OK;
+}
+static int csr_times(vtx_ctx* c, bool checked, bool sorted, bool placed) {        // after the stream is synchronised
+    const int pair[4][2] = {{EV_CSR_CHECK0, EV_CSR_CHECK1}, {EV_CSR_SORT0, EV_CSR_SORT1}, {EV_CSR_SORT1, EV_CSR_OFFSETS1}, {EV_CSR_OFFSETS1, EV_CSR_PLACE1}};
+    const bool on[4] = {checked, sorted, true, placed};
+    for (int i = 0; i < 4; ++i) {
+        c->csr_ms[i] = 0.f;
+        if (on[i]) HIP_TRY(c, hipEventElapsedTime(&c->csr_ms[i], c->ev_csr[pair[i][0]], c->ev_csr[pair[i][1]]));
+    }
+    return VTX_OK;
+}
+
+int vtx_last_csr_ms(vtx_ctx* c, float* ms, uint32_t n) {
+    if (!c) return VTX_E_INVAL;
+    if (!ms) return fail(c, VTX_E_INVAL, "vtx_last_csr_ms: null output");
+    for (uint32_t i = 0; i < n && i < 4; ++i) ms[i] = c->csr_ms[i];
+    return VTX_OK;
+}
+
+int vtx_device_csr(vtx_ctx* c, uint32_t row_begin, uint32_t row_end, vtx_csr* out) {
+    if (!c) return VTX_E_INVAL;
+    if (!out) return fail(c, VTX_E_INVAL, "vtx_device_csr: null output");
+    memset(out, 0, sizeof *out);
+    if (!c->ran) return fail(c, VTX_E_STATE, "vtx_device_csr: no completed vtx_run");
+    if (row_begin > row_end) return fail(c, VTX_E_INVAL, "vtx_device_csr: row_begin %u > row_end %u", row_begin, row_end);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    const uint64_t nnz = c->nnz;
+    const uint32_t* d_row = c->d_o_row.as<uint32_t>();
+    if (int rc = csr_events(c)) return rc;
+    if (nnz) {
+        if (int rc = csr_flag_zero(c)) return rc;
+        HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK0], s));
+        HIP_TRY(c, vtxr_window_check(d_row, nnz, row_begin, row_end, c->d_csr_flag.as<uint32_t>(), s));
+        HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK1], s));
+        uint32_t flag = 0;
+        if (int rc = csr_flag_read(c, &flag)) return rc;
+        if (flag) return fail(c, VTX_E_INVAL, "vtx_device_csr: %s [%u, %u)", csr_bad_reason(flag), row_begin, row_end);
+    }
+    HIP_TRY(c, c->d_csr_indptr.reserve(((size_t)(row_end - row_begin) + 1) * sizeof(uint64_t)));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT1], s));
+    HIP_TRY(c, vtxr_offsets(d_row, nnz, row_begin, row_end, c->d_csr_indptr.as<uint64_t>(), s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = csr_times(c, nnz != 0, false, false)) return rc;
+    out->indptr = c->d_csr_indptr.as<uint64_t>();
+    out->indices = c->d_o_col.as<uint32_t>();
+    out->alt = c->d_o_alt.as<uint32_t>(); out->ref = c->d_o_ref.as<uint32_t>(); out->unk = c->d_o_unk.as<uint32_t>();
+    out->value = c->d_o_val.as<double>(); out->ref_value = c->d_o_refval.as<double>();
+    out->nnz = nnz;
+    out->row_begin = row_begin; out->row_end = row_end; out->n_cols = c->cfg.n_barcodes;
+    return VTX_OK;
+}
+
+int vtx_csr_transpose(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
+                      uint64_t* d_indptr_t, uint32_t* d_indices_t, uint32_t* d_perm, const void* const* d_payload_in, void* const* d_payload_out,
+                      const uint32_t* payload_elem_bytes, uint32_t n_payload) {
+    if (!c) return VTX_E_INVAL;
+    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "vtx_csr_transpose: %llu entries: positions are 32-bit", (unsigned long long)nnz);
+    if (!d_indptr || !d_indptr_t || (nnz && (!d_indices || !d_indices_t))) return fail(c, VTX_E_INVAL, "vtx_csr_transpose: null array");
+    if (n_payload && (!d_payload_in || !d_payload_out || !payload_elem_bytes)) return fail(c, VTX_E_INVAL, "vtx_csr_transpose: null payload list");
+    for (uint32_t a = 0; a < n_payload; ++a) {
+        if (payload_elem_bytes[a] != 4 && payload_elem_bytes[a] != 8)
+            return fail(c, VTX_E_INVAL, "vtx_csr_transpose: payload %u has elements of %u bytes (4 or 8)", a, payload_elem_bytes[a]);
+        if (nnz && (!d_payload_in[a] || !d_payload_out[a])) return fail(c, VTX_E_INVAL, "vtx_csr_transpose: payload %u is null", a);
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    // the caller's arrays are read, and judged, before a single byte is written through them
+    if (int rc = csr_events(c)) return rc;
+    if (int rc = csr_flag_zero(c)) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK0], s));
+    HIP_TRY(c, vtxr_check(d_indptr, n_major, nnz, d_indices, n_minor, c->d_csr_flag.as<uint32_t>(), s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK1], s));
+    uint32_t flag = 0;
+    if (int rc = csr_flag_read(c, &flag)) return rc;
+    if (flag) return fail(c, VTX_E_INVAL, "vtx_csr_transpose: %s", csr_bad_reason(flag));
+    uint32_t* perm = d_perm;
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT0], s));
+    if (nnz) {
+        const int end_bit = (int)bits_for(n_minor - 1);
+        const size_t tmp = vtxr_sort_temp_bytes(nnz, end_bit);
+        HIP_TRY(c, c->d_csr_keys.reserve((size_t)nnz * sizeof(uint32_t)));
+        HIP_TRY(c, c->d_csr_iota.reserve((size_t)nnz * sizeof(uint32_t)));
+        HIP_TRY(c, c->d_csr_tmp.reserve(tmp));
+        if (!perm) { HIP_TRY(c, c->d_csr_perm.reserve((size_t)nnz * sizeof(uint32_t))); perm = c->d_csr_perm.as<uint32_t>(); }
+        HIP_TRY(c, vtxr_sort_positions(d_indices, c->d_csr_keys.as<uint32_t>(), c->d_csr_iota.as<uint32_t>(), perm, nnz, end_bit, c->d_csr_tmp.p, tmp, s));
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT1], s));
+    HIP_TRY(c, vtxr_offsets(c->d_csr_keys.as<uint32_t>(), nnz, 0, n_minor, d_indptr_t, s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, vtxr_place(d_indptr, n_major, perm, nnz, d_indices_t, d_payload_in, d_payload_out, payload_elem_bytes, n_payload, s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = csr_times(c, true, true, true)) return rc;
     return VTX_OK;
 }
 

@@ -264,5 +264,16 @@ hipError_t vtxk_unpack_nibbles(const uint8_t* in, uint64_t n_in, uint8_t* out, h
 hipError_t vtxk_prep_check(const vtx_record* records, uint32_t n, const uint32_t* rec_locus, const vtx_locus* loci,
                            uint64_t read_bytes, uint32_t max_read_len, uint32_t n_barcodes, int use_umi, uint32_t n_shapes, uint8_t* shape,
                            uint32_t* seq, uint32_t* shape_cnt, unsigned long long* counters, hipStream_t s);
+// ---- vtx_csr.hip: row offsets of sorted keys, the checks of a caller's CSR, the stable sort of positions by column, the placement ----
+// flag: one zeroed word, the OR of vtxr::Bad bits (vtx_csr_core.h).  n < 2^32 wherever positions are 32-bit (sort, place).
+hipError_t vtxr_window_check(const uint32_t* row, uint64_t n, uint32_t begin, uint32_t end, uint32_t* flag, hipStream_t s);
+hipError_t vtxr_offsets(const uint32_t* key, uint64_t n, uint32_t begin, uint32_t end, uint64_t* indptr, hipStream_t s);
+hipError_t vtxr_check(const uint64_t* indptr, uint32_t n_major, uint64_t nnz, const uint32_t* indices, uint32_t n_minor, uint32_t* flag,
+                      hipStream_t s);
+size_t vtxr_sort_temp_bytes(uint64_t n, int end_bit);
+hipError_t vtxr_sort_positions(const uint32_t* key, uint32_t* key_sorted, uint32_t* iota, uint32_t* perm, uint64_t n, int end_bit, void* temp,
+                               size_t temp_bytes, hipStream_t s);
+hipError_t vtxr_place(const uint64_t* indptr, uint32_t n_major, const uint32_t* perm, uint64_t n, uint32_t* indices_t, const void* const* in,
+                      void* const* out, const uint32_t* elem_bytes, uint32_t n_payload, hipStream_t s);
 }
 #endif

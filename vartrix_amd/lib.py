@@ -38,6 +38,7 @@ SYMBOLS = (
     "vtx_set_debug", "vtx_fetch_stage", "vtx_debug_bands", "vtx_debug_tables", "vtx_set_read_format",
     "vtx_submit_bam", "vtx_submit_bam_segments", "vtx_debug_ingest", "vtx_debug_inflate", "vtx_comm_ranks", "vtx_write_mtx", "vtx_prefetch_file",
     "vtx_last_crc_ms", "vtx_write_mtx_gz", "vtx_mtx_part", "vtx_mtx_part_free", "vtx_mtx_join",
+    "vtx_device_csr", "vtx_csr_transpose", "vtx_last_csr_ms",
 )
 # (entry points with a digit in their name: tests/test_abi.py finds the header's declarations with [a-z_]+ and compares them with SYMBOLS,
 # so these are listed — and checked against the header and every build of the library, tests/test_abi_f64.py — on their own)
@@ -87,6 +88,13 @@ def load(variant=None):
     L.vtx_device_scores.argtypes = [ctxp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.vtx_device_coo.restype = C.c_int
     L.vtx_device_coo.argtypes = [ctxp, C.POINTER(abi.VtxCoo)]
+    L.vtx_device_csr.restype = C.c_int
+    L.vtx_device_csr.argtypes = [ctxp, C.c_uint32, C.c_uint32, C.POINTER(abi.VtxCsr)]
+    L.vtx_csr_transpose.restype = C.c_int
+    L.vtx_csr_transpose.argtypes = [ctxp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32]
+    L.vtx_last_csr_ms.restype = C.c_int
+    L.vtx_last_csr_ms.argtypes = [ctxp, C.POINTER(C.c_float), C.c_uint32]
     L.vtx_last_timing.restype = C.c_int
     L.vtx_last_timing.argtypes = [ctxp, C.POINTER(abi.VtxTiming)]
     L.vtx_last_cells.restype = C.c_int
@@ -357,6 +365,34 @@ class Context:
         for k in ("row", "col", "alt", "ref", "unk", "value", "ref_value"):
             out[k] = C.cast(getattr(coo, k), C.c_void_p).value or 0
         return out
+
+    def device_csr(self, row_begin: int, row_end: int) -> dict:
+        """Raw device addresses of the last run's variant-major CSR over the rows [row_begin, row_end) (vtx_device_csr): ``indptr``
+        (row_end - row_begin + 1 uint64), ``indices`` (the address ``device_coo()["col"]`` reports), the five data arrays, plus nnz,
+        row_begin, row_end, n_cols.  VTX_E_INVAL when a triplet's row lies outside the window."""
+        st = abi.VtxCsr()
+        self._check(self._L.vtx_device_csr(self._h, int(row_begin), int(row_end), C.byref(st)))
+        out = {"nnz": int(st.nnz), "row_begin": int(st.row_begin), "row_end": int(st.row_end), "n_cols": int(st.n_cols)}
+        for k in ("indptr", "indices", "alt", "ref", "unk", "value", "ref_value"):
+            out[k] = C.cast(getattr(st, k), C.c_void_p).value or 0
+        return out
+
+    def csr_transpose(self, n_major: int, n_minor: int, nnz: int, indptr: int, indices: int, indptr_t: int, indices_t: int, perm: int = 0,
+                      payloads=()):
+        """Stable transpose of a CSR in device memory (vtx_csr_transpose); every array is a raw device ADDRESS.  ``payloads``: a list
+        of (address in, address out, element bytes 4 | 8) that move with the entries.  ``perm`` = 0: not wanted."""
+        n = len(payloads)
+        p_in = (C.c_void_p * max(n, 1))(*[int(p[0]) or None for p in payloads])
+        p_out = (C.c_void_p * max(n, 1))(*[int(p[1]) or None for p in payloads])
+        p_sz = (C.c_uint32 * max(n, 1))(*[int(p[2]) for p in payloads])
+        self._check(self._L.vtx_csr_transpose(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, indptr_t or None,
+                                              indices_t or None, perm or None, p_in, p_out, p_sz, n))
+
+    def csr_ms(self) -> dict:
+        """Device time of the last ``device_csr`` / ``csr_transpose`` by phase, milliseconds (vtx_last_csr_ms: events on the context's stream)."""
+        ms = (C.c_float * 4)()
+        self._check(self._L.vtx_last_csr_ms(self._h, ms, 4))
+        return dict(zip(("check", "sort", "offsets", "place"), (float(v) for v in ms)))
 
     def comm_init(self, ident: bytes, rank: int, world: int):
         """Join the RCCL communicator of the sharded run (collective; vtx_comm_init)."""
