@@ -530,9 +530,63 @@ int vtx_csr_transpose(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t
                       const void* const* d_payload_in, void* const* d_payload_out,
                       const uint32_t* payload_elem_bytes, uint32_t n_payload);
 
-/* Device time of the context's last vtx_device_csr or vtx_csr_transpose that succeeded, in milliseconds, from events on the context's
- * own stream: ms[0] the check of the inputs, ms[1] the sort of the positions by column, ms[2] the offsets, ms[3] the placement of the
- * indices and payloads (vtx_device_csr: 1 and 3 are 0).  Writes the first n of the four, at most four.                               */
+/* ---- summaries and selections of a CSR (vartrix_amd/csrc/vtx_csr_ops.hip) -------------------------------------------------------------
+ * The first two steps of every consumer of the variants x cells matrices, where the matrices are: the per-row counts of entries with
+ * alt / ref support, and the selection of rows and columns by masks (the locus filter of the demultiplexers).  Like vtx_csr_transpose
+ * these work on ANY CSR in caller-owned DEVICE memory, need a context (device, stream, work space) but no run, are synchronous on the
+ * context's stream, and check their inputs on the device BEFORE anything is written: indptr[0] == 0, indptr non-decreasing,
+ * indptr[n_major] == nnz, every index < n_minor; a violation returns VTX_E_INVAL (the reason in vtx_strerror), no output byte is
+ * written and the context stays usable.  VTX_E_UNSUPPORTED for nnz >= 2^32; VTX_E_INVAL for a null array that is needed or a payload
+ * element size other than 4 / 8.  Integer work only: every result is a function of the input alone.
+ *
+ * The seven statistics of a row, from the (alt, ref, unk) counts of its entries; n_major elements each, any pointer may be NULL (that
+ * array is not written).  The counts are u32, the sums u64: a row of u32 counts can pass 2^32.                                        */
+typedef struct vtx_csr_stats {
+    uint32_t *n_entries, *n_alt, *n_ref, *n_both;   /* entries; entries with alt > 0; with ref > 0; with both (what consensus writes as 3) */
+    uint64_t *sum_alt, *sum_ref, *sum_unk;          /* sums of the counts */
+} vtx_csr_stats;
+
+/* The statistics of every row of the CSR d_indptr[n_major + 1], d_indices[nnz] whose entries carry the counts d_alt / d_ref /
+ * d_unk[nnz] (vtx_csr's arrays, or the payloads a vtx_csr_transpose moved: then the rows are cells).  A row without entries gets
+ * zeros.  A group of 1 .. 64 lanes (from nnz / n_major alone) walks a row and folds inside its wavefront: no atomics, no zeroing
+ * pass.  A row is walked by its one group however long it is: for the library's own matrices that is at most n_minor entries; a CSR
+ * with duplicate indices (longer rows) is accepted and correct, and need not be fast.  d_indices is read by the check only.  No work
+ * space beyond the check's flag word.                                                                                                */
+int vtx_csr_row_stats(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
+                      const uint64_t* d_indptr, const uint32_t* d_indices,
+                      const uint32_t* d_alt, const uint32_t* d_ref, const uint32_t* d_unk,
+                      const vtx_csr_stats* out);
+
+/* Stable selection of rows and columns.  d_keep_major[n_major] / d_keep_minor[n_minor] are byte masks: any non-zero byte keeps, a
+ * NULL mask keeps everything (a bool array is a valid mask as it is).  An entry survives when its row and its column do; the kept rows
+ * and columns are renumbered 0, 1, ... in their order, and the entries keep their source order inside a row.
+ * vtx_csr_select_plan reports the sizes of the result: the caller allocates d_indptr_out[n_major_out + 1], d_indices_out[nnz_out], the
+ * payload outputs of nnz_out elements and, if wanted, d_major_ids[n_major_out] / d_minor_ids[n_minor_out] (the source row / column of
+ * every kept one; may be NULL), and passes the three sizes back to vtx_csr_select.  vtx_csr_select is STATELESS: it recomputes the
+ * sizes from its own arguments, and if they differ from the ones passed in it returns VTX_E_INVAL and writes no output byte — an
+ * allocation made for another selection cannot be overrun.  d_indices_out receives the NEW column numbers; n_payload arrays of
+ * payload_elem_bytes[i] = 4 or 8 bytes per entry move with the kept entries, bit for bit (NaN payloads, -0.0, explicit zeros).  The
+ * three arrays of pointers and sizes are HOST arrays of device pointers.  Outputs must not overlap inputs.
+ * Work space (stays with the context, like the transpose's): 4 (nnz + 1) bytes of positions, 4 (n_major + n_minor + 2) bytes of maps
+ * and the scan's own.                                                                                                                */
+int vtx_csr_select_plan(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
+                        const uint64_t* d_indptr, const uint32_t* d_indices,
+                        const uint8_t* d_keep_major, const uint8_t* d_keep_minor,
+                        uint32_t* n_major_out, uint32_t* n_minor_out, uint64_t* nnz_out);
+int vtx_csr_select(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
+                   const uint64_t* d_indptr, const uint32_t* d_indices,
+                   const uint8_t* d_keep_major, const uint8_t* d_keep_minor,
+                   uint32_t n_major_out, uint32_t n_minor_out, uint64_t nnz_out,
+                   uint64_t* d_indptr_out, uint32_t* d_indices_out,
+                   uint32_t* d_major_ids, uint32_t* d_minor_ids,
+                   const void* const* d_payload_in, void* const* d_payload_out,
+                   const uint32_t* payload_elem_bytes, uint32_t n_payload);
+
+/* Device time of the context's last CSR call that succeeded, in milliseconds, from events on the context's own stream.
+ * vtx_device_csr / vtx_csr_transpose: ms[0] the check of the inputs, ms[1] the sort of the positions by column, ms[2] the offsets,
+ * ms[3] the placement of the indices and payloads (vtx_device_csr: 1 and 3 are 0).  vtx_csr_row_stats: ms[0] the check, ms[3] the
+ * reduction (1 and 2 are 0).  vtx_csr_select_plan / vtx_csr_select: ms[0] the check, ms[1] the scans, ms[2] the offsets and ids, ms[3]
+ * the placement (the plan: 2 and 3 are 0).  Writes the first n of the four, at most four.                                            */
 int vtx_last_csr_ms(vtx_ctx* ctx, float* ms, uint32_t n);
 
 /* ---- Multi-GPU: one process (one ctx) per GPU, loci sharded over the ranks (src/main.rs:284-291: chunks of loci
@@ -619,6 +673,9 @@ const char* vtx_status_name(int status);
  * vtx_bam_ingest, vtx_ingest_stats, vtx_bam_segment, vtx_bam_segments, vtx_mtx_part, vtx_csr} as compiled into the library,
  * for binding self-checks.  Writes min(n, 17) entries; returns VTX_ABI_VERSION.             */
 int vtx_abi_sizes(uint32_t* out, uint32_t n);
+/* sizeof(vtx_csr_stats) as compiled into the library.  A call of its own: the table above stays at its 17 entries, which callers
+ * already rely on (a caller that asks vtx_abi_sizes for more gets 17).                                                               */
+uint32_t vtx_sizeof_csr_stats(void);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,17 @@ ONE process, each entry the median of --runs repetitions after one warm-up.
 The device times are the library's own (vtx_last_csr_ms: events on the context's stream around the check of the inputs, the sort, the
 offsets and the placement); the host wall time is what a caller waits, the readback of the check's flag word included.  The results of
 the device calls are compared with scipy's before anything is timed.
-GPU box:   python tools/csr_profile.py --json profiles/r12_csr.json"""
+GPU box:   python tools/csr_profile.py --json profiles/r12_csr.json
+
+--ops measures the summaries and selections of that CSR instead (vtx_csr_row_stats variant-major and cell-major, vtx_csr_select_plan and
+vtx_csr_select keeping the variants with n_alt >= 10 and n_ref >= 10, all five payloads), each compared with numpy / scipy before it is
+timed, against what a user does today: on the device in torch (CSR -> COO rows, index_add_, boolean masking, offsets from a bincount —
+each reported only if this torch build can do it, with the error otherwise), and on the host (fetch + numpy / scipy).  It also records
+which operations this torch build offers on a sparse CSR tensor.
+--sweep times the statistics kernel at every group size G (the developer library's VTX_CSR_STATS_G, so VTX_LIB_VARIANT=dev) on synthetic
+CSRs of three shapes — config 3 variant-major and cell-major, and four reads per locus — next to the G the rule picks; no batch is run.
+GPU box:   python tools/csr_profile.py --ops --json profiles/r13_csr_ops.json
+           VTX_LIB_VARIANT=dev python tools/csr_profile.py --sweep --json profiles/r13_csr_ops.json     (joins the record above)"""
 import argparse
 import json
 import os
@@ -36,15 +46,11 @@ ap.add_argument("--barcodes", type=int, default=10_000)
 ap.add_argument("--reads-per-locus", type=int, default=256)
 ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--skip-mmread", action="store_true", help="leave out the Matrix-Market round trip (minutes of parsing at config-3 size)")
+ap.add_argument("--ops", action="store_true", help="measure vtx_csr_row_stats / vtx_csr_select instead of the hand-over")
+ap.add_argument("--sweep", action="store_true", help="time csr_row_stats_kernel at every group size (developer library), no batch")
 args = ap.parse_args()
 
 dev = torch.device("cuda", 0)
-spec = synth.SynthSpec(n_loci=args.loci, n_barcodes=args.barcodes, reads_per_locus=args.reads_per_locus, read_len=150, padding=100,
-                       use_umi=False, indel_frac=0.0, sub_error=0.005, depth_sigma=0.0, seed=20260926)      # bench.py's config 3, its defaults spelled out
-t0 = time.perf_counter()
-batch = synth.make_batch(spec)
-print("batch: %d records in %.1f s" % (batch.n_records, time.perf_counter() - t0), flush=True)
-n_rows, n_cols = args.loci, args.barcodes
 
 
 def timed(fn):
@@ -73,6 +79,94 @@ def series(fn, phases=None):
     return one
 
 
+def finish(res):
+    print(json.dumps(res), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+    if args.sweep and os.path.exists(args.json):                 # the sweep joins the --ops record it belongs to
+        whole = json.load(open(args.json))
+        whole["group_size_sweep"] = res
+        res = whole
+    json.dump(res, open(args.json, "w"), indent=1)
+
+
+def stats_buffers(n):
+    from vartrix_amd import abi
+    return {k: torch.empty(n, dtype=torch.int32 if k in abi.CSR_STAT_COUNTS else torch.int64, device=dev) for k in abi.CSR_STAT_NAMES}
+
+
+def stats_call(ctx, csr, n_major, n_minor, out):
+    nnz = int(csr["indices"].shape[0])
+    return lambda: ctx.csr_row_stats(n_major, n_minor, nnz, csr["indptr"].data_ptr(), csr["indices"].data_ptr(), csr["alt"].data_ptr(),
+                                     csr["ref"].data_ptr(), csr["unk"].data_ptr(), {k: v.data_ptr() for k, v in out.items()})
+
+
+def host_stats(indptr, alt, ref, unk):
+    """numpy's seven statistics of every row (counts by bincount, sums by add.reduceat in uint64)."""
+    n, lens = len(indptr) - 1, np.diff(indptr)
+    rows, full = np.repeat(np.arange(n), lens), lens > 0
+
+    def total(a):
+        o = np.zeros(n, np.uint64)
+        o[full] = np.add.reduceat(a.astype(np.uint64), indptr[:-1][full])
+        return o
+    return {"n_entries": lens, "n_alt": np.bincount(rows[alt > 0], minlength=n), "n_ref": np.bincount(rows[ref > 0], minlength=n),
+            "n_both": np.bincount(rows[(alt > 0) & (ref > 0)], minlength=n), "sum_alt": total(alt), "sum_ref": total(ref), "sum_unk": total(unk)}
+
+
+def same_stats(out, want):
+    for k, v in want.items():
+        got = out[k].cpu().numpy()
+        got = got.view(np.uint32) if got.dtype == np.int32 else got.view(np.uint64)
+        assert np.array_equal(got.astype(np.uint64), v.astype(np.uint64)), k
+
+
+if args.sweep:
+    if lib.DEFAULT_VARIANT != "dev":
+        sys.exit("--sweep needs the developer library: VTX_LIB_VARIANT=dev")
+    # mean row lengths: 23.92 M entries (config 3) and 378 345 (4 reads per locus, profiles/r06_depth_noise.jsonl) over 100 000 x 10 000
+    shapes = {"config3_variant_major": (args.loci, args.barcodes, 239.23), "config3_cell_major": (args.barcodes, args.loci, 2392.3),
+              "four_reads_per_locus_variant_major": (args.loci, args.barcodes, 3.78), "four_reads_per_locus_cell_major": (args.barcodes, args.loci, 37.8)}
+    res = {"what": "csr_row_stats_kernel<G> at every G (tools/csr_profile.py --sweep): device ms of the reduction (vtx_last_csr_ms[3]), median of "
+                   "%d after one warm-up; synthetic CSRs with Poisson row lengths" % args.runs, "shapes": {}}
+    gen = torch.Generator(device=dev).manual_seed(7)
+    with lib.Context(default_config(n_barcodes=4)) as ctx:
+        for name, (n_major, n_minor, mean) in shapes.items():
+            lens = torch.poisson(torch.full((n_major,), mean, device=dev), generator=gen).clamp_(max=n_minor).to(torch.int64)
+            indptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(lens, 0)])
+            nnz = int(indptr[-1])
+            csr = {"indptr": indptr, "indices": torch.zeros(nnz, dtype=torch.int32, device=dev)}       # read by the check only
+            for k in ("alt", "ref", "unk"):
+                csr[k] = torch.randint(0, 3, (nnz,), dtype=torch.int32, device=dev, generator=gen)
+            out = stats_buffers(n_major)
+            call = stats_call(ctx, csr, n_major, n_minor, out)
+            want = host_stats(indptr.cpu().numpy(), *[csr[k].cpu().numpy() for k in ("alt", "ref", "unk")])
+            one = {"n_major": n_major, "n_minor": n_minor, "nnz": nnz, "reduction_ms_by_G": {}}
+            for G in ("rule", 1, 2, 4, 8, 16, 32, 64):
+                if G == "rule":
+                    os.environ.pop("VTX_CSR_STATS_G", None)
+                else:
+                    os.environ["VTX_CSR_STATS_G"] = str(G)
+                for v in out.values():
+                    v.fill_(-1)
+                torch.cuda.synchronize(dev)
+                call()
+                same_stats(out, want)                            # every G gives numpy's answer before it is timed
+                one["reduction_ms_by_G"][str(G)] = series(call, ctx.csr_ms)["device_ms_by_phase_median"]["place"]
+                print(name, "G", G, one["reduction_ms_by_G"][str(G)], flush=True)
+            os.environ.pop("VTX_CSR_STATS_G", None)
+            res["shapes"][name] = one
+            del csr, out
+    finish(res)
+    sys.exit(0)
+
+spec = synth.SynthSpec(n_loci=args.loci, n_barcodes=args.barcodes, reads_per_locus=args.reads_per_locus, read_len=150, padding=100,
+                       use_umi=False, indel_frac=0.0, sub_error=0.005, depth_sigma=0.0, seed=20260926)      # bench.py's config 3, its defaults spelled out
+t0 = time.perf_counter()
+batch = synth.make_batch(spec)
+print("batch: %d records in %.1f s" % (batch.n_records, time.perf_counter() - t0), flush=True)
+n_rows, n_cols = args.loci, args.barcodes
+
+
 res = {"what": "CSR hand-over of a config-3 run (tools/csr_profile.py): median of %d after one warm-up, one process" % args.runs,
        "loci": n_rows, "barcodes": n_cols, "records": int(batch.n_records), "entries": {}}
 with lib.Context(default_config(n_barcodes=n_cols)) as ctx:
@@ -82,6 +176,128 @@ with lib.Context(default_config(n_barcodes=n_cols)) as ctx:
     part = api._device_part(ctx, torch, dev, 0, n_rows)
     nnz = int(part["indices"].shape[0])
     res["nnz"] = nnz
+    if args.ops:
+        res["what"] = "summaries and selections of a config-3 run's CSR (tools/csr_profile.py --ops): median of %d after one warm-up, one process" % args.runs
+        E = res["entries"]
+        t = api._transpose(ctx, torch, dev, part, n_rows, n_cols)
+        coo = ctx.fetch_coo()
+        indptr_h, indices_h = part["indptr"].cpu().numpy(), part["indices"].cpu().numpy()
+        # ---- correctness first ----
+        v_out, c_out = stats_buffers(n_rows), stats_buffers(n_cols)
+        v_call, c_call = stats_call(ctx, part, n_rows, n_cols, v_out), stats_call(ctx, t, n_cols, n_rows, c_out)
+        torch.cuda.synchronize(dev)
+        v_call()
+        c_call()
+        v_want = host_stats(indptr_h, coo["alt"], coo["ref"], coo["unk"])
+        same_stats(v_out, v_want)
+        order = np.argsort(coo["col"], kind="stable")
+        same_stats(c_out, host_stats(np.searchsorted(coo["col"][order], np.arange(n_cols + 1)), coo["alt"][order], coo["ref"][order], coo["unk"][order]))
+        positions = sp.csr_matrix((np.arange(nnz, dtype=np.float64), indices_h, indptr_h), shape=(n_rows, n_cols))
+        res["select"] = {}
+
+        def selection(label, rule, keep_h):
+            """One selection of variants: checked against scipy's indexing, then ready to be timed -> (plan call, select call, outputs)."""
+            keep = torch.from_numpy(keep_h).to(dev)
+            head = (n_rows, n_cols, nnz, part["indptr"].data_ptr(), part["indices"].data_ptr(), keep.data_ptr(), 0)
+            torch.cuda.synchronize(dev)
+            sizes = ctx.csr_select_plan(*head)
+            sel = {"indptr": torch.empty(sizes[0] + 1, dtype=torch.int64, device=dev), "indices": torch.empty(sizes[2], dtype=torch.int32, device=dev)}
+            for k in api.DATA_FIELDS:
+                sel[k] = torch.empty(sizes[2], dtype=part[k].dtype, device=dev)
+            ids = torch.empty(sizes[0], dtype=torch.int32, device=dev)
+            pay = [(part[k].data_ptr(), sel[k].data_ptr(), part[k].element_size()) for k in api.DATA_FIELDS]
+            torch.cuda.synchronize(dev)
+
+            def select_call():
+                return ctx.csr_select(*head, sizes, sel["indptr"].data_ptr(), sel["indices"].data_ptr(), ids.data_ptr(), 0, pay)
+            select_call()
+            want = positions[keep_h]
+            assert sizes == (int(keep_h.sum()), n_cols, want.nnz)
+            assert np.array_equal(sel["indptr"].cpu().numpy(), want.indptr) and np.array_equal(sel["indices"].cpu().numpy(), want.indices)
+            src = want.data.astype(np.int64)
+            for k in api.DATA_FIELDS:
+                assert np.array_equal(sel[k].cpu().numpy().view(np.uint8), np.ascontiguousarray(coo[k][src]).view(np.uint8)), k
+            assert np.array_equal(ids.cpu().numpy(), np.flatnonzero(keep_h))
+            res["select"][label] = {"rule": rule, "variants_kept": sizes[0], "entries_kept": sizes[2]}
+            print("%s: selection equals scipy's: %d of %d variants, %d of %d entries kept" % (label, sizes[0], n_rows, sizes[2], nnz), flush=True)
+            return keep, (lambda: ctx.csr_select_plan(*head)), select_call, sel, (keep, ids, pay)
+        # the issue's rule, and — it keeps every variant of this batch, 239 cells a row — the median of n_alt, which keeps about half
+        med = int(np.median(v_want["n_alt"]))
+        keep, plan_call, select_call, sel, _hold = selection("min10", "n_alt >= 10 and n_ref >= 10", (v_want["n_alt"] >= 10) & (v_want["n_ref"] >= 10))
+        keep_h = v_want["n_alt"] > med
+        keep2, plan2, select2, sel2, _hold2 = selection("above_median", "n_alt > %d (the median)" % med, keep_h)
+        sizes = (int(keep_h.sum()), n_cols, int(sel2["indices"].shape[0]))
+        del order
+        # ---- the device calls ----
+        E["row_stats_variant_major"] = series(v_call, ctx.csr_ms)
+        E["row_stats_cell_major"] = series(c_call, ctx.csr_ms)
+        E["select_plan_min10"] = series(plan_call, ctx.csr_ms)
+        E["select_five_payloads_min10"] = series(select_call, ctx.csr_ms)
+        E["select_plan_above_median"] = series(plan2, ctx.csr_ms)
+        E["select_five_payloads_above_median"] = series(select2, ctx.csr_ms)
+        keep, sel = keep2, sel2                                  # the baselines below make the selection that drops rows
+        E["api_row_stats_variant_major"] = series(lambda: api._row_stats(ctx, torch, dev, part, n_rows, n_cols))
+        E["api_select"] = series(lambda: api._select(ctx, torch, dev, part, n_rows, n_cols, keep, None))
+        # ---- which operations this torch build offers on a sparse CSR tensor ----
+        m = torch.sparse_csr_tensor(part["indptr"], part["indices"].to(torch.int64), part["alt"].to(torch.float64), size=(n_rows, n_cols))
+        probes = {"sum(dim=1)": lambda: m.sum(dim=1), "sum()": lambda: m.sum(), "boolean row selection m[mask]": lambda: m[keep],
+                  "index_select(0, ids)": lambda: m.index_select(0, torch.nonzero(keep).ravel()), "to_sparse_coo()": lambda: m.to_sparse_coo(),
+                  "(m != 0)": lambda: m != 0, "select(0, 5)": lambda: m.select(0, 5), "transpose(0, 1)": lambda: m.transpose(0, 1),
+                  "int32 values": lambda: torch.sparse_csr_tensor(part["indptr"], part["indices"].to(torch.int64), part["alt"], size=(n_rows, n_cols)).sum()}
+        res["torch_sparse_csr_support"] = {"torch": torch.__version__}
+        for name, fn in probes.items():
+            try:
+                fn()
+                torch.cuda.synchronize(dev)
+                res["torch_sparse_csr_support"][name] = "ok"
+            except Exception as e:                               # noqa: BLE001  (the record IS the error)
+                res["torch_sparse_csr_support"][name] = "%s: %s" % (type(e).__name__, str(e).splitlines()[0][:160])
+        del m
+        # ---- what a user does today, on the device in torch: rows from the offsets (the COO view), index_add_, boolean masking ----
+        def torch_rows():
+            return torch.repeat_interleave(torch.arange(n_rows, device=dev), part["indptr"][1:] - part["indptr"][:-1])
+
+        def torch_stats():
+            rows = torch_rows()
+            a, r, u = part["alt"], part["ref"], part["unk"]
+            out = {}
+            for k, w in (("n_entries", torch.ones_like(a, dtype=torch.int64)), ("n_alt", (a > 0).to(torch.int64)), ("n_ref", (r > 0).to(torch.int64)),
+                         ("n_both", ((a > 0) & (r > 0)).to(torch.int64)), ("sum_alt", a.to(torch.int64)), ("sum_ref", r.to(torch.int64)),
+                         ("sum_unk", u.to(torch.int64))):
+                out[k] = torch.zeros(n_rows, dtype=torch.int64, device=dev).index_add_(0, rows, w)
+            torch.cuda.synchronize(dev)
+            return out
+
+        def torch_select():
+            rows = torch_rows()
+            k = keep[rows]
+            out = {f: part[f][k] for f in ("indices",) + api.DATA_FIELDS}
+            new_row = (torch.cumsum(keep.to(torch.int64), 0) - 1)[rows[k]]
+            out["indptr"] = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(torch.bincount(new_row, minlength=sizes[0]), 0)])
+            torch.cuda.synchronize(dev)
+            return out
+        def same_selection(o):
+            for f in sel:
+                assert torch.equal(o[f], sel[f]), f
+        for name, fn, check in (("torch_index_add_stats", torch_stats, lambda o: same_stats(o, v_want)), ("torch_mask_select", torch_select, same_selection)):
+            try:
+                check(fn())
+                E[name] = series(fn)
+            except Exception as e:                               # noqa: BLE001
+                E[name] = {"error": "%s: %s" % (type(e).__name__, str(e).splitlines()[0][:200] if str(e) else "")}
+        # ---- ... and on the host: fetch + numpy / scipy ----
+        def host_stats_today():
+            c = ctx.fetch_coo()
+            return host_stats(np.searchsorted(c["row"], np.arange(n_rows + 1)), c["alt"], c["ref"], c["unk"])
+
+        def host_select_today():
+            c = ctx.fetch_coo()
+            return [sp.coo_matrix((c[f], (c["row"], c["col"])), shape=(n_rows, n_cols)).tocsr()[keep_h] for f in api.DATA_FIELDS]
+        E["fetch_numpy_stats"] = series(host_stats_today)
+        E["fetch_scipy_select_five_matrices"] = series(host_select_today)
+        E["fetch_coo_alone"] = series(ctx.fetch_coo)
+        finish(res)
+        sys.exit(0)
     # ---- correctness first: the device's offsets and transpose against scipy's ----
     coo = ctx.fetch_coo()
     want = sp.coo_matrix((coo["value"], (coo["row"], coo["col"])), shape=(n_rows, n_cols)).tocsr()
@@ -124,6 +340,4 @@ with lib.Context(default_config(n_barcodes=n_cols)) as ctx:
                 return scipy.io.mmread(path).tocsr()
             res["entries"]["write_mtx_mmread"] = series(today_file)
             res["entries"]["write_mtx_mmread"]["file_bytes"] = os.path.getsize(path)
-print(json.dumps(res), flush=True)
-os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-json.dump(res, open(args.json, "w"), indent=1)
+finish(res)

@@ -125,6 +125,16 @@ class VtxCsr(C.Structure):
     ]
 
 
+CSR_STAT_COUNTS = ("n_entries", "n_alt", "n_ref", "n_both")        # uint32 per row
+CSR_STAT_SUMS = ("sum_alt", "sum_ref", "sum_unk")                   # uint64 per row
+CSR_STAT_NAMES = CSR_STAT_COUNTS + CSR_STAT_SUMS
+
+
+class VtxCsrStats(C.Structure):
+    """vtx_csr_stats: where vtx_csr_row_stats stores the seven statistics of every row; a NULL pointer is not written."""
+    _fields_ = [(k, C.POINTER(C.c_uint32)) for k in CSR_STAT_COUNTS] + [(k, C.POINTER(C.c_uint64)) for k in CSR_STAT_SUMS]
+
+
 class VtxTiming(C.Structure):
     _fields_ = [
         ("total_ms", C.c_float),

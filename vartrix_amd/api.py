@@ -7,6 +7,11 @@ is one stable transpose of the stacked whole (``vtx_csr_transpose``).  Every arr
 (the reference's ``matrix`` / ``ref_matrix``, src/main.rs:323-346) and the alt / ref / unknown counts behind them
 (CellCounts, src/main.rs:1032-1039), which no file of the command line holds outside the coverage mode.
 
+``run(stats=True)`` adds the seven statistics of every variant and of every cell (``vtx_csr_row_stats`` on the CSR and on its transpose),
+``run(min_alt_cells=, min_ref_cells=)`` drops the variants too few cells inform before anything is transposed or copied (the locus
+filter of the demultiplexers: ``vtx_csr_row_stats`` + ``vtx_csr_select`` on the stacked CSR), and ``select()`` cuts a finished result
+down by boolean masks.
+
 There is no CPU path: the scores, the calls, the offsets and the transpose are computed on the GPU; torch carries the device arrays
 (``__cuda_array_interface__``) and, for ``to="scipy"``, copies the finished arrays to the host.
 """
@@ -31,8 +36,12 @@ class Result:
     unknown_counts: object
     variants: list            # "{chrom}_{pos0}" per VCF record, what --out-variants writes
     barcodes: list
-    metrics: dict             # the nine counters of hostlib.METRIC_NAMES
+    metrics: dict             # the nine counters of hostlib.METRIC_NAMES (of the whole run, whatever is filtered afterwards)
     shape: tuple
+    variant_stats: dict = None    # run(stats=True): abi.CSR_STAT_NAMES -> one array per (kept) variant
+    cell_stats: dict = None       # ... per cell, of the matrix as returned
+    variant_index: object = None  # the source row of every kept variant (int64); None when nothing was filtered
+    orient: str = None            # "variants" or "cells": what the rows of the matrices are
 
 
 def _is_torch(a) -> bool:
@@ -98,17 +107,57 @@ def _empty_part(torch, dev, n_rows):
     return part
 
 
-def _transpose(ctx, torch, dev, csr, n_major, n_minor):
-    """One stable transpose of the stacked CSR on the device; ``perm`` is computed once and moves all five data arrays."""
+def _transpose(ctx, torch, dev, csr, n_major, n_minor, fields=DATA_FIELDS):
+    """One stable transpose of the stacked CSR on the device; ``perm`` is computed once and moves every data array of ``fields``."""
     nnz = int(csr["indices"].shape[0])
     out = {"indptr": torch.empty(n_minor + 1, dtype=torch.int64, device=dev), "indices": torch.empty(nnz, dtype=torch.int32, device=dev)}
-    for k in DATA_FIELDS:
+    for k in fields:
         out[k] = torch.empty_like(csr[k])
-    src = {k: v.contiguous() for k, v in csr.items()}
+    src = {k: csr[k].contiguous() for k in ("indptr", "indices") + tuple(fields)}
     torch.cuda.synchronize(dev)              # the library works on its own stream: torch's writes to these arrays have to be done
     ctx.csr_transpose(n_major, n_minor, nnz, src["indptr"].data_ptr(), src["indices"].data_ptr(), out["indptr"].data_ptr(),
-                      out["indices"].data_ptr(), 0, [(src[k].data_ptr(), out[k].data_ptr(), _ELEM_BYTES[k]) for k in DATA_FIELDS])
+                      out["indices"].data_ptr(), 0, [(src[k].data_ptr(), out[k].data_ptr(), src[k].element_size()) for k in fields])
     return out
+
+
+def _row_stats(ctx, torch, dev, csr, n_major, n_minor, names=abi.CSR_STAT_NAMES):
+    """``names`` of the seven statistics of every row of a CSR with ``alt`` / ``ref`` / ``unk`` arrays, on the device: int64 tensors
+    (the counts are exact; a sum is the library's uint64, exact below 2^63)."""
+    nnz = int(csr["indices"].shape[0])
+    raw = {k: torch.empty(n_major, dtype=torch.int32 if k in abi.CSR_STAT_COUNTS else torch.int64, device=dev) for k in names}
+    src = {k: csr[k].contiguous() for k in ("indptr", "indices", "alt", "ref", "unk")}
+    torch.cuda.synchronize(dev)
+    ctx.csr_row_stats(n_major, n_minor, nnz, src["indptr"].data_ptr(), src["indices"].data_ptr(), src["alt"].data_ptr(), src["ref"].data_ptr(),
+                      src["unk"].data_ptr(), {k: v.data_ptr() for k, v in raw.items()})
+    return {k: (v.to(torch.int64) & 0xFFFFFFFF) if k in abi.CSR_STAT_COUNTS else v for k, v in raw.items()}
+
+
+def _select(ctx, torch, dev, csr, n_major, n_minor, keep_major=None, keep_minor=None):
+    """Rows and columns of a CSR (a dict of device tensors: ``indptr``, ``indices`` and any data arrays of 4- or 8-byte elements) by
+    boolean device tensors, on the device: one plan, one select that moves every data array.  -> (the selected CSR, the source row of
+    every kept row, the source column of every kept column; int32)."""
+    nnz = int(csr["indices"].shape[0])
+    fields = [k for k in csr if k not in ("indptr", "indices")]
+    src = {k: v.contiguous() for k, v in csr.items()}
+    masks = [None if m is None else m.to(device=dev, dtype=torch.bool).contiguous() for m in (keep_major, keep_minor)]
+    ptrs = [0 if m is None else m.data_ptr() for m in masks]
+    torch.cuda.synchronize(dev)
+    head = (n_major, n_minor, nnz, src["indptr"].data_ptr(), src["indices"].data_ptr())
+    sizes = ctx.csr_select_plan(*head, *ptrs)
+    out = {"indptr": torch.empty(sizes[0] + 1, dtype=torch.int64, device=dev), "indices": torch.empty(sizes[2], dtype=torch.int32, device=dev)}
+    for k in fields:
+        out[k] = torch.empty(sizes[2], dtype=src[k].dtype, device=dev)
+    major_ids, minor_ids = (torch.empty(n, dtype=torch.int32, device=dev) for n in sizes[:2])
+    ctx.csr_select(*head, *ptrs, sizes, out["indptr"].data_ptr(), out["indices"].data_ptr(), major_ids.data_ptr(), minor_ids.data_ptr(),
+                   [(src[k].data_ptr(), out[k].data_ptr(), src[k].element_size()) for k in fields])
+    return out, major_ids, minor_ids
+
+
+def _stats_out(st, to):
+    """The statistics as the caller gets them: device tensors (int64) for torch, numpy for scipy (uint32 counts, uint64 sums)."""
+    if to == "torch":
+        return dict(st)
+    return {k: v.cpu().numpy().astype(np.uint32) if k in abi.CSR_STAT_COUNTS else v.cpu().numpy().view(np.uint64) for k, v in st.items()}
 
 
 def _finish(csr, field, shape, to, torch):
@@ -124,7 +173,7 @@ def _finish(csr, field, shape, to, torch):
 
 def run(vcf, bam, fasta, cell_barcodes, *, scoring_method="consensus", padding=100, mapq=0, primary_alignments=False,
         no_duplicates=False, umi=False, bam_tag="CB", valid_chars="ATGCatgc", aligner="banded", ingest="auto", stream_loci=None,
-        threads=1, device=0, orient="variants", to="scipy") -> Result:
+        threads=1, device=0, orient="variants", to="scipy", stats=False, min_alt_cells=0, min_ref_cells=0) -> Result:
     """Genotype the cells of ``bam`` at the variants of ``vcf`` and return every matrix of the run as CSR.
 
     The arguments up to ``valid_chars`` are the command line's (the reference's, src/main.rs:54-160).  ``ingest``: "host" packs the
@@ -134,7 +183,14 @@ def run(vcf, bam, fasta, cell_barcodes, *, scoring_method="consensus", padding=1
     ``stream_loci=N``: the VCF in ranges of N records, one context reused.  ``orient``: "variants" (variants x cells, the files'
     orientation) or "cells" (cells x variants: AnnData's X).  ``to``: "scipy" (``scipy.sparse.csr_matrix`` on the host) or "torch"
     (``torch.sparse_csr_tensor`` on ``device``; the values never pass through the host).  Explicit zeros and NaN are kept.  The
-    result does not depend on ``ingest``, ``stream_loci`` or ``to``."""
+    result does not depend on ``ingest``, ``stream_loci`` or ``to``.
+
+    ``min_alt_cells=a, min_ref_cells=r`` (either > 0) keep the variants with alt support in at least ``a`` cells and ref support in at
+    least ``r`` (``n_alt >= a and n_ref >= r``).  The filter runs on the stacked variant-major CSR on the device, before the transpose
+    and before anything reaches the host: ``variants``, ``shape`` and every matrix follow the kept set, ``variant_index`` holds its
+    source rows, ``metrics`` stay those of the whole run.  ``stats=True`` fills ``variant_stats`` and ``cell_stats``: per variant and
+    per cell of the matrix as returned (after the filter) the number of entries, of entries with alt > 0, with ref > 0, with both, and
+    the sums of the alt / ref / unknown counts — device tensors for ``to="torch"``, numpy for ``to="scipy"``."""
     import torch
     if scoring_method not in abi.MODES:
         raise ValueError("scoring_method %r: one of %s" % (scoring_method, sorted(abi.MODES)))
@@ -146,6 +202,8 @@ def run(vcf, bam, fasta, cell_barcodes, *, scoring_method="consensus", padding=1
         raise ValueError("orient %r: variants or cells" % (orient,))
     if to not in ("scipy", "torch"):
         raise ValueError("to %r: scipy or torch" % (to,))
+    if int(min_alt_cells) < 0 or int(min_ref_cells) < 0:
+        raise ValueError("min_alt_cells %r / min_ref_cells %r: numbers of cells, 0 or more" % (min_alt_cells, min_ref_cells))
     if stream_loci is not None and int(stream_loci) < 1:
         raise ValueError("stream_loci %r: a positive number of VCF records, or None" % (stream_loci,))
     dev = torch.device("cuda", int(device))
@@ -231,16 +289,80 @@ def run(vcf, bam, fasta, cell_barcodes, *, scoring_method="consensus", padding=1
         ctx = state["ctx"]
         n_rows, n_cols = int(state["n_variants"]), len(state["barcodes"])
         csr = stack_parts(parts)
+        variants, variant_index = list(state["variants"]), None
+        if int(min_alt_cells) > 0 or int(min_ref_cells) > 0:      # on the variant-major whole, before the transpose and any copy
+            st = _row_stats(ctx, torch, dev, csr, n_rows, n_cols, ("n_alt", "n_ref"))
+            keep = (st["n_alt"] >= int(min_alt_cells)) & (st["n_ref"] >= int(min_ref_cells))
+            csr, kept, _ = _select(ctx, torch, dev, csr, n_rows, n_cols, keep, None)
+            variant_index = kept.cpu().numpy().astype(np.int64)
+            variants = [variants[i] for i in variant_index]
+            n_rows = len(variants)
+        variant_stats = cell_stats = None
+        if stats:
+            variant_stats = _stats_out(_row_stats(ctx, torch, dev, csr, n_rows, n_cols), to)
         shape = (n_rows, n_cols)
         if orient == "cells":
             csr = _transpose(ctx, torch, dev, csr, n_rows, n_cols)
             shape = (n_cols, n_rows)
+        if stats:                                # the other axis: the same call on the transpose (the one orient="cells" needs anyway)
+            by_cell = csr if orient == "cells" else _transpose(ctx, torch, dev, csr, n_rows, n_cols, ("alt", "ref", "unk"))
+            cell_stats = _stats_out(_row_stats(ctx, torch, dev, by_cell, n_cols, n_rows), to)
         coverage = abi.MODES[scoring_method] == abi.MODE_COVERAGE
         return Result(matrix=_finish(csr, "value", shape, to, torch),
                       ref_matrix=_finish(csr, "ref_value", shape, to, torch) if coverage else None,
                       alt_counts=_finish(csr, "alt", shape, to, torch), ref_counts=_finish(csr, "ref", shape, to, torch),
-                      unknown_counts=_finish(csr, "unk", shape, to, torch), variants=list(state["variants"]),
-                      barcodes=[b.decode() if isinstance(b, bytes) else b for b in state["barcodes"]], metrics=metrics, shape=shape)
+                      unknown_counts=_finish(csr, "unk", shape, to, torch), variants=variants,
+                      barcodes=[b.decode() if isinstance(b, bytes) else b for b in state["barcodes"]], metrics=metrics, shape=shape,
+                      variant_stats=variant_stats, cell_stats=cell_stats, variant_index=variant_index, orient=orient)
     finally:
         if state["ctx"] is not None:
             state["ctx"].close()
+
+
+_MATRIX_FIELDS = ("matrix", "ref_matrix", "alt_counts", "ref_counts", "unknown_counts")
+
+
+def _mask(mask, n, what):
+    """A boolean mask over ``n`` names as a numpy array (None: everything)."""
+    if mask is None:
+        return np.ones(n, bool)
+    m = np.asarray(mask.cpu() if _is_torch(mask) else mask)
+    if m.ndim != 1 or m.shape[0] != n:
+        raise ValueError("select: the mask over the %s has shape %s, the result has %d %s" % (what, m.shape, n, what))
+    if m.dtype != bool:
+        raise ValueError("select: the mask over the %s has dtype %s: a boolean mask, one value per name" % (what, m.dtype))
+    return m
+
+
+def select(result: Result, variants=None, cells=None) -> Result:
+    """The variants and cells of a ``Result`` that boolean masks keep (None: all), as a new ``Result`` of the same container type with
+    the names trimmed; ``variant_index`` follows, ``metrics`` stay those of the run.  A torch result is cut on its device — one
+    ``vtx_csr_select_plan`` and one ``vtx_csr_select`` move the data arrays of all its matrices, on a bare context for that device —
+    a scipy result by scipy's own indexing on the host.  Statistics describe the matrix they were counted on and are not carried
+    over.  ``ValueError`` for a mask of the wrong length."""
+    n_var, n_cell = len(result.variants), len(result.barcodes)
+    vm, cm = _mask(variants, n_var, "variants"), _mask(cells, n_cell, "cells")
+    orient = result.orient or ("cells" if tuple(result.shape) == (n_cell, n_var) != (n_var, n_cell) else "variants")
+    rows, cols = (vm, cm) if orient == "variants" else (cm, vm)
+    mats = {f: getattr(result, f) for f in _MATRIX_FIELDS if getattr(result, f) is not None}
+    shape = (int(rows.sum()), int(cols.sum()))
+    if _is_torch(result.matrix):
+        import torch
+        first = result.matrix
+        dev = first.device
+        csr = {"indptr": first.crow_indices(), "indices": first.col_indices().to(torch.int32)}
+        for f, m in mats.items():
+            if m.values().shape[0] != csr["indices"].shape[0]:
+                raise ValueError("select: %s does not have the sparsity of matrix" % f)
+            csr[f] = m.values()
+        index = torch.cuda.current_device() if dev.index is None else dev.index
+        with lib.Context(abi.default_config(n_barcodes=max(n_cell, 1), device=index)) as ctx:    # no batch, no run: device, stream, work space
+            out, _, _ = _select(ctx, torch, dev, csr, int(first.shape[0]), int(first.shape[1]), torch.as_tensor(rows, device=dev),
+                                torch.as_tensor(cols, device=dev))
+        cut = {f: torch.sparse_csr_tensor(out["indptr"], out["indices"].to(torch.int64), out[f], size=shape) for f in mats}
+    else:
+        cut = {f: m[rows][:, cols] for f, m in mats.items()}
+    index = np.arange(n_var, dtype=np.int64) if result.variant_index is None else np.asarray(result.variant_index, np.int64)
+    return Result(**{f: cut.get(f) for f in _MATRIX_FIELDS}, variants=[v for v, k in zip(result.variants, vm) if k],
+                  barcodes=[b for b, k in zip(result.barcodes, cm) if k], metrics=dict(result.metrics), shape=shape,
+                  variant_index=None if variants is None and result.variant_index is None else index[vm], orient=result.orient)

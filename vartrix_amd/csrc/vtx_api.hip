@@ -32,6 +32,7 @@
 #include "vtx_inflate_core.h"
 #include "vtx_mtx_join.h"
 #include "vtx_csr_core.h"
+#include "vtx_csr_ops_core.h"
 #include "../../include/vtx_band_semantics.h"
 
 extern "C" hipError_t vtxk_inclusive_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, void* temp,
@@ -163,6 +164,7 @@ struct vtx_ctx {
     DevBuf d_o_row, d_o_col, d_o_alt, d_o_ref, d_o_unk, d_o_val, d_o_refval;
     DevBuf d_csr_indptr;                     // vtx_device_csr: the row offsets of d_o_row (a buffer of its own: no other call works in it)
     DevBuf d_csr_flag, d_csr_keys, d_csr_iota, d_csr_perm, d_csr_tmp;   // vtx_csr_transpose: flag word, sorted columns, positions, perm (when the caller wants none), the sort's work space
+    DevBuf d_sel_pos, d_sel_major, d_sel_minor, d_sel_tmp;   // vtx_csr_select_plan / vtx_csr_select: pos[nnz + 1], major_map[n_major + 1], minor_map[n_minor + 1], the scan's work space
     bool band_long_lists = false;      // (performance feedback between runs: see vtx_run)
     int read_format = VTX_READS_BYTES;     // vtx_set_read_format
     DevBuf d_read_packed;                  // VTX_READS_NIBBLES: the arena as uploaded, unpacked into d_read
@@ -699,6 +701,8 @@ int vtx_abi_sizes(uint32_t* out, uint32_t n) {
     return VTX_ABI_VERSION;
 }
 
+uint32_t vtx_sizeof_csr_stats(void) { return (uint32_t)sizeof(vtx_csr_stats); }
+
 const char* vtx_status_name(int status) {
     switch (status) {
     case VTX_OK: return "VTX_OK";
@@ -777,6 +781,7 @@ void vtx_destroy(vtx_ctx* c) {
     for (DevBuf* b : bufs) b->release();
     c->d_slow_ws.release(); c->d_slow_retry.release(); c->d_read_packed.release();
     c->d_csr_indptr.release(); c->d_csr_flag.release(); c->d_csr_keys.release(); c->d_csr_iota.release(); c->d_csr_perm.release(); c->d_csr_tmp.release();
+    c->d_sel_pos.release(); c->d_sel_major.release(); c->d_sel_minor.release(); c->d_sel_tmp.release();
     DevBuf* ib[] = {&c->d_bam_comp, &c->d_bam_data, &c->d_bam_blocks, &c->d_bam_seeds, &c->d_bam_seed_cnt, &c->d_bam_seed_scan, &c->d_bam_iv, &c->d_bam_cnt,
                     &c->d_bam_rec, &c->d_bam_nhit, &c->d_bam_rsz, &c->d_bam_tsz, &c->d_bam_hscan, &c->d_bam_rscan, &c->d_bam_tscan, &c->d_bam_info, &c->d_bam_segs};
     for (DevBuf* b : ib) b->release();
@@ -2768,9 +2773,9 @@ static int csr_events(vtx_ctx* c) {
     for (auto& ev : c->ev_csr) if (!ev) HIP_TRY(c, hipEventCreate(&ev));
     return VTX_OK;
 }
-static int csr_times(vtx_ctx* c, bool checked, bool sorted, bool placed) {        // after the stream is synchronised
+static int csr_times(vtx_ctx* c, bool checked, bool sorted, bool placed, bool offsets = true) {        // after the stream is synchronised
     const int pair[4][2] = {{EV_CSR_CHECK0, EV_CSR_CHECK1}, {EV_CSR_SORT0, EV_CSR_SORT1}, {EV_CSR_SORT1, EV_CSR_OFFSETS1}, {EV_CSR_OFFSETS1, EV_CSR_PLACE1}};
-    const bool on[4] = {checked, sorted, true, placed};
+    const bool on[4] = {checked, sorted, offsets, placed};
     for (int i = 0; i < 4; ++i) {
         c->csr_ms[i] = 0.f;
         if (on[i]) HIP_TRY(c, hipEventElapsedTime(&c->csr_ms[i], c->ev_csr[pair[i][0]], c->ev_csr[pair[i][1]]));
@@ -2861,6 +2866,114 @@ int vtx_csr_transpose(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t n
     HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = csr_times(c, true, true, true)) return rc;
+    return VTX_OK;
+}
+
+// ---- summaries and selections of a caller's CSR (include/vtx.h, vtx_csr_ops.hip) ----
+// the check every one of these calls begins with: the caller's arrays are read, and judged, before a single byte is written
+static int csr_checked(vtx_ctx* c, const char* who, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr,
+                       const uint32_t* d_indices) {
+    hipStream_t s = c->stream;
+    if (int rc = csr_events(c)) return rc;
+    if (int rc = csr_flag_zero(c)) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK0], s));
+    HIP_TRY(c, vtxr_check(d_indptr, n_major, nnz, d_indices, n_minor, c->d_csr_flag.as<uint32_t>(), s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK1], s));
+    uint32_t flag = 0;
+    if (int rc = csr_flag_read(c, &flag)) return rc;
+    if (flag) return fail(c, VTX_E_INVAL, "%s: %s", who, csr_bad_reason(flag));
+    return VTX_OK;
+}
+
+int vtx_csr_row_stats(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
+                      const uint32_t* d_alt, const uint32_t* d_ref, const uint32_t* d_unk, const vtx_csr_stats* out) {
+    if (!c) return VTX_E_INVAL;
+    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "vtx_csr_row_stats: %llu entries: positions are 32-bit", (unsigned long long)nnz);
+    if (!out || !d_indptr || (nnz && (!d_indices || !d_alt || !d_ref || !d_unk))) return fail(c, VTX_E_INVAL, "vtx_csr_row_stats: null array");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    if (int rc = csr_checked(c, "vtx_csr_row_stats", n_major, n_minor, nnz, d_indptr, d_indices)) return rc;
+    uint32_t G = vtxr::group_lanes(nnz, n_major);
+    if (const char* e = VTX_DEV_ENV("VTX_CSR_STATS_G")) G = (uint32_t)atoi(e);    // developer library: the sweep behind the rule (tools/csr_profile.py)
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, vtxr_row_stats(d_indptr, n_major, d_alt, d_ref, d_unk, out, G, s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = csr_times(c, true, false, true, false)) return rc;      // no sort, no offsets here
+    return VTX_OK;
+}
+
+// The scans of a selection; the three sizes come back to the host.  Writes into the context's work space only.
+static int csr_select_scans(vtx_ctx* c, const char* who, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr,
+                            const uint32_t* d_indices, const uint8_t* d_keep_major, const uint8_t* d_keep_minor, uint32_t sizes[3]) {
+    hipStream_t s = c->stream;
+    if (int rc = csr_checked(c, who, n_major, n_minor, nnz, d_indptr, d_indices)) return rc;
+    const size_t tmp = std::max(vtxr_scan_temp_bytes(nnz + 1), std::max(vtxr_scan_temp_bytes((uint64_t)n_major + 1), vtxr_scan_temp_bytes((uint64_t)n_minor + 1)));
+    HIP_TRY(c, c->d_sel_pos.reserve(((size_t)nnz + 1) * sizeof(uint32_t)));
+    HIP_TRY(c, c->d_sel_major.reserve(((size_t)n_major + 1) * sizeof(uint32_t)));
+    HIP_TRY(c, c->d_sel_minor.reserve(((size_t)n_minor + 1) * sizeof(uint32_t)));
+    HIP_TRY(c, c->d_sel_tmp.reserve(std::max<size_t>(tmp, 1)));      // never a null work space: with one the scan only reports its size
+    uint32_t *pos = c->d_sel_pos.as<uint32_t>(), *major_map = c->d_sel_major.as<uint32_t>(), *minor_map = c->d_sel_minor.as<uint32_t>();
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT0], s));
+    HIP_TRY(c, vtxr_mask_map(d_keep_minor, n_minor, minor_map, c->d_sel_tmp.p, tmp, s));
+    HIP_TRY(c, vtxr_keep_positions(d_indptr, n_major, d_indices, nnz, d_keep_major, d_keep_minor, pos, c->d_sel_tmp.p, tmp, s));
+    HIP_TRY(c, vtxr_mask_map(d_keep_major, n_major, major_map, c->d_sel_tmp.p, tmp, s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT1], s));
+    HIP_TRY(c, hipMemcpyAsync(&sizes[0], major_map + n_major, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&sizes[1], minor_map + n_minor, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&sizes[2], pos + nnz, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return VTX_OK;
+}
+
+int vtx_csr_select_plan(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
+                        const uint8_t* d_keep_major, const uint8_t* d_keep_minor, uint32_t* n_major_out, uint32_t* n_minor_out,
+                        uint64_t* nnz_out) {
+    if (!c) return VTX_E_INVAL;
+    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "vtx_csr_select_plan: %llu entries: positions are 32-bit", (unsigned long long)nnz);
+    if (!d_indptr || (nnz && !d_indices) || !n_major_out || !n_minor_out || !nnz_out) return fail(c, VTX_E_INVAL, "vtx_csr_select_plan: null array");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    uint32_t sizes[3] = {0, 0, 0};
+    if (int rc = csr_select_scans(c, "vtx_csr_select_plan", n_major, n_minor, nnz, d_indptr, d_indices, d_keep_major, d_keep_minor, sizes)) return rc;
+    if (int rc = csr_times(c, true, true, false, false)) return rc;
+    *n_major_out = sizes[0]; *n_minor_out = sizes[1]; *nnz_out = sizes[2];
+    return VTX_OK;
+}
+
+int vtx_csr_select(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
+                   const uint8_t* d_keep_major, const uint8_t* d_keep_minor, uint32_t n_major_out, uint32_t n_minor_out, uint64_t nnz_out,
+                   uint64_t* d_indptr_out, uint32_t* d_indices_out, uint32_t* d_major_ids, uint32_t* d_minor_ids,
+                   const void* const* d_payload_in, void* const* d_payload_out, const uint32_t* payload_elem_bytes, uint32_t n_payload) {
+    if (!c) return VTX_E_INVAL;
+    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "vtx_csr_select: %llu entries: positions are 32-bit", (unsigned long long)nnz);
+    if (!d_indptr || !d_indptr_out || (nnz && !d_indices) || (nnz_out && !d_indices_out)) return fail(c, VTX_E_INVAL, "vtx_csr_select: null array");
+    if (n_payload && (!d_payload_in || !d_payload_out || !payload_elem_bytes)) return fail(c, VTX_E_INVAL, "vtx_csr_select: null payload list");
+    for (uint32_t a = 0; a < n_payload; ++a) {
+        if (payload_elem_bytes[a] != 4 && payload_elem_bytes[a] != 8)
+            return fail(c, VTX_E_INVAL, "vtx_csr_select: payload %u has elements of %u bytes (4 or 8)", a, payload_elem_bytes[a]);
+        if ((nnz && !d_payload_in[a]) || (nnz_out && !d_payload_out[a])) return fail(c, VTX_E_INVAL, "vtx_csr_select: payload %u is null", a);
+    }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    uint32_t sizes[3] = {0, 0, 0};
+    if (int rc = csr_select_scans(c, "vtx_csr_select", n_major, n_minor, nnz, d_indptr, d_indices, d_keep_major, d_keep_minor, sizes)) return rc;
+    // stateless: the sizes are this call's own; a caller whose arrays were made for other ones is refused before a byte is written
+    if (sizes[0] != n_major_out || sizes[1] != n_minor_out || sizes[2] != nnz_out)
+        return fail(c, VTX_E_INVAL, "vtx_csr_select: the selection has %u rows, %u columns and %u entries, the caller said %u, %u and %llu (vtx_csr_select_plan)",
+                    sizes[0], sizes[1], sizes[2], n_major_out, n_minor_out, (unsigned long long)nnz_out);
+    const uint32_t *pos = c->d_sel_pos.as<uint32_t>(), *major_map = c->d_sel_major.as<uint32_t>(), *minor_map = c->d_sel_minor.as<uint32_t>();
+    float scan_ms = 0.f;                                      // the stream was idle while the sizes came back: the offsets' time starts anew
+    HIP_TRY(c, hipEventElapsedTime(&scan_ms, c->ev_csr[EV_CSR_SORT0], c->ev_csr[EV_CSR_SORT1]));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT1], s));
+    HIP_TRY(c, vtxr_select_offsets(d_indptr, n_major, d_keep_major, major_map, pos, d_indptr_out, s));
+    HIP_TRY(c, vtxr_select_ids(d_keep_major, n_major, major_map, d_major_ids, s));
+    HIP_TRY(c, vtxr_select_ids(d_keep_minor, n_minor, minor_map, d_minor_ids, s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    if (nnz_out) HIP_TRY(c, vtxr_select_place(d_indices, nnz, pos, minor_map, d_indices_out, d_payload_in, d_payload_out, payload_elem_bytes, n_payload, s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = csr_times(c, true, false, true)) return rc;
+    c->csr_ms[1] = scan_ms;
     return VTX_OK;
 }
 

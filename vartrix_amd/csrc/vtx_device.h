@@ -275,5 +275,18 @@ hipError_t vtxr_sort_positions(const uint32_t* key, uint32_t* key_sorted, uint32
                                size_t temp_bytes, hipStream_t s);
 hipError_t vtxr_place(const uint64_t* indptr, uint32_t n_major, const uint32_t* perm, uint64_t n, uint32_t* indices_t, const void* const* in,
                       void* const* out, const uint32_t* elem_bytes, uint32_t n_payload, hipStream_t s);
+// ---- vtx_csr_ops.hip: the statistics of every row of a CSR; the stable selection of rows and columns by byte masks ----
+// Every CSR here has passed vtxr_check.  G: vtxr::group_lanes (vtx_csr_ops_core.h).  The maps and pos are exclusive sums made in place.
+hipError_t vtxr_row_stats(const uint64_t* indptr, uint32_t n_major, const uint32_t* alt, const uint32_t* ref, const uint32_t* unk,
+                          const vtx_csr_stats* out, uint32_t G, hipStream_t s);
+size_t vtxr_scan_temp_bytes(uint64_t n);
+hipError_t vtxr_mask_map(const uint8_t* mask, uint32_t n, uint32_t* map, void* temp, size_t temp_bytes, hipStream_t s);
+hipError_t vtxr_keep_positions(const uint64_t* indptr, uint32_t n_major, const uint32_t* indices, uint64_t nnz, const uint8_t* keep_major,
+                               const uint8_t* keep_minor, uint32_t* pos, void* temp, size_t temp_bytes, hipStream_t s);
+hipError_t vtxr_select_offsets(const uint64_t* indptr, uint32_t n_major, const uint8_t* keep_major, const uint32_t* major_map, const uint32_t* pos,
+                               uint64_t* indptr_out, hipStream_t s);
+hipError_t vtxr_select_ids(const uint8_t* mask, uint32_t n, const uint32_t* map, uint32_t* ids, hipStream_t s);
+hipError_t vtxr_select_place(const uint32_t* indices, uint64_t nnz, const uint32_t* pos, const uint32_t* minor_map, uint32_t* indices_out,
+                             const void* const* in, void* const* out, const uint32_t* elem_bytes, uint32_t n_payload, hipStream_t s);
 }
 #endif

@@ -39,6 +39,7 @@ SYMBOLS = (
     "vtx_submit_bam", "vtx_submit_bam_segments", "vtx_debug_ingest", "vtx_debug_inflate", "vtx_comm_ranks", "vtx_write_mtx", "vtx_prefetch_file",
     "vtx_last_crc_ms", "vtx_write_mtx_gz", "vtx_mtx_part", "vtx_mtx_part_free", "vtx_mtx_join",
     "vtx_device_csr", "vtx_csr_transpose", "vtx_last_csr_ms",
+    "vtx_csr_row_stats", "vtx_csr_select_plan", "vtx_csr_select", "vtx_sizeof_csr_stats",
 )
 # (entry points with a digit in their name: tests/test_abi.py finds the header's declarations with [a-z_]+ and compares them with SYMBOLS,
 # so these are listed — and checked against the header and every build of the library, tests/test_abi_f64.py — on their own)
@@ -93,6 +94,16 @@ def load(variant=None):
     L.vtx_csr_transpose.restype = C.c_int
     L.vtx_csr_transpose.argtypes = [ctxp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32]
+    csr_in = [ctxp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]       # ctx, n_major, n_minor, nnz, d_indptr, d_indices
+    L.vtx_csr_row_stats.restype = C.c_int
+    L.vtx_csr_row_stats.argtypes = csr_in + [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.VtxCsrStats)]
+    L.vtx_csr_select_plan.restype = C.c_int
+    L.vtx_csr_select_plan.argtypes = csr_in + [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.vtx_csr_select.restype = C.c_int
+    L.vtx_csr_select.argtypes = csr_in + [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32]
+    L.vtx_sizeof_csr_stats.restype = C.c_uint32
+    L.vtx_sizeof_csr_stats.argtypes = []
     L.vtx_last_csr_ms.restype = C.c_int
     L.vtx_last_csr_ms.argtypes = [ctxp, C.POINTER(C.c_float), C.c_uint32]
     L.vtx_last_timing.restype = C.c_int
@@ -389,10 +400,45 @@ class Context:
                                               indices_t or None, perm or None, p_in, p_out, p_sz, n))
 
     def csr_ms(self) -> dict:
-        """Device time of the last ``device_csr`` / ``csr_transpose`` by phase, milliseconds (vtx_last_csr_ms: events on the context's stream)."""
+        """Device time of the last CSR call by phase, milliseconds (vtx_last_csr_ms: events on the context's stream).  ``sort`` is the
+        scans of a selection, ``place`` the reduction of ``csr_row_stats``."""
         ms = (C.c_float * 4)()
         self._check(self._L.vtx_last_csr_ms(self._h, ms, 4))
         return dict(zip(("check", "sort", "offsets", "place"), (float(v) for v in ms)))
+
+    def csr_row_stats(self, n_major: int, n_minor: int, nnz: int, indptr: int, indices: int, alt: int, ref: int, unk: int, out: dict):
+        """The statistics of every row of a CSR in device memory (vtx_csr_row_stats); every array is a raw device ADDRESS.  ``out``:
+        name (``abi.CSR_STAT_NAMES``) -> address of n_major uint32 (the four counts) / uint64 (the three sums); a name that is missing
+        or 0 is not computed into memory."""
+        unknown = set(out) - set(abi.CSR_STAT_NAMES)
+        if unknown:
+            raise ValueError("csr_row_stats: unknown statistics %s" % sorted(unknown))
+        st = abi.VtxCsrStats()
+        for k, typ in st._fields_:
+            setattr(st, k, C.cast(C.c_void_p(int(out.get(k) or 0) or None), typ))
+        self._check(self._L.vtx_csr_row_stats(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
+                                              ref or None, unk or None, C.byref(st)))
+
+    def csr_select_plan(self, n_major: int, n_minor: int, nnz: int, indptr: int, indices: int, keep_major: int = 0, keep_minor: int = 0):
+        """The sizes (n_major_out, n_minor_out, nnz_out) of the selection of a CSR in device memory by byte masks (vtx_csr_select_plan);
+        a mask address of 0 keeps everything."""
+        a, b, n = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._check(self._L.vtx_csr_select_plan(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, keep_major or None,
+                                                keep_minor or None, C.byref(a), C.byref(b), C.byref(n)))
+        return int(a.value), int(b.value), int(n.value)
+
+    def csr_select(self, n_major: int, n_minor: int, nnz: int, indptr: int, indices: int, keep_major: int, keep_minor: int, sizes, indptr_out: int,
+                   indices_out: int, major_ids: int = 0, minor_ids: int = 0, payloads=()):
+        """Stable selection of rows and columns of a CSR in device memory (vtx_csr_select).  ``sizes``: what ``csr_select_plan`` returned
+        for the same inputs, the sizes the outputs were allocated for — any other selection is refused with nothing written.
+        ``payloads``: (address in, address out, element bytes 4 | 8) per array that moves with the entries."""
+        n = len(payloads)
+        p_in = (C.c_void_p * max(n, 1))(*[int(p[0]) or None for p in payloads])
+        p_out = (C.c_void_p * max(n, 1))(*[int(p[1]) or None for p in payloads])
+        p_sz = (C.c_uint32 * max(n, 1))(*[int(p[2]) for p in payloads])
+        self._check(self._L.vtx_csr_select(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, keep_major or None,
+                                           keep_minor or None, int(sizes[0]), int(sizes[1]), int(sizes[2]), indptr_out or None, indices_out or None,
+                                           major_ids or None, minor_ids or None, p_in, p_out, p_sz, n))
 
     def comm_init(self, ident: bytes, rank: int, world: int):
         """Join the RCCL communicator of the sharded run (collective; vtx_comm_init)."""
