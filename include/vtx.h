@@ -330,7 +330,9 @@ typedef struct vtx_ingest_stats {
  * read-only mapping of their own) into their pinned buffers and push them.  A later
  * vtx_submit_bam whose blocks lie inside the range uses the bytes (it waits for the copy first), any other uploads its own.  A
  * context may be created for this before the barcode list is known: cfg.n_barcodes = 0 means "taken from the first
- * vtx_set_barcodes".                                                                                                              */
+ * vtx_set_barcodes".  Every entry point that moves data through the context's copy workers or takes the prefetch's device buffer waits
+ * for a copy in flight first: vtx_submit, vtx_submit_raw, vtx_debug_crc32 and a plain vtx_mtx_part keep the prefetched bytes for a later
+ * vtx_submit_bam; a later vtx_prefetch_file, vtx_debug_inflate and the gzip matrix writers drop them.                                  */
 int vtx_prefetch_file(vtx_ctx* ctx, const char* path, uint64_t file_off, uint64_t n);
 int vtx_submit_bam(vtx_ctx* ctx, const vtx_bam_ingest* ingest, vtx_ingest_stats* stats);
 

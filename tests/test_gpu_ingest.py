@@ -322,6 +322,64 @@ def test_declines_loudly():
             assert st.bam_records > 500
 
 
+def test_rejects_of_the_plan_core_reach_the_caller_word_for_word():
+    """The plan checks are host code (vtx_ingest_plan_core.h, tests/test_ingest_plan_core.py): a block out of order and a seed outside
+    its segment give, through the API, the status and the text — numbers included — the core's host build gives for the same plan; the
+    context ingests the untouched plan afterwards."""
+    from test_ingest_plan_core import load_core, run_core
+    core = load_core()
+    with hostlib.plan_ingest(**ref_inputs()) as plan:
+        a = plan.arrays()
+        assert len(a["blocks"]) >= 3 and len(a["seeds"]) >= 2
+        blocks = a["blocks"].copy()
+        blocks[[1, 2]] = blocks[[2, 1]]
+        g = abi.VtxBamIngest.from_buffer_copy(plan.ingest)
+        g.blocks = blocks.ctypes.data
+        # the same plan as ONE segment to the end of its stream, its last seed moved to the segment's end
+        seeds = a["seeds"].copy()
+        end = min(int(a["end_upos"]), int(a["blocks"]["isize"].sum()))
+        seeds[-1] = end
+        seg = np.array([(0, len(blocks), 0, len(seeds), end, 0, 0, abi.SEGMENT_TO_EOF, 0)], abi.BAM_SEGMENT_DTYPE)
+        sg = abi.VtxBamSegments()
+        sg.base = abi.VtxBamIngest.from_buffer_copy(plan.ingest)
+        sg.base.seeds, sg.segments, sg.n_segments = seeds.ctypes.data, seg.ctypes.data, 1
+        with lib.Context(default_config(n_barcodes=len(plan.barcodes))) as ctx:
+            ctx.set_barcodes(plan.barcodes)
+            want = ctx.submit_bam(plan.ingest, plan.n_loci)
+            raw = ctx.debug_ingest(abi.INGEST_RAW_RECORDS).tobytes()
+            for bad, bad_sg, words in ((g, None, "block 2: out of order"), (None, sg, "seed %d: not ascending or outside segment 0" % (len(seeds) - 1))):
+                status, why, _ = run_core(core, bad, bad_sg)
+                assert status == abi.VTX_E_INVAL and words in why
+                with pytest.raises(lib.VtxError) as ei:
+                    ctx.submit_bam(bad, plan.n_loci) if bad_sg is None else ctx.submit_bam_segments(bad_sg, plan.n_loci)
+                assert ei.value.status == status and str(ei.value) == str(lib.VtxError(status, why))
+                st = ctx.submit_bam(plan.ingest, plan.n_loci)
+                assert int(st.raw_records) == int(want.raw_records) > 0 and ctx.debug_ingest(abi.INGEST_RAW_RECORDS).tobytes() == raw
+
+
+def test_a_raw_batch_between_prefetch_and_ingest_keeps_the_prefetch():
+    """vtx_submit_raw (like vtx_submit) waits for a vtx_prefetch_file in flight — its upload goes through the copy workers the prefetch
+    uses — and leaves the prefetched bytes alone: prefetch_file, submit_raw of the host-packed batch, submit_bam of the plan gives the raw
+    records of submit_bam on a fresh context, and the ingest used the prefetched bytes (stats.prefetch_ms: 0 = not used)."""
+    inputs = ref_inputs()
+    packed = hostlib.pack_files(raw=True, nibbles=True, threads=3, **inputs)[0]
+    with hostlib.plan_ingest(**inputs) as plan:
+        outs = []
+        for pf in (False, True):
+            with lib.Context(default_config(n_barcodes=len(plan.barcodes))) as ctx:
+                ctx.set_barcodes(plan.barcodes)
+                if pf:
+                    ctx.prefetch_file(inputs["bam"])
+                    rs = ctx.submit_raw(packed)
+                    assert int(rs.kept) > 0
+                st = ctx.submit_bam(plan.ingest, plan.n_loci)
+                assert (st.prefetch_ms > 0) == pf
+                ctx.run()
+                coo = ctx.fetch_coo()
+                outs.append((int(st.raw_records), ctx.debug_ingest(abi.INGEST_RAW_RECORDS).tobytes(), coo["row"].tobytes(), coo["value"].tobytes()))
+        assert outs[0] == outs[1] and outs[0][0] > 0
+
+
 def test_prefetched_bytes_give_the_same_ingest():
     """vtx_prefetch_file: the BAM's bytes travel before the plan exists; vtx_submit_bam then uses them (whole file, a sub-range that
     does not cover the plan's blocks — ignored — and a context created with n_barcodes 0)."""

@@ -318,14 +318,26 @@ int upload(vtx_ctx* c, const std::vector<UploadJob>& jobs, const std::atomic<boo
     return VTX_OK;
 }
 
-// Gathers byte ranges of one host mapping into ONE compact device buffer: piece k lands at dst + off[k] (off ascending, pieces back
-// to back).  The destination is cut into kUpChunk chunks; a worker copies whatever pieces (or parts of them) fall into its chunk
+// vtx_prefetch_file's thread runs upload(): it uses the context's pinned buffers, events and copy streams, runs the lazy upload_init and
+// writes c->err, all without a lock.  So every entry point that uploads, downloads through the copy workers or takes d_bam_comp calls
+// this first — the ONE place the thread is waited for.  Keep: the prefetched bytes stay valid for a later vtx_submit_bam (the caller
+// leaves d_bam_comp alone).  Drop: the caller is about to overwrite d_bam_comp.  Cancel: nobody wants the bytes — the copy stops at its
+// next chunk instead of being waited for as a whole — and they are dropped.
+enum class Prefetch { Keep, Drop, Cancel };
+void prefetch_settle(vtx_ctx* c, Prefetch mode) {
+    if (mode == Prefetch::Cancel) c->pf_cancel = true;
+    if (c->pf_thread.joinable()) c->pf_thread.join();
+    c->pf_cancel = false;
+    if (mode != Prefetch::Keep) c->pf_valid = false;
+}
+
+// Gathers byte ranges of one host mapping (src) into ONE compact device buffer: piece k, the bytes at src + file_off, lands at
+// dst + dst_off (dst_off ascending, pieces back to back: vtxp::Piece).  The destination is cut into kUpChunk chunks; a worker copies whatever pieces (or parts of them) fall into its chunk
 // into its pinned buffer and pushes the chunk with one DMA — ten thousand segments of a sparse plan cost ten thousand memcpys on the
 // host, not ten thousand DMAs.
-struct GatherPiece { const char* src; size_t off, bytes; };
-int upload_gather(vtx_ctx* c, void* dst, const std::vector<GatherPiece>& pieces) {
+int upload_gather(vtx_ctx* c, void* dst, const uint8_t* src, const std::vector<vtxp::Piece>& pieces) {
     if (pieces.empty()) return VTX_OK;
-    const size_t total = pieces.back().off + pieces.back().bytes;
+    const size_t total = (size_t)(pieces.back().dst_off + pieces.back().bytes);
     const size_t n_chunks = (total + vtx_ctx::kUpChunk - 1) / vtx_ctx::kUpChunk;
     if (!n_chunks) return VTX_OK;
     if (int rc = upload_init(c)) return rc;
@@ -343,10 +355,10 @@ int upload_gather(vtx_ctx* c, void* dst, const std::vector<GatherPiece>& pieces)
             hipError_t e = used[slot] ? hipEventSynchronize(c->up_ev[w][slot]) : hipSuccess;   // the DMA out of this buffer is done
             if (e == hipSuccess) {
                 // first piece that ends behind lo
-                size_t k = (size_t)(std::upper_bound(pieces.begin(), pieces.end(), lo, [](size_t v, const GatherPiece& g) { return v < g.off + g.bytes; }) - pieces.begin());
-                for (; k < pieces.size() && pieces[k].off < hi; ++k) {
-                    const size_t a = std::max(lo, pieces[k].off), b = std::min(hi, pieces[k].off + pieces[k].bytes);
-                    memcpy((char*)c->up_pin[w][slot] + (a - lo), pieces[k].src + (a - pieces[k].off), b - a);
+                size_t k = (size_t)(std::upper_bound(pieces.begin(), pieces.end(), lo, [](size_t v, const vtxp::Piece& g) { return v < g.dst_off + g.bytes; }) - pieces.begin());
+                for (; k < pieces.size() && pieces[k].dst_off < hi; ++k) {
+                    const size_t a = std::max<size_t>(lo, pieces[k].dst_off), b = std::min<size_t>(hi, pieces[k].dst_off + pieces[k].bytes);
+                    memcpy((char*)c->up_pin[w][slot] + (a - lo), src + pieces[k].file_off + (a - pieces[k].dst_off), b - a);
                 }
                 e = hipMemcpyAsync((char*)dst + lo, c->up_pin[w][slot], hi - lo, hipMemcpyHostToDevice, c->up_stream[w]);
             }
@@ -564,6 +576,20 @@ void comm_release(vtx_ctx* c) {
     c->comm = nullptr; c->comm_world = 0;
 }
 
+// d_bam_cnt: the ingest's VTXG_N_COUNTERS 64-bit counters (vtx_ingest.h), then four 32-bit words — the ingest's err[], the matrix
+// writers' flag.  The ONE place that knows how the buffer is carved.
+struct BamCounters {
+    unsigned long long* counters;
+    uint32_t* err;
+    static constexpr size_t kBytes = VTXG_N_COUNTERS * sizeof(uint64_t) + 4 * sizeof(uint32_t);
+};
+int reserve_bam_counters(vtx_ctx* c, BamCounters* out) {
+    HIP_TRY(c, c->d_bam_cnt.reserve(BamCounters::kBytes));
+    out->counters = c->d_bam_cnt.as<unsigned long long>();
+    out->err = (uint32_t*)(out->counters + VTXG_N_COUNTERS);
+    return VTX_OK;
+}
+
 // per-record device buffers of the resident batch (scores, group structure, COO staging)
 int reserve_record_buffers(vtx_ctx* c, uint32_t nr) {
     const size_t u32 = sizeof(uint32_t);
@@ -765,7 +791,7 @@ int vtx_create(const vtx_config* cfg, vtx_ctx** out) {
 
 void vtx_destroy(vtx_ctx* c) {
     if (!c) return;
-    if (c->pf_thread.joinable()) c->pf_thread.join();
+    prefetch_settle(c, Prefetch::Keep);
     if (c->pf_map) { munmap(c->pf_map, c->pf_map_bytes); c->pf_map = nullptr; }
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -900,6 +926,7 @@ static int band_reserve(vtx_ctx* c, BandPlan& p, bool quiet) {
 
 int vtx_submit(vtx_ctx* c, const vtx_batch* b) {
     if (!c) return VTX_E_INVAL;
+    prefetch_settle(c, Prefetch::Keep);                   // (upload() below; d_bam_comp is not touched: the bytes stay good for a later vtx_submit_bam)
     if (!b) return fail(c, VTX_E_INVAL, "vtx_submit: null batch");
     c->submitted = false; c->ran = false;
     const uint32_t nl = b->n_loci, nr = b->n_records;
@@ -1189,6 +1216,7 @@ static int check_loci_haps(vtx_ctx* c, const char* who, const vtx_locus* loci, u
 
 int vtx_submit_raw(vtx_ctx* c, const vtx_raw_batch* b, vtx_raw_stats* stats) {
     if (!c) return VTX_E_INVAL;
+    prefetch_settle(c, Prefetch::Keep);                   // (as in vtx_submit)
     if (!b) return fail(c, VTX_E_INVAL, "vtx_submit_raw: null batch");
     c->submitted = false; c->ran = false;
     if (!c->bc_ready) return fail(c, VTX_E_STATE, "vtx_submit_raw: no barcode list (vtx_set_barcodes)");
@@ -1228,8 +1256,7 @@ int vtx_submit_raw(vtx_ctx* c, const vtx_raw_batch* b, vtx_raw_stats* stats) {
 int vtx_prefetch_file(vtx_ctx* c, const char* path, uint64_t file_off, uint64_t n) {
     if (!c) return VTX_E_INVAL;
     if (!path) return fail(c, VTX_E_INVAL, "vtx_prefetch_file: null argument");
-    if (c->pf_thread.joinable()) c->pf_thread.join();
-    c->pf_valid = false;
+    prefetch_settle(c, Prefetch::Drop);
     if (c->pf_map) { munmap(c->pf_map, c->pf_map_bytes); c->pf_map = nullptr; }
     const int fd = open(path, O_RDONLY);
     struct stat st;
@@ -1260,241 +1287,263 @@ int vtx_prefetch_file(vtx_ctx* c, const char* path, uint64_t file_off, uint64_t 
 // ---- vtx_submit_bam: the ingest itself on the device (vtx_ingest.hip) ----
 // sg == nullptr: one contiguous stretch (vtx_submit_bam).  Else the segmented plan of vtx_submit_bam_segments: g = &sg->base holds the
 // segments' blocks and seeds back to back; only the segments' byte ranges travel, and the record chains end per segment.
-static int submit_bam_impl(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_segments* sg, vtx_ingest_stats* st) {
-    c->submitted = false; c->ran = false;
-    if (st) memset(st, 0, sizeof *st);
-    if (!c->bc_ready) return fail(c, VTX_E_STATE, "vtx_submit_bam: no barcode list (vtx_set_barcodes)");
-    const uint32_t nl = g->n_loci, nb = g->n_blocks;
-    if ((nb && (!g->blocks || !g->file)) || (nl && !g->loci) || (g->hap_bytes && !g->hap_arena) || (g->n_seeds && !g->seeds) ||
-        (g->n_intervals && !g->intervals) || !g->tid_begin || (g->n_ref && !g->tid_max_span))
-        return fail(c, VTX_E_INVAL, "vtx_submit_bam: null array with non-zero count");
-    if (g->hap_bytes > 0xffffffffull) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: hap arena above 4 GiB");
-    uint32_t max_hap = 0, max_hap_all = 0;
-    if (int rc = check_loci_haps(c, "vtx_submit_bam", g->loci, nl, g->hap_bytes, &max_hap, &max_hap_all)) return rc;
-    note_long_loci(c, g->loci, nl);
-    if (g->tid_begin[0] != 0 || g->tid_begin[g->n_ref] != g->n_intervals) return fail(c, VTX_E_INVAL, "vtx_submit_bam: tid_begin does not cover the intervals");
-    for (uint32_t t = 0; t < g->n_ref; ++t) {
-        if (g->tid_begin[t] > g->tid_begin[t + 1]) return fail(c, VTX_E_INVAL, "vtx_submit_bam: tid_begin not ascending at %u", t);
-        for (uint32_t k = g->tid_begin[t]; k < g->tid_begin[t + 1]; ++k) {
-            const vtx_bam_interval& I = g->intervals[k];
-            if (I.locus >= nl || I.end < I.start || (k > g->tid_begin[t] && g->intervals[k - 1].start > I.start) || (int64_t)I.end - I.start > g->tid_max_span[t])
-                return fail(c, VTX_E_INVAL, "vtx_submit_bam: interval %u: bad locus / order / span", k);
-        }
-    }
-    // blocks: consecutive in the file; the compressed range [lo, hi) travels as it is, and the 8 bytes behind it: a block's trailer
-    // (CRC32, ISIZE) follows its payload, and bgzf_crc32_kernel reads the CRC32 of every block
-    const uint64_t kTrailer = 8;
-    std::vector<vtxg_block> blocks(nb);
-    uint64_t lo = nb ? g->blocks[0].coff : 0, hi = lo, utotal = 0;
-    for (uint32_t i = 0; i < nb; ++i) {
-        const vtx_bgzf_block& B = g->blocks[i];
-        if (B.coff < hi || B.coff + B.clen > g->file_bytes || B.isize > 65536u)
-            return fail(c, VTX_E_INVAL, "vtx_submit_bam: block %u: out of order, outside the file or above 64 KiB", i);
-        if (B.coff + B.clen + kTrailer > g->file_bytes)
-            return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: BGZF block %u: its trailer (CRC32, ISIZE) lies beyond the end of the file: the host packer decides", i);
-        blocks[i] = vtxg_block{B.coff - lo, utotal, B.clen, B.isize};
-        hi = B.coff + B.clen;
-        utotal += B.isize;
-    }
-    // segmented: blocks[].coff is rebased to the compact buffer the segments' byte ranges are gathered into; the segment table
-    // tiles the blocks and the seeds in order; every seed and every end lies inside its segment's inflated bytes
-    std::vector<vtxg_segment> segs;
-    std::vector<uint32_t> seed_seg;
-    std::vector<GatherPiece> pieces;
-    uint64_t comp_bytes = nb ? hi - lo + kTrailer : 0;
-    if (sg) {
-        const uint32_t nseg = sg->n_segments;
-        if ((nseg && !sg->segments) || (!nseg && (nb || g->n_seeds))) return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: blocks or seeds without segments");
-        segs.resize(nseg); seed_seg.resize(g->n_seeds); pieces.reserve(nseg);
-        uint32_t nbk = 0, nsd = 0;
-        uint64_t ub = 0, cb = 0;
-        for (uint32_t k = 0; k < nseg; ++k) {
-            const vtx_bam_segment& S = sg->segments[k];
-            if (S.block_begin != nbk || S.block_end <= S.block_begin || S.block_end > nb || S.seed_begin != nsd || S.seed_end <= S.seed_begin || S.seed_end > g->n_seeds)
-                return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: segment %u: its blocks / seeds do not follow the segment before, or are empty", k);
-            const uint64_t first = g->blocks[S.block_begin].coff, end = g->blocks[S.block_end - 1].coff + g->blocks[S.block_end - 1].clen;
-            uint64_t ul = ub;
-            for (uint32_t i = S.block_begin; i < S.block_end; ++i) { blocks[i].coff = cb + (g->blocks[i].coff - first); ul += g->blocks[i].isize; }
-            const bool to_eof = (S.flags & VTX_SEGMENT_TO_EOF) != 0;
-            if (S.end_upos > ul || (!to_eof && S.end_upos + 12 > ul) || S.end_upos <= ub)
-                return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: segment %u: its end (and the 12 bytes of the record there) lies outside its blocks", k);
-            for (uint32_t i = S.seed_begin; i < S.seed_end; ++i) {
-                if (g->seeds[i] < ub || g->seeds[i] >= S.end_upos || (i > S.seed_begin && g->seeds[i] <= g->seeds[i - 1]))
-                    return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: seed %u: not ascending or outside segment %u", i, k);
-                seed_seg[i] = k;
-            }
-            segs[k] = vtxg_segment{ub, ul, S.end_upos, S.seed_end, S.end_tid, S.end_pos, S.flags};
-            pieces.push_back(GatherPiece{(const char*)g->file + first, (size_t)cb, (size_t)(end - first + kTrailer)});      // (with its last block's trailer)
-            nbk = S.block_end; nsd = S.seed_end; ub = ul; cb += end - first + kTrailer;
-        }
-        if (nbk != nb || nsd != g->n_seeds) return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: blocks or seeds behind the last segment");
-        comp_bytes = cb;
-    }
-    const uint64_t end_upos = std::min<uint64_t>(g->end_upos, utotal);
-    for (uint32_t i = 0; !sg && i < g->n_seeds; ++i)
-        if (g->seeds[i] >= end_upos || (i && g->seeds[i] <= g->seeds[i - 1])) return fail(c, VTX_E_INVAL, "vtx_submit_bam: seed %u: not ascending or beyond the end", i);
+// The ingest runs as the stages below, in the order ingest_run lists them, over one IngestState.
+struct IngestState {
+    const vtx_bam_ingest* g = nullptr;
+    const vtx_bam_segments* sg = nullptr;
+    vtx_ingest_stats* st = nullptr;
+    vtxp::Layout L;                                    // the plan in the device's layout (vtx_ingest_plan_core.h)
+    uint32_t max_hap = 0, max_hap_all = 0;             // check_loci_haps
+    bool prefetched = false;                           // the compressed bytes are a vtx_prefetch_file's, already in d_bam_comp
+    float pf_wait_ms = 0, h2d_ms = 0;
+    vtxp::IntervalArrays d_iv{};                       // L.iv on the device
+    BamCounters d_cnt{};
+    const vtxg_segment* d_segs = nullptr;              // segmented: the segment table, then the seeds' segment numbers
+    const uint32_t* d_seed_seg = nullptr;
+    uint32_t n_rec = 0;                                // BAM records the chains found
+    uint32_t err[3] = {0, 0, 0};                       // the err words as last read back
+    unsigned long long cnt[VTXG_N_COUNTERS] = {0};     // the counters after the filters' first pass
+};
 
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipStream_t s = c->stream;
-    const size_t u32 = sizeof(uint32_t), u64 = sizeof(uint64_t);
-    const uint32_t ns = g->n_seeds, ni = g->n_intervals, nref = g->n_ref;
-    // bytes a vtx_prefetch_file already brought (or is still bringing) to the device?
-    // (Tried in round 6: inflating the blocks of a 128 MB segment as soon as it has landed, on streams of their own.  Every launch of
-    //  the latency-bound inflate kernel takes its full ~35 ms whatever the block count, and the copies still in flight queued behind
-    //  the kernels: inflate 94 -> 250 ms, the copy 0.09 -> 1.4 s.  The copy is waited for as a whole.)
+static float ms_since(std::chrono::steady_clock::time_point t) { return (float)(1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count()); }
+
+// the slicing width of bgzf_crc32_kernel (experiment knob: 4 / 8 / 16)
+static int crc_width() {
+    static const int w = VTX_DEV_ENV("VTX_CRC_WIDTH") ? atoi(VTX_DEV_ENV("VTX_CRC_WIDTH")) : VTXG_CRC_WIDTH;
+    return w;
+}
+
+// what the err words say, most specific first
+static int ingest_error(vtx_ctx* c, const IngestState& is) {
+    const uint32_t e0 = is.err[0], e1 = is.err[1];
+    if (!(e0 & (0x1ffu | VTXG_ERR_CRC | VTXG_ERR_CHAIN)) && (e0 & VTXG_ERR_SEG_END))
+        return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam_segments: %u of %u segments cannot prove their end (the record the index names there starts in front of the segment's last locus: a read spliced over four windows): the host packer decides", is.err[2], is.sg ? is.sg->n_segments : 0u);
+    if (e0 & 0x1ffu) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: BGZF block %u does not inflate on the device (status bits 0x%x): the host packer decides", e1, e0 & 0x1ffu);
+    if (e0 & VTXG_ERR_CRC) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: BGZF block %u: the CRC32 of its inflated bytes does not match its trailer: the host packer decides", e1);
+    if (e0 & VTXG_ERR_CHAIN) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: a record chain does not end on the index's next record start (index and file disagree, or a malformed record)");
+    return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: malformed BAM record");
+}
+
+// The caller's plan: checked, then rewritten into the device's layout.  The order of the checks is the API's: the barcode list, null
+// arrays and the hap arena's size (the core), the loci's haplotypes, then everything else about the plan (the core again).
+static int ingest_check_layout(vtx_ctx* c, IngestState& is) {
+    const vtx_bam_ingest* g = is.g;
+    c->submitted = false; c->ran = false;
+    if (is.st) memset(is.st, 0, sizeof *is.st);
+    if (!c->bc_ready) return fail(c, VTX_E_STATE, "vtx_submit_bam: no barcode list (vtx_set_barcodes)");
+    char why[512];
+    if (int rc = vtxp::check_arrays(*g, why, sizeof why)) return fail(c, rc, "%s", why);
+    if (int rc = check_loci_haps(c, "vtx_submit_bam", g->loci, g->n_loci, g->hap_bytes, &is.max_hap, &is.max_hap_all)) return rc;
+    note_long_loci(c, g->loci, g->n_loci);
+    if (int rc = vtxp::layout(*g, is.sg, is.L, why, sizeof why)) return fail(c, rc, "%s", why);
+    return VTX_OK;
+}
+
+// bytes a vtx_prefetch_file already brought (or is still bringing) to the device?
+// (Tried in round 6: inflating the blocks of a 128 MB segment as soon as it has landed, on streams of their own.  Every launch of
+//  the latency-bound inflate kernel takes its full ~35 ms whatever the block count, and the copies still in flight queued behind
+//  the kernels: inflate 94 -> 250 ms, the copy 0.09 -> 1.4 s.  The copy is waited for as a whole.)
+static void ingest_settle_prefetch(vtx_ctx* c, IngestState& is) {
+    const vtxp::Layout& L = is.L;
     const auto t_pf = std::chrono::steady_clock::now();
     // (a segmented plan has no use for the file as a whole: the prefetch stops at its next chunk and its bytes are dropped)
-    if (sg) c->pf_cancel = true;
-    if (c->pf_thread.joinable()) c->pf_thread.join();
-    c->pf_cancel = false;
-    const float pf_wait_ms = (float)(1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_pf).count());
-    const bool prefetched = !sg && c->pf_valid && c->pf_rc == VTX_OK && nb && c->pf_off <= lo && hi + kTrailer <= c->pf_off + c->pf_n;
-    if (prefetched) { const uint64_t shift = lo - c->pf_off; for (auto& B : blocks) B.coff += shift; }
-    else { c->pf_valid = false; HIP_TRY(c, c->d_bam_comp.reserve((size_t)comp_bytes + kBamPad)); }
-    if (sg) HIP_TRY(c, c->d_bam_segs.reserve(segs.size() * sizeof(vtxg_segment) + (size_t)g->n_seeds * sizeof(uint32_t) + 64));
-    HIP_TRY(c, c->d_bam_data.reserve((size_t)utotal + kBamPad));
-    HIP_TRY(c, c->d_bam_blocks.reserve((size_t)nb * sizeof(vtxg_block)));
+    prefetch_settle(c, is.sg ? Prefetch::Cancel : Prefetch::Keep);
+    is.pf_wait_ms = ms_since(t_pf);
+    is.prefetched = !is.sg && c->pf_valid && c->pf_rc == VTX_OK && is.g->n_blocks && c->pf_off <= L.lo && L.hi + vtxp::kTrailer <= c->pf_off + c->pf_n;
+    if (is.prefetched) { const uint64_t shift = L.lo - c->pf_off; for (auto& B : is.L.blocks) B.coff += shift; }
+    else c->pf_valid = false;                          // (d_bam_comp is about to take this plan's own bytes)
+}
+
+// every buffer the stages up to the record count need, and the typed pointers into the shared ones
+static int ingest_reserve(vtx_ctx* c, IngestState& is) {
+    const vtx_bam_ingest* g = is.g;
+    const vtxp::Layout& L = is.L;
+    const size_t u32 = sizeof(uint32_t), u64 = sizeof(uint64_t);
+    const uint32_t ns = g->n_seeds;
+    if (!is.prefetched) HIP_TRY(c, c->d_bam_comp.reserve((size_t)L.comp_bytes + kBamPad));
+    if (is.sg) HIP_TRY(c, c->d_bam_segs.reserve(L.segs.size() * sizeof(vtxg_segment) + (size_t)ns * sizeof(uint32_t) + 64));
+    HIP_TRY(c, c->d_bam_data.reserve((size_t)L.utotal + kBamPad));
+    HIP_TRY(c, c->d_bam_blocks.reserve((size_t)g->n_blocks * sizeof(vtxg_block)));
     HIP_TRY(c, c->d_bam_seeds.reserve((size_t)ns * u64));
     HIP_TRY(c, c->d_bam_seed_cnt.reserve((size_t)ns * u32 + 16));
     HIP_TRY(c, c->d_bam_seed_scan.reserve((size_t)ns * u32 + 16));
-    HIP_TRY(c, c->d_bam_iv.reserve((size_t)ni * 3 * u32 + ((size_t)nref + 1) * u32 + (size_t)nref * u32 + 64));
-    HIP_TRY(c, c->d_bam_cnt.reserve(VTXG_N_COUNTERS * u64 + 4 * u32));
+    HIP_TRY(c, c->d_bam_iv.reserve(L.iv.size() * u32 + 64));
+    if (int rc = reserve_bam_counters(c, &is.d_cnt)) return rc;
     HIP_TRY(c, c->d_scan_tmp.reserve(vtxk_scan_temp_bytes(std::max(ns, 1u))));
-    // intervals as arrays: start[ni], end[ni], locus[ni], tid_begin[nref + 1], tid_span[nref]
-    std::vector<uint32_t> ivh((size_t)ni * 3 + nref + 1 + nref);
-    for (uint32_t k = 0; k < ni; ++k) { ivh[k] = (uint32_t)g->intervals[k].start; ivh[ni + k] = (uint32_t)g->intervals[k].end; ivh[2 * (size_t)ni + k] = g->intervals[k].locus; }
-    for (uint32_t t = 0; t <= nref; ++t) ivh[3 * (size_t)ni + t] = g->tid_begin[t];
-    for (uint32_t t = 0; t < nref; ++t) ivh[3 * (size_t)ni + nref + 1 + t] = (uint32_t)g->tid_max_span[t];
-    const int32_t* d_iv_start = c->d_bam_iv.as<int32_t>();
-    const int32_t* d_iv_end = d_iv_start + ni;
-    const uint32_t* d_iv_locus = (const uint32_t*)(d_iv_end + ni);
-    const uint32_t* d_tid_begin = d_iv_locus + ni;
-    const int32_t* d_tid_span = (const int32_t*)(d_tid_begin + nref + 1);
-    unsigned long long* d_counters = c->d_bam_cnt.as<unsigned long long>();
-    uint32_t* d_err = (uint32_t*)(d_counters + VTXG_N_COUNTERS);
     HIP_TRY(c, c->d_hap.reserve(g->hap_bytes + 16));
-    HIP_TRY(c, c->d_loci.reserve((size_t)nl * sizeof(vtx_locus)));
-
-    const auto t0 = std::chrono::steady_clock::now();
-    auto since = [&](std::chrono::steady_clock::time_point t) { return (float)(1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count()); };
-    HIP_TRY(c, hipMemsetAsync(d_counters, 0, VTXG_N_COUNTERS * u64 + 4 * u32, s));
-    HIP_TRY(c, hipMemsetAsync(d_err + 1, 0xff, u32, s));
+    HIP_TRY(c, c->d_loci.reserve((size_t)g->n_loci * sizeof(vtx_locus)));
+    is.d_iv = vtxp::IntervalArrays{c->d_bam_iv.as<uint32_t>(), g->n_intervals, g->n_ref};
     // segment table, then the seeds' segment numbers (8-byte aligned: the table's entries are 40 bytes)
-    const vtxg_segment* d_segs = c->d_bam_segs.as<vtxg_segment>();
-    const uint32_t* d_seed_seg = (const uint32_t*)(d_segs + segs.size());
-    if (sg) {
-        if (int rc = upload_gather(c, c->d_bam_comp.p, pieces)) return rc;
-        if (int rc = upload(c, {{c->d_bam_segs.p, segs.data(), segs.size() * sizeof(vtxg_segment)},
-                                {(void*)d_seed_seg, seed_seg.data(), seed_seg.size() * sizeof(uint32_t)}})) return rc;
+    is.d_segs = c->d_bam_segs.as<vtxg_segment>();
+    is.d_seed_seg = (const uint32_t*)(is.d_segs + L.segs.size());
+    return VTX_OK;
+}
+
+// the counters and err words zeroed; then the plan and the file's bytes (unless a prefetch brought them) to the device
+static int ingest_upload(vtx_ctx* c, IngestState& is) {
+    const vtx_bam_ingest* g = is.g;
+    const vtxp::Layout& L = is.L;
+    hipStream_t s = c->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(c, hipMemsetAsync(is.d_cnt.counters, 0, BamCounters::kBytes, s));
+    HIP_TRY(c, hipMemsetAsync(is.d_cnt.err + 1, 0xff, sizeof(uint32_t), s));
+    if (is.sg) {
+        if (int rc = upload_gather(c, c->d_bam_comp.p, g->file, L.pieces)) return rc;
+        if (int rc = upload(c, {{c->d_bam_segs.p, L.segs.data(), L.segs.size() * sizeof(vtxg_segment)},
+                                {(void*)is.d_seed_seg, L.seed_seg.data(), L.seed_seg.size() * sizeof(uint32_t)}})) return rc;
     }
-    if (int rc = upload(c, {{c->d_bam_comp.p, g->file + lo, prefetched || sg ? (size_t)0 : (size_t)comp_bytes},
-                            {c->d_bam_blocks.p, blocks.data(), (size_t)nb * sizeof(vtxg_block)},
-                            {c->d_bam_seeds.p, g->seeds, (size_t)ns * u64},
-                            {c->d_bam_iv.p, ivh.data(), ivh.size() * u32},
-                            {c->d_loci.p, g->loci, (size_t)nl * sizeof(vtx_locus)},
+    if (int rc = upload(c, {{c->d_bam_comp.p, g->file + L.lo, is.prefetched || is.sg ? (size_t)0 : (size_t)L.comp_bytes},
+                            {c->d_bam_blocks.p, L.blocks.data(), L.blocks.size() * sizeof(vtxg_block)},
+                            {c->d_bam_seeds.p, g->seeds, (size_t)g->n_seeds * sizeof(uint64_t)},
+                            {c->d_bam_iv.p, L.iv.data(), L.iv.size() * sizeof(uint32_t)},
+                            {c->d_loci.p, g->loci, (size_t)g->n_loci * sizeof(vtx_locus)},
                             {c->d_hap.p, g->hap_arena, (size_t)g->hap_bytes}})) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
-    const float h2d_ms = since(t0);
-    // ---- inflate, record boundaries ----
+    is.h2d_ms = ms_since(t0);
+    return VTX_OK;
+}
+
+// ---- inflate; then the CRC32 of every block's inflated bytes against its trailer (htslib's check in bgzf_read_block): in front of
+//      the first reader of those bytes, on the same stream, its verdict in the same err words ----
+static int ingest_inflate_crc(vtx_ctx* c, IngestState& is) {
+    hipStream_t s = c->stream;
+    const uint32_t nb = is.g->n_blocks;
     HIP_TRY(c, hipEventRecord(c->ev[EV_INGEST_START], s));
-    HIP_TRY(c, vtxg_inflate(c->d_bam_comp.as<uint8_t>(), c->d_bam_blocks.as<vtxg_block>(), nb, c->d_bam_data.as<uint8_t>(), d_err, nullptr, 0, s));
+    HIP_TRY(c, vtxg_inflate(c->d_bam_comp.as<uint8_t>(), c->d_bam_blocks.as<vtxg_block>(), nb, c->d_bam_data.as<uint8_t>(), is.d_cnt.err, nullptr, 0, s));
     HIP_TRY(c, hipEventRecord(c->ev[EV_INFLATE_END], s));
-    // ---- the CRC32 of every block's inflated bytes against its trailer (htslib's check in bgzf_read_block): in front of the first
-    //      reader of those bytes, on the same stream, its verdict in the same err words ----
     static const bool no_crc = VTX_DEV_ENV("VTX_NO_CRC") != nullptr;                                   // A/B timing only: the check off
-    static const int crc_width = VTX_DEV_ENV("VTX_CRC_WIDTH") ? atoi(VTX_DEV_ENV("VTX_CRC_WIDTH")) : VTXG_CRC_WIDTH;   // experiment knob: 4 / 8 / 16
     HIP_TRY(c, hipEventRecord(c->ev_crc[0], s));
-    if (!no_crc) HIP_TRY(c, vtxg_crc32(c->d_bam_comp.as<uint8_t>(), c->d_bam_blocks.as<vtxg_block>(), nb, c->d_bam_data.as<uint8_t>(), d_err, nullptr, 0, crc_width, s));
+    if (!no_crc) HIP_TRY(c, vtxg_crc32(c->d_bam_comp.as<uint8_t>(), c->d_bam_blocks.as<vtxg_block>(), nb, c->d_bam_data.as<uint8_t>(), is.d_cnt.err, nullptr, 0, crc_width(), s));
     HIP_TRY(c, hipEventRecord(c->ev_crc[1], s));
     c->crc_ms = 0;
-    uint32_t n_rec = 0;
+    return VTX_OK;
+}
+
+// One pass of the record chains, a chain per seed.  off == nullptr: the records of every chain are counted into d_bam_seed_cnt; else
+// (off = the inclusive scan of those counts) their offsets go to rec_upos.
+static int ingest_chain_pass(vtx_ctx* c, const IngestState& is, const uint32_t* off, uint64_t* rec_upos) {
+    const uint8_t* data = c->d_bam_data.as<uint8_t>();
+    const uint64_t* seeds = c->d_bam_seeds.as<uint64_t>();
+    uint32_t* cnt = c->d_bam_seed_cnt.as<uint32_t>();
+    const uint32_t ns = is.g->n_seeds;
+    if (is.sg) HIP_TRY(c, vtxg_chain_segments(data, seeds, ns, is.d_seed_seg, is.d_segs, cnt, off, rec_upos, is.d_cnt.err, c->stream));
+    else HIP_TRY(c, vtxg_chain(data, is.L.utotal, seeds, ns, is.L.end_upos, cnt, off, rec_upos, is.d_cnt.err, c->stream));
+    return VTX_OK;
+}
+
+// ---- record boundaries: count per seed, scan, (the first verdict on the blocks and the chains,) emit ----
+static int ingest_chains(vtx_ctx* c, IngestState& is) {
+    hipStream_t s = c->stream;
+    const size_t u32 = sizeof(uint32_t);
+    const uint32_t ns = is.g->n_seeds;
     if (ns) {
-        if (sg) HIP_TRY(c, vtxg_chain_segments(c->d_bam_data.as<uint8_t>(), c->d_bam_seeds.as<uint64_t>(), ns, d_seed_seg, d_segs, c->d_bam_seed_cnt.as<uint32_t>(), nullptr, nullptr, d_err, s));
-        else HIP_TRY(c, vtxg_chain(c->d_bam_data.as<uint8_t>(), utotal, c->d_bam_seeds.as<uint64_t>(), ns, end_upos, c->d_bam_seed_cnt.as<uint32_t>(), nullptr, nullptr, d_err, s));
+        if (int rc = ingest_chain_pass(c, is, nullptr, nullptr)) return rc;
         HIP_TRY(c, vtxk_inclusive_scan_u32(c->d_bam_seed_cnt.as<uint32_t>(), c->d_bam_seed_scan.as<uint32_t>(), ns, c->d_scan_tmp.p, vtxk_scan_temp_bytes(ns), s));
-        HIP_TRY(c, hipMemcpyAsync(&n_rec, c->d_bam_seed_scan.as<uint32_t>() + (ns - 1), u32, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(&is.n_rec, c->d_bam_seed_scan.as<uint32_t>() + (ns - 1), u32, hipMemcpyDeviceToHost, s));
     }
-    uint32_t err[3] = {0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(err, d_err, 3 * u32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(is.err, is.d_cnt.err, 3 * u32, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    auto ingest_error = [&](uint32_t e0, uint32_t e1) -> int {
-        if (!(e0 & (0x1ffu | VTXG_ERR_CRC | VTXG_ERR_CHAIN)) && (e0 & VTXG_ERR_SEG_END))
-            return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam_segments: %u of %u segments cannot prove their end (the record the index names there starts in front of the segment's last locus: a read spliced over four windows): the host packer decides", err[2], sg ? sg->n_segments : 0u);
-        if (e0 & 0x1ffu) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: BGZF block %u does not inflate on the device (status bits 0x%x): the host packer decides", e1, e0 & 0x1ffu);
-        if (e0 & VTXG_ERR_CRC) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: BGZF block %u: the CRC32 of its inflated bytes does not match its trailer: the host packer decides", e1);
-        if (e0 & VTXG_ERR_CHAIN) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: a record chain does not end on the index's next record start (index and file disagree, or a malformed record)");
-        return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: malformed BAM record");
-    };
-    if (err[0]) return ingest_error(err[0], err[1]);
+    if (is.err[0]) return ingest_error(c, is);
+    const uint32_t n_rec = is.n_rec;
     if ((uint64_t)n_rec > 0xfffffff0ull) return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: more than 2^32 BAM records in one ingest");
-    HIP_TRY(c, c->d_bam_rec.reserve((size_t)n_rec * u64 + 16));
+    HIP_TRY(c, c->d_bam_rec.reserve((size_t)n_rec * sizeof(uint64_t) + 16));
     DevBuf* per_rec[] = {&c->d_bam_nhit, &c->d_bam_rsz, &c->d_bam_tsz, &c->d_bam_hscan, &c->d_bam_rscan, &c->d_bam_tscan};
     for (DevBuf* d : per_rec) HIP_TRY(c, d->reserve((size_t)n_rec * u32 + 16));
     HIP_TRY(c, c->d_bam_info.reserve((size_t)n_rec * sizeof(vtxg_recinfo) + 16));
     HIP_TRY(c, c->d_scan_tmp.reserve(vtxk_scan_temp_bytes(std::max(n_rec, 1u))));
-    if (ns && sg) HIP_TRY(c, vtxg_chain_segments(c->d_bam_data.as<uint8_t>(), c->d_bam_seeds.as<uint64_t>(), ns, d_seed_seg, d_segs, c->d_bam_seed_cnt.as<uint32_t>(),
-                                                 c->d_bam_seed_scan.as<uint32_t>(), c->d_bam_rec.as<uint64_t>(), d_err, s));
-    else if (ns) HIP_TRY(c, vtxg_chain(c->d_bam_data.as<uint8_t>(), utotal, c->d_bam_seeds.as<uint64_t>(), ns, end_upos, c->d_bam_seed_cnt.as<uint32_t>(),
-                                   c->d_bam_seed_scan.as<uint32_t>(), c->d_bam_rec.as<uint64_t>(), d_err, s));
+    if (ns) { if (int rc = ingest_chain_pass(c, is, c->d_bam_seed_scan.as<uint32_t>(), c->d_bam_rec.as<uint64_t>())) return rc; }
     HIP_TRY(c, hipEventRecord(c->ev[EV_INDEX_END], s));
-    // ---- fetch + filters per (read, locus) pair: counts, then offsets, then the raw records ----
-    const vtxg_filter f{nref, g->min_mapq, g->primary_only ? 1u : 0u, g->no_duplicates ? 1u : 0u, (uint32_t)(uint8_t)g->bam_tag[0] | ((uint32_t)(uint8_t)g->bam_tag[1] << 8)};
-    HIP_TRY(c, vtxg_scan(0, c->d_bam_data.as<uint8_t>(), c->d_bam_rec.as<uint64_t>(), n_rec, f, d_iv_start, d_iv_end, d_iv_locus, d_tid_begin, d_tid_span,
+    return VTX_OK;
+}
+
+// One pass of the fetch + filters per (read, locus) pair.  emit == 0: the counts per record and the counters; emit == 1 (behind the
+// scans of the counts): the raw records, their loci, the tag and read arenas.
+static int ingest_scan_pass(vtx_ctx* c, const IngestState& is, int emit) {
+    const vtx_bam_ingest* g = is.g;
+    const vtxg_filter f{g->n_ref, g->min_mapq, g->primary_only ? 1u : 0u, g->no_duplicates ? 1u : 0u, (uint32_t)(uint8_t)g->bam_tag[0] | ((uint32_t)(uint8_t)g->bam_tag[1] << 8)};
+    const vtxp::IntervalArrays& iv = is.d_iv;
+    HIP_TRY(c, vtxg_scan(emit, c->d_bam_data.as<uint8_t>(), c->d_bam_rec.as<uint64_t>(), is.n_rec, f, iv.start(), iv.end(), iv.locus(), iv.tid_begin(), iv.tid_span(),
                          c->d_bam_nhit.as<uint32_t>(), c->d_bam_rsz.as<uint32_t>(), c->d_bam_tsz.as<uint32_t>(), c->d_bam_info.as<vtxg_recinfo>(),
-                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_counters, d_err, s));
-    unsigned long long cnt[VTXG_N_COUNTERS] = {0};
-    HIP_TRY(c, hipMemcpyAsync(cnt, d_counters, sizeof cnt, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(err, d_err, 2 * u32, hipMemcpyDeviceToHost, s));
+                         emit ? c->d_bam_hscan.as<uint32_t>() : nullptr, emit ? c->d_bam_rscan.as<uint32_t>() : nullptr, emit ? c->d_bam_tscan.as<uint32_t>() : nullptr,
+                         emit ? c->d_raw.as<vtx_raw_record>() : nullptr, emit ? c->d_raw_locus.as<uint32_t>() : nullptr, emit ? c->d_tags.as<uint8_t>() : nullptr,
+                         emit ? c->d_read_packed.as<uint8_t>() : nullptr, is.d_cnt.counters, is.d_cnt.err, c->stream));
+    return VTX_OK;
+}
+
+// ---- fetch + filters per (read, locus) pair: counts, then offsets, then the raw records ----
+static int ingest_filter(vtx_ctx* c, IngestState& is) {
+    hipStream_t s = c->stream;
+    const uint32_t n_rec = is.n_rec;
+    if (int rc = ingest_scan_pass(c, is, 0)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(is.cnt, is.d_cnt.counters, sizeof is.cnt, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(is.err, is.d_cnt.err, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (err[0]) return ingest_error(err[0], err[1]);
-    const uint64_t read_bases = cnt[6], tag_bytes = cnt[7], n_pairs = cnt[8];
+    if (is.err[0]) return ingest_error(c, is);
+    const uint64_t read_bases = is.cnt[6], tag_bytes = is.cnt[7], n_pairs = is.cnt[8];
     if (read_bases > 0xF0000000ull || tag_bytes > 0xF0000000ull || n_pairs > 0x7fffffffull)
         return fail(c, VTX_E_UNSUPPORTED, "vtx_submit_bam: the reads of this range need more than one batch (%llu bases, %llu tag bytes, %llu pairs): pack ranges of loci",
                     (unsigned long long)read_bases, (unsigned long long)tag_bytes, (unsigned long long)n_pairs);
-    const uint32_t nr = (uint32_t)n_pairs;
-    if (int rc = raw_reserve(c, nl, nr, g->hap_bytes, read_bases, tag_bytes, true)) return rc;
+    if (int rc = raw_reserve(c, is.g->n_loci, (uint32_t)n_pairs, is.g->hap_bytes, read_bases, tag_bytes, true)) return rc;
     if (n_rec) {
         const size_t tb = vtxk_scan_temp_bytes(n_rec);
         HIP_TRY(c, vtxk_inclusive_scan_u32(c->d_bam_nhit.as<uint32_t>(), c->d_bam_hscan.as<uint32_t>(), n_rec, c->d_scan_tmp.p, tb, s));
         HIP_TRY(c, vtxk_inclusive_scan_u32(c->d_bam_rsz.as<uint32_t>(), c->d_bam_rscan.as<uint32_t>(), n_rec, c->d_scan_tmp.p, tb, s));
         HIP_TRY(c, vtxk_inclusive_scan_u32(c->d_bam_tsz.as<uint32_t>(), c->d_bam_tscan.as<uint32_t>(), n_rec, c->d_scan_tmp.p, tb, s));
-        HIP_TRY(c, vtxg_scan(1, c->d_bam_data.as<uint8_t>(), c->d_bam_rec.as<uint64_t>(), n_rec, f, d_iv_start, d_iv_end, d_iv_locus, d_tid_begin, d_tid_span,
-                             c->d_bam_nhit.as<uint32_t>(), c->d_bam_rsz.as<uint32_t>(), c->d_bam_tsz.as<uint32_t>(), c->d_bam_info.as<vtxg_recinfo>(),
-                             c->d_bam_hscan.as<uint32_t>(), c->d_bam_rscan.as<uint32_t>(), c->d_bam_tscan.as<uint32_t>(), c->d_raw.as<vtx_raw_record>(),
-                             c->d_raw_locus.as<uint32_t>(), c->d_tags.as<uint8_t>(), c->d_read_packed.as<uint8_t>(), d_counters, d_err, s));
+        if (int rc = ingest_scan_pass(c, is, 1)) return rc;
     }
     HIP_TRY(c, vtxk_unpack_nibbles(c->d_read_packed.as<uint8_t>(), read_bases / 2, c->d_read.as<uint8_t>(), s));
     HIP_TRY(c, hipEventRecord(c->ev[EV_FILTER_END], s));
     HIP_TRY(c, hipStreamSynchronize(s));
+    return VTX_OK;
+}
+
+// the stages' device times, the preparation every raw batch goes through (raw_prepare), and the statistics
+static int ingest_publish(vtx_ctx* c, const IngestState& is) {
+    const uint64_t read_bases = is.cnt[6], tag_bytes = is.cnt[7];
+    const uint32_t nr = (uint32_t)is.cnt[8];
     float inflate_ms = 0, index_ms = 0, filter_ms = 0;
     HIP_TRY(c, hipEventElapsedTime(&inflate_ms, c->ev[EV_INGEST_START], c->ev[EV_INFLATE_END]));
     HIP_TRY(c, hipEventElapsedTime(&c->crc_ms, c->ev_crc[0], c->ev_crc[1]));
     HIP_TRY(c, hipEventElapsedTime(&index_ms, c->ev_crc[1], c->ev[EV_INDEX_END]));
     HIP_TRY(c, hipEventElapsedTime(&filter_ms, c->ev[EV_INDEX_END], c->ev[EV_FILTER_END]));
-    c->bam_n_rec = n_rec; c->bam_n_raw = nr; c->bam_utotal = utotal; c->bam_read_bases = read_bases; c->bam_tag_bytes = tag_bytes;
+    c->bam_n_rec = is.n_rec; c->bam_n_raw = nr; c->bam_utotal = is.L.utotal; c->bam_read_bases = read_bases; c->bam_tag_bytes = tag_bytes;
     vtx_raw_stats rs{};
-    if (int rc = raw_prepare(c, nl, nr, read_bases, tag_bytes, true, max_hap, max_hap_all, false, &rs)) return rc;
-    if (st) {
-        st->num_reads = cnt[0]; st->num_low_mapq = cnt[1]; st->num_non_primary = cnt[2]; st->num_duplicates = cnt[3];
-        st->num_not_useful = cnt[4]; st->num_no_barcode_tag = cnt[5];
-        st->bam_records = n_rec; st->raw_records = nr; st->inflated_bytes = utotal; st->compressed_bytes = comp_bytes;
-        st->raw = rs; st->h2d_ms = h2d_ms; st->inflate_ms = inflate_ms; st->index_ms = index_ms; st->filter_ms = filter_ms;
-        st->prefetch_ms = prefetched ? c->pf_ms : 0.f; st->prefetch_wait_ms = prefetched ? pf_wait_ms : 0.f;
+    if (int rc = raw_prepare(c, is.g->n_loci, nr, read_bases, tag_bytes, true, is.max_hap, is.max_hap_all, false, &rs)) return rc;
+    if (vtx_ingest_stats* st = is.st) {
+        st->num_reads = is.cnt[0]; st->num_low_mapq = is.cnt[1]; st->num_non_primary = is.cnt[2]; st->num_duplicates = is.cnt[3];
+        st->num_not_useful = is.cnt[4]; st->num_no_barcode_tag = is.cnt[5];
+        st->bam_records = is.n_rec; st->raw_records = nr; st->inflated_bytes = is.L.utotal; st->compressed_bytes = is.L.comp_bytes;
+        st->raw = rs; st->h2d_ms = is.h2d_ms; st->inflate_ms = inflate_ms; st->index_ms = index_ms; st->filter_ms = filter_ms;
+        st->prefetch_ms = is.prefetched ? c->pf_ms : 0.f; st->prefetch_wait_ms = is.prefetched ? is.pf_wait_ms : 0.f;
     }
     return VTX_OK;
+}
+
+static int ingest_run(vtx_ctx* c, const vtx_bam_ingest* g, const vtx_bam_segments* sg, vtx_ingest_stats* st) {
+    IngestState is;
+    is.g = g; is.sg = sg; is.st = st;
+    if (int rc = ingest_check_layout(c, is)) return rc;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    ingest_settle_prefetch(c, is);
+    if (int rc = ingest_reserve(c, is)) return rc;
+    if (int rc = ingest_upload(c, is)) return rc;
+    if (int rc = ingest_inflate_crc(c, is)) return rc;
+    if (int rc = ingest_chains(c, is)) return rc;
+    if (int rc = ingest_filter(c, is)) return rc;
+    return ingest_publish(c, is);
 }
 
 int vtx_submit_bam(vtx_ctx* c, const vtx_bam_ingest* g, vtx_ingest_stats* st) {
     if (!c) return VTX_E_INVAL;
     if (!g) return fail(c, VTX_E_INVAL, "vtx_submit_bam: null argument");
-    return submit_bam_impl(c, g, nullptr, st);
+    return ingest_run(c, g, nullptr, st);
 }
 
 // ---- vtx_submit_bam_segments: the same ingest for a plan of several stretches of the file (sparse loci) ----
 int vtx_submit_bam_segments(vtx_ctx* c, const vtx_bam_segments* sg, vtx_ingest_stats* st) {
     if (!c) return VTX_E_INVAL;
     if (!sg) return fail(c, VTX_E_INVAL, "vtx_submit_bam_segments: null argument");
-    return submit_bam_impl(c, &sg->base, sg, st);
+    return ingest_run(c, &sg->base, sg, st);
 }
 
 // Test hook: bgzf_inflate_kernel on arbitrary raw-DEFLATE payloads — block i is file[blocks[i].coff .. + clen) and must inflate to
@@ -1505,21 +1554,21 @@ int vtx_debug_inflate(vtx_ctx* c, const uint8_t* file, uint64_t file_bytes, cons
     std::vector<vtxg_block> blocks(n);
     uint64_t utotal = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        if (blk[i].coff + blk[i].clen > file_bytes || blk[i].isize > 65536u) return fail(c, VTX_E_INVAL, "vtx_debug_inflate: block %u outside the input or above 64 KiB", i);
+        if (blk[i].coff > file_bytes || blk[i].clen > file_bytes - blk[i].coff || blk[i].isize > 65536u) return fail(c, VTX_E_INVAL, "vtx_debug_inflate: block %u outside the input or above 64 KiB", i);
         blocks[i] = vtxg_block{blk[i].coff, utotal, blk[i].clen, blk[i].isize};
         utotal += blk[i].isize;
     }
     if (utotal > out_cap) return fail(c, VTX_E_INVAL, "vtx_debug_inflate: output buffer too small");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
-    if (c->pf_thread.joinable()) c->pf_thread.join();
-    c->pf_valid = false;
+    prefetch_settle(c, Prefetch::Drop);
     HIP_TRY(c, c->d_bam_comp.reserve((size_t)file_bytes + kBamPad));
     HIP_TRY(c, c->d_bam_data.reserve((size_t)utotal + kBamPad));
     HIP_TRY(c, c->d_bam_blocks.reserve((size_t)n * sizeof(vtxg_block) + 16));
-    HIP_TRY(c, c->d_bam_cnt.reserve(VTXG_N_COUNTERS * sizeof(uint64_t) + 4 * sizeof(uint32_t)));
+    BamCounters cnt;
+    if (int rc = reserve_bam_counters(c, &cnt)) return rc;
     HIP_TRY(c, c->d_bam_seed_cnt.reserve((size_t)n * sizeof(uint32_t) + 16));
-    uint32_t* d_err = (uint32_t*)(c->d_bam_cnt.as<unsigned long long>() + VTXG_N_COUNTERS);
+    uint32_t* d_err = cnt.err;
     HIP_TRY(c, hipMemsetAsync(d_err, 0, 4 * sizeof(uint32_t), s));
     HIP_TRY(c, hipMemsetAsync(c->d_bam_data.p, 0xEE, (size_t)utotal + kBamPad, s));
     if (file_bytes) HIP_TRY(c, hipMemcpyAsync(c->d_bam_comp.p, file, (size_t)file_bytes, hipMemcpyHostToDevice, s));
@@ -1543,18 +1592,18 @@ int vtx_debug_crc32(vtx_ctx* c, const uint8_t* data, uint64_t n_bytes, const uin
     }
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
-    if (c->pf_thread.joinable()) c->pf_thread.join();
-    static const int crc_width = VTX_DEV_ENV("VTX_CRC_WIDTH") ? atoi(VTX_DEV_ENV("VTX_CRC_WIDTH")) : VTXG_CRC_WIDTH;
+    prefetch_settle(c, Prefetch::Keep);                   // (upload() below; d_bam_comp is not touched)
     HIP_TRY(c, c->d_bam_data.reserve((size_t)n_bytes + 64));
     HIP_TRY(c, c->d_bam_blocks.reserve((size_t)n * sizeof(vtxg_block) + 16));
-    HIP_TRY(c, c->d_bam_cnt.reserve(VTXG_N_COUNTERS * sizeof(uint64_t) + 4 * sizeof(uint32_t)));
+    BamCounters cnt;
+    if (int rc = reserve_bam_counters(c, &cnt)) return rc;
     HIP_TRY(c, c->d_bam_seed_cnt.reserve((size_t)n * sizeof(uint32_t) + 16));
-    uint32_t* d_err = (uint32_t*)(c->d_bam_cnt.as<unsigned long long>() + VTXG_N_COUNTERS);
+    uint32_t* d_err = cnt.err;
     HIP_TRY(c, hipMemsetAsync(d_err, 0, 4 * sizeof(uint32_t), s));
     if (int rc = upload(c, {{c->d_bam_data.p, data, (size_t)n_bytes}, {c->d_bam_blocks.p, blocks.data(), (size_t)n * sizeof(vtxg_block)}})) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
     HIP_TRY(c, hipEventRecord(c->ev_crc[0], s));
-    HIP_TRY(c, vtxg_crc32(nullptr, c->d_bam_blocks.as<vtxg_block>(), n, c->d_bam_data.as<uint8_t>(), d_err, c->d_bam_seed_cnt.as<uint32_t>(), 0, crc_width, s));
+    HIP_TRY(c, vtxg_crc32(nullptr, c->d_bam_blocks.as<vtxg_block>(), n, c->d_bam_data.as<uint8_t>(), d_err, c->d_bam_seed_cnt.as<uint32_t>(), 0, crc_width(), s));
     HIP_TRY(c, hipEventRecord(c->ev_crc[1], s));
     if (n) HIP_TRY(c, hipMemcpyAsync(crc_out, c->d_bam_seed_cnt.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
@@ -2596,10 +2645,11 @@ static int mtx_text_engine(vtx_ctx* c, const char* fn, bool real, bool gz, int w
     uint32_t kSlab = 48u << 20;                           // lines per pass: <= 33 bytes each (real: <= 54), 32-bit text offsets
     static_assert((uint64_t)(48u << 20) * VTXG_MTX_LINE_MAX < (1ull << 32), "a pass's text has 32-bit offsets");
     if (VTX_DEV_ENV("VTX_MTX_SLAB")) kSlab = std::min(kSlab, (uint32_t)std::max(1, atoi(VTX_DEV_ENV("VTX_MTX_SLAB"))));   // test hook: several passes
-    HIP_TRY(c, c->d_bam_cnt.reserve(VTXG_N_COUNTERS * sizeof(uint64_t) + 4 * sizeof(uint32_t)));
-    double* d_sum = (double*)c->d_bam_cnt.p;
-    uint32_t* d_flag = (uint32_t*)(c->d_bam_cnt.as<unsigned long long>() + VTXG_N_COUNTERS);
-    HIP_TRY(c, hipMemsetAsync(c->d_bam_cnt.p, 0, VTXG_N_COUNTERS * sizeof(uint64_t) + 4 * sizeof(uint32_t), s));
+    BamCounters cnt;                                      // (here: the sum in the first counter's eight bytes, the flag in the first of the four words)
+    if (int rc = reserve_bam_counters(c, &cnt)) return rc;
+    double* d_sum = (double*)cnt.counters;
+    uint32_t* d_flag = cnt.err;
+    HIP_TRY(c, hipMemsetAsync(cnt.counters, 0, BamCounters::kBytes, s));
     *text_total = 0;
     bool first = true;
     for (uint64_t base = 0; base < nnz || (hl && first); base += kSlab) {
@@ -2636,8 +2686,7 @@ static int mtx_text_engine(vtx_ctx* c, const char* fn, bool real, bool gz, int w
         const uint32_t n_chunks = (uint32_t)((t_bytes + vtxd::CHUNK - 1) / vtxd::CHUNK);
         // d_bam_comp is where vtx_prefetch_file's thread copies a BAM: like every other user of it, wait for that thread and drop the
         // prefetch before the encoder's slots take the buffer (a later vtx_submit_bam uploads its bytes again)
-        if (c->pf_thread.joinable()) c->pf_thread.join();
-        c->pf_valid = false;
+        prefetch_settle(c, Prefetch::Drop);
         DevBuf &slots = c->d_bam_comp, &packed = c->d_bam_rec, &sizes = c->d_bam_rsz, &ends = c->d_bam_rscan, &tok = c->d_bam_info;
         if (e == hipSuccess) e = slots.reserve((size_t)n_chunks * vtxd::SLOT);
         if (e == hipSuccess) e = packed.reserve((size_t)n_chunks * vtxd::SLOT);
@@ -2714,7 +2763,7 @@ int vtx_mtx_part(vtx_ctx* c, int which, int real, int gz, struct vtx_mtx_part* o
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     // the part comes back through download(): the copy workers' pinned buffers and streams, which a vtx_prefetch_file in flight is using
     // for its upload — wait for it (plain parts too; a gz part drops the prefetched bytes as well, in the engine)
-    if (c->pf_thread.joinable()) c->pf_thread.join();
+    prefetch_settle(c, Prefetch::Keep);
     MtxSink sink;
     uint64_t text_total = 0;
     double sum = 0.0;

@@ -6,10 +6,9 @@
 #include <stdint.h>
 
 #include "../../include/vtx.h"
+#include "vtx_ingest_plan_core.h"      // vtxg_block, vtxg_segment: the plan in the device's layout, and the host code that makes it
 #include "vtx_scan_core.h"
 
-// a BGZF block on the device: offsets into the uploaded compressed range / the inflated buffer
-struct vtxg_block { uint64_t coff, uoff; uint32_t clen, isize; };
 // the read filters of evaluate_alns that need no dictionary (src/main.rs:833-864) + the tag to look for (--bam-tag, :126-129)
 typedef vtxs::Filter vtxg_filter;      // { n_ref, min_mapq, primary_only, no_duplicates, bam_tag }: vtx_scan_core.h, where the scan reads it
 // per BAM record with at least one surviving pair: where its tags lie (relative to the record body) and their lengths
@@ -23,9 +22,6 @@ struct vtxg_recinfo { uint32_t bc_rel, umi_rel, lens; };
 #define VTXG_ERR_RECORD (1u << 17)     // a record whose fields run past its block_size
 #define VTXG_ERR_SEG_END (1u << 18)    // a segment's end is not proven: the record there may still overlap its loci (err[2]: how many)
 #define VTXG_ERR_CRC (1u << 19)        // a block whose inflated bytes do not have the CRC32 of its trailer (err[1]: the first; only when every block inflated)
-// a segment of a segmented plan on the device: its stretch [ubegin, ulimit) of the concatenated inflated stream, where its last chain
-// lands, one past its last seed, and what the record at end_upos must lie beyond (vtx_bam_segment)
-struct vtxg_segment { uint64_t ubegin, ulimit, end_upos; uint32_t seed_end; int32_t end_tid, end_pos; uint32_t flags; };
 
 extern "C" {
 hipError_t vtxg_inflate(const uint8_t* comp, const vtxg_block* blocks, uint32_t n_blocks, uint8_t* out, uint32_t* err, uint32_t* status, uint32_t b_base, hipStream_t s);
