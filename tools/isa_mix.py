@@ -1,5 +1,6 @@
 """VALU issue cycles per instruction of one kernel: its opcode histogram (static, from `hipcc -S`) weighted by the
-per-opcode issue cycles measured by tools/valu_peak.hip on the GPU box (profiles/r03_valu_peak_microbench.txt).
+per-opcode issue cycles measured by tools/valu_peak.hip on the GPU box (profiles/r15_valu_peak_microbench.txt: round 3's list plus
+v_dot4_u32_u8, 4.1 cycles).
 On gfx950 a wave64 VALU instruction issues over 2 cycles (SIMD-32: 32-bit add / and / xor / mov / shift ...) or 4 (v_max / v_min,
 3-operand ops, packed 16-bit, DPP, SDWA, v_cndmask ...), quarter-rate 32-bit multiplies over 8+ — so "instructions x 4" overstates
 and "x 2" understates what the pipe is busy.  The histogram is STATIC (every instruction of the kernel counted once): a proxy
@@ -68,7 +69,7 @@ def klass(op, cyc):
 
 def main():
     asm = open(sys.argv[1]).read()
-    cyc = microbench(sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "r03_valu_peak_microbench.txt"))
+    cyc = microbench(sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "r15_valu_peak_microbench.txt"))
     sym, body = kernel_body(asm, sys.argv[2])
     hist = collections.Counter()
     for l in body.split("\n"):

@@ -2107,6 +2107,35 @@ extern "C" hipError_t vtxk_diag_phases(unsigned long long* out) {
     memset(h, 0, sizeof h);
     return hipMemcpyToSymbol(HIP_SYMBOL(g_diag_phase), h, sizeof h);
 }
+#ifdef VTX_DEVTOOLS
+// (developer build; tests/test_gpu_byteops.py) the DEVICE paths of vtx_fast_core.h's byte compare and base codes over n pairs of 8-byte
+// words given and returned in host memory: out[i] = eq8(a[i], b[i]), out[n + i] = kw_code8(a[i]), out[2 n + i] = kw_code of a[i]'s low
+// six bytes, as the kernels call it
+__global__ void dev_byteops_kernel(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = vtxf::eq8(a[i], b[i]);
+    out[n + i] = vtxf::kw_code8(a[i]);
+    out[2 * n + i] = vtxf::kw_code((uint32_t)a[i], (uint32_t)(a[i] >> 32) & 0xffffu);
+}
+extern "C" hipError_t vtxk_dev_byteops(const uint64_t* a, const uint64_t* b, uint32_t n, uint32_t* out) {
+    if (!n) return hipSuccess;
+    uint64_t* d_in = nullptr;
+    uint32_t* d_out = nullptr;
+    hipError_t e = hipMalloc(&d_in, 2 * (size_t)n * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc(&d_out, 3 * (size_t)n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(d_in, a, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_in + n, b, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(dev_byteops_kernel, dim3((n + 255u) / 256u), dim3(256), 0, 0, d_in, d_in + n, n, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, 3 * (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return e;
+}
+#endif
 #define REFINE_WORDS 12u       // record of band_refine_kernel: task, d, r | cert << 4 | far matches << 16, zc, RM piece words
 extern "C" uint32_t vtxk_band_refine_words(void) { return REFINE_WORDS; }
 // record of band_tail_kernel (vtx_fast_core.h: tail_pack), word-major: word i of record p at i * cap + p — the ballot-compacted positions
@@ -2490,16 +2519,34 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
         if (cnt > 0) {
             const uint32_t base = atomicAdd(&q_count[0], (uint32_t)cnt);
             if (t3_mode) {
-                for (int t = 0; t < cnt; ++t) {
-                    const int e = vtxf::m_next(need_it), s0 = e - 2;
-                    // the pair's rows s0 .. e as three bits (rows below 0 are no rows)
-                    const int kk = s0 >> 6, b = s0 & 63;                                      // (s0 < 0: kk = -1)
-                    const uint64_t wl = kk <= 0 ? nrows.w[0] : (kk == 1 ? nrows.w[1] : (A > 3 && kk == 3 ? nrows.w[vtxf::NW - 1] : nrows.w[2]));
-                    const uint64_t wh = kk <= 0 ? nrows.w[1] : (kk == 1 ? nrows.w[2] : (A > 3 && kk == 2 ? nrows.w[vtxf::NW - 1] : 0ull));
-                    const uint32_t m3 = s0 < 0 ? ((uint32_t)nrows.w[0] << (uint32_t)(-s0)) & 7u
-                                               : (uint32_t)((wl >> b) | (b > 61 ? wh << (64 - b) : 0ull)) & 7u;
-                    q_ent[base + t] = (uint16_t)(((uint32_t)(tid >> 1) << 11) | (m3 << 8) | (uint32_t)e);
+                // The block ends are walked in place, 32 bits at a time with a compile-time index (need_it is m_iter(nd) as it was
+                // made: cur = nd.w[0], nx[k - 1] = nd.w[k]; m_next is not called in this mode, so the words never move).  The rows
+                // e - 2, e - 1, e of the block that ends at bit b of such a half are bits b, b + 1, b + 2 of nrows << 2 there — one
+                // funnel shift over that half and its upper neighbour; rows below 0 are the zeros the shift by 2 brought in.  (Until
+                // round 15: m_next, then nrows' words picked by a run-time index — chains of 64-bit selects — and a run-time
+                // 64-bit shift with a cross-word fix-up, per entry.)
+                const uint32_t pr = (uint32_t)(tid >> 1) << 11;
+                int t = 0;
+#pragma unroll
+                for (int k = 0; k < A; ++k) {
+                    uint64_t& ndk = k == 0 ? need_it.cur : need_it.nx[k > 0 ? k - 1 : 0];
+                    const uint64_t s2k = (nrows.w[k] << 2) | (k > 0 ? nrows.w[k > 0 ? k - 1 : 0] >> 62 : 0ull);
+                    const uint32_t s2n = (k + 1 < A ? (uint32_t)nrows.w[k + 1 < A ? k + 1 : k] << 2 : 0u) | (uint32_t)(nrows.w[k] >> 62);
+                    uint32_t hw[2] = {(uint32_t)ndk, (uint32_t)(ndk >> 32)};
+#pragma unroll
+                    for (int hf = 0; hf < 2; ++hf) {
+                        const uint32_t lo = hf ? (uint32_t)(s2k >> 32) : (uint32_t)s2k, hi = hf ? s2n : (uint32_t)(s2k >> 32);
+                        while (hw[hf] != 0 && t < cnt) {
+                            const uint32_t b = (uint32_t)__builtin_ctz(hw[hf]);
+                            hw[hf] &= hw[hf] - 1u;
+                            const uint32_t m3 = __builtin_amdgcn_alignbit(hi, lo, b) & 7u;
+                            q_ent[base + t] = (uint16_t)(pr | (m3 << 8) | ((uint32_t)(64 * k + 32 * hf) + b));
+                            ++t;
+                        }
+                    }
+                    ndk = (uint64_t)hw[0] | ((uint64_t)hw[1] << 32);
                 }
+                need_it.st -= cnt;
             } else {
                 for (int t = 0; t < cnt; ++t) q_ent[base + t] = (uint16_t)(((uint32_t)(tid >> 1) << 8) | (uint32_t)vtxf::m_next(need_it));
             }

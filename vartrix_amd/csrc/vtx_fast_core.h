@@ -154,20 +154,34 @@ VTXF_HD uint32_t t3_word_b(uint32_t c) { return 2u * ((c >> 2) & 0xffu); }
 VTXF_HD uint32_t t3_bit_b(uint32_t c) { return 16u + ((c & 3u) | ((c >> 10) << 2)); }
 VTXF_HD uint32_t t3_word_c(uint32_t c) { return 2u * (c & 0xffu) + 1u; }
 VTXF_HD uint32_t t3_bit_c(uint32_t c) { return c >> 8; }
-// 16-bit code of eight bases (two bits per byte, like kw_code): base i at bits 2 i
-VTXF_HD uint32_t kw_code8(uint64_t w8) {
-    uint32_t a = ((uint32_t)w8 >> 1) & 0x03030303u, b = ((uint32_t)(w8 >> 32) >> 1) & 0x03030303u;
-    a |= a >> 6; a = (a | (a >> 12)) & 0xffu;
-    b |= b >> 6; b = (b | (b >> 12)) & 0xffu;
-    return a | (b << 8);
+// Byte and bit compaction by dot product (device code only): v_dot4_u32_u8 sums four bytes times four byte weights in one instruction,
+// which is what "one or two bits of every byte, side by side" is — a shift-and-or ladder otherwise.  The host builds of this header (the
+// unit tests of the kernel logic, the sanitized cores, the host pass of hipcc) keep the portable code; tests/test_gpu_byteops.py pins the
+// two against the definition and against each other.
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_udot4)
+#define VTXF_DOT4 1
+#endif
+#endif
+#ifndef VTXF_DOT4
+#define VTXF_DOT4 0
+#endif
+// two bits per byte of four bytes ((b >> 1) & 3 each), byte i at bits 2 i
+VTXF_HD uint32_t kw_pack4(uint32_t v) {
+    uint32_t a = (v >> 1) & 0x03030303u;
+#if VTXF_DOT4
+    return __builtin_amdgcn_udot4(a, 0x40100401u, 0u, false);
+#else
+    a |= a >> 6;
+    return (a | (a >> 12)) & 0xffu;
+#endif
 }
+// 16-bit code of eight bases (two bits per byte, like kw_code): base i at bits 2 i
+VTXF_HD uint32_t kw_code8(uint64_t w8) { return kw_pack4((uint32_t)w8) | (kw_pack4((uint32_t)(w8 >> 32)) << 8); }
 // 12-bit code of a k-mer, two bits per byte ((b >> 1) & 3: A 0, C 1, T 2, G 3; any other byte lands on one of them — equal
 // bytes always give equal codes, which is all a presence filter needs)
 VTXF_HD uint32_t kw_code(uint32_t lo, uint32_t hi) {
-    uint32_t a = (lo >> 1) & 0x03030303u, b = (hi >> 1) & 0x0303u;
-    a |= a >> 6; a = (a | (a >> 12)) & 0xffu;          // bytes 0-3 -> bits 0-7
-    b = (b | (b >> 6)) & 0xfu;                         // bytes 4-5 -> bits 0-3
-    return a | (b << 8);
+    return kw_pack4(lo) | (kw_pack4(hi & 0xffffu) << 8);       // bytes 0-3 -> bits 0-7, bytes 4-5 -> bits 8-11
 }
 
 // hash of a k-mer (bytes 0-3 in lo, bytes 4-5 in hi): bucket = bits 18.. of the product, tag = its top 4 bits
@@ -257,15 +271,30 @@ template <class F> VTXF_FN void m_for_each(M192 a, F f) {
         for (uint64_t v = a.w[k]; v; v &= v - 1) f(64 * k + ctz64(v));
 }
 
-// 8 byte-equality flags of two 8-byte words as 8 bits
-VTXF_FN uint32_t eq8(uint64_t a, uint64_t b) {
+// 8 byte-INequality flags of two 8-byte words as 8 bits, at bits NE8_SH .. NE8_SH + 7 (nothing set below or above them).
+// Device: the flag of a byte stays where the non-zero test leaves it (bit 7: adding 0x7f to the low seven bits carries into bit 7 and
+// never beyond — each byte's sum is at most 0xfe), the dot products weigh byte i with 2^i — the second accumulating into the first — and
+// the callers fold the shift by 7 into the one they need anyway.
+#if VTXF_DOT4
+constexpr int NE8_SH = 7;
+VTXF_FN uint32_t ne8_raw(uint64_t a, uint64_t b) {
+    const uint32_t zl = (uint32_t)a ^ (uint32_t)b, zh = (uint32_t)(a >> 32) ^ (uint32_t)(b >> 32), lo7 = 0x7f7f7f7fu, b7 = 0x80808080u;
+    const uint32_t fl = (((zl & lo7) + lo7) | zl) & b7, fh = (((zh & lo7) + lo7) | zh) & b7;
+    return __builtin_amdgcn_udot4(fh, 0x80402010u, __builtin_amdgcn_udot4(fl, 0x08040201u, 0u, false), false);
+}
+#else
+constexpr int NE8_SH = 0;
+VTXF_FN uint32_t ne8_raw(uint64_t a, uint64_t b) {
     const uint64_t z = a ^ b, lo7 = 0x7f7f7f7f7f7f7f7full;
-    const uint64_t t = ~(((z & lo7) + lo7) | z | lo7);        // 0x80 in every byte of z that is zero
+    const uint64_t t = (((z & lo7) + lo7) | z) & ~lo7;        // 0x80 in every byte of z that is not zero
     const uint32_t l = (uint32_t)(t >> 7), h = (uint32_t)(t >> 39);   // flags at bits 0, 8, 16, 24
     const uint32_t cl = (l | (l >> 7) | (l >> 14) | (l >> 21)) & 0xfu;
     const uint32_t ch = (h | (h >> 7) | (h >> 14) | (h >> 21)) & 0xfu;
     return cl | (ch << 4);
 }
+#endif
+// 8 byte-equality flags of two 8-byte words as 8 bits
+VTXF_FN uint32_t eq8(uint64_t a, uint64_t b) { return (ne8_raw(a, b) >> NE8_SH) ^ 0xffu; }
 
 // Same-diagonal joins of the run bound (proof: oracle/vtx_certify.c).  D >= 1 bases between two runs on one diagonal:
 //   join_free(D)     6 ceil((D + 5) / 6) - D: the gap-free stretch with as few mismatches as runs of <= 5 allow (a caller that
@@ -456,15 +485,19 @@ template <int C> VTXF_FN uint64_t diag_mask_word(const ReadWords& rw, const uint
     W16 h[4];
 VTXF_UNROLL
     for (int k = 0; k < 4; ++k) h[k] = ld16(yb + (8 * (8 * C + 2 * k) + d));
-    uint64_t out = 0;
+    // The MISMATCH flags, assembled as two 32-bit halves with compile-time shifts and complemented once.  An 8-base word outside
+    // [wa, wb) is not zeroed here: all of its bits lie outside [max(0, -d), min(m, n - d)) — 8 wa <= -d, 8 wb >= min(m, n - d) — and
+    // diag_mask ANDs with exactly that range.  (The word test stays where it guards an ADDRESS: the read's bytes beyond RW words.)
+    uint32_t half[2] = {0u, 0u};
 VTXF_UNROLL
     for (int k = 0; k < 8; ++k) {
         const int w = 8 * C + k;
         const uint64_t xw = w < RW ? rw.w[w < RW ? w : 0] : ld8(x + 8 * (w >= wa && w < wb ? w : 0));        // (compile-time choice: C is)
-        const uint64_t e = (uint64_t)eq8(xw, (k & 1) ? h[k >> 1].b : h[k >> 1].a) << (8 * k);
-        out |= (w >= wa && w < wb) ? e : 0ull;
+        const uint32_t ne = ne8_raw(xw, (k & 1) ? h[k >> 1].b : h[k >> 1].a);
+        const int s = 8 * (k & 3) - NE8_SH;                      // (a constant once the loop is unrolled)
+        half[k >> 2] |= s < 0 ? ne >> (s < 0 ? -s : 0) : ne << (s < 0 ? 0 : s);
     }
-    return out;
+    return ~((uint64_t)half[0] | ((uint64_t)half[1] << 32));
 }
 template <int A = NW> VTXF_FN M192 diag_mask(const ReadWords& rw, const uint8_t* x, int m, const Tab& tb, int n, int d) {
     const uint8_t* yb = tb.gt + tb.bytes;
@@ -528,7 +561,7 @@ VTXF_FN bool verify_diag(const uint8_t* x, int m, const Tab& tb, int n, int dc) 
     const int vlo = imax(0, -dc), vhi = imin(m, n - dc);
     if (vhi - vlo < 20) return false;                     // (the mask must hold >= 20 matching bases anyway)
     const int p = vlo + ((vhi - vlo - 8) >> 1);
-    return __builtin_popcount(eq8(ld8(x + p), ld8(tb.gt + tb.bytes + (p + dc)))) >= 6;
+    return __builtin_popcount(ne8_raw(ld8(x + p), ld8(tb.gt + tb.bytes + (p + dc)))) <= 2;      // (at most two of the eight differ)
 }
 template <class LN, int A = NW> VTXF_FN Front front_rest(const uint8_t* x, int m, const Tab& tb, int n, const LN& ln, int d, M192 M, bool tw = false);
 
