@@ -169,7 +169,7 @@ struct vtx_ctx {
     int read_format = VTX_READS_BYTES;     // vtx_set_read_format
     DevBuf d_read_packed;                  // VTX_READS_NIBBLES: the arena as uploaded, unpacked into d_read
     uint64_t gt_used = 0;      // bytes of d_gtables the last banded run's table kernel wrote (vtx_debug_tables)
-    DevBuf d_band_ws, d_band_ws2, d_band, d_poly, d_gtables, d_hard, d_over, d_over2, d_pend, d_pend_buf, d_cnt, d_band2, d_hard2, d_fail, d_fail_tmp, d_refine, d_tail;   // banded flavour
+    DevBuf d_band_ws, d_band_ws2, d_band, d_poly, d_gtables, d_hard, d_over, d_over2, d_pend, d_pend_buf, d_cnt, d_band2, d_hard2, d_fail, d_fail_tmp, d_refine, d_tail, d_recheck;   // banded flavour
     DevBuf d_tight2, d_tight2_pack;                                          // band_diag2_kernel: tasks whose band is one diagonal stretch after all
     DevBuf d_recheck2, d_recheck2_pack;                                      // ... of which the full-matrix check did not settle (full != certificate); first they hold band_stream_kernel's task list and diagonals
     DevBuf d_sweep_log;                                                      // band_sweep_kernel: the section logs of the resident workgroups (48 MB: 1 536 x 8 x 1 024 words)
@@ -803,7 +803,7 @@ void vtx_destroy(vtx_ctx* c) {
                       &c->d_cnt, &c->d_redo, &c->d_redo_cnt, &c->d_bc_slots, &c->d_bc_hash, &c->d_bc_off, &c->d_bc_bytes,
                       &c->d_raw, &c->d_tags, &c->d_raw_locus, &c->d_key_lc, &c->d_key_lc2, &c->d_key_umi, &c->d_key_umi2,
                       &c->d_idx, &c->d_idx2, &c->d_shape, &c->d_shape2, &c->d_seq, &c->d_locus_cnt, &c->d_locus_scan,
-                      &c->d_prep_cnt, &c->d_sort_tmp, &c->d_fail, &c->d_fail_tmp, &c->d_refine, &c->d_tail, &c->d_tight, &c->d_tight_pack, &c->d_dband, &c->d_dband_pack, &c->d_dense, &c->d_stage, &c->d_sweep_log, &c->d_tight2, &c->d_tight2_pack, &c->d_recheck2, &c->d_recheck2_pack};
+                      &c->d_prep_cnt, &c->d_sort_tmp, &c->d_fail, &c->d_fail_tmp, &c->d_refine, &c->d_tail, &c->d_recheck, &c->d_tight, &c->d_tight_pack, &c->d_dband, &c->d_dband_pack, &c->d_dense, &c->d_stage, &c->d_sweep_log, &c->d_tight2, &c->d_tight2_pack, &c->d_recheck2, &c->d_recheck2_pack};
     for (DevBuf* b : bufs) b->release();
     c->d_slow_ws.release(); c->d_slow_retry.release(); c->d_read_packed.release();
     c->d_csr_indptr.release(); c->d_csr_flag.release(); c->d_csr_keys.release(); c->d_csr_iota.release(); c->d_csr_perm.release(); c->d_csr_tmp.release();
@@ -853,6 +853,11 @@ static uint32_t band_refine_cap(uint32_t chunk) { return std::max(65536u, chunk 
 // records band_diag_kernel may leave for band_tail_kernel per chunk (tasks whose generic set grows: 8 % of a clean workload's tasks; a
 // task that does not fit finishes in its wavefront).  128 bytes each; no room for them (the buffer is optional): every task stays.
 static uint32_t band_tail_cap(uint32_t chunk) { return std::max(65536u, chunk / 4); }
+// records band_diag_kernel may leave for the recheck per chunk (tasks that fail its coarse harmless test; the tail's record, 128 bytes).
+// Measured on the host mirror (profiles/r16_recheck_census.txt): 0.08 % of the headline's tasks, 0.6 % at 3 % substitution errors,
+// 2.1 % at 8 % — one task in 32 (3.1 %) is one and a half times the noisiest of them: 190 MB on the headline's 48.6 M tasks.  A task that finds no slot
+// leaves as before (W_NOT_HARMLESS: the sweep), and so does every task when the buffer cannot be had.
+static uint32_t band_recheck_cap(uint32_t chunk) { return std::max(16384u, chunk / 32); }
 struct BandPlan {
     uint64_t n_tasks = 0;
     uint32_t chunk = 0, band_stride = 0, hard_cap = 0, pend_cap = 0, slots = 0, poly_stride = 0, tasks_per_locus = 0;
@@ -911,6 +916,10 @@ static int band_reserve(vtx_ctx* c, BandPlan& p, bool quiet) {
     if (p.gt_bytes && c->d_tail.reserve((size_t)band_tail_cap(p.chunk) * vtxk_band_tail_words() * sizeof(uint32_t)) != hipSuccess) {
         (void)hipGetLastError();                                                                          // records for band_tail_kernel
         c->d_tail.release();
+    }
+    if (p.gt_bytes && c->d_recheck.reserve((size_t)band_recheck_cap(p.chunk) * vtxk_band_tail_words() * sizeof(uint32_t)) != hipSuccess) {
+        (void)hipGetLastError();                                                                          // records for the recheck
+        c->d_recheck.release();
     }
     if (p.gt_bytes) RES(d_tight, (size_t)p.chunk * sizeof(uint32_t));       // tasks with a certificate but no verdict ...
     if (p.gt_bytes) RES(d_tight_pack, (size_t)p.chunk * sizeof(uint32_t));  // ... and their bands (one diagonal stretch each: one word)
@@ -1735,9 +1744,9 @@ inline hipError_t launch_band_run(const TaskArrays& a, uint32_t n, uint32_t task
             gtables, gt_bytes, task_list, long_lists, s); }
 inline hipError_t launch_band_diag(const TaskArrays& a, uint32_t n, uint32_t task_base, uint32_t mh, uint32_t mh_min, uint32_t* fail_list, uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus,
         uint32_t gt_l0, uint32_t gt_n, uint8_t* gtables, size_t gt_bytes, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, uint32_t* tail_rec,
-        uint32_t tail_cap, bool tail_inline, hipStream_t s) {
+        uint32_t tail_cap, bool tail_inline, uint32_t* recheck_rec, uint32_t recheck_cap, hipStream_t s) {
     return vtxk_launch_band_diag(n, task_base, a.records, a.rec_locus, a.loci, a.read, a.hap, mh, mh_min, a.ref, a.alt, fail_list, refine_rec, refine_cap, counters, tasks_per_locus, gt_l0, gt_n, gtables, gt_bytes, stats, tight_list,
-            tight_pack, stage, dense_list, dense_mask, max_read, tail_rec, tail_cap, tail_inline ? 1 : 0, s); }
+            tight_pack, stage, dense_list, dense_mask, max_read, tail_rec, tail_cap, tail_inline ? 1 : 0, recheck_rec, recheck_cap, s); }
 inline hipError_t launch_band_refine(const TaskArrays& a, const uint32_t* recs, uint32_t n, uint32_t mh, uint32_t* fail_list, uint32_t* counters, uint32_t tasks_per_locus, uint32_t gt_l0, const uint8_t* gtables, int stats,
         uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, const uint32_t* n_dev, hipStream_t s) {
     return vtxk_launch_band_refine(recs, n, a.records, a.rec_locus, a.loci, a.read, mh, a.ref, a.alt, fail_list, counters, tasks_per_locus, gt_l0, gtables, stats, tight_list, tight_pack, stage, n_dev, s); }
@@ -1781,7 +1790,8 @@ struct BandPass {
     uint32_t fork_nt = 0;
     // one chunk of tasks [base, base + nt): the loci whose tables are resident, and what band_diag_kernel left for band_run_kernel
     struct Chunk { uint64_t base; uint32_t nt; bool last; uint32_t gt_l0 = 0, gt_n = 0; bool diag = false, swept = false; uint32_t n_fail = 0; const uint32_t* fail_list = nullptr;
-                   uint32_t tail_cap = 0; bool tail_side = false; };    // band_tail_kernel's record buffer; whether diag_sweep_path launches that kernel on the side stream
+                   uint32_t tail_cap = 0; bool tail_side = false;       // band_tail_kernel's record buffer; whether diag_sweep_path launches that kernel on the side stream
+                   uint32_t recheck_cap = 0; };                         // the recheck's record buffer (0: no recheck for this chunk)
     BandPass(vtx_ctx* c_, RunState& rs_, uint32_t mh_, uint32_t mh_min_, uint64_t t_begin_, uint64_t t_end_, bool chunk_tables_) : c(c_), rs(rs_), mh(mh_), mh_min(mh_min_), t_begin(t_begin_), t_end(t_end_),
              chunk_tables(chunk_tables_) {}
     int run() {
@@ -1993,8 +2003,15 @@ struct BandPass {
         ch.tail_cap = std::min(tail_cap, tail_cap_hook);
         // The sweep path with its two branches: band_tail_kernel goes to the side one (diag_sweep_path).  Every other path keeps it behind band_diag_kernel on this stream.
         ch.tail_side = sweep_path && fork_on() && !kn.tail_inline && vtxk_band_tail_on(c->d_tail.as<uint32_t>(), ch.tail_cap);
+        // The recheck of the tasks that fail band_diag_kernel's harmless test (diag_sweep_path launches it): on the path with the two branches only, where a task it clears has a tight
+        // list to go to and band_corridor_kernel behind it.  Every other path (no fork, no tight list, round 3's, four-byte entries: vtxk_band_recheck_on) hands the kernel no buffer.
+        const uint32_t recheck_cap = (uint32_t)std::min<size_t>(band_recheck_cap(bp.chunk), c->d_recheck.cap / (vtxk_band_tail_words() * sizeof(uint32_t)));
+        const uint32_t recheck_cap_hook = VTX_DEV_ENV("VTX_DIAG_RECHECK_CAP") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_RECHECK_CAP")) : 0xffffffffu;   // test hook: a small buffer (read per run)
+        ch.recheck_cap = std::min(recheck_cap, recheck_cap_hook);
+        if (!(sweep_path && fork_on() && refine_list && !kn.no_corridor && vtxk_band_recheck_on(c->d_recheck.as<uint32_t>(), ch.recheck_cap, mh))) ch.recheck_cap = 0;
         const hipError_t e = launch_band_diag(a, ch.nt, (uint32_t)ch.base, mh, mh_min, c->d_fail.as<uint32_t>(), refine_list, refine_cap, d_cnt, bp.tasks_per_locus, ch.gt_l0, ch.gt_n, c->d_gtables.as<uint8_t>(), bp.gt_bytes,
-                                              kn.diag_stats, tight_list, tight_pack, rs.stage, dense_list, kn.dense_mask, c->max_read_len, c->d_tail.as<uint32_t>(), ch.tail_cap, !ch.tail_side, s);
+                                              kn.diag_stats, tight_list, tight_pack, rs.stage, dense_list, kn.dense_mask, c->max_read_len, c->d_tail.as<uint32_t>(), ch.tail_cap, !ch.tail_side,
+                                              ch.recheck_cap ? c->d_recheck.as<uint32_t>() : nullptr, ch.recheck_cap, s);
         if (e != hipSuccess) {
             // (the tables do not fit the buffer for this chunk: band_run_kernel alone, tables in LDS)
             if (getenv("VTX_DEBUG")) fprintf(stderr, "[vtx] band_diag_kernel not launched for tasks [%llu, +%u): %s\n", (unsigned long long)ch.base, ch.nt, hipGetErrorString(e));
@@ -2017,6 +2034,8 @@ struct BandPass {
     // so with a tight list it ends decided, as a refine / corridor record or as a tight entry (vtx_band.hip: band_tail_kernel): VTX_CNT_RUN_LEFT and VTX_CNT_DENSE, which the main branch
     // starts from, are final when band_diag_kernel ends, and the side branch reads its own two counts on the device.  The kernel gets no fail_list and no dense_list: those are the main
     // branch's.  d_tail is free again at EV_BRANCH_END, which the main stream joins before the next chunk.
+    // (It does not wait for the recheck on the main stream either.  Measured: started behind that kernel instead of beside it, the recheck takes what it takes beside the tail,
+    // 0.19 ms — it is a few hundred wavefronts of dependent LDS round trips, not a matter of room — and the step loses 0.17 ms: DESIGN.md 4.3.7.)
     int tail_on_side(const Chunk& ch) {
         HIP_TRY(c, hipStreamWaitEvent(s2, c->ev[EV_DIAG_END], 0));
         HIP_TRY(c, hipEventRecord(c->ev[EV_BRANCH_START], s2));
@@ -2031,6 +2050,14 @@ struct BandPass {
         hipStream_t sb = fork ? s2 : s;                                             // the refine / one-diagonal branch
         if (ch.tail_side) { if (int rc = tail_on_side(ch)) return rc; }             // (before the host waits: it starts while band_diag_kernel drains)
         if (!fork && refine_list) HIP_TRY(c, second_look(ch, std::min(refine_cap, ch.nt), s));
+        // The recheck, on THIS stream, in front of the counter copy: it appends to the fail (or dense) list what it does not clear and to the refine / tight lists what it does — beside
+        // band_tail_kernel on the side stream, through the same atomics — so the four counts below include everything it listed: RUN_LEFT and DENSE are final, REFINE and TIGHT are
+        // the bounds they were.  Its grid comes from the buffer's capacity and it reads its record count on the device: no round trip of its own.
+        if (ch.recheck_cap) {
+            HIP_TRY(c, vtxk_launch_band_recheck(mh, c->max_read_len, a.ref, a.alt, c->d_fail.as<uint32_t>(), refine_list, refine_cap, d_cnt, bp.tasks_per_locus, kn.diag_stats, tight_list, tight_pack, rs.stage,
+                                                dense_list, kn.dense_mask, c->d_recheck.as<uint32_t>(), ch.recheck_cap, s));
+            ++rs.launches;
+        }
         HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_RUN_LEFT, d_cnt + VTX_CNT_RUN_LEFT, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // RUN_LEFT, DENSE, REFINE, TIGHT
         if (ch.tail_side) HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_TAIL, d_cnt + VTX_CNT_TAIL, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
@@ -2254,6 +2281,9 @@ struct BandPass {
             fprintf(stderr, "[vtx] band_refine_kernel: %llu tasks listed\n", (unsigned long long)refined_total);
             fprintf(stderr, "[vtx] band_diag_kernel: %llu of %llu tasks left to band_run_kernel (%.2f %%), %.2f ms: shape=%u no-diagonal=%u pieces=%u matches=%u not-harmless=%u generic=%u not-tight=%u no-main=%u\n",
                     (unsigned long long)diag_left, (unsigned long long)diag_total, 100.0 * (double)diag_left / (double)diag_total, (double)diag_ms, why[1], why[2], why[3], why[4], why[5], why[7], why[8], why[9]);
+            uint32_t cleared = 0;
+            HIP_TRY(c, hipMemcpy(&cleared, d_cnt + VTX_CNT_RECHECK_CLEARED, sizeof cleared, hipMemcpyDeviceToHost));
+            fprintf(stderr, "[vtx] band_tail_kernel, recheck: %u tasks that failed band_diag_kernel's harmless test rechecked, %u cleared\n", why[VTX_CNT_RECHECK_TOTAL - VTX_CNT_DIAG_WHY], cleared);
             if (VTX_DEVTOOLS_ON) fprintf(stderr, "[vtx] band_tail_kernel: %u records routed towards the dense or fail list beside a tight list\n", why[VTX_CNT_TAIL_STRAY - VTX_CNT_DIAG_WHY]);
         }
         if (getenv("VTX_DEBUG") && diag2_total) fprintf(stderr, "[vtx] band_diag2_kernel: %llu tasks looked at, %llu scored, %llu left with a one-diagonal band, %llu to band_sweep_kernel (%llu through band_stream_kernel)\n",

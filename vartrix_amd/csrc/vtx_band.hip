@@ -53,6 +53,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "vtx_device.h"
 #include "vtx_fast_core.h"
@@ -2143,6 +2144,7 @@ extern "C" uint32_t vtxk_band_refine_words(void) { return REFINE_WORDS; }
 extern "C" uint32_t vtxk_band_tail_words(void) { return (uint32_t)vtxf::TAIL_WORDS; }
 #define TAIL_DECIDED 0x80000000u   // (band_tail_kernel, word 3 after its first pass: decided; else why | TAIL_TIGHT)
 #define TAIL_TIGHT 0x10u
+#define TAIL_CLEARED 0x20u         // (its recheck mode: the tight harmless test cleared the task)
 
 // Where a task goes once the last phase of the certificate is over — band_diag_kernel's lanes and band_tail_kernel's (the tasks the
 // former left in the middle of that phase) alike; every lane of the wavefront calls it.  fail: no verdict (why, aux: back_rest's);
@@ -2235,7 +2237,8 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     const uint8_t* __restrict__ gtables, uint32_t gt_l0, int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score,
     uint32_t* __restrict__ fail_list, uint32_t* __restrict__ refine_rec, uint32_t refine_cap, uint32_t* __restrict__ counters,
     uint32_t stats, uint32_t* __restrict__ tight_list, uint32_t* __restrict__ tight_pack, uint8_t* __restrict__ stage,
-    uint32_t* __restrict__ dense_list, uint32_t dense_mask, uint32_t min_hap, uint32_t* __restrict__ tail_rec, uint32_t tail_cap) {
+    uint32_t* __restrict__ dense_list, uint32_t dense_mask, uint32_t min_hap, uint32_t* __restrict__ tail_rec, uint32_t tail_cap,
+    uint32_t* __restrict__ recheck_rec, uint32_t recheck_cap) {
     // min_hap: tasks of loci whose longer haplotype has <= min_hap bases are left alone (vtx_run's second pass over a batch that mixes
     // haplotypes of <= 255 bases with a few longer ones: the first pass, with two-byte entries and the sweep behind it, scored them).
     // dense_list != nullptr (round 4): a task left for a reason in dense_mask (bit = vtxf::Why; by default W_MATCHES: more than 40
@@ -2708,7 +2711,22 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     if (live) vtxf::back_sort(ns, ln, (int)(s_cnt[tid] >> 16));
     PH(8);                                                              // sort
     if (VTX_ABLATE((stats >> 8) & 0xffu) == 7) { if (live && ns == 0x7fffffff) counters[VTX_CNT_DIAG_DUMMY] = 1; return; }            // (profiling aid) ... + the sort
-    if (live && !vtxf::back_harmless(fr, ns, ln)) { live = false; fail = true; why = vtxf::W_NOT_HARMLESS; }
+    // A task that fails the test here — one running maximum over every earlier match: a bound that grows by one per chance match — has
+    // failed the coarse form only.  With a recheck buffer it leaves the tail's record (recheck_rec, counters[VTX_CNT_RECHECK]) and
+    // nothing else: band_tail_kernel's recheck mode runs the tight form on the same list and routes the task.  No buffer, or the
+    // buffer full: W_NOT_HARMLESS, as before.
+    bool recheck = false;
+    if (live && !vtxf::back_harmless(fr, ns, ln)) { live = false; recheck = recheck_rec != nullptr; fail = !recheck; why = vtxf::W_NOT_HARMLESS; }
+    const uint64_t km = __ballot(recheck);
+    if (km) {
+        uint32_t base = 0;
+        const int leader = __ffsll((long long)km) - 1;
+        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_RECHECK], (uint32_t)__popcll(km));
+        base = (uint32_t)__shfl((int)base, leader);
+        const uint32_t pos = base + (uint32_t)__popcll(km & ((1ull << tid) - 1ull));
+        if (recheck && pos >= recheck_cap) { recheck = false; fail = true; }
+        if (recheck) vtxf::tail_pack(recheck_rec + pos, recheck_cap, task, fr, ns, ln);
+    }
     PH(9);                                                              // harmless tests
     // The closure's first scan decides whether the generic set stays empty (92 % of the live tasks: one scan and the main-only run bound
     // on piece words in registers).  A task whose set must grow — closure rescans, a fixpoint over (r + ng)^2 piece pairs — costs what
@@ -2757,7 +2775,13 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
 // 60 - 62 VGPRs and no probe queue (band_diag_kernel: 128): LDS — the lane's words and the GM generic piece words, 8.7 KB a wavefront —
 // bounds it at 18 wavefronts per CU, 4.5 per SIMD, against 4 of band_diag_kernel's that hide the fixpoint's LDS round trips.
 // =============================================================================================
-template <class ST, int A>
+// RECHECK (the kernel's second mode; vtx_fast_core.h: recheck_rest): the records are those of tasks that FAILED band_diag_kernel's
+// harmless test — the coarse form.  The lane gets a byte per match (LaneSR: 2.5 KB more LDS per wavefront), the tight form of the test
+// runs on the record's list, and a task it clears goes on as above: back_rest, then decided, a record for the second look or a tight
+// entry.  A task it does not clear is routed as band_diag_kernel routed it before: W_NOT_HARMLESS, no certificate, towards fail_list
+// (or dense_list when dense_mask names the reason) — so this mode needs those lists and runs in front of their readers.
+// counters[VTX_CNT_RECHECK_TOTAL] / [VTX_CNT_RECHECK_CLEARED]: the records looked at and cleared (statistics).
+template <class ST, int A, bool RECHECK = false>
 __global__ __launch_bounds__(64) void band_tail_kernel(
     uint32_t* __restrict__ tail_rec, uint32_t tail_cap, const uint32_t* __restrict__ n_dev,
     int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score, uint32_t* __restrict__ fail_list, uint32_t* __restrict__ refine_rec,
@@ -2765,9 +2789,12 @@ __global__ __launch_bounds__(64) void band_tail_kernel(
     uint8_t* __restrict__ stage, uint32_t* __restrict__ dense_list, uint32_t dense_mask) {
     __shared__ uint32_t lane_mem[vtxf::LANE_WORDS * 64];
     __shared__ uint32_t gen_mem[vtxf::GM * 64];
-    typedef vtxf::LaneS<ST, vtxf::S_WORDS, (A <= 3)> LaneT;
+    typedef typename std::conditional<RECHECK, vtxf::LaneSR<ST, vtxf::S_WORDS, (A <= 3)>, vtxf::LaneS<ST, vtxf::S_WORDS, (A <= 3)>>::type LaneT;
+    __shared__ uint8_t bound_mem[RECHECK ? LaneT::SMAX * 64 : 64];          // (RECHECK: u(k) of lane t at bound_mem[k * 64 + t], k < SMAX)
     const int tid = threadIdx.x & 63;
-    const LaneT ln{lane_mem + vtxf::S_WORDS * 64 + tid, 64, (ST*)lane_mem + tid, 64};
+    LaneT ln;
+    ln.base = lane_mem + vtxf::S_WORDS * 64 + tid; ln.stride = 64; ln.sb = (ST*)lane_mem + tid; ln.sstride = 64;
+    if constexpr (RECHECK) { ln.ub = bound_mem + tid; ln.ustride = 64; }
     const vtxf::Lane gl{gen_mem + tid, 64};
     const uint32_t nd = *n_dev, n_recs = nd < tail_cap ? nd : tail_cap;
     const uint32_t lanes = gridDim.x * 64u;
@@ -2782,12 +2809,16 @@ __global__ __launch_bounds__(64) void band_tail_kernel(
         int ns = 0;
         uint32_t pack = 0, why = 0, aux = 0xffffffffu;
         const uint32_t task = vtxf::tail_unpack(rec, tail_cap, fr, ns, ln, &pack);
-        const int32_t sc = vtxf::back_rest(fr, ns, ln, gl, &why, 0, nullptr, &aux);
+        bool cleared = true;                                              // (a record of the tail passed the harmless test before it was deferred)
+        int32_t sc;
+        if constexpr (RECHECK) sc = vtxf::recheck_rest(fr, ns, ln, gl, &why, &aux, &cleared);
+        else sc = vtxf::back_rest(fr, ns, ln, gl, &why, 0, nullptr, &aux);
         uint32_t out = TAIL_DECIDED;
         if (sc >= 0) { (((task & 1u) ? alt_score : ref_score) + (task >> 1))[0] = sc; if (stage) stage[task] = 1; }
         else {
-            out = why | (tight_list ? TAIL_TIGHT : 0u);
-            if (tight_list) {
+            const bool keeps = tight_list != nullptr && cleared;          // the task holds its certificate
+            out = why | (keeps ? TAIL_TIGHT : 0u);
+            if (keeps) {
                 static_assert(4 + 2 * vtxf::NW <= 4 + vtxf::RM, "the far rows fit where the main pieces were");
                 const vtxf::M192 far = vtxf::far_rows(fr.d, ns, ln);
 #pragma unroll
@@ -2797,8 +2828,9 @@ __global__ __launch_bounds__(64) void band_tail_kernel(
                 }
             }
         }
-        rec[3 * (size_t)tail_cap] = out;
+        rec[3 * (size_t)tail_cap] = out | (RECHECK && cleared ? TAIL_CLEARED : 0u);
     }
+    if (RECHECK && blockIdx.x == 0 && tid == 0) atomicAdd(&counters[VTX_CNT_RECHECK_TOTAL], n_recs);
     // 2. the routing, wavefront-uniform (its ballots see every lane): the same lane, the same records
     for (uint32_t p0 = blockIdx.x * 64u; p0 < n_recs; p0 += lanes) {
         const uint32_t p = p0 + (uint32_t)tid;
@@ -2811,7 +2843,11 @@ __global__ __launch_bounds__(64) void band_tail_kernel(
         const bool fail = !(out & TAIL_DECIDED), tight = (out & TAIL_TIGHT) != 0;
         // (libvtx_dev.so: with a tight list every undecided record carries TAIL_TIGHT, so the routing below ends at refine_rec or
         // tight_list — what lets this kernel run beside the readers of dense_list / fail_list.  A record that would take either: counted.)
-        if (VTX_DEVTOOLS_ON && tight_list && fail && !tight) atomicAdd(&counters[VTX_CNT_TAIL_STRAY], 1u);
+        if (!RECHECK && VTX_DEVTOOLS_ON && tight_list && fail && !tight) atomicAdd(&counters[VTX_CNT_TAIL_STRAY], 1u);
+        if constexpr (RECHECK) {
+            const uint64_t cm = __ballot(p < n_recs && (out & TAIL_CLEARED) != 0);
+            if (cm && tid == 0) atomicAdd(&counters[VTX_CNT_RECHECK_CLEARED], (uint32_t)__popcll(cm));
+        }
         if (fail && tight) {
             const uint32_t* rec = tail_rec + p;
 #pragma unroll
@@ -2915,7 +2951,11 @@ __global__ __launch_bounds__(256) void band_corridor_kernel(
     uint32_t* __restrict__ tight_list, uint32_t* __restrict__ tight_pack, uint8_t* __restrict__ stage, const uint32_t* __restrict__ n_dev) {
     if (n_dev) { const uint32_t nd = *n_dev; n_recs = nd < n_recs ? nd : n_recs; }
     const int tid = threadIdx.x & 63;
-    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    // The grid covers the HOST's bound of the record count (vtx_api.hip: diag_sweep_path) up to what the device holds at once
+    // (vtxk_launch_band_corridor); the workgroups loop over the device's count, 256 records a trip (uniform per workgroup: the ballot
+    // below sees every lane).
+  for (uint32_t slot0 = blockIdx.x * 256u; slot0 < n_recs; slot0 += gridDim.x * 256u) {
+    const uint32_t slot = slot0 + threadIdx.x;
     bool fail = false;
     uint32_t task = 0, pack = 0;
     if (slot < n_recs) {
@@ -2949,13 +2989,31 @@ __global__ __launch_bounds__(256) void band_corridor_kernel(
             if (stats & 0xffu) atomicAdd(&counters[VTX_CNT_DIAG_WHY + vtxf::W_NOT_TIGHT], 1u);
         }
     }
+  }
+}
+// workgroups of band_corridor_kernel the device holds at once (65 536 when the runtime cannot say)
+static uint32_t corridor_resident_grid() {
+    static const uint32_t n = [] {
+        int dev = 0, cus = 0, per_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, band_corridor_kernel, 256, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
+            (void)hipGetLastError();
+            return 65536u;
+        }
+        return (uint32_t)cus * (uint32_t)per_cu;
+    }();
+    return n;
 }
 extern "C" hipError_t vtxk_launch_band_corridor(const uint32_t* recs, uint32_t n_recs, const vtx_record* records, const uint32_t* rec_locus,
                                                 const vtx_locus* loci, const uint8_t* read_arena, const uint8_t* hap_arena,
                                                 int32_t* ref_score, int32_t* alt_score, uint32_t* counters, int stats,
                                                 uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, const uint32_t* n_dev, hipStream_t s) {
     if (!n_recs) return hipSuccess;
-    hipLaunchKernelGGL(band_corridor_kernel, dim3((n_recs + 255) / 256), dim3(256), 0, s, recs, n_recs, records, rec_locus, loci, read_arena,
+    // (n_dev != nullptr: n_recs is a bound — 3.5 M lanes for the headline's 43 k records — and a workgroup past the device's count costs its
+    //  dispatch: at most a resident grid then.  libvtx_dev.so, VTX_CORRIDOR_FULL_GRID=1: the grid over the bound, for the A/B.)
+    const uint32_t blocks = (n_recs + 255) / 256;
+    const uint32_t grid = n_dev && !VTX_DEV_ENV("VTX_CORRIDOR_FULL_GRID") ? std::min(blocks, corridor_resident_grid()) : blocks;
+    hipLaunchKernelGGL(band_corridor_kernel, dim3(grid), dim3(256), 0, s, recs, n_recs, records, rec_locus, loci, read_arena,
                        hap_arena, ref_score, alt_score, counters, (uint32_t)stats, tight_list, tight_pack, stage, n_dev);
     return hipGetLastError();
 }
@@ -3145,12 +3203,12 @@ extern "C" int vtxk_band_tail_on(const uint32_t* tail_rec, uint32_t tail_cap) {
 // of the records.  With the 65 536 of the launch that has the device to itself a workgroup that ends hands its 8.7 KB of LDS to the
 // next one of this kernel, and a neighbour's workgroup (band_sweep_kernel: 19.1 KB in one piece) finds no room until the last record
 // is taken (DESIGN.md 4.3.7 has the measurement).
-template <class ST, int A>
+template <class ST, int A, bool RECHECK = false>
 static uint32_t tail_resident_grid() {
     static const uint32_t n = [] {
         int dev = 0, cus = 0, per_cu = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, band_tail_kernel<ST, A>, 64, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, band_tail_kernel<ST, A, RECHECK>, 64, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
             (void)hipGetLastError();
             return 65536u;
         }
@@ -3179,6 +3237,31 @@ extern "C" hipError_t vtxk_launch_band_tail(uint32_t max_hap, uint32_t max_read,
 #undef LAUNCH_TAIL
     return hipGetLastError();
 }
+// Whether band_diag_kernel leaves recheck records (tasks that fail its harmless test): a buffer with room, two-byte match entries (the
+// tight test's byte per match is laid out for them: every haplotype <= 255 bases), and (libvtx_dev.so) neither VTX_DIAG_NO_RECHECK=1
+// nor the profiling aids of VTX_DIAG_ABLATE.  As with the tail, the one place that decides it.
+extern "C" int vtxk_band_recheck_on(const uint32_t* recheck_rec, uint32_t recheck_cap, uint32_t max_hap) {
+    return recheck_rec != nullptr && recheck_cap != 0 && diag_narrow(max_hap) && !VTX_DEV_ENV("VTX_DIAG_NO_RECHECK") && !VTX_DEV_ENV("VTX_DIAG_ABLATE");
+}
+// band_tail_kernel's recheck mode over the records a vtxk_launch_band_diag with the same arguments (vtxk_band_recheck_on) left in
+// recheck_rec; s runs behind that band_diag_kernel and in front of every reader of the lists and their counts: the kernel appends to
+// all of them.  A resident grid looping over the device's count (counters[VTX_CNT_RECHECK]): the kernel may run beside
+// band_tail_kernel on another stream, and the host does not know the count.
+extern "C" hipError_t vtxk_launch_band_recheck(uint32_t max_hap, uint32_t max_read, int32_t* ref_score, int32_t* alt_score, uint32_t* fail_list,
+                                               uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, int stats,
+                                               uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask,
+                                               uint32_t* recheck_rec, uint32_t recheck_cap, hipStream_t s) {
+    if (!vtxk_band_recheck_on(recheck_rec, recheck_cap, max_hap) || !fail_list) return hipErrorInvalidValue;
+    const uint32_t st = diag_stats_word(stats, tasks_per_locus);
+#define LAUNCH_RECHECK(AV)                                                                                                               \
+    hipLaunchKernelGGL((band_tail_kernel<uint16_t, AV, true>),                                                                             \
+                       dim3(std::min({(recheck_cap + 63u) / 64u, 65536u, tail_resident_grid<uint16_t, AV, true>()})), dim3(64), 0, s,      \
+                       recheck_rec, recheck_cap, counters + VTX_CNT_RECHECK, ref_score, alt_score, fail_list, refine_rec, refine_cap,      \
+                       counters, st, tight_list, tight_pack, stage, dense_list, dense_mask)
+    if (diag_three_words(max_read)) LAUNCH_RECHECK(3); else LAUNCH_RECHECK(vtxf::NW);
+#undef LAUNCH_RECHECK
+    return hipGetLastError();
+}
 
 // Tables of loci [gt_l0, gt_l0 + n_loci) into gtables (the same layout and bucket count vtxk_launch_band_run picks for this
 // shape of data), then band_diag_kernel over tasks [task_base, task_base + n_tasks).  Returns hipErrorInvalidValue when the
@@ -3190,13 +3273,17 @@ extern "C" hipError_t vtxk_launch_band_diag(uint32_t n_tasks, uint32_t task_base
                                             uint32_t tasks_per_locus, uint32_t gt_l0, uint32_t n_loci, uint8_t* gtables,
                                             size_t gtables_bytes, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage,
                                             uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, uint32_t* tail_rec, uint32_t tail_cap,
-                                            int tail_inline, hipStream_t s) {
+                                            int tail_inline, uint32_t* recheck_rec, uint32_t recheck_cap, hipStream_t s) {
+    // recheck_rec != nullptr: room for recheck_cap records (the tail's layout) of tasks that fail the kernel's harmless test;
+    // counters[VTX_CNT_RECHECK] counts them.  The caller launches vtxk_launch_band_recheck behind this call when vtxk_band_recheck_on
+    // says the records exist.  nullptr: such a task leaves with W_NOT_HARMLESS.
     // max_read: the longest read of the batch (the fast kernels' records) — up to 192 bases the kernel is built with three mask words
     // tail_rec != nullptr: room for tail_cap records of band_tail_kernel (TAIL_WORDS words each, word-major); counters[VTX_CNT_TAIL]
     // counts them.  tail_inline != 0: band_tail_kernel is launched here, behind band_diag_kernel on the same stream; 0: the caller
     // launches it (vtxk_launch_band_tail, when vtxk_band_tail_on says the records exist) on a stream that waits for this one.
     if (!n_tasks) return hipSuccess;
     if (!vtxk_band_tail_on(tail_rec, tail_cap)) tail_rec = nullptr;
+    if (!vtxk_band_recheck_on(recheck_rec, recheck_cap, max_hap)) recheck_rec = nullptr;
     const uint32_t n_heads = pick_heads(tasks_per_locus, true);
     const size_t tstride = band_table_stride(max_hap, n_heads);
     if (!gtables || (size_t)n_loci * 2 * tstride > gtables_bytes) return hipErrorInvalidValue;
@@ -3208,8 +3295,9 @@ extern "C" hipError_t vtxk_launch_band_diag(uint32_t n_tasks, uint32_t task_base
     hipLaunchKernelGGL((band_diag_kernel<4, STV, AV>), dim3(((n_blocks + 7) / 8) * 8), dim3(256), 0, s, n_tasks, task_base, n_blocks,       \
                        records, rec_locus, loci, read_arena, max_hap, (uint32_t)tstride, n_heads, (const uint8_t*)gtables, gt_l0,           \
                        ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list, tight_pack, stage, dense_list,     \
-                       dense_mask, min_hap, tail_rec, tail_cap)
+                       dense_mask, min_hap, tail_rec, tail_cap, recheck_rec, recheck_cap)
     if (tail_rec) { const hipError_t e = hipMemsetAsync(counters + VTX_CNT_TAIL, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
+    if (recheck_rec) { const hipError_t e = hipMemsetAsync(counters + VTX_CNT_RECHECK, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
     const bool three = diag_three_words(max_read);
     if (diag_narrow(max_hap)) { if (three) LAUNCH_DIAG(uint16_t, 3); else LAUNCH_DIAG(uint16_t, vtxf::NW); }
     else { if (three) LAUNCH_DIAG(uint32_t, 3); else LAUNCH_DIAG(uint32_t, vtxf::NW); }

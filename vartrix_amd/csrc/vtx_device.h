@@ -74,7 +74,10 @@ enum VtxBandCnt {
     VTX_CNT_DIAG_DUMMY = 40,      //   where band_diag_kernel's profiling aids leave their dummy store (W_NOT_TIGHT's word: results are wrong anyway)
     VTX_CNT_TAIL = 44,            //   records band_diag_kernel leaves for band_tail_kernel (zeroed per launch)
     VTX_CNT_TAIL_STRAY = 45,      //   libvtx_dev.so: records band_tail_kernel routed towards dense_list / fail_list although a tight list exists (must stay 0)
-    VTX_CNT_STREAMED = 48,        // band_diag2_kernel: tasks handed to band_stream_kernel (zeroed per call of the second stage)
+    VTX_CNT_RECHECK = 46,         //   records band_diag_kernel leaves for band_tail_kernel's recheck mode: tasks that failed its harmless test (zeroed per launch)
+    VTX_CNT_RECHECK_TOTAL = 47,   //   statistics: the records that kernel looked at, over the pass ...
+    VTX_CNT_RECHECK_CLEARED = 49, //   ... and those the tight harmless test cleared
+    VTX_CNT_STREAMED = 48,       // band_diag2_kernel: tasks handed to band_stream_kernel (zeroed per call of the second stage)
     VTX_CNT_SWEEP_WHY = 56,       // [56, 64): band_sweep_kernel's reasons (statistics)
     VTX_CNT_SLOW = 13,            // slow_align_kernel: tasks to retry.  Aliases VTX_CNT_DENSE: the slow path runs after the banded stage
     VTX_CNT_WORDS = 64
@@ -120,8 +123,13 @@ hipError_t vtxk_launch_band_diag(uint32_t n_tasks, uint32_t task_base, const vtx
                                  uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, uint32_t gt_l0, uint32_t n_loci,
                                  uint8_t* gtables, size_t gtables_bytes, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage,
                                  uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, uint32_t* tail_rec, uint32_t tail_cap,
-                                 int tail_inline, hipStream_t s);
+                                 int tail_inline, uint32_t* recheck_rec, uint32_t recheck_cap, hipStream_t s);
 int vtxk_band_tail_on(const uint32_t* tail_rec, uint32_t tail_cap);
+int vtxk_band_recheck_on(const uint32_t* recheck_rec, uint32_t recheck_cap, uint32_t max_hap);
+hipError_t vtxk_launch_band_recheck(uint32_t max_hap, uint32_t max_read, int32_t* ref_score, int32_t* alt_score, uint32_t* fail_list,
+                                    uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, int stats,
+                                    uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask,
+                                    uint32_t* recheck_rec, uint32_t recheck_cap, hipStream_t s);
 hipError_t vtxk_launch_band_tail(uint32_t max_hap, uint32_t max_read, int32_t* ref_score, int32_t* alt_score, uint32_t* fail_list,
                                  uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, int stats,
                                  uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask,

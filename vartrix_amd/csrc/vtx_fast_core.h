@@ -415,6 +415,23 @@ template <class ST, int SW = S_WORDS, bool UB4_ = true> struct LaneS {
     VTXF_MEM uint32_t& at(int i) const { return base[i * stride]; }
     VTXF_MEM ST& s(int k) const { return sb[k * sstride]; }
 };
+// The first stage's lane with the second stage's byte per match (u(k)): the same words, the same list, and back_harmless takes its
+// TIGHT form on it.  The lane of the recheck (recheck_rest below): a task that failed the first stage's harmless test is looked at
+// again from its tail record, not probed again.
+template <class ST, int SW = S_WORDS, bool UB4_ = true> struct LaneSR {
+    typedef ST SType;
+    static constexpr bool UB4 = UB4_;
+    uint32_t* base; int stride;
+    ST* sb; int sstride;
+    uint8_t* ub; int ustride;
+    static constexpr int XS = sizeof(ST) == 2 ? 8 : 16;
+    static constexpr int SMAX = SW * 4 / (int)sizeof(ST);
+    static constexpr uint32_t YM = (1u << XS) - 1u, ONE = (1u << XS) | 1u;
+    static constexpr bool TIGHT = true;
+    VTXF_MEM uint32_t& at(int i) const { return base[i * stride]; }
+    VTXF_MEM ST& s(int k) const { return sb[k * sstride]; }
+    VTXF_MEM uint8_t& u(int k) const { return ub[k * ustride]; }
+};
 // The lane of the SECOND stage (band_diag2_kernel, round 5): two-byte entries, S2_WORDS words of them, and a byte per entry for the
 // dp bound of the harmless test (u(k)): with it the bound of an off-diagonal match comes from the matches that can really precede it
 // (back_harmless), not from every earlier one.
@@ -1155,6 +1172,21 @@ template <class LN> VTXF_FN uint32_t tail_unpack(const uint32_t* rec, size_t str
         }
     }
     return task;
+}
+// ---- the recheck of a task that failed the FIRST stage's harmless test (band_diag_kernel -> band_tail_kernel's recheck mode).  That
+//      test bounds the dp of a match by one running maximum over every earlier match of the list: the bound grows by one per chance
+//      match.  The task leaves the same record (tail_pack: the sorted list of ALL its off-diagonal matches — ns <= SMAX and back_sort —
+//      the main piece words, the front's figures); unpacked into a lane with a byte per match (LaneSR) the test runs again in its TIGHT
+//      form, the second stage's (back_harmless: the bound and why it holds; the list it needs: probe_harmless_stream's comment), and
+//      a task it clears goes on exactly as one the first test cleared: closure, run bound, verdict.
+//      *cleared: the tight test's verdict.  Returns the score (>= 0), or -1 with *why — W_NOT_HARMLESS when not cleared (the task has
+//      no certificate), back_rest's otherwise (the task keeps its certificate and its one-diagonal band). ----
+template <class LN> VTXF_FN int32_t recheck_rest(const Front& fr, int ns, const LN& ln, const Lane& gl, uint32_t* why, uint32_t* aux, bool* cleared) {
+    static_assert(LN::TIGHT, "the recheck is the tight form of the test: a lane with a byte per match");
+    if (aux) *aux = 0xffffffffu;
+    *cleared = back_harmless(fr, ns, ln);
+    if (!*cleared) { *why = W_NOT_HARMLESS; return -1; }
+    return back_rest(fr, ns, ln, gl, why, 0, nullptr, aux);
 }
 
 // ======== the corridor certificate (round 6; band_corridor_kernel; proof below, brute-force check in tests/test_fastcore.py) ========
