@@ -1963,8 +1963,10 @@ __global__ __launch_bounds__(64) void band_tables_kernel(const vtx_locus* __rest
                                                          const uint8_t* __restrict__ hap_arena, uint32_t max_hap, uint32_t min_hap,
                                                          uint32_t table_stride, uint32_t n_heads, uint8_t* __restrict__ gtables, uint32_t with_t3) {
     // with_t3 == 0: t3[] is neither built nor written, and the launch leaves its 2 KB out of the workgroup's LDS (band_diag_kernel will not
-    // read it: vtxk_launch_band_diag decides per batch, band_use_t3) — the kernel's time is the bytes it writes and the tables in flight per
-    // CU.  (The twin lists stay: at four reads per locus they cost the table kernel 0.04 ms and save band_diag_kernel 0.1.)
+    // read it: vtxk_launch_band_diag decides per batch, band_use_t3) — the kernel's time is the bytes it writes: 100 k loci, a workgroup
+    // per table, 0.41 ms without t3[] (1.06 GB, 30 workgroups per CU) and 0.56 with (1.47 GB, 22 per CU), 2.6 TB/s both, before the
+    // non-temporal copy-out.  (The twin lists stay: at four reads per locus they cost the table kernel 0.04 ms and save band_diag_kernel 0.1.)
+    // The launch gives every table a workgroup of its own (launch_band_tables); the loop over t serves the developer library's grid hook.
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     uint8_t* tb = (uint8_t*)smem;
     const int tid = threadIdx.x;
@@ -2018,7 +2020,8 @@ __global__ __launch_bounds__(64) void band_tables_kernel(const vtx_locus* __rest
             }
         }
         // (t3[] built on its own in the LDS the entries take afterwards and copied out first — 2 KB less LDS per wavefront, 30 tables in
-        //  flight per CU instead of 22 — was measured: 0.68 against 0.69 ms.  The kernel's time is the bytes it writes now: 1.44 GB.)
+        //  flight per CU instead of 22 — was measured in round 6 under the looping grid: 0.68 against 0.69 ms.  With a workgroup per table the
+        //  kernel writes at the same rate with 22 and with 30 tables in flight per CU: its time is the bytes it writes, 1.47 GB.)
         // uniqueness flags (build_tables: a haplotype with a byte >= 0x80 gets none), the presence bitmap, and (round 6) the three-row
         // sets and the twin list — the pairs (y, y') of positions with the same k-mer in (y, y') order: rounds of 64 positions, the
         // twins of a position counted by the walk that decides its uniqueness, a prefix sum per round, the chains ascend (the same
@@ -2090,9 +2093,13 @@ __global__ __launch_bounds__(64) void band_tables_kernel(const vtx_locus* __rest
             }
         }
         wave_sync();
-        const uint4* src = (const uint4*)smem;
-        uint4* dst = (uint4*)(gtables + (size_t)t * table_stride);
-        for (uint32_t i = tid; i < used_bytes / 16; i += 64) dst[i] = src[i];
+        // non-temporal stores: the kernel's time is the bytes it writes (1.47 GB for 100 k loci with t3[]: 2.6 TB/s with plain stores,
+        // 2.8 with these), and band_diag_kernel reads a table long after it was written (0.567 -> 0.523 ms, the
+        // reader's time unchanged)
+        typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
+        const u32x4* src = (const u32x4*)smem;
+        u32x4* dst = (u32x4*)(gtables + (size_t)t * table_stride);
+        for (uint32_t i = tid; i < used_bytes / 16; i += 64) __builtin_nontemporal_store(src[i], dst + i);
     }
 }
 
@@ -2284,7 +2291,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     const uint32_t slot = blk * 256 + threadIdx.x;
     const bool have = slot < n_tasks;
     const uint32_t task = task_base + slot;
-    bool fail = false, live = false, whole = false, twins = false;
+    bool fail = false, live = false, whole = false, twins = false, load = false;
     uint32_t why = 0;
     // (where a task's score goes is recomputed at each of the four stores: a pointer held across the kernel is two registers of 128)
     auto my_score = [&]() -> int32_t* { return ((task & 1u) ? alt_score : ref_score) + (task >> 1); };
@@ -2305,6 +2312,12 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
         const vtx_locus loc = loci[my_locus];
         m = (int)rec.read_len; n = (int)(hap ? loc.alt_len : loc.ref_len);
         o_read[tid] = rec.read_off;                                      // (also where this lane drops out: its partner may probe the read)
+        x = read_arena + rec.read_off;                                   // (... and takes half of the read's words from this lane, below)
+        // one of the pair's two lanes gets as far as its table (the tests below, with the longer haplotype for n): BOTH load their
+        // half of the read.  (A haplotype below six bases beside an ordinary one — a deletion at a padding of one or two bases: the
+        // short one's lane drops out, and the other lane's read ended at base 8 HW when the halves were loaded by live lanes only.)
+        const uint32_t mx = max(loc.ref_len, loc.alt_len);
+        load = m >= vtxf::K && m <= 64 * A && (uint32_t)m <= VTX_FAST_READ_LEN && mx >= (uint32_t)vtxf::K && mx <= max_hap && mx > min_hap;
         if (m == 0 || n == 0) {
             *my_score() = 0;                                             // empty read / haplotype: score 0
             if (stage) stage[task] = 1;
@@ -2318,7 +2331,6 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
             tb.bytes = tb.ent + vtxf::tab_bytes_off(max_hap, n_heads);
             tb.uq = tb.ent + vtxf::tab_uq_off(max_hap, n_heads);
             tb.pb = tb.ent + vtxf::tab_pb_off(max_hap, n_heads);
-            x = read_arena + rec.read_off;
             live = true;
             // (round 6) a haplotype with a twin list (two-byte entries only: positions are bytes there): the matches of the rows whose
             // main-diagonal k-mer is intact come from the list, the probes look at the other rows only.  (Asked here: the byte is on
@@ -2340,7 +2352,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
         for (int k = 0; k < HW / 2; ++k) {                             // words [HW half + 2k, + 2): bytes [8 HW half + 16 k, + 16)
             const int off = 8 * HW * half + 16 * k;
             uint4 v = make_uint4(0, 0, 0, 0);
-            if (live && off < m) __builtin_memcpy(&v, x + off, 16);    // (the arena is padded by 16 bytes)
+            if (load && off < m) __builtin_memcpy(&v, x + off, 16);    // (the arena is padded by 16 bytes)
             mine[2 * k] = (uint64_t)v.x | ((uint64_t)v.y << 32);
             mine[2 * k + 1] = (uint64_t)v.z | ((uint64_t)v.w << 32);
         }
@@ -3027,6 +3039,11 @@ static uint32_t gt_max_tpl() {
 }
 // the tables of n_loci loci in global memory: band_tables_kernel (a table per wavefront); VTX_BAND_TABLES_V1=1: round 3's kernel
 // (a locus per wavefront, serial chain insertion) — the reference the new one is compared with byte for byte (tests)
+//
+// The grid: a workgroup per table.  Rounds 4 - 16 launched min(2 n_loci, 8 192) workgroups that looped over the tables; the kernel
+// gets faster with every step towards short workgroups and is slower on the grid the device holds at once than on those 8 192
+// (DESIGN.md 4.3.2 has the sweep: 100 k loci with t3[], 5 888 resident workgroups 0.79 ms, 8 192 0.68, 25 000 0.61, 200 000 0.56) —
+// as band_tail_kernel with the device to itself (4.3.7).  The loop stays in the kernel for the developer library's grid hook.
 static void launch_band_tables(const vtx_locus* loci, uint32_t gt_l0, uint32_t n_loci, const uint8_t* hap_arena, uint32_t max_hap, uint32_t min_hap,
                                size_t tstride, uint32_t n_heads, uint8_t* gtables, bool with_t3, hipStream_t s) {
 #ifdef VTX_DEVTOOLS
@@ -3037,7 +3054,10 @@ static void launch_band_tables(const vtx_locus* loci, uint32_t gt_l0, uint32_t n
     }
 #endif
     const size_t lds = with_t3 ? tstride : (size_t)((vtxf::tab_t3_off(max_hap, n_heads) + 15u) & ~15u);     // (the kernel's used_bytes)
-    hipLaunchKernelGGL(band_tables_kernel, dim3(std::min(2u * n_loci, 256u * 32u)), dim3(64), lds, s, loci, gt_l0, n_loci,
+    uint32_t grid = 2u * n_loci;
+    // (libvtx_dev.so, VTX_BAND_TABLES_GRID: any grid — the measurements of DESIGN.md 4.3.2, and a test's few tables round the loop)
+    if (VTX_DEV_ENV("VTX_BAND_TABLES_GRID")) grid = std::min(1u << 20, std::max(1u, (uint32_t)atoi(VTX_DEV_ENV("VTX_BAND_TABLES_GRID"))));
+    hipLaunchKernelGGL(band_tables_kernel, dim3(grid), dim3(64), lds, s, loci, gt_l0, n_loci,
                            hap_arena, max_hap, min_hap, (uint32_t)tstride, n_heads, gtables, with_t3 ? 1u : 0u);
 }
 // Blocks of three rows and t3[] (vtx_fast_core.h): 2 KB more to write per table, whatever the depth.  Headline 14.67 ms per step without
