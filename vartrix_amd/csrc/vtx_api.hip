@@ -1670,7 +1670,7 @@ int vtx_fetch_records(vtx_ctx* c, vtx_record* records, uint32_t* rec_begin, uint
 
 namespace {
 
-// ---- vtx_run: the hooks, the arrays every launch takes, the launchers' short forms --------------------------------------------
+// ---- vtx_run: the hooks, the state its stages share -------------------------------------------------------------------------
 // The developer hooks of vtx_run that hold for the life of the process (libvtx_dev.so; in libvtx.so every VTX_DEV_ENV is the constant
 // nullptr and the members are their defaults), and whether VTX_DEBUG asked for the kernels' statistics.  Read once, by band_knobs().
 inline bool env_is(const char* v, const char* what) { return v && !strcmp(v, what); }
@@ -1699,62 +1699,8 @@ struct BandKnobs {
     int diag_stats = getenv("VTX_DEBUG") ? 1 : 0;                               // band_diag_kernel and its followers count theirs
 };
 const BandKnobs& band_knobs() { static const BandKnobs k; return k; }
-// The batch's arrays that nearly every kernel launch takes; filled once per run from the context.
-struct TaskArrays { const vtx_record* records; const uint32_t* rec_locus; const vtx_locus* loci; const uint8_t* read; const uint8_t* hap; int32_t* ref; int32_t* alt; };
-// What the stages of one vtx_run share.  stage: one byte per task saying which stage decided it (vtx_fetch_stage), or nullptr
-struct RunState { TaskArrays a{}; uint8_t* stage = nullptr; uint32_t launches = 0, hard_total = 0; float band_run_ms = 0; };
-// vtxk_launch_*(...) with the arrays taken from the bundle: a call shows what distinguishes it.
-inline hipError_t launch_sw_full(const TaskArrays& a, int R, int GL, uint32_t n, const uint32_t* work, uint32_t mh, hipStream_t s) {
-    return vtxk_launch_sw_full(R, GL, n, work, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, mh, s); }
-inline hipError_t launch_sw_full_lut(const TaskArrays& a, int R, uint32_t n, const uint32_t* work, uint32_t mh, uint32_t loci_cap, uint32_t* redo, uint32_t* redo_count, hipStream_t s) {
-    return vtxk_launch_sw_full_lut(R, n, work, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, mh, loci_cap, redo, redo_count, s); }
-inline hipError_t launch_sw_full_duo(const TaskArrays& a, int R, uint32_t n, const uint32_t* work, uint32_t mh, uint32_t loci_cap, uint32_t* redo, uint32_t* redo_count, uint32_t pair_cols, hipStream_t s) {
-    return vtxk_launch_sw_full_duo(R, n, work, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, mh, loci_cap, redo, redo_count, pair_cols, s); }
-inline hipError_t launch_sw_banded(const TaskArrays& a, const int* shape, uint32_t n, const uint32_t* hard, const uint16_t* band, uint32_t band_stride, uint32_t mh, hipStream_t s) {
-    return vtxk_launch_sw_banded(shape[0], shape[1], n, hard, a.records, a.rec_locus, a.loci, a.read, a.hap, band, band_stride, a.ref, a.alt, mh, s); }
-inline hipError_t launch_sw_banded_dev(const TaskArrays& a, const int* shape, uint32_t n_cap, const uint32_t* hard, const uint32_t* n_dev, const uint16_t* band, uint32_t band_stride, uint32_t mh, hipStream_t s) {
-    return vtxk_launch_sw_banded_dev(shape[0], shape[1], n_cap, hard, n_dev, a.records, a.rec_locus, a.loci, a.read, a.hap, band, band_stride, a.ref, a.alt, mh, s); }
-inline hipError_t launch_sw_check(const TaskArrays& a, const int* shape, uint32_t n_cap, const uint32_t* list, const uint32_t* packs, const uint32_t* n_dev, uint32_t mh, uint32_t* recheck_list, uint32_t* recheck_pack,
-        uint32_t* recheck_count, uint8_t* stage, hipStream_t s) {
-    return vtxk_launch_sw_check(shape[0], shape[1], n_cap, list, packs, n_dev, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, mh, recheck_list, recheck_pack, recheck_count, stage, s); }
-inline hipError_t launch_sw_diag_band(const TaskArrays& a, const int* shape, uint32_t n_cap, const uint32_t* list, const uint32_t* packs, const uint32_t* n_dev, uint32_t mh, uint8_t* stage, hipStream_t s) {
-    return vtxk_launch_sw_diag_band(shape[0], shape[1], n_cap, list, packs, n_dev, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, mh, stage, s); }
-inline hipError_t launch_band_expand(const TaskArrays& a, const uint32_t* hard, uint32_t n, const uint16_t* src, uint32_t src_stride, uint16_t* band, uint32_t band_stride, hipStream_t s) {
-    return vtxk_launch_band_expand(hard, n, a.records, a.rec_locus, a.loci, src, src_stride, band, band_stride, s); }
-inline hipError_t launch_band(const TaskArrays& a, const uint32_t* tasks, uint32_t n, uint8_t* ws, uint64_t ws_stride, uint32_t m_cap, uint32_t mh, uint16_t* band, uint32_t band_stride, uint32_t* hard, uint32_t* over,
-        uint32_t* counters, int in_lds, uint32_t max_read, hipStream_t s) {
-    return vtxk_launch_band(tasks, n, 0, a.records, a.rec_locus, a.loci, a.read, a.hap, ws, ws_stride, m_cap, mh, a.ref, a.alt, band, band_stride, hard, over, counters, in_lds, max_read, s); }
-inline hipError_t launch_band_coop(const TaskArrays& a, int tier, const uint32_t* tasks, uint32_t n, uint32_t mh, uint16_t* band, uint32_t band_stride, uint32_t* hard, uint32_t* over, uint32_t* counters, hipStream_t s) {
-    return vtxk_launch_band_coop(tier, tasks, n, a.records, a.rec_locus, a.loci, a.read, a.hap, mh, a.ref, a.alt, band, band_stride, hard, over, counters, s); }
-inline hipError_t launch_band_sweep(const TaskArrays& a, const uint32_t* tasks, uint32_t n, uint16_t* band, uint32_t band_stride, uint32_t* hard, uint32_t* over, uint32_t* counters, uint32_t* stat_counters, uint8_t* stage,
-        uint32_t* glog, hipStream_t s) {
-    return vtxk_launch_band_sweep(tasks, n, nullptr, a.records, a.rec_locus, a.loci, a.read, a.hap, band, band_stride, hard, over, counters, stat_counters, stage, nullptr, glog, s); }
-#ifdef VTX_DEVTOOLS
-inline hipError_t launch_band_sweep_v1(const TaskArrays& a, int tier, const uint32_t* tasks, uint32_t n, uint16_t* band, uint32_t band_stride, uint32_t* hard, uint32_t* over, uint32_t* counters, uint32_t* stat_counters, uint8_t* stage,
-        hipStream_t s) {
-    return vtxk_launch_band_sweep_v1(tier, tasks, n, nullptr, a.records, a.rec_locus, a.loci, a.read, a.hap, band, band_stride, hard, over, counters, stat_counters, stage, nullptr, s); }
-#endif
-inline hipError_t launch_slow_align(const TaskArrays& a, const uint32_t* recs, const uint32_t* tasks, uint32_t n, int banded, uint8_t* ws, uint64_t ws_stride, uint32_t m_cap, uint32_t mh, uint32_t max_read, uint32_t* retry,
-        uint32_t* counters, hipStream_t s) {
-    return vtxk_launch_slow_align(recs, tasks, n, banded, a.records, a.rec_locus, a.loci, a.read, a.hap, ws, ws_stride, m_cap, mh, max_read, a.ref, a.alt, retry, counters, s); }
-inline hipError_t launch_band_run(const TaskArrays& a, uint32_t n, uint32_t task_base, uint32_t mh, uint32_t mh_min, uint32_t* logbuf, uint16_t* poly, uint32_t poly_stride, uint32_t* hard, uint32_t* over, uint32_t* pend,
-        uint32_t* pend_buf, uint32_t hard_cap, uint32_t pend_cap, uint32_t* counters, uint32_t tasks_per_locus, uint32_t gt_l0, uint32_t gt_n, uint8_t* gtables, size_t gt_bytes, const uint32_t* task_list, int long_lists,
-        hipStream_t s) {
-    return vtxk_launch_band_run(n, task_base, a.records, a.rec_locus, a.loci, a.read, a.hap, mh, mh_min, a.ref, a.alt, logbuf, poly, poly_stride, hard, over, pend, pend_buf, hard_cap, pend_cap, counters, tasks_per_locus, gt_l0, gt_n,
-            gtables, gt_bytes, task_list, long_lists, s); }
-inline hipError_t launch_band_diag(const TaskArrays& a, uint32_t n, uint32_t task_base, uint32_t mh, uint32_t mh_min, uint32_t* fail_list, uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus,
-        uint32_t gt_l0, uint32_t gt_n, uint8_t* gtables, size_t gt_bytes, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, uint32_t* tail_rec,
-        uint32_t tail_cap, bool tail_inline, uint32_t* recheck_rec, uint32_t recheck_cap, hipStream_t s) {
-    return vtxk_launch_band_diag(n, task_base, a.records, a.rec_locus, a.loci, a.read, a.hap, mh, mh_min, a.ref, a.alt, fail_list, refine_rec, refine_cap, counters, tasks_per_locus, gt_l0, gt_n, gtables, gt_bytes, stats, tight_list,
-            tight_pack, stage, dense_list, dense_mask, max_read, tail_rec, tail_cap, tail_inline ? 1 : 0, recheck_rec, recheck_cap, s); }
-inline hipError_t launch_band_refine(const TaskArrays& a, const uint32_t* recs, uint32_t n, uint32_t mh, uint32_t* fail_list, uint32_t* counters, uint32_t tasks_per_locus, uint32_t gt_l0, const uint8_t* gtables, int stats,
-        uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, const uint32_t* n_dev, hipStream_t s) {
-    return vtxk_launch_band_refine(recs, n, a.records, a.rec_locus, a.loci, a.read, mh, a.ref, a.alt, fail_list, counters, tasks_per_locus, gt_l0, gtables, stats, tight_list, tight_pack, stage, n_dev, s); }
-inline hipError_t launch_band_diag2(const TaskArrays& a, const uint32_t* tasks, uint32_t n, uint32_t mh, uint32_t tasks_per_locus, uint32_t gt_l0, const uint8_t* gtables, uint32_t* sweep_list, uint32_t* tight_list, uint32_t* tight_pack,
-        uint32_t* counters, uint32_t* stream_list, uint32_t* stream_diag, uint32_t* stream_cnt, uint8_t* stage, hipStream_t s) {
-    return vtxk_launch_band_diag2(tasks, n, a.records, a.rec_locus, a.loci, a.read, mh, a.ref, a.alt, tasks_per_locus, gt_l0, gtables, sweep_list, tight_list, tight_pack, counters, stream_list, stream_diag, stream_cnt, stage, s); }
-inline hipError_t launch_band_corridor(const TaskArrays& a, const uint32_t* recs, uint32_t n, uint32_t* counters, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, const uint32_t* n_dev, hipStream_t s) {
-    return vtxk_launch_band_corridor(recs, n, a.records, a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, counters, stats, tight_list, tight_pack, stage, n_dev, s); }
+// What the stages of one vtx_run share.  a: the batch's arrays, filled once per run from the context; stage: one byte per task saying which stage decided it (vtx_fetch_stage), or nullptr
+struct RunState { vtx_task_arrays a{}; uint8_t* stage = nullptr; uint32_t launches = 0, hard_total = 0; float band_run_ms = 0; };
 
 // ---- vtx_run: one pass of the banded stages ---------------------------------------------------------------------------------------
 // Tasks [t_begin, t_end) whose locus has its longer haplotype in (mh_min, mh] (the others are left alone); chunk_tables: the tables are built per chunk for the loci the chunk spans, whatever the
@@ -1769,13 +1715,17 @@ struct BandPass {
     const uint64_t t_begin, t_end;
     const bool chunk_tables;
     const BandKnobs& kn = band_knobs();
-    const TaskArrays& a = rs.a;
+    const vtx_task_arrays& a = rs.a;
     hipStream_t s = c->stream, s2 = nullptr;
     BandPlan bp;
     bool gt_chunked = false, sweep_path = false;
     uint32_t* d_cnt = nullptr;
     const int* shape = kShapes[0];              // the masked DP's (rows per lane, lanes per record) for the batch's longest read
     uint32_t *tight_list = nullptr, *tight_pack = nullptr, *dense_list = nullptr, *refine_list = nullptr, refine_cap = 0;   // band_diag_kernel's other outputs
+    // The launchers' bundles that hold for the whole pass, built once in run(): the pass's shape; the lists of band_diag_kernel and the kernels over its records; band_run_kernel's outputs
+    vtx_band_shape sh{};
+    vtx_diag_routes routes{};
+    vtx_band_out run_out{};
     // The general band kernel (tasks band_run_kernel could not hold) is a handful of serial lanes: ~4.5 ms of latency for 0.1 % of config 3.  It runs on a side
     // stream, with its own hard list; started once the overflow list is complete, finished (slabs grow until every task fits) after the main path's launches are queued.
     struct { uint32_t n_over = 0, cap2 = 0, todo = 0, off = 0, total = 0; const uint32_t* tasks = nullptr; bool active = false; uint32_t n_hard = 0, n_again = 0; } fb;
@@ -1789,9 +1739,9 @@ struct BandPass {
     bool sweep_tail_side = false;               // ... with band_tail_kernel on the side one
     uint32_t fork_nt = 0;
     // one chunk of tasks [base, base + nt): the loci whose tables are resident, and what band_diag_kernel left for band_run_kernel
-    struct Chunk { uint64_t base; uint32_t nt; bool last; uint32_t gt_l0 = 0, gt_n = 0; bool diag = false, swept = false; uint32_t n_fail = 0; const uint32_t* fail_list = nullptr;
-                   uint32_t tail_cap = 0; bool tail_side = false;       // band_tail_kernel's record buffer; whether diag_sweep_path launches that kernel on the side stream
-                   uint32_t recheck_cap = 0; };                         // the recheck's record buffer (0: no recheck for this chunk)
+    struct Chunk { uint64_t base; uint32_t nt; bool last; vtx_band_tables tb{}; bool diag = false, swept = false; uint32_t n_fail = 0; const uint32_t* fail_list = nullptr;
+                   vtx_rec_buf tail{}; bool tail_side = false;          // band_tail_kernel's record buffer; whether diag_sweep_path launches that kernel on the side stream
+                   vtx_rec_buf recheck{}; };                            // the recheck's record buffer (cap 0: no recheck for this chunk)
     BandPass(vtx_ctx* c_, RunState& rs_, uint32_t mh_, uint32_t mh_min_, uint64_t t_begin_, uint64_t t_end_, bool chunk_tables_) : c(c_), rs(rs_), mh(mh_), mh_min(mh_min_), t_begin(t_begin_), t_end(t_end_),
              chunk_tables(chunk_tables_) {}
     int run() {
@@ -1799,9 +1749,9 @@ struct BandPass {
         if (int rc = band_reserve(c, bp, false)) return rc;
         gt_chunked = bp.gt_bytes && (bp.gt_loci < c->n_loci || chunk_tables);
         d_cnt = c->d_cnt.as<uint32_t>();
-        int sh = 0;
-        while ((uint32_t)(kShapes[sh][0] * kShapes[sh][1]) < c->max_read_len) ++sh;
-        shape = kShapes[sh];
+        int k = 0;
+        while ((uint32_t)(kShapes[k][0] * kShapes[k][1]) < c->max_read_len) ++k;
+        shape = kShapes[k];
         if (!c->stream2) {
             HIP_TRY(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
             HIP_TRY(c, hipEventCreateWithFlags(&c->ev2, hipEventDisableTiming));
@@ -1816,12 +1766,15 @@ struct BandPass {
         dense_list = sweep_path ? c->d_dense.as<uint32_t>() : nullptr;
         refine_cap = std::min(band_refine_cap(bp.chunk), env_u32(VTX_DEV_ENV("VTX_DIAG_REFINE_CAP"), 10, 0xffffffffu));   // (test hook: a small record buffer, read per run)
         refine_list = kn.no_refine ? nullptr : c->d_refine.as<uint32_t>();
+        sh = vtx_band_shape{mh, mh_min, c->max_read_len, bp.tasks_per_locus};
+        routes = vtx_diag_routes{c->d_fail.as<uint32_t>(), refine_list, refine_cap, d_cnt, kn.diag_stats, tight_list, tight_pack, rs.stage, dense_list, kn.dense_mask};
+        run_out = vtx_band_out{c->d_poly.as<uint16_t>(), bp.poly_stride / 2, c->d_hard.as<uint32_t>(), c->d_over.as<uint32_t>(), d_cnt};
         HIP_TRY(c, hipMemsetAsync(d_cnt, 0, VTX_CNT_WORDS * sizeof(uint32_t), s));
         for (uint64_t base = t_begin; base < t_end; base += bp.chunk) {
             Chunk ch{base, (uint32_t)std::min<uint64_t>(bp.chunk, t_end - base), base + bp.chunk >= t_end};
             ch.fail_list = c->d_fail.as<uint32_t>();
             if (int rc = resident_tables(ch)) return rc;
-            if (ch.gt_n && !kn.no_diag) { if (int rc = diag_stage(ch)) return rc; }
+            if (ch.tb.n_loci && !kn.no_diag) { if (int rc = diag_stage(ch)) return rc; }
             if (int rc = run_stage(ch)) return rc;
             if (sweep_used && ch.last) { if (int rc = last_chunk()) return rc; }
         }
@@ -1832,8 +1785,8 @@ struct BandPass {
         if (rs.stage) HIP_TRY(c, vtxk_mark_stage(hard, n_hard, nullptr, code, rs.stage, st));
         for (uint32_t off = 0; off < n_hard; off += n_slots) {
             const uint32_t cnt_s = std::min(n_slots, n_hard - off);
-            HIP_TRY(c, launch_band_expand(a, hard + off, cnt_s, src ? src + (size_t)off * bp.poly_stride : band, src ? bp.poly_stride : 2 * bp.band_stride, band, bp.band_stride, st));
-            HIP_TRY(c, launch_sw_banded(a, shape, cnt_s, hard + off, band, bp.band_stride, mh, st));
+            HIP_TRY(c, vtxk_launch_band_expand(a, hard + off, cnt_s, src ? src + (size_t)off * bp.poly_stride : band, src ? bp.poly_stride : 2 * bp.band_stride, band, bp.band_stride, st));
+            HIP_TRY(c, vtxk_launch_sw_banded(a, shape[0], shape[1], cnt_s, hard + off, band, bp.band_stride, mh, st));
             rs.launches += 2;
         }
         return VTX_OK;
@@ -1852,10 +1805,12 @@ struct BandPass {
         const uint32_t tier_cap = tier == 0 ? 512u : (tier == 1 ? 1024u : 4096u);
         // (haplotypes up to 1000 bases: the kernel walks its Fenwick tree in ten unrolled steps, tn = n + 8 < 1024)
         const bool coop = tier >= 0 && !kn.no_coop && c->max_read_len <= 256 && mh <= 1000 && vtxk_band_coop_lds(mh, tier_cap) <= 64u * 1024;
+        // (its own band slots and hard list; the tasks that need a larger slab go to the other half of d_over2)
+        const vtx_band_out out{c->d_band2.as<uint16_t>(), bp.band_stride, c->d_hard2.as<uint32_t>(), fallback_other(), d_cnt + VTX_CNT_GENERAL_HARD};
         if (coop) {
             fb.cap2 = tier_cap;
             HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_GENERAL_AGAIN, 0, sizeof(uint32_t), s2));
-            HIP_TRY(c, launch_band_coop(a, tier, fb.tasks, fb.todo, mh, c->d_band2.as<uint16_t>(), bp.band_stride, c->d_hard2.as<uint32_t>(), fallback_other(), d_cnt + VTX_CNT_GENERAL_HARD, s2));
+            HIP_TRY(c, vtxk_launch_band_coop(a, tier, fb.tasks, fb.todo, sh, out, s2));
         } else {
             const bool in_lds = fb.cap2 < 512 && fb.todo <= kn.lds_tasks && !VTX_DEV_ENV("VTX_BAND_NO_LDS_FALLBACK") && vtxk_band_lds_stride(kLdsMatches, mh, c->max_read_len) <= 160 * 1024 - 512;
             fb.cap2 = in_lds ? kLdsMatches : (uint32_t)std::max<uint64_t>(std::min<uint64_t>((uint64_t)fb.cap2 * 16, worst), 512);
@@ -1865,8 +1820,7 @@ struct BandPass {
                 HIP_TRY(c, c->d_band_ws2.reserve(lanes < 64 ? (size_t)fb.todo * stride2 : ((size_t)fb.todo + 63) / 64 * 64 * stride2));   // (sparse lanes: a contiguous slab per task)
             }
             HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_GENERAL_AGAIN, 0, sizeof(uint32_t), s2));
-            HIP_TRY(c, launch_band(a, fb.tasks, fb.todo, c->d_band_ws2.as<uint8_t>(), stride2, fb.cap2, mh, c->d_band2.as<uint16_t>(), bp.band_stride, c->d_hard2.as<uint32_t>(), fallback_other(), d_cnt + VTX_CNT_GENERAL_HARD,
-                    in_lds ? 1 : 0, c->max_read_len, s2));
+            HIP_TRY(c, vtxk_launch_band(a, fb.tasks, fb.todo, 0, c->d_band_ws2.as<uint8_t>(), stride2, fb.cap2, sh, out, in_lds ? 1 : 0, s2));
         }
         HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_GENERAL_HARD, d_cnt + VTX_CNT_GENERAL_HARD, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s2));   // pinned: does not block
         ++rs.launches;
@@ -1908,27 +1862,28 @@ struct BandPass {
     int sweep_slices([[maybe_unused]] int tier, const uint32_t* list, uint32_t n, uint32_t* over_out, uint32_t* counters) {
         uint32_t* why = kn.sweep_stats ? d_cnt + VTX_CNT_SWEEP_WHY : nullptr;
         HIP_TRY(c, c->d_sweep_log.reserve(vtxk_band_sweep_log_bytes()));
+        const vtx_band_out out{c->d_band.as<uint16_t>(), bp.band_stride, c->d_hard.as<uint32_t>(), over_out, counters};
         for (uint32_t off = 0; off < n; off += bp.slots) {
             const uint32_t cnt_s = std::min(bp.slots, n - off);
             HIP_TRY(c, hipMemsetAsync(counters, 0, sizeof(uint32_t), s));
 #ifdef VTX_DEVTOOLS
-            if (kn.sweep_v1) HIP_TRY(c, launch_band_sweep_v1(a, tier, list + off, cnt_s, c->d_band.as<uint16_t>(), bp.band_stride, c->d_hard.as<uint32_t>(), over_out, counters, why, rs.stage, s));
+            if (kn.sweep_v1) HIP_TRY(c, vtxk_launch_band_sweep_v1(a, tier, list + off, cnt_s, nullptr, out, why, rs.stage, nullptr, s));
             else
 #endif
-            HIP_TRY(c, launch_band_sweep(a, list + off, cnt_s, c->d_band.as<uint16_t>(), bp.band_stride, c->d_hard.as<uint32_t>(), over_out, counters, why, rs.stage, c->d_sweep_log.as<uint32_t>(), s));
-            HIP_TRY(c, launch_sw_banded_dev(a, shape, cnt_s, c->d_hard.as<uint32_t>(), counters, c->d_band.as<uint16_t>(), bp.band_stride, mh, s));
+            HIP_TRY(c, vtxk_launch_band_sweep(a, list + off, cnt_s, nullptr, out, why, rs.stage, nullptr, c->d_sweep_log.as<uint32_t>(), s));
+            HIP_TRY(c, vtxk_launch_sw_banded_dev(a, shape[0], shape[1], cnt_s, out.hard_list, counters, out.band, out.band_stride, mh, s));
             rs.launches += 2;
         }
         return VTX_OK;
     }
     // Second stage (round 5; DESIGN.md 4.3.3b, where its threshold of 700 k tasks is measured): band_diag2_kernel, band_stream_kernel for what exceeds its list, the full-matrix check + masked DP
-    // over the one-diagonal bands they prove; what they leave — out[0, *n_out) — takes the sweep.  One host round trip for the counts. The tables of the tasks' loci have to be resident (gt_l0:
-    // first locus of the table buffer).
+    // over the one-diagonal bands they prove; what they leave — out[0, *n_out) — takes the sweep.  One host round trip for the counts. The tables of the tasks' loci have to be resident (tb:
+    // the table buffer as the stage that built them was handed it).
     bool second_stage_on(uint32_t n) const { return !kn.no_diag2 && n >= kn.diag2_min && mh <= 255; }
-    int second_stage(const uint32_t* list, uint32_t n, uint32_t gt_l0, uint32_t* out, uint32_t* n_out) {
+    int second_stage(const uint32_t* list, uint32_t n, const vtx_band_tables& tb, uint32_t* out, uint32_t* n_out) {
         HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_DIAG2_LEFT, 0, 2 * sizeof(uint32_t), s));
         HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_STREAMED, 0, sizeof(uint32_t), s));
-        HIP_TRY(c, launch_band_diag2(a, list, n, mh, bp.tasks_per_locus, gt_l0, c->d_gtables.as<uint8_t>(), out, c->d_tight2.as<uint32_t>(), c->d_tight2_pack.as<uint32_t>(), d_cnt + VTX_CNT_DIAG2_LEFT,
+        HIP_TRY(c, vtxk_launch_band_diag2(a, list, n, sh, tb, out, c->d_tight2.as<uint32_t>(), c->d_tight2_pack.as<uint32_t>(), d_cnt + VTX_CNT_DIAG2_LEFT,
                 kn.no_stream ? nullptr : c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), d_cnt + VTX_CNT_STREAMED, rs.stage, s));
         HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_DIAG2_LEFT, d_cnt + VTX_CNT_DIAG2_LEFT, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_STREAMED, d_cnt + VTX_CNT_STREAMED, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -1941,8 +1896,9 @@ struct BandPass {
         if (n_tight2) {
             // certificate == full-matrix score decides practically all of them (cert <= banded <= full); the masked DP for the rest (count on the device)
             HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_CHECK2, 0, sizeof(uint32_t), s));
-            HIP_TRY(c, launch_sw_check(a, shape, n_tight2, c->d_tight2.as<uint32_t>(), c->d_tight2_pack.as<uint32_t>(), nullptr, mh, c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), d_cnt + VTX_CNT_CHECK2, rs.stage, s));
-            HIP_TRY(c, launch_sw_diag_band(a, shape, n_tight2, c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), d_cnt + VTX_CNT_CHECK2, mh, rs.stage, s));
+            HIP_TRY(c, vtxk_launch_sw_check(a, shape[0], shape[1], n_tight2, c->d_tight2.as<uint32_t>(), c->d_tight2_pack.as<uint32_t>(), nullptr, mh, c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(),
+                                            d_cnt + VTX_CNT_CHECK2, rs.stage, s));
+            HIP_TRY(c, vtxk_launch_sw_diag_band(a, shape[0], shape[1], n_tight2, c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), d_cnt + VTX_CNT_CHECK2, mh, rs.stage, s));
             // (its grid is sized for n_tight2 although a few hundred tasks remain: the workgroups past the device count leave at once)
             rs.launches += 2;
             tight2_total += n_tight2;
@@ -1981,16 +1937,17 @@ struct BandPass {
         HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_HARD, 0, sizeof(uint32_t), s));
         HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_PENDING, 0, sizeof(uint32_t), s));
         HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_BLOCK, 0, 8 * sizeof(uint32_t), s));
-        ch.gt_l0 = 0; ch.gt_n = bp.gt_bytes ? c->n_loci : 0;
+        uint32_t gt_l0 = 0, gt_n = bp.gt_bytes ? c->n_loci : 0;
         if (gt_chunked) {
             uint32_t ends[2];
             HIP_TRY(c, hipMemcpyAsync(&ends[0], a.rec_locus + ch.base / 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             HIP_TRY(c, hipMemcpyAsync(&ends[1], a.rec_locus + (ch.base + ch.nt - 1) / 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             HIP_TRY(c, hipStreamSynchronize(s));
-            ch.gt_l0 = ends[0]; ch.gt_n = ends[1] - ends[0] + 1;
-            if (ch.gt_n > bp.gt_loci) ch.gt_n = 0;              // does not fit after all: tables in LDS for this chunk
+            gt_l0 = ends[0]; gt_n = ends[1] - ends[0] + 1;
+            if (gt_n > bp.gt_loci) gt_n = 0;                    // does not fit after all: tables in LDS for this chunk
         }
-        c->gt_used = (ch.gt_n && bp.gt_loci) ? (uint64_t)ch.gt_n * (bp.gt_bytes / bp.gt_loci) : 0;     // (gt_bytes = gt_loci x bytes per locus)
+        ch.tb = vtx_band_tables{gt_n ? c->d_gtables.as<uint8_t>() : nullptr, bp.gt_bytes, gt_l0, gt_n};      // (no table buffer for band_run_kernel: it builds them in LDS)
+        c->gt_used = (gt_n && bp.gt_loci) ? (uint64_t)gt_n * (bp.gt_bytes / bp.gt_loci) : 0;     // (gt_bytes = gt_loci x bytes per locus)
         HIP_TRY(c, hipEventRecord(c->ev[EV_CHUNK_START], s));
         return VTX_OK;
     }
@@ -2000,18 +1957,16 @@ struct BandPass {
         HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_RUN_LEFT, 0, 4 * sizeof(uint32_t), s));   // RUN_LEFT, DENSE, REFINE, TIGHT
         const uint32_t tail_cap = (uint32_t)std::min<size_t>(band_tail_cap(bp.chunk), c->d_tail.cap / (vtxk_band_tail_words() * sizeof(uint32_t)));
         const uint32_t tail_cap_hook = VTX_DEV_ENV("VTX_DIAG_TAIL_CAP") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_TAIL_CAP")) : 0xffffffffu;   // test hook: a small buffer (read per run)
-        ch.tail_cap = std::min(tail_cap, tail_cap_hook);
+        ch.tail = vtx_rec_buf{c->d_tail.as<uint32_t>(), std::min(tail_cap, tail_cap_hook)};
         // The sweep path with its two branches: band_tail_kernel goes to the side one (diag_sweep_path).  Every other path keeps it behind band_diag_kernel on this stream.
-        ch.tail_side = sweep_path && fork_on() && !kn.tail_inline && vtxk_band_tail_on(c->d_tail.as<uint32_t>(), ch.tail_cap);
+        ch.tail_side = sweep_path && fork_on() && !kn.tail_inline && vtxk_band_tail_on(ch.tail);
         // The recheck of the tasks that fail band_diag_kernel's harmless test (diag_sweep_path launches it): on the path with the two branches only, where a task it clears has a tight
         // list to go to and band_corridor_kernel behind it.  Every other path (no fork, no tight list, round 3's, four-byte entries: vtxk_band_recheck_on) hands the kernel no buffer.
         const uint32_t recheck_cap = (uint32_t)std::min<size_t>(band_recheck_cap(bp.chunk), c->d_recheck.cap / (vtxk_band_tail_words() * sizeof(uint32_t)));
         const uint32_t recheck_cap_hook = VTX_DEV_ENV("VTX_DIAG_RECHECK_CAP") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_RECHECK_CAP")) : 0xffffffffu;   // test hook: a small buffer (read per run)
-        ch.recheck_cap = std::min(recheck_cap, recheck_cap_hook);
-        if (!(sweep_path && fork_on() && refine_list && !kn.no_corridor && vtxk_band_recheck_on(c->d_recheck.as<uint32_t>(), ch.recheck_cap, mh))) ch.recheck_cap = 0;
-        const hipError_t e = launch_band_diag(a, ch.nt, (uint32_t)ch.base, mh, mh_min, c->d_fail.as<uint32_t>(), refine_list, refine_cap, d_cnt, bp.tasks_per_locus, ch.gt_l0, ch.gt_n, c->d_gtables.as<uint8_t>(), bp.gt_bytes,
-                                              kn.diag_stats, tight_list, tight_pack, rs.stage, dense_list, kn.dense_mask, c->max_read_len, c->d_tail.as<uint32_t>(), ch.tail_cap, !ch.tail_side,
-                                              ch.recheck_cap ? c->d_recheck.as<uint32_t>() : nullptr, ch.recheck_cap, s);
+        ch.recheck = vtx_rec_buf{c->d_recheck.as<uint32_t>(), std::min(recheck_cap, recheck_cap_hook)};
+        if (!(sweep_path && fork_on() && refine_list && !kn.no_corridor && vtxk_band_recheck_on(ch.recheck, mh))) ch.recheck = vtx_rec_buf{nullptr, 0};
+        const hipError_t e = vtxk_launch_band_diag(a, ch.nt, (uint32_t)ch.base, sh, ch.tb, routes, ch.tail, !ch.tail_side, ch.recheck, s);
         if (e != hipSuccess) {
             // (the tables do not fit the buffer for this chunk: band_run_kernel alone, tables in LDS)
             if (getenv("VTX_DEBUG")) fprintf(stderr, "[vtx] band_diag_kernel not launched for tasks [%llu, +%u): %s\n", (unsigned long long)ch.base, ch.nt, hipGetErrorString(e));
@@ -2022,8 +1977,8 @@ struct BandPass {
     // the records band_diag_kernel left: with a tight list (round 6) every task that holds a certificate and a one-diagonal
     // band, for band_corridor_kernel; else (VTX_BAND_NO_TIGHT, libvtx_dev.so's VTX_BAND_NO_CORRIDOR) round 3's, for band_refine_kernel
     hipError_t second_look(const Chunk& ch, uint32_t n_rec, hipStream_t st) {
-        if (tight_list && !kn.no_corridor) return launch_band_corridor(a, refine_list, n_rec, d_cnt, kn.diag_stats, tight_list, tight_pack, rs.stage, d_cnt + VTX_CNT_REFINE, st);
-        return launch_band_refine(a, refine_list, n_rec, mh, c->d_fail.as<uint32_t>(), d_cnt, bp.tasks_per_locus, ch.gt_l0, c->d_gtables.as<uint8_t>(), kn.diag_stats, tight_list, tight_pack, rs.stage, d_cnt + VTX_CNT_REFINE, st);
+        if (tight_list && !kn.no_corridor) return vtxk_launch_band_corridor(a, refine_list, n_rec, routes, d_cnt + VTX_CNT_REFINE, st);
+        return vtxk_launch_band_refine(a, refine_list, n_rec, sh, ch.tb, routes, d_cnt + VTX_CNT_REFINE, st);
     }
     // What the stage left, in two branches over disjoint tasks: side stream — band_tail_kernel (tail_on_side), band_refine_kernel / band_corridor_kernel over its records, then the masked DP over the
     // one-diagonal bands; this stream — band_sweep_kernel + masked DP over the repeats and the short fail list.  One host round trip, right after band_diag_kernel.  (VTX_BAND_NO_TIGHT: the
@@ -2039,8 +1994,9 @@ struct BandPass {
     int tail_on_side(const Chunk& ch) {
         HIP_TRY(c, hipStreamWaitEvent(s2, c->ev[EV_DIAG_END], 0));
         HIP_TRY(c, hipEventRecord(c->ev[EV_BRANCH_START], s2));
-        HIP_TRY(c, vtxk_launch_band_tail(mh, c->max_read_len, a.ref, a.alt, nullptr, refine_list, refine_cap, d_cnt, bp.tasks_per_locus, kn.diag_stats, tight_list, tight_pack, rs.stage, nullptr,
-                                         kn.dense_mask, c->d_tail.as<uint32_t>(), ch.tail_cap, 1, s2));
+        vtx_diag_routes side = routes;
+        side.fail_list = nullptr; side.dense_list = nullptr;
+        HIP_TRY(c, vtxk_launch_band_tail(a, sh, side, ch.tail, 1, s2));
         return VTX_OK;
     }
     int diag_sweep_path(Chunk& ch) {
@@ -2053,9 +2009,8 @@ struct BandPass {
         // The recheck, on THIS stream, in front of the counter copy: it appends to the fail (or dense) list what it does not clear and to the refine / tight lists what it does — beside
         // band_tail_kernel on the side stream, through the same atomics — so the four counts below include everything it listed: RUN_LEFT and DENSE are final, REFINE and TIGHT are
         // the bounds they were.  Its grid comes from the buffer's capacity and it reads its record count on the device: no round trip of its own.
-        if (ch.recheck_cap) {
-            HIP_TRY(c, vtxk_launch_band_recheck(mh, c->max_read_len, a.ref, a.alt, c->d_fail.as<uint32_t>(), refine_list, refine_cap, d_cnt, bp.tasks_per_locus, kn.diag_stats, tight_list, tight_pack, rs.stage,
-                                                dense_list, kn.dense_mask, c->d_recheck.as<uint32_t>(), ch.recheck_cap, s));
+        if (ch.recheck.cap) {
+            HIP_TRY(c, vtxk_launch_band_recheck(a, sh, routes, ch.recheck, s));
             ++rs.launches;
         }
         HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_RUN_LEFT, d_cnt + VTX_CNT_RUN_LEFT, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // RUN_LEFT, DENSE, REFINE, TIGHT
@@ -2063,7 +2018,7 @@ struct BandPass {
         HIP_TRY(c, hipStreamSynchronize(s));
         // band_tail_kernel on the side stream: REFINE and TIGHT are what that kernel had appended when the copy ran, and every one of its n_tail records may still become a record for the
         // second look or, that buffer full, a tight entry.  These two are BOUNDS for the grids; the kernels read the final counts on the device, the figures of vtx_timing arrive with the events.
-        const uint32_t n_tail = ch.tail_side ? std::min(c->h_pin[PIN_TAIL], ch.tail_cap) : 0u;
+        const uint32_t n_tail = ch.tail_side ? std::min(c->h_pin[PIN_TAIL], ch.tail.cap) : 0u;
         const uint32_t n_refine = (uint32_t)std::min<uint64_t>((uint64_t)c->h_pin[PIN_REFINE] + n_tail, refine_cap);
         // (forked: the tight list still grows by what the refinement leaves — at most its records)
         const uint32_t n_tight = (uint32_t)std::min<uint64_t>((uint64_t)c->h_pin[PIN_TIGHT] + (fork && refine_list ? n_refine : 0u) + n_tail, ch.nt);
@@ -2098,11 +2053,11 @@ struct BandPass {
             HIP_TRY(c, c->d_dband.reserve((size_t)bp.chunk * sizeof(uint32_t)));
             HIP_TRY(c, c->d_dband_pack.reserve((size_t)bp.chunk * sizeof(uint32_t)));
             HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_CHECK, 0, sizeof(uint32_t), sb));
-            HIP_TRY(c, launch_sw_check(a, shape, n_tight, tight_list, tight_pack, dp_cnt, mh, c->d_dband.as<uint32_t>(), c->d_dband_pack.as<uint32_t>(), d_cnt + VTX_CNT_CHECK, rs.stage, sb));
+            HIP_TRY(c, vtxk_launch_sw_check(a, shape[0], shape[1], n_tight, tight_list, tight_pack, dp_cnt, mh, c->d_dband.as<uint32_t>(), c->d_dband_pack.as<uint32_t>(), d_cnt + VTX_CNT_CHECK, rs.stage, sb));
             dp_list = c->d_dband.as<uint32_t>(); dp_pack = c->d_dband_pack.as<uint32_t>(); dp_cnt = d_cnt + VTX_CNT_CHECK;
             ++rs.launches;
         }
-        HIP_TRY(c, launch_sw_diag_band(a, shape, n_tight, dp_list, dp_pack, dp_cnt, mh, rs.stage, sb));
+        HIP_TRY(c, vtxk_launch_sw_diag_band(a, shape[0], shape[1], n_tight, dp_list, dp_pack, dp_cnt, mh, rs.stage, sb));
         ++rs.launches;
         return VTX_OK;
     }
@@ -2122,7 +2077,7 @@ struct BandPass {
         uint32_t n_sweep = n_dense;
         if (second_stage_on(n_dense)) {
             uint32_t* sweep2 = (dl == dense_list) ? dense_list + ch.nt : dense_list;          // (the half of d_dense the list is not in)
-            if (int rc = second_stage(dl, n_dense, ch.gt_l0, sweep2, &n_sweep)) return rc;
+            if (int rc = second_stage(dl, n_dense, ch.tb, sweep2, &n_sweep)) return rc;
             sl = sweep2;
         }
         if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, c->d_over.as<uint32_t>() + 2 * bp.n_tasks, d_cnt + VTX_CNT_SWEEP_HARD)) return rc; }
@@ -2139,7 +2094,7 @@ struct BandPass {
         ch.n_fail = c->h_pin[PIN_RUN_LEFT];
         const uint32_t n_refine = std::min(c->h_pin[PIN_R3_REFINE], refine_cap);
         if (n_refine) {
-            HIP_TRY(c, launch_band_refine(a, refine_list, n_refine, mh, c->d_fail.as<uint32_t>(), d_cnt, bp.tasks_per_locus, ch.gt_l0, c->d_gtables.as<uint8_t>(), kn.diag_stats, nullptr, nullptr, rs.stage, nullptr, s));
+            HIP_TRY(c, vtxk_launch_band_refine(a, refine_list, n_refine, sh, ch.tb, routes, nullptr, s));          // (this path has no tight list: routes.tight_list == nullptr)
             HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_RUN_LEFT, d_cnt + VTX_CNT_RUN_LEFT, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             HIP_TRY(c, hipStreamSynchronize(s));
             ch.n_fail = c->h_pin[PIN_RUN_LEFT];
@@ -2154,9 +2109,8 @@ struct BandPass {
     // the masked DP over its hard list; after the last chunk of a pass without a sweep, the general kernel's start
     int run_stage(Chunk& ch) {
         HIP_TRY(c, hipEventRecord(c->ev[EV_BAND_RUN_START], s));
-        if (!ch.diag || ch.n_fail) HIP_TRY(c, launch_band_run(a, ch.diag ? ch.n_fail : ch.nt, ch.diag ? 0u : (uint32_t)ch.base, mh, mh_min, c->d_band_ws.as<uint32_t>(), c->d_poly.as<uint16_t>(), bp.poly_stride / 2,
-            c->d_hard.as<uint32_t>(), c->d_over.as<uint32_t>(), c->d_pend.as<uint32_t>(), c->d_pend_buf.as<uint32_t>(), bp.hard_cap, bp.pend_cap, d_cnt, bp.tasks_per_locus, ch.gt_l0, ch.gt_n,
-            ch.gt_n ? c->d_gtables.as<uint8_t>() : nullptr, bp.gt_bytes, ch.diag ? ch.fail_list : nullptr, c->band_long_lists ? 1 : 0, s));
+        if (!ch.diag || ch.n_fail) HIP_TRY(c, vtxk_launch_band_run(a, ch.diag ? ch.n_fail : ch.nt, ch.diag ? 0u : (uint32_t)ch.base, sh, ch.tb, run_out, c->d_band_ws.as<uint32_t>(), c->d_pend.as<uint32_t>(),
+            c->d_pend_buf.as<uint32_t>(), bp.hard_cap, bp.pend_cap, ch.diag ? ch.fail_list : nullptr, c->band_long_lists ? 1 : 0, s));
         HIP_TRY(c, hipEventRecord(c->ev[EV_BAND_RUN_END], s));                  // (complete once the read-back below is: no synchronisation of its own)
         const bool run_skipped = ch.swept && ch.n_fail == 0;             // nothing went to band_run_kernel: its counters are what they were
         if (run_skipped) {
@@ -2183,7 +2137,7 @@ struct BandPass {
         cnt[VTX_CNT_PENDING] = std::min(cnt[VTX_CNT_PENDING], bp.pend_cap);
         if (cnt[VTX_CNT_PENDING]) {
             // tasks whose piece list overflowed its LDS slots: the same certificate, from their pending records
-            HIP_TRY(c, vtxk_launch_band_pending(c->d_pend.as<uint32_t>(), cnt[VTX_CNT_PENDING], c->d_pend_buf.as<uint32_t>(), a.ref, a.alt, c->d_poly.as<uint16_t>(), bp.poly_stride / 2, c->d_hard.as<uint32_t>(), d_cnt, s));
+            HIP_TRY(c, vtxk_launch_band_pending(a, c->d_pend.as<uint32_t>(), cnt[VTX_CNT_PENDING], c->d_pend_buf.as<uint32_t>(), run_out, s));
             HIP_TRY(c, hipMemcpyAsync(cnt + VTX_CNT_HARD, d_cnt + VTX_CNT_HARD, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             HIP_TRY(c, hipStreamSynchronize(s));
             pending_total += cnt[VTX_CNT_PENDING];
@@ -2197,7 +2151,7 @@ struct BandPass {
     // The six-wavefront variant of band_run_kernel keeps 12-entry lists: the tasks that overflowed them ([a0, a1) of the overflow list) get a second chance in the 15-entry variant before the
     // general kernel — what overflows again is appended behind a1 and then moved down to a0. (task-list mode runs the 15-entry variant: nothing to give a second chance to)
     int second_chance(const Chunk& ch) {
-        const bool short_lists = !ch.diag && ch.gt_n && vtxk_band_second_chance(bp.tasks_per_locus, c->band_long_lists ? 1 : 0);
+        const bool short_lists = !ch.diag && ch.tb.n_loci && vtxk_band_second_chance(bp.tasks_per_locus, c->band_long_lists ? 1 : 0);
         if (short_lists && ch.nt >= (1u << 20)) {
             // feedback for the next run of this context: many overflows of the 12-entry lists (noisy reads: 3.3 % of the
             // tasks at 3 % substitution errors, 0.2 % at 0.5 %) make the 15-entry variant the better first pass
@@ -2207,8 +2161,7 @@ struct BandPass {
         const uint32_t a0 = over_before, a1 = cnt[VTX_CNT_OVERFLOW];
         uint32_t* over = c->d_over.as<uint32_t>();
         HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_BLOCK, 0, 8 * sizeof(uint32_t), s));
-        HIP_TRY(c, launch_band_run(a, a1 - a0, 0, mh, mh_min, c->d_band_ws.as<uint32_t>(), c->d_poly.as<uint16_t>(), bp.poly_stride / 2, c->d_hard.as<uint32_t>(), over, c->d_pend.as<uint32_t>(), c->d_pend_buf.as<uint32_t>(),
-                bp.hard_cap, bp.pend_cap, d_cnt, bp.tasks_per_locus, ch.gt_l0, ch.gt_n, c->d_gtables.as<uint8_t>(), bp.gt_bytes, over + a0, 0, s));
+        HIP_TRY(c, vtxk_launch_band_run(a, a1 - a0, 0, sh, ch.tb, run_out, c->d_band_ws.as<uint32_t>(), c->d_pend.as<uint32_t>(), c->d_pend_buf.as<uint32_t>(), bp.hard_cap, bp.pend_cap, over + a0, 0, s));
         HIP_TRY(c, hipEventRecord(c->ev[EV_BAND_RUN_END], s));
         HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
@@ -2231,7 +2184,8 @@ struct BandPass {
             const uint32_t* sl = over;
             uint32_t n_sweep = nA;
             if (second_stage_on(nA) && bp.gt_bytes && !gt_chunked && nA <= bp.chunk && c->d_dense.cap >= (size_t)nA * sizeof(uint32_t)) {
-                if (int rc = second_stage(over, nA, 0, c->d_dense.as<uint32_t>(), &n_sweep)) return rc;
+                const vtx_band_tables every_locus{c->d_gtables.as<uint8_t>(), bp.gt_bytes, 0, c->n_loci};
+                if (int rc = second_stage(over, nA, every_locus, c->d_dense.as<uint32_t>(), &n_sweep)) return rc;
                 sl = c->d_dense.as<uint32_t>();
             }
             if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, declined, d_cnt + VTX_CNT_SWEEP_HARD)) return rc; }
@@ -2305,7 +2259,7 @@ int run_prologue(vtx_ctx* c, RunState& rs) {
     c->timing.diag_ms = c->timing.check_ms = c->timing.sweep_ms = 0;
     c->timing.diag_left = c->timing.checked_tasks = c->timing.swept_tasks = c->timing.resweep_tasks = 0;
     c->timing.diag2_tasks = c->timing.diag2_scored = c->timing.diag2_streamed = 0;
-    rs.a = TaskArrays{c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>()};
+    rs.a = vtx_task_arrays{c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>()};
     if (c->stage_trace && nr) {
         HIP_TRY(c, c->d_stage.reserve(2 * (size_t)nr));
         rs.stage = c->d_stage.as<uint8_t>();
@@ -2323,7 +2277,7 @@ int run_prologue(vtx_ctx* c, RunState& rs) {
 int run_full_dp(vtx_ctx* c, RunState& rs) {
     hipStream_t s = c->stream;
     const BandKnobs& kn = band_knobs();
-    const TaskArrays& a = rs.a;
+    const vtx_task_arrays& a = rs.a;
     const uint32_t mh = c->max_hap_len;
     uint32_t *work = c->d_work.as<uint32_t>(), *d_redo = c->d_redo.as<uint32_t>();
     bool any_lut = false; const bool full_dp = c->cfg.aligner != VTX_ALIGNER_BANDED;
@@ -2334,9 +2288,9 @@ int run_full_dp(vtx_ctx* c, RunState& rs) {
         const Bucket& bk = c->buckets[b];
         const bool use_pair = bk.pair && !kn.no_pair;
         uint32_t* redo_cnt = c->d_redo_cnt.as<uint32_t>() + b;
-        if (bk.duo && !kn.no_duo) HIP_TRY(c, launch_sw_full_duo(a, bk.R, bk.count, work + bk.offset, mh, use_pair ? kPairLociCap : duo_loci_cap(mh), d_redo + bk.offset, redo_cnt, use_pair ? duo_pair_cols(mh) : 0u, s));
-        else if (bk.lut) HIP_TRY(c, launch_sw_full_lut(a, bk.R, bk.count, work + bk.offset, mh, kLutLociCap, d_redo + bk.offset, redo_cnt, s));
-        else HIP_TRY(c, launch_sw_full(a, bk.R, bk.GL, bk.count, work + bk.offset, mh, s));
+        if (bk.duo && !kn.no_duo) HIP_TRY(c, vtxk_launch_sw_full_duo(a, bk.R, bk.count, work + bk.offset, mh, use_pair ? kPairLociCap : duo_loci_cap(mh), d_redo + bk.offset, redo_cnt, use_pair ? duo_pair_cols(mh) : 0u, s));
+        else if (bk.lut) HIP_TRY(c, vtxk_launch_sw_full_lut(a, bk.R, bk.count, work + bk.offset, mh, kLutLociCap, d_redo + bk.offset, redo_cnt, s));
+        else HIP_TRY(c, vtxk_launch_sw_full(a, bk.R, bk.GL, bk.count, work + bk.offset, mh, s));
         ++rs.launches;
     }
     if (any_lut) {
@@ -2346,7 +2300,7 @@ int run_full_dp(vtx_ctx* c, RunState& rs) {
         for (size_t b = 0; b < c->buckets.size(); ++b) {
             const Bucket& bk = c->buckets[b];
             if (!(bk.lut || bk.duo) || !redo[b]) continue;
-            HIP_TRY(c, launch_sw_full(a, bk.R, bk.GL, redo[b], d_redo + bk.offset, mh, s));
+            HIP_TRY(c, vtxk_launch_sw_full(a, bk.R, bk.GL, redo[b], d_redo + bk.offset, mh, s));
             ++rs.launches;
         }
     }
@@ -2385,7 +2339,7 @@ int run_slow(vtx_ctx* c, RunState& rs) {
         HIP_TRY(c, c->d_slow_ws.reserve((size_t)todo * stride));
         HIP_TRY(c, hipMemsetAsync(d_scnt, 0, sizeof(uint32_t), s));
         uint32_t* retry = c->d_slow_retry.as<uint32_t>() + ((tasks == c->d_slow_retry.as<uint32_t>()) ? n_slow : 0);
-        HIP_TRY(c, launch_slow_align(rs.a, c->d_work.as<uint32_t>() + c->slow_off, tasks, todo, banded, c->d_slow_ws.as<uint8_t>(), stride, cap, mh, c->max_read_all, retry, d_scnt, s));
+        HIP_TRY(c, vtxk_launch_slow_align(rs.a, c->d_work.as<uint32_t>() + c->slow_off, tasks, todo, banded, c->d_slow_ws.as<uint8_t>(), stride, cap, mh, c->max_read_all, retry, d_scnt, s));
         uint32_t left = 0;
         HIP_TRY(c, hipMemcpyAsync(&left, d_scnt, sizeof left, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
@@ -2553,17 +2507,16 @@ int vtx_debug_bands(vtx_ctx* c, const uint32_t* tasks, uint32_t n_tasks, uint32_
     DBG_TRY(hipMemcpyAsync(d_t.p, tasks, (size_t)n_tasks * 4, hipMemcpyHostToDevice, s));
     DBG_TRY(hipMemsetAsync(d_c.p, 0, VTX_CNT_WORDS * 4, s));
     DBG_TRY(c->d_sweep_log.reserve(vtxk_band_sweep_log_bytes()));
-    const TaskArrays a{c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), nullptr, nullptr};
+    const vtx_task_arrays a{c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), nullptr, nullptr};
+    const vtx_band_out out{d_b.as<uint16_t>(), bs, d_h.as<uint32_t>(), d_o.as<uint32_t>(), d_c.as<uint32_t>()};
     uint32_t* dbg = dbg_on ? d_d.as<uint32_t>() : nullptr;
 #ifdef VTX_DEVTOOLS
     // (libvtx_dev.so: VTX_SWEEP_V1=1 asks round 4's kernel instead; VTX_SWEEP_TIER=1 its 1024-section variant)
     if (VTX_DEV_ENV("VTX_SWEEP_V1"))
-        DBG_TRY(vtxk_launch_band_sweep_v1(VTX_DEV_ENV("VTX_SWEEP_TIER") ? atoi(VTX_DEV_ENV("VTX_SWEEP_TIER")) : 0, d_t.as<uint32_t>(), n_tasks, nullptr, a.records, a.rec_locus, a.loci, a.read, a.hap,
-                                          d_b.as<uint16_t>(), bs, d_h.as<uint32_t>(), d_o.as<uint32_t>(), d_c.as<uint32_t>(), nullptr, nullptr, dbg, s));
+        DBG_TRY(vtxk_launch_band_sweep_v1(a, VTX_DEV_ENV("VTX_SWEEP_TIER") ? atoi(VTX_DEV_ENV("VTX_SWEEP_TIER")) : 0, d_t.as<uint32_t>(), n_tasks, nullptr, out, nullptr, nullptr, dbg, s));
     else
 #endif
-    DBG_TRY(vtxk_launch_band_sweep(d_t.as<uint32_t>(), n_tasks, nullptr, a.records, a.rec_locus, a.loci, a.read, a.hap, d_b.as<uint16_t>(), bs, d_h.as<uint32_t>(), d_o.as<uint32_t>(), d_c.as<uint32_t>(),
-                                   nullptr, nullptr, dbg, c->d_sweep_log.as<uint32_t>(), s));
+    DBG_TRY(vtxk_launch_band_sweep(a, d_t.as<uint32_t>(), n_tasks, nullptr, out, nullptr, nullptr, dbg, c->d_sweep_log.as<uint32_t>(), s));
     struct { uint32_t hard = 0, declined = 0; } swept;   // band_sweep_kernel's two counters
     DBG_TRY(hipMemcpyAsync(&swept, d_c.p, sizeof swept, hipMemcpyDeviceToHost, s));
     DBG_TRY(hipStreamSynchronize(s));

@@ -684,15 +684,12 @@ __global__ __launch_bounds__(64) void band_coop_kernel(
 // per wavefront in lockstep, the template's G) were SLOWER, 171 and 258 ms — the same number of tasks in flight, longer rows;
 // START and END of neighbouring rows in one instruction stream plus the 512-match tier: 90 + 11 ms (the step: 257 ms with the
 // serial kernel alone, 234 ms with the first version, 200 ms now; full size 800 -> 590 ms).
-extern "C" hipError_t vtxk_launch_band_coop(int tier, const uint32_t* tasks, uint32_t n_tasks, const vtx_record* records,
-                                            const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                            const uint8_t* hap_arena, uint32_t max_hap, int32_t* ref_score, int32_t* alt_score,
-                                            uint16_t* band, uint32_t band_stride, uint32_t* hard_list, uint32_t* overflow_list,
-                                            uint32_t* counters, hipStream_t s) {
+extern "C" hipError_t vtxk_launch_band_coop(const vtx_task_arrays& a, int tier, const uint32_t* tasks, uint32_t n_tasks, const vtx_band_shape& sh,
+                                            const vtx_band_out& out, hipStream_t s) {
     if (!n_tasks) return hipSuccess;
     const uint32_t mc = tier == 0 ? 512u : (tier == 1 ? 1024u : 4096u), tpw = 1u;
     static const uint32_t ablate = VTX_DEV_ENV("VTX_COOP_ABLATE") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_COOP_ABLATE")) : 0u;     // profiling aid
-    const size_t task_bytes = vtxk_band_coop_lds(max_hap, mc), shmem = task_bytes * tpw;
+    const size_t task_bytes = vtxk_band_coop_lds(sh.max_hap, mc), shmem = task_bytes * tpw;
     if (shmem > 64 * 1024) return hipErrorInvalidValue;
 #define LAUNCH_COOP(G, MC)                                                                                               \
     {                                                                                                                    \
@@ -700,9 +697,9 @@ extern "C" hipError_t vtxk_launch_band_coop(int tier, const uint32_t* tasks, uin
             hipError_t e = hipFuncSetAttribute((const void*)band_coop_kernel<G, MC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
             if (e != hipSuccess) return e;                                                                               \
         }                                                                                                                \
-        hipLaunchKernelGGL((band_coop_kernel<G, MC>), dim3((n_tasks + tpw - 1) / tpw), dim3(64), shmem, s, tasks, n_tasks, records, rec_locus, \
-                           loci, read_arena, hap_arena, max_hap, (uint32_t)task_bytes, ref_score, alt_score, band, band_stride,   \
-                           hard_list, overflow_list, counters, ablate);                                                  \
+        hipLaunchKernelGGL((band_coop_kernel<G, MC>), dim3((n_tasks + tpw - 1) / tpw), dim3(64), shmem, s, tasks, n_tasks, a.records, a.rec_locus, \
+                           a.loci, a.read, a.hap, sh.max_hap, (uint32_t)task_bytes, a.ref, a.alt, out.band, out.band_stride,     \
+                           out.hard_list, out.overflow_list, out.counters, ablate);                                      \
     }
     if (tier == 0) LAUNCH_COOP(64, 512) else if (tier == 1) LAUNCH_COOP(64, 1024) else LAUNCH_COOP(64, 4096)
 #undef LAUNCH_COOP
@@ -734,35 +731,30 @@ extern "C" size_t vtxk_band_lds_stride(uint32_t m_cap, uint32_t max_hap, uint32_
 }
 
 // in_lds != 0: the in-LDS variant (workspace unused); the caller has checked that at least one task fits 160 KiB
-extern "C" hipError_t vtxk_launch_band(const uint32_t* tasks, uint32_t n_tasks, uint32_t task_base,
-                                       const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci,
-                                       const uint8_t* read_arena, const uint8_t* hap_arena, uint8_t* workspace,
-                                       uint64_t ws_stride, uint32_t m_cap, uint32_t max_hap, int32_t* ref_score,
-                                       int32_t* alt_score, uint16_t* band, uint32_t band_stride, uint32_t* hard_list,
-                                       uint32_t* overflow_list, uint32_t* counters, int in_lds, uint32_t max_read,
-                                       hipStream_t s) {
+extern "C" hipError_t vtxk_launch_band(const vtx_task_arrays& a, const uint32_t* tasks, uint32_t n_tasks, uint32_t task_base, uint8_t* workspace,
+                                       uint64_t ws_stride, uint32_t m_cap, const vtx_band_shape& sh, const vtx_band_out& out, int in_lds, hipStream_t s) {
     if (!n_tasks) return hipSuccess;
     if (in_lds) {
-        const size_t stride = vtxk_band_lds_stride(m_cap, max_hap, max_read);
+        const size_t stride = vtxk_band_lds_stride(m_cap, sh.max_hap, sh.max_read);
         const uint32_t per_wg = (uint32_t)std::min<size_t>(64, (160 * 1024 - 512) / stride);
         if (!per_wg) return hipErrorInvalidValue;
         const size_t shmem = (size_t)per_wg * stride;
         hipError_t e = hipFuncSetAttribute((const void*)band_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(band_kernel<true>, dim3((n_tasks + per_wg - 1) / per_wg), dim3(64), shmem, s, tasks, n_tasks,
-                           task_base, records, rec_locus, loci, read_arena, hap_arena, workspace, (uint64_t)stride, m_cap,
-                           max_hap, ref_score, alt_score, band, band_stride, hard_list, overflow_list, counters, per_wg, max_read);
+                           task_base, a.records, a.rec_locus, a.loci, a.read, a.hap, workspace, (uint64_t)stride, m_cap,
+                           sh.max_hap, a.ref, a.alt, out.band, out.band_stride, out.hard_list, out.overflow_list, out.counters, per_wg, sh.max_read);
         return hipGetLastError();
     }
     const uint32_t lanes = vtxk_band_lanes(n_tasks);
     if (lanes < 64)
-        hipLaunchKernelGGL((band_kernel<false, 1>), dim3((n_tasks + lanes - 1) / lanes), dim3(64), 0, s, tasks, n_tasks, task_base, records,
-                           rec_locus, loci, read_arena, hap_arena, workspace, ws_stride, m_cap, max_hap, ref_score, alt_score,
-                           band, band_stride, hard_list, overflow_list, counters, lanes, 0u);
+        hipLaunchKernelGGL((band_kernel<false, 1>), dim3((n_tasks + lanes - 1) / lanes), dim3(64), 0, s, tasks, n_tasks, task_base, a.records,
+                           a.rec_locus, a.loci, a.read, a.hap, workspace, ws_stride, m_cap, sh.max_hap, a.ref, a.alt,
+                           out.band, out.band_stride, out.hard_list, out.overflow_list, out.counters, lanes, 0u);
     else
-        hipLaunchKernelGGL((band_kernel<false, 64>), dim3((n_tasks + lanes - 1) / lanes), dim3(64), 0, s, tasks, n_tasks, task_base, records,
-                           rec_locus, loci, read_arena, hap_arena, workspace, ws_stride, m_cap, max_hap, ref_score, alt_score,
-                           band, band_stride, hard_list, overflow_list, counters, lanes, 0u);
+        hipLaunchKernelGGL((band_kernel<false, 64>), dim3((n_tasks + lanes - 1) / lanes), dim3(64), 0, s, tasks, n_tasks, task_base, a.records,
+                           a.rec_locus, a.loci, a.read, a.hap, workspace, ws_stride, m_cap, sh.max_hap, a.ref, a.alt,
+                           out.band, out.band_stride, out.hard_list, out.overflow_list, out.counters, lanes, 0u);
     return hipGetLastError();
 }
 
@@ -1762,12 +1754,11 @@ extern "C" uint32_t vtxk_band_task_words(void) { return TASK_WORDS; }
 
 extern "C" uint32_t vtxk_band_pend_words(void) { return PEND_WORDS; }
 
-extern "C" hipError_t vtxk_launch_band_pending(const uint32_t* pending, uint32_t n_pending, const uint32_t* pend_buf,
-                                               int32_t* ref_score, int32_t* alt_score, uint16_t* band,
-                                               uint32_t band_stride, uint32_t* hard_list, uint32_t* counters, hipStream_t s) {
+extern "C" hipError_t vtxk_launch_band_pending(const vtx_task_arrays& a, const uint32_t* pending, uint32_t n_pending, const uint32_t* pend_buf,
+                                               const vtx_band_out& out, hipStream_t s) {
     if (!n_pending) return hipSuccess;
     hipLaunchKernelGGL(band_pending_kernel, dim3((n_pending + 7) / 8), dim3(256), 0, s, pending, n_pending, pend_buf,
-                       ref_score, alt_score, band, band_stride, hard_list, counters);
+                       a.ref, a.alt, out.band, out.band_stride, out.hard_list, out.counters);
     return hipGetLastError();
 }
 
@@ -1858,16 +1849,13 @@ extern "C" size_t vtxk_slow_ws_stride(uint32_t m_cap, uint32_t max_hap, uint32_t
     return (o + 63) & ~(size_t)63;
 }
 
-extern "C" hipError_t vtxk_launch_slow_align(const uint32_t* recs, const uint32_t* tasks, uint32_t n_tasks, int banded,
-                                             const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci,
-                                             const uint8_t* read_arena, const uint8_t* hap_arena, uint8_t* workspace,
-                                             uint64_t ws_stride, uint32_t m_cap, uint32_t max_hap, uint32_t max_read,
-                                             int32_t* ref_score, int32_t* alt_score, uint32_t* retry_list, uint32_t* counters,
-                                             hipStream_t s) {
+extern "C" hipError_t vtxk_launch_slow_align(const vtx_task_arrays& a, const uint32_t* recs, const uint32_t* tasks, uint32_t n_tasks, int banded,
+                                             uint8_t* workspace, uint64_t ws_stride, uint32_t m_cap, uint32_t max_hap, uint32_t max_read,
+                                             uint32_t* retry_list, uint32_t* counters, hipStream_t s) {
     if (!n_tasks) return hipSuccess;
-    hipLaunchKernelGGL(slow_align_kernel, dim3((n_tasks + 63) / 64), dim3(64), 0, s, recs, tasks, n_tasks, banded, records,
-                       rec_locus, loci, read_arena, hap_arena, workspace, ws_stride, m_cap, max_hap, max_read, ref_score,
-                       alt_score, retry_list, counters);
+    hipLaunchKernelGGL(slow_align_kernel, dim3((n_tasks + 63) / 64), dim3(64), 0, s, recs, tasks, n_tasks, banded, a.records,
+                       a.rec_locus, a.loci, a.read, a.hap, workspace, ws_stride, m_cap, max_hap, max_read, a.ref,
+                       a.alt, retry_list, counters);
     return hipGetLastError();
 }
 
@@ -3016,17 +3004,15 @@ static uint32_t corridor_resident_grid() {
     }();
     return n;
 }
-extern "C" hipError_t vtxk_launch_band_corridor(const uint32_t* recs, uint32_t n_recs, const vtx_record* records, const uint32_t* rec_locus,
-                                                const vtx_locus* loci, const uint8_t* read_arena, const uint8_t* hap_arena,
-                                                int32_t* ref_score, int32_t* alt_score, uint32_t* counters, int stats,
-                                                uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, const uint32_t* n_dev, hipStream_t s) {
+extern "C" hipError_t vtxk_launch_band_corridor(const vtx_task_arrays& a, const uint32_t* recs, uint32_t n_recs, const vtx_diag_routes& routes,
+                                                const uint32_t* n_dev, hipStream_t s) {
     if (!n_recs) return hipSuccess;
     // (n_dev != nullptr: n_recs is a bound — 3.5 M lanes for the headline's 43 k records — and a workgroup past the device's count costs its
     //  dispatch: at most a resident grid then.  libvtx_dev.so, VTX_CORRIDOR_FULL_GRID=1: the grid over the bound, for the A/B.)
     const uint32_t blocks = (n_recs + 255) / 256;
     const uint32_t grid = n_dev && !VTX_DEV_ENV("VTX_CORRIDOR_FULL_GRID") ? std::min(blocks, corridor_resident_grid()) : blocks;
-    hipLaunchKernelGGL(band_corridor_kernel, dim3(grid), dim3(256), 0, s, recs, n_recs, records, rec_locus, loci, read_arena,
-                       hap_arena, ref_score, alt_score, counters, (uint32_t)stats, tight_list, tight_pack, stage, n_dev);
+    hipLaunchKernelGGL(band_corridor_kernel, dim3(grid), dim3(256), 0, s, recs, n_recs, a.records, a.rec_locus, a.loci, a.read,
+                       a.hap, a.ref, a.alt, routes.counters, (uint32_t)routes.stats, routes.tight_list, routes.tight_pack, routes.stage, n_dev);
     return hipGetLastError();
 }
 
@@ -3077,6 +3063,14 @@ static uint32_t pick_heads(uint32_t tasks_per_locus, bool global_tables) {
     if (tasks_per_locus < 48) return 256;
     return 512;
 }
+// Bucket count and stride of a haplotype's table for a shape of data.  The one place that picks them: vtxk_band_gtables_bytes sizes the
+// buffer from it, vtxk_launch_band_run and vtxk_launch_band_diag build the tables by it, vtxk_launch_band_refine and
+// vtxk_launch_band_diag2 read them by it.  global: as pick_heads has it (false: a table band_run_kernel builds for itself in LDS).
+struct TableGeom { uint32_t n_heads; size_t tstride; };
+static TableGeom table_geom(const vtx_band_shape& sh, bool global) {
+    const uint32_t n_heads = pick_heads(sh.tasks_per_locus, global);
+    return {n_heads, band_table_stride(sh.max_hap, n_heads, !global)};
+}
 
 // Global table buffer for this shape of data: bytes to reserve (0: tables live in LDS) and how many loci they hold.  The
 // kernel addresses the tables with 32-bit offsets: at most 4 GB, i.e. ~400 k deep / ~580 k shallow loci at padding 100 —
@@ -3084,7 +3078,7 @@ static uint32_t pick_heads(uint32_t tasks_per_locus, bool global_tables) {
 extern "C" size_t vtxk_band_gtables_bytes(uint32_t n_loci, uint32_t max_hap, uint32_t tasks_per_locus, uint32_t* loci_cap) {
     if (loci_cap) *loci_cap = 0;
     if (tasks_per_locus >= gt_max_tpl()) return 0;
-    const size_t per_locus = 2 * band_table_stride(max_hap, pick_heads(tasks_per_locus, true));
+    const size_t per_locus = 2 * table_geom(vtx_band_shape{max_hap, 0, 0, tasks_per_locus}, true).tstride;
     size_t cap = ((size_t)4 << 30) - 65536;
     if (VTX_DEV_ENV("VTX_BAND_GT_BYTES")) cap = std::max<size_t>(per_locus, strtoull(VTX_DEV_ENV("VTX_BAND_GT_BYTES"), nullptr, 10));   // test hook
     const size_t hold = std::min<size_t>(n_loci, cap / per_locus);
@@ -3104,19 +3098,15 @@ extern "C" int vtxk_band_second_chance(uint32_t tasks_per_locus, int long_lists)
 extern "C" uint32_t vtxk_band_run_grid(uint32_t nt, uint32_t wpe) { return 256u * (nt == 64 ? 4u * wpe : wpe); }
 extern "C" uint32_t vtxk_band_run_lanes(void) { return 256u * 256u * (uint32_t)std::max(VTX_WPE, 6); }     // max over both block sizes of grid x nt
 
-extern "C" hipError_t vtxk_launch_band_run(uint32_t n_tasks, uint32_t task_base, const vtx_record* records,
-                                           const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                           const uint8_t* hap_arena, uint32_t max_hap, uint32_t min_hap, int32_t* ref_score,
-                                           int32_t* alt_score, uint32_t* logbuf, uint16_t* band,
-                                           uint32_t band_stride, uint32_t* hard_list, uint32_t* overflow_list,
-                                           uint32_t* pending_list, uint32_t* pend_buf, uint32_t hard_cap, uint32_t pend_cap,
-                                           uint32_t* counters, uint32_t tasks_per_locus, uint32_t gt_l0, uint32_t n_loci,
-                                           uint8_t* gtables, size_t gtables_bytes, const uint32_t* task_list, int long_lists,
+extern "C" hipError_t vtxk_launch_band_run(const vtx_task_arrays& a, uint32_t n_tasks, uint32_t task_base, const vtx_band_shape& sh,
+                                           const vtx_band_tables& tb, const vtx_band_out& out, uint32_t* logbuf, uint32_t* pending_list,
+                                           uint32_t* pend_buf, uint32_t hard_cap, uint32_t pend_cap, const uint32_t* task_list, int long_lists,
                                            hipStream_t s) {
     // long_lists: the caller saw many tasks overflow the 12-entry lists (noisy reads): 15-entry lists from the start
-    // gtables != nullptr: room for the tables of loci [gt_l0, gt_l0 + n_loci) — the loci of THIS range of tasks; they are
+    // tb.gtables != nullptr: room for the tables of loci [gt_l0, gt_l0 + n_loci) — the loci of THIS range of tasks; they are
     // built here, then read by the kernel
     if (!n_tasks) return hipSuccess;
+    const uint32_t tasks_per_locus = sh.tasks_per_locus;
     // (LDS-table variants, the fallback:) deep data (>= 64 tasks per locus): 256-task workgroups.  A workgroup processes its loci in passes of `tables / 2`
     // loci (the k-mer tables live in LDS); in a pass only the lanes of those loci work.  512-entry head arrays: two loci
     // fit next to the 28 KiB of lane arrays at 4 workgroups per CU, one pass per workgroup nearly always (2048-entry heads
@@ -3130,14 +3120,12 @@ extern "C" hipError_t vtxk_launch_band_run(uint32_t n_tasks, uint32_t task_base,
     // (no barrier per block: config 3 51.1 -> 50.6 ms, 64 reads per locus +4 %).  Without the buffer (or when the
     // tables would not fit it) they live in LDS: 256-task workgroups for deep loci (two tables per pass next to the lane
     // arrays, four workgroups per CU), one-wavefront workgroups with up to 32 tables below 64 tasks per locus.
-    const bool want_global = tasks_per_locus < gt_max_tpl() && gtables;
-    uint32_t n_heads = pick_heads(tasks_per_locus, want_global);
-    size_t tstride = band_table_stride(max_hap, n_heads, !want_global);
-    if (want_global && (size_t)n_loci * 2 * tstride > gtables_bytes) {       // the buffer is too small: tables in LDS
-        n_heads = pick_heads(tasks_per_locus, false);
-        tstride = band_table_stride(max_hap, n_heads, true);
-    }
-    const bool global_tables = want_global && (size_t)n_loci * 2 * tstride <= gtables_bytes;
+    const bool want_global = tasks_per_locus < gt_max_tpl() && tb.gtables;
+    TableGeom g = table_geom(sh, want_global);
+    if (want_global && (size_t)tb.n_loci * 2 * g.tstride > tb.gtables_bytes) g = table_geom(sh, false);       // the buffer is too small: tables in LDS
+    const uint32_t n_heads = g.n_heads;
+    const size_t tstride = g.tstride;
+    const bool global_tables = want_global && (size_t)tb.n_loci * 2 * tstride <= tb.gtables_bytes;
     const bool wave_wg = global_tables || tasks_per_locus < 64;
     const uint32_t nt = wave_wg ? 64 : 256;
     // wavefronts per SIMD and list entries per lane.  Tables in LDS: 4 x 15 (111 VGPRs; 5 -> 93 VGPRs cost more than the
@@ -3167,7 +3155,7 @@ extern "C" hipError_t vtxk_launch_band_run(uint32_t n_tasks, uint32_t task_base,
     if (shmem > 160 * 1024 - 256) return hipErrorInvalidValue;
     if (task_list && !global_tables) return hipErrorInvalidValue;    // (list mode reads the tables the first pass built)
     if (global_tables && !task_list)
-        launch_band_tables(loci, gt_l0, n_loci, hap_arena, max_hap, min_hap, tstride, n_heads, gtables, false, s);
+        launch_band_tables(a.loci, tb.gt_l0, tb.n_loci, a.hap, sh.max_hap, sh.min_hap, tstride, n_heads, tb.gtables, false, s);
     const uint32_t ablate = (uint32_t)(VTX_DEV_ENV("VTX_BAND_ABLATE") ? atoi(VTX_DEV_ENV("VTX_BAND_ABLATE")) : 0);
     const uint32_t xcd_claim = ((tasks_per_locus >= 24 || VTX_DEV_ENV("VTX_BAND_XCD")) && !VTX_DEV_ENV("VTX_BAND_NO_XCD")) ? 1u : 0u;   // (measured: config 3 -3 %, 64 / 32 reads per locus -4.5 %, 16: -1 %, 4: +2 %)
 #define LAUNCH_RUN(NTV, GTV, WV, PV)                                                                                 \
@@ -3180,10 +3168,10 @@ extern "C" hipError_t vtxk_launch_band_run(uint32_t n_tasks, uint32_t task_base,
         hipLaunchKernelGGL((band_run_kernel<NTV, GTV, WV, PV>),                                                      \
                            dim3(std::min((n_tasks + NTV - 1) / NTV, vtxk_band_run_grid(NTV, WV))),                    \
                            dim3(NTV), shmem, s, n_tasks,                                                             \
-                           task_base, records, rec_locus, loci, read_arena, hap_arena, max_hap, min_hap, tables,     \
-                           (uint32_t)tstride, ref_score, alt_score, logbuf, band, band_stride, hard_list,            \
-                           overflow_list, pending_list, pend_buf, hard_cap, pend_cap, counters, ablate, n_heads,     \
-                           (const uint8_t*)gtables, gt_l0, task_list ? 0u : xcd_claim, task_list);                   \
+                           task_base, a.records, a.rec_locus, a.loci, a.read, a.hap, sh.max_hap, sh.min_hap, tables, \
+                           (uint32_t)tstride, a.ref, a.alt, logbuf, out.band, out.band_stride, out.hard_list,        \
+                           out.overflow_list, pending_list, pend_buf, hard_cap, pend_cap, out.counters, ablate, n_heads, \
+                           (const uint8_t*)tb.gtables, tb.gt_l0, task_list ? 0u : xcd_claim, task_list);             \
     }
     if (variant == 1) LAUNCH_RUN(64, true, 4, VTX_PS)
     else if (variant == 2) LAUNCH_RUN(64, true, 5, VTX_PS)
@@ -3193,7 +3181,8 @@ extern "C" hipError_t vtxk_launch_band_run(uint32_t n_tasks, uint32_t task_base,
     return hipGetLastError();
 }
 
-// What band_diag_kernel and band_tail_kernel must agree on, whoever launches the latter: the template choice and the stats word.
+// What band_diag_kernel and band_tail_kernel agree on, whoever launches the latter: the template choice and the stats word, each a function
+// of the vtx_band_shape and the vtx_diag_routes that the three launchers (diag, tail, recheck) are handed alike.
 // two-byte match entries (40 per task) whenever a haplotype position fits a byte; VTX_DIAG_WIDE=1 forces the four-byte variant (tests)
 static bool diag_narrow(uint32_t max_hap) {
     static const bool force_wide = VTX_DEV_ENV("VTX_DIAG_WIDE") != nullptr;
@@ -3203,22 +3192,22 @@ static bool diag_three_words(uint32_t max_read) {
     static const bool force_four = VTX_DEV_ENV("VTX_DIAG_FOUR_WORDS") != nullptr;      // (tests: the four-word build on short reads)
     return max_read <= 192 && !force_four && vtxf::NW >= 3;
 }
-static uint32_t diag_stats_word(int stats, uint32_t tasks_per_locus) {
-    return (uint32_t)stats | (VTX_DEV_ENV("VTX_DIAG_ABLATE") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_ABLATE")) << 8 : 0u) |
+static uint32_t diag_stats_word(const vtx_diag_routes& routes, const vtx_band_shape& sh) {
+    return (uint32_t)routes.stats |(VTX_DEV_ENV("VTX_DIAG_ABLATE") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_ABLATE")) << 8 : 0u) |
            (VTX_DEV_ENV("VTX_BAND_NO_CORRIDOR") ? 0x10000u : 0u) |         // (A/B hook: round 5's records for band_refine_kernel)
            (VTX_DEV_ENV("VTX_DIAG_NO_TWINS") ? 0x20000u : 0u) |            // (A/B hook: every row that is not intact and unique is probed, the twin lists unused)
            (VTX_DEV_ENV("VTX_DIAG_PHASES") ? 0x80000u : 0u) |
-           (band_use_t3(tasks_per_locus) ? 0u : 0x40000u);                 // (a queue entry and a presence-bitmap word per row instead of t3[] and blocks of three rows)
+           (band_use_t3(sh.tasks_per_locus) ? 0u : 0x40000u);              // (a queue entry and a presence-bitmap word per row instead of t3[] and blocks of three rows)
 }
 // Whether band_diag_kernel leaves records for band_tail_kernel at all: a buffer with room, and (libvtx_dev.so) neither VTX_DIAG_NO_TAIL=1
 // nor the profiling aids of VTX_DIAG_ABLATE, which keep every task in its wavefront, the path of rounds 3 - 6.  The one place that decides
 // it: vtxk_launch_band_diag asks, and so does a caller that launches the tail itself.
-extern "C" int vtxk_band_tail_on(const uint32_t* tail_rec, uint32_t tail_cap) {
-    return tail_rec != nullptr && tail_cap != 0 && !VTX_DEV_ENV("VTX_DIAG_NO_TAIL") && !VTX_DEV_ENV("VTX_DIAG_ABLATE");
+extern "C" int vtxk_band_tail_on(vtx_rec_buf tail) {
+    return tail.rec != nullptr && tail.cap != 0 && !VTX_DEV_ENV("VTX_DIAG_NO_TAIL") && !VTX_DEV_ENV("VTX_DIAG_ABLATE");
 }
-// band_tail_kernel over the records a vtxk_launch_band_diag with the same arguments (n_tasks > 0, hipSuccess, vtxk_band_tail_on) left in
-// tail_rec; s runs behind that band_diag_kernel.  The lists are diag_route's: a caller that runs the kernel beside the readers of
-// fail_list / dense_list passes nullptr for both — with a tight list no record is routed to either (see band_tail_kernel).
+// band_tail_kernel over the records a vtxk_launch_band_diag with the same shape, routes and buffer (n_tasks > 0, hipSuccess,
+// vtxk_band_tail_on) left in tail.rec; s runs behind that band_diag_kernel.  The lists are diag_route's: a caller that runs the kernel beside
+// the readers of fail_list / dense_list passes a copy of the routes with both null — with a tight list no record is routed to either (see band_tail_kernel).
 // resident_grid != 0 (the kernel runs beside others): no more workgroups than the device holds at once, each looping over its share
 // of the records.  With the 65 536 of the launch that has the device to itself a workgroup that ends hands its 8.7 KB of LDS to the
 // next one of this kernel, and a neighbour's workgroup (band_sweep_kernel: 19.1 KB in one piece) finds no room until the last record
@@ -3236,23 +3225,21 @@ static uint32_t tail_resident_grid() {
     }();
     return n;
 }
-extern "C" hipError_t vtxk_launch_band_tail(uint32_t max_hap, uint32_t max_read, int32_t* ref_score, int32_t* alt_score, uint32_t* fail_list,
-                                            uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, int stats,
-                                            uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask,
-                                            uint32_t* tail_rec, uint32_t tail_cap, int resident_grid, hipStream_t s) {
-    if (!vtxk_band_tail_on(tail_rec, tail_cap)) return hipErrorInvalidValue;
-    if (!tight_list && !fail_list) return hipErrorInvalidValue;            // (without a tight list the undecided records go to fail_list)
-    const uint32_t st = diag_stats_word(stats, tasks_per_locus);
+extern "C" hipError_t vtxk_launch_band_tail(const vtx_task_arrays& a, const vtx_band_shape& sh, const vtx_diag_routes& routes, vtx_rec_buf tail,
+                                            int resident_grid, hipStream_t s) {
+    if (!vtxk_band_tail_on(tail)) return hipErrorInvalidValue;
+    if (!routes.tight_list && !routes.fail_list) return hipErrorInvalidValue;            // (without a tight list the undecided records go to fail_list)
+    const uint32_t st = diag_stats_word(routes, sh);
     // (libvtx_dev.so, VTX_DIAG_TAIL_GRID: a small grid, so that a test's few thousand records make every lane loop)
     const uint32_t grid_hook = VTX_DEV_ENV("VTX_DIAG_TAIL_GRID") ? std::max(1u, (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_TAIL_GRID"))) : 65536u;
 #define LAUNCH_TAIL(STV, AV)                                                                                                              \
     hipLaunchKernelGGL((band_tail_kernel<STV, AV>),                                                                                         \
-                       dim3(std::min({(tail_cap + 63u) / 64u, 65536u, grid_hook, resident_grid ? tail_resident_grid<STV, AV>() : 65536u})), \
-                       dim3(64), 0, s, tail_rec, tail_cap,                                                                                  \
-                       counters + VTX_CNT_TAIL, ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list,          \
-                       tight_pack, stage, dense_list, dense_mask)
-    const bool three = diag_three_words(max_read);
-    if (diag_narrow(max_hap)) { if (three) LAUNCH_TAIL(uint16_t, 3); else LAUNCH_TAIL(uint16_t, vtxf::NW); }
+                       dim3(std::min({(tail.cap + 63u) / 64u, 65536u, grid_hook, resident_grid ? tail_resident_grid<STV, AV>() : 65536u})), \
+                       dim3(64), 0, s, tail.rec, tail.cap,                                                                                  \
+                       routes.counters + VTX_CNT_TAIL, a.ref, a.alt, routes.fail_list, routes.refine_rec, routes.refine_cap,                \
+                       routes.counters, st, routes.tight_list, routes.tight_pack, routes.stage, routes.dense_list, routes.dense_mask)
+    const bool three = diag_three_words(sh.max_read);
+    if (diag_narrow(sh.max_hap)) { if (three) LAUNCH_TAIL(uint16_t, 3); else LAUNCH_TAIL(uint16_t, vtxf::NW); }
     else { if (three) LAUNCH_TAIL(uint32_t, 3); else LAUNCH_TAIL(uint32_t, vtxf::NW); }
 #undef LAUNCH_TAIL
     return hipGetLastError();
@@ -3260,87 +3247,75 @@ extern "C" hipError_t vtxk_launch_band_tail(uint32_t max_hap, uint32_t max_read,
 // Whether band_diag_kernel leaves recheck records (tasks that fail its harmless test): a buffer with room, two-byte match entries (the
 // tight test's byte per match is laid out for them: every haplotype <= 255 bases), and (libvtx_dev.so) neither VTX_DIAG_NO_RECHECK=1
 // nor the profiling aids of VTX_DIAG_ABLATE.  As with the tail, the one place that decides it.
-extern "C" int vtxk_band_recheck_on(const uint32_t* recheck_rec, uint32_t recheck_cap, uint32_t max_hap) {
-    return recheck_rec != nullptr && recheck_cap != 0 && diag_narrow(max_hap) && !VTX_DEV_ENV("VTX_DIAG_NO_RECHECK") && !VTX_DEV_ENV("VTX_DIAG_ABLATE");
+extern "C" int vtxk_band_recheck_on(vtx_rec_buf recheck, uint32_t max_hap) {
+    return recheck.rec != nullptr && recheck.cap != 0 && diag_narrow(max_hap) && !VTX_DEV_ENV("VTX_DIAG_NO_RECHECK") && !VTX_DEV_ENV("VTX_DIAG_ABLATE");
 }
-// band_tail_kernel's recheck mode over the records a vtxk_launch_band_diag with the same arguments (vtxk_band_recheck_on) left in
-// recheck_rec; s runs behind that band_diag_kernel and in front of every reader of the lists and their counts: the kernel appends to
+// band_tail_kernel's recheck mode over the records a vtxk_launch_band_diag with the same shape, routes and buffer (vtxk_band_recheck_on) left in
+// recheck.rec; s runs behind that band_diag_kernel and in front of every reader of the lists and their counts: the kernel appends to
 // all of them.  A resident grid looping over the device's count (counters[VTX_CNT_RECHECK]): the kernel may run beside
 // band_tail_kernel on another stream, and the host does not know the count.
-extern "C" hipError_t vtxk_launch_band_recheck(uint32_t max_hap, uint32_t max_read, int32_t* ref_score, int32_t* alt_score, uint32_t* fail_list,
-                                               uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, int stats,
-                                               uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask,
-                                               uint32_t* recheck_rec, uint32_t recheck_cap, hipStream_t s) {
-    if (!vtxk_band_recheck_on(recheck_rec, recheck_cap, max_hap) || !fail_list) return hipErrorInvalidValue;
-    const uint32_t st = diag_stats_word(stats, tasks_per_locus);
+extern "C" hipError_t vtxk_launch_band_recheck(const vtx_task_arrays& a, const vtx_band_shape& sh, const vtx_diag_routes& routes, vtx_rec_buf recheck,
+                                               hipStream_t s) {
+    if (!vtxk_band_recheck_on(recheck, sh.max_hap) || !routes.fail_list) return hipErrorInvalidValue;
+    const uint32_t st = diag_stats_word(routes, sh);
 #define LAUNCH_RECHECK(AV)                                                                                                               \
     hipLaunchKernelGGL((band_tail_kernel<uint16_t, AV, true>),                                                                             \
-                       dim3(std::min({(recheck_cap + 63u) / 64u, 65536u, tail_resident_grid<uint16_t, AV, true>()})), dim3(64), 0, s,      \
-                       recheck_rec, recheck_cap, counters + VTX_CNT_RECHECK, ref_score, alt_score, fail_list, refine_rec, refine_cap,      \
-                       counters, st, tight_list, tight_pack, stage, dense_list, dense_mask)
-    if (diag_three_words(max_read)) LAUNCH_RECHECK(3); else LAUNCH_RECHECK(vtxf::NW);
+                       dim3(std::min({(recheck.cap + 63u) / 64u, 65536u, tail_resident_grid<uint16_t, AV, true>()})), dim3(64), 0, s,      \
+                       recheck.rec, recheck.cap, routes.counters + VTX_CNT_RECHECK, a.ref, a.alt, routes.fail_list, routes.refine_rec,     \
+                       routes.refine_cap, routes.counters, st, routes.tight_list, routes.tight_pack, routes.stage, routes.dense_list,      \
+                       routes.dense_mask)
+    if (diag_three_words(sh.max_read)) LAUNCH_RECHECK(3); else LAUNCH_RECHECK(vtxf::NW);
 #undef LAUNCH_RECHECK
     return hipGetLastError();
 }
 
-// Tables of loci [gt_l0, gt_l0 + n_loci) into gtables (the same layout and bucket count vtxk_launch_band_run picks for this
-// shape of data), then band_diag_kernel over tasks [task_base, task_base + n_tasks).  Returns hipErrorInvalidValue when the
+// Tables of loci [tb.gt_l0, tb.gt_l0 + tb.n_loci) into tb.gtables (table_geom: the layout and bucket count vtxk_launch_band_run picks
+// for this shape of data), then band_diag_kernel over tasks [task_base, task_base + n_tasks).  Returns hipErrorInvalidValue when the
 // tables do not fit the buffer (the caller then runs band_run_kernel alone, which falls back to tables in LDS).
-extern "C" hipError_t vtxk_launch_band_diag(uint32_t n_tasks, uint32_t task_base, const vtx_record* records,
-                                            const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                            const uint8_t* hap_arena, uint32_t max_hap, uint32_t min_hap, int32_t* ref_score, int32_t* alt_score,
-                                            uint32_t* fail_list, uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters,
-                                            uint32_t tasks_per_locus, uint32_t gt_l0, uint32_t n_loci, uint8_t* gtables,
-                                            size_t gtables_bytes, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage,
-                                            uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, uint32_t* tail_rec, uint32_t tail_cap,
-                                            int tail_inline, uint32_t* recheck_rec, uint32_t recheck_cap, hipStream_t s) {
-    // recheck_rec != nullptr: room for recheck_cap records (the tail's layout) of tasks that fail the kernel's harmless test;
+extern "C" hipError_t vtxk_launch_band_diag(const vtx_task_arrays& a, uint32_t n_tasks, uint32_t task_base, const vtx_band_shape& sh,
+                                            const vtx_band_tables& tb, const vtx_diag_routes& routes, vtx_rec_buf tail, int tail_inline,
+                                            vtx_rec_buf recheck, hipStream_t s) {
+    // recheck.rec != nullptr: room for recheck.cap records (the tail's layout) of tasks that fail the kernel's harmless test;
     // counters[VTX_CNT_RECHECK] counts them.  The caller launches vtxk_launch_band_recheck behind this call when vtxk_band_recheck_on
     // says the records exist.  nullptr: such a task leaves with W_NOT_HARMLESS.
-    // max_read: the longest read of the batch (the fast kernels' records) — up to 192 bases the kernel is built with three mask words
-    // tail_rec != nullptr: room for tail_cap records of band_tail_kernel (TAIL_WORDS words each, word-major); counters[VTX_CNT_TAIL]
+    // sh.max_read: the longest read of the batch (the fast kernels' records) — up to 192 bases the kernel is built with three mask words
+    // tail.rec != nullptr: room for tail.cap records of band_tail_kernel (TAIL_WORDS words each, word-major); counters[VTX_CNT_TAIL]
     // counts them.  tail_inline != 0: band_tail_kernel is launched here, behind band_diag_kernel on the same stream; 0: the caller
     // launches it (vtxk_launch_band_tail, when vtxk_band_tail_on says the records exist) on a stream that waits for this one.
     if (!n_tasks) return hipSuccess;
-    if (!vtxk_band_tail_on(tail_rec, tail_cap)) tail_rec = nullptr;
-    if (!vtxk_band_recheck_on(recheck_rec, recheck_cap, max_hap)) recheck_rec = nullptr;
-    const uint32_t n_heads = pick_heads(tasks_per_locus, true);
-    const size_t tstride = band_table_stride(max_hap, n_heads);
-    if (!gtables || (size_t)n_loci * 2 * tstride > gtables_bytes) return hipErrorInvalidValue;
-    const bool use_t3 = band_use_t3(tasks_per_locus);
-    launch_band_tables(loci, gt_l0, n_loci, hap_arena, max_hap, min_hap, tstride, n_heads, gtables, use_t3, s);
+    if (!vtxk_band_tail_on(tail)) tail.rec = nullptr;
+    if (!vtxk_band_recheck_on(recheck, sh.max_hap)) recheck.rec = nullptr;
+    const TableGeom g = table_geom(sh, true);
+    if (!tb.gtables || (size_t)tb.n_loci * 2 * g.tstride > tb.gtables_bytes) return hipErrorInvalidValue;
+    const bool use_t3 = band_use_t3(sh.tasks_per_locus);
+    launch_band_tables(a.loci, tb.gt_l0, tb.n_loci, a.hap, sh.max_hap, sh.min_hap, g.tstride, g.n_heads, tb.gtables, use_t3, s);
     const uint32_t n_blocks = (n_tasks + 255) / 256;
-    const uint32_t st = diag_stats_word(stats, tasks_per_locus);
+    const uint32_t st = diag_stats_word(routes, sh);
 #define LAUNCH_DIAG(STV, AV)                                                                                                              \
     hipLaunchKernelGGL((band_diag_kernel<4, STV, AV>), dim3(((n_blocks + 7) / 8) * 8), dim3(256), 0, s, n_tasks, task_base, n_blocks,       \
-                       records, rec_locus, loci, read_arena, max_hap, (uint32_t)tstride, n_heads, (const uint8_t*)gtables, gt_l0,           \
-                       ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, st, tight_list, tight_pack, stage, dense_list,     \
-                       dense_mask, min_hap, tail_rec, tail_cap, recheck_rec, recheck_cap)
-    if (tail_rec) { const hipError_t e = hipMemsetAsync(counters + VTX_CNT_TAIL, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
-    if (recheck_rec) { const hipError_t e = hipMemsetAsync(counters + VTX_CNT_RECHECK, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
-    const bool three = diag_three_words(max_read);
-    if (diag_narrow(max_hap)) { if (three) LAUNCH_DIAG(uint16_t, 3); else LAUNCH_DIAG(uint16_t, vtxf::NW); }
+                       a.records, a.rec_locus, a.loci, a.read, sh.max_hap, (uint32_t)g.tstride, g.n_heads, (const uint8_t*)tb.gtables,      \
+                       tb.gt_l0, a.ref, a.alt, routes.fail_list, routes.refine_rec, routes.refine_cap, routes.counters, st,                 \
+                       routes.tight_list, routes.tight_pack, routes.stage, routes.dense_list, routes.dense_mask, sh.min_hap, tail.rec,      \
+                       tail.cap, recheck.rec, recheck.cap)
+    if (tail.rec) { const hipError_t e = hipMemsetAsync(routes.counters + VTX_CNT_TAIL, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
+    if (recheck.rec) { const hipError_t e = hipMemsetAsync(routes.counters + VTX_CNT_RECHECK, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
+    const bool three = diag_three_words(sh.max_read);
+    if (diag_narrow(sh.max_hap)) { if (three) LAUNCH_DIAG(uint16_t, 3); else LAUNCH_DIAG(uint16_t, vtxf::NW); }
     else { if (three) LAUNCH_DIAG(uint32_t, 3); else LAUNCH_DIAG(uint32_t, vtxf::NW); }
 #undef LAUNCH_DIAG
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess || !tail_rec || !tail_inline) return e;
-    return vtxk_launch_band_tail(max_hap, max_read, ref_score, alt_score, fail_list, refine_rec, refine_cap, counters, tasks_per_locus, stats, tight_list,
-                                 tight_pack, stage, dense_list, dense_mask, tail_rec, tail_cap, 0, s);
+    if (e != hipSuccess || !tail.rec || !tail_inline) return e;
+    return vtxk_launch_band_tail(a, sh, routes, tail, 0, s);
 }
 
 // band_refine_kernel over n_recs records of REFINE_WORDS words: the tables are the ones vtxk_launch_band_diag built
-extern "C" hipError_t vtxk_launch_band_refine(const uint32_t* recs, uint32_t n_recs, const vtx_record* records,
-                                              const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                              uint32_t max_hap, int32_t* ref_score, int32_t* alt_score, uint32_t* fail_list,
-                                              uint32_t* counters, uint32_t tasks_per_locus, uint32_t gt_l0, const uint8_t* gtables,
-                                              int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, const uint32_t* n_dev,
-                                              hipStream_t s) {
+extern "C" hipError_t vtxk_launch_band_refine(const vtx_task_arrays& a, const uint32_t* recs, uint32_t n_recs, const vtx_band_shape& sh,
+                                              const vtx_band_tables& tb, const vtx_diag_routes& routes, const uint32_t* n_dev, hipStream_t s) {
     if (!n_recs) return hipSuccess;
-    const uint32_t n_heads = pick_heads(tasks_per_locus, true);
-    const size_t tstride = band_table_stride(max_hap, n_heads);
-    hipLaunchKernelGGL(band_refine_kernel, dim3((n_recs + 255) / 256), dim3(256), 0, s, recs, n_recs, records, rec_locus, loci, read_arena,
-                       max_hap, (uint32_t)tstride, n_heads, gtables, gt_l0, ref_score, alt_score, fail_list, counters, (uint32_t)stats,
-                       tight_list, tight_pack, stage, n_dev);
+    const TableGeom g = table_geom(sh, true);
+    hipLaunchKernelGGL(band_refine_kernel, dim3((n_recs + 255) / 256), dim3(256), 0, s, recs, n_recs, a.records, a.rec_locus, a.loci, a.read,
+                       sh.max_hap, (uint32_t)g.tstride, g.n_heads, (const uint8_t*)tb.gtables, tb.gt_l0, a.ref, a.alt, routes.fail_list,
+                       routes.counters, (uint32_t)routes.stats, routes.tight_list, routes.tight_pack, routes.stage, n_dev);
     return hipGetLastError();
 }
 
@@ -3462,23 +3437,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VTX_STREAM_W
 
 // band_diag2_kernel (+ band_stream_kernel when stream_list != nullptr) over a task list (the tables are the ones vtxk_launch_band_diag
 // built for the chunk); counters[0] / [1]: sweep / tight; *stream_cnt: the tasks that went through band_stream_kernel
-extern "C" hipError_t vtxk_launch_band_diag2(const uint32_t* tasks, uint32_t n_tasks, const vtx_record* records, const uint32_t* rec_locus,
-                                             const vtx_locus* loci, const uint8_t* read_arena, uint32_t max_hap, int32_t* ref_score,
-                                             int32_t* alt_score, uint32_t tasks_per_locus, uint32_t gt_l0, const uint8_t* gtables,
-                                             uint32_t* sweep_list, uint32_t* tight_list, uint32_t* tight_pack, uint32_t* counters,
-                                             uint32_t* stream_list, uint32_t* stream_diag, uint32_t* stream_cnt, uint8_t* stage,
+extern "C" hipError_t vtxk_launch_band_diag2(const vtx_task_arrays& a, const uint32_t* tasks, uint32_t n_tasks, const vtx_band_shape& sh,
+                                             const vtx_band_tables& tb, uint32_t* sweep_list, uint32_t* tight_list, uint32_t* tight_pack,
+                                             uint32_t* counters, uint32_t* stream_list, uint32_t* stream_diag, uint32_t* stream_cnt, uint8_t* stage,
                                              hipStream_t s) {
     if (!n_tasks) return hipSuccess;
-    if (max_hap > 255) return hipErrorInvalidValue;                  // (two-byte list entries)
-    const uint32_t n_heads = pick_heads(tasks_per_locus, true);
-    const size_t tstride = band_table_stride(max_hap, n_heads);
-    hipLaunchKernelGGL(band_diag2_kernel, dim3((n_tasks + 63) / 64), dim3(64), 0, s, tasks, n_tasks, records, rec_locus, loci, read_arena,
-                       max_hap, (uint32_t)tstride, n_heads, gtables, gt_l0, ref_score, alt_score, sweep_list, tight_list, tight_pack,
+    if (sh.max_hap > 255) return hipErrorInvalidValue;               // (two-byte list entries)
+    const TableGeom g = table_geom(sh, true);
+    const uint8_t* gtables = tb.gtables;
+    hipLaunchKernelGGL(band_diag2_kernel, dim3((n_tasks + 63) / 64), dim3(64), 0, s, tasks, n_tasks, a.records, a.rec_locus, a.loci, a.read,
+                       sh.max_hap, (uint32_t)g.tstride, g.n_heads, gtables, tb.gt_l0, a.ref, a.alt, sweep_list, tight_list, tight_pack,
                        stream_list, stream_diag, stream_cnt, counters, stage);
     if (stream_list) {
         // (*stream_cnt <= n_tasks tasks: workgroups past the count leave at once)
-        hipLaunchKernelGGL(band_stream_kernel, dim3((n_tasks + 63) / 64), dim3(64), 0, s, stream_list, stream_diag, stream_cnt, records, rec_locus, loci,
-                           read_arena, max_hap, (uint32_t)tstride, n_heads, gtables, gt_l0, ref_score, alt_score, sweep_list, tight_list,
+        hipLaunchKernelGGL(band_stream_kernel, dim3((n_tasks + 63) / 64), dim3(64), 0, s, stream_list, stream_diag, stream_cnt, a.records, a.rec_locus,
+                           a.loci, a.read, sh.max_hap, (uint32_t)g.tstride, g.n_heads, gtables, tb.gt_l0, a.ref, a.alt, sweep_list, tight_list,
                            tight_pack, counters);
     }
     return hipGetLastError();
@@ -3486,11 +3459,10 @@ extern "C" hipError_t vtxk_launch_band_diag2(const uint32_t* tasks, uint32_t n_t
 
 extern "C" uint32_t vtxk_band_poly_stride(void) { return (2 + 2 * (4 * SG + 6) + 7) & ~7u; }   // u16 per polyline record
 
-extern "C" hipError_t vtxk_launch_band_expand(const uint32_t* hard_list, uint32_t n_hard, const vtx_record* records,
-                                              const uint32_t* rec_locus, const vtx_locus* loci, const uint16_t* src,
+extern "C" hipError_t vtxk_launch_band_expand(const vtx_task_arrays& a, const uint32_t* hard_list, uint32_t n_hard, const uint16_t* src,
                                               uint32_t src_stride, uint16_t* band, uint32_t band_stride, hipStream_t s) {
     if (!n_hard) return hipSuccess;
-    hipLaunchKernelGGL(band_expand_kernel, dim3((n_hard + 15) / 16), dim3(256), 0, s, hard_list, n_hard, records,
-                       rec_locus, loci, src, src_stride, band, band_stride);
+    hipLaunchKernelGGL(band_expand_kernel, dim3((n_hard + 15) / 16), dim3(256), 0, s, hard_list, n_hard, a.records,
+                       a.rec_locus, a.loci, src, src_stride, band, band_stride);
     return hipGetLastError();
 }

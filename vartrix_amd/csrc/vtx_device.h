@@ -83,102 +83,73 @@ enum VtxBandCnt {
     VTX_CNT_WORDS = 64
 };
 
+// The argument bundles of the vtxk_launch_* functions: what many launches share travels by name, what distinguishes a launch (task
+// ranges, lists, tiers, workspaces, the stream) stays positional.  HOST code only: a launcher unpacks a bundle at its hipLaunchKernelGGL
+// and the kernels keep their __restrict__ parameters (a pointer that reaches a kernel through a struct loses the noalias they carry).
+// the batch's arrays nearly every kernel takes; filled once per run from the context
+struct vtx_task_arrays { const vtx_record* records; const uint32_t* rec_locus; const vtx_locus* loci; const uint8_t* read; const uint8_t* hap; int32_t* ref; int32_t* alt; };
+// the shape of one pass of the banded stage: the haplotypes it takes are those in (min_hap, max_hap] bases, max_read the batch's longest read
+struct vtx_band_shape { uint32_t max_hap, min_hap, max_read, tasks_per_locus; };
+// the k-mer tables in global memory: room for those of loci [gt_l0, gt_l0 + n_loci) (gtables == nullptr: tables in LDS)
+struct vtx_band_tables { uint8_t* gtables; size_t gtables_bytes; uint32_t gt_l0, n_loci; };
+// where band_diag_kernel and the kernels over its records (band_tail_kernel in both modes, band_refine_kernel, band_corridor_kernel)
+// send a task: the lists, their counters (the base of the VtxBandCnt block) and the statistics switch.  band_diag_kernel and the
+// launches of band_tail_kernel over its records take the SAME object, but for a null fail_list / dense_list where the tail says so.
+struct vtx_diag_routes { uint32_t* fail_list; uint32_t* refine_rec; uint32_t refine_cap; uint32_t* counters; int stats; uint32_t* tight_list; uint32_t* tight_pack;
+                         uint8_t* stage; uint32_t* dense_list; uint32_t dense_mask; };
+// a record buffer band_diag_kernel fills for band_tail_kernel (the tail's, the recheck's): cap records of vtxk_band_tail_words() words
+struct vtx_rec_buf { uint32_t* rec; uint32_t cap; };
+// where a kernel that builds bands leaves them: band slots, the hard list of the tasks that own one, the list of the tasks it cannot
+// hold, and the counters of the two lists (counters[0], counters[1]; band_run_kernel: the base of the VtxBandCnt block)
+struct vtx_band_out { uint16_t* band; uint32_t band_stride; uint32_t* hard_list; uint32_t* overflow_list; uint32_t* counters; };
+
 extern "C" {
-hipError_t vtxk_launch_sw_full(int R, int GL, uint32_t n_work, const uint32_t* work, const vtx_record* records,
-                               const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                               const uint8_t* hap_arena, int32_t* ref_score, int32_t* alt_score,
-                               uint32_t max_hap_len, hipStream_t stream);
-hipError_t vtxk_launch_sw_full_lut(int R, uint32_t n_work, const uint32_t* work, const vtx_record* records,
-                                   const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                   const uint8_t* hap_arena, int32_t* ref_score, int32_t* alt_score, uint32_t max_hap_len,
-                                   uint32_t loci_cap, uint32_t* redo, uint32_t* redo_count, hipStream_t stream);
-hipError_t vtxk_launch_sw_full_duo(int R, uint32_t n_work, const uint32_t* work, const vtx_record* records,
-                                   const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                   const uint8_t* hap_arena, int32_t* ref_score, int32_t* alt_score, uint32_t max_hap_len,
-                                   uint32_t loci_cap, uint32_t* redo, uint32_t* redo_count, uint32_t pair_cols,
-                                   hipStream_t stream);
-hipError_t vtxk_launch_sw_banded(int R, int GL, uint32_t n_hard, const uint32_t* hard, const vtx_record* records,
-                                 const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                 const uint8_t* hap_arena, const uint16_t* band, uint32_t band_stride, int32_t* ref_score,
-                                 int32_t* alt_score, uint32_t max_hap_len, hipStream_t stream);
+hipError_t vtxk_launch_sw_full(const vtx_task_arrays& a, int R, int GL, uint32_t n_work, const uint32_t* work, uint32_t max_hap_len, hipStream_t stream);
+hipError_t vtxk_launch_sw_full_lut(const vtx_task_arrays& a, int R, uint32_t n_work, const uint32_t* work, uint32_t max_hap_len, uint32_t loci_cap, uint32_t* redo,
+                                   uint32_t* redo_count, hipStream_t stream);
+hipError_t vtxk_launch_sw_full_duo(const vtx_task_arrays& a, int R, uint32_t n_work, const uint32_t* work, uint32_t max_hap_len, uint32_t loci_cap, uint32_t* redo,
+                                   uint32_t* redo_count, uint32_t pair_cols, hipStream_t stream);
+hipError_t vtxk_launch_sw_banded(const vtx_task_arrays& a, int R, int GL, uint32_t n_hard, const uint32_t* hard, const uint16_t* band, uint32_t band_stride,
+                                 uint32_t max_hap_len, hipStream_t stream);
 size_t vtxk_band_ws_stride(uint32_t m_cap, uint32_t max_hap);
 size_t vtxk_band_lds_stride(uint32_t m_cap, uint32_t max_hap, uint32_t max_read);
-hipError_t vtxk_launch_band(const uint32_t* tasks, uint32_t n_tasks, uint32_t task_base, const vtx_record* records,
-                            const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                            const uint8_t* hap_arena, uint8_t* workspace, uint64_t ws_stride, uint32_t m_cap,
-                            uint32_t max_hap, int32_t* ref_score, int32_t* alt_score, uint16_t* band, uint32_t band_stride,
-                            uint32_t* hard_list, uint32_t* overflow_list, uint32_t* counters, int in_lds, uint32_t max_read,
-                            hipStream_t s);
-hipError_t vtxk_launch_band_run(uint32_t n_tasks, uint32_t task_base, const vtx_record* records,
-                                const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                const uint8_t* hap_arena, uint32_t max_hap, uint32_t min_hap, int32_t* ref_score,
-                                int32_t* alt_score, uint32_t* logbuf, uint16_t* band, uint32_t band_stride,
-                                uint32_t* hard_list, uint32_t* overflow_list, uint32_t* pending_list, uint32_t* pend_buf,
-                                uint32_t hard_cap, uint32_t pend_cap, uint32_t* counters, uint32_t tasks_per_locus,
-                                uint32_t gt_l0, uint32_t n_loci, uint8_t* gtables, size_t gtables_bytes, const uint32_t* task_list,
-                                int long_lists, hipStream_t s);
-hipError_t vtxk_launch_band_diag(uint32_t n_tasks, uint32_t task_base, const vtx_record* records, const uint32_t* rec_locus,
-                                 const vtx_locus* loci, const uint8_t* read_arena, const uint8_t* hap_arena, uint32_t max_hap, uint32_t min_hap,
-                                 int32_t* ref_score, int32_t* alt_score, uint32_t* fail_list, uint32_t* refine_rec,
-                                 uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, uint32_t gt_l0, uint32_t n_loci,
-                                 uint8_t* gtables, size_t gtables_bytes, int stats, uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage,
-                                 uint32_t* dense_list, uint32_t dense_mask, uint32_t max_read, uint32_t* tail_rec, uint32_t tail_cap,
-                                 int tail_inline, uint32_t* recheck_rec, uint32_t recheck_cap, hipStream_t s);
-int vtxk_band_tail_on(const uint32_t* tail_rec, uint32_t tail_cap);
-int vtxk_band_recheck_on(const uint32_t* recheck_rec, uint32_t recheck_cap, uint32_t max_hap);
-hipError_t vtxk_launch_band_recheck(uint32_t max_hap, uint32_t max_read, int32_t* ref_score, int32_t* alt_score, uint32_t* fail_list,
-                                    uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, int stats,
-                                    uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask,
-                                    uint32_t* recheck_rec, uint32_t recheck_cap, hipStream_t s);
-hipError_t vtxk_launch_band_tail(uint32_t max_hap, uint32_t max_read, int32_t* ref_score, int32_t* alt_score, uint32_t* fail_list,
-                                 uint32_t* refine_rec, uint32_t refine_cap, uint32_t* counters, uint32_t tasks_per_locus, int stats,
-                                 uint32_t* tight_list, uint32_t* tight_pack, uint8_t* stage, uint32_t* dense_list, uint32_t dense_mask,
-                                 uint32_t* tail_rec, uint32_t tail_cap, int resident_grid, hipStream_t s);
+hipError_t vtxk_launch_band(const vtx_task_arrays& a, const uint32_t* tasks, uint32_t n_tasks, uint32_t task_base, uint8_t* workspace, uint64_t ws_stride, uint32_t m_cap,
+                            const vtx_band_shape& sh, const vtx_band_out& out, int in_lds, hipStream_t s);
+hipError_t vtxk_launch_band_run(const vtx_task_arrays& a, uint32_t n_tasks, uint32_t task_base, const vtx_band_shape& sh, const vtx_band_tables& tb,
+                                const vtx_band_out& out, uint32_t* logbuf, uint32_t* pending_list, uint32_t* pend_buf, uint32_t hard_cap, uint32_t pend_cap,
+                                const uint32_t* task_list, int long_lists, hipStream_t s);
+hipError_t vtxk_launch_band_diag(const vtx_task_arrays& a, uint32_t n_tasks, uint32_t task_base, const vtx_band_shape& sh, const vtx_band_tables& tb,
+                                 const vtx_diag_routes& routes, vtx_rec_buf tail, int tail_inline, vtx_rec_buf recheck, hipStream_t s);
+int vtxk_band_tail_on(vtx_rec_buf tail);
+int vtxk_band_recheck_on(vtx_rec_buf recheck, uint32_t max_hap);
+hipError_t vtxk_launch_band_recheck(const vtx_task_arrays& a, const vtx_band_shape& sh, const vtx_diag_routes& routes, vtx_rec_buf recheck, hipStream_t s);
+hipError_t vtxk_launch_band_tail(const vtx_task_arrays& a, const vtx_band_shape& sh, const vtx_diag_routes& routes, vtx_rec_buf tail, int resident_grid, hipStream_t s);
 uint32_t vtxk_band_refine_words(void);
 uint32_t vtxk_band_tail_words(void);
-hipError_t vtxk_launch_band_corridor(const uint32_t* recs, uint32_t n_recs, const vtx_record* records, const uint32_t* rec_locus,
-                                     const vtx_locus* loci, const uint8_t* read_arena, const uint8_t* hap_arena, int32_t* ref_score,
-                                     int32_t* alt_score, uint32_t* counters, int stats, uint32_t* tight_list, uint32_t* tight_pack,
-                                     uint8_t* stage, const uint32_t* n_dev, hipStream_t s);
-hipError_t vtxk_launch_band_refine(const uint32_t* recs, uint32_t n_recs, const vtx_record* records, const uint32_t* rec_locus,
-                                   const vtx_locus* loci, const uint8_t* read_arena, uint32_t max_hap, int32_t* ref_score,
-                                   int32_t* alt_score, uint32_t* fail_list, uint32_t* counters, uint32_t tasks_per_locus,
-                                   uint32_t gt_l0, const uint8_t* gtables, int stats, uint32_t* tight_list, uint32_t* tight_pack,
-                                   uint8_t* stage, const uint32_t* n_dev, hipStream_t s);
+hipError_t vtxk_launch_band_corridor(const vtx_task_arrays& a, const uint32_t* recs, uint32_t n_recs, const vtx_diag_routes& routes, const uint32_t* n_dev, hipStream_t s);
+hipError_t vtxk_launch_band_refine(const vtx_task_arrays& a, const uint32_t* recs, uint32_t n_recs, const vtx_band_shape& sh, const vtx_band_tables& tb,
+                                   const vtx_diag_routes& routes, const uint32_t* n_dev, hipStream_t s);
 // the second stage over the tasks band_diag_kernel left with too many off-diagonal matches (vtx_band.hip: band_diag2_kernel, and
 // band_stream_kernel for what exceeds its list when stream_list != nullptr)
-hipError_t vtxk_launch_band_diag2(const uint32_t* tasks, uint32_t n_tasks, const vtx_record* records, const uint32_t* rec_locus,
-                                  const vtx_locus* loci, const uint8_t* read_arena, uint32_t max_hap, int32_t* ref_score,
-                                  int32_t* alt_score, uint32_t tasks_per_locus, uint32_t gt_l0, const uint8_t* gtables,
-                                  uint32_t* sweep_list, uint32_t* tight_list, uint32_t* tight_pack, uint32_t* counters,
-                                  uint32_t* stream_list, uint32_t* stream_diag, uint32_t* stream_cnt, uint8_t* stage, hipStream_t s);
+hipError_t vtxk_launch_band_diag2(const vtx_task_arrays& a, const uint32_t* tasks, uint32_t n_tasks, const vtx_band_shape& sh, const vtx_band_tables& tb,
+                                  uint32_t* sweep_list, uint32_t* tight_list, uint32_t* tight_pack, uint32_t* counters, uint32_t* stream_list,
+                                  uint32_t* stream_diag, uint32_t* stream_cnt, uint8_t* stage, hipStream_t s);
 // ---- the band for any task (vtx_sweep.hip), the masked DP over a device-counted list, the full-matrix check ----
-hipError_t vtxk_launch_band_sweep(const uint32_t* tasks, uint32_t n_tasks, const uint32_t* n_dev, const vtx_record* records,
-                                  const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena, const uint8_t* hap_arena,
-                                  uint16_t* band, uint32_t band_stride, uint32_t* hard_list, uint32_t* overflow_list, uint32_t* counters,
+hipError_t vtxk_launch_band_sweep(const vtx_task_arrays& a, const uint32_t* tasks, uint32_t n_tasks, const uint32_t* n_dev, const vtx_band_out& out,
                                   uint32_t* stat_counters, uint8_t* stage, uint32_t* dbg, uint32_t* glog, hipStream_t s);
 size_t vtxk_band_sweep_log_bytes(void);            // glog: the section logs of the resident workgroups
 uint32_t vtxk_band_sweep_grid(uint32_t n_tasks);
 #ifdef VTX_DEVTOOLS
 // round 4's kernel (vtx_sweep_v1.hip, libvtx_dev.so only: VTX_SWEEP_V1=1), the reference of the A/B tests
-hipError_t vtxk_launch_band_sweep_v1(int tier, const uint32_t* tasks, uint32_t n_tasks, const uint32_t* n_dev, const vtx_record* records,
-                                     const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena, const uint8_t* hap_arena,
-                                     uint16_t* band, uint32_t band_stride, uint32_t* hard_list, uint32_t* overflow_list, uint32_t* counters,
+hipError_t vtxk_launch_band_sweep_v1(const vtx_task_arrays& a, int tier, const uint32_t* tasks, uint32_t n_tasks, const uint32_t* n_dev, const vtx_band_out& out,
                                      uint32_t* stat_counters, uint8_t* stage, uint32_t* dbg, hipStream_t s);
 #endif
 uint32_t vtxk_band_sweep_max_len(void);
-hipError_t vtxk_launch_sw_banded_dev(int R, int GL, uint32_t n_cap, const uint32_t* hard, const uint32_t* n_dev,
-                                     const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci,
-                                     const uint8_t* read_arena, const uint8_t* hap_arena, const uint16_t* band, uint32_t band_stride,
-                                     int32_t* ref_score, int32_t* alt_score, uint32_t max_hap_len, hipStream_t stream);
-hipError_t vtxk_launch_sw_check(int R, int GL, uint32_t n_cap, const uint32_t* list, const uint32_t* packs, const uint32_t* n_dev,
-                                const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci,
-                                const uint8_t* read_arena, const uint8_t* hap_arena, int32_t* ref_score, int32_t* alt_score,
-                                uint32_t max_hap_len, uint32_t* recheck_list, uint32_t* recheck_pack, uint32_t* recheck_count,
-                                uint8_t* stage, hipStream_t stream);
-hipError_t vtxk_launch_sw_diag_band(int R, int GL, uint32_t n_cap, const uint32_t* list, const uint32_t* packs, const uint32_t* n_dev,
-                                    const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci,
-                                    const uint8_t* read_arena, const uint8_t* hap_arena, int32_t* ref_score, int32_t* alt_score,
+hipError_t vtxk_launch_sw_banded_dev(const vtx_task_arrays& a, int R, int GL, uint32_t n_cap, const uint32_t* hard, const uint32_t* n_dev, const uint16_t* band,
+                                     uint32_t band_stride, uint32_t max_hap_len, hipStream_t stream);
+hipError_t vtxk_launch_sw_check(const vtx_task_arrays& a, int R, int GL, uint32_t n_cap, const uint32_t* list, const uint32_t* packs, const uint32_t* n_dev,
+                                uint32_t max_hap_len, uint32_t* recheck_list, uint32_t* recheck_pack, uint32_t* recheck_count, uint8_t* stage, hipStream_t stream);
+hipError_t vtxk_launch_sw_diag_band(const vtx_task_arrays& a, int R, int GL, uint32_t n_cap, const uint32_t* list, const uint32_t* packs, const uint32_t* n_dev,
                                     uint32_t max_hap_len, uint8_t* stage, hipStream_t stream);
 hipError_t vtxk_mark_stage(const uint32_t* list, uint32_t n, const uint32_t* n_dev, uint8_t code, uint8_t* stage, hipStream_t s);
 hipError_t vtxk_mark_stage_records(const uint32_t* recs, uint32_t n, uint8_t code, uint8_t* stage, hipStream_t s);
@@ -186,32 +157,24 @@ hipError_t vtxk_fill_i32(int32_t* p, uint32_t n, int32_t v, hipStream_t s);
 int vtxk_band_second_chance(uint32_t tasks_per_locus, int long_lists);
 uint32_t vtxk_band_lanes(uint32_t n_tasks);
 size_t vtxk_band_coop_lds(uint32_t max_hap, uint32_t mc);
-hipError_t vtxk_launch_band_coop(int tier, const uint32_t* tasks, uint32_t n_tasks, const vtx_record* records, const uint32_t* rec_locus,
-                                 const vtx_locus* loci, const uint8_t* read_arena, const uint8_t* hap_arena, uint32_t max_hap,
-                                 int32_t* ref_score, int32_t* alt_score, uint16_t* band, uint32_t band_stride, uint32_t* hard_list,
-                                 uint32_t* overflow_list, uint32_t* counters, hipStream_t s);
+hipError_t vtxk_launch_band_coop(const vtx_task_arrays& a, int tier, const uint32_t* tasks, uint32_t n_tasks, const vtx_band_shape& sh, const vtx_band_out& out, hipStream_t s);
 size_t vtxk_band_gtables_bytes(uint32_t n_loci, uint32_t max_hap, uint32_t tasks_per_locus, uint32_t* loci_cap);
 uint32_t vtxk_band_task_words(void);
 uint32_t vtxk_band_pend_words(void);
 uint32_t vtxk_band_run_grid(uint32_t nt, uint32_t wpe);
 uint32_t vtxk_band_run_lanes(void);
-hipError_t vtxk_launch_band_pending(const uint32_t* pending, uint32_t n_pending, const uint32_t* pend_buf,
-                                    int32_t* ref_score, int32_t* alt_score, uint16_t* band, uint32_t band_stride,
-                                    uint32_t* hard_list, uint32_t* counters, hipStream_t s);
+// (out: band_run_kernel's; the kernel lists nothing in overflow_list)
+hipError_t vtxk_launch_band_pending(const vtx_task_arrays& a, const uint32_t* pending, uint32_t n_pending, const uint32_t* pend_buf, const vtx_band_out& out, hipStream_t s);
 uint32_t vtxk_band_poly_stride(void);
-hipError_t vtxk_launch_band_expand(const uint32_t* hard_list, uint32_t n_hard, const vtx_record* records,
-                                   const uint32_t* rec_locus, const vtx_locus* loci, const uint16_t* src,
-                                   uint32_t src_stride, uint16_t* band, uint32_t band_stride, hipStream_t s);
+hipError_t vtxk_launch_band_expand(const vtx_task_arrays& a, const uint32_t* hard_list, uint32_t n_hard, const uint16_t* src, uint32_t src_stride, uint16_t* band,
+                                   uint32_t band_stride, hipStream_t s);
 /* Records the fast kernels hold: reads up to VTX_FAST_READ_LEN bases (16 rows x 64 lanes), haplotypes up to
  * VTX_FAST_HAP_LEN (LDS tables).  Longer ones take slow_align_kernel (exact, one lane per alignment, global scratch). */
 #define VTX_FAST_READ_LEN 1024u
 #define VTX_FAST_HAP_LEN 2400u
 size_t vtxk_slow_ws_stride(uint32_t m_cap, uint32_t max_hap, uint32_t max_read);
-hipError_t vtxk_launch_slow_align(const uint32_t* recs, const uint32_t* tasks, uint32_t n_tasks, int banded,
-                                  const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci,
-                                  const uint8_t* read_arena, const uint8_t* hap_arena, uint8_t* workspace, uint64_t ws_stride,
-                                  uint32_t m_cap, uint32_t max_hap, uint32_t max_read, int32_t* ref_score, int32_t* alt_score,
-                                  uint32_t* retry_list, uint32_t* counters, hipStream_t s);
+hipError_t vtxk_launch_slow_align(const vtx_task_arrays& a, const uint32_t* recs, const uint32_t* tasks, uint32_t n_tasks, int banded, uint8_t* workspace,
+                                  uint64_t ws_stride, uint32_t m_cap, uint32_t max_hap, uint32_t max_read, uint32_t* retry_list, uint32_t* counters, hipStream_t s);
 hipError_t vtxk_values_from_counts(const uint32_t* alt, const uint32_t* ref, const uint32_t* unk, uint32_t n, int mode,
                                    double* o_val, double* o_refval, hipStream_t s);
 hipError_t vtxk_group_heads(const vtx_record* records, const uint32_t* rec_locus, uint32_t n, uint32_t* head_cell,

@@ -214,11 +214,8 @@ __global__ __launch_bounds__(256) void sw_full_kernel(
     const uint8_t*, int32_t*, int32_t*, uint32_t);
 INST(2, 16) INST(4, 16) INST(6, 16) INST(8, 16) INST(10, 16) INST(12, 16) INST(16, 16) INST(8, 64) INST(16, 64)
 
-extern "C" hipError_t vtxk_launch_sw_full(int R, int GL, uint32_t n_work, const uint32_t* work,
-                                          const vtx_record* records, const uint32_t* rec_locus,
-                                          const vtx_locus* loci, const uint8_t* read_arena,
-                                          const uint8_t* hap_arena, int32_t* ref_score, int32_t* alt_score,
-                                          uint32_t max_hap_len, hipStream_t stream) {
+extern "C" hipError_t vtxk_launch_sw_full(const vtx_task_arrays& a, int R, int GL, uint32_t n_work, const uint32_t* work, uint32_t max_hap_len,
+                                          hipStream_t stream) {
     if (n_work == 0) return hipSuccess;
     const uint32_t groups = 256 / GL;
     // slot stride = 16 (mod 32) words: the two 16-lane records of a 32-lane LDS group hit disjoint banks
@@ -232,8 +229,8 @@ extern "C" hipError_t vtxk_launch_sw_full(int R, int GL, uint32_t n_work, const 
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
             if (e != hipSuccess) return e;                                                              \
         }                                                                                               \
-        hipLaunchKernelGGL((sw_full_kernel<r, gl>), grid, block, shmem, stream, work, n_work, records,  \
-                           rec_locus, loci, read_arena, hap_arena, ref_score, alt_score, lcols);        \
+        hipLaunchKernelGGL((sw_full_kernel<r, gl>), grid, block, shmem, stream, work, n_work, a.records, \
+                           a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, lcols);                    \
         return hipGetLastError();                                                                       \
     }
     CASE(2, 16) CASE(4, 16) CASE(6, 16) CASE(8, 16) CASE(10, 16) CASE(12, 16) CASE(16, 16) CASE(8, 64) CASE(16, 64)
@@ -710,12 +707,9 @@ __global__ __launch_bounds__(256) void sw_banded_kernel(
     }
 }
 
-static hipError_t launch_sw_pairs(int mode, int R, int GL, uint32_t n_hard, const uint32_t* hard, const uint32_t* n_dev,
-                                  const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci,
-                                  const uint8_t* read_arena, const uint8_t* hap_arena, const uint16_t* band,
-                                  uint32_t band_stride, int32_t* ref_score, int32_t* alt_score, uint32_t max_hap_len,
-                                  uint32_t* recheck_list, uint32_t* recheck_count, uint8_t* stage, const uint32_t* packs,
-                                  uint32_t* recheck_pack, hipStream_t stream) {
+static hipError_t launch_sw_pairs(const vtx_task_arrays& a, int mode, int R, int GL, uint32_t n_hard, const uint32_t* hard, const uint32_t* n_dev,
+                                  const uint16_t* band, uint32_t band_stride, uint32_t max_hap_len, uint32_t* recheck_list, uint32_t* recheck_count,
+                                  uint8_t* stage, const uint32_t* packs, uint32_t* recheck_pack, hipStream_t stream) {
     if (n_hard == 0) return hipSuccess;
     const uint32_t pairs = (n_hard + 1) / 2;
     const uint32_t lcols = ((GL + max_hap_len + GL + 8) + 3u) & ~3u;
@@ -735,8 +729,8 @@ static hipError_t launch_sw_pairs(int mode, int R, int GL, uint32_t n_hard, cons
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);   \
             if (e != hipSuccess) return e;                                                                \
         }                                                                                                 \
-        hipLaunchKernelGGL((sw_banded_kernel<r, gl, f>), grid, block, shmem, stream, hard, n_hard, n_dev, records, \
-                           rec_locus, loci, read_arena, hap_arena, band, band_stride, ref_score, alt_score, lcols, \
+        hipLaunchKernelGGL((sw_banded_kernel<r, gl, f>), grid, block, shmem, stream, hard, n_hard, n_dev, a.records, \
+                           a.rec_locus, a.loci, a.read, a.hap, band, band_stride, a.ref, a.alt, lcols,    \
                            recheck_list, recheck_count, stage, packs, recheck_pack);                      \
         return hipGetLastError();                                                                         \
     }
@@ -747,40 +741,25 @@ static hipError_t launch_sw_pairs(int mode, int R, int GL, uint32_t n_hard, cons
     return hipErrorInvalidValue;
 }
 
-extern "C" hipError_t vtxk_launch_sw_banded(int R, int GL, uint32_t n_hard, const uint32_t* hard,
-                                            const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci,
-                                            const uint8_t* read_arena, const uint8_t* hap_arena, const uint16_t* band,
-                                            uint32_t band_stride, int32_t* ref_score, int32_t* alt_score,
-                                            uint32_t max_hap_len, hipStream_t stream) {
-    return launch_sw_pairs(0, R, GL, n_hard, hard, nullptr, records, rec_locus, loci, read_arena, hap_arena, band, band_stride,
-                           ref_score, alt_score, max_hap_len, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+extern "C" hipError_t vtxk_launch_sw_banded(const vtx_task_arrays& a, int R, int GL, uint32_t n_hard, const uint32_t* hard, const uint16_t* band,
+                                            uint32_t band_stride, uint32_t max_hap_len, hipStream_t stream) {
+    return launch_sw_pairs(a, 0, R, GL, n_hard, hard, nullptr, band, band_stride, max_hap_len, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 // the masked DP over a list whose length lives on the device (n_dev; n_cap bounds the grid)
-extern "C" hipError_t vtxk_launch_sw_banded_dev(int R, int GL, uint32_t n_cap, const uint32_t* hard, const uint32_t* n_dev,
-                                                const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci,
-                                                const uint8_t* read_arena, const uint8_t* hap_arena, const uint16_t* band,
-                                                uint32_t band_stride, int32_t* ref_score, int32_t* alt_score,
-                                                uint32_t max_hap_len, hipStream_t stream) {
-    return launch_sw_pairs(0, R, GL, n_cap, hard, n_dev, records, rec_locus, loci, read_arena, hap_arena, band, band_stride,
-                           ref_score, alt_score, max_hap_len, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+extern "C" hipError_t vtxk_launch_sw_banded_dev(const vtx_task_arrays& a, int R, int GL, uint32_t n_cap, const uint32_t* hard, const uint32_t* n_dev,
+                                                const uint16_t* band, uint32_t band_stride, uint32_t max_hap_len, hipStream_t stream) {
+    return launch_sw_pairs(a, 0, R, GL, n_cap, hard, n_dev, band, band_stride, max_hap_len, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 // the masked DP over tasks whose band is one diagonal stretch (packs[i] = vtxf::band_pack of list[i]); stage: VTX_STAGE_DIAG_DP
-extern "C" hipError_t vtxk_launch_sw_diag_band(int R, int GL, uint32_t n_cap, const uint32_t* list, const uint32_t* packs,
-                                               const uint32_t* n_dev, const vtx_record* records, const uint32_t* rec_locus,
-                                               const vtx_locus* loci, const uint8_t* read_arena, const uint8_t* hap_arena,
-                                               int32_t* ref_score, int32_t* alt_score, uint32_t max_hap_len, uint8_t* stage,
-                                               hipStream_t stream) {
-    return launch_sw_pairs(2, R, GL, n_cap, list, n_dev, records, rec_locus, loci, read_arena, hap_arena, nullptr, 0,
-                           ref_score, alt_score, max_hap_len, nullptr, nullptr, stage, packs, nullptr, stream);
+extern "C" hipError_t vtxk_launch_sw_diag_band(const vtx_task_arrays& a, int R, int GL, uint32_t n_cap, const uint32_t* list, const uint32_t* packs,
+                                               const uint32_t* n_dev, uint32_t max_hap_len, uint8_t* stage, hipStream_t stream) {
+    return launch_sw_pairs(a, 2, R, GL, n_cap, list, n_dev, nullptr, 0, max_hap_len, nullptr, nullptr, stage, packs, nullptr, stream);
 }
 // full-matrix CHECK of provisional scores (see the kernel): tasks whose full score differs go to recheck_list / recheck_pack
-extern "C" hipError_t vtxk_launch_sw_check(int R, int GL, uint32_t n_cap, const uint32_t* list, const uint32_t* packs, const uint32_t* n_dev,
-                                           const vtx_record* records, const uint32_t* rec_locus, const vtx_locus* loci,
-                                           const uint8_t* read_arena, const uint8_t* hap_arena, int32_t* ref_score,
-                                           int32_t* alt_score, uint32_t max_hap_len, uint32_t* recheck_list, uint32_t* recheck_pack,
+extern "C" hipError_t vtxk_launch_sw_check(const vtx_task_arrays& a, int R, int GL, uint32_t n_cap, const uint32_t* list, const uint32_t* packs,
+                                           const uint32_t* n_dev, uint32_t max_hap_len, uint32_t* recheck_list, uint32_t* recheck_pack,
                                            uint32_t* recheck_count, uint8_t* stage, hipStream_t stream) {
-    return launch_sw_pairs(1, R, GL, n_cap, list, n_dev, records, rec_locus, loci, read_arena, hap_arena, nullptr, 0,
-                           ref_score, alt_score, max_hap_len, recheck_list, recheck_count, stage, packs, recheck_pack, stream);
+    return launch_sw_pairs(a, 1, R, GL, n_cap, list, n_dev, nullptr, 0, max_hap_len, recheck_list, recheck_count, stage, packs, recheck_pack, stream);
 }
 
 __global__ void fill_i32_kernel(int32_t* __restrict__ p, uint32_t n, int32_t v) {
@@ -1266,11 +1245,8 @@ __global__ __launch_bounds__(256) void sw_full_duo_kernel(
     }
 }
 
-extern "C" hipError_t vtxk_launch_sw_full_duo(int R, uint32_t n_work, const uint32_t* work, const vtx_record* records,
-                                              const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                              const uint8_t* hap_arena, int32_t* ref_score, int32_t* alt_score,
-                                              uint32_t max_hap_len, uint32_t loci_cap, uint32_t* redo, uint32_t* redo_count,
-                                              uint32_t pair_cols, hipStream_t stream) {
+extern "C" hipError_t vtxk_launch_sw_full_duo(const vtx_task_arrays& a, int R, uint32_t n_work, const uint32_t* work, uint32_t max_hap_len, uint32_t loci_cap,
+                                              uint32_t* redo, uint32_t* redo_count, uint32_t pair_cols, hipStream_t stream) {
     if (n_work == 0) return hipSuccess;
     // columns: PRE sentinels + haplotype (at least 16) + lane skew + 4x unroll slack
     const uint32_t lcols = 16 + (max_hap_len > 16 ? max_hap_len : 16) + 16 + 4;
@@ -1285,8 +1261,8 @@ extern "C" hipError_t vtxk_launch_sw_full_duo(int R, uint32_t n_work, const uint
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);  \
             if (e != hipSuccess) return e;                                                               \
         }                                                                                                \
-        hipLaunchKernelGGL((sw_full_duo_kernel<r>), grid, block, shmem, stream, work, n_work, records,   \
-                           rec_locus, loci, read_arena, hap_arena, ref_score, alt_score, lcols, loci_cap, redo, redo_count, pair_cols); \
+        hipLaunchKernelGGL((sw_full_duo_kernel<r>), grid, block, shmem, stream, work, n_work, a.records, \
+                           a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, lcols, loci_cap, redo, redo_count, pair_cols); \
         return hipGetLastError();                                                                        \
     }
     CASE(2) CASE(4) CASE(6) CASE(8) CASE(10) CASE(12) CASE(16)
@@ -1294,11 +1270,8 @@ extern "C" hipError_t vtxk_launch_sw_full_duo(int R, uint32_t n_work, const uint
     return hipErrorInvalidValue;
 }
 
-extern "C" hipError_t vtxk_launch_sw_full_lut(int R, uint32_t n_work, const uint32_t* work, const vtx_record* records,
-                                              const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                              const uint8_t* hap_arena, int32_t* ref_score, int32_t* alt_score,
-                                              uint32_t max_hap_len, uint32_t loci_cap, uint32_t* redo, uint32_t* redo_count,
-                                              hipStream_t stream) {
+extern "C" hipError_t vtxk_launch_sw_full_lut(const vtx_task_arrays& a, int R, uint32_t n_work, const uint32_t* work, uint32_t max_hap_len, uint32_t loci_cap,
+                                              uint32_t* redo, uint32_t* redo_count, hipStream_t stream) {
     if (n_work == 0) return hipSuccess;
     // columns: PRE sentinels + haplotype + (GL - 1 + 3) trailing steps (4x unrolled loop) + 1
     const uint32_t lcols = 16 + max_hap_len + 16 + 4;
@@ -1311,8 +1284,8 @@ extern "C" hipError_t vtxk_launch_sw_full_lut(int R, uint32_t n_work, const uint
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);  \
             if (e != hipSuccess) return e;                                                               \
         }                                                                                                \
-        hipLaunchKernelGGL((sw_full_lut_kernel<r>), grid, block, shmem, stream, work, n_work, records,   \
-                           rec_locus, loci, read_arena, hap_arena, ref_score, alt_score, lcols, loci_cap, redo, redo_count); \
+        hipLaunchKernelGGL((sw_full_lut_kernel<r>), grid, block, shmem, stream, work, n_work, a.records, \
+                           a.rec_locus, a.loci, a.read, a.hap, a.ref, a.alt, lcols, loci_cap, redo, redo_count); \
         return hipGetLastError();                                                                        \
     }
     CASE(2) CASE(4) CASE(6) CASE(8) CASE(10) CASE(12) CASE(16)

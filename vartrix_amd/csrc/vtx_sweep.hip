@@ -573,17 +573,13 @@ extern "C" uint32_t vtxk_band_sweep_grid(uint32_t n_tasks) {
 // the log slices of the largest grid (one buffer for the life of the context)
 extern "C" size_t vtxk_band_sweep_log_bytes(void) { return (size_t)GRID_MAX * 8 * LOGCAP * sizeof(uint32_t); }
 
-extern "C" hipError_t vtxk_launch_band_sweep(const uint32_t* tasks, uint32_t n_tasks, const uint32_t* n_dev,
-                                             const vtx_record* records,
-                                             const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                             const uint8_t* hap_arena, uint16_t* band, uint32_t band_stride, uint32_t* hard_list,
-                                             uint32_t* overflow_list, uint32_t* counters, uint32_t* stat_counters, uint8_t* stage,
-                                             uint32_t* dbg, uint32_t* glog, hipStream_t s) {
+extern "C" hipError_t vtxk_launch_band_sweep(const vtx_task_arrays& a, const uint32_t* tasks, uint32_t n_tasks, const uint32_t* n_dev, const vtx_band_out& out,
+                                             uint32_t* stat_counters, uint8_t* stage, uint32_t* dbg, uint32_t* glog, hipStream_t s) {
     if (!n_tasks) return hipSuccess;
     static const uint32_t ablate = VTX_DEV_ENV("VTX_SWEEP_ABLATE") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_SWEEP_ABLATE")) << 8 : 0u;
     const size_t shmem = (size_t)8 * TASK_W * sizeof(uint32_t);
-    hipLaunchKernelGGL(band_sweep_kernel, dim3(vtxk_band_sweep_grid(n_tasks)), dim3(64), shmem, s, tasks, n_tasks, n_dev, records,
-                       rec_locus, loci, read_arena, hap_arena, band, band_stride, hard_list, overflow_list, counters,
+    hipLaunchKernelGGL(band_sweep_kernel, dim3(vtxk_band_sweep_grid(n_tasks)), dim3(64), shmem, s, tasks, n_tasks, n_dev, a.records,
+                       a.rec_locus, a.loci, a.read, a.hap, out.band, out.band_stride, out.hard_list, out.overflow_list, out.counters,
                        ablate, stat_counters, stage, dbg, glog);
     return hipGetLastError();
 }

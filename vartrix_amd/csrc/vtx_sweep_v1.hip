@@ -507,12 +507,8 @@ __global__ __launch_bounds__(64) void band_sweep_v1_kernel(
 
 // tier 0: 256 sections per task (first pass: 4.8 KB of LDS per task, still four wavefronts per CU); tier 1: 1024 (second pass over
 // the first's log overflows: 7.9 KB per task, two wavefronts per CU)
-extern "C" hipError_t vtxk_launch_band_sweep_v1(int tier, const uint32_t* tasks, uint32_t n_tasks, const uint32_t* n_dev,
-                                             const vtx_record* records,
-                                             const uint32_t* rec_locus, const vtx_locus* loci, const uint8_t* read_arena,
-                                             const uint8_t* hap_arena, uint16_t* band, uint32_t band_stride, uint32_t* hard_list,
-                                             uint32_t* overflow_list, uint32_t* counters, uint32_t* stat_counters, uint8_t* stage,
-                                             uint32_t* dbg, hipStream_t s) {
+extern "C" hipError_t vtxk_launch_band_sweep_v1(const vtx_task_arrays& a, int tier, const uint32_t* tasks, uint32_t n_tasks, const uint32_t* n_dev,
+                                                const vtx_band_out& out, uint32_t* stat_counters, uint8_t* stage, uint32_t* dbg, hipStream_t s) {
     if (!n_tasks) return hipSuccess;
     static const uint32_t ablate = VTX_DEV_ENV("VTX_SWEEP_ABLATE") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_SWEEP_ABLATE")) << 8 : 0u;
 #define LAUNCH_SWEEP(CAP)                                                                                          \
@@ -523,9 +519,9 @@ extern "C" hipError_t vtxk_launch_band_sweep_v1(int tier, const uint32_t* tasks,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);           \
             if (e != hipSuccess) return e;                                                                         \
         }                                                                                                          \
-        hipLaunchKernelGGL(band_sweep_v1_kernel<CAP>, dim3((n_tasks + 7) / 8), dim3(64), shmem, s, tasks, n_tasks, n_dev, records, \
-                           rec_locus, loci, read_arena, hap_arena, band, band_stride, hard_list, overflow_list, counters,      \
-                           ablate, stat_counters, stage, dbg);                                                     \
+        hipLaunchKernelGGL(band_sweep_v1_kernel<CAP>, dim3((n_tasks + 7) / 8), dim3(64), shmem, s, tasks, n_tasks, n_dev, a.records, \
+                           a.rec_locus, a.loci, a.read, a.hap, out.band, out.band_stride, out.hard_list, out.overflow_list,       \
+                           out.counters, ablate, stat_counters, stage, dbg);                                       \
     }
     if (tier == 0) LAUNCH_SWEEP(256) else LAUNCH_SWEEP(1024)
 #undef LAUNCH_SWEEP
