@@ -584,11 +584,42 @@ int vtx_csr_select(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t nn
                    const void* const* d_payload_in, void* const* d_payload_out,
                    const uint32_t* payload_elem_bytes, uint32_t n_payload);
 
+/* ---- pseudobulk: the CSR summed per group of columns (vartrix_amd/csrc/vtx_csr_group.hip) ----------------------------------------------
+ * The step after the statistics and the filter: with a label per column (per cell: its cluster, donor, clone, sample) the n_major x
+ * n_minor matrix folds into n_major x n_groups.  d_group[n_minor] holds a group number < n_groups per column, or VTX_GROUP_NONE for a
+ * column that belongs to no group: its entries are left out.  The result is a CSR with one entry per (row, group) pair that has at
+ * least one source entry, group numbers ascending inside a row; each entry carries the seven numbers of vtx_csr_stats over the source
+ * entries of that row whose column has that label (so n_alt is the number of cells of the group with alt support, sum_alt their alt
+ * count).  vtx_csr_stats is the output struct, its arrays nnz_out long; any pointer may be NULL and is then not written.
+ * Like vtx_csr_select these work on ANY CSR in caller-owned DEVICE memory (rows in any order inside, duplicate indices allowed), need
+ * a context but no run, are synchronous on the context's stream, and check their inputs on the device BEFORE anything is written: the
+ * CSR as above, then the labels: every d_group[j] must be < n_groups or == VTX_GROUP_NONE.  A violation returns VTX_E_INVAL (the reason
+ * in vtx_strerror; for a label it names the lowest offending column), no output byte is written and the context stays usable.
+ * VTX_E_INVAL also for n_groups == 0 and a null array that is needed; VTX_E_UNSUPPORTED for nnz >= 2^32 and for n_groups >
+ * vtx_csr_group_max().  vtx_csr_group_plan reports nnz_out: the caller allocates d_indptr_out[n_major + 1], d_indices_out[nnz_out] and
+ * the arrays of `out`, and passes nnz_out back.  vtx_csr_group_sum is STATELESS: it recounts, and if its own nnz_out differs from the
+ * one passed in it returns VTX_E_INVAL and writes no output byte.  Outputs must not overlap inputs.
+ * One wavefront folds a row in a tile of vtx_csr_group_window() groups in LDS; with more groups it repeats the row once per window
+ * (correct, and need not be fast), which vtx_csr_group_max() = 256 windows bounds.  Integer additions only: the result is a function
+ * of the input alone.  Work space (stays with the context): 4 (n_major + 1) bytes of counts plus the scan's own.                       */
+#define VTX_GROUP_NONE 0xFFFFFFFFu     /* a column that belongs to no group: its entries are left out */
+uint32_t vtx_csr_group_window(void);   /* W: groups one pass holds in LDS */
+uint32_t vtx_csr_group_max(void);      /* the largest n_groups accepted */
+int vtx_csr_group_plan(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
+                       const uint64_t* d_indptr, const uint32_t* d_indices,
+                       const uint32_t* d_group, uint32_t n_groups, uint64_t* nnz_out);
+int vtx_csr_group_sum(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
+                      const uint64_t* d_indptr, const uint32_t* d_indices,
+                      const uint32_t* d_alt, const uint32_t* d_ref, const uint32_t* d_unk,
+                      const uint32_t* d_group, uint32_t n_groups, uint64_t nnz_out,
+                      uint64_t* d_indptr_out, uint32_t* d_indices_out, const vtx_csr_stats* out);
+
 /* Device time of the context's last CSR call that succeeded, in milliseconds, from events on the context's own stream.
  * vtx_device_csr / vtx_csr_transpose: ms[0] the check of the inputs, ms[1] the sort of the positions by column, ms[2] the offsets,
  * ms[3] the placement of the indices and payloads (vtx_device_csr: 1 and 3 are 0).  vtx_csr_row_stats: ms[0] the check, ms[3] the
  * reduction (1 and 2 are 0).  vtx_csr_select_plan / vtx_csr_select: ms[0] the check, ms[1] the scans, ms[2] the offsets and ids, ms[3]
- * the placement (the plan: 2 and 3 are 0).  Writes the first n of the four, at most four.                                            */
+ * the placement (the plan: 2 and 3 are 0).  vtx_csr_group_plan / vtx_csr_group_sum: ms[0] the checks of the CSR and of the labels,
+ * ms[1] the count and its scan, ms[3] the fill (2 is 0; the plan: 3 is 0 too).  Writes the first n of the four, at most four.         */
 int vtx_last_csr_ms(vtx_ctx* ctx, float* ms, uint32_t n);
 
 /* ---- Multi-GPU: one process (one ctx) per GPU, loci sharded over the ranks (src/main.rs:284-291: chunks of loci

@@ -19,7 +19,14 @@ which operations this torch build offers on a sparse CSR tensor.
 --sweep times the statistics kernel at every group size G (the developer library's VTX_CSR_STATS_G, so VTX_LIB_VARIANT=dev) on synthetic
 CSRs of three shapes — config 3 variant-major and cell-major, and four reads per locus — next to the G the rule picks; no batch is run.
 GPU box:   python tools/csr_profile.py --ops --json profiles/r13_csr_ops.json
-           VTX_LIB_VARIANT=dev python tools/csr_profile.py --sweep --json profiles/r13_csr_ops.json     (joins the record above)"""
+           VTX_LIB_VARIANT=dev python tools/csr_profile.py --sweep --json profiles/r13_csr_ops.json     (joins the record above)
+
+--group measures the pseudobulk fold (vtx_csr_group_plan + vtx_csr_group_sum) on synthetic CSRs of config 3's shape in both orientations
+(Poisson row lengths, uniform random columns and labels; no batch is run) at n_groups = 8, 64, W and 4 W, each result compared with a
+numpy model before it is timed, next to (a) vtx_csr_row_stats on the same CSR — the floor: the same bytes without the gather —, (b) torch
+on the device (rows by repeat_interleave, key = row * n_groups + label, seven index_add_ into a dense buffer) and (c) the host (the
+arrays copied out, scipy A @ one-hot).
+GPU box:   python tools/csr_profile.py --group --json profiles/r14_csr_group.json"""
 import argparse
 import json
 import os
@@ -48,6 +55,7 @@ ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--skip-mmread", action="store_true", help="leave out the Matrix-Market round trip (minutes of parsing at config-3 size)")
 ap.add_argument("--ops", action="store_true", help="measure vtx_csr_row_stats / vtx_csr_select instead of the hand-over")
 ap.add_argument("--sweep", action="store_true", help="time csr_row_stats_kernel at every group size (developer library), no batch")
+ap.add_argument("--group", action="store_true", help="measure vtx_csr_group_plan / vtx_csr_group_sum on synthetic CSRs, no batch")
 args = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -156,6 +164,98 @@ if args.sweep:
             os.environ.pop("VTX_CSR_STATS_G", None)
             res["shapes"][name] = one
             del csr, out
+    finish(res)
+    sys.exit(0)
+
+if args.group:
+    from vartrix_amd import abi
+    W = lib.load().vtx_csr_group_window()
+    shapes = {"config3_variant_major": (args.loci, args.barcodes, 239.23), "config3_cell_major": (args.barcodes, args.loci, 2392.3)}
+    res = {"what": "vtx_csr_group_plan + vtx_csr_group_sum (tools/csr_profile.py --group): median of %d after one warm-up, one process; synthetic "
+                   "CSRs with Poisson row lengths, uniform random columns and labels; device ms by phase from vtx_last_csr_ms" % args.runs,
+           "window": W, "group_max": lib.load().vtx_csr_group_max(), "shapes": {}}
+    gen = torch.Generator(device=dev).manual_seed(11)
+
+    def model(indptr, indices, counts, label, n_groups):
+        """numpy: the kept entries sorted by (row, group), add.reduceat in uint64 -> (offsets, groups, the seven arrays)."""
+        rows = np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr))
+        key = rows * n_groups + label[indices]
+        order = np.argsort(key, kind="stable")
+        key = key[order]
+        starts = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]]))
+        a, r, u = (c[order] for c in counts)
+        cols = [np.ones(len(key), np.uint64), a > 0, r > 0, (a > 0) & (r > 0), a, r, u]
+        return (np.searchsorted(key[starts] // n_groups, np.arange(len(indptr))), key[starts] % n_groups,
+                [np.add.reduceat(c.astype(np.uint64), starts) for c in cols])
+
+    with lib.Context(default_config(n_barcodes=4)) as ctx:
+        for name, (n_major, n_minor, mean) in shapes.items():
+            lens = torch.poisson(torch.full((n_major,), mean, device=dev), generator=gen).clamp_(max=n_minor).to(torch.int64)
+            indptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(lens, 0)])
+            nnz = int(indptr[-1])
+            csr = {"indptr": indptr, "indices": torch.randint(0, n_minor, (nnz,), dtype=torch.int32, device=dev, generator=gen)}
+            for k in ("alt", "ref", "unk"):
+                csr[k] = torch.randint(0, 3, (nnz,), dtype=torch.int32, device=dev, generator=gen)
+            host = {k: v.cpu().numpy() for k, v in csr.items()}
+            one = {"n_major": n_major, "n_minor": n_minor, "nnz": nnz, "n_groups": {}}
+            floor_out = stats_buffers(n_major)
+            one["row_stats_floor"] = series(stats_call(ctx, csr, n_major, n_minor, floor_out), ctx.csr_ms)
+            head = (n_major, n_minor, nnz, csr["indptr"].data_ptr(), csr["indices"].data_ptr())
+            for n_groups in (8, 64, W, 4 * W):
+                label = torch.randint(0, n_groups, (n_minor,), dtype=torch.int32, device=dev, generator=gen)
+                torch.cuda.synchronize(dev)
+                n_out = ctx.csr_group_plan(*head, label.data_ptr(), n_groups)
+                out = {"indptr": torch.empty(n_major + 1, dtype=torch.int64, device=dev), "indices": torch.empty(n_out, dtype=torch.int32, device=dev)}
+                out.update(stats_buffers(n_out))
+                torch.cuda.synchronize(dev)
+
+                def sum_call():
+                    return ctx.csr_group_sum(*head, csr["alt"].data_ptr(), csr["ref"].data_ptr(), csr["unk"].data_ptr(), label.data_ptr(), n_groups, n_out,
+                                             out["indptr"].data_ptr(), out["indices"].data_ptr(), {k: out[k].data_ptr() for k in abi.CSR_STAT_NAMES})
+                sum_call()
+                # ---- correctness first ----
+                w_ptr, w_idx, w_cols = model(host["indptr"], host["indices"], [host[k] for k in ("alt", "ref", "unk")], label.cpu().numpy().astype(np.int64), n_groups)
+                assert n_out == len(w_idx) and np.array_equal(out["indptr"].cpu().numpy(), w_ptr) and np.array_equal(out["indices"].cpu().numpy(), w_idx)
+                same_stats(out, dict(zip(abi.CSR_STAT_NAMES, w_cols)))
+                print("%s n_groups %d: equals the numpy model, %d entries" % (name, n_groups, n_out), flush=True)
+                E = {"nnz_out": n_out}
+                E["group_plan"] = series(lambda: ctx.csr_group_plan(*head, label.data_ptr(), n_groups), ctx.csr_ms)
+                E["group_sum"] = series(sum_call, ctx.csr_ms)
+
+                def torch_fold():
+                    rows = torch.repeat_interleave(torch.arange(n_major, device=dev), csr["indptr"][1:] - csr["indptr"][:-1])
+                    key = rows * n_groups + label[csr["indices"].to(torch.int64)].to(torch.int64)
+                    a, r, u = csr["alt"], csr["ref"], csr["unk"]
+                    o = [torch.zeros(n_major * n_groups, dtype=torch.int64, device=dev).index_add_(0, key, w.to(torch.int64))
+                         for w in (torch.ones_like(a), a > 0, r > 0, (a > 0) & (r > 0), a, r, u)]
+                    torch.cuda.synchronize(dev)
+                    return o
+
+                def host_fold():
+                    h = {k: v.cpu().numpy() for k, v in csr.items()}
+                    lab = label.cpu().numpy().astype(np.int64)
+                    onehot = sp.csr_matrix((np.ones(n_minor, np.int64), (np.arange(n_minor), lab)), shape=(n_minor, n_groups))
+                    mats = [sp.csr_matrix((d.astype(np.int64), h["indices"], h["indptr"]), shape=(n_major, n_minor))
+                            for d in (np.ones(nnz), h["alt"] > 0, h["ref"] > 0, (h["alt"] > 0) & (h["ref"] > 0), h["alt"], h["ref"], h["unk"])]
+                    return [m @ onehot for m in mats]
+                try:
+                    dense = torch_fold()
+                    rows_out = torch.repeat_interleave(torch.arange(n_major, device=dev), out["indptr"][1:] - out["indptr"][:-1])
+                    at = rows_out * n_groups + out["indices"].to(torch.int64)
+                    for d, k in zip(dense, abi.CSR_STAT_NAMES):
+                        assert torch.equal(d[at], out[k].to(torch.int64) & (0xFFFFFFFF if k in abi.CSR_STAT_COUNTS else -1)), k
+                    del dense, rows_out, at
+                    E["torch_index_add_dense"] = series(torch_fold)
+                except Exception as e:                           # noqa: BLE001  (the record IS the error)
+                    E["torch_index_add_dense"] = {"error": "%s: %s" % (type(e).__name__, str(e).splitlines()[0][:200] if str(e) else "")}
+                if n_groups == W:                                # the host does not care much how many groups there are: one point
+                    E["host_copy_scipy_onehot"] = series(host_fold)
+                one["n_groups"][str(n_groups)] = E
+                print(name, n_groups, "plan", E["group_plan"]["device_ms_by_phase_median"], "sum", E["group_sum"]["device_ms_by_phase_median"],
+                      "torch", E["torch_index_add_dense"].get("host_wall_ms_median"), flush=True)
+                del out, label
+            res["shapes"][name] = one
+            del csr, host, floor_out
     finish(res)
     sys.exit(0)
 

@@ -130,6 +130,9 @@ CSR_STAT_SUMS = ("sum_alt", "sum_ref", "sum_unk")                   # uint64 per
 CSR_STAT_NAMES = CSR_STAT_COUNTS + CSR_STAT_SUMS
 
 
+VTX_GROUP_NONE = 0xFFFFFFFF          # vtx_csr_group_*: the label of a column that belongs to no group
+
+
 class VtxCsrStats(C.Structure):
     """vtx_csr_stats: where vtx_csr_row_stats stores the seven statistics of every row; a NULL pointer is not written."""
     _fields_ = [(k, C.POINTER(C.c_uint32)) for k in CSR_STAT_COUNTS] + [(k, C.POINTER(C.c_uint64)) for k in CSR_STAT_SUMS]

@@ -12,11 +12,18 @@ is one stable transpose of the stacked whole (``vtx_csr_transpose``).  Every arr
 filter of the demultiplexers: ``vtx_csr_row_stats`` + ``vtx_csr_select`` on the stacked CSR), and ``select()`` cuts a finished result
 down by boolean masks.
 
+``pseudobulk()`` folds a result into variants x groups by a label per cell (cluster, donor, clone, sample): per (variant, group) the alt /
+ref / unknown counts summed over the cells of the group and the number of its cells that support each allele (``vtx_csr_group_plan`` +
+``vtx_csr_group_sum`` on the device for a torch result, scipy on the host for a scipy one); ``run(groups=)`` does it on the stacked CSR
+of the run, and ``read_groups()`` reads the labels from a two-column file such as cellranger's ``clusters.csv``.
+
 There is no CPU path: the scores, the calls, the offsets and the transpose are computed on the GPU; torch carries the device arrays
 (``__cuda_array_interface__``) and, for ``to="scipy"``, copies the finished arrays to the host.
 """
 from __future__ import annotations
 
+import gzip
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -42,6 +49,32 @@ class Result:
     cell_stats: dict = None       # ... per cell, of the matrix as returned
     variant_index: object = None  # the source row of every kept variant (int64); None when nothing was filtered
     orient: str = None            # "variants" or "cells": what the rows of the matrices are
+    groups: object = None         # run(groups=): the GroupResult of the matrix as returned (after the filter)
+
+
+@dataclass
+class GroupResult:
+    """A result folded by a label per cell: variants x groups (``orient="variants"``) or groups x variants (``"cells"``).  Every matrix
+    is int64 and has an entry where at least one cell of the group has an entry for the variant (a scipy result folded on the host:
+    where the number itself is not zero)."""
+    alt_counts: object        # the alt / ref / unknown counts summed over the cells of the group
+    ref_counts: object
+    unknown_counts: object
+    n_cells: object           # cells of the group with an entry for the variant
+    n_alt_cells: object       # ... with alt support (alt > 0), with ref support, with both (what consensus writes as 3)
+    n_ref_cells: object
+    n_both_cells: object
+    variants: list
+    groups: list              # the distinct labels at least one cell of the run has, sorted: as numbers if every one parses as an int
+    group_sizes: object       # cells per group, from the labels (numpy int64)
+    shape: tuple
+    orient: str
+    n_unmatched: int = 0      # keys of a dict of labels that are no barcode of the run
+
+
+# GroupResult field -> the statistic of vtx_csr_stats it is
+_GROUP_FIELDS = {"alt_counts": "sum_alt", "ref_counts": "sum_ref", "unknown_counts": "sum_unk", "n_cells": "n_entries",
+                 "n_alt_cells": "n_alt", "n_ref_cells": "n_ref", "n_both_cells": "n_both"}
 
 
 def _is_torch(a) -> bool:
@@ -153,6 +186,115 @@ def _select(ctx, torch, dev, csr, n_major, n_minor, keep_major=None, keep_minor=
     return out, major_ids, minor_ids
 
 
+def read_groups(path) -> dict:
+    """barcode -> label from a file of two columns, barcode then label: comma-separated for ``.csv`` / ``.csv.gz``, tab-separated
+    otherwise; ``.gz`` is read through gzip.  A first line whose first field is ``Barcode`` or ``barcode`` is a header (cellranger's
+    ``clusters.csv``).  Labels stay strings; empty lines are skipped."""
+    path = os.fspath(path)
+    name = path[:-3] if path.endswith(".gz") else path
+    sep = "," if name.endswith(".csv") else "\t"
+    out = {}
+    with (gzip.open(path, "rt") if path.endswith(".gz") else open(path, "rt")) as f:
+        for n, line in enumerate(f):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            fields = line.split(sep)
+            if len(fields) < 2:
+                raise ValueError("%s line %d: two columns, barcode and label, separated by %r" % (path, n + 1, sep))
+            if n == 0 and fields[0] in ("Barcode", "barcode"):
+                continue
+            out[fields[0]] = fields[1]
+    return out
+
+
+def _labels(groups, barcodes):
+    """The labels of the cells as numbers.  -> (uint32 per barcode: the position of its label in ``names``, abi.VTX_GROUP_NONE for a
+    cell that is left out; names: the sorted distinct labels; cells per group (int64); keys of a dict that are no barcode)."""
+    if isinstance(groups, (str, os.PathLike)):
+        groups = read_groups(groups)
+    n_unmatched = 0
+    if isinstance(groups, dict):
+        by_name = {(k.decode() if isinstance(k, bytes) else k): v for k, v in groups.items()}
+        n_unmatched = len(set(by_name) - set(barcodes))
+        per_cell = [by_name.get(b) for b in barcodes]
+    else:
+        per_cell = list(groups)
+        if len(per_cell) != len(barcodes):
+            raise ValueError("pseudobulk: %d labels for %d barcodes: one label per cell (None leaves the cell out)" % (len(per_cell), len(barcodes)))
+    names = list({g for g in per_cell if g is not None})
+    try:
+        names.sort(key=lambda g: (int(str(g)), str(g)))      # numbers, if every label is one
+    except ValueError:
+        names.sort(key=str)
+    number = {g: i for i, g in enumerate(names)}
+    labels = np.array([abi.VTX_GROUP_NONE if g is None else number[g] for g in per_cell], np.uint32).reshape(len(barcodes))
+    sizes = np.bincount(labels[labels != abi.VTX_GROUP_NONE].astype(np.int64), minlength=len(names)).astype(np.int64)
+    return labels, names, sizes, n_unmatched
+
+
+def _group_sum(ctx, torch, dev, csr, n_major, n_minor, labels, n_groups):
+    """A CSR with ``alt`` / ``ref`` / ``unk`` arrays summed per group of columns on the device: one plan, one sum.  -> the n_major x
+    n_groups CSR (``indptr``, ``indices`` and the seven arrays of ``abi.CSR_STAT_NAMES``, int64)."""
+    nnz = int(csr["indices"].shape[0])
+    src = {k: csr[k].contiguous() for k in ("indptr", "indices", "alt", "ref", "unk")}
+    group = torch.from_numpy(np.ascontiguousarray(labels, np.uint32).view(np.int32).copy()).to(dev)
+    torch.cuda.synchronize(dev)
+    head = (n_major, n_minor, nnz, src["indptr"].data_ptr(), src["indices"].data_ptr())
+    n_out = ctx.csr_group_plan(*head, group.data_ptr(), n_groups)
+    out = {"indptr": torch.empty(n_major + 1, dtype=torch.int64, device=dev), "indices": torch.empty(n_out, dtype=torch.int32, device=dev)}
+    raw = {k: torch.empty(n_out, dtype=torch.int32 if k in abi.CSR_STAT_COUNTS else torch.int64, device=dev) for k in abi.CSR_STAT_NAMES}
+    torch.cuda.synchronize(dev)
+    ctx.csr_group_sum(*head, src["alt"].data_ptr(), src["ref"].data_ptr(), src["unk"].data_ptr(), group.data_ptr(), n_groups, n_out,
+                      out["indptr"].data_ptr(), out["indices"].data_ptr(), {k: v.data_ptr() for k, v in raw.items()})
+    for k, v in raw.items():
+        out[k] = (v.to(torch.int64) & 0xFFFFFFFF) if k in abi.CSR_STAT_COUNTS else v
+    return out
+
+
+def _pseudobulk_device(ctx, torch, dev, csr, variants, barcodes, groups, orient, to):
+    """The fold of a VARIANT-major device CSR (``indptr``, ``indices``, ``alt``, ``ref``, ``unk``) as a GroupResult; ``orient="cells"``:
+    one more transpose, of the small result."""
+    labels, names, sizes, n_unmatched = _labels(groups, barcodes)
+    n_var, n_cell, n_groups = len(variants), len(barcodes), len(names)
+    shape = (n_var, n_groups) if orient == "variants" else (n_groups, n_var)
+    if not n_groups:                             # no cell has a label: nothing to sum, and the library takes no fold into 0 groups
+        out = {"indptr": torch.zeros(shape[0] + 1, dtype=torch.int64, device=dev), "indices": torch.zeros(0, dtype=torch.int32, device=dev)}
+        out.update({k: torch.zeros(0, dtype=torch.int64, device=dev) for k in abi.CSR_STAT_NAMES})
+    else:
+        out = _group_sum(ctx, torch, dev, csr, n_var, n_cell, labels, n_groups)
+        if orient == "cells":
+            out = _transpose(ctx, torch, dev, out, n_var, n_groups, abi.CSR_STAT_NAMES)
+    if to == "torch":
+        cols = out["indices"].to(torch.int64)
+        mats = {f: torch.sparse_csr_tensor(out["indptr"], cols, out[k], size=shape) for f, k in _GROUP_FIELDS.items()}
+    else:
+        import scipy.sparse as sp
+        indptr, cols = out["indptr"].cpu().numpy(), out["indices"].cpu().numpy()
+        mats = {f: sp.csr_matrix((out[k].cpu().numpy(), cols, indptr), shape=shape) for f, k in _GROUP_FIELDS.items()}
+    return GroupResult(**mats, variants=list(variants), groups=names, group_sizes=sizes, shape=shape, orient=orient, n_unmatched=n_unmatched)
+
+
+def _pseudobulk_host(result, groups, orient):
+    """The fold of a scipy result on the host: ``A @ one-hot`` for the sums, the same of ``A > 0`` for the support counts."""
+    import scipy.sparse as sp
+    labels, names, sizes, n_unmatched = _labels(groups, result.barcodes)
+    n_var, n_cell, n_groups = len(result.variants), len(result.barcodes), len(names)
+    cells = np.flatnonzero(labels != abi.VTX_GROUP_NONE)
+    onehot = sp.csr_matrix((np.ones(len(cells), np.int64), (cells, labels[cells].astype(np.int64))), shape=(n_cell, n_groups))
+
+    def fold(m):
+        m = sp.csr_matrix(m).astype(np.int64)
+        return sp.csr_matrix(m @ onehot if orient == "variants" else onehot.T @ m)
+    alt, ref, unk = (sp.csr_matrix(m) for m in (result.alt_counts, result.ref_counts, result.unknown_counts))
+    entries = sp.csr_matrix((np.ones(len(alt.data), np.int64), alt.indices, alt.indptr), shape=alt.shape)      # every stored entry, explicit zeros too
+    has_alt, has_ref = alt > 0, ref > 0
+    mats = dict(alt_counts=fold(alt), ref_counts=fold(ref), unknown_counts=fold(unk), n_cells=fold(entries), n_alt_cells=fold(has_alt),
+                n_ref_cells=fold(has_ref), n_both_cells=fold(has_alt.multiply(has_ref)))
+    shape = (n_var, n_groups) if orient == "variants" else (n_groups, n_var)
+    return GroupResult(**mats, variants=list(result.variants), groups=names, group_sizes=sizes, shape=shape, orient=orient, n_unmatched=n_unmatched)
+
+
 def _stats_out(st, to):
     """The statistics as the caller gets them: device tensors (int64) for torch, numpy for scipy (uint32 counts, uint64 sums)."""
     if to == "torch":
@@ -173,7 +315,7 @@ def _finish(csr, field, shape, to, torch):
 
 def run(vcf, bam, fasta, cell_barcodes, *, scoring_method="consensus", padding=100, mapq=0, primary_alignments=False,
         no_duplicates=False, umi=False, bam_tag="CB", valid_chars="ATGCatgc", aligner="banded", ingest="auto", stream_loci=None,
-        threads=1, device=0, orient="variants", to="scipy", stats=False, min_alt_cells=0, min_ref_cells=0) -> Result:
+        threads=1, device=0, orient="variants", to="scipy", stats=False, min_alt_cells=0, min_ref_cells=0, groups=None) -> Result:
     """Genotype the cells of ``bam`` at the variants of ``vcf`` and return every matrix of the run as CSR.
 
     The arguments up to ``valid_chars`` are the command line's (the reference's, src/main.rs:54-160).  ``ingest``: "host" packs the
@@ -190,7 +332,11 @@ def run(vcf, bam, fasta, cell_barcodes, *, scoring_method="consensus", padding=1
     and before anything reaches the host: ``variants``, ``shape`` and every matrix follow the kept set, ``variant_index`` holds its
     source rows, ``metrics`` stay those of the whole run.  ``stats=True`` fills ``variant_stats`` and ``cell_stats``: per variant and
     per cell of the matrix as returned (after the filter) the number of entries, of entries with alt > 0, with ref > 0, with both, and
-    the sums of the alt / ref / unknown counts — device tensors for ``to="torch"``, numpy for ``to="scipy"``."""
+    the sums of the alt / ref / unknown counts — device tensors for ``to="torch"``, numpy for ``to="scipy"``.
+
+    ``groups`` (a label per cell, a dict from barcode to label, or the path of a file ``read_groups`` takes: see ``pseudobulk``) fills
+    ``Result.groups`` with the ``GroupResult`` of the run: the fold runs on the stacked variant-major CSR on the device, after the
+    filter and before the transpose."""
     import torch
     if scoring_method not in abi.MODES:
         raise ValueError("scoring_method %r: one of %s" % (scoring_method, sorted(abi.MODES)))
@@ -206,6 +352,8 @@ def run(vcf, bam, fasta, cell_barcodes, *, scoring_method="consensus", padding=1
         raise ValueError("min_alt_cells %r / min_ref_cells %r: numbers of cells, 0 or more" % (min_alt_cells, min_ref_cells))
     if stream_loci is not None and int(stream_loci) < 1:
         raise ValueError("stream_loci %r: a positive number of VCF records, or None" % (stream_loci,))
+    if isinstance(groups, (str, os.PathLike)):
+        groups = read_groups(groups)         # a file that cannot be read fails before the run, not after it
     dev = torch.device("cuda", int(device))
     files = dict(vcf=str(vcf), bam=str(bam), fasta=str(fasta), cell_barcodes=str(cell_barcodes))
     filt = dict(padding=int(padding), mapq=int(mapq), primary_only=bool(primary_alignments), no_duplicates=bool(no_duplicates),
@@ -300,6 +448,10 @@ def run(vcf, bam, fasta, cell_barcodes, *, scoring_method="consensus", padding=1
         variant_stats = cell_stats = None
         if stats:
             variant_stats = _stats_out(_row_stats(ctx, torch, dev, csr, n_rows, n_cols), to)
+        barcodes = [b.decode() if isinstance(b, bytes) else b for b in state["barcodes"]]
+        group_result = None
+        if groups is not None:                   # on the variant-major whole as well: the transpose of orient="cells" is of the small result
+            group_result = _pseudobulk_device(ctx, torch, dev, csr, variants, barcodes, groups, orient, to)
         shape = (n_rows, n_cols)
         if orient == "cells":
             csr = _transpose(ctx, torch, dev, csr, n_rows, n_cols)
@@ -312,8 +464,8 @@ def run(vcf, bam, fasta, cell_barcodes, *, scoring_method="consensus", padding=1
                       ref_matrix=_finish(csr, "ref_value", shape, to, torch) if coverage else None,
                       alt_counts=_finish(csr, "alt", shape, to, torch), ref_counts=_finish(csr, "ref", shape, to, torch),
                       unknown_counts=_finish(csr, "unk", shape, to, torch), variants=variants,
-                      barcodes=[b.decode() if isinstance(b, bytes) else b for b in state["barcodes"]], metrics=metrics, shape=shape,
-                      variant_stats=variant_stats, cell_stats=cell_stats, variant_index=variant_index, orient=orient)
+                      barcodes=barcodes, metrics=metrics, shape=shape,
+                      variant_stats=variant_stats, cell_stats=cell_stats, variant_index=variant_index, orient=orient, groups=group_result)
     finally:
         if state["ctx"] is not None:
             state["ctx"].close()
@@ -366,3 +518,39 @@ def select(result: Result, variants=None, cells=None) -> Result:
     return Result(**{f: cut.get(f) for f in _MATRIX_FIELDS}, variants=[v for v, k in zip(result.variants, vm) if k],
                   barcodes=[b for b, k in zip(result.barcodes, cm) if k], metrics=dict(result.metrics), shape=shape,
                   variant_index=None if variants is None and result.variant_index is None else index[vm], orient=result.orient)
+
+
+def pseudobulk(result: Result, groups, *, to=None) -> GroupResult:
+    """Fold a ``Result`` by a label per cell into variants x groups (groups x variants for a result with ``orient="cells"``): per
+    variant and group the alt / ref / unknown counts summed over the cells of the group, and the number of its cells with an entry,
+    with alt support, with ref support and with both.
+
+    ``groups``: a sequence of ``len(result.barcodes)`` labels, ``None`` leaving a cell out; or a dict from barcode to label — barcodes
+    of the run that the dict lacks are left out, keys that are no barcode of the run are ignored and counted in ``n_unmatched``; or the
+    path of a file ``read_groups`` takes.  ``GroupResult.groups`` is the sorted list of the distinct labels at least one cell has: by
+    number if every label parses as an int, by ``str`` otherwise.  A filtered result folds its kept variants.
+
+    A torch result is folded on its device — one ``vtx_csr_group_plan`` and one ``vtx_csr_group_sum`` on a bare context for that device
+    (at most ``vtx_csr_group_max()`` groups) — into ``torch.sparse_csr_tensor``s, or into scipy matrices on the host with
+    ``to="scipy"``; a scipy result is folded on the host with scipy."""
+    n_var, n_cell = len(result.variants), len(result.barcodes)
+    orient = result.orient or ("cells" if tuple(result.shape) == (n_cell, n_var) != (n_var, n_cell) else "variants")
+    if to not in (None, "scipy", "torch"):
+        raise ValueError("to %r: scipy, torch, or None for the container of the result" % (to,))
+    if not _is_torch(result.alt_counts):
+        if to == "torch":
+            raise ValueError("pseudobulk: a scipy result is folded on the host; to=\"torch\" needs a torch result (run(to=\"torch\"))")
+        return _pseudobulk_host(result, groups, orient)
+    import torch
+    first = result.alt_counts
+    dev = first.device
+    csr = {"indptr": first.crow_indices(), "indices": first.col_indices().to(torch.int32)}
+    for k, m in (("alt", first), ("ref", result.ref_counts), ("unk", result.unknown_counts)):
+        if m.values().shape[0] != csr["indices"].shape[0]:
+            raise ValueError("pseudobulk: the count matrices do not have one sparsity")
+        csr[k] = m.values().to(torch.int32)
+    index = torch.cuda.current_device() if dev.index is None else dev.index
+    with lib.Context(abi.default_config(n_barcodes=max(n_cell, 1), device=index)) as ctx:    # no batch, no run: device, stream, work space
+        if orient == "cells":                    # back to variant-major: the fold sums over the columns
+            csr = _transpose(ctx, torch, dev, csr, n_cell, n_var, ("alt", "ref", "unk"))
+        return _pseudobulk_device(ctx, torch, dev, csr, result.variants, result.barcodes, groups, orient, to or "torch")

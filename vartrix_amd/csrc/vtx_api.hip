@@ -33,6 +33,7 @@
 #include "vtx_mtx_join.h"
 #include "vtx_csr_core.h"
 #include "vtx_csr_ops_core.h"
+#include "vtx_csr_group_core.h"
 #include "../../include/vtx_band_semantics.h"
 
 extern "C" hipError_t vtxk_inclusive_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, void* temp,
@@ -165,6 +166,7 @@ struct vtx_ctx {
     DevBuf d_csr_indptr;                     // vtx_device_csr: the row offsets of d_o_row (a buffer of its own: no other call works in it)
     DevBuf d_csr_flag, d_csr_keys, d_csr_iota, d_csr_perm, d_csr_tmp;   // vtx_csr_transpose: flag word, sorted columns, positions, perm (when the caller wants none), the sort's work space
     DevBuf d_sel_pos, d_sel_major, d_sel_minor, d_sel_tmp;   // vtx_csr_select_plan / vtx_csr_select: pos[nnz + 1], major_map[n_major + 1], minor_map[n_minor + 1], the scan's work space
+    DevBuf d_grp_flag, d_grp_pos, d_grp_tmp;   // vtx_csr_group_plan / vtx_csr_group_sum: the lowest column with a bad label, pos[n_major + 1], the scan's work space
     bool band_long_lists = false;      // (performance feedback between runs: see vtx_run)
     int read_format = VTX_READS_BYTES;     // vtx_set_read_format
     DevBuf d_read_packed;                  // VTX_READS_NIBBLES: the arena as uploaded, unpacked into d_read
@@ -808,6 +810,7 @@ void vtx_destroy(vtx_ctx* c) {
     c->d_slow_ws.release(); c->d_slow_retry.release(); c->d_read_packed.release();
     c->d_csr_indptr.release(); c->d_csr_flag.release(); c->d_csr_keys.release(); c->d_csr_iota.release(); c->d_csr_perm.release(); c->d_csr_tmp.release();
     c->d_sel_pos.release(); c->d_sel_major.release(); c->d_sel_minor.release(); c->d_sel_tmp.release();
+    c->d_grp_flag.release(); c->d_grp_pos.release(); c->d_grp_tmp.release();
     DevBuf* ib[] = {&c->d_bam_comp, &c->d_bam_data, &c->d_bam_blocks, &c->d_bam_seeds, &c->d_bam_seed_cnt, &c->d_bam_seed_scan, &c->d_bam_iv, &c->d_bam_cnt,
                     &c->d_bam_rec, &c->d_bam_nhit, &c->d_bam_rsz, &c->d_bam_tsz, &c->d_bam_hscan, &c->d_bam_rscan, &c->d_bam_tscan, &c->d_bam_info, &c->d_bam_segs};
     for (DevBuf* b : ib) b->release();
@@ -3006,6 +3009,87 @@ int vtx_csr_select(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = csr_times(c, true, false, true)) return rc;
     c->csr_ms[1] = scan_ms;
+    return VTX_OK;
+}
+
+// ---- pseudobulk: a caller's CSR summed per group of columns (include/vtx.h, vtx_csr_group.hip) ----
+uint32_t vtx_csr_group_window(void) { return vtxr::GROUP_WINDOW; }
+uint32_t vtx_csr_group_max(void) { return vtxr::GROUP_MAX; }
+static_assert(VTX_GROUP_NONE == vtxr::GROUP_NONE, "the header's and the kernels' label of no group");
+
+// what both calls refuse on the host, before the device is touched
+static int csr_group_args(vtx_ctx* c, const char* who, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
+                          const uint32_t* d_group, uint32_t n_groups) {
+    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "%s: %llu entries: positions are 32-bit", who, (unsigned long long)nnz);
+    if (!n_groups) return fail(c, VTX_E_INVAL, "%s: no groups", who);
+    if (n_groups > vtxr::GROUP_MAX)
+        return fail(c, VTX_E_UNSUPPORTED, "%s: %u groups: at most %u (%u windows of %u)", who, n_groups, vtxr::GROUP_MAX, vtxr::GROUP_MAX_WINDOWS, vtxr::GROUP_WINDOW);
+    if (!d_indptr || (nnz && !d_indices) || (n_minor && !d_group)) return fail(c, VTX_E_INVAL, "%s: null array", who);
+    return VTX_OK;
+}
+
+// The checks of the CSR and of the labels, the count and its scan; nnz_out comes back to the host.  Writes into the context's work space only.
+static int csr_group_counts(vtx_ctx* c, const char* who, uint32_t n_minor, uint64_t nnz, const vtx_group_in& in, uint32_t* nnz_out) {
+    hipStream_t s = c->stream;
+    if (int rc = csr_events(c)) return rc;
+    if (int rc = csr_flag_zero(c)) return rc;
+    HIP_TRY(c, c->d_grp_flag.reserve(sizeof(uint32_t)));
+    HIP_TRY(c, hipMemsetAsync(c->d_grp_flag.p, 0xFF, sizeof(uint32_t), s));      // no column yet
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK0], s));
+    HIP_TRY(c, vtxr_check(in.indptr, in.n_major, nnz, in.indices, n_minor, c->d_csr_flag.as<uint32_t>(), s));
+    HIP_TRY(c, vtxr_group_check(in.group, n_minor, in.n_groups, c->d_grp_flag.as<uint32_t>(), s));      // reads group[0 .. n_minor) only, whatever the CSR is
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK1], s));
+    uint32_t flag = 0, first_bad = 0;
+    HIP_TRY(c, hipMemcpyAsync(&first_bad, c->d_grp_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (int rc = csr_flag_read(c, &flag)) return rc;
+    if (flag) return fail(c, VTX_E_INVAL, "%s: %s", who, csr_bad_reason(flag));
+    if (first_bad != 0xFFFFFFFFu)
+        return fail(c, VTX_E_INVAL, "%s: the label of column %u is neither below n_groups = %u nor VTX_GROUP_NONE", who, first_bad, in.n_groups);
+    const size_t tmp = vtxr_scan_temp_bytes((uint64_t)in.n_major + 1);
+    HIP_TRY(c, c->d_grp_pos.reserve(((size_t)in.n_major + 1) * sizeof(uint32_t)));
+    HIP_TRY(c, c->d_grp_tmp.reserve(std::max<size_t>(tmp, 1)));      // never a null work space: with one the scan only reports its size
+    uint32_t* pos = c->d_grp_pos.as<uint32_t>();
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT0], s));
+    HIP_TRY(c, vtxr_group_count(in, pos, c->d_grp_tmp.p, tmp, s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT1], s));
+    HIP_TRY(c, hipMemcpyAsync(nnz_out, pos + in.n_major, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return VTX_OK;
+}
+
+int vtx_csr_group_plan(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
+                       const uint32_t* d_group, uint32_t n_groups, uint64_t* nnz_out) {
+    if (!c) return VTX_E_INVAL;
+    if (int rc = csr_group_args(c, "vtx_csr_group_plan", n_minor, nnz, d_indptr, d_indices, d_group, n_groups)) return rc;
+    if (!nnz_out) return fail(c, VTX_E_INVAL, "vtx_csr_group_plan: null output");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const vtx_group_in in{d_indptr, n_major, d_indices, nullptr, nullptr, nullptr, d_group, n_groups};
+    uint32_t n = 0;
+    if (int rc = csr_group_counts(c, "vtx_csr_group_plan", n_minor, nnz, in, &n)) return rc;
+    if (int rc = csr_times(c, true, true, false, false)) return rc;
+    *nnz_out = n;
+    return VTX_OK;
+}
+
+int vtx_csr_group_sum(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
+                      const uint32_t* d_alt, const uint32_t* d_ref, const uint32_t* d_unk, const uint32_t* d_group, uint32_t n_groups,
+                      uint64_t nnz_out, uint64_t* d_indptr_out, uint32_t* d_indices_out, const vtx_csr_stats* out) {
+    if (!c) return VTX_E_INVAL;
+    if (int rc = csr_group_args(c, "vtx_csr_group_sum", n_minor, nnz, d_indptr, d_indices, d_group, n_groups)) return rc;
+    if (!out || !d_indptr_out || (nnz && (!d_alt || !d_ref || !d_unk)) || (nnz_out && !d_indices_out)) return fail(c, VTX_E_INVAL, "vtx_csr_group_sum: null array");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    const vtx_group_in in{d_indptr, n_major, d_indices, d_alt, d_ref, d_unk, d_group, n_groups};
+    uint32_t n = 0;
+    if (int rc = csr_group_counts(c, "vtx_csr_group_sum", n_minor, nnz, in, &n)) return rc;
+    // stateless: the size is this call's own; a caller whose arrays were made for another fold is refused before a byte is written
+    if (n != nnz_out)
+        return fail(c, VTX_E_INVAL, "vtx_csr_group_sum: the result has %u entries, the caller said %llu (vtx_csr_group_plan)", n, (unsigned long long)nnz_out);
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, vtxr_group_fill(in, c->d_grp_pos.as<uint32_t>(), d_indptr_out, d_indices_out, out, s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = csr_times(c, true, true, true, false)) return rc;      // checks, count + scan, no offsets phase, fill
     return VTX_OK;
 }
 

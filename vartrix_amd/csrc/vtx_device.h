@@ -260,4 +260,17 @@ hipError_t vtxr_select_ids(const uint8_t* mask, uint32_t n, const uint32_t* map,
 hipError_t vtxr_select_place(const uint32_t* indices, uint64_t nnz, const uint32_t* pos, const uint32_t* minor_map, uint32_t* indices_out,
                              const void* const* in, void* const* out, const uint32_t* elem_bytes, uint32_t n_payload, hipStream_t s);
 }
+// ---- vtx_csr_group.hip: the CSR summed per group of columns (pseudobulk).  The CSR has passed vtxr_check, the labels vtxr_group_check ----
+// the matrix and its labels as the count and the fill kernel read them: group[n_minor], every label < n_groups or VTX_GROUP_NONE;
+// alt / ref / unk are not read by the count
+struct vtx_group_in { const uint64_t* indptr; uint32_t n_major; const uint32_t* indices; const uint32_t *alt, *ref, *unk; const uint32_t* group; uint32_t n_groups; };
+extern "C" {
+// first_bad: one word, 0xFFFFFFFF in front of the check; behind it the lowest column whose label is neither a group nor VTX_GROUP_NONE
+hipError_t vtxr_group_check(const uint32_t* group, uint32_t n_minor, uint32_t n_groups, uint32_t* first_bad, hipStream_t s);
+// pos[0 .. n_major]: the (row, group) pairs in the rows below r (counted, then summed in place); pos[n_major] = nnz_out
+hipError_t vtxr_group_count(const vtx_group_in& in, uint32_t* pos, void* temp, size_t temp_bytes, hipStream_t s);
+// indptr_out[n_major + 1] from pos; indices_out and the arrays of `out` (any of them NULL: not written) have pos[n_major] elements
+hipError_t vtxr_group_fill(const vtx_group_in& in, const uint32_t* pos, uint64_t* indptr_out, uint32_t* indices_out, const vtx_csr_stats* out,
+                           hipStream_t s);
+}
 #endif

@@ -40,6 +40,7 @@ SYMBOLS = (
     "vtx_last_crc_ms", "vtx_write_mtx_gz", "vtx_mtx_part", "vtx_mtx_part_free", "vtx_mtx_join",
     "vtx_device_csr", "vtx_csr_transpose", "vtx_last_csr_ms",
     "vtx_csr_row_stats", "vtx_csr_select_plan", "vtx_csr_select", "vtx_sizeof_csr_stats",
+    "vtx_csr_group_window", "vtx_csr_group_max", "vtx_csr_group_plan", "vtx_csr_group_sum",
 )
 # (entry points with a digit in their name: tests/test_abi.py finds the header's declarations with [a-z_]+ and compares them with SYMBOLS,
 # so these are listed — and checked against the header and every build of the library, tests/test_abi_f64.py — on their own)
@@ -102,6 +103,15 @@ def load(variant=None):
     L.vtx_csr_select.restype = C.c_int
     L.vtx_csr_select.argtypes = csr_in + [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32]
+    L.vtx_csr_group_window.restype = C.c_uint32
+    L.vtx_csr_group_window.argtypes = []
+    L.vtx_csr_group_max.restype = C.c_uint32
+    L.vtx_csr_group_max.argtypes = []
+    L.vtx_csr_group_plan.restype = C.c_int
+    L.vtx_csr_group_plan.argtypes = csr_in + [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.vtx_csr_group_sum.restype = C.c_int
+    L.vtx_csr_group_sum.argtypes = csr_in + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                             C.POINTER(abi.VtxCsrStats)]
     L.vtx_sizeof_csr_stats.restype = C.c_uint32
     L.vtx_sizeof_csr_stats.argtypes = []
     L.vtx_last_csr_ms.restype = C.c_int
@@ -439,6 +449,30 @@ class Context:
         self._check(self._L.vtx_csr_select(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, keep_major or None,
                                            keep_minor or None, int(sizes[0]), int(sizes[1]), int(sizes[2]), indptr_out or None, indices_out or None,
                                            major_ids or None, minor_ids or None, p_in, p_out, p_sz, n))
+
+    def csr_group_plan(self, n_major: int, n_minor: int, nnz: int, indptr: int, indices: int, group: int, n_groups: int) -> int:
+        """nnz_out of the CSR in device memory summed per group of columns (vtx_csr_group_plan): the number of (row, group) pairs with at
+        least one entry.  ``group``: the address of n_minor uint32 labels, each below ``n_groups`` or ``abi.VTX_GROUP_NONE``."""
+        n = C.c_uint64()
+        self._check(self._L.vtx_csr_group_plan(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, group or None,
+                                               int(n_groups), C.byref(n)))
+        return int(n.value)
+
+    def csr_group_sum(self, n_major: int, n_minor: int, nnz: int, indptr: int, indices: int, alt: int, ref: int, unk: int, group: int,
+                      n_groups: int, nnz_out: int, indptr_out: int, indices_out: int, out: dict):
+        """The CSR in device memory summed per group of columns (vtx_csr_group_sum) into a CSR of n_major x n_groups.  ``nnz_out``: what
+        ``csr_group_plan`` returned for the same inputs, the size the outputs were allocated for — any other fold is refused with
+        nothing written.  ``out``: name (``abi.CSR_STAT_NAMES``) -> address of nnz_out uint32 (the four counts) / uint64 (the three
+        sums); a name that is missing or 0 is not written."""
+        unknown = set(out) - set(abi.CSR_STAT_NAMES)
+        if unknown:
+            raise ValueError("csr_group_sum: unknown statistics %s" % sorted(unknown))
+        st = abi.VtxCsrStats()
+        for k, typ in st._fields_:
+            setattr(st, k, C.cast(C.c_void_p(int(out.get(k) or 0) or None), typ))
+        self._check(self._L.vtx_csr_group_sum(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
+                                              ref or None, unk or None, group or None, int(n_groups), int(nnz_out), indptr_out or None,
+                                              indices_out or None, C.byref(st)))
 
     def comm_init(self, ident: bytes, rank: int, world: int):
         """Join the RCCL communicator of the sharded run (collective; vtx_comm_init)."""
