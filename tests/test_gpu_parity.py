@@ -115,7 +115,9 @@ def test_banded_low_complexity_overflow_slabs():
 
 @pytest.mark.parametrize("read_len", [1, 5, 17, 31, 32, 33, 64, 65, 100, 151, 160, 161, 200, 250, 256, 257, 400, 1000])
 def test_read_length_buckets(read_len):
-    """Every kernel shape (rows-per-lane x lanes-per-record) incl. bucket edges."""
+    """Read lengths at the edges of every (rows-per-lane x lanes-per-record) bucket: every shape of the full flavour's kernels, and
+    the banded PIPELINE at those read lengths — where the certificates decide most of the 144 records, so nothing here shows that a
+    task reached the masked DP at that shape.  The masked DP's own shapes: tests/test_gpu_masked_dp.py."""
     spec = synth.SynthSpec(n_loci=12, n_barcodes=40, reads_per_locus=12, read_len=read_len,
                            padding=max(100, read_len // 2 + 20), indel_frac=0.4, seed=read_len)
     batch = synth.make_batch(spec)

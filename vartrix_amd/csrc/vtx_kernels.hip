@@ -28,6 +28,9 @@
 //     packed VALU ops per cell pair.  Scores <= min(read, hap) length < 2^15.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#ifdef VTX_DEVTOOLS
+#include <vector>            // (vtxk_dev_sw_pairs)
+#endif
 
 #include "vtx_device.h"
 #include "vtx_call_core.h"
@@ -619,8 +622,12 @@ __global__ __launch_bounds__(256) void sw_banded_kernel(
                     if (jj >= cA - 20 && jj <= cB + 20) {
                         const int c0 = jj - 20 > cA ? jj - 20 : cA, c1 = jj + 20 < cB ? jj + 20 : cB;
                         const int l_ = c0 - d - 20, h_ = c1 - d + 21;
+                        // (both clamped into [0, m + 1]: with every square of the column above row 0 — d > c1 + 21 — h_ is negative, and a
+                        //  negative hv of the low half would spill its sign bits into the high half's hi: the PARTNER's column went empty;
+                        //  tests/test_gpu_masked_dp.py::test_mode2_band_above_the_matrix_leaves_its_partner_alone)
+                        const int hc = h_ < (int)m[k] + 1 ? h_ : (int)m[k] + 1;
                         lv = (uint32_t)(l_ > 0 ? l_ : 0);
-                        hv = (uint32_t)(h_ < (int)m[k] + 1 ? h_ : (int)m[k] + 1);
+                        hv = (uint32_t)(hc > 0 ? hc : 0);
                     }
                     if (k == 0) { la = lv; ha = hv; } else { lb = lv; hb = hv; }
                 }
@@ -761,6 +768,96 @@ extern "C" hipError_t vtxk_launch_sw_check(const vtx_task_arrays& a, int R, int 
                                            uint32_t* recheck_count, uint8_t* stage, hipStream_t stream) {
     return launch_sw_pairs(a, 1, R, GL, n_cap, list, n_dev, nullptr, 0, max_hap_len, recheck_list, recheck_count, stage, packs, recheck_pack, stream);
 }
+
+#ifdef VTX_DEVTOOLS
+// (developer build; tests/test_gpu_masked_dp.py) sw_banded_kernel on its own, over arrays given and returned in HOST memory: no
+// context, scratch buffers of its own, the launch through launch_sw_pairs (so the workgroup size and the LDS come from the production
+// logic).  mode 0: band = one slot per list entry, lo[0 .. n] then hi[0 .. n] band_stride apart (what vtx_debug_bands returns);
+// mode 2: packs; mode 1: packs (or null) and the provisional scores prov_ref / prov_alt, uploaded as the score arrays.  In modes 0 and 2
+// both score arrays start as score_poison, the stage bytes always as stage_poison.  n_dev < 0: a null pointer, else the device-side
+// length.  Returns the score arrays (n_records each) and the stage bytes (2 n_records) whole, and for mode 1 the recheck count, list
+// and packs (room for n_list entries each).  hipErrorInvalidValue BEFORE any launch unless (R, GL) is a shape of launch_sw_pairs,
+// every listed task exists, its read fits R * GL rows, its haplotype max_hap_len and its band slot, and its bytes lie in the arenas.
+extern "C" hipError_t vtxk_dev_sw_pairs(const vtx_record* records, uint32_t n_records, const uint32_t* rec_locus, const vtx_locus* loci, uint32_t n_loci,
+                                        const uint8_t* read_arena, uint64_t read_bytes, const uint8_t* hap_arena, uint64_t hap_bytes,
+                                        const uint32_t* list, uint32_t n_list, int mode, int R, int GL, uint32_t max_hap_len,
+                                        const uint16_t* band, uint32_t band_stride, const uint32_t* packs, const int32_t* prov_ref,
+                                        const int32_t* prov_alt, int64_t n_dev, int32_t score_poison, uint8_t stage_poison,
+                                        int32_t* ref_out, int32_t* alt_out, uint8_t* stage_out, uint32_t* recheck_count_out,
+                                        uint32_t* recheck_list_out, uint32_t* recheck_pack_out) {
+    static const int shapes[][2] = {{2, 16}, {4, 16}, {6, 16}, {8, 16}, {10, 16}, {12, 16}, {16, 16}, {8, 64}, {16, 64}};   // (the CASE line of launch_sw_pairs)
+    bool shape_ok = false;
+    for (const auto& s : shapes) shape_ok |= s[0] == R && s[1] == GL;
+    if (!shape_ok || mode < 0 || mode > 2 || !n_records || !n_loci || !records || !rec_locus || !loci || !list || !ref_out || !alt_out || !stage_out)
+        return hipErrorInvalidValue;
+    if (max_hap_len > VTX_FAST_HAP_LEN || n_dev > 0xffffffffll) return hipErrorInvalidValue;
+    if (mode == 0 && (!band || !band_stride)) return hipErrorInvalidValue;
+    if (mode == 2 && !packs) return hipErrorInvalidValue;
+    if (mode == 1 && (!prov_ref || !prov_alt || !recheck_count_out || !recheck_list_out || !recheck_pack_out)) return hipErrorInvalidValue;
+    for (uint32_t i = 0; i < n_list; ++i) {
+        const uint32_t t = list[i], rid = t >> 1;
+        if (rid >= n_records || rec_locus[rid] >= n_loci) return hipErrorInvalidValue;
+        const vtx_record& rec = records[rid];
+        const vtx_locus& loc = loci[rec_locus[rid]];
+        const uint32_t n = (t & 1) ? loc.alt_len : loc.ref_len, hoff = (t & 1) ? loc.alt_off : loc.ref_off;
+        if (rec.read_len > (uint32_t)(R * GL) || n > max_hap_len) return hipErrorInvalidValue;
+        if ((uint64_t)rec.read_off + rec.read_len > read_bytes || (uint64_t)hoff + n > hap_bytes) return hipErrorInvalidValue;
+        if (mode == 0 && n + 1 > band_stride) return hipErrorInvalidValue;
+    }
+    // (recheck buffers: a slot per list entry and one per record slot of a last, partly filled workgroup)
+    const size_t n_re = (size_t)n_list + 64, band_words = mode == 0 ? (size_t)n_list * 2 * band_stride : 0;
+    void* bufs[16];
+    int nb = 0;
+    hipError_t e = hipSuccess;
+    auto up = [&](const void* src, size_t bytes) -> void* {          // a device copy of src (at least 16 bytes, so that no pointer is null)
+        void* d = nullptr;
+        if (e == hipSuccess) e = hipMalloc(&d, bytes < 16 ? 16 : bytes);
+        if (e == hipSuccess && d) bufs[nb++] = d;
+        if (e == hipSuccess && src && bytes) e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
+        return e == hipSuccess ? d : nullptr;
+    };
+    std::vector<int32_t> fill((size_t)n_records, score_poison);
+    const vtx_record* d_records = (const vtx_record*)up(records, (size_t)n_records * sizeof(vtx_record));
+    const uint32_t* d_rec_locus = (const uint32_t*)up(rec_locus, (size_t)n_records * sizeof(uint32_t));
+    const vtx_locus* d_loci = (const vtx_locus*)up(loci, (size_t)n_loci * sizeof(vtx_locus));
+    const uint8_t* d_read = (const uint8_t*)up(read_arena, (size_t)read_bytes);
+    const uint8_t* d_hap = (const uint8_t*)up(hap_arena, (size_t)hap_bytes);
+    const uint32_t* d_list = (const uint32_t*)up(list, (size_t)n_list * sizeof(uint32_t));
+    int32_t* d_ref = (int32_t*)up(mode == 1 ? prov_ref : fill.data(), (size_t)n_records * sizeof(int32_t));
+    int32_t* d_alt = (int32_t*)up(mode == 1 ? prov_alt : fill.data(), (size_t)n_records * sizeof(int32_t));
+    const uint16_t* d_band = mode == 0 ? (const uint16_t*)up(band, band_words * sizeof(uint16_t)) : nullptr;
+    const uint32_t* d_packs = (mode != 0 && packs) ? (const uint32_t*)up(packs, (size_t)n_list * sizeof(uint32_t)) : nullptr;
+    uint8_t* d_stage = (uint8_t*)up(nullptr, 2 * (size_t)n_records);
+    const uint32_t nd = n_dev < 0 ? 0u : (uint32_t)n_dev;
+    const uint32_t* d_ndev = n_dev < 0 ? nullptr : (const uint32_t*)up(&nd, sizeof nd);
+    uint32_t *d_recount = nullptr, *d_relist = nullptr, *d_repack = nullptr;
+    if (mode == 1) {
+        d_recount = (uint32_t*)up(nullptr, sizeof(uint32_t));
+        d_relist = (uint32_t*)up(nullptr, n_re * sizeof(uint32_t));
+        d_repack = (uint32_t*)up(nullptr, n_re * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(d_recount, 0, sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(d_relist, 0xff, n_re * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(d_repack, 0xff, n_re * sizeof(uint32_t));
+    }
+    if (e == hipSuccess) e = hipMemset(d_stage, stage_poison, 2 * (size_t)n_records);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) {
+        const vtx_task_arrays a{d_records, d_rec_locus, d_loci, d_read, d_hap, d_ref, d_alt};
+        e = launch_sw_pairs(a, mode, R, GL, n_list, d_list, d_ndev, d_band, band_stride, max_hap_len, d_relist, d_recount, d_stage, d_packs, d_repack, 0);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(ref_out, d_ref, (size_t)n_records * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(alt_out, d_alt, (size_t)n_records * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(stage_out, d_stage, 2 * (size_t)n_records, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && mode == 1) {
+        e = hipMemcpy(recheck_count_out, d_recount, sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(recheck_list_out, d_relist, (size_t)n_list * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(recheck_pack_out, d_repack, (size_t)n_list * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    }
+    for (int i = 0; i < nb; ++i) (void)hipFree(bufs[i]);
+    return e;
+}
+#endif
 
 __global__ void fill_i32_kernel(int32_t* __restrict__ p, uint32_t n, int32_t v) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
