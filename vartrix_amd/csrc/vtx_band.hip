@@ -2103,6 +2103,18 @@ extern "C" hipError_t vtxk_diag_phases(unsigned long long* out) {
     memset(h, 0, sizeof h);
     return hipMemcpyToSymbol(HIP_SYMBOL(g_diag_phase), h, sizeof h);
 }
+// The pair's 2 HW words from the HW each of its lanes (2i, 2i + 1) holds: out[k] = the even lane's mine[k], out[HW + k] = the odd lane's,
+// in both lanes.  A lane takes its partner's half whatever became of the partner (a lane without a table has loaded its half all the
+// same: band_diag_kernel), so every lane of the pair must be here.
+template <int HW> __device__ __forceinline__ void pair_gather(const uint64_t (&mine)[HW], int half, uint64_t* out) {
+#pragma unroll
+    for (int k = 0; k < HW; ++k) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)mine[k], 1), hi = (uint32_t)__shfl_xor((int)(uint32_t)(mine[k] >> 32), 1);
+        const uint64_t theirs = (uint64_t)lo | ((uint64_t)hi << 32);
+        out[k] = half ? theirs : mine[k];
+        out[HW + k] = half ? mine[k] : theirs;
+    }
+}
 #ifdef VTX_DEVTOOLS
 // (developer build; tests/test_gpu_byteops.py) the DEVICE paths of vtx_fast_core.h's byte compare and base codes over n pairs of 8-byte
 // words given and returned in host memory: out[i] = eq8(a[i], b[i]), out[n + i] = kw_code8(a[i]), out[2 n + i] = kw_code of a[i]'s low
@@ -2127,6 +2139,86 @@ extern "C" hipError_t vtxk_dev_byteops(const uint64_t* a, const uint64_t* b, uin
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out, d_out, 3 * (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return e;
+}
+// (developer build; tests/test_gpu_maskops.py) the DEVICE paths of the mask and bit helpers band_diag_kernel is built from, over n items given
+// and returned in host memory (the host build of the same header: tests/fastcore/maskops_host.cpp, same layouts):
+//   op 0  in: n x (lo, hi) int32      out: n x 8 words — m_range<3>(lo, hi), then m_range<4>(lo, hi)
+//   op 1  in: n x int32               out: n words — ones_below
+//   op 2  in: n x uint32 D            out: n x (lo, hi) uint32 — closure_count(D) into zeroed counters
+//   op 3  in: n x (entry, code) words out: n x uint32 — t3_hits(entry, (uint32_t)code)
+//   op 4  in: n x 8 int32 — four piece words, d, best_dp, sx, sy   out: n x 2 uint32 — harmless_item4, and harmless_item over the same pieces
+//   op 5  in: n x 5 words — four mask words, a row                 out: n x uint32 — m_bit(mask, row), the need-bit test of twin_matches
+//   op 6  in: n x 16 words, lane l's words at [16 l, 16 l + 16); n a multiple of 64: whole wavefronts, every lane active
+//         out: n x 56 words — pair_gather<12> (24 words), then pair_gather<16> (32): the function band_diag_kernel calls
+//   op 7  in: n x 48 uint32 — nc, d, used (low, high), hull_lo, hull_hi, then 40 two-byte entries x << 8 | y, one per word, two words unused
+//         out: n x int32 — closure_scan over the first nc entries
+struct DevMatchList {
+    const uint32_t* p;
+    static constexpr int XS = 8;
+    static constexpr uint32_t YM = 0xffu;
+    __device__ uint32_t s(int k) const { return p[k]; }
+};
+__global__ void dev_maskops_kernel(uint32_t op, const void* __restrict__ in, uint32_t n, void* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (op == 0) {
+        const int lo = ((const int32_t*)in)[2 * i], hi = ((const int32_t*)in)[2 * i + 1];
+        const vtxf::M192 a = vtxf::m_range<3>(lo, hi), b = vtxf::m_range<4>(lo, hi);
+        for (int k = 0; k < 4; ++k) {
+            ((uint64_t*)out)[8 * (size_t)i + k] = k < vtxf::NW ? a.w[k < vtxf::NW ? k : 0] : 0ull;
+            ((uint64_t*)out)[8 * (size_t)i + 4 + k] = k < vtxf::NW ? b.w[k < vtxf::NW ? k : 0] : 0ull;
+        }
+    } else if (op == 1) {
+        ((uint64_t*)out)[i] = vtxf::ones_below(((const int32_t*)in)[i]);
+    } else if (op == 2) {
+        uint32_t lo = 0, hi = 0;
+        vtxf::closure_count(((const uint32_t*)in)[i], lo, hi);
+        ((uint32_t*)out)[2 * i] = lo; ((uint32_t*)out)[2 * i + 1] = hi;
+    } else if (op == 3) {
+        ((uint32_t*)out)[i] = vtxf::t3_hits(((const uint64_t*)in)[2 * i], (uint32_t)((const uint64_t*)in)[2 * i + 1]);
+    } else if (op == 4) {
+        const int32_t* p = (const int32_t*)in + 8 * (size_t)i;
+        const uint32_t pw4[4] = {(uint32_t)p[0], (uint32_t)p[1], (uint32_t)p[2], (uint32_t)p[3]};
+        struct { const uint32_t* w; __device__ uint32_t at(int k) const { return w[k]; } } pl{pw4};
+        int r = 0;
+        while (r < 4 && pw4[r] != 0u) ++r;
+        ((uint32_t*)out)[2 * i] = vtxf::harmless_item4(pw4, p[4], p[5], p[6], p[7]);
+        ((uint32_t*)out)[2 * i + 1] = vtxf::harmless_item(pl, r, p[4], p[5], p[6], p[7]);
+    } else if (op == 5) {
+        const uint64_t* p = (const uint64_t*)in + 5 * (size_t)i;
+        vtxf::M192 a;
+        for (int k = 0; k < vtxf::NW; ++k) a.w[k] = p[k];
+        ((uint32_t*)out)[i] = vtxf::m_bit(a, (int)p[4]) ? 1u : 0u;
+    } else if (op == 7) {
+        const uint32_t* p = (const uint32_t*)in + 48 * (size_t)i;
+        ((int32_t*)out)[i] = vtxf::closure_scan((int)p[1], (int)p[0], DevMatchList{p + 6}, (uint64_t)p[2] | ((uint64_t)p[3] << 32), (int)p[4], (int)p[5]);
+    } else if (op == 6) {
+        uint64_t mine[16], m12[12], g12[24], g16[32];
+        for (int k = 0; k < 16; ++k) mine[k] = ((const uint64_t*)in)[16 * (size_t)i + k];
+        for (int k = 0; k < 12; ++k) m12[k] = mine[k];
+        pair_gather<12>(m12, (int)(i & 1u), g12);
+        pair_gather<16>(mine, (int)(i & 1u), g16);
+        uint64_t* o = (uint64_t*)out + 56 * (size_t)i;
+        for (int k = 0; k < 24; ++k) o[k] = g12[k];
+        for (int k = 0; k < 32; ++k) o[24 + k] = g16[k];
+    }
+}
+extern "C" hipError_t vtxk_dev_maskops(uint32_t op, const void* in, uint32_t n, void* out) {
+    static const size_t in_b[8] = {8, 4, 4, 16, 32, 40, 128, 192}, out_b[8] = {64, 8, 8, 4, 8, 4, 448, 4};
+    if (op > 7 || (op == 6 && n % 64u != 0u)) return hipErrorInvalidValue;
+    if (!n) return hipSuccess;
+    void *d_in = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc(&d_in, n * in_b[op]);
+    if (e == hipSuccess) e = hipMalloc(&d_out, n * out_b[op]);
+    if (e == hipSuccess) e = hipMemcpy(d_in, in, n * in_b[op], hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(dev_maskops_kernel, dim3((n + 255u) / 256u), dim3(256), 0, 0, op, (const void*)d_in, n, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, n * out_b[op], hipMemcpyDeviceToHost);
     (void)hipFree(d_in);
     (void)hipFree(d_out);
     return e;
@@ -2344,13 +2436,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
             mine[2 * k] = (uint64_t)v.x | ((uint64_t)v.y << 32);
             mine[2 * k + 1] = (uint64_t)v.z | ((uint64_t)v.w << 32);
         }
-#pragma unroll
-        for (int k = 0; k < HW; ++k) {
-            const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)mine[k], 1), hi = (uint32_t)__shfl_xor((int)(uint32_t)(mine[k] >> 32), 1);
-            const uint64_t theirs = (uint64_t)lo | ((uint64_t)hi << 32);
-            rw.w[k] = half ? theirs : mine[k];
-            rw.w[HW + k] = half ? mine[k] : theirs;
-        }
+        pair_gather<HW>(mine, half, rw.w);
     }
     // ---- the main diagonal.  Lanes 2i / 2i + 1 hold the two haplotypes of one record: each looks ONE sample row up in its own
     //      table per round and the two exchange their candidates (a candidate is only ever a candidate: the lane keeps it if
@@ -2585,9 +2671,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
             uint32_t nh = 0, hits[EPL];                                 // hits: bits 0-2 rows of the block in the even lane's haplotype, 3-5 in the odd lane's
 #pragma unroll
             for (int u = 0; u < EPL; ++u) {
-                const uint32_t b0 = c16[u] & 15u, b1 = 16u + (((c16[u] >> 2) & 3u) | (((c16[u] >> 12) & 3u) << 2)), b2 = 32u + (c16[u] >> 12);
-                const uint32_t ha = ((uint32_t)(ea[u] >> b0) & 1u) | (((uint32_t)(ea[u] >> b1) & 1u) << 1) | (((uint32_t)(ea[u] >> b2) & 1u) << 2);
-                const uint32_t hb = ((uint32_t)(eb[u] >> b0) & 1u) | (((uint32_t)(eb[u] >> b1) & 1u) << 1) | (((uint32_t)(eb[u] >> b2) & 1u) << 2);
+                const uint32_t ha = vtxf::t3_hits(ea[u], c16[u]), hb = vtxf::t3_hits(eb[u], c16[u]);
                 const uint32_t m3 = on[u] ? (ent2[u] >> 8) & 7u : 0u;
                 hits[u] = (ha & m3) | ((hb & m3) << 3);
                 nh += (uint32_t)__builtin_popcount(hits[u]);

@@ -154,6 +154,13 @@ VTXF_HD uint32_t t3_word_b(uint32_t c) { return 2u * ((c >> 2) & 0xffu); }
 VTXF_HD uint32_t t3_bit_b(uint32_t c) { return 16u + ((c & 3u) | ((c >> 10) << 2)); }
 VTXF_HD uint32_t t3_word_c(uint32_t c) { return 2u * (c & 0xffu) + 1u; }
 VTXF_HD uint32_t t3_bit_c(uint32_t c) { return c >> 8; }
+// the three membership bits (bit i: row i of the block) a t3 entry e holds for the 16-bit code c16 of eight bases (kw_code8): the first
+// two sets lie in the entry's low dword, the third in its high one — 32-bit shifts, no 64-bit one
+VTXF_HD uint32_t t3_hits(uint64_t e, uint32_t c16) {
+    const uint32_t lo = (uint32_t)e, hi = (uint32_t)(e >> 32);
+    const uint32_t b0 = c16 & 15u, b1 = 16u + (((c16 >> 2) & 3u) | (((c16 >> 12) & 3u) << 2)), b2 = c16 >> 12;
+    return ((lo >> b0) & 1u) | (((lo >> b1) & 1u) << 1) | (((hi >> b2) & 1u) << 2);
+}
 // Byte and bit compaction by dot product (device code only): v_dot4_u32_u8 sums four bytes times four byte weights in one instruction,
 // which is what "one or two bits of every byte, side by side" is — a shift-and-or ladder otherwise.  The host builds of this header (the
 // unit tests of the kernel logic, the sanitized cores, the host pass of hipcc) keep the portable code; tests/test_gpu_byteops.py pins the
@@ -223,6 +230,12 @@ template <int A = NW> VTXF_FN M192 m_range(int lo, int hi) {             // bits
     VTXF_UNROLL
     for (int k = 0; k < NW; ++k) r.w[k] = k < A ? ones_below(hi - 64 * k) & ~ones_below(lo - 64 * k) : 0ull;
     return r;
+}
+// bit i of a mask, 0 <= i < MAX_READ, i known at run time only: a three-way select of the 64-bit word, then one shift (selecting the
+// dword and shifting 32 bits was counted in round 19: 37 VALU instructions more in band_diag_kernel)
+VTXF_FN bool m_bit(const M192& a, int i) {
+    const uint64_t w = i < 64 ? a.w[0] : (i < 128 ? a.w[1] : (NW > 3 && i >= 192 ? a.w[NW - 1] : a.w[2]));
+    return ((w >> (i & 63)) & 1ull) != 0;
 }
 // lowest set bit: its index (MAX_READ: none), cleared in a
 VTXF_FN int m_pop_lowest(M192& a) {
@@ -718,8 +731,7 @@ VTXF_UNROLL
             const int y = (int)((w >> (16 * j)) & 0xffu), y2 = (int)((w >> (16 * j + 8)) & 0xffu);
             const int row = y - fr.d;
             if (i0 + j >= cnt || row < 0 || row > m - K) continue;
-            const uint64_t nw = row < 64 ? fr.need.w[0] : (row < 128 ? fr.need.w[1] : (NW > 3 && row >= 192 ? fr.need.w[NW - 1] : fr.need.w[2]));
-            if ((nw >> (row & 63)) & 1ull) continue;                         // the row's k-mer is not intact: it is probed
+            if (m_bit(fr.need, row)) continue;                                // the row's k-mer is not intact: it is probed
             if (ns < LN::SMAX) ln.s(ns) = (typename LN::SType)(((uint32_t)row << LN::XS) | (uint32_t)y2);
             ++ns;
         }
@@ -857,21 +869,28 @@ template <class PL> VTXF_FN uint32_t harmless_item(const PL& pl, int r, int d, i
 }
 // the same against up to four main pieces held in registers (a piece word of 0 is no piece: it ends before it starts) — the usual task
 // has one to three, and the per-match loop over the lane's LDS words was a chain of dependent round trips
+// (no compare and select in front of the maximum and the minimum: the two conditions are a third, steep line each.  With a = min(sx,
+//  sy - d) and b = max(sx, sy - d), both taken only as far as a piece can tell them apart (pieces lie within 256 bases),
+//      t >= 0    <=>  a >= pu + K (and the piece exists),   its value   min(3 a + dpf - pu - K, the piece's last match)
+//      t0 <= lm1 <=>  b <= pv - 5 - K (and the piece exists), its value max(dpf + 2 pu, 3 b + dpf - pu + 3 K)
+//  and (a - pu - K) * 2^20 + 2^11 is above every value (< 2^11) where the first holds and below -2^19 where it does not — no such
+//  value survives "bv - q + 1 > 0", q > -2^17 —, (b - (pv - 5 - K)) * 2^20 at most 0 where the second holds and at least 2^20 where it
+//  does not, beyond best_dp + q.  What depends on the piece alone is the same for every match of the task.)
 VTXF_FN uint32_t harmless_item4(const uint32_t (&pw4)[4], int d, int best_dp, int sx, int sy) {
     const int q = sx + sy - d;
-    const int lim = imin(sx, sy - d) - K;
-    int bv = -1000000, minH = 1000000;
+    const int a = imax(imin(imin(sx, sy - d), 300), -1), b = imin(imax(sx, sy - d), 300);
+    const int a3 = 3 * a, b3 = 3 * b, as = a * (1 << 20), bs = b * (1 << 20);
+    int bv = -(1 << 29), minH = 1 << 29;
     VTXF_UNROLL
     for (int i = 0; i < 4; ++i) {
         const uint32_t pw = pw4[i];
         const int pu = (int)(pw & 0xffu), pv = (int)((pw >> 8) & 0xffu), dpf = (int)((pw >> 16) & 0xffu);
-        const int lm1 = pv - 5 - pu;
-        const int t = imin(lim - pu, lm1);
-        if (t >= 0) bv = imax(bv, dpf + t + 2 * (pu + t + K));
-        const int t0 = imax(0, imax(sx + K - pu, sy + K - d - pu));
-        if (t0 <= lm1) minH = imin(minH, dpf + 3 * t0 + 2 * pu);
+        const bool is = pv - 5 - pu >= 0;                                     // (a piece word of 0 is no piece)
+        const int ta = is ? pu + K : 1000, tb = is ? pv - 5 - K : -700;       // a >= ta: a main match ends before s; b <= tb: one starts after it ends
+        bv = imax(bv, imin(imin(a3 + (dpf - pu - K), dpf + 3 * pv - pu - 3), as + ((1 << 11) - ta * (1 << 20))));
+        minH = imin(minH, imax(imax(dpf + 2 * pu, b3 + (dpf - pu + 3 * K)), bs - tb * (1 << 20)));
     }
-    const int A = bv > -1000000 ? imin(imax(bv - q + 1, 0), 255) : 0;
+    const int A = imin(imax(bv - q + 1, 0), 255);
 #if VTXF_MUTANT == 5
     const int T = imin(imax(imin(best_dp, minH - q - 2 * K), 0), 255);        // (mutant: one closer still counts as harmless)
 #else
@@ -922,6 +941,9 @@ template <class LN> VTXF_FN bool back_harmless(const Front& fr, int ns, const LN
     } else {
         int runmax = 0;
         if (fr.r <= 4) {
+            // harmless_item4's steep lines rest on |sy - d| and |q| < 2^17 and on piece words of three bytes: entries hold x in a byte
+            // and y in at most 16 bits, d is a diagonal of such a y
+            static_assert(LN::XS <= 16 && LN::YM <= 0xffffu, "harmless_item4: coordinates of at most 16 bits");
             uint32_t pw4[4];
             VTXF_UNROLL
             for (int i = 0; i < 4; ++i) pw4[i] = i < fr.r ? (ln.at(i) & 0x00ffffffu) : 0u;
@@ -955,6 +977,17 @@ template <class LN> VTXF_FN int32_t back(const Front& fr, int ns, const LN& ln, 
     if (!back_harmless(fr, ns, ln)) { *why = W_NOT_HARMLESS; return -1; }
     return back_rest(fr, ns, ln, gl, why, ablate, rf, aux);
 }
+// One far match at distance D in the seven cumulative counters (bytes 0-3 of lo, 0-2 of hi): byte j gains one iff D < 6, 8, 12, 16 | 24,
+// 32, 40 — what  cum += 0x0001010101010101 << 8 bin,  bin = (D >= 6) + (D >= 8) + (D >= 12) + (D >= 16) + (D >= 24) + (D >= 32),  adds
+// for D < 40, and nothing beyond — without the bin: D in every byte, subtracted from 0x80 + the byte's last distance.  Bit 7 of a
+// byte survives iff D is within it, and no borrow crosses a byte (D is capped at 127 first, which is beyond every counter).
+VTXF_FN void closure_count(uint32_t D, uint32_t& lo, uint32_t& hi) {
+    const uint32_t c = D < 127u ? D : 127u;
+    uint32_t rep = c | (c << 8);
+    rep |= rep << 16;
+    lo += ((0x8f8b8785u - rep) >> 7) & 0x01010101u;
+    hi += ((0x00a79f97u - rep) >> 7) & 0x00010101u;                // (the top byte borrows from nowhere and is masked)
+}
 // One scan of the closure (below): the far match nearest to the hull [hull_lo, hull_hi] of the generic diagonals when the far matches
 // (those not in `used`) violate condition (*) — the piece the generic set must take in next —, -1 when the set is complete.
 // Far matches are binned by their distance D from the hull; the cumulative count up to a bin's upper edge must stay within
@@ -963,26 +996,29 @@ template <class LN> VTXF_FN int closure_scan(int d, int nc, const LN& ln, uint64
     constexpr int XS = LN::XS;
     constexpr uint32_t YM = LN::YM;
     // cumulative counters, one byte each: D <= 5, 7, 11, 15, 23, 31, 39 (a match at D >= 40 > ns can never be in the way)
-    uint64_t cum = 0;
-    int near_k = -1, near_d = 1 << 20;
+    uint32_t cum_lo = 0, cum_hi = 0;
+    // the nearest far match as ONE word, D << 8 | k (k < 64; the first of equal distances has the smaller word, as a strict
+    // "D < nearest so far" in list order keeps it); a match that is not far is distance 0xffffffff: it counts in no bin and is
+    // never the nearest
+    uint32_t near = 0xffffffffu;
     for (int k0 = 0; k0 < nc; k0 += 4) {               // (four words per trip, loaded together)
         uint32_t w4[4];
         VTXF_UNROLL
         for (int j = 0; j < 4; ++j) w4[j] = ln.s(imin(k0 + j, nc - 1));
+        // bit j: match k0 + j is in the generic set already, or beyond the list's end
+        const uint32_t skip = (uint32_t)(used >> k0) | (~0u << imin(nc - k0, 4));
         VTXF_UNROLL
         for (int j = 0; j < 4; ++j) {
-            const int k = k0 + j;
-            if (k >= nc || ((used >> k) & 1ull)) continue;
             const uint32_t w = w4[j];
             const int delta = (int)(w & YM) - (int)(w >> XS) - d;
-            const int D = delta > hull_hi ? delta - hull_hi : (delta < hull_lo ? hull_lo - delta : 0);
-            if (D < near_d) { near_d = D; near_k = k; }
-            if (D < 40) {
-                const int bin = (D >= 6) + (D >= 8) + (D >= 12) + (D >= 16) + (D >= 24) + (D >= 32);
-                cum += 0x0001010101010101ull << (8 * bin);
-            }
+            // hull_lo <= hull_hi: at most one of the two differences is positive
+            const uint32_t D = (uint32_t)imax(imax(delta - hull_hi, hull_lo - delta), 0) | (0u - ((skip >> j) & 1u));
+            near = near < ((D << 8) | (uint32_t)(k0 + j)) ? near : ((D << 8) | (uint32_t)(k0 + j));
+            closure_count(D, cum_lo, cum_hi);
         }
     }
+    const uint64_t cum = (uint64_t)cum_lo | ((uint64_t)cum_hi << 32);
+    const int near_k = near >= 0xffffff00u ? -1 : (int)(near & 0xffu), near_d = (int)(near >> 8);
     if (near_k < 0) return -1;                                    // nothing is far
 #if VTXF_MUTANT == 6
     bool ok = near_d >= 3;                                         // (mutant: a far piece three diagonals out)
