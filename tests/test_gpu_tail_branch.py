@@ -159,7 +159,7 @@ def test_context_reuse():
 
 def test_tail_routes_nothing_to_the_main_branch():
     """libvtx_dev.so counts the records band_tail_kernel's routing sends towards dense_list / fail_list although a tight list exists
-    (VTX_CNT_TAIL_STRAY; printed with VTX_DEBUG's statistics): 0 on every batch.  Inline, so that such a record would be counted and
+    (vtx_band_counters::tail_stray; printed with VTX_DEBUG's statistics): 0 on every batch.  Inline, so that such a record would be counted and
     listed, not written through the null lists of the side launch."""
     out, err = run_dev({"VTX_DEBUG": "1", "VTX_BAND_TAIL_INLINE": "1"})
     stray = [int(n) for n in re.findall(r"band_tail_kernel: (\d+) records routed towards the dense or fail list", err)]

@@ -105,17 +105,14 @@ enum EvSlot {
 };
 enum PrepEv { EV_PREP_START = 0, EV_PREP_END = 1 };                                                // the same array in vtx_submit_raw: around the preparation
 enum IngestEv { EV_INGEST_START = 0, EV_INFLATE_END = 1, EV_INDEX_END = 2, EV_FILTER_END = 3 };    // ... and in vtx_submit_bam: its phases
-// vtx_ctx::h_pin: counter words copied back asynchronously.
-enum PinWord {
-    PIN_GENERAL_HARD = 0, PIN_GENERAL_AGAIN = 1,                        // fallback_launch copies VTX_CNT_GENERAL_HARD, _AGAIN here (side stream); fallback_finish reads both
-    PIN_RUN_LEFT = 8, PIN_DENSE = 9, PIN_REFINE = 10, PIN_TIGHT = 11,   // diag_sweep_path copies VTX_CNT_RUN_LEFT .. VTX_CNT_TIGHT here and reads them
-    PIN_R3_REFINE = 9,      // diag_round3_path copies and reads PIN_RUN_LEFT, and VTX_CNT_REFINE here: no dense list on that path, PIN_DENSE's word is free
-    PIN_FORK_TIGHT = 12,    // diag_sweep_path copies VTX_CNT_TIGHT on the side stream (forked); collect_sweep_times reads
-    PIN_TAIL = 13,          // diag_sweep_path copies VTX_CNT_TAIL here (band_tail_kernel on the side stream) and reads it: what that kernel may still append
-    PIN_FORK_REFINE = 17,   // diag_sweep_path copies VTX_CNT_REFINE on the side stream (band_tail_kernel there); collect_sweep_times reads
-    PIN_DIAG2_LEFT = 14, PIN_DIAG2_TIGHT = 15,                          // second_stage copies VTX_CNT_DIAG2_LEFT, _TIGHT here and reads both
-    PIN_STREAMED = 16,      // second_stage copies VTX_CNT_STREAMED here and reads it
-    PIN_WORDS = 64
+// vtx_ctx::h_pin: the counters of the banded stage that are read back asynchronously.  A member has the type of the vtx_band_counters member it mirrors (read_back).
+struct PinnedCounters {
+    vtx_cnt_pair general;                   // GeneralFallback::launch copies (side stream); finish reads
+    vtx_band_counters::lists_t lists;       // diag_sweep_path copies the group and reads it; diag_round3_path copies and reads run_left and refine, the two lists that path has
+    uint32_t tail;                          // diag_sweep_path copies (band_tail_kernel on the side stream) and reads: what that kernel may still append
+    uint32_t fork_tight, fork_refine;       // diag_sweep_path copies lists.tight (forked) and lists.refine (band_tail_kernel there) on the side stream; collect_sweep_times reads
+    vtx_band_counters::diag2_t diag2;       // second_stage copies and reads
+    uint32_t streamed;                      // likewise
 };
 
 thread_local std::string g_create_err;
@@ -144,7 +141,7 @@ struct vtx_ctx {
     int comm_rank = 0, comm_world = 0;
     DevBuf d_g_cnt, d_g_row, d_g_col, d_g_alt, d_g_ref, d_g_unk, d_g_val, d_g_refval;
     uint64_t g_nnz = 0;
-    uint32_t* h_pin = nullptr;               // pinned words for counters read back asynchronously (a D2H copy into pageable
+    PinnedCounters* h_pin = nullptr;         // pinned memory for counters read back asynchronously (a D2H copy into pageable
                                              // memory blocks the host until the stream reaches it)
     hipEvent_t ev[EV_COUNT] = {};
     hipEvent_t ev_crc[2] = {};               // around bgzf_crc32_kernel (vtx_submit_bam, vtx_debug_crc32)
@@ -913,7 +910,7 @@ static int band_reserve(vtx_ctx* c, BandPlan& p, bool quiet) {
     RES(d_band, (size_t)p.slots * 2 * p.band_stride * sizeof(uint16_t));
     RES(d_hard, ((size_t)p.hard_cap + p.pend_cap) * sizeof(uint32_t));
     RES(d_over, 4 * (size_t)p.n_tasks * sizeof(uint32_t));   // [0, 2n): band_run_kernel's overflows and their second-chance appends; [2n, 4n): what band_sweep_kernel declines (its own region: the appends of an overflowing chunk cannot reach it)
-    RES(d_cnt, 64 * sizeof(uint32_t));
+    RES(d_cnt, sizeof(vtx_band_counters));
     if (p.gt_bytes) RES(d_fail, 2 * (size_t)p.chunk * sizeof(uint32_t));  // tasks band_diag_kernel leaves to band_run_kernel (as listed, then sorted)
     if (p.gt_bytes) RES(d_refine, (size_t)band_refine_cap(p.chunk) * vtxk_band_refine_words() * sizeof(uint32_t));   // records for band_refine_kernel
     if (p.gt_bytes && c->d_tail.reserve((size_t)band_tail_cap(p.chunk) * vtxk_band_tail_words() * sizeof(uint32_t)) != hipSuccess) {
@@ -1698,19 +1695,25 @@ struct BandKnobs {
     bool no_corridor = VTX_DEV_ENV("VTX_BAND_NO_CORRIDOR") != nullptr;          // round 3's band_refine_kernel instead of band_corridor_kernel
     uint32_t run_min = env_u32(VTX_DEV_ENV("VTX_BAND_RUN_MIN"), 10, 65536u);    // the shortest list worth band_run_kernel's launch (see repeats)
     bool no_split = VTX_DEV_ENV("VTX_BAND_NO_SPLIT") != nullptr;                // test hook: the single pass of rounds 3 - 5
-    bool sweep_stats = getenv("VTX_DEBUG") != nullptr;                          // band_sweep_kernel counts its reasons
-    int diag_stats = getenv("VTX_DEBUG") ? 1 : 0;                               // band_diag_kernel and its followers count theirs
+    bool debug = getenv("VTX_DEBUG") != nullptr;                                // the [vtx] lines on stderr
+    bool sweep_stats = debug;                                                   // band_sweep_kernel counts its reasons
+    int diag_stats = debug ? 1 : 0;                                             // band_diag_kernel and its followers count theirs
 };
 const BandKnobs& band_knobs() { static const BandKnobs k; return k; }
 // What the stages of one vtx_run share.  a: the batch's arrays, filled once per run from the context; stage: one byte per task saying which stage decided it (vtx_fetch_stage), or nullptr
 struct RunState { vtx_task_arrays a{}; uint8_t* stage = nullptr; uint32_t launches = 0, hard_total = 0; float band_run_ms = 0; };
+
+// A member of the banded stage's counter block (vtx_band_counters, device memory) zeroed, and copied to the host: to the member of the same type in PinnedCounters (does not
+// block), or to pageable memory (blocks until the stream reaches the copy).  The size is the member's.
+template <class T> hipError_t zero(T& member, hipStream_t st) { return hipMemsetAsync(&member, 0, sizeof(T), st); }
+template <class T> hipError_t read_back(T& host, const T& member, hipStream_t st) { return hipMemcpyAsync(&host, &member, sizeof(T), hipMemcpyDeviceToHost, st); }
 
 // ---- vtx_run: one pass of the banded stages ---------------------------------------------------------------------------------------
 // Tasks [t_begin, t_end) whose locus has its longer haplotype in (mh_min, mh] (the others are left alone); chunk_tables: the tables are built per chunk for the loci the chunk spans, whatever the
 // buffer would hold. Per chunk of tasks (task = 2*record + hap), round 4 (the stages are described in vtx_band.hip's header): tables -> band_diag_kernel (+ band_refine_kernel): scores of the
 // certified tasks, and three lists — tasks whose band is one diagonal stretch (masked DP straight from one word), repeats (band_sweep_kernel + masked DP), the others (band_run_kernel: seeds,
 // chain, general certificate; its hard list -> expand -> masked DP).  What overflows band_run_kernel's lists joins the repeats after the last chunk; what band_sweep_kernel declines twice takes
-// the general band kernel (side stream). The counters are VtxBandCnt (vtx_device.h), the words read back through pinned memory PinWord, the events EvSlot.
+// the general band kernel (side stream). The counters are vtx_band_counters (vtx_device.h), what is read back through pinned memory PinnedCounters, the events EvSlot.
 struct BandPass {
     vtx_ctx* const c;
     RunState& rs;
@@ -1722,25 +1725,20 @@ struct BandPass {
     hipStream_t s = c->stream, s2 = nullptr;
     BandPlan bp;
     bool gt_chunked = false, sweep_path = false;
-    uint32_t* d_cnt = nullptr;
+    vtx_band_counters* d_cnt = nullptr;
     const int* shape = kShapes[0];              // the masked DP's (rows per lane, lanes per record) for the batch's longest read
     uint32_t *tight_list = nullptr, *tight_pack = nullptr, *dense_list = nullptr, *refine_list = nullptr, refine_cap = 0;   // band_diag_kernel's other outputs
     // The launchers' bundles that hold for the whole pass, built once in run(): the pass's shape; the lists of band_diag_kernel and the kernels over its records; band_run_kernel's outputs
     vtx_band_shape sh{};
     vtx_diag_routes routes{};
     vtx_band_out run_out{};
-    // The general band kernel (tasks band_run_kernel could not hold) is a handful of serial lanes: ~4.5 ms of latency for 0.1 % of config 3.  It runs on a side
-    // stream, with its own hard list; started once the overflow list is complete, finished (slabs grow until every task fits) after the main path's launches are queued.
-    struct { uint32_t n_over = 0, cap2 = 0, todo = 0, off = 0, total = 0; const uint32_t* tasks = nullptr; bool active = false; uint32_t n_hard = 0, n_again = 0; } fb;
-    uint32_t cnt[VTX_CNT_PENDING + 1] = {0};    // host copy of the block's first words
+    vtx_band_counters::run_t cnt{};             // host copy of band_run_kernel's counters
     uint32_t pending_total = 0, over_before = 0, resweep_total = 0;
     uint64_t diag_total = 0, diag_left = 0, refined_total = 0, checked_total = 0, swept_total = 0, diag2_total = 0, diag2_scored = 0, tight2_total = 0, stream_total = 0;
     float diag_ms = 0, check_ms = 0, sweep_ms = 0;
     bool sweep_used = false;                    // some chunk took the round-4 path
-    bool sweep_pending = false;                 // the events of a swept chunk have not been read yet
-    bool sweep_forked = false;                  // ... and that chunk ran its two branches side by side
-    bool sweep_tail_side = false;               // ... with band_tail_kernel on the side one
-    uint32_t fork_nt = 0;
+    // a swept chunk whose events (and, forked, final counts) collect_sweep_times has not read yet: whether it ran its two branches side by side, with band_tail_kernel on the side one; its tasks
+    struct OpenSweep { bool open = false, forked = false, tail_side = false; uint32_t nt = 0; } open_sweep;
     // one chunk of tasks [base, base + nt): the loci whose tables are resident, and what band_diag_kernel left for band_run_kernel
     struct Chunk { uint64_t base; uint32_t nt; bool last; vtx_band_tables tb{}; bool diag = false, swept = false; uint32_t n_fail = 0; const uint32_t* fail_list = nullptr;
                    vtx_rec_buf tail{}; bool tail_side = false;          // band_tail_kernel's record buffer; whether diag_sweep_path launches that kernel on the side stream
@@ -1751,14 +1749,14 @@ struct BandPass {
         bp = band_plan(c->n_records, c->n_loci, mh);
         if (int rc = band_reserve(c, bp, false)) return rc;
         gt_chunked = bp.gt_bytes && (bp.gt_loci < c->n_loci || chunk_tables);
-        d_cnt = c->d_cnt.as<uint32_t>();
+        d_cnt = c->d_cnt.as<vtx_band_counters>();
         int k = 0;
         while ((uint32_t)(kShapes[k][0] * kShapes[k][1]) < c->max_read_len) ++k;
         shape = kShapes[k];
         if (!c->stream2) {
             HIP_TRY(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
             HIP_TRY(c, hipEventCreateWithFlags(&c->ev2, hipEventDisableTiming));
-            HIP_TRY(c, hipHostMalloc((void**)&c->h_pin, PIN_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+            HIP_TRY(c, hipHostMalloc((void**)&c->h_pin, sizeof(PinnedCounters), hipHostMallocDefault));
         }
         s2 = c->stream2;
         // Round 4's path (sweep + masked DP for what the certificate stages leave), or round 3's (VTX_BAND_LEGACY=1; a haplotype above 255 bases)
@@ -1771,8 +1769,8 @@ struct BandPass {
         refine_list = kn.no_refine ? nullptr : c->d_refine.as<uint32_t>();
         sh = vtx_band_shape{mh, mh_min, c->max_read_len, bp.tasks_per_locus};
         routes = vtx_diag_routes{c->d_fail.as<uint32_t>(), refine_list, refine_cap, d_cnt, kn.diag_stats, tight_list, tight_pack, rs.stage, dense_list, kn.dense_mask};
-        run_out = vtx_band_out{c->d_poly.as<uint16_t>(), bp.poly_stride / 2, c->d_hard.as<uint32_t>(), c->d_over.as<uint32_t>(), d_cnt};
-        HIP_TRY(c, hipMemsetAsync(d_cnt, 0, VTX_CNT_WORDS * sizeof(uint32_t), s));
+        run_out = vtx_band_out{c->d_poly.as<uint16_t>(), bp.poly_stride / 2, c->d_hard.as<uint32_t>(), c->d_over.as<uint32_t>(), nullptr, d_cnt};
+        HIP_TRY(c, zero(*d_cnt, s));
         for (uint64_t base = t_begin; base < t_end; base += bp.chunk) {
             Chunk ch{base, (uint32_t)std::min<uint64_t>(bp.chunk, t_end - base), base + bp.chunk >= t_end};
             ch.fail_list = c->d_fail.as<uint32_t>();
@@ -1794,87 +1792,97 @@ struct BandPass {
         }
         return VTX_OK;
     }
-    // the half of d_over2 the general kernel's current list is not in: where it writes the tasks that need a larger slab
-    uint32_t* fallback_other() const { return c->d_over2.as<uint32_t>() + ((fb.tasks == c->d_over2.as<uint32_t>()) ? fb.n_over : 0); }
-    int fallback_launch() {
-        // A few overflow tasks (shallow data: some hundreds per run) first try the in-LDS variant of the general kernel
-        // with a slab for kLdsMatches k-mer matches: their ~2 ms of serial HBM latency were a third of a shallow step.
-        const uint32_t kLdsMatches = 512;
-        const uint64_t worst = (uint64_t)c->max_read_len * mh;
-        if (fb.cap2 >= worst && fb.cap2 >= 512) return fail(c, VTX_E_STATE, "vtx_run: band kernel overflow with a worst-case slab");
-        // first three rounds: the cooperative kernel, everything in LDS (band_coop_kernel: a wavefront per task, up to 512 matches,
-        // then 1024, then 4096; reads up to 256 bases); what that cannot hold takes the serial kernel below
-        const int tier = fb.cap2 < 512 ? 0 : (fb.cap2 == 512 ? 1 : (fb.cap2 == 1024 ? 2 : -1));
-        const uint32_t tier_cap = tier == 0 ? 512u : (tier == 1 ? 1024u : 4096u);
-        // (haplotypes up to 1000 bases: the kernel walks its Fenwick tree in ten unrolled steps, tn = n + 8 < 1024)
-        const bool coop = tier >= 0 && !kn.no_coop && c->max_read_len <= 256 && mh <= 1000 && vtxk_band_coop_lds(mh, tier_cap) <= 64u * 1024;
-        // (its own band slots and hard list; the tasks that need a larger slab go to the other half of d_over2)
-        const vtx_band_out out{c->d_band2.as<uint16_t>(), bp.band_stride, c->d_hard2.as<uint32_t>(), fallback_other(), d_cnt + VTX_CNT_GENERAL_HARD};
-        if (coop) {
-            fb.cap2 = tier_cap;
-            HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_GENERAL_AGAIN, 0, sizeof(uint32_t), s2));
-            HIP_TRY(c, vtxk_launch_band_coop(a, tier, fb.tasks, fb.todo, sh, out, s2));
-        } else {
-            const bool in_lds = fb.cap2 < 512 && fb.todo <= kn.lds_tasks && !VTX_DEV_ENV("VTX_BAND_NO_LDS_FALLBACK") && vtxk_band_lds_stride(kLdsMatches, mh, c->max_read_len) <= 160 * 1024 - 512;
-            fb.cap2 = in_lds ? kLdsMatches : (uint32_t)std::max<uint64_t>(std::min<uint64_t>((uint64_t)fb.cap2 * 16, worst), 512);
-            const size_t stride2 = vtxk_band_ws_stride(fb.cap2, mh);
-            if (!in_lds) {                                                  // whole wavefronts: the 64 slabs are interleaved, vtxk_band_lanes() of them in use
-                const size_t lanes = vtxk_band_lanes(fb.todo);
-                HIP_TRY(c, c->d_band_ws2.reserve(lanes < 64 ? (size_t)fb.todo * stride2 : ((size_t)fb.todo + 63) / 64 * 64 * stride2));   // (sparse lanes: a contiguous slab per task)
+    // The general band kernel (tasks band_run_kernel could not hold) is a handful of serial lanes: ~4.5 ms of latency for 0.1 % of config 3.  It runs on a side
+    // stream, with its own hard list; started once the overflow list is complete, finished (slabs grow until every task fits) after the main path's launches are queued.
+    struct GeneralFallback {
+        BandPass& pass;                         // (its masked DP and its counter block)
+        vtx_ctx* const c = pass.c; const BandKnobs& kn = pass.kn; const vtx_task_arrays& a = pass.a; const vtx_band_shape& sh = pass.sh; const BandPlan& bp = pass.bp; RunState& rs = pass.rs;
+        const hipStream_t& s2 = pass.s2;        // (the side stream: set in BandPass::run)
+        uint32_t n_over = 0, cap2 = 0, todo = 0, off = 0, total = 0; const uint32_t* tasks = nullptr; bool active = false; uint32_t n_hard = 0, n_again = 0;
+        explicit GeneralFallback(BandPass& p) : pass(p) {}
+        // the half of d_over2 the general kernel's current list is not in: where it writes the tasks that need a larger slab
+        uint32_t* other() const { return c->d_over2.as<uint32_t>() + ((tasks == c->d_over2.as<uint32_t>()) ? n_over : 0); }
+        int launch() {
+            // A few overflow tasks (shallow data: some hundreds per run) first try the in-LDS variant of the general kernel
+            // with a slab for kLdsMatches k-mer matches: their ~2 ms of serial HBM latency were a third of a shallow step.
+            const uint32_t kLdsMatches = 512, mh = sh.max_hap;
+            const uint64_t worst = (uint64_t)c->max_read_len * mh;
+            if (cap2 >= worst && cap2 >= 512) return fail(c, VTX_E_STATE, "vtx_run: band kernel overflow with a worst-case slab");
+            // first three rounds: the cooperative kernel, everything in LDS (band_coop_kernel: a wavefront per task, up to 512 matches,
+            // then 1024, then 4096; reads up to 256 bases); what that cannot hold takes the serial kernel below
+            const int tier = cap2 < 512 ? 0 : (cap2 == 512 ? 1 : (cap2 == 1024 ? 2 : -1));
+            const uint32_t tier_cap = tier == 0 ? 512u : (tier == 1 ? 1024u : 4096u);
+            // (haplotypes up to 1000 bases: the kernel walks its Fenwick tree in ten unrolled steps, tn = n + 8 < 1024)
+            const bool coop = tier >= 0 && !kn.no_coop && c->max_read_len <= 256 && mh <= 1000 && vtxk_band_coop_lds(mh, tier_cap) <= 64u * 1024;
+            // (its own band slots and hard list; the tasks that need a larger slab go to the other half of d_over2)
+            vtx_cnt_pair& cnt = pass.d_cnt->general;
+            const vtx_band_out out{c->d_band2.as<uint16_t>(), bp.band_stride, c->d_hard2.as<uint32_t>(), other(), &cnt};
+            if (coop) {
+                cap2 = tier_cap;
+                HIP_TRY(c, zero(cnt.overflow, s2));
+                HIP_TRY(c, vtxk_launch_band_coop(a, tier, tasks, todo, sh, out, s2));
+            } else {
+                const bool in_lds = cap2 < 512 && todo <= kn.lds_tasks && !VTX_DEV_ENV("VTX_BAND_NO_LDS_FALLBACK") && vtxk_band_lds_stride(kLdsMatches, mh, c->max_read_len) <= 160 * 1024 - 512;
+                cap2 = in_lds ? kLdsMatches : (uint32_t)std::max<uint64_t>(std::min<uint64_t>((uint64_t)cap2 * 16, worst), 512);
+                const size_t stride2 = vtxk_band_ws_stride(cap2, mh);
+                if (!in_lds) {                                                  // whole wavefronts: the 64 slabs are interleaved, vtxk_band_lanes() of them in use
+                    const size_t lanes = vtxk_band_lanes(todo);
+                    HIP_TRY(c, c->d_band_ws2.reserve(lanes < 64 ? (size_t)todo * stride2 : ((size_t)todo + 63) / 64 * 64 * stride2));   // (sparse lanes: a contiguous slab per task)
+                }
+                HIP_TRY(c, zero(cnt.overflow, s2));
+                HIP_TRY(c, vtxk_launch_band(a, tasks, todo, 0, c->d_band_ws2.as<uint8_t>(), stride2, cap2, sh, out, in_lds ? 1 : 0, s2));
             }
-            HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_GENERAL_AGAIN, 0, sizeof(uint32_t), s2));
-            HIP_TRY(c, vtxk_launch_band(a, fb.tasks, fb.todo, 0, c->d_band_ws2.as<uint8_t>(), stride2, fb.cap2, sh, out, in_lds ? 1 : 0, s2));
+            HIP_TRY(c, read_back(c->h_pin->general, cnt, s2));   // pinned: does not block
+            ++rs.launches;
+            return VTX_OK;
         }
-        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_GENERAL_HARD, d_cnt + VTX_CNT_GENERAL_HARD, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s2));   // pinned: does not block
-        ++rs.launches;
-        return VTX_OK;
-    }
-    int fallback_start(uint32_t off, uint32_t total) {   // the overflow list d_over[0, total) is complete and visible
-        const uint32_t n_over = std::min(std::max(bp.slots, 1024u), total - off);   // slices (bounds d_band2)
-        fb.off = off; fb.total = total; fb.n_over = n_over; fb.todo = n_over; fb.cap2 = 512 / 16; fb.tasks = c->d_over.as<uint32_t>() + off; fb.active = true;
-        HIP_TRY(c, c->d_over2.reserve(2 * (size_t)n_over * sizeof(uint32_t)));
-        HIP_TRY(c, c->d_hard2.reserve((size_t)n_over * sizeof(uint32_t)));
-        HIP_TRY(c, c->d_band2.reserve((size_t)n_over * 2 * bp.band_stride * sizeof(uint16_t)));
-        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_GENERAL_HARD, 0, 2 * sizeof(uint32_t), s2));
-        return fallback_launch();
-    }
-    int fallback_finish() {
-        if (!fb.active) return VTX_OK;
-        for (;;) {
+        int start(uint32_t off_, uint32_t total_) {   // the overflow list d_over[0, total) is complete and visible
+            n_over = std::min(std::max(bp.slots, 1024u), total_ - off_);   // slices (bounds d_band2)
+            off = off_; total = total_; todo = n_over; cap2 = 512 / 16; tasks = c->d_over.as<uint32_t>() + off; active = true;
+            HIP_TRY(c, c->d_over2.reserve(2 * (size_t)n_over * sizeof(uint32_t)));
+            HIP_TRY(c, c->d_hard2.reserve((size_t)n_over * sizeof(uint32_t)));
+            HIP_TRY(c, c->d_band2.reserve((size_t)n_over * 2 * bp.band_stride * sizeof(uint16_t)));
+            HIP_TRY(c, zero(pass.d_cnt->general, s2));
+            return launch();
+        }
+        int finish() {
+            if (!active) return VTX_OK;
             for (;;) {
-                HIP_TRY(c, hipStreamSynchronize(s2));
-                fb.n_hard = c->h_pin[PIN_GENERAL_HARD]; fb.n_again = c->h_pin[PIN_GENERAL_AGAIN];
-                // tasks that still do not fit were written to the other half of d_over2: rerun them with a larger slab
-                fb.tasks = fallback_other();
-                fb.todo = fb.n_again;
-                if (!fb.todo) break;
-                if (int rc = fallback_launch()) return rc;
+                for (;;) {
+                    HIP_TRY(c, hipStreamSynchronize(s2));
+                    n_hard = c->h_pin->general.hard; n_again = c->h_pin->general.overflow;
+                    // tasks that still do not fit were written to the other half of d_over2: rerun them with a larger slab
+                    tasks = other();
+                    todo = n_again;
+                    if (!todo) break;
+                    if (int rc = launch()) return rc;
+                }
+                if (int rc = pass.masked_dp(n_hard, c->d_hard2.as<uint32_t>(), nullptr, c->d_band2.as<uint16_t>(), std::max(n_hard, 1u), s2, VTX_STAGE_GENERAL_DP)) return rc;
+                rs.hard_total += n_hard;
+                if (off + n_over >= total) break;
+                if (int rc = start(off + n_over, total)) return rc;      // next slice (same stream: in order)
             }
-            if (int rc = masked_dp(fb.n_hard, c->d_hard2.as<uint32_t>(), nullptr, c->d_band2.as<uint16_t>(), std::max(fb.n_hard, 1u), s2, VTX_STAGE_GENERAL_DP)) return rc;
-            rs.hard_total += fb.n_hard;
-            if (fb.off + fb.n_over >= fb.total) break;
-            if (int rc = fallback_start(fb.off + fb.n_over, fb.total)) return rc;      // next slice (same stream: in order)
+            HIP_TRY(c, hipEventRecord(c->ev2, s2));
+            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev2, 0));         // the reduction kernels read every score
+            return VTX_OK;
         }
-        HIP_TRY(c, hipEventRecord(c->ev2, s2));
-        HIP_TRY(c, hipStreamWaitEvent(s, c->ev2, 0));             // the reduction kernels read every score
-        return VTX_OK;
-    }
+    } fb{*this};
     // the band of every listed task (band_sweep_kernel), one slice of band slots at a time, then the masked DP over the slice (its length — the tasks the sweep did not decline — is read on the
     // device: counters[0]; declined: counters[1]) (libvtx_dev.so, VTX_SWEEP_V1=1: round 4's kernel instead — 256 sections per task (tier 0), then a second pass with 1 024 (tier 1) over what the
     // first declined.  tier means nothing to band_sweep_kernel: the production build ignores it; the parameter stays so that the callers read the same in both builds.)
-    int sweep_slices([[maybe_unused]] int tier, const uint32_t* list, uint32_t n, uint32_t* over_out, uint32_t* counters) {
-        uint32_t* why = kn.sweep_stats ? d_cnt + VTX_CNT_SWEEP_WHY : nullptr;
+    int sweep_slices([[maybe_unused]] int tier, const uint32_t* list, uint32_t n, uint32_t* over_out, vtx_cnt_pair* counters) {
+        uint32_t* why = kn.sweep_stats ? d_cnt->sweep_why : nullptr;
         HIP_TRY(c, c->d_sweep_log.reserve(vtxk_band_sweep_log_bytes()));
         const vtx_band_out out{c->d_band.as<uint16_t>(), bp.band_stride, c->d_hard.as<uint32_t>(), over_out, counters};
         for (uint32_t off = 0; off < n; off += bp.slots) {
             const uint32_t cnt_s = std::min(bp.slots, n - off);
-            HIP_TRY(c, hipMemsetAsync(counters, 0, sizeof(uint32_t), s));
+            HIP_TRY(c, zero(counters->hard, s));
 #ifdef VTX_DEVTOOLS
             if (kn.sweep_v1) HIP_TRY(c, vtxk_launch_band_sweep_v1(a, tier, list + off, cnt_s, nullptr, out, why, rs.stage, nullptr, s));
             else
 #endif
             HIP_TRY(c, vtxk_launch_band_sweep(a, list + off, cnt_s, nullptr, out, why, rs.stage, nullptr, c->d_sweep_log.as<uint32_t>(), s));
-            HIP_TRY(c, vtxk_launch_sw_banded_dev(a, shape[0], shape[1], cnt_s, out.hard_list, counters, out.band, out.band_stride, mh, s));
+            HIP_TRY(c, vtxk_launch_sw_banded_dev(a, shape[0], shape[1], cnt_s, out.hard_list, &counters->hard, out.band, out.band_stride, mh, s));
             rs.launches += 2;
         }
         return VTX_OK;
@@ -1884,24 +1892,24 @@ struct BandPass {
     // the table buffer as the stage that built them was handed it).
     bool second_stage_on(uint32_t n) const { return !kn.no_diag2 && n >= kn.diag2_min && mh <= 255; }
     int second_stage(const uint32_t* list, uint32_t n, const vtx_band_tables& tb, uint32_t* out, uint32_t* n_out) {
-        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_DIAG2_LEFT, 0, 2 * sizeof(uint32_t), s));
-        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_STREAMED, 0, sizeof(uint32_t), s));
-        HIP_TRY(c, vtxk_launch_band_diag2(a, list, n, sh, tb, out, c->d_tight2.as<uint32_t>(), c->d_tight2_pack.as<uint32_t>(), d_cnt + VTX_CNT_DIAG2_LEFT,
-                kn.no_stream ? nullptr : c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), d_cnt + VTX_CNT_STREAMED, rs.stage, s));
-        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_DIAG2_LEFT, d_cnt + VTX_CNT_DIAG2_LEFT, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_STREAMED, d_cnt + VTX_CNT_STREAMED, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, zero(d_cnt->diag2, s));
+        HIP_TRY(c, zero(d_cnt->streamed, s));
+        HIP_TRY(c, vtxk_launch_band_diag2(a, list, n, sh, tb, out, c->d_tight2.as<uint32_t>(), c->d_tight2_pack.as<uint32_t>(), &d_cnt->diag2.left,
+                kn.no_stream ? nullptr : c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), &d_cnt->streamed, rs.stage, s));
+        HIP_TRY(c, read_back(c->h_pin->diag2, d_cnt->diag2, s));
+        HIP_TRY(c, read_back(c->h_pin->streamed, d_cnt->streamed, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        stream_total += std::min(c->h_pin[PIN_STREAMED], n);
-        const uint32_t n_sweep = std::min(c->h_pin[PIN_DIAG2_LEFT], n);
-        const uint32_t n_tight2 = std::min(c->h_pin[PIN_DIAG2_TIGHT], n - n_sweep);
+        stream_total += std::min(c->h_pin->streamed, n);
+        const uint32_t n_sweep = std::min(c->h_pin->diag2.left, n);
+        const uint32_t n_tight2 = std::min(c->h_pin->diag2.tight, n - n_sweep);
         ++rs.launches;
         diag2_total += n; diag2_scored += n - n_sweep - n_tight2;
         if (n_tight2) {
             // certificate == full-matrix score decides practically all of them (cert <= banded <= full); the masked DP for the rest (count on the device)
-            HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_CHECK2, 0, sizeof(uint32_t), s));
+            HIP_TRY(c, zero(d_cnt->check2, s));
             HIP_TRY(c, vtxk_launch_sw_check(a, shape[0], shape[1], n_tight2, c->d_tight2.as<uint32_t>(), c->d_tight2_pack.as<uint32_t>(), nullptr, mh, c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(),
-                                            d_cnt + VTX_CNT_CHECK2, rs.stage, s));
-            HIP_TRY(c, vtxk_launch_sw_diag_band(a, shape[0], shape[1], n_tight2, c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), d_cnt + VTX_CNT_CHECK2, mh, rs.stage, s));
+                                            &d_cnt->check2, rs.stage, s));
+            HIP_TRY(c, vtxk_launch_sw_diag_band(a, shape[0], shape[1], n_tight2, c->d_recheck2.as<uint32_t>(), c->d_recheck2_pack.as<uint32_t>(), &d_cnt->check2, mh, rs.stage, s));
             // (its grid is sized for n_tight2 although a few hundred tasks remain: the workgroups past the device count leave at once)
             rs.launches += 2;
             tight2_total += n_tight2;
@@ -1909,17 +1917,17 @@ struct BandPass {
         *n_out = n_sweep; return 0;
     }
     int collect_sweep_times() {
-        if (!sweep_pending) return VTX_OK;
-        sweep_pending = false;
+        const OpenSweep sw = open_sweep;
+        open_sweep = OpenSweep{};
+        if (!sw.open) return VTX_OK;
         HIP_TRY(c, hipEventSynchronize(c->ev[EV_SWEEP_END]));
         float ms = 0;
         // BRANCH_START .. BRANCH_END: band_tail_kernel (when it runs on the side stream) + band_refine_kernel (forked only) + the one-diagonal bands' masked DP; then band_sweep_kernel + its
         // masked DP (the chunk's repeats) — forked: FORK_START .. SWEEP_END on the main stream, BESIDE the first interval, not after it
         HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_BRANCH_START], c->ev[EV_BRANCH_END])); check_ms += ms;
-        HIP_TRY(c, hipEventElapsedTime(&ms, sweep_forked ? c->ev[EV_FORK_START] : c->ev[EV_BRANCH_END], c->ev[EV_SWEEP_END])); sweep_ms += ms;
-        if (sweep_forked) checked_total += std::min(c->h_pin[PIN_FORK_TIGHT], fork_nt);          // (copied before BRANCH_END, which SWEEP_END waited for)
-        if (sweep_tail_side) refined_total += std::min(c->h_pin[PIN_FORK_REFINE], refine_cap);   // (likewise; band_tail_kernel's records included)
-        sweep_forked = false; sweep_tail_side = false;
+        HIP_TRY(c, hipEventElapsedTime(&ms, sw.forked ? c->ev[EV_FORK_START] : c->ev[EV_BRANCH_END], c->ev[EV_SWEEP_END])); sweep_ms += ms;
+        if (sw.forked) checked_total += std::min(c->h_pin->fork_tight, sw.nt);                // (copied before BRANCH_END, which SWEEP_END waited for)
+        if (sw.tail_side) refined_total += std::min(c->h_pin->fork_refine, refine_cap);       // (likewise; band_tail_kernel's records included)
         return VTX_OK;
     }
     // Sorts list[0, n) by task into `sorted` when it has more than 64 entries and the temporary buffer can be had; *at = where the list then is.  (Lists come out in the order the wavefronts
@@ -1937,9 +1945,9 @@ struct BandPass {
     // the chunk's counters, and the loci of this range of tasks (tables in global memory are built per range)
     int resident_tables(Chunk& ch) {
         if (int rc = collect_sweep_times()) return rc;                              // (a chunk re-records the events)
-        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_HARD, 0, sizeof(uint32_t), s));
-        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_PENDING, 0, sizeof(uint32_t), s));
-        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_BLOCK, 0, 8 * sizeof(uint32_t), s));
+        HIP_TRY(c, zero(d_cnt->run.hard, s));
+        HIP_TRY(c, zero(d_cnt->run.pending, s));
+        HIP_TRY(c, zero(d_cnt->block, s));
         uint32_t gt_l0 = 0, gt_n = bp.gt_bytes ? c->n_loci : 0;
         if (gt_chunked) {
             uint32_t ends[2];
@@ -1957,7 +1965,7 @@ struct BandPass {
     // Stage 1 (tables in global memory): band_diag_kernel decides the tasks whose alignment lives on one diagonal
     // (vtx_fast_core.h) and lists the others; band_run_kernel then takes that LIST instead of the whole range.
     int diag_stage(Chunk& ch) {
-        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_RUN_LEFT, 0, 4 * sizeof(uint32_t), s));   // RUN_LEFT, DENSE, REFINE, TIGHT
+        HIP_TRY(c, zero(d_cnt->lists, s));
         const uint32_t tail_cap = (uint32_t)std::min<size_t>(band_tail_cap(bp.chunk), c->d_tail.cap / (vtxk_band_tail_words() * sizeof(uint32_t)));
         const uint32_t tail_cap_hook = VTX_DEV_ENV("VTX_DIAG_TAIL_CAP") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_TAIL_CAP")) : 0xffffffffu;   // test hook: a small buffer (read per run)
         ch.tail = vtx_rec_buf{c->d_tail.as<uint32_t>(), std::min(tail_cap, tail_cap_hook)};
@@ -1972,7 +1980,7 @@ struct BandPass {
         const hipError_t e = vtxk_launch_band_diag(a, ch.nt, (uint32_t)ch.base, sh, ch.tb, routes, ch.tail, !ch.tail_side, ch.recheck, s);
         if (e != hipSuccess) {
             // (the tables do not fit the buffer for this chunk: band_run_kernel alone, tables in LDS)
-            if (getenv("VTX_DEBUG")) fprintf(stderr, "[vtx] band_diag_kernel not launched for tasks [%llu, +%u): %s\n", (unsigned long long)ch.base, ch.nt, hipGetErrorString(e));
+            if (kn.debug) fprintf(stderr, "[vtx] band_diag_kernel not launched for tasks [%llu, +%u): %s\n", (unsigned long long)ch.base, ch.nt, hipGetErrorString(e));
             (void)hipGetLastError(); return VTX_OK;
         }
         return sweep_path ? diag_sweep_path(ch) : diag_round3_path(ch);
@@ -1980,8 +1988,8 @@ struct BandPass {
     // the records band_diag_kernel left: with a tight list (round 6) every task that holds a certificate and a one-diagonal
     // band, for band_corridor_kernel; else (VTX_BAND_NO_TIGHT, libvtx_dev.so's VTX_BAND_NO_CORRIDOR) round 3's, for band_refine_kernel
     hipError_t second_look(const Chunk& ch, uint32_t n_rec, hipStream_t st) {
-        if (tight_list && !kn.no_corridor) return vtxk_launch_band_corridor(a, refine_list, n_rec, routes, d_cnt + VTX_CNT_REFINE, st);
-        return vtxk_launch_band_refine(a, refine_list, n_rec, sh, ch.tb, routes, d_cnt + VTX_CNT_REFINE, st);
+        if (tight_list && !kn.no_corridor) return vtxk_launch_band_corridor(a, refine_list, n_rec, routes, &d_cnt->lists.refine, st);
+        return vtxk_launch_band_refine(a, refine_list, n_rec, sh, ch.tb, routes, &d_cnt->lists.refine, st);
     }
     // What the stage left, in two branches over disjoint tasks: side stream — band_tail_kernel (tail_on_side), band_refine_kernel / band_corridor_kernel over its records, then the masked DP over the
     // one-diagonal bands; this stream — band_sweep_kernel + masked DP over the repeats and the short fail list.  One host round trip, right after band_diag_kernel.  (VTX_BAND_NO_TIGHT: the
@@ -1989,7 +1997,7 @@ struct BandPass {
     // (the two branches: a tight list to feed the side one, and no VTX_BAND_NO_FORK)
     bool fork_on() const { return tight_list != nullptr && !kn.no_fork; }
     // band_tail_kernel on the side stream, behind band_diag_kernel (EV_DIAG_END) and beside everything the main stream does from there on.  A task deferred to it passed back_harmless,
-    // so with a tight list it ends decided, as a refine / corridor record or as a tight entry (vtx_band.hip: band_tail_kernel): VTX_CNT_RUN_LEFT and VTX_CNT_DENSE, which the main branch
+    // so with a tight list it ends decided, as a refine / corridor record or as a tight entry (vtx_band.hip: band_tail_kernel): lists.run_left and lists.dense, which the main branch
     // starts from, are final when band_diag_kernel ends, and the side branch reads its own two counts on the device.  The kernel gets no fail_list and no dense_list: those are the main
     // branch's.  d_tail is free again at EV_BRANCH_END, which the main stream joins before the next chunk.
     // (It does not wait for the recheck on the main stream either.  Measured: started behind that kernel instead of beside it, the recheck takes what it takes beside the tail,
@@ -2010,33 +2018,34 @@ struct BandPass {
         if (ch.tail_side) { if (int rc = tail_on_side(ch)) return rc; }             // (before the host waits: it starts while band_diag_kernel drains)
         if (!fork && refine_list) HIP_TRY(c, second_look(ch, std::min(refine_cap, ch.nt), s));
         // The recheck, on THIS stream, in front of the counter copy: it appends to the fail (or dense) list what it does not clear and to the refine / tight lists what it does — beside
-        // band_tail_kernel on the side stream, through the same atomics — so the four counts below include everything it listed: RUN_LEFT and DENSE are final, REFINE and TIGHT are
+        // band_tail_kernel on the side stream, through the same atomics — so the four counts below include everything it listed: run_left and dense are final, refine and tight are
         // the bounds they were.  Its grid comes from the buffer's capacity and it reads its record count on the device: no round trip of its own.
         if (ch.recheck.cap) {
             HIP_TRY(c, vtxk_launch_band_recheck(a, sh, routes, ch.recheck, s));
             ++rs.launches;
         }
-        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_RUN_LEFT, d_cnt + VTX_CNT_RUN_LEFT, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // RUN_LEFT, DENSE, REFINE, TIGHT
-        if (ch.tail_side) HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_TAIL, d_cnt + VTX_CNT_TAIL, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        vtx_band_counters::lists_t& pin = c->h_pin->lists;
+        HIP_TRY(c, read_back(pin, d_cnt->lists, s));
+        if (ch.tail_side) HIP_TRY(c, read_back(c->h_pin->tail, d_cnt->tail, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        // band_tail_kernel on the side stream: REFINE and TIGHT are what that kernel had appended when the copy ran, and every one of its n_tail records may still become a record for the
+        // band_tail_kernel on the side stream: refine and tight are what that kernel had appended when the copy ran, and every one of its n_tail records may still become a record for the
         // second look or, that buffer full, a tight entry.  These two are BOUNDS for the grids; the kernels read the final counts on the device, the figures of vtx_timing arrive with the events.
-        const uint32_t n_tail = ch.tail_side ? std::min(c->h_pin[PIN_TAIL], ch.tail.cap) : 0u;
-        const uint32_t n_refine = (uint32_t)std::min<uint64_t>((uint64_t)c->h_pin[PIN_REFINE] + n_tail, refine_cap);
+        const uint32_t n_tail = ch.tail_side ? std::min(c->h_pin->tail, ch.tail.cap) : 0u;
+        const uint32_t n_refine = (uint32_t)std::min<uint64_t>((uint64_t)pin.refine + n_tail, refine_cap);
         // (forked: the tight list still grows by what the refinement leaves — at most its records)
-        const uint32_t n_tight = (uint32_t)std::min<uint64_t>((uint64_t)c->h_pin[PIN_TIGHT] + (fork && refine_list ? n_refine : 0u) + n_tail, ch.nt);
+        const uint32_t n_tight = (uint32_t)std::min<uint64_t>((uint64_t)pin.tight + (fork && refine_list ? n_refine : 0u) + n_tail, ch.nt);
         if (!ch.tail_side) refined_total += n_refine;                               // (else: collect_sweep_times)
         rs.launches += 2;
         if (fork && !ch.tail_side) HIP_TRY(c, hipStreamWaitEvent(s2, c->ev[EV_DIAG_END], 0));
         if (!ch.tail_side) HIP_TRY(c, hipEventRecord(c->ev[EV_BRANCH_START], sb));
         if (fork && refine_list && n_refine) HIP_TRY(c, second_look(ch, n_refine, sb));
         if (n_tight) { if (int rc = one_diagonal_dp(n_tight, fork, sb)) return rc; }
-        if (fork) HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_FORK_TIGHT, d_cnt + VTX_CNT_TIGHT, sizeof(uint32_t), hipMemcpyDeviceToHost, sb));   // the list's final length (read in collect_sweep_times)
-        if (ch.tail_side) HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_FORK_REFINE, d_cnt + VTX_CNT_REFINE, sizeof(uint32_t), hipMemcpyDeviceToHost, sb));   // ... and the records' final count
+        if (fork) HIP_TRY(c, read_back(c->h_pin->fork_tight, d_cnt->lists.tight, sb));   // the list's final length (read in collect_sweep_times)
+        if (ch.tail_side) HIP_TRY(c, read_back(c->h_pin->fork_refine, d_cnt->lists.refine, sb));   // ... and the records' final count
         HIP_TRY(c, hipEventRecord(c->ev[EV_BRANCH_END], sb));
         if (fork) HIP_TRY(c, hipEventRecord(c->ev[EV_FORK_START], s));                          // (this stream's branch starts here)
-        ch.n_fail = c->h_pin[PIN_RUN_LEFT];
-        const uint32_t n_dense = std::min(c->h_pin[PIN_DENSE], ch.nt);
+        ch.n_fail = pin.run_left;
+        const uint32_t n_dense = std::min(pin.dense, ch.nt);
         if (!fork) checked_total += n_tight;                                    // (forked: the exact count arrives with the events)
         diag_total += ch.nt; diag_left += (uint64_t)ch.n_fail + n_dense;
         if (int rc = repeats(ch, n_dense)) return rc;
@@ -2045,19 +2054,19 @@ struct BandPass {
         if (int rc = sort_by_task(c->d_fail.as<uint32_t>(), c->d_fail.as<uint32_t>() + ch.nt, ch.n_fail, &ch.fail_list)) return rc;
         if (fork) HIP_TRY(c, hipStreamWaitEvent(s, c->ev[EV_BRANCH_END], 0));                    // join: what follows reads every score
         HIP_TRY(c, hipEventRecord(c->ev[EV_SWEEP_END], s));
-        sweep_pending = true; sweep_forked = fork; sweep_tail_side = ch.tail_side; fork_nt = ch.nt;
+        open_sweep = OpenSweep{true, fork, ch.tail_side, ch.nt};
         return VTX_OK;
     }
     // tasks with a certificate but no verdict: their band is one diagonal stretch (tight_pack): the masked DP expands it itself.  (VTX_BAND_CHECK=1: the full-matrix check first — full == cert
     // decides a task, cert <= banded <= full; measured: 5.6 ns per task against 10 for the DP it saves on 20 - 30 % of noisy reads.)
     int one_diagonal_dp(uint32_t n_tight, bool fork, hipStream_t sb) {
-        const uint32_t *dp_list = tight_list, *dp_pack = tight_pack, *dp_cnt = fork ? d_cnt + VTX_CNT_TIGHT : nullptr;
+        const uint32_t *dp_list = tight_list, *dp_pack = tight_pack, *dp_cnt = fork ? &d_cnt->lists.tight : nullptr;
         if (kn.use_check) {
             HIP_TRY(c, c->d_dband.reserve((size_t)bp.chunk * sizeof(uint32_t)));
             HIP_TRY(c, c->d_dband_pack.reserve((size_t)bp.chunk * sizeof(uint32_t)));
-            HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_CHECK, 0, sizeof(uint32_t), sb));
-            HIP_TRY(c, vtxk_launch_sw_check(a, shape[0], shape[1], n_tight, tight_list, tight_pack, dp_cnt, mh, c->d_dband.as<uint32_t>(), c->d_dband_pack.as<uint32_t>(), d_cnt + VTX_CNT_CHECK, rs.stage, sb));
-            dp_list = c->d_dband.as<uint32_t>(); dp_pack = c->d_dband_pack.as<uint32_t>(); dp_cnt = d_cnt + VTX_CNT_CHECK;
+            HIP_TRY(c, zero(d_cnt->check, sb));
+            HIP_TRY(c, vtxk_launch_sw_check(a, shape[0], shape[1], n_tight, tight_list, tight_pack, dp_cnt, mh, c->d_dband.as<uint32_t>(), c->d_dband_pack.as<uint32_t>(), &d_cnt->check, rs.stage, sb));
+            dp_list = c->d_dband.as<uint32_t>(); dp_pack = c->d_dband_pack.as<uint32_t>(); dp_cnt = &d_cnt->check;
             ++rs.launches;
         }
         HIP_TRY(c, vtxk_launch_sw_diag_band(a, shape[0], shape[1], n_tight, dp_list, dp_pack, dp_cnt, mh, rs.stage, sb));
@@ -2083,24 +2092,25 @@ struct BandPass {
             if (int rc = second_stage(dl, n_dense, ch.tb, sweep2, &n_sweep)) return rc;
             sl = sweep2;
         }
-        if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, c->d_over.as<uint32_t>() + 2 * bp.n_tasks, d_cnt + VTX_CNT_SWEEP_HARD)) return rc; }
+        if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, c->d_over.as<uint32_t>() + 2 * bp.n_tasks, &d_cnt->sweep)) return rc; }
         swept_total += n_sweep;
         return VTX_OK;
     }
     // round 3's path (VTX_BAND_LEGACY, or a haplotype above band_sweep_kernel's 255 bases): band_refine_kernel, then band_run_kernel over the fail list
     int diag_round3_path(Chunk& ch) {
         ch.diag = true;
-        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_RUN_LEFT, d_cnt + VTX_CNT_RUN_LEFT, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_R3_REFINE, d_cnt + VTX_CNT_REFINE, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        vtx_band_counters::lists_t& pin = c->h_pin->lists;              // (this path has a fail list and records, no dense or tight list: it copies and reads those two words)
+        HIP_TRY(c, read_back(pin.run_left, d_cnt->lists.run_left, s));
+        HIP_TRY(c, read_back(pin.refine, d_cnt->lists.refine, s));
         HIP_TRY(c, hipEventRecord(c->ev[EV_DIAG_END], s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        ch.n_fail = c->h_pin[PIN_RUN_LEFT];
-        const uint32_t n_refine = std::min(c->h_pin[PIN_R3_REFINE], refine_cap);
+        ch.n_fail = pin.run_left;
+        const uint32_t n_refine = std::min(pin.refine, refine_cap);
         if (n_refine) {
             HIP_TRY(c, vtxk_launch_band_refine(a, refine_list, n_refine, sh, ch.tb, routes, nullptr, s));          // (this path has no tight list: routes.tight_list == nullptr)
-            HIP_TRY(c, hipMemcpyAsync(c->h_pin + PIN_RUN_LEFT, d_cnt + VTX_CNT_RUN_LEFT, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, read_back(pin.run_left, d_cnt->lists.run_left, s));
             HIP_TRY(c, hipStreamSynchronize(s));
-            ch.n_fail = c->h_pin[PIN_RUN_LEFT];
+            ch.n_fail = pin.run_left;
             refined_total += n_refine;
             ++rs.launches;
         }
@@ -2117,13 +2127,13 @@ struct BandPass {
         HIP_TRY(c, hipEventRecord(c->ev[EV_BAND_RUN_END], s));                  // (complete once the read-back below is: no synchronisation of its own)
         const bool run_skipped = ch.swept && ch.n_fail == 0;             // nothing went to band_run_kernel: its counters are what they were
         if (run_skipped) {
-            cnt[VTX_CNT_HARD] = 0; cnt[VTX_CNT_PENDING] = 0; cnt[VTX_CNT_OVERFLOW] = over_before;
+            cnt.hard = 0; cnt.pending = 0; cnt.overflow = over_before;
         } else {
-            HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, read_back(cnt, d_cnt->run, s));
             HIP_TRY(c, hipStreamSynchronize(s));
         }
         if (int rc = second_chance(ch)) return rc;
-        over_before = cnt[VTX_CNT_OVERFLOW];
+        over_before = cnt.overflow;
         float ms = 0;
         if (!run_skipped) {
             HIP_TRY(c, hipEventElapsedTime(&ms, ch.swept ? c->ev[EV_BAND_RUN_START] : c->ev[EV_CHUNK_START], c->ev[EV_BAND_RUN_END]));
@@ -2131,23 +2141,23 @@ struct BandPass {
             if (int rc = collect_sweep_times()) return rc;
         }
         if (ch.diag) { HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_CHUNK_START], c->ev[EV_DIAG_END])); diag_ms += ms; }
-        if (!sweep_used && ch.last && cnt[VTX_CNT_OVERFLOW])      // last chunk: the overflow list is complete
-            if (int rc = fallback_start(0, cnt[VTX_CNT_OVERFLOW])) return rc;
-        if (cnt[VTX_CNT_HARD] > bp.hard_cap) {               // the excess went to the general kernel's list: slots in use = hard_cap
-            cnt[VTX_CNT_HARD] = bp.hard_cap;
-            HIP_TRY(c, hipMemcpyAsync(d_cnt + VTX_CNT_HARD, cnt + VTX_CNT_HARD, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (!sweep_used && ch.last && cnt.overflow)      // last chunk: the overflow list is complete
+            if (int rc = fb.start(0, cnt.overflow)) return rc;
+        if (cnt.hard > bp.hard_cap) {               // the excess went to the general kernel's list: slots in use = hard_cap
+            cnt.hard = bp.hard_cap;
+            HIP_TRY(c, hipMemcpyAsync(&d_cnt->run.hard, &cnt.hard, sizeof cnt.hard, hipMemcpyHostToDevice, s));
         }
-        cnt[VTX_CNT_PENDING] = std::min(cnt[VTX_CNT_PENDING], bp.pend_cap);
-        if (cnt[VTX_CNT_PENDING]) {
+        cnt.pending = std::min(cnt.pending, bp.pend_cap);
+        if (cnt.pending) {
             // tasks whose piece list overflowed its LDS slots: the same certificate, from their pending records
-            HIP_TRY(c, vtxk_launch_band_pending(a, c->d_pend.as<uint32_t>(), cnt[VTX_CNT_PENDING], c->d_pend_buf.as<uint32_t>(), run_out, s));
-            HIP_TRY(c, hipMemcpyAsync(cnt + VTX_CNT_HARD, d_cnt + VTX_CNT_HARD, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, vtxk_launch_band_pending(a, c->d_pend.as<uint32_t>(), cnt.pending, c->d_pend_buf.as<uint32_t>(), run_out, s));
+            HIP_TRY(c, read_back(cnt.hard, d_cnt->run.hard, s));
             HIP_TRY(c, hipStreamSynchronize(s));
-            pending_total += cnt[VTX_CNT_PENDING];
+            pending_total += cnt.pending;
             ++rs.launches;
         }
-        if (int rc = masked_dp(cnt[VTX_CNT_HARD], c->d_hard.as<uint32_t>(), c->d_poly.as<uint16_t>(), c->d_band.as<uint16_t>(), bp.slots, s, VTX_STAGE_RUN_DP)) return rc;
-        rs.hard_total += cnt[VTX_CNT_HARD];
+        if (int rc = masked_dp(cnt.hard, c->d_hard.as<uint32_t>(), c->d_poly.as<uint16_t>(), c->d_band.as<uint16_t>(), bp.slots, s, VTX_STAGE_RUN_DP)) return rc;
+        rs.hard_total += cnt.hard;
         ++rs.launches;
         return VTX_OK;
     }
@@ -2158,20 +2168,20 @@ struct BandPass {
         if (short_lists && ch.nt >= (1u << 20)) {
             // feedback for the next run of this context: many overflows of the 12-entry lists (noisy reads: 3.3 % of the
             // tasks at 3 % substitution errors, 0.2 % at 0.5 %) make the 15-entry variant the better first pass
-            if ((uint64_t)(cnt[VTX_CNT_OVERFLOW] - over_before) * 50 > ch.nt) c->band_long_lists = true;
+            if ((uint64_t)(cnt.overflow - over_before) * 50 > ch.nt) c->band_long_lists = true;
         }
-        if (!short_lists || cnt[VTX_CNT_OVERFLOW] <= over_before) return VTX_OK;
-        const uint32_t a0 = over_before, a1 = cnt[VTX_CNT_OVERFLOW];
+        if (!short_lists || cnt.overflow <= over_before) return VTX_OK;
+        const uint32_t a0 = over_before, a1 = cnt.overflow;
         uint32_t* over = c->d_over.as<uint32_t>();
-        HIP_TRY(c, hipMemsetAsync(d_cnt + VTX_CNT_BLOCK, 0, 8 * sizeof(uint32_t), s));
+        HIP_TRY(c, zero(d_cnt->block, s));
         HIP_TRY(c, vtxk_launch_band_run(a, a1 - a0, 0, sh, ch.tb, run_out, c->d_band_ws.as<uint32_t>(), c->d_pend.as<uint32_t>(), c->d_pend_buf.as<uint32_t>(), bp.hard_cap, bp.pend_cap, over + a0, 0, s));
         HIP_TRY(c, hipEventRecord(c->ev[EV_BAND_RUN_END], s));
-        HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, read_back(cnt, d_cnt->run, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        const uint32_t again = cnt[VTX_CNT_OVERFLOW] - a1;          // <= a1 - a0: source and destination do not overlap
+        const uint32_t again = cnt.overflow - a1;          // <= a1 - a0: source and destination do not overlap
         if (again) HIP_TRY(c, hipMemcpyAsync(over + a0, over + a1, (size_t)again * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        cnt[VTX_CNT_OVERFLOW] = a0 + again;
-        HIP_TRY(c, hipMemcpyAsync(d_cnt + VTX_CNT_OVERFLOW, cnt + VTX_CNT_OVERFLOW, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        cnt.overflow = a0 + again;
+        HIP_TRY(c, hipMemcpyAsync(&d_cnt->run.overflow, &cnt.overflow, sizeof cnt.overflow, hipMemcpyHostToDevice, s));
         ++rs.launches;
         return VTX_OK;
     }
@@ -2180,7 +2190,7 @@ struct BandPass {
     // is left).
     int last_chunk() {
         uint32_t *over = c->d_over.as<uint32_t>(), *declined = over + 2 * bp.n_tasks;
-        const uint32_t nA = cnt[VTX_CNT_OVERFLOW];
+        const uint32_t nA = cnt.overflow;
         if (nA) {
             // (these tasks left band_diag_kernel for another reason than their number of matches, and then overflowed band_run_kernel's piece lists: repeats as well — on real-sequence loci 0.9 M
             // tasks.  The second stage first, when the tables of every locus are still resident.)
@@ -2191,35 +2201,36 @@ struct BandPass {
                 if (int rc = second_stage(over, nA, every_locus, c->d_dense.as<uint32_t>(), &n_sweep)) return rc;
                 sl = c->d_dense.as<uint32_t>();
             }
-            if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, declined, d_cnt + VTX_CNT_SWEEP_HARD)) return rc; }
+            if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, declined, &d_cnt->sweep)) return rc; }
             swept_total += n_sweep;
         }
         uint32_t nB = 0, nC = 0;
-        HIP_TRY(c, hipMemcpyAsync(&nB, d_cnt + VTX_CNT_SWEEP_DECLINED, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, read_back(nB, d_cnt->sweep.overflow, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         if (int rc = collect_sweep_times()) return rc;
         if (nB && kn.sweep_v1) {                    // (round 4's kernel only: its second pass with the larger log)
             resweep_total = nB;
-            if (int rc = sweep_slices(1, declined, nB, declined + nB, d_cnt + VTX_CNT_SWEEP2_HARD)) return rc;
-            HIP_TRY(c, hipMemcpyAsync(&nC, d_cnt + VTX_CNT_SWEEP2_DECLINED, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            if (int rc = sweep_slices(1, declined, nB, declined + nB, &d_cnt->sweep2)) return rc;
+            HIP_TRY(c, read_back(nC, d_cnt->sweep2.overflow, s));
             HIP_TRY(c, hipStreamSynchronize(s));
         } else if (nB) {                            // what band_sweep_kernel declines (bytes outside ACGTN, > 255 bases, > 1 024 sections, a
             nC = nB; nB = 0;                        // full stash bucket) takes the general band kernel
         }
-        cnt[VTX_CNT_OVERFLOW] = nC;
-        if (nC) { if (int rc = fallback_start((uint32_t)(2 * bp.n_tasks) + nB, (uint32_t)(2 * bp.n_tasks) + nB + nC)) return rc; }
+        cnt.overflow = nC;
+        if (nC) { if (int rc = fb.start((uint32_t)(2 * bp.n_tasks) + nB, (uint32_t)(2 * bp.n_tasks) + nB + nC)) return rc; }
         return VTX_OK;
     }
     // the general kernel's end; the pass's times and task counts ADDED to the run's; the VTX_DEBUG lines
     int publish() {
-        const uint32_t fast_overflow = cnt[VTX_CNT_OVERFLOW];
-        if (getenv("VTX_DEBUG")) {
-            uint32_t why[VTX_CNT_DROPPED + 1], *run_why = why + VTX_CNT_RUN_WHY;
-            HIP_TRY(c, hipMemcpy(why, d_cnt, sizeof why, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[vtx] band_run_kernel: %u tasks hard only because pieces were dropped from a full list\n", why[VTX_CNT_DROPPED]);
+        const uint32_t fast_overflow = cnt.overflow;
+        if (kn.debug) {
+            vtx_band_counters::run_t run;
+            HIP_TRY(c, hipMemcpy(&run, &d_cnt->run, sizeof run, hipMemcpyDeviceToHost));
+            const uint32_t* run_why = run.why;
+            fprintf(stderr, "[vtx] band_run_kernel: %u tasks hard only because pieces were dropped from a full list\n", run.dropped);
             fprintf(stderr, "[vtx] band_run_kernel overflow reasons: bound=%u parked-full=%u log-full=%u other=%u traceback=%u\n", run_why[1], run_why[2], run_why[3], run_why[4], run_why[5]);
         }
-        if (int rc = fallback_finish()) return rc;
+        if (int rc = fb.finish()) return rc;
         c->fast_overflow += fast_overflow;
         c->timing.diag_ms += diag_ms; c->timing.diag_left += (uint32_t)std::min<uint64_t>(diag_left, 0xffffffffull);
         c->timing.check_ms += check_ms; c->timing.sweep_ms += sweep_ms;
@@ -2232,20 +2243,19 @@ struct BandPass {
         c->timing.checked_tasks += (uint32_t)std::min<uint64_t>(checked_total, 0xffffffffull);
         if (swept_total) rs.hard_total += (uint32_t)std::min<uint64_t>(swept_total - std::min<uint64_t>(swept_total, fast_overflow), 0xffffffffull);
         rs.hard_total += (uint32_t)std::min<uint64_t>(checked_total, 0xffffffffull);      // (tasks with a certificate: masked DP over their diagonal band; with VTX_BAND_CHECK an upper bound)
-        if (getenv("VTX_DEBUG") && diag_total) {
-            uint32_t why[16];
-            HIP_TRY(c, hipMemcpy(why, d_cnt + VTX_CNT_DIAG_WHY, sizeof why, hipMemcpyDeviceToHost));
+        if (kn.debug && diag_total) {
+            vtx_band_counters all;
+            HIP_TRY(c, hipMemcpy(&all, d_cnt, sizeof all, hipMemcpyDeviceToHost));
+            const uint32_t* why = all.diag_why;
             fprintf(stderr, "[vtx] band_refine_kernel: %llu tasks listed\n", (unsigned long long)refined_total);
             fprintf(stderr, "[vtx] band_diag_kernel: %llu of %llu tasks left to band_run_kernel (%.2f %%), %.2f ms: shape=%u no-diagonal=%u pieces=%u matches=%u not-harmless=%u generic=%u not-tight=%u no-main=%u\n",
                     (unsigned long long)diag_left, (unsigned long long)diag_total, 100.0 * (double)diag_left / (double)diag_total, (double)diag_ms, why[1], why[2], why[3], why[4], why[5], why[7], why[8], why[9]);
-            uint32_t cleared = 0;
-            HIP_TRY(c, hipMemcpy(&cleared, d_cnt + VTX_CNT_RECHECK_CLEARED, sizeof cleared, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[vtx] band_tail_kernel, recheck: %u tasks that failed band_diag_kernel's harmless test rechecked, %u cleared\n", why[VTX_CNT_RECHECK_TOTAL - VTX_CNT_DIAG_WHY], cleared);
-            if (VTX_DEVTOOLS_ON) fprintf(stderr, "[vtx] band_tail_kernel: %u records routed towards the dense or fail list beside a tight list\n", why[VTX_CNT_TAIL_STRAY - VTX_CNT_DIAG_WHY]);
+            fprintf(stderr, "[vtx] band_tail_kernel, recheck: %u tasks that failed band_diag_kernel's harmless test rechecked, %u cleared\n", all.recheck_total, all.recheck_cleared);
+            if (VTX_DEVTOOLS_ON) fprintf(stderr, "[vtx] band_tail_kernel: %u records routed towards the dense or fail list beside a tight list\n", all.tail_stray);
         }
-        if (getenv("VTX_DEBUG") && diag2_total) fprintf(stderr, "[vtx] band_diag2_kernel: %llu tasks looked at, %llu scored, %llu left with a one-diagonal band, %llu to band_sweep_kernel (%llu through band_stream_kernel)\n",
+        if (kn.debug && diag2_total) fprintf(stderr, "[vtx] band_diag2_kernel: %llu tasks looked at, %llu scored, %llu left with a one-diagonal band, %llu to band_sweep_kernel (%llu through band_stream_kernel)\n",
             (unsigned long long)diag2_total, (unsigned long long)diag2_scored, (unsigned long long)tight2_total, (unsigned long long)(diag2_total - diag2_scored - tight2_total), (unsigned long long)stream_total);
-        if (getenv("VTX_DEBUG")) fprintf(stderr, "[vtx] banded: %llu tasks, %u overflowed band_run_kernel, %u bounded by the pending kernel, %u hard\n", (unsigned long long)bp.n_tasks, fast_overflow, pending_total, rs.hard_total);
+        if (kn.debug) fprintf(stderr, "[vtx] banded: %llu tasks, %u overflowed band_run_kernel, %u bounded by the pending kernel, %u hard\n", (unsigned long long)bp.n_tasks, fast_overflow, pending_total, rs.hard_total);
         return VTX_OK;
     }
 };
@@ -2331,8 +2341,8 @@ int run_slow(vtx_ctx* c, RunState& rs) {
     const uint32_t n_slow = 2 * c->slow_cnt;
     const int banded = c->cfg.aligner == VTX_ALIGNER_BANDED;
     if (rs.stage) HIP_TRY(c, vtxk_mark_stage_records(c->d_work.as<uint32_t>() + c->slow_off, c->slow_cnt, VTX_STAGE_SLOW, rs.stage, s));
-    HIP_TRY(c, c->d_cnt.reserve(VTX_CNT_WORDS * sizeof(uint32_t)));
-    uint32_t* d_scnt = c->d_cnt.as<uint32_t>() + VTX_CNT_SLOW;
+    HIP_TRY(c, c->d_cnt.reserve(sizeof(vtx_band_counters)));
+    uint32_t* d_scnt = &c->d_cnt.as<vtx_band_counters>()->slow;
     HIP_TRY(c, c->d_slow_retry.reserve(2 * (size_t)n_slow * sizeof(uint32_t)));
     const uint32_t* tasks = nullptr; uint32_t todo = n_slow, cap = 1024;
     const uint32_t mh = std::max(c->max_hap_all, 1u);
@@ -2340,7 +2350,7 @@ int run_slow(vtx_ctx* c, RunState& rs) {
         const uint64_t worst = (uint64_t)c->max_read_all * mh;
         const size_t stride = vtxk_slow_ws_stride(cap, mh, c->max_read_all);
         HIP_TRY(c, c->d_slow_ws.reserve((size_t)todo * stride));
-        HIP_TRY(c, hipMemsetAsync(d_scnt, 0, sizeof(uint32_t), s));
+        HIP_TRY(c, hipMemsetAsync(d_scnt, 0, sizeof *d_scnt, s));
         uint32_t* retry = c->d_slow_retry.as<uint32_t>() + ((tasks == c->d_slow_retry.as<uint32_t>()) ? n_slow : 0);
         HIP_TRY(c, vtxk_launch_slow_align(rs.a, c->d_work.as<uint32_t>() + c->slow_off, tasks, todo, banded, c->d_slow_ws.as<uint8_t>(), stride, cap, mh, c->max_read_all, retry, d_scnt, s));
         uint32_t left = 0;
@@ -2504,14 +2514,14 @@ int vtx_debug_bands(vtx_ctx* c, const uint32_t* tasks, uint32_t n_tasks, uint32_
     auto done = [&](int rc) { d_t.release(); d_h.release(); d_o.release(); d_c.release(); d_b.release(); d_d.release(); return rc; };
 #define DBG_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return done(fail(c, VTX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_))); } while (0)
     DBG_TRY(d_t.reserve((size_t)n_tasks * 4)); DBG_TRY(d_h.reserve((size_t)n_tasks * 4)); DBG_TRY(d_o.reserve((size_t)n_tasks * 4));
-    DBG_TRY(d_c.reserve(VTX_CNT_WORDS * 4)); DBG_TRY(d_b.reserve((size_t)n_tasks * 2 * bs * sizeof(uint16_t)));
+    DBG_TRY(d_c.reserve(sizeof(vtx_cnt_pair))); DBG_TRY(d_b.reserve((size_t)n_tasks * 2 * bs * sizeof(uint16_t)));
     const bool dbg_on = VTX_DEV_ENV("VTX_SWEEP_DBG") != nullptr;        // developer aid: the kernel's per-task intermediate state on stderr
     if (dbg_on) DBG_TRY(d_d.reserve((size_t)n_tasks * 64 * 4));
     DBG_TRY(hipMemcpyAsync(d_t.p, tasks, (size_t)n_tasks * 4, hipMemcpyHostToDevice, s));
-    DBG_TRY(hipMemsetAsync(d_c.p, 0, VTX_CNT_WORDS * 4, s));
+    DBG_TRY(hipMemsetAsync(d_c.p, 0, sizeof(vtx_cnt_pair), s));
     DBG_TRY(c->d_sweep_log.reserve(vtxk_band_sweep_log_bytes()));
     const vtx_task_arrays a{c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), nullptr, nullptr};
-    const vtx_band_out out{d_b.as<uint16_t>(), bs, d_h.as<uint32_t>(), d_o.as<uint32_t>(), d_c.as<uint32_t>()};
+    const vtx_band_out out{d_b.as<uint16_t>(), bs, d_h.as<uint32_t>(), d_o.as<uint32_t>(), d_c.as<vtx_cnt_pair>()};
     uint32_t* dbg = dbg_on ? d_d.as<uint32_t>() : nullptr;
 #ifdef VTX_DEVTOOLS
     // (libvtx_dev.so: VTX_SWEEP_V1=1 asks round 4's kernel instead; VTX_SWEEP_TIER=1 its 1024-section variant)
@@ -2520,7 +2530,7 @@ int vtx_debug_bands(vtx_ctx* c, const uint32_t* tasks, uint32_t n_tasks, uint32_
     else
 #endif
     DBG_TRY(vtxk_launch_band_sweep(a, d_t.as<uint32_t>(), n_tasks, nullptr, out, nullptr, nullptr, dbg, c->d_sweep_log.as<uint32_t>(), s));
-    struct { uint32_t hard = 0, declined = 0; } swept;   // band_sweep_kernel's two counters
+    vtx_cnt_pair swept{};                    // band_sweep_kernel's two counters: band slots, declined tasks
     DBG_TRY(hipMemcpyAsync(&swept, d_c.p, sizeof swept, hipMemcpyDeviceToHost, s));
     DBG_TRY(hipStreamSynchronize(s));
     std::vector<uint32_t> hard(swept.hard);

@@ -60,6 +60,8 @@
 #include "vtx_band_trim.h"
 #include "../../include/vtx_band_semantics.h"
 
+static_assert(vtxf::W_COUNT <= VTX_DIAG_WHY_COUNT, "vtxf::Why has outgrown vtx_band_counters::diag_why: raise VTX_DIAG_WHY_COUNT (the spare words shrink with it)");
+
 #define KMER 6
 #define BANDW 20
 // The certificate (run_ub / ub_join_same: "a mismatch costs 5 + 1", "short runs <= K - 1 = 5", "a gap of length L costs 5 + L",
@@ -509,7 +511,7 @@ __global__ __launch_bounds__(64) void band_coop_kernel(
         }
     }
     wave_sync();                                                       // (y6 is dead: rmin / rmax may be written)
-    if (VTX_ABLATE(ablate) == 1) { if (mt[0] == 0x7fffffffu) counters[2] = 1; return; }     // (profiling aid: phase A only; results are wrong)
+    if (VTX_ABLATE(ablate) == 1) { if (mt[0] == 0x7fffffffu) counters[1] = 1; return; }     // (profiling aid: phase A only; results are wrong)
     // ---- B: sdpkpp ----
     const int tn = n + KMER + 2;                                      // < 1024 (the host launches this kernel for haplotypes <= 1000 bases): tree paths of <= 10 nodes
     if (live) for (int i = l; i <= tn; i += G) tree[i] = 0;
@@ -598,7 +600,7 @@ __global__ __launch_bounds__(64) void band_coop_kernel(
     for (int d = 1; d < G; d <<= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)best, d, G); best = o > best ? o : best; }
     // (the reference starts `best` at (k, match 0): an END beats it iff (dp, index) > (k, 0) — dp >= k always, so the maximum
     //  over (dp, index) is the same entry)
-    if (VTX_ABLATE(ablate) == 2) { if (best == 0x7fffffffu) counters[2] = 1; return; }      // (profiling aid: phases A + B)
+    if (VTX_ABLATE(ablate) == 2) { if (best == 0x7fffffffu) counters[1] = 1; return; }      // (profiling aid: phases A + B)
     // ---- traceback (one lane per task), the chain reversed in path[] ----
     if (live && l == 0) {
         uint32_t cur = best & 0xffffu, len = 0;
@@ -699,7 +701,7 @@ extern "C" hipError_t vtxk_launch_band_coop(const vtx_task_arrays& a, int tier, 
         }                                                                                                                \
         hipLaunchKernelGGL((band_coop_kernel<G, MC>), dim3((n_tasks + tpw - 1) / tpw), dim3(64), shmem, s, tasks, n_tasks, a.records, a.rec_locus, \
                            a.loci, a.read, a.hap, sh.max_hap, (uint32_t)task_bytes, a.ref, a.alt, out.band, out.band_stride,     \
-                           out.hard_list, out.overflow_list, out.counters, ablate);                                      \
+                           out.hard_list, out.overflow_list, &out.counters->hard, ablate);                                      \
     }
     if (tier == 0) LAUNCH_COOP(64, 512) else if (tier == 1) LAUNCH_COOP(64, 1024) else LAUNCH_COOP(64, 4096)
 #undef LAUNCH_COOP
@@ -743,18 +745,18 @@ extern "C" hipError_t vtxk_launch_band(const vtx_task_arrays& a, const uint32_t*
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(band_kernel<true>, dim3((n_tasks + per_wg - 1) / per_wg), dim3(64), shmem, s, tasks, n_tasks,
                            task_base, a.records, a.rec_locus, a.loci, a.read, a.hap, workspace, (uint64_t)stride, m_cap,
-                           sh.max_hap, a.ref, a.alt, out.band, out.band_stride, out.hard_list, out.overflow_list, out.counters, per_wg, sh.max_read);
+                           sh.max_hap, a.ref, a.alt, out.band, out.band_stride, out.hard_list, out.overflow_list, &out.counters->hard, per_wg, sh.max_read);
         return hipGetLastError();
     }
     const uint32_t lanes = vtxk_band_lanes(n_tasks);
     if (lanes < 64)
         hipLaunchKernelGGL((band_kernel<false, 1>), dim3((n_tasks + lanes - 1) / lanes), dim3(64), 0, s, tasks, n_tasks, task_base, a.records,
                            a.rec_locus, a.loci, a.read, a.hap, workspace, ws_stride, m_cap, sh.max_hap, a.ref, a.alt,
-                           out.band, out.band_stride, out.hard_list, out.overflow_list, out.counters, lanes, 0u);
+                           out.band, out.band_stride, out.hard_list, out.overflow_list, &out.counters->hard, lanes, 0u);
     else
         hipLaunchKernelGGL((band_kernel<false, 64>), dim3((n_tasks + lanes - 1) / lanes), dim3(64), 0, s, tasks, n_tasks, task_base, a.records,
                            a.rec_locus, a.loci, a.read, a.hap, workspace, ws_stride, m_cap, sh.max_hap, a.ref, a.alt,
-                           out.band, out.band_stride, out.hard_list, out.overflow_list, out.counters, lanes, 0u);
+                           out.band, out.band_stride, out.hard_list, out.overflow_list, &out.counters->hard, lanes, 0u);
     return hipGetLastError();
 }
 
@@ -1348,7 +1350,7 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
     uint32_t* __restrict__ logbuf, uint16_t* __restrict__ band, uint32_t band_stride,
     uint32_t* __restrict__ hard_list, uint32_t* __restrict__ overflow_list, uint32_t* __restrict__ pending_list,
     uint32_t* __restrict__ pend_buf, uint32_t hard_cap, uint32_t pend_cap,
-    uint32_t* __restrict__ counters, uint32_t ablate, uint32_t n_heads, const uint8_t* __restrict__ gtables,
+    vtx_band_counters* __restrict__ counters, uint32_t ablate, uint32_t n_heads, const uint8_t* __restrict__ gtables,
     uint32_t gt_l0, uint32_t xcd_claim, const uint32_t* __restrict__ task_list) {
     // task_list != nullptr (GT only): the tasks are task_list[0 .. n_tasks) instead of task_base + 0 .. n_tasks — the second
     // chance of the tasks whose 12-entry lists overflowed, in the 15-entry variant
@@ -1374,7 +1376,7 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
     uint32_t* mylog = logbuf + (size_t)blockIdx.x * NT * TASK_WORDS + tid * 2;
     const uint32_t n_blocks = (n_tasks + NT - 1) / NT;
     // Workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8); each XCD claims blocks from its own eighth of the
-    // batch first (counters[VTX_CNT_BLOCK + xcd]), so the ~8 wavefronts that share a locus' tables and reads meet in one L2, and
+    // batch first (counters->block[xcd]), so the ~8 wavefronts that share a locus' tables and reads meet in one L2, and
     // helps the other eighths out when its own is done.
     // (xcd_claim == 0: one range for all)
     const bool by_xcd = xcd_claim != 0;
@@ -1388,7 +1390,7 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
         while (turn < 8) {
             const uint32_t r = (xcd + turn) & 7u;
             const uint32_t lo = r * per_xcd, hi = min(n_blocks, lo + per_xcd);
-            const uint32_t k = lo + atomicAdd(&counters[VTX_CNT_BLOCK + r], 1u);
+            const uint32_t k = lo + atomicAdd(VTX_COUNTER_AT(counters, block, r), 1u);
             if (lo < hi && k < hi) { b = k; break; }
             ++turn;
         }
@@ -1424,9 +1426,9 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
                  max(loci[my_locus].ref_len, loci[my_locus].alt_len) <= min_hap)) done = true;
     // a task without any k-mer match has the whole matrix in band (Band::full_matrix): hard list, marker slot
     // (hard slots beyond the capacity of the band buffer go to the general kernel's list, which makes them hard in slices)
-#define PUSH_FULL_MATRIX() { const uint32_t h_ = atomicAdd(&counters[VTX_CNT_HARD], 1u);                                    \
+#define PUSH_FULL_MATRIX() { const uint32_t h_ = atomicAdd(&counters->run.hard, 1u);                                    \
                              if (h_ < hard_cap) { hard_list[h_] = task; band[(size_t)h_ * 2 * band_stride] = BAND_FULL_MATRIX; } \
-                             else overflow_list[atomicAdd(&counters[VTX_CNT_OVERFLOW], 1u)] = task; }
+                             else overflow_list[atomicAdd(&counters->run.overflow, 1u)] = task; }
 
     for (uint32_t lbase = GT ? 0u : l_first; lbase <= (GT ? 0u : l_last); lbase += loci_per_pass) {     // GT: one pass over every locus
         const uint32_t n_tab = GT ? 0u : min(loci_per_pass, l_last - lbase + 1) * 2;
@@ -1465,7 +1467,7 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
                 const uint32_t nb = (xr + KMER < m) ? x[xr + KMER] : 0;
                 wl = (wl >> 8) | (wh << 24); wh = ((wh >> 8) & 0xff) | (nb << 8);
             }
-            if (cntm == 0xffffffffu) counters[VTX_CNT_RUN_WHY_LAST] = cntm;
+            if (cntm == 0xffffffffu) counters->run.why[5] = cntm;
             continue;
         }
 
@@ -1602,7 +1604,7 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
         bool overflow = st.overflow;
         uint32_t why = st.why;
         if (!overflow && st.n_ent == 0 && st.best_v < 0) { PUSH_FULL_MATRIX() continue; }   // no k-mer match
-        if (VTX_ABLATE(ablate) == 3) { if (st.n_ent == 0xffffu) counters[VTX_CNT_RUN_WHY_LAST] = st.n_ent; continue; }   // (profiling aid) phase 1 only
+        if (VTX_ABLATE(ablate) == 3) { if (st.n_ent == 0xffffu) counters->run.why[5] = st.n_ent; continue; }   // (profiling aid) phase 1 only
         // ================= phase 2: the rest of the chain DP =================
         if (!overflow) {
             uint32_t no_a = NONE_ID, no_b = NONE_ID;
@@ -1618,25 +1620,25 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
         }
         const uint32_t lg_n = st.lg_n;
         const uint32_t best_id = st.best_id;
-        if (overflow) { overflow_list[atomicAdd(&counters[VTX_CNT_OVERFLOW], 1u)] = task; atomicAdd(&counters[VTX_CNT_RUN_WHY + why], 1u); continue; }
+        if (overflow) { overflow_list[atomicAdd(&counters->run.overflow, 1u)] = task; atomicAdd(VTX_COUNTER_AT(counters, run.why, why), 1u); continue; }
         // ================= certificate: chain-of-runs upper bound vs the staircase's own score =================
         // Tasks whose list lost pieces to run_compact cannot bound here: their pieces (list + spill area) go to
         // band_pending_kernel, which computes the same bound with a wavefront's lanes over up to 32 pieces.
         const bool pending = st.ub_ok && st.n_sp > 0;
         const int32_t ub = (st.ub_ok && !pending) ? run_ub<NT>(pm_a, pm_id, tid, st.n_ent) : INT32_MAX;
-        if (VTX_ABLATE(ablate) == 4) { if (ub == -1) counters[VTX_CNT_RUN_WHY_LAST] = 1; continue; }   // (profiling aid) everything but the staircase walk
+        if (VTX_ABLATE(ablate) == 4) { if (ub == -1) counters->run.why[5] = 1; continue; }   // (profiling aid) everything but the staircase walk
         uint32_t verts[4 * SG + 6];
         uint32_t nv = 0;
         int32_t cert = 0;
         {
             const int fr = band_finish(mylog, 2 * NT, lg_n, best_id, x, yb, m, n, ub, verts, &nv, &cert);
             if (fr == 0) { *my_score = ub; continue; }
-            if (fr == 2) { overflow_list[atomicAdd(&counters[VTX_CNT_OVERFLOW], 1u)] = task; atomicAdd(&counters[VTX_CNT_RUN_WHY_LAST], 1u); continue; }
+            if (fr == 2) { overflow_list[atomicAdd(&counters->run.overflow, 1u)] = task; atomicAdd(&counters->run.why[5], 1u); continue; }
         }
         if (pending) {
             // a record for band_pending_kernel: header, certificate, list entries, staircase, spilled pieces
-            const uint32_t pi = atomicAdd(&counters[VTX_CNT_PENDING], 1u);
-            if (pi >= pend_cap) { overflow_list[atomicAdd(&counters[VTX_CNT_OVERFLOW], 1u)] = task; continue; }
+            const uint32_t pi = atomicAdd(&counters->run.pending, 1u);
+            if (pi >= pend_cap) { overflow_list[atomicAdd(&counters->run.overflow, 1u)] = task; continue; }
             uint32_t* prec = pend_buf + (size_t)pi * PEND_WORDS;
             prec[0] = st.n_ent | (st.n_sp << 8) | (nv << 16);
             prec[1] = (uint32_t)cert;
@@ -1649,9 +1651,9 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
             pending_list[pi] = task;
             continue;
         }
-        if (!st.ub_ok) atomicAdd(&counters[VTX_CNT_DROPPED], 1u);         // statistics: hard only because too many pieces were dropped
-        const uint32_t h = atomicAdd(&counters[VTX_CNT_HARD], 1u);
-        if (h >= hard_cap) { overflow_list[atomicAdd(&counters[VTX_CNT_OVERFLOW], 1u)] = task; continue; }
+        if (!st.ub_ok) atomicAdd(&counters->run.dropped, 1u);         // statistics: hard only because too many pieces were dropped
+        const uint32_t h = atomicAdd(&counters->run.hard, 1u);
+        if (h >= hard_cap) { overflow_list[atomicAdd(&counters->run.overflow, 1u)] = task; continue; }
         hard_list[h] = task;
         uint16_t* lo = band + (size_t)h * 2 * band_stride;
         lo[0] = BAND_POLYLINE; lo[1] = (uint16_t)nv;
@@ -1675,7 +1677,7 @@ __global__ __launch_bounds__(NT, WPE) void band_run_kernel(
 __global__ __launch_bounds__(256) void band_pending_kernel(
     const uint32_t* __restrict__ pending, uint32_t n_pending, const uint32_t* __restrict__ pend_buf,
     int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score, uint16_t* __restrict__ band, uint32_t band_stride,
-    uint32_t* __restrict__ hard_list, uint32_t* __restrict__ counters) {
+    uint32_t* __restrict__ hard_list, vtx_band_counters* __restrict__ counters) {
     __shared__ uint32_t s_id[8][32], s_lg[8][32];      // per task: piece start, (bases << 16 | G)
     const int grp = threadIdx.x >> 5, l = threadIdx.x & 31;
     const uint32_t pi = blockIdx.x * 8 + grp;
@@ -1742,7 +1744,7 @@ __global__ __launch_bounds__(256) void band_pending_kernel(
         return;
     }
     uint32_t h = 0;
-    if (l == 0) { h = atomicAdd(&counters[VTX_CNT_HARD], 1u); hard_list[h] = task; }
+    if (l == 0) { h = atomicAdd(&counters->run.hard, 1u); hard_list[h] = task; }
     h = (uint32_t)__shfl((int)h, 0, 32);
     uint16_t* lo = band + (size_t)h * 2 * band_stride;
     if (l == 0) { lo[0] = BAND_POLYLINE; lo[1] = (uint16_t)nv; }
@@ -1758,7 +1760,7 @@ extern "C" hipError_t vtxk_launch_band_pending(const vtx_task_arrays& a, const u
                                                const vtx_band_out& out, hipStream_t s) {
     if (!n_pending) return hipSuccess;
     hipLaunchKernelGGL(band_pending_kernel, dim3((n_pending + 7) / 8), dim3(256), 0, s, pending, n_pending, pend_buf,
-                       a.ref, a.alt, out.band, out.band_stride, out.hard_list, out.counters);
+                       a.ref, a.alt, out.band, out.band_stride, out.hard_list, out.run_counters);
     return hipGetLastError();
 }
 
@@ -1929,7 +1931,7 @@ __global__ __launch_bounds__(256) void band_expand_kernel(const uint32_t* __rest
 // haplotypes of one record: their read loads coalesce); the blocks are dealt so that each XCD works through one
 // contiguous eighth of the batch (workgroups go to the XCDs round-robin): the ~8 wavefronts that share a locus' tables
 // and reads meet in one L2.
-// counters[VTX_CNT_RUN_LEFT] = tasks left to band_run_kernel; counters[VTX_CNT_DIAG_WHY + why] = reasons (stats != 0).
+// counters->lists.run_left = tasks left to band_run_kernel; counters->diag_why[why] = reasons (stats != 0).
 // =============================================================================================
 
 // =============================================================================================
@@ -2236,11 +2238,11 @@ extern "C" uint32_t vtxk_band_tail_words(void) { return (uint32_t)vtxf::TAIL_WOR
 // Where a task goes once the last phase of the certificate is over — band_diag_kernel's lanes and band_tail_kernel's (the tasks the
 // former left in the middle of that phase) alike; every lane of the wavefront calls it.  fail: no verdict (why, aux: back_rest's);
 // tight: the task holds its certificate (harmless matches only).  The lists, each reserved with one atomic per wavefront:
-//   refine_rec (counters[VTX_CNT_REFINE])  with a tight list a record for band_corridor_kernel (every task that keeps its certificate), else round 3's
+//   refine_rec (counters->lists.refine)  with a tight list a record for band_corridor_kernel (every task that keeps its certificate), else round 3's
 //                              record for band_refine_kernel (main pieces only, bounds apart); the buffer full: on to the lists below
-//   tight_list (counters[VTX_CNT_TIGHT])  the certificate's band (pack), the certificate as a provisional score
-//   dense_list (counters[VTX_CNT_DENSE])  the reasons in dense_mask (W_MATCHES: only when spread) — band_sweep_kernel
-//   fail_list  (counters[VTX_CNT_RUN_LEFT])  the rest — band_run_kernel
+//   tight_list (counters->lists.tight)  the certificate's band (pack), the certificate as a provisional score
+//   dense_list (counters->lists.dense)  the reasons in dense_mask (W_MATCHES: only when spread) — band_sweep_kernel
+//   fail_list  (counters->lists.run_left)  the rest — band_run_kernel
 // Round 6, the sweep path (a tight list): EVERY task that leaves the last phase with its certificate — harmless matches only, bounds
 // apart or the generic set full — leaves a record for band_corridor_kernel (the task, its one-diagonal band, the rows of its
 // matches far out: vtx_fast_core.h, "the corridor certificate") instead of taking the masked DP; what that kernel does not decide
@@ -2251,7 +2253,7 @@ template <class LaneT, class FarOf>
 __device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t why, bool tight, uint32_t aux, bool spread, FarOf far_of, const LaneT& ln,
                                            int r, int cert, uint32_t zc, uint32_t pack, int32_t* __restrict__ ref_score,
                                            int32_t* __restrict__ alt_score, uint32_t* __restrict__ fail_list, uint32_t* __restrict__ refine_rec,
-                                           uint32_t refine_cap, uint32_t* __restrict__ counters, uint32_t stats, uint32_t* __restrict__ tight_list,
+                                           uint32_t refine_cap, vtx_band_counters* __restrict__ counters, uint32_t stats, uint32_t* __restrict__ tight_list,
                                            uint32_t* __restrict__ tight_pack, uint32_t* __restrict__ dense_list, uint32_t dense_mask) {
     const int tid = threadIdx.x & 63;
     const bool corr_mode = tight_list != nullptr && refine_rec != nullptr && !(stats & 0x10000u);
@@ -2260,7 +2262,7 @@ __device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t wh
     if (am) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)am) - 1;
-        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_REFINE], (uint32_t)__popcll(am));
+        if (tid == leader) base = atomicAdd(&counters->lists.refine, (uint32_t)__popcll(am));
         base = (uint32_t)__shfl((int)base, leader);
         const uint32_t pos = base + (uint32_t)__popcll(am & ((1ull << tid) - 1ull));
         if (again && pos >= refine_cap) again = false;              // (the record buffer is full: band_run_kernel takes it)
@@ -2285,7 +2287,7 @@ __device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t wh
     if (tm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)tm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_TIGHT], (uint32_t)__popcll(tm));
+        if (tid == leader) base = atomicAdd(&counters->lists.tight, (uint32_t)__popcll(tm));
         base = (uint32_t)__shfl((int)base, leader);
         if (tight) {
             const uint32_t pos = base + (uint32_t)__popcll(tm & ((1ull << tid) - 1ull));
@@ -2299,7 +2301,7 @@ __device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t wh
     if (dm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)dm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_DENSE], (uint32_t)__popcll(dm));
+        if (tid == leader) base = atomicAdd(&counters->lists.dense, (uint32_t)__popcll(dm));
         base = (uint32_t)__shfl((int)base, leader);
         if (dense) dense_list[base + (uint32_t)__popcll(dm & ((1ull << tid) - 1ull))] = task;
     }
@@ -2307,11 +2309,11 @@ __device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t wh
     if (fm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)fm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_RUN_LEFT], (uint32_t)__popcll(fm));
+        if (tid == leader) base = atomicAdd(&counters->lists.run_left, (uint32_t)__popcll(fm));
         base = (uint32_t)__shfl((int)base, leader);
         if (fail && !again && !tight && !dense) fail_list[base + (uint32_t)__popcll(fm & ((1ull << tid) - 1ull))] = task;
     }
-    if (fail && !again && (stats & 0xffu)) atomicAdd(&counters[VTX_CNT_DIAG_WHY + why], 1u);
+    if (fail && !again && (stats & 0xffu)) atomicAdd(VTX_COUNTER_AT(counters, diag_why, why), 1u);
 }
 // ST: type of an off-diagonal match entry — uint16_t (x << 8 | y: 40 entries per task in the same LDS) when every haplotype of
 // the batch has <= 255 bases, else uint32_t (20 entries).
@@ -2322,22 +2324,22 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     const vtx_record* __restrict__ records, const uint32_t* __restrict__ rec_locus, const vtx_locus* __restrict__ loci,
     const uint8_t* __restrict__ read_arena, uint32_t max_hap, uint32_t table_stride, uint32_t n_heads,
     const uint8_t* __restrict__ gtables, uint32_t gt_l0, int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score,
-    uint32_t* __restrict__ fail_list, uint32_t* __restrict__ refine_rec, uint32_t refine_cap, uint32_t* __restrict__ counters,
+    uint32_t* __restrict__ fail_list, uint32_t* __restrict__ refine_rec, uint32_t refine_cap, vtx_band_counters* __restrict__ counters,
     uint32_t stats, uint32_t* __restrict__ tight_list, uint32_t* __restrict__ tight_pack, uint8_t* __restrict__ stage,
     uint32_t* __restrict__ dense_list, uint32_t dense_mask, uint32_t min_hap, uint32_t* __restrict__ tail_rec, uint32_t tail_cap,
     uint32_t* __restrict__ recheck_rec, uint32_t recheck_cap) {
     // min_hap: tasks of loci whose longer haplotype has <= min_hap bases are left alone (vtx_run's second pass over a batch that mixes
     // haplotypes of <= 255 bases with a few longer ones: the first pass, with two-byte entries and the sweep behind it, scored them).
     // dense_list != nullptr (round 4): a task left for a reason in dense_mask (bit = vtxf::Why; by default W_MATCHES: more than 40
-    // off-diagonal k-mer matches — repeats) goes there (counters[VTX_CNT_DENSE]): band_run_kernel's piece lists would overflow on it, it takes
+    // off-diagonal k-mer matches — repeats) goes there (counters->lists.dense): band_run_kernel's piece lists would overflow on it, it takes
     // band_sweep_kernel directly.
     // tight_list != nullptr (round 4): a task whose off-diagonal matches are all harmless but whose bounds do not meet (or whose
     // generic set overflows) HAS a certificate — the chain is the closed form's, cert <= banded — so it leaves with
-    // its band (the (2w + 1)-squares along ONE diagonal stretch: tight_pack[i] = vtxf::band_pack) on tight_list (counters[VTX_CNT_TIGHT]):
+    // its band (the (2w + 1)-squares along ONE diagonal stretch: tight_pack[i] = vtxf::band_pack) on tight_list (counters->lists.tight):
     // the band-masked DP scores it from that word, without band_sweep_kernel; score = cert meanwhile, a PROVISIONAL score
     // (the optional full-matrix check sw_banded_kernel<.., 1> decides it where full == cert).  Not on fail_list.  stage != nullptr: stage[task] = 1 for every task decided here (vtx_fetch_stage).
     // refine_rec != nullptr: a task with main pieces only whose bounds do not meet leaves a 12-word record for band_refine_kernel
-    // (counters[VTX_CNT_REFINE]; REFINE_WORDS) instead of going to band_run_kernel's list: that kernel prices the stretches of >= 3 errors
+    // (counters->lists.refine; REFINE_WORDS) instead of going to band_run_kernel's list: that kernel prices the stretches of >= 3 errors
     // within a few bases from the real neighbour diagonals and needs nothing else of what this one found.
     // Four wavefronts per workgroup, each on its own 64 consecutive tasks and its own slice of the LDS (no workgroup barrier
     // anywhere): the four share their loci's tables in the CU's L1.
@@ -2418,7 +2420,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
             if constexpr (sizeof(ST) == 2) twins = !(stats & 0x20000u) && vtxf::tab_has_twins(tb);
         }
     }
-    if (VTX_ABLATE((stats >> 8) & 0xffu) == 4) { if (live && m == 0x7fffffff) counters[VTX_CNT_DIAG_DUMMY] = 1; return; }           // (profiling aid) task set-up only
+    if (VTX_ABLATE((stats >> 8) & 0xffu) == 4) { if (live && m == 0x7fffffff) counters->diag_dummy = 1; return; }           // (profiling aid) task set-up only
     // ---- the read, once: lanes 2i / 2i + 1 hold the two haplotypes of ONE record, so each loads half of its 8-byte words (16-byte
     //      loads) and the two swap halves — a quarter of the load instructions and of the L2 lines 8-byte loads per lane cost ----
     PH(0);                                                              // task set-up
@@ -2469,7 +2471,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
         }
         if (live && !have_d) { live = false; fail = true; why = vtxf::W_NO_DIAG; }
         PH(3);                                                          // the mask
-        if (VTX_ABLATE((stats >> 8) & 0xffu) == 3) { if (live && d == 0x7fffffff) counters[VTX_CNT_DIAG_DUMMY] = 1; return; }       // (profiling aid) up to the diagonal and its mask
+        if (VTX_ABLATE((stats >> 8) & 0xffu) == 3) { if (live && d == 0x7fffffff) counters->diag_dummy = 1; return; }       // (profiling aid) up to the diagonal and its mask
         if (live) {
             vtxf::TwinHead th;
             if (twins) th = vtxf::twin_head(tb);
@@ -2536,7 +2538,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
         }
     }
     vtxf::MIter need_it = vtxf::m_iter(nd);
-    if (VTX_ABLATE((stats >> 8) & 0xffu) == 1) { if (live && fr.cert == 0x7fffffff) counters[VTX_CNT_DIAG_DUMMY] = 1; return; }      // (profiling aid) front only
+    if (VTX_ABLATE((stats >> 8) & 0xffu) == 1) { if (live && fr.cert == 0x7fffffff) counters->diag_dummy = 1; return; }      // (profiling aid) front only
     const uint32_t pb_rel = vtxf::tab_pb_off(max_hap, n_heads), head_rel = max_hap * 8u, bytes_rel = vtxf::tab_bytes_off(max_hap, n_heads);
     const uint32_t t3_rel = vtxf::tab_t3_off(max_hap, n_heads);
     // pass 2 over the first n_walk entries of the walk list (every lane calls it; 0xffff: a slot reserved by a lane that did not fit)
@@ -2763,7 +2765,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     walk_list(q_count[1]);
     wave_sync();
     PH(7);                                                              // the walks
-    if (VTX_ABLATE((stats >> 8) & 0xffu) == 2) { if (live && s_cnt[tid] == 0x7fffffffu) counters[VTX_CNT_DIAG_DUMMY] = 1; return; }   // (profiling aid) front + probes
+    if (VTX_ABLATE((stats >> 8) & 0xffu) == 2) { if (live && s_cnt[tid] == 0x7fffffffu) counters->diag_dummy = 1; return; }   // (profiling aid) front + probes
     uint32_t aux = 0xffffffffu;
     bool tight = false;
     // ---- the last phase, every lane for itself: sort, harmless tests, closure, run bound (vtx_fast_core.h).  (Pooling the harmless
@@ -2794,9 +2796,9 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     }
     if (live) vtxf::back_sort(ns, ln, (int)(s_cnt[tid] >> 16));
     PH(8);                                                              // sort
-    if (VTX_ABLATE((stats >> 8) & 0xffu) == 7) { if (live && ns == 0x7fffffff) counters[VTX_CNT_DIAG_DUMMY] = 1; return; }            // (profiling aid) ... + the sort
+    if (VTX_ABLATE((stats >> 8) & 0xffu) == 7) { if (live && ns == 0x7fffffff) counters->diag_dummy = 1; return; }            // (profiling aid) ... + the sort
     // A task that fails the test here — one running maximum over every earlier match: a bound that grows by one per chance match — has
-    // failed the coarse form only.  With a recheck buffer it leaves the tail's record (recheck_rec, counters[VTX_CNT_RECHECK]) and
+    // failed the coarse form only.  With a recheck buffer it leaves the tail's record (recheck_rec, counters->recheck) and
     // nothing else: band_tail_kernel's recheck mode runs the tight form on the same list and routes the task.  No buffer, or the
     // buffer full: W_NOT_HARMLESS, as before.
     bool recheck = false;
@@ -2805,7 +2807,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     if (km) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)km) - 1;
-        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_RECHECK], (uint32_t)__popcll(km));
+        if (tid == leader) base = atomicAdd(&counters->recheck, (uint32_t)__popcll(km));
         base = (uint32_t)__shfl((int)base, leader);
         const uint32_t pos = base + (uint32_t)__popcll(km & ((1ull << tid) - 1ull));
         if (recheck && pos >= recheck_cap) { recheck = false; fail = true; }
@@ -2814,7 +2816,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     PH(9);                                                              // harmless tests
     // The closure's first scan decides whether the generic set stays empty (92 % of the live tasks: one scan and the main-only run bound
     // on piece words in registers).  A task whose set must grow — closure rescans, a fixpoint over (r + ng)^2 piece pairs — costs what
-    // its whole wavefront waits for: it leaves a record for band_tail_kernel instead (tail_rec, counters[VTX_CNT_TAIL]; vtxf::tail_pack) and writes
+    // its whole wavefront waits for: it leaves a record for band_tail_kernel instead (tail_rec, counters->tail; vtxf::tail_pack) and writes
     // nothing else here.  The buffer full: it goes on here, as without the record.  (Headline: closure + bound 19.4 -> 9.9 k cycles per
     // wavefront, the kernel 10.64 -> 9.44 ms, band_tail_kernel 0.68 ms; DESIGN 4.3.2, "where the kernel's time goes".)
     int first = -2;
@@ -2824,7 +2826,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     if (xm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)xm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_TAIL], (uint32_t)__popcll(xm));
+        if (tid == leader) base = atomicAdd(&counters->tail, (uint32_t)__popcll(xm));
         base = (uint32_t)__shfl((int)base, leader);
         const uint32_t pos = base + (uint32_t)__popcll(xm & ((1ull << tid) - 1ull));
         if (defer && pos >= tail_cap) defer = false;
@@ -2849,7 +2851,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
 
 // =============================================================================================
 // band_tail_kernel — the rest of the last phase for the tasks band_diag_kernel deferred: those whose closure must take an off-diagonal
-// piece into the generic set (7.4 % of the headline's tasks).  One lane per record, over the device's record count (counters[VTX_CNT_TAIL]); the
+// piece into the generic set (7.4 % of the headline's tasks).  One lane per record, over the device's record count (counters->tail); the
 // record goes back into band_diag_kernel's LDS layout and the same vtxf::back_rest runs on it, then the same routing (diag_route):
 // every task ends with the score, stage and lists it had when decided in its wavefront.  With a tight list an undecided task holds its
 // certificate (it passed back_harmless before it was deferred): diag_route sends it to refine_rec or tight_list, never to dense_list or
@@ -2864,12 +2866,12 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
 // runs on the record's list, and a task it clears goes on as above: back_rest, then decided, a record for the second look or a tight
 // entry.  A task it does not clear is routed as band_diag_kernel routed it before: W_NOT_HARMLESS, no certificate, towards fail_list
 // (or dense_list when dense_mask names the reason) — so this mode needs those lists and runs in front of their readers.
-// counters[VTX_CNT_RECHECK_TOTAL] / [VTX_CNT_RECHECK_CLEARED]: the records looked at and cleared (statistics).
+// counters->recheck_total / recheck_cleared: the records looked at and cleared (statistics).
 template <class ST, int A, bool RECHECK = false>
 __global__ __launch_bounds__(64) void band_tail_kernel(
     uint32_t* __restrict__ tail_rec, uint32_t tail_cap, const uint32_t* __restrict__ n_dev,
     int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score, uint32_t* __restrict__ fail_list, uint32_t* __restrict__ refine_rec,
-    uint32_t refine_cap, uint32_t* __restrict__ counters, uint32_t stats, uint32_t* __restrict__ tight_list, uint32_t* __restrict__ tight_pack,
+    uint32_t refine_cap, vtx_band_counters* __restrict__ counters, uint32_t stats, uint32_t* __restrict__ tight_list, uint32_t* __restrict__ tight_pack,
     uint8_t* __restrict__ stage, uint32_t* __restrict__ dense_list, uint32_t dense_mask) {
     __shared__ uint32_t lane_mem[vtxf::LANE_WORDS * 64];
     __shared__ uint32_t gen_mem[vtxf::GM * 64];
@@ -2914,7 +2916,7 @@ __global__ __launch_bounds__(64) void band_tail_kernel(
         }
         rec[3 * (size_t)tail_cap] = out | (RECHECK && cleared ? TAIL_CLEARED : 0u);
     }
-    if (RECHECK && blockIdx.x == 0 && tid == 0) atomicAdd(&counters[VTX_CNT_RECHECK_TOTAL], n_recs);
+    if (RECHECK && blockIdx.x == 0 && tid == 0) atomicAdd(&counters->recheck_total, n_recs);
     // 2. the routing, wavefront-uniform (its ballots see every lane): the same lane, the same records
     for (uint32_t p0 = blockIdx.x * 64u; p0 < n_recs; p0 += lanes) {
         const uint32_t p = p0 + (uint32_t)tid;
@@ -2927,10 +2929,10 @@ __global__ __launch_bounds__(64) void band_tail_kernel(
         const bool fail = !(out & TAIL_DECIDED), tight = (out & TAIL_TIGHT) != 0;
         // (libvtx_dev.so: with a tight list every undecided record carries TAIL_TIGHT, so the routing below ends at refine_rec or
         // tight_list — what lets this kernel run beside the readers of dense_list / fail_list.  A record that would take either: counted.)
-        if (!RECHECK && VTX_DEVTOOLS_ON && tight_list && fail && !tight) atomicAdd(&counters[VTX_CNT_TAIL_STRAY], 1u);
+        if (!RECHECK && VTX_DEVTOOLS_ON && tight_list && fail && !tight) atomicAdd(&counters->tail_stray, 1u);
         if constexpr (RECHECK) {
             const uint64_t cm = __ballot(p < n_recs && (out & TAIL_CLEARED) != 0);
-            if (cm && tid == 0) atomicAdd(&counters[VTX_CNT_RECHECK_CLEARED], (uint32_t)__popcll(cm));
+            if (cm && tid == 0) atomicAdd(&counters->recheck_cleared, (uint32_t)__popcll(cm));
         }
         if (fail && tight) {
             const uint32_t* rec = tail_rec + p;
@@ -2958,9 +2960,9 @@ __global__ __launch_bounds__(256) void band_refine_kernel(
     const vtx_record* __restrict__ records, const uint32_t* __restrict__ rec_locus, const vtx_locus* __restrict__ loci,
     const uint8_t* __restrict__ read_arena, uint32_t max_hap, uint32_t table_stride, uint32_t n_heads,
     const uint8_t* __restrict__ gtables, uint32_t gt_l0, int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score,
-    uint32_t* __restrict__ fail_list, uint32_t* __restrict__ counters, uint32_t stats, uint32_t* __restrict__ tight_list,
+    uint32_t* __restrict__ fail_list, vtx_band_counters* __restrict__ counters, uint32_t stats, uint32_t* __restrict__ tight_list,
     uint32_t* __restrict__ tight_pack, uint8_t* __restrict__ stage, const uint32_t* __restrict__ n_dev) {
-    // tight_list != nullptr (round 4): an undecided record still has its certificate: provisional score + tight_list (counters[VTX_CNT_TIGHT])
+    // tight_list != nullptr (round 4): an undecided record still has its certificate: provisional score + tight_list (counters->lists.tight)
     // instead of fail_list (see band_diag_kernel).  n_dev: the record count lives on the device (min(*n_dev, n_recs)).
     __shared__ uint32_t piece_mem_[4][vtxf::RM * 64];
     if (n_dev) { const uint32_t nd = *n_dev; n_recs = nd < n_recs ? nd : n_recs; }
@@ -3006,13 +3008,13 @@ __global__ __launch_bounds__(256) void band_refine_kernel(
     if (fm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)fm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[tight_list ? VTX_CNT_TIGHT : VTX_CNT_RUN_LEFT], (uint32_t)__popcll(fm));
+        if (tid == leader) base = atomicAdd(tight_list ? &counters->lists.tight : &counters->lists.run_left, (uint32_t)__popcll(fm));
         base = (uint32_t)__shfl((int)base, leader);
         if (fail) {
             const uint32_t pos = base + (uint32_t)__popcll(fm & ((1ull << tid) - 1ull));
             (tight_list ? tight_list : fail_list)[pos] = task;
             if (tight_list) tight_pack[pos] = pack;
-            if (stats & 0xffu) atomicAdd(&counters[VTX_CNT_DIAG_WHY + vtxf::W_NOT_TIGHT], 1u);
+            if (stats & 0xffu) atomicAdd(&counters->diag_why[vtxf::W_NOT_TIGHT], 1u);
         }
     }
 }
@@ -3031,7 +3033,7 @@ __global__ __launch_bounds__(256) void band_corridor_kernel(
     const uint32_t* __restrict__ recs, uint32_t n_recs,
     const vtx_record* __restrict__ records, const uint32_t* __restrict__ rec_locus, const vtx_locus* __restrict__ loci,
     const uint8_t* __restrict__ read_arena, const uint8_t* __restrict__ hap_arena,
-    int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score, uint32_t* __restrict__ counters, uint32_t stats,
+    int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score, vtx_band_counters* __restrict__ counters, uint32_t stats,
     uint32_t* __restrict__ tight_list, uint32_t* __restrict__ tight_pack, uint8_t* __restrict__ stage, const uint32_t* __restrict__ n_dev) {
     if (n_dev) { const uint32_t nd = *n_dev; n_recs = nd < n_recs ? nd : n_recs; }
     const int tid = threadIdx.x & 63;
@@ -3064,13 +3066,13 @@ __global__ __launch_bounds__(256) void band_corridor_kernel(
     if (fm) {
         uint32_t base = 0;
         const int leader = __ffsll((long long)fm) - 1;
-        if (tid == leader) base = atomicAdd(&counters[VTX_CNT_TIGHT], (uint32_t)__popcll(fm));
+        if (tid == leader) base = atomicAdd(&counters->lists.tight, (uint32_t)__popcll(fm));
         base = (uint32_t)__shfl((int)base, leader);
         if (fail) {
             const uint32_t pos = base + (uint32_t)__popcll(fm & ((1ull << tid) - 1ull));
             tight_list[pos] = task;
             tight_pack[pos] = pack;
-            if (stats & 0xffu) atomicAdd(&counters[VTX_CNT_DIAG_WHY + vtxf::W_NOT_TIGHT], 1u);
+            if (stats & 0xffu) atomicAdd(&counters->diag_why[vtxf::W_NOT_TIGHT], 1u);
         }
     }
   }
@@ -3254,7 +3256,7 @@ extern "C" hipError_t vtxk_launch_band_run(const vtx_task_arrays& a, uint32_t n_
                            dim3(NTV), shmem, s, n_tasks,                                                             \
                            task_base, a.records, a.rec_locus, a.loci, a.read, a.hap, sh.max_hap, sh.min_hap, tables, \
                            (uint32_t)tstride, a.ref, a.alt, logbuf, out.band, out.band_stride, out.hard_list,        \
-                           out.overflow_list, pending_list, pend_buf, hard_cap, pend_cap, out.counters, ablate, n_heads, \
+                           out.overflow_list, pending_list, pend_buf, hard_cap, pend_cap, out.run_counters, ablate, n_heads, \
                            (const uint8_t*)tb.gtables, tb.gt_l0, task_list ? 0u : xcd_claim, task_list);             \
     }
     if (variant == 1) LAUNCH_RUN(64, true, 4, VTX_PS)
@@ -3320,7 +3322,7 @@ extern "C" hipError_t vtxk_launch_band_tail(const vtx_task_arrays& a, const vtx_
     hipLaunchKernelGGL((band_tail_kernel<STV, AV>),                                                                                         \
                        dim3(std::min({(tail.cap + 63u) / 64u, 65536u, grid_hook, resident_grid ? tail_resident_grid<STV, AV>() : 65536u})), \
                        dim3(64), 0, s, tail.rec, tail.cap,                                                                                  \
-                       routes.counters + VTX_CNT_TAIL, a.ref, a.alt, routes.fail_list, routes.refine_rec, routes.refine_cap,                \
+                       &routes.counters->tail, a.ref, a.alt, routes.fail_list, routes.refine_rec, routes.refine_cap,                \
                        routes.counters, st, routes.tight_list, routes.tight_pack, routes.stage, routes.dense_list, routes.dense_mask)
     const bool three = diag_three_words(sh.max_read);
     if (diag_narrow(sh.max_hap)) { if (three) LAUNCH_TAIL(uint16_t, 3); else LAUNCH_TAIL(uint16_t, vtxf::NW); }
@@ -3336,7 +3338,7 @@ extern "C" int vtxk_band_recheck_on(vtx_rec_buf recheck, uint32_t max_hap) {
 }
 // band_tail_kernel's recheck mode over the records a vtxk_launch_band_diag with the same shape, routes and buffer (vtxk_band_recheck_on) left in
 // recheck.rec; s runs behind that band_diag_kernel and in front of every reader of the lists and their counts: the kernel appends to
-// all of them.  A resident grid looping over the device's count (counters[VTX_CNT_RECHECK]): the kernel may run beside
+// all of them.  A resident grid looping over the device's count (counters->recheck): the kernel may run beside
 // band_tail_kernel on another stream, and the host does not know the count.
 extern "C" hipError_t vtxk_launch_band_recheck(const vtx_task_arrays& a, const vtx_band_shape& sh, const vtx_diag_routes& routes, vtx_rec_buf recheck,
                                                hipStream_t s) {
@@ -3345,7 +3347,7 @@ extern "C" hipError_t vtxk_launch_band_recheck(const vtx_task_arrays& a, const v
 #define LAUNCH_RECHECK(AV)                                                                                                               \
     hipLaunchKernelGGL((band_tail_kernel<uint16_t, AV, true>),                                                                             \
                        dim3(std::min({(recheck.cap + 63u) / 64u, 65536u, tail_resident_grid<uint16_t, AV, true>()})), dim3(64), 0, s,      \
-                       recheck.rec, recheck.cap, routes.counters + VTX_CNT_RECHECK, a.ref, a.alt, routes.fail_list, routes.refine_rec,     \
+                       recheck.rec, recheck.cap, &routes.counters->recheck, a.ref, a.alt, routes.fail_list, routes.refine_rec,     \
                        routes.refine_cap, routes.counters, st, routes.tight_list, routes.tight_pack, routes.stage, routes.dense_list,      \
                        routes.dense_mask)
     if (diag_three_words(sh.max_read)) LAUNCH_RECHECK(3); else LAUNCH_RECHECK(vtxf::NW);
@@ -3360,10 +3362,10 @@ extern "C" hipError_t vtxk_launch_band_diag(const vtx_task_arrays& a, uint32_t n
                                             const vtx_band_tables& tb, const vtx_diag_routes& routes, vtx_rec_buf tail, int tail_inline,
                                             vtx_rec_buf recheck, hipStream_t s) {
     // recheck.rec != nullptr: room for recheck.cap records (the tail's layout) of tasks that fail the kernel's harmless test;
-    // counters[VTX_CNT_RECHECK] counts them.  The caller launches vtxk_launch_band_recheck behind this call when vtxk_band_recheck_on
+    // counters->recheck counts them.  The caller launches vtxk_launch_band_recheck behind this call when vtxk_band_recheck_on
     // says the records exist.  nullptr: such a task leaves with W_NOT_HARMLESS.
     // sh.max_read: the longest read of the batch (the fast kernels' records) — up to 192 bases the kernel is built with three mask words
-    // tail.rec != nullptr: room for tail.cap records of band_tail_kernel (TAIL_WORDS words each, word-major); counters[VTX_CNT_TAIL]
+    // tail.rec != nullptr: room for tail.cap records of band_tail_kernel (TAIL_WORDS words each, word-major); counters->tail
     // counts them.  tail_inline != 0: band_tail_kernel is launched here, behind band_diag_kernel on the same stream; 0: the caller
     // launches it (vtxk_launch_band_tail, when vtxk_band_tail_on says the records exist) on a stream that waits for this one.
     if (!n_tasks) return hipSuccess;
@@ -3381,8 +3383,8 @@ extern "C" hipError_t vtxk_launch_band_diag(const vtx_task_arrays& a, uint32_t n
                        tb.gt_l0, a.ref, a.alt, routes.fail_list, routes.refine_rec, routes.refine_cap, routes.counters, st,                 \
                        routes.tight_list, routes.tight_pack, routes.stage, routes.dense_list, routes.dense_mask, sh.min_hap, tail.rec,      \
                        tail.cap, recheck.rec, recheck.cap)
-    if (tail.rec) { const hipError_t e = hipMemsetAsync(routes.counters + VTX_CNT_TAIL, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
-    if (recheck.rec) { const hipError_t e = hipMemsetAsync(routes.counters + VTX_CNT_RECHECK, 0, sizeof(uint32_t), s); if (e != hipSuccess) return e; }
+    if (tail.rec) { const hipError_t e = hipMemsetAsync(&routes.counters->tail, 0, sizeof routes.counters->tail, s); if (e != hipSuccess) return e; }
+    if (recheck.rec) { const hipError_t e = hipMemsetAsync(&routes.counters->recheck, 0, sizeof routes.counters->recheck, s); if (e != hipSuccess) return e; }
     const bool three = diag_three_words(sh.max_read);
     if (diag_narrow(sh.max_hap)) { if (three) LAUNCH_DIAG(uint16_t, 3); else LAUNCH_DIAG(uint16_t, vtxf::NW); }
     else { if (three) LAUNCH_DIAG(uint32_t, 3); else LAUNCH_DIAG(uint32_t, vtxf::NW); }

@@ -3,6 +3,7 @@
 #define VTX_DEVICE_H
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/vtx.h"
@@ -44,44 +45,46 @@ static __host__ __device__ inline bool vtx_bytes_equal(const uint8_t* a, const u
     return eq;
 }
 
-// The banded stage's counter block (vtx_ctx::d_cnt): VTX_CNT_WORDS words, zeroed once per pass of the stage unless noted.  The host
-// (vtx_api.hip) and every kernel or launcher that is handed the BASE of the block index it through these names; a kernel that is
-// handed a pointer INTO the block (band_kernel / band_coop_kernel: GENERAL_HARD; the sweeps: SWEEP_HARD / SWEEP2_HARD and SWEEP_WHY;
-// band_diag2_kernel: DIAG2_LEFT, STREAMED; the full-matrix check: CHECK / CHECK2; slow_align_kernel: SLOW) counts from that word.
-enum VtxBandCnt {
-    VTX_CNT_HARD = 0,             // band_run_kernel / band_pending_kernel: entries of the hard list (zeroed per chunk)
-    VTX_CNT_OVERFLOW = 1,         // band_run_kernel: entries of the overflow list (grows over the chunks)
-    VTX_CNT_RUN_WHY = 2,          // [2, 8): band_run_kernel's overflow reasons ...
-    VTX_CNT_RUN_WHY_LAST = 7,     //   ... the last one: traceback (also where that kernel's profiling aids leave their dummy store)
-    VTX_CNT_GENERAL_HARD = 8,     // the general band kernel (side stream): hard tasks ...
-    VTX_CNT_GENERAL_AGAIN = 9,    //   ... and tasks that need a larger slab (zeroed per launch)
-    VTX_CNT_DROPPED = 10,         // band_run_kernel, statistics: hard only because pieces were dropped from a full list
-    VTX_CNT_PENDING = 11,         // band_run_kernel: pending records (zeroed per chunk)
-    VTX_CNT_RUN_LEFT = 12,        // band_diag_kernel / band_refine_kernel: tasks left for band_run_kernel (12 .. 15 zeroed per chunk)
-    VTX_CNT_DENSE = 13,           // band_diag_kernel: tasks for band_sweep_kernel
-    VTX_CNT_REFINE = 14,          // band_diag_kernel: records for band_refine_kernel / band_corridor_kernel
-    VTX_CNT_TIGHT = 15,           // band_diag_kernel and those two: tasks with a one-diagonal band
-    VTX_CNT_BLOCK = 16,           // [16, 24): band_run_kernel's block counters, one per XCD (zeroed per launch)
-    VTX_CNT_CHECK = 24,           // the full-matrix check in front of the first stage's one-diagonal bands: what it leaves
-    VTX_CNT_CHECK2 = 25,          // ... of the second stage's
-    VTX_CNT_SWEEP_HARD = 26,      // band_sweep_kernel, first pass: band slots of the slice (zeroed per slice) ...
-    VTX_CNT_SWEEP_DECLINED = 27,  //   ... and declined tasks
-    VTX_CNT_SWEEP2_HARD = 28,     // round 4's second pass (libvtx_dev.so): the same two
-    VTX_CNT_SWEEP2_DECLINED = 29,
-    VTX_CNT_DIAG2_LEFT = 30,      // band_diag2_kernel / band_stream_kernel: tasks left for the sweep ...
-    VTX_CNT_DIAG2_TIGHT = 31,     //   ... and with a one-diagonal band (both zeroed per call of the second stage)
-    VTX_CNT_DIAG_WHY = 32,        // [32, 48): band_diag_kernel's reasons, by vtxf::Why (statistics); three words past W_COUNT are in use:
-    VTX_CNT_DIAG_DUMMY = 40,      //   where band_diag_kernel's profiling aids leave their dummy store (W_NOT_TIGHT's word: results are wrong anyway)
-    VTX_CNT_TAIL = 44,            //   records band_diag_kernel leaves for band_tail_kernel (zeroed per launch)
-    VTX_CNT_TAIL_STRAY = 45,      //   libvtx_dev.so: records band_tail_kernel routed towards dense_list / fail_list although a tight list exists (must stay 0)
-    VTX_CNT_RECHECK = 46,         //   records band_diag_kernel leaves for band_tail_kernel's recheck mode: tasks that failed its harmless test (zeroed per launch)
-    VTX_CNT_RECHECK_TOTAL = 47,   //   statistics: the records that kernel looked at, over the pass ...
-    VTX_CNT_RECHECK_CLEARED = 49, //   ... and those the tight harmless test cleared
-    VTX_CNT_STREAMED = 48,       // band_diag2_kernel: tasks handed to band_stream_kernel (zeroed per call of the second stage)
-    VTX_CNT_SWEEP_WHY = 56,       // [56, 64): band_sweep_kernel's reasons (statistics)
-    VTX_CNT_SLOW = 13,            // slow_align_kernel: tasks to retry.  Aliases VTX_CNT_DENSE: the slow path runs after the banded stage
-    VTX_CNT_WORDS = 64
+// The banded stage's counter block (vtx_ctx::d_cnt): 64 words, all of them zeroed once per pass of the stage (BandPass::run); the groups
+// say what zeroes them more often.  A group is what the host zeroes or copies as a unit, by its name and sizeof.  A kernel or launcher
+// that is handed the BASE of the block (vtx_diag_routes::counters, vtx_band_out::run_counters) names the members; a kernel
+// that is handed the address of a MEMBER counts from it: a vtx_cnt_pair as counters[0], counters[1] (band_kernel / band_coop_kernel:
+// general; the sweeps: sweep, sweep2; band_diag2_kernel: diag2, from left), a single word as *count (the full-matrix check: check, check2;
+// band_diag2_kernel: streamed; slow_align_kernel: slow; band_tail_kernel: tail, recheck), the sweeps' reasons as stat_counters[].
+struct vtx_cnt_pair { uint32_t hard, overflow; };   // the entries of a kernel's hard list (its band slots in use) and of its overflow list (the tasks it hands on)
+constexpr uint32_t VTX_DIAG_WHY_COUNT = 10;         // vtxf::W_COUNT (vtx_fast_core.h, which not every user of this header can include; vtx_band.hip asserts that the reasons fit)
+struct vtx_band_counters {
+    // band_run_kernel / band_pending_kernel; BandPass::cnt mirrors the group.  hard, pending: zeroed per chunk; overflow grows over the
+    // chunks; why (that kernel's overflow reasons, the last one the traceback: also where its profiling aids leave their dummy store)
+    // and dropped (hard only because pieces were dropped from a full list) are statistics
+    struct run_t { uint32_t hard, overflow, why[6], dropped, pending; } run;
+    // the general band kernel (side stream): hard tasks, tasks that need a larger slab.  Zeroed per slice of its list, again per launch
+    vtx_cnt_pair general;
+    // band_diag_kernel's lists and those of the kernels over its records, zeroed per chunk: tasks left for band_run_kernel, tasks for
+    // band_sweep_kernel, records for band_refine_kernel / band_corridor_kernel, tasks with a one-diagonal band
+    struct lists_t { uint32_t run_left, dense, refine, tight; } lists;
+    uint32_t block[8];                  // band_run_kernel's block counters, one per XCD: zeroed per launch
+    // what the full-matrix check in front of the one-diagonal bands leaves, of the first stage and of the second: zeroed per launch
+    uint32_t check, check2;
+    // band_sweep_kernel: band slots of the slice (zeroed per slice) and declined tasks (per pass); sweep2: the second pass of round 4's kernel (libvtx_dev.so)
+    vtx_cnt_pair sweep, sweep2;
+    struct diag2_t { uint32_t left, tight; } diag2;   // band_diag2_kernel / band_stream_kernel: tasks left for the sweep, tasks with a one-diagonal band; zeroed per call of the second stage
+    uint32_t diag_why[VTX_DIAG_WHY_COUNT];   // band_diag_kernel's reasons, by vtxf::Why (statistics)
+    uint32_t diag_dummy;                // where band_diag_kernel's profiling aids leave their dummy store
+    uint32_t slow;                      // slow_align_kernel: tasks to retry (zeroed per call)
+    // band_tail_kernel.  tail, recheck: the records band_diag_kernel leaves for it and for its recheck mode (tasks that failed the harmless test), zeroed per launch of that
+    // kernel; tail_stray (libvtx_dev.so, statistics): records routed towards dense_list / fail_list although a tight list exists: must stay 0
+    uint32_t tail, tail_stray, recheck;
+    uint32_t recheck_total, recheck_cleared;   // statistics: the records the recheck looked at, and those the tight harmless test cleared
+    uint32_t streamed;                  // band_diag2_kernel: tasks handed to band_stream_kernel; zeroed per call of the second stage
+    uint32_t spare[16 - VTX_DIAG_WHY_COUNT];   // (a new word, or a new reason of vtxf::Why, takes one of these)
+    uint32_t sweep_why[8];              // band_sweep_kernel's reasons (statistics)
 };
+static_assert(sizeof(vtx_band_counters) == 64 * 4, "the counter block is 64 words");
+// The word of an array member at a RUN-TIME index, addressed as `counters[FIRST + i]` was: from the block's base, the sum formed in 32 bits.  (Written cnt->array[i] the compiler folds
+// the array's offset into the instruction; that saves an addition and moves band_diag_kernel's and band_run_kernel's registers and schedule.  The kernels' code is the code
+// that was measured: profiles/r20_band_counters.json.)
+#define VTX_COUNTER_AT(cnt, array, i) ((uint32_t*)(cnt) + ((uint32_t)(offsetof(vtx_band_counters, array) / sizeof(uint32_t)) + (i)))
 
 // The argument bundles of the vtxk_launch_* functions: what many launches share travels by name, what distinguishes a launch (task
 // ranges, lists, tiers, workspaces, the stream) stays positional.  HOST code only: a launcher unpacks a bundle at its hipLaunchKernelGGL
@@ -93,15 +96,15 @@ struct vtx_band_shape { uint32_t max_hap, min_hap, max_read, tasks_per_locus; };
 // the k-mer tables in global memory: room for those of loci [gt_l0, gt_l0 + n_loci) (gtables == nullptr: tables in LDS)
 struct vtx_band_tables { uint8_t* gtables; size_t gtables_bytes; uint32_t gt_l0, n_loci; };
 // where band_diag_kernel and the kernels over its records (band_tail_kernel in both modes, band_refine_kernel, band_corridor_kernel)
-// send a task: the lists, their counters (the base of the VtxBandCnt block) and the statistics switch.  band_diag_kernel and the
+// send a task: the lists, their counters (the base of the block) and the statistics switch.  band_diag_kernel and the
 // launches of band_tail_kernel over its records take the SAME object, but for a null fail_list / dense_list where the tail says so.
-struct vtx_diag_routes { uint32_t* fail_list; uint32_t* refine_rec; uint32_t refine_cap; uint32_t* counters; int stats; uint32_t* tight_list; uint32_t* tight_pack;
+struct vtx_diag_routes { uint32_t* fail_list; uint32_t* refine_rec; uint32_t refine_cap; vtx_band_counters* counters; int stats; uint32_t* tight_list; uint32_t* tight_pack;
                          uint8_t* stage; uint32_t* dense_list; uint32_t dense_mask; };
 // a record buffer band_diag_kernel fills for band_tail_kernel (the tail's, the recheck's): cap records of vtxk_band_tail_words() words
 struct vtx_rec_buf { uint32_t* rec; uint32_t cap; };
 // where a kernel that builds bands leaves them: band slots, the hard list of the tasks that own one, the list of the tasks it cannot
-// hold, and the counters of the two lists (counters[0], counters[1]; band_run_kernel: the base of the VtxBandCnt block)
-struct vtx_band_out { uint16_t* band; uint32_t band_stride; uint32_t* hard_list; uint32_t* overflow_list; uint32_t* counters; };
+// hold, and the counters of the two lists (band_run_kernel and band_pending_kernel take run_counters, the base of the block)
+struct vtx_band_out { uint16_t* band; uint32_t band_stride; uint32_t* hard_list; uint32_t* overflow_list; vtx_cnt_pair* counters; vtx_band_counters* run_counters; };
 
 extern "C" {
 hipError_t vtxk_launch_sw_full(const vtx_task_arrays& a, int R, int GL, uint32_t n_work, const uint32_t* work, uint32_t max_hap_len, hipStream_t stream);

@@ -579,7 +579,7 @@ extern "C" hipError_t vtxk_launch_band_sweep(const vtx_task_arrays& a, const uin
     static const uint32_t ablate = VTX_DEV_ENV("VTX_SWEEP_ABLATE") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_SWEEP_ABLATE")) << 8 : 0u;
     const size_t shmem = (size_t)8 * TASK_W * sizeof(uint32_t);
     hipLaunchKernelGGL(band_sweep_kernel, dim3(vtxk_band_sweep_grid(n_tasks)), dim3(64), shmem, s, tasks, n_tasks, n_dev, a.records,
-                       a.rec_locus, a.loci, a.read, a.hap, out.band, out.band_stride, out.hard_list, out.overflow_list, out.counters,
+                       a.rec_locus, a.loci, a.read, a.hap, out.band, out.band_stride, out.hard_list, out.overflow_list, &out.counters->hard,
                        ablate, stat_counters, stage, dbg, glog);
     return hipGetLastError();
 }

@@ -521,7 +521,7 @@ extern "C" hipError_t vtxk_launch_band_sweep_v1(const vtx_task_arrays& a, int ti
         }                                                                                                          \
         hipLaunchKernelGGL(band_sweep_v1_kernel<CAP>, dim3((n_tasks + 7) / 8), dim3(64), shmem, s, tasks, n_tasks, n_dev, a.records, \
                            a.rec_locus, a.loci, a.read, a.hap, out.band, out.band_stride, out.hard_list, out.overflow_list,       \
-                           out.counters, ablate, stat_counters, stage, dbg);                                       \
+                           &out.counters->hard, ablate, stat_counters, stage, dbg);                                       \
     }
     if (tier == 0) LAUNCH_SWEEP(256) else LAUNCH_SWEEP(1024)
 #undef LAUNCH_SWEEP
