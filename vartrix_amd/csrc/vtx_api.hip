@@ -1947,7 +1947,6 @@ struct BandPass {
         if (int rc = collect_sweep_times()) return rc;                              // (a chunk re-records the events)
         HIP_TRY(c, zero(d_cnt->run.hard, s));
         HIP_TRY(c, zero(d_cnt->run.pending, s));
-        HIP_TRY(c, zero(d_cnt->block, s));
         uint32_t gt_l0 = 0, gt_n = bp.gt_bytes ? c->n_loci : 0;
         if (gt_chunked) {
             uint32_t ends[2];
@@ -2122,6 +2121,7 @@ struct BandPass {
     // the masked DP over its hard list; after the last chunk of a pass without a sweep, the general kernel's start
     int run_stage(Chunk& ch) {
         HIP_TRY(c, hipEventRecord(c->ev[EV_BAND_RUN_START], s));
+        if (!ch.diag || ch.n_fail) HIP_TRY(c, zero(d_cnt->block, s));      // (here, not per chunk: band_diag_kernel's claim loop, where libvtx_dev.so runs it, has counted in them since)
         if (!ch.diag || ch.n_fail) HIP_TRY(c, vtxk_launch_band_run(a, ch.diag ? ch.n_fail : ch.nt, ch.diag ? 0u : (uint32_t)ch.base, sh, ch.tb, run_out, c->d_band_ws.as<uint32_t>(), c->d_pend.as<uint32_t>(),
             c->d_pend_buf.as<uint32_t>(), bp.hard_cap, bp.pend_cap, ch.diag ? ch.fail_list : nullptr, c->band_long_lists ? 1 : 0, s));
         HIP_TRY(c, hipEventRecord(c->ev[EV_BAND_RUN_END], s));                  // (complete once the read-back below is: no synchronisation of its own)

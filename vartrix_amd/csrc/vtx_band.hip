@@ -2250,12 +2250,11 @@ extern "C" uint32_t vtxk_band_tail_words(void) { return (uint32_t)vtxf::TAIL_WOR
 // round 3's records for band_refine_kernel, main pieces only.)
 // far_of(): vtxf::far_rows of the task (asked only for a corridor record); ln: its main piece words (round 3's records).
 template <class LaneT, class FarOf>
-__device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t why, bool tight, uint32_t aux, bool spread, FarOf far_of, const LaneT& ln,
+__device__ __forceinline__ void diag_route(int tid, uint32_t task, bool fail, uint32_t why, bool tight, uint32_t aux, bool spread, FarOf far_of, const LaneT& ln,
                                            int r, int cert, uint32_t zc, uint32_t pack, int32_t* __restrict__ ref_score,
                                            int32_t* __restrict__ alt_score, uint32_t* __restrict__ fail_list, uint32_t* __restrict__ refine_rec,
                                            uint32_t refine_cap, vtx_band_counters* __restrict__ counters, uint32_t stats, uint32_t* __restrict__ tight_list,
                                            uint32_t* __restrict__ tight_pack, uint32_t* __restrict__ dense_list, uint32_t dense_mask) {
-    const int tid = threadIdx.x & 63;
     const bool corr_mode = tight_list != nullptr && refine_rec != nullptr && !(stats & 0x10000u);
     bool again = corr_mode ? (fail && tight) : (fail && why == vtxf::W_NOT_TIGHT && refine_rec != nullptr && aux != 0xffffffffu);
     const uint64_t am = __ballot(again);
@@ -2318,14 +2317,17 @@ __device__ __forceinline__ void diag_route(uint32_t task, bool fail, uint32_t wh
 // ST: type of an off-diagonal match entry — uint16_t (x << 8 | y: 40 entries per task in the same LDS) when every haplotype of
 // the batch has <= 255 bases, else uint32_t (20 entries).
 // A: mask words in use — 3 when no read of the batch exceeds 192 bases (the instruction count of rounds 3 - 5), else vtxf::NW = 4.
-template <int WPE, class ST, int A>
-__global__ __launch_bounds__(256, WPE) void band_diag_kernel(
+// WG: threads of a workgroup, 64 or 256.  CLAIM: the wavefront loops over blocks of tasks it claims (DIAG_WG, DIAG_CLAIM below: what the launch uses).
+__device__ __forceinline__ int per_trip_v(int v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ uint32_t per_trip_s(uint32_t v) { asm volatile("" : "+s"(v)); return v; }
+template <int WG, bool CLAIM, class ST, int A>
+__global__ __launch_bounds__(WG, 4) void band_diag_kernel(
     uint32_t n_tasks, uint32_t task_base, uint32_t n_blocks,
     const vtx_record* __restrict__ records, const uint32_t* __restrict__ rec_locus, const vtx_locus* __restrict__ loci,
-    const uint8_t* __restrict__ read_arena, uint32_t max_hap, uint32_t table_stride, uint32_t n_heads,
+    const uint8_t* __restrict__ read_arena, uint32_t max_hap_, uint32_t table_stride, uint32_t n_heads_,
     const uint8_t* __restrict__ gtables, uint32_t gt_l0, int32_t* __restrict__ ref_score, int32_t* __restrict__ alt_score,
     uint32_t* __restrict__ fail_list, uint32_t* __restrict__ refine_rec, uint32_t refine_cap, vtx_band_counters* __restrict__ counters,
-    uint32_t stats, uint32_t* __restrict__ tight_list, uint32_t* __restrict__ tight_pack, uint8_t* __restrict__ stage,
+    uint32_t stats_, uint32_t* __restrict__ tight_list, uint32_t* __restrict__ tight_pack, uint8_t* __restrict__ stage,
     uint32_t* __restrict__ dense_list, uint32_t dense_mask, uint32_t min_hap, uint32_t* __restrict__ tail_rec, uint32_t tail_cap,
     uint32_t* __restrict__ recheck_rec, uint32_t recheck_cap) {
     // min_hap: tasks of loci whose longer haplotype has <= min_hap bases are left alone (vtx_run's second pass over a batch that mixes
@@ -2341,24 +2343,32 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     // refine_rec != nullptr: a task with main pieces only whose bounds do not meet leaves a 12-word record for band_refine_kernel
     // (counters->lists.refine; REFINE_WORDS) instead of going to band_run_kernel's list: that kernel prices the stretches of >= 3 errors
     // within a few bases from the real neighbour diagonals and needs nothing else of what this one found.
-    // Four wavefronts per workgroup, each on its own 64 consecutive tasks and its own slice of the LDS (no workgroup barrier
-    // anywhere): the four share their loci's tables in the CU's L1.
+    // A WAVEFRONT is the unit: it works on a block of 64 consecutive tasks in its own slice of the LDS, and nothing in the kernel
+    // waits for another wavefront (no workgroup barrier anywhere).  The launch therefore makes the wavefront the workgroup (WG = 64,
+    // 10 184 B of LDS, 16 workgroups per CU): a wavefront that ends frees its slot and its LDS at once.  Until round 20 four
+    // wavefronts shared a workgroup — for the CU's L1, where their loci's tables meet — and the three that were done held their slots
+    // until the slowest ended, while the next workgroup waited for four free slots at a time: one slot in six stood empty
+    // (headline 8.71 -> 7.83 ms).  The neighbouring blocks still run on one XCD, the tables meet in its L2.
+    // CLAIM (libvtx_dev.so only): a grid the device holds at once, its wavefronts claiming blocks in a loop.  Measured slower — the
+    // loop carries the kernel's arguments and what the compiler hoists through a body that has no register to spare, and spills —
+    // and kept for tests/test_gpu_diag_claim.py and the record.
+    constexpr int NWV = WG / 64;
     constexpr int QROWS = 12;                                  // rows a lane contributes to the pool per round
     static_assert(64 * QROWS * 2 >= vtxf::GM * 64 * 4, "back() borrows the probe queue for its generic pieces");
-    __shared__ uint32_t lane_mem_[4][vtxf::LANE_WORDS * 64];
-    __shared__ uint16_t q_ent_[4][64 * QROWS];                 // pooled probes of one round: owner lane << 8 | row
-    __shared__ uint32_t o_read_[4][64], o_tab_[4][64], s_cnt_[4][64];      // per owner lane: read offset, table offset, matches found
-    __shared__ int32_t o_diag_[4][64];
+    __shared__ uint32_t lane_mem_[NWV][vtxf::LANE_WORDS * 64];
+    __shared__ uint16_t q_ent_[NWV][64 * QROWS];               // pooled probes of one round: owner lane << 8 | row
+    __shared__ uint32_t o_read_[NWV][64], o_tab_[NWV][64], s_cnt_[NWV][64];      // per owner lane: read offset, table offset, matches found
+    __shared__ int32_t o_diag_[NWV][64];
     constexpr int WALK_CAP = 224;                              // entries of the walk list (the survivors of pass 1, across rounds)
-    __shared__ uint16_t q_walk_[4][WALK_CAP];
-    __shared__ uint32_t q_count_[4][2];
-    const int wv = threadIdx.x >> 6, tid = threadIdx.x & 63;
-    const bool ph_on = VTX_DEVTOOLS_ON && (stats & 0x80000u);
+    __shared__ uint16_t q_walk_[NWV][WALK_CAP];
+    __shared__ uint32_t q_count_[NWV][2];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const bool ph_on = VTX_DEVTOOLS_ON && (stats_ & 0x80000u);
     unsigned long long ph_t = ph_on ? __builtin_readcyclecounter() : 0ull;
     auto PH = [&](int i) {
         if (VTX_DEVTOOLS_ON && ph_on) {
             const unsigned long long now = __builtin_readcyclecounter();
-            if (tid == 0) atomicAdd(&g_diag_phase[blockIdx.x & 255u][i], now - ph_t);
+            if (lane == 0) atomicAdd(&g_diag_phase[blockIdx.x & 255u][i], now - ph_t);
             ph_t = now;
         }
     };
@@ -2367,20 +2377,25 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
     uint16_t* q_walk = q_walk_[wv];
     uint32_t *o_read = o_read_[wv], *o_tab = o_tab_[wv], *s_cnt = s_cnt_[wv], *q_count = q_count_[wv];
     int32_t* o_diag = o_diag_[wv];
-    const uint32_t per_xcd = (n_blocks + 7) / 8;
-    const uint32_t blk = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
-    if (blk >= n_blocks) return;
-    const uint32_t slot = blk * 256 + threadIdx.x;
+    typedef vtxf::LaneS<ST, vtxf::S_WORDS, (A <= 3)> LaneT;
+    // One block of 64 consecutive tasks, blk of n_blocks.  With the claim loop the LDS is what the block before left: every reader of it
+    // is guarded by a count of this trip, and everything per task is set up here.
+    auto trip = [&](uint32_t blk) {
+    // (CLAIM: the lane number and three arguments pass through per_trip_*(), values the compiler takes as new on every trip.  What follows
+    //  from them alone — LDS addresses, the tables' offsets, the masks of the block ends — is then computed where a trip uses it, as
+    //  without the loop; hoisted in front of the loop it stays in registers for the whole kernel.)
+    const int tid = CLAIM ? per_trip_v(lane) : lane;
+    const uint32_t max_hap = CLAIM ? per_trip_s(max_hap_) : max_hap_, n_heads = CLAIM ? per_trip_s(n_heads_) : n_heads_, stats = CLAIM ? per_trip_s(stats_) : stats_;
+    const LaneT ln{lane_mem + vtxf::S_WORDS * 64 + tid, 64, (ST*)lane_mem + tid, 64};
+    const uint32_t slot = blk * 64 + tid;
     const bool have = slot < n_tasks;
     const uint32_t task = task_base + slot;
     bool fail = false, live = false, whole = false, twins = false, load = false;
     uint32_t why = 0;
     // (where a task's score goes is recomputed at each of the four stores: a pointer held across the kernel is two registers of 128)
     auto my_score = [&]() -> int32_t* { return ((task & 1u) ? alt_score : ref_score) + (task >> 1); };
-    vtxf::Front fr;
+    vtxf::Front fr{};
     fr.why = vtxf::W_SHAPE; fr.d = 0; fr.need = vtxf::m_zero();
-    typedef vtxf::LaneS<ST, vtxf::S_WORDS, (A <= 3)> LaneT;
-    const LaneT ln{lane_mem + vtxf::S_WORDS * 64 + tid, 64, (ST*)lane_mem + tid, 64};
     vtxf::Tab tb;
     tb.gt = gtables; tb.ent = tb.head = tb.bytes = tb.uq = tb.pb = 0; tb.hmask = n_heads - 1;
     s_cnt[tid] = 0;
@@ -2473,7 +2488,7 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
         PH(3);                                                          // the mask
         if (VTX_ABLATE((stats >> 8) & 0xffu) == 3) { if (live && d == 0x7fffffff) counters->diag_dummy = 1; return; }       // (profiling aid) up to the diagonal and its mask
         if (live) {
-            vtxf::TwinHead th;
+            vtxf::TwinHead th{};
             if (twins) th = vtxf::twin_head(tb);
             fr = vtxf::front_rest<LaneT, A>(x, m, tb, n, ln, d, M, twins);
             if (fr.why != vtxf::W_OK) { live = false; fail = true; why = fr.why; }
@@ -2842,11 +2857,41 @@ __global__ __launch_bounds__(256, WPE) void band_diag_kernel(
         else { fail = true; tight = tight_list != nullptr; }
     }
     PH(10);                                                             // closure, run bound
-    diag_route(task, fail, why, tight, aux, spread, [&]() { return vtxf::far_rows(fr.d, ns, ln); }, ln, fr.r, fr.cert, fr.zc, vtxf::band_pack(fr),
+    diag_route(tid, task, fail, why, tight, aux, spread, [&]() { return vtxf::far_rows(fr.d, ns, ln); }, ln, fr.r, fr.cert, fr.zc, vtxf::band_pack(fr),
                ref_score, alt_score, fail_list,
                refine_rec, refine_cap, counters, stats, tight_list, tight_pack, dense_list, dense_mask);
     PH(11);                                                             // lists
-    if (VTX_DEVTOOLS_ON && ph_on && tid == 0) atomicAdd(&g_diag_phase[blockIdx.x & 255u][15], 1ull);
+    if (VTX_DEVTOOLS_ON && ph_on && tid == 0) atomicAdd(&g_diag_phase[blockIdx.x & 255u][15], 1ull);     // (a trip: the cycles above are per 64 tasks)
+    };
+    if constexpr (!CLAIM) {
+        // a workgroup per WG consecutive tasks, the workgroups dealt to the 8 XCDs round-robin (blockIdx % 8): XCD x takes the x-th eighth
+        // of the batch, so that the wavefronts that share a locus' tables meet in one L2
+        const uint32_t n_wgb = (n_blocks + NWV - 1) / NWV, per_wgb = (n_wgb + 7) / 8;
+        const uint32_t wgb = (blockIdx.x & 7u) * per_wgb + (blockIdx.x >> 3);
+        if (wgb < n_wgb && wgb * NWV + wv < n_blocks) trip(wgb * NWV + wv);
+    } else {
+        // The wavefront claims blocks until none is left, as band_run_kernel's workgroups do: from its XCD's eighth of the batch first
+        // (counters->block[xcd], zeroed by the launch), then it helps the other eighths out.  Lane 0 claims; the block and the turn are
+        // the loop's only state, both scalar.
+        const uint32_t per_xcd = (n_blocks + 7) / 8;
+        uint32_t turn = 0;                                               // eighths found empty so far (8: nothing left)
+        for (;;) {
+            uint32_t blk = 0xffffffffu;
+            if (lane == 0)
+                while (turn < 8) {
+                    const uint32_t r = ((blockIdx.x & 7u) + turn) & 7u;
+                    const uint32_t lo = r * per_xcd, hi = min(n_blocks, lo + per_xcd);
+                    const uint32_t k = lo + atomicAdd(VTX_COUNTER_AT(counters, block, r), 1u);
+                    if (lo < hi && k < hi) { blk = k; break; }
+                    ++turn;
+                }
+            turn = (uint32_t)__builtin_amdgcn_readfirstlane((int)turn);
+            blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)blk);
+            if (blk == 0xffffffffu) break;
+            wave_sync();                                                 // (the last trip's LDS reads — diag_route's — before this trip's writes)
+            trip(blk);
+        }
+    }
 }
 
 // =============================================================================================
@@ -2940,7 +2985,7 @@ __global__ __launch_bounds__(64) void band_tail_kernel(
             for (int i = 0; i < vtxf::NW; ++i)
                 far.w[i] = (uint64_t)rec[(size_t)(4 + 2 * i) * tail_cap] | ((uint64_t)rec[(size_t)(5 + 2 * i) * tail_cap] << 32);
         }
-        diag_route(task, fail, out & 15u, tight, 0xffffffffu, false, [&]() { return far; }, ln, 0, (int)(w2 >> 18), 0u, pack, ref_score,
+        diag_route(tid, task, fail, out & 15u, tight, 0xffffffffu, false, [&]() { return far; }, ln, 0, (int)(w2 >> 18), 0u, pack, ref_score,
                    alt_score, fail_list, refine_rec, refine_cap, counters, stats, tight_list, tight_pack, dense_list, dense_mask);
     }
 }
@@ -3355,6 +3400,24 @@ extern "C" hipError_t vtxk_launch_band_recheck(const vtx_task_arrays& a, const v
     return hipGetLastError();
 }
 
+// band_diag_kernel's workgroup (threads) and the grid of its claim loop: the workgroups the device holds at once — the occupancy query
+// times the CU count, as for band_tail_kernel's side launches.  (The query failing: no cap; the loop is right on any grid.)
+constexpr int DIAG_WG = 64;
+constexpr bool DIAG_CLAIM = false;
+template <int WG, bool CLAIM, class ST, int A>
+static uint32_t diag_grid(uint32_t n_wgb, uint32_t grid_hook) {
+    if constexpr (!CLAIM) return ((n_wgb + 7) / 8) * 8;                  // (no loop: a workgroup per WG tasks, in eighths)
+    static const uint32_t n = [] {
+        int dev = 0, cus = 0, per_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, band_diag_kernel<WG, CLAIM, ST, A>, WG, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
+            (void)hipGetLastError();
+            return 0xffffffffu;
+        }
+        return (uint32_t)cus * (uint32_t)per_cu;
+    }();
+    return std::min({n_wgb, grid_hook, n});
+}
 // Tables of loci [tb.gt_l0, tb.gt_l0 + tb.n_loci) into tb.gtables (table_geom: the layout and bucket count vtxk_launch_band_run picks
 // for this shape of data), then band_diag_kernel over tasks [task_base, task_base + n_tasks).  Returns hipErrorInvalidValue when the
 // tables do not fit the buffer (the caller then runs band_run_kernel alone, which falls back to tables in LDS).
@@ -3375,20 +3438,40 @@ extern "C" hipError_t vtxk_launch_band_diag(const vtx_task_arrays& a, uint32_t n
     if (!tb.gtables || (size_t)tb.n_loci * 2 * g.tstride > tb.gtables_bytes) return hipErrorInvalidValue;
     const bool use_t3 = band_use_t3(sh.tasks_per_locus);
     launch_band_tables(a.loci, tb.gt_l0, tb.n_loci, a.hap, sh.max_hap, sh.min_hap, g.tstride, g.n_heads, tb.gtables, use_t3, s);
-    const uint32_t n_blocks = (n_tasks + 255) / 256;
+    const uint32_t n_blocks = (n_tasks + 63) / 64;                        // what a wavefront claims: 64 consecutive tasks
+    // (libvtx_dev.so: VTX_DIAG_CLAIM=0 — no claim loop, a workgroup per WG tasks, the launch of rounds 3 - 20; VTX_DIAG_WG=64|256 — the
+    //  other workgroup size; VTX_DIAG_GRID=<n> — any grid for the loop, so that a test's few blocks go round it.  Read per launch.)
+    const bool claim = VTX_DEV_ENV("VTX_DIAG_CLAIM") ? atoi(VTX_DEV_ENV("VTX_DIAG_CLAIM")) != 0 : DIAG_CLAIM;
+    const uint32_t wg = VTX_DEV_ENV("VTX_DIAG_WG") ? (atoi(VTX_DEV_ENV("VTX_DIAG_WG")) == 64 ? 64u : 256u) : (uint32_t)DIAG_WG;
+    const uint32_t grid_hook = VTX_DEV_ENV("VTX_DIAG_GRID") ? std::max(1u, (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_GRID"))) : 0xffffffffu;
+    const uint32_t n_wgb = (n_tasks + wg - 1) / wg;
     const uint32_t st = diag_stats_word(routes, sh);
-#define LAUNCH_DIAG(STV, AV)                                                                                                              \
-    hipLaunchKernelGGL((band_diag_kernel<4, STV, AV>), dim3(((n_blocks + 7) / 8) * 8), dim3(256), 0, s, n_tasks, task_base, n_blocks,       \
+    // The loop's grid: what the device holds at once and never more than there are blocks (a shallow batch has fewer blocks than the
+    // device has places: no wavefront starts only to find nothing).  Without the loop: a workgroup per WG tasks, in eighths.
+#define LAUNCH_DIAG_AS(WGV, CLV, STV, AV)                                                                                                 \
+    hipLaunchKernelGGL((band_diag_kernel<WGV, CLV, STV, AV>),                                                                               \
+                       dim3(diag_grid<WGV, CLV, STV, AV>(n_wgb, grid_hook)), dim3(WGV), 0, s, n_tasks, task_base, n_blocks,               \
                        a.records, a.rec_locus, a.loci, a.read, sh.max_hap, (uint32_t)g.tstride, g.n_heads, (const uint8_t*)tb.gtables,      \
                        tb.gt_l0, a.ref, a.alt, routes.fail_list, routes.refine_rec, routes.refine_cap, routes.counters, st,                 \
                        routes.tight_list, routes.tight_pack, routes.stage, routes.dense_list, routes.dense_mask, sh.min_hap, tail.rec,      \
                        tail.cap, recheck.rec, recheck.cap)
+#ifdef VTX_DEVTOOLS
+#define LAUNCH_DIAG(STV, AV)                                                                                                              \
+    do {                                                                                                                                  \
+        if (wg == 64) { if (claim) LAUNCH_DIAG_AS(64, true, STV, AV); else LAUNCH_DIAG_AS(64, false, STV, AV); }                           \
+        else { if (claim) LAUNCH_DIAG_AS(256, true, STV, AV); else LAUNCH_DIAG_AS(256, false, STV, AV); }                                  \
+    } while (0)
+#else
+#define LAUNCH_DIAG(STV, AV) LAUNCH_DIAG_AS(DIAG_WG, DIAG_CLAIM, STV, AV)
+#endif
+    if (claim) { const hipError_t e = hipMemsetAsync(routes.counters->block, 0, sizeof routes.counters->block, s); if (e != hipSuccess) return e; }
     if (tail.rec) { const hipError_t e = hipMemsetAsync(&routes.counters->tail, 0, sizeof routes.counters->tail, s); if (e != hipSuccess) return e; }
     if (recheck.rec) { const hipError_t e = hipMemsetAsync(&routes.counters->recheck, 0, sizeof routes.counters->recheck, s); if (e != hipSuccess) return e; }
     const bool three = diag_three_words(sh.max_read);
     if (diag_narrow(sh.max_hap)) { if (three) LAUNCH_DIAG(uint16_t, 3); else LAUNCH_DIAG(uint16_t, vtxf::NW); }
     else { if (three) LAUNCH_DIAG(uint32_t, 3); else LAUNCH_DIAG(uint32_t, vtxf::NW); }
 #undef LAUNCH_DIAG
+#undef LAUNCH_DIAG_AS
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || !tail.rec || !tail_inline) return e;
     return vtxk_launch_band_tail(a, sh, routes, tail, 0, s);

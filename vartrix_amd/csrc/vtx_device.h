@@ -63,7 +63,10 @@ struct vtx_band_counters {
     // band_diag_kernel's lists and those of the kernels over its records, zeroed per chunk: tasks left for band_run_kernel, tasks for
     // band_sweep_kernel, records for band_refine_kernel / band_corridor_kernel, tasks with a one-diagonal band
     struct lists_t { uint32_t run_left, dense, refine, tight; } lists;
-    uint32_t block[8];                  // band_run_kernel's block counters, one per XCD: zeroed per launch
+    // block counters of a claim loop, one per XCD: band_run_kernel's (BandPass::run_stage and its second chance zero them in front of each
+    // launch) and, in libvtx_dev.so with VTX_DIAG_CLAIM=1, band_diag_kernel's before that (vtxk_launch_band_diag zeroes them in front of
+    // its kernel, per chunk); the two kernels run on one stream, never side by side
+    uint32_t block[8];
     // what the full-matrix check in front of the one-diagonal bands leaves, of the first stage and of the second: zeroed per launch
     uint32_t check, check2;
     // band_sweep_kernel: band slots of the slice (zeroed per slice) and declined tasks (per pass); sweep2: the second pass of round 4's kernel (libvtx_dev.so)
