@@ -614,12 +614,43 @@ int vtx_csr_group_sum(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t
                       const uint32_t* d_group, uint32_t n_groups, uint64_t nnz_out,
                       uint64_t* d_indptr_out, uint32_t* d_indices_out, const vtx_csr_stats* out);
 
+/* ---- donor tally: a cell's reads by the genotype class of every pooled donor (vartrix_amd/csrc/vtx_csr_geno.hip) ------------------------
+ * The step that produces the donor label: cells of pooled samples are scored against the known genotypes of the donors.  The CSR's
+ * MINOR dimension is the variants (rows = cells: the payloads a vtx_csr_transpose moved).  d_geno[n_minor * n_donors] holds one byte
+ * per (variant, donor), variant-major: 0 hom-ref, 1 het, 2 hom-alt, or VTX_GENO_NONE for a donor without a call there.  For every
+ * (row r, donor d, class g = 0, 1, 2, 3 = missing), at element (r * n_donors + d) * 4 + g of each array of `out`:
+ *   sum_alt / sum_ref   the alt / ref counts summed over the entries of row r whose variant has class g in donor d
+ *   n_obs               how many of those entries have alt + ref > 0
+ * Every likelihood model in use is a linear function of these numbers.  The arrays have n_major * n_donors * 4 elements; any pointer
+ * may be NULL and is then not written; every element of the others is written, zeros for rows without entries.
+ * Like vtx_csr_select this works on ANY CSR in caller-owned DEVICE memory (rows in any order inside, duplicate indices allowed: every
+ * entry counts), needs a context but no run, is synchronous on the context's stream, and checks its inputs on the device BEFORE
+ * anything is written: the CSR as above, then the table: every byte must be 0, 1, 2 or VTX_GENO_NONE.  A violation returns VTX_E_INVAL
+ * (the reason in vtx_strerror; for a byte it names the variant and the donor of the lowest offending position), no output byte is
+ * written and the context stays usable.  VTX_E_INVAL also for n_donors == 0, a null `out` and a null array that is needed (d_geno
+ * unless n_minor == 0); VTX_E_UNSUPPORTED for nnz >= 2^32 and for n_donors > vtx_csr_geno_max().  Outputs must not overlap inputs.
+ * One wavefront walks a row with up to 64 donors on its lanes and keeps the twelve numbers of a donor in registers; with more donors
+ * it repeats the row once per 64 (correct, and need not be fast), which vtx_csr_geno_max() = 16 passes bounds.  No atomics, no zeroing
+ * pass, integer additions only: the result is a function of the input alone.  Work space: the checks' flag words only.                */
+#define VTX_GENO_NONE 0xFFu            /* a donor without a genotype call at a variant */
+typedef struct vtx_geno_tally {
+    uint64_t *sum_alt, *sum_ref;       /* n_major * n_donors * 4 elements each */
+    uint32_t *n_obs;
+} vtx_geno_tally;
+uint32_t vtx_csr_geno_max(void);       /* the largest n_donors accepted */
+uint32_t vtx_sizeof_geno_tally(void);  /* sizeof(vtx_geno_tally) as the library was built: 24 (the table of vtx_abi_sizes is unchanged) */
+int vtx_csr_geno_tally(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
+                       const uint64_t* d_indptr, const uint32_t* d_indices,
+                       const uint32_t* d_alt, const uint32_t* d_ref,
+                       const uint8_t* d_geno, uint32_t n_donors, const vtx_geno_tally* out);
+
 /* Device time of the context's last CSR call that succeeded, in milliseconds, from events on the context's own stream.
  * vtx_device_csr / vtx_csr_transpose: ms[0] the check of the inputs, ms[1] the sort of the positions by column, ms[2] the offsets,
  * ms[3] the placement of the indices and payloads (vtx_device_csr: 1 and 3 are 0).  vtx_csr_row_stats: ms[0] the check, ms[3] the
  * reduction (1 and 2 are 0).  vtx_csr_select_plan / vtx_csr_select: ms[0] the check, ms[1] the scans, ms[2] the offsets and ids, ms[3]
  * the placement (the plan: 2 and 3 are 0).  vtx_csr_group_plan / vtx_csr_group_sum: ms[0] the checks of the CSR and of the labels,
- * ms[1] the count and its scan, ms[3] the fill (2 is 0; the plan: 3 is 0 too).  Writes the first n of the four, at most four.         */
+ * ms[1] the count and its scan, ms[3] the fill (2 is 0; the plan: 3 is 0 too).  vtx_csr_geno_tally: ms[0] the checks of the CSR and
+ * of the genotype table, ms[3] the tally (1 and 2 are 0).  Writes the first n of the four, at most four.                              */
 int vtx_last_csr_ms(vtx_ctx* ctx, float* ms, uint32_t n);
 
 /* ---- Multi-GPU: one process (one ctx) per GPU, loci sharded over the ranks (src/main.rs:284-291: chunks of loci

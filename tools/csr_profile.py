@@ -26,7 +26,13 @@ GPU box:   python tools/csr_profile.py --ops --json profiles/r13_csr_ops.json
 numpy model before it is timed, next to (a) vtx_csr_row_stats on the same CSR — the floor: the same bytes without the gather —, (b) torch
 on the device (rows by repeat_interleave, key = row * n_groups + label, seven index_add_ into a dense buffer) and (c) the host (the
 arrays copied out, scipy A @ one-hot).
-GPU box:   python tools/csr_profile.py --group --json profiles/r14_csr_group.json"""
+GPU box:   python tools/csr_profile.py --group --json profiles/r14_csr_group.json
+
+--geno measures the donor tally (vtx_csr_geno_tally) on the synthetic CSR of config 3's cell-major shape (the generator --group uses) with
+a random genotype table of 8 and of 64 donors, each result compared with a numpy model before it is timed, next to (a) vtx_csr_row_stats
+on the same CSR — the same bytes without the gather — and (b) torch on the device (rows by repeat_interleave, a gather of the genotype
+rows, three index_add_ into a dense buffer).
+GPU box:   python tools/csr_profile.py --geno --json profiles/r22_csr_geno.json"""
 import argparse
 import json
 import os
@@ -56,6 +62,7 @@ ap.add_argument("--skip-mmread", action="store_true", help="leave out the Matrix
 ap.add_argument("--ops", action="store_true", help="measure vtx_csr_row_stats / vtx_csr_select instead of the hand-over")
 ap.add_argument("--sweep", action="store_true", help="time csr_row_stats_kernel at every group size (developer library), no batch")
 ap.add_argument("--group", action="store_true", help="measure vtx_csr_group_plan / vtx_csr_group_sum on synthetic CSRs, no batch")
+ap.add_argument("--geno", action="store_true", help="measure vtx_csr_geno_tally on a synthetic cell-major CSR, no batch")
 args = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -256,6 +263,75 @@ if args.group:
                 del out, label
             res["shapes"][name] = one
             del csr, host, floor_out
+    finish(res)
+    sys.exit(0)
+
+if args.geno:
+    from vartrix_amd import abi
+    n_major, n_minor, mean = args.barcodes, args.loci, 2392.3 * args.loci / 100_000
+    res = {"what": "vtx_csr_geno_tally (tools/csr_profile.py --geno): median of %d after one warm-up, one process; a synthetic cell-major CSR "
+                   "with Poisson row lengths and uniform random columns, a random genotype table (classes 0 / 1 / 2 / missing at 35 / 30 / 20 / "
+                   "15 %%); device ms by phase from vtx_last_csr_ms" % args.runs, "geno_max": lib.load().vtx_csr_geno_max(), "n_donors": {}}
+    gen = torch.Generator(device=dev).manual_seed(11)
+    byte_of = torch.tensor([0, 1, 2, abi.VTX_GENO_NONE], dtype=torch.uint8, device=dev)
+    with lib.Context(default_config(n_barcodes=4)) as ctx:
+        lens = torch.poisson(torch.full((n_major,), mean, device=dev), generator=gen).clamp_(max=n_minor).to(torch.int64)
+        indptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(lens, 0)])
+        nnz = int(indptr[-1])
+        csr = {"indptr": indptr, "indices": torch.randint(0, n_minor, (nnz,), dtype=torch.int32, device=dev, generator=gen)}
+        for k in ("alt", "ref", "unk"):
+            csr[k] = torch.randint(0, 3, (nnz,), dtype=torch.int32, device=dev, generator=gen)
+        host = {k: v.cpu().numpy() for k, v in csr.items()}
+        rows_host = np.repeat(np.arange(n_major, dtype=np.int64), np.diff(host["indptr"]))
+        res.update({"n_major": n_major, "n_minor": n_minor, "nnz": nnz})
+        floor_out = stats_buffers(n_major)
+        res["row_stats_floor"] = series(stats_call(ctx, csr, n_major, n_minor, floor_out), ctx.csr_ms)
+        for n_donors in (8, 64):
+            cls = torch.multinomial(torch.tensor([0.35, 0.3, 0.2, 0.15], device=dev), n_minor * n_donors, replacement=True, generator=gen)
+            table = byte_of[cls].reshape(n_minor, n_donors).contiguous()
+            n = n_major * n_donors * 4
+            out = {"sum_alt": torch.empty(n, dtype=torch.int64, device=dev), "sum_ref": torch.empty(n, dtype=torch.int64, device=dev),
+                   "n_obs": torch.empty(n, dtype=torch.int32, device=dev)}
+            torch.cuda.synchronize(dev)
+
+            def tally_call():
+                return ctx.csr_geno_tally(n_major, n_minor, nnz, csr["indptr"].data_ptr(), csr["indices"].data_ptr(), csr["alt"].data_ptr(),
+                                          csr["ref"].data_ptr(), table.data_ptr(), n_donors, {k: v.data_ptr() for k, v in out.items()})
+            tally_call()
+            # ---- correctness first: per donor, numpy's bincount over (row, class) with the counts as weights (exact: sums far below 2^53) ----
+            got = {k: v.cpu().numpy().reshape(n_major, n_donors, 4) for k, v in out.items()}
+            cls_host = cls.reshape(n_minor, n_donors).cpu().numpy()
+            seen = ((host["alt"] + host["ref"]) > 0).astype(np.float64)
+            for d in range(n_donors):
+                key = rows_host * 4 + cls_host[host["indices"], d]
+                for k, w in (("sum_alt", host["alt"]), ("sum_ref", host["ref"]), ("n_obs", seen)):
+                    want = np.bincount(key, weights=w, minlength=n_major * 4).astype(np.int64).reshape(n_major, 4)
+                    assert np.array_equal(got[k][:, d].astype(np.int64), want), (n_donors, d, k)
+            print("n_donors %d: equals the numpy model" % n_donors, flush=True)
+            E = {"geno_tally": series(tally_call, ctx.csr_ms)}
+
+            def torch_tally():
+                rows = torch.repeat_interleave(torch.arange(n_major, device=dev), csr["indptr"][1:] - csr["indptr"][:-1])
+                g = table[csr["indices"].to(torch.int64)].to(torch.int64)                  # nnz x n_donors: the gather of the genotype rows
+                g = torch.where(g == abi.VTX_GENO_NONE, 3, g)
+                key = ((rows[:, None] * n_donors + torch.arange(n_donors, device=dev)) * 4 + g).reshape(-1)
+                a, r = csr["alt"].to(torch.int64), csr["ref"].to(torch.int64)
+                o = [torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, key, w[:, None].expand(nnz, n_donors).reshape(-1))
+                     for w in (a, r, ((a + r) > 0).to(torch.int64))]
+                torch.cuda.synchronize(dev)
+                return o
+            try:
+                dense = torch_tally()
+                for d, k in zip(dense, abi.GENO_TALLY_NAMES):
+                    assert torch.equal(d, out[k].to(torch.int64)), k
+                del dense
+                E["torch_gather_index_add_dense"] = series(torch_tally)
+            except Exception as e:                               # noqa: BLE001  (the record IS the error)
+                E["torch_gather_index_add_dense"] = {"error": "%s: %s" % (type(e).__name__, str(e).splitlines()[0][:200] if str(e) else "")}
+            res["n_donors"][str(n_donors)] = E
+            print(n_donors, "tally", E["geno_tally"]["device_ms_by_phase_median"], "wall", E["geno_tally"]["host_wall_ms_median"], "torch",
+                  E["torch_gather_index_add_dense"].get("host_wall_ms_median", E["torch_gather_index_add_dense"].get("error")), flush=True)
+            del out, table, cls
     finish(res)
     sys.exit(0)
 

@@ -133,6 +133,15 @@ CSR_STAT_NAMES = CSR_STAT_COUNTS + CSR_STAT_SUMS
 VTX_GROUP_NONE = 0xFFFFFFFF          # vtx_csr_group_*: the label of a column that belongs to no group
 
 
+VTX_GENO_NONE = 0xFF                 # vtx_csr_geno_tally: the genotype byte of a donor without a call at a variant
+GENO_TALLY_NAMES = ("sum_alt", "sum_ref", "n_obs")                    # uint64, uint64, uint32: n_major * n_donors * 4 elements each
+
+
+class VtxGenoTally(C.Structure):
+    """vtx_geno_tally: where vtx_csr_geno_tally stores the twelve numbers of every (row, donor) pair; a NULL pointer is not written."""
+    _fields_ = [("sum_alt", C.POINTER(C.c_uint64)), ("sum_ref", C.POINTER(C.c_uint64)), ("n_obs", C.POINTER(C.c_uint32))]
+
+
 class VtxCsrStats(C.Structure):
     """vtx_csr_stats: where vtx_csr_row_stats stores the seven statistics of every row; a NULL pointer is not written."""
     _fields_ = [(k, C.POINTER(C.c_uint32)) for k in CSR_STAT_COUNTS] + [(k, C.POINTER(C.c_uint64)) for k in CSR_STAT_SUMS]

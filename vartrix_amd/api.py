@@ -17,6 +17,10 @@ ref / unknown counts summed over the cells of the group and the number of its ce
 ``vtx_csr_group_sum`` on the device for a torch result, scipy on the host for a scipy one); ``run(groups=)`` does it on the stacked CSR
 of the run, and ``read_groups()`` reads the labels from a two-column file such as cellranger's ``clusters.csv``.
 
+``donor_tally()`` produces what the donor label is made from when samples are pooled: per (cell, donor) pair the cell's alt and ref reads
+by the class of the donor's known genotype at each variant (``vtx_csr_geno_tally`` on the device for a torch result, scipy on the host
+for a scipy one; ``read_genotypes()`` reads the table from a VCF), and ``assign_donors()`` is the plain likelihood on top, in numpy.
+
 There is no CPU path: the scores, the calls, the offsets and the transpose are computed on the GPU; torch carries the device arrays
 (``__cuda_array_interface__``) and, for ``to="scipy"``, copies the finished arrays to the host.
 """
@@ -554,3 +558,206 @@ def pseudobulk(result: Result, groups, *, to=None) -> GroupResult:
         if orient == "cells":                    # back to variant-major: the fold sums over the columns
             csr = _transpose(ctx, torch, dev, csr, n_cell, n_var, ("alt", "ref", "unk"))
         return _pseudobulk_device(ctx, torch, dev, csr, result.variants, result.barcodes, groups, orient, to or "torch")
+
+
+@dataclass
+class DonorTally:
+    """Every cell's reads by the genotype class of every donor: arrays of cells x donors x 4, int64 (numpy, or torch tensors on the
+    result's device).  The last axis is the class of the donor's genotype at the variant of an entry: 0 hom-ref, 1 het, 2 hom-alt,
+    3 missing."""
+    alt: object               # alt reads of the cell at the variants where the donor has that class
+    ref: object               # ref reads
+    n_obs: object             # entries of the cell with alt + ref > 0 at those variants
+    donors: list
+    barcodes: list
+
+
+@dataclass
+class DonorAssignment:
+    best: object              # int64 per cell: the donor (an index into ``donors``) with the highest likelihood; -1 for a cell without a read at a genotyped variant
+    margin: object            # float64 per cell: the best log-likelihood minus the second best; +inf with one donor
+    log_lik: object           # float64, cells x donors
+    donors: list
+    barcodes: list
+
+
+_GT_CLASS = {("0", "0"): 0, ("0", "1"): 1, ("1", "0"): 1, ("1", "1"): 2}
+
+
+def read_genotypes(path, variants):
+    """The genotypes of the donors of a text VCF (plain or ``.gz``) at the variants of a run.  -> (uint8 array, len(variants) x
+    donors: 0 hom-ref, 1 het, 2 hom-alt, ``abi.VTX_GENO_NONE`` missing; the donor names of the ``#CHROM`` line).
+
+    A record belongs to the variant named ``"{chrom}_{pos0}"`` (``pos0`` = POS - 1: what ``Result.variants`` holds).  Its ``GT`` is
+    split at ``/`` or ``|``: ``0/0`` is 0, ``0/1`` and ``1/0`` are 1, ``1/1`` is 2; everything else is missing — a ``.``, a haploid
+    call, an allele index above 1, a record without ``GT``.  A name that occurs more than once, in the file or in ``variants``, is
+    ambiguous and missing for every donor; so is a variant the file lacks."""
+    path = os.fspath(path)
+    times = {}
+    for v in variants:
+        times[v] = times.get(v, 0) + 1
+    donors, seen, calls = [], {}, {}
+    with (gzip.open(path, "rt") if path.endswith(".gz") else open(path, "rt")) as f:
+        for line in f:
+            line = line.rstrip("\r\n")
+            if line.startswith("##") or not line.strip():
+                continue
+            fields = line.split("\t")
+            if line.startswith("#"):
+                donors = fields[9:]
+                continue
+            if len(fields) < 2:
+                continue
+            try:
+                name = "%s_%d" % (fields[0], int(fields[1]) - 1)
+            except ValueError:
+                continue
+            seen[name] = seen.get(name, 0) + 1
+            if name not in times or seen[name] > 1:
+                continue
+            row = np.full(len(donors), abi.VTX_GENO_NONE, np.uint8)
+            keys = fields[8].split(":") if len(fields) > 8 else []
+            if "GT" in keys:
+                at = keys.index("GT")
+                for d, sample in enumerate(fields[9:9 + len(donors)]):
+                    parts = sample.split(":")
+                    gt = parts[at] if at < len(parts) else "."
+                    row[d] = _GT_CLASS.get(tuple(gt.replace("|", "/").split("/")), abi.VTX_GENO_NONE)
+            calls[name] = row
+    geno = np.full((len(variants), len(donors)), abi.VTX_GENO_NONE, np.uint8)
+    for i, v in enumerate(variants):
+        if times[v] == 1 and seen.get(v, 0) == 1:
+            geno[i] = calls[v]
+    return geno, list(donors)
+
+
+def _genotypes(genotypes, donors, variants):
+    """The table as (uint8 array of len(variants) x donors, donor names), from an array or from a path for ``read_genotypes``."""
+    if isinstance(genotypes, (str, os.PathLike)):
+        geno, names = read_genotypes(genotypes, variants)
+    else:
+        raw = np.asarray(genotypes.cpu() if _is_torch(genotypes) else genotypes)
+        if raw.ndim != 2 or raw.shape[0] != len(variants):
+            raise ValueError("donor_tally: genotypes of shape %s: one row per variant of the result (%d), one column per donor" % (raw.shape, len(variants)))
+        wide = raw.astype(np.int64)
+        bad = np.argwhere(~np.isin(wide, (0, 1, 2, abi.VTX_GENO_NONE)))
+        if len(bad):
+            raise ValueError("donor_tally: the genotype of variant %d, donor %d is %d: 0, 1, 2 or VTX_GENO_NONE" % (bad[0][0], bad[0][1], wide[tuple(bad[0])]))
+        geno, names = np.ascontiguousarray(wide.astype(np.uint8)), list(range(raw.shape[1]))
+    if donors is not None:
+        names = list(donors)
+        if len(names) != geno.shape[1]:
+            raise ValueError("donor_tally: %d donor names for %d columns of genotypes" % (len(names), geno.shape[1]))
+    return geno, names
+
+
+def _geno_tally(ctx, torch, dev, csr, n_major, n_minor, geno, n_donors):
+    """A CELL-major CSR with ``alt`` / ``ref`` arrays against the table on the device (``vtx_csr_geno_tally``) -> the three arrays of
+    ``abi.GENO_TALLY_NAMES`` as int64 tensors of n_major x n_donors x 4."""
+    nnz = int(csr["indices"].shape[0])
+    src = {k: csr[k].contiguous() for k in ("indptr", "indices", "alt", "ref")}
+    table = torch.from_numpy(np.ascontiguousarray(geno, np.uint8).reshape(-1).copy()).to(dev)
+    n = n_major * n_donors * 4
+    raw = {"sum_alt": torch.empty(n, dtype=torch.int64, device=dev), "sum_ref": torch.empty(n, dtype=torch.int64, device=dev),
+           "n_obs": torch.empty(n, dtype=torch.int32, device=dev)}
+    torch.cuda.synchronize(dev)
+    ctx.csr_geno_tally(n_major, n_minor, nnz, src["indptr"].data_ptr(), src["indices"].data_ptr(), src["alt"].data_ptr(), src["ref"].data_ptr(),
+                       table.data_ptr(), n_donors, {k: v.data_ptr() for k, v in raw.items()})
+    raw["n_obs"] = raw["n_obs"].to(torch.int64) & 0xFFFFFFFF
+    return {k: v.reshape(n_major, n_donors, 4) for k, v in raw.items()}
+
+
+def _donor_tally_host(result, geno, orient):
+    """The tally of a scipy result on the host: per class ``A^T @ (geno == g)`` for a variant-major ``A``, ``A @ (geno == g)`` for a
+    cell-major one; ``A`` the alt counts, the ref counts, and the indicator of alt + ref > 0."""
+    import scipy.sparse as sp
+    alt, ref = (sp.csr_matrix(m).astype(np.int64) for m in (result.alt_counts, result.ref_counts))
+    obs = sp.csr_matrix((alt + ref) > 0).astype(np.int64)
+    n_cell, n_donors = len(result.barcodes), geno.shape[1]
+    out = {k: np.zeros((n_cell, n_donors, 4), np.int64) for k in ("alt", "ref", "n_obs")}
+    for g, byte in enumerate((0, 1, 2, abi.VTX_GENO_NONE)):
+        has = (geno == byte).astype(np.int64)
+        for k, m in (("alt", alt), ("ref", ref), ("n_obs", obs)):
+            out[k][:, :, g] = np.asarray((m.T if orient == "variants" else m) @ has).reshape(n_cell, n_donors)
+    return out
+
+
+def donor_tally(result: Result, genotypes, donors=None, *, to=None) -> DonorTally:
+    """Every cell's reads tallied against the known genotypes of pooled donors: per (cell, donor) pair the alt reads, the ref reads and
+    the informative entries of the cell, by the class of the donor's genotype at the entry's variant (0 hom-ref, 1 het, 2 hom-alt,
+    3 missing) — the integer part of scoring cells against donors, and what ``assign_donors`` takes.
+
+    ``genotypes``: an array of ``len(result.variants)`` x donors holding 0, 1, 2 or ``abi.VTX_GENO_NONE``, or the path of a VCF for
+    ``read_genotypes``; a result cut by ``select`` takes the table cut by the same mask.  ``donors``: their names (default: the VCF's
+    sample names, or 0, 1, ... for an array).
+
+    A torch result is tallied on its device — one ``vtx_csr_geno_tally`` on a bare context for that device (at most
+    ``vtx_csr_geno_max()`` donors), after one transpose of the alt and ref counts if the result is variant-major — into int64
+    tensors, or into numpy arrays with ``to="scipy"``; a scipy result is tallied on the host with scipy into numpy arrays."""
+    n_var, n_cell = len(result.variants), len(result.barcodes)
+    orient = result.orient or ("cells" if tuple(result.shape) == (n_cell, n_var) != (n_var, n_cell) else "variants")
+    if to not in (None, "scipy", "torch"):
+        raise ValueError("to %r: scipy, torch, or None for the container of the result" % (to,))
+    geno, names = _genotypes(genotypes, donors, result.variants)
+    n_donors = geno.shape[1]
+    if not _is_torch(result.alt_counts):
+        if to == "torch":
+            raise ValueError("donor_tally: a scipy result is tallied on the host; to=\"torch\" needs a torch result (run(to=\"torch\"))")
+        out = _donor_tally_host(result, geno, orient)
+        return DonorTally(alt=out["alt"], ref=out["ref"], n_obs=out["n_obs"], donors=names, barcodes=list(result.barcodes))
+    import torch
+    first = result.alt_counts
+    dev = first.device
+    if first.values().shape[0] != result.ref_counts.values().shape[0]:
+        raise ValueError("donor_tally: the count matrices do not have one sparsity")
+    csr = {"indptr": first.crow_indices(), "indices": first.col_indices().to(torch.int32), "alt": first.values().to(torch.int32),
+           "ref": result.ref_counts.values().to(torch.int32)}
+    if not n_donors:                             # nothing to tally against, and the library takes no table without donors
+        out = {k: torch.zeros((n_cell, 0, 4), dtype=torch.int64, device=dev) for k in abi.GENO_TALLY_NAMES}
+    else:
+        index = torch.cuda.current_device() if dev.index is None else dev.index
+        with lib.Context(abi.default_config(n_barcodes=max(n_cell, 1), device=index)) as ctx:    # no batch, no run: device, stream, work space
+            if orient == "variants":             # to cell-major: a wavefront tallies the row of a cell
+                csr = _transpose(ctx, torch, dev, csr, n_var, n_cell, ("alt", "ref"))
+            out = _geno_tally(ctx, torch, dev, csr, n_cell, n_var, geno, n_donors)
+    if to == "scipy":
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+    return DonorTally(alt=out["sum_alt"], ref=out["sum_ref"], n_obs=out["n_obs"], donors=names, barcodes=list(result.barcodes))
+
+
+def assign_donors(tally_or_result, genotypes=None, *, error=0.01) -> DonorAssignment:
+    """The most likely donor of every cell under the plain genotype model: a read of a cell shows the alt allele with probability
+    ``p = (error, 0.5, 1 - error)`` where its donor is hom-ref, het, hom-alt.  Takes a ``DonorTally``, or a ``Result`` with the
+    ``genotypes`` ``donor_tally`` takes.  In numpy float64, from the integer tallies, in exactly this order:
+
+        ll = alt[..., 0] * log(p[0]) + ref[..., 0] * log1p(-p[0]) + alt[..., 1] * log(p[1]) + ref[..., 1] * log1p(-p[1])
+             + alt[..., 2] * log(p[2]) + ref[..., 2] * log1p(-p[2])
+
+    so that the same tallies give the same bits wherever they were counted.  Missing genotypes contribute nothing.  ``best`` is the
+    donor with the highest ``ll``, the lowest index on a tie, and -1 for a cell whose ``n_obs`` over the classes 0 - 2 is zero for every
+    donor; ``margin`` is the best minus the second best, ``+inf`` with one donor.  ``error`` must lie in (0, 0.5).
+
+    Out of scope: doublets, ambient RNA, and clustering without genotypes (souporcell's and vireo's other modes)."""
+    if not 0.0 < float(error) < 0.5:
+        raise ValueError("assign_donors: error %r: a probability in (0, 0.5)" % (error,))
+    tally = tally_or_result
+    if isinstance(tally, Result):
+        if genotypes is None:
+            raise ValueError("assign_donors: a Result needs the genotypes of the donors")
+        tally = donor_tally(tally, genotypes, to="scipy" if _is_torch(tally.alt_counts) else None)
+    alt, ref, n_obs = (np.asarray(a.cpu() if _is_torch(a) else a).astype(np.float64) for a in (tally.alt, tally.ref, tally.n_obs))
+    p = (float(error), 0.5, 1.0 - float(error))
+    ll = (alt[..., 0] * np.log(p[0]) + ref[..., 0] * np.log1p(-p[0]) + alt[..., 1] * np.log(p[1]) + ref[..., 1] * np.log1p(-p[1])
+          + alt[..., 2] * np.log(p[2]) + ref[..., 2] * np.log1p(-p[2]))
+    n_cell, n_donors = ll.shape
+    if n_donors:
+        best = np.argmax(ll, axis=1).astype(np.int64)
+        best[n_obs[..., :3].sum(axis=(1, 2)) == 0] = -1
+    else:
+        best = np.full(n_cell, -1, np.int64)
+    if n_donors >= 2:
+        top = np.sort(ll, axis=1)
+        margin = top[:, -1] - top[:, -2]
+    else:
+        margin = np.full(n_cell, np.inf)
+    return DonorAssignment(best=best, margin=margin, log_lik=ll, donors=list(tally.donors), barcodes=list(tally.barcodes))

@@ -279,4 +279,14 @@ hipError_t vtxr_group_count(const vtx_group_in& in, uint32_t* pos, void* temp, s
 hipError_t vtxr_group_fill(const vtx_group_in& in, const uint32_t* pos, uint64_t* indptr_out, uint32_t* indices_out, const vtx_csr_stats* out,
                            hipStream_t s);
 }
+// ---- vtx_csr_geno.hip: a cell's reads tallied against donor genotypes.  The CSR has passed vtxr_check, the table vtxr_geno_check ----
+// the matrix (rows = cells, indices = variants) and the table as the tally kernel reads them: geno[n_minor * n_donors], variant-major,
+// every byte 0, 1, 2 or VTX_GENO_NONE
+struct vtx_geno_in { const uint64_t* indptr; uint32_t n_major; const uint32_t* indices; const uint32_t *alt, *ref; const uint8_t* geno; uint32_t n_donors; };
+extern "C" {
+// first_bad: one 64-bit word, all ones in front of the check; behind it the lowest flat index of a byte that is neither a class nor VTX_GENO_NONE
+hipError_t vtxr_geno_check(const uint8_t* geno, uint64_t n_bytes, uint64_t* first_bad, hipStream_t s);
+// the arrays of `out` (any of them NULL: not written) have n_major * n_donors * 4 elements, each stored once
+hipError_t vtxr_geno_tally(const vtx_geno_in& in, const vtx_geno_tally* out, hipStream_t s);
+}
 #endif

@@ -41,6 +41,7 @@ SYMBOLS = (
     "vtx_device_csr", "vtx_csr_transpose", "vtx_last_csr_ms",
     "vtx_csr_row_stats", "vtx_csr_select_plan", "vtx_csr_select", "vtx_sizeof_csr_stats",
     "vtx_csr_group_window", "vtx_csr_group_max", "vtx_csr_group_plan", "vtx_csr_group_sum",
+    "vtx_csr_geno_max", "vtx_sizeof_geno_tally", "vtx_csr_geno_tally",
 )
 # (entry points with a digit in their name: tests/test_abi.py finds the header's declarations with [a-z_]+ and compares them with SYMBOLS,
 # so these are listed — and checked against the header and every build of the library, tests/test_abi_f64.py — on their own)
@@ -112,6 +113,12 @@ def load(variant=None):
     L.vtx_csr_group_sum.restype = C.c_int
     L.vtx_csr_group_sum.argtypes = csr_in + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
                                              C.POINTER(abi.VtxCsrStats)]
+    L.vtx_csr_geno_max.restype = C.c_uint32
+    L.vtx_csr_geno_max.argtypes = []
+    L.vtx_sizeof_geno_tally.restype = C.c_uint32
+    L.vtx_sizeof_geno_tally.argtypes = []
+    L.vtx_csr_geno_tally.restype = C.c_int
+    L.vtx_csr_geno_tally.argtypes = csr_in + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(abi.VtxGenoTally)]
     L.vtx_sizeof_csr_stats.restype = C.c_uint32
     L.vtx_sizeof_csr_stats.argtypes = []
     L.vtx_last_csr_ms.restype = C.c_int
@@ -473,6 +480,21 @@ class Context:
         self._check(self._L.vtx_csr_group_sum(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
                                               ref or None, unk or None, group or None, int(n_groups), int(nnz_out), indptr_out or None,
                                               indices_out or None, C.byref(st)))
+
+    def csr_geno_tally(self, n_major: int, n_minor: int, nnz: int, indptr: int, indices: int, alt: int, ref: int, geno: int, n_donors: int,
+                       out: dict):
+        """Every row of a CSR in device memory (rows = cells, indices = variants) tallied against the genotypes of ``n_donors`` donors
+        (vtx_csr_geno_tally).  ``geno``: the address of n_minor * n_donors bytes, variant-major, each 0, 1, 2 or ``abi.VTX_GENO_NONE``.
+        ``out``: name (``abi.GENO_TALLY_NAMES``) -> address of n_major * n_donors * 4 uint64 (``sum_alt``, ``sum_ref``) / uint32
+        (``n_obs``); a name that is missing or 0 is not written."""
+        unknown = set(out) - set(abi.GENO_TALLY_NAMES)
+        if unknown:
+            raise ValueError("csr_geno_tally: unknown outputs %s" % sorted(unknown))
+        st = abi.VtxGenoTally()
+        for k, typ in st._fields_:
+            setattr(st, k, C.cast(C.c_void_p(int(out.get(k) or 0) or None), typ))
+        self._check(self._L.vtx_csr_geno_tally(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
+                                               ref or None, geno or None, int(n_donors), C.byref(st)))
 
     def comm_init(self, ident: bytes, rank: int, world: int):
         """Join the RCCL communicator of the sharded run (collective; vtx_comm_init)."""
