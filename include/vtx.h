@@ -172,7 +172,7 @@ typedef struct vtx_timing {
     float sweep_ms;        /* band_sweep_kernel + band-masked DP over what is left (part of band_ms)                 */
     uint32_t checked_tasks; /* alignments that left the certificate stages WITH a certificate: one-diagonal band + masked DP */
     uint32_t swept_tasks;  /* alignments handed to band_sweep_kernel                                                 */
-    uint32_t resweep_tasks; /* (round 4's sweep kernel, developer build only: tasks of its second pass)                     */
+    uint32_t resweep_tasks; /* always 0: round 4's sweep kernel, which counted its second pass here, is gone; kept for the layout */
     uint32_t diag2_tasks;  /* alignments the second single-diagonal stage looked at (band_diag2_kernel: what the first left with
                               more off-diagonal matches than its list holds) ...                                              */
     uint32_t diag2_scored; /* ... of which it decided outright (cert == ub); the rest of them is in checked_tasks (one-diagonal

@@ -24,7 +24,7 @@ ROUND3_STAGES = (abi.STAGE_UNKNOWN, abi.STAGE_RUN_DP, abi.STAGE_GENERAL_DP)     
 # vtx_timing's task counts.  All of them are compared with the fresh context's on the production library: each is a count of tasks
 # with a property of the task (list lengths read back after the kernels finished), none depends on the order of the atomics that
 # built the lists.
-# (resweep_tasks is not listed: only round 4's sweep kernel in the developer library sets it.)
+# (resweep_tasks is not listed: nothing sets it since round 4's sweep kernel left the developer library, last in commit 5c0dd06; it is always 0.)
 TASK_COUNTS = ("hard_tasks", "overflow_tasks", "diag_left", "checked_tasks", "swept_tasks", "diag2_tasks", "diag2_scored", "diag2_streamed")
 COO_INT = ("row", "col", "alt", "ref", "unk")
 

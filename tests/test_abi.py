@@ -101,3 +101,30 @@ def test_production_library_has_no_experiment_hooks(L):
     D = lib.load("dev")
     for name in lib.SYMBOLS:
         assert hasattr(D, name), name
+
+
+def test_every_developer_hook_is_used_and_documented():
+    """A path selected only by a variable that nobody sets is untested code: every name in VTX_DEV_ENV("...") of the library sources
+    occurs in a test, a tool or bench.py, and in DESIGN.md."""
+    # VTX_SWEEP_DBG: vtx_debug_bands prints band_sweep_kernel's per-task state through the kernel's `dbg` parameter; taking the hook
+    # out would change a production kernel
+    exempt = {"VTX_SWEEP_DBG"}
+    csrc = os.path.join(ROOT, "vartrix_amd", "csrc")
+    hooks = set()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".h")):
+            hooks |= set(re.findall(r'VTX_DEV_ENV\("([A-Z0-9_]+)"\)', open(os.path.join(csrc, f)).read()))
+    assert len(hooks) >= 30 and exempt <= hooks
+    users = open(os.path.join(ROOT, "bench.py")).read()
+    for top in ("tests", "tools"):
+        for d, _dirs, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                if f.endswith((".py", ".sh", ".cpp", ".hip", ".h")) or f == "Makefile":
+                    users += open(os.path.join(d, f), errors="replace").read()
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+
+    def names(text):
+        return set(re.findall(r"VTX_[A-Z0-9_]+", text))
+    used, documented = names(users), names(design)
+    assert sorted(hooks - exempt - used) == [], "set by no test, tool or bench.py"
+    assert sorted(hooks - documented) == [], "not in DESIGN.md"

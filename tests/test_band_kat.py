@@ -101,26 +101,20 @@ def test_oracle_reproduces_every_vector(kat):
 def test_sweep_model_reproduces_every_band(kat):
     subprocess.check_call(["make", "-C", os.path.join(HERE, "sweepmodel"), "-s"])
     L = C.CDLL(os.path.join(HERE, "sweepmodel", "libsweep_model.so"))
-    L.vtxs_band.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.vtxs_band.restype = C.c_int
     L.vtxs_band2.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vtxs_band2.restype = C.c_int
     done = 0
     for v in kat["vectors"]:
         x, y = v["read"].encode("latin-1"), v["hap"].encode("latin-1")
-        for model in (1, 2):                                   # round 4's formulation (dp ring) and round 5's (sections per diagonal)
-            lo = np.zeros(len(y) + 1, np.int32)
-            hi = np.zeros(len(y) + 1, np.int32)
-            if model == 1:
-                rc = L.vtxs_band(x, len(x), y, len(y), 1 << 20, 1 << 20, lo.ctypes.data, hi.ctypes.data, None)
-            else:
-                rc = L.vtxs_band2(x, len(x), y, len(y), 1 << 20, 1 << 20, 1 << 20, lo.ctypes.data, hi.ctypes.data, None)
-            if rc == 1:
-                continue                                       # bytes outside ACGTN / more than 255 bases: the kernel declines those
-            assert rc == 0
-            assert np.array_equal(lo, unrle(v["lo_rle"])) and np.array_equal(hi, unrle(v["hi_rle"]))
-            done += 1
-    assert done >= 300
+        lo = np.zeros(len(y) + 1, np.int32)                    # (round 5's formulation: sections per diagonal)
+        hi = np.zeros(len(y) + 1, np.int32)
+        rc = L.vtxs_band2(x, len(x), y, len(y), 1 << 20, 1 << 20, 1 << 20, lo.ctypes.data, hi.ctypes.data, None)
+        if rc == 1:
+            continue                                           # bytes outside ACGTN / more than 255 bases: the kernel declines those
+        assert rc == 0
+        assert np.array_equal(lo, unrle(v["lo_rle"])) and np.array_equal(hi, unrle(v["hi_rle"]))
+        done += 1
+    assert done >= 220                                         # (of 360 vectors the model accepts 220; 140 are declined with status 1)
 
 
 @pytest.mark.gpu

@@ -47,8 +47,8 @@ CONFIGS = {
 }
 HOOKS = sorted({k for env in CONFIGS.values() for k in env} |
                {"VTX_BAND_HARD_CAP", "VTX_BAND_SLOTS", "VTX_DIAG_TAIL_CAP", "VTX_DIAG_TAIL_GRID", "VTX_DIAG_REFINE_CAP", "VTX_DIAG_RECHECK_CAP",
-                "VTX_DIAG_NO_TAIL", "VTX_DIAG_NO_RECHECK", "VTX_DIAG_ABLATE", "VTX_BAND_NO_DIAG2", "VTX_BAND_NO_STREAM", "VTX_BAND_NO_REFINE",
-                "VTX_BAND_DENSE_MASK", "VTX_BAND_RUN_MIN", "VTX_SWEEP_V1", "VTX_DEBUG"})
+                "VTX_DIAG_NO_TAIL", "VTX_DIAG_NO_RECHECK", "VTX_DIAG_ABLATE", "VTX_BAND_NO_STREAM", "VTX_BAND_NO_REFINE",
+                "VTX_BAND_DENSE_MASK", "VTX_BAND_RUN_MIN", "VTX_DEBUG"})
 
 # The child: the four batches, each on a fresh context with the stage trace on; one JSON object per batch.
 CODE = r'''

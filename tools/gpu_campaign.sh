@@ -11,7 +11,9 @@
 #                                                           design for values != 0, only the kernel times are read
 #   bash tools/gpu_campaign.sh variants OUTDIR WORKLOAD LIB...   the same workload on several builds of the library, one line each: LIB is
 #                                                           prod (libvtx.so) or a VTX_LIB_VARIANT name (dev, lazy0, ..., or an experimental
-#                                                           libvtx_<name>.so built by hand: how S2_WORDS / the stream kernel's occupancy were chosen)
+#                                                           libvtx_<name>.so built by hand: how S2_WORDS / the stream kernel's occupancy were chosen).
+#                                                           The Makefile's A/B builds nw3 / not3 and round 4's sweep kernel (VTX_SWEEP_V1) are gone, last in
+#                                                           commit 5c0dd06: VTX_DIAG_FOUR_WORDS / VTX_DIAG_NO_T3 on dev select the same code at run time
 #   bash tools/gpu_campaign.sh final   OUTDIR               the round's closing set: default bench line, stats of every workload, the depth
 #                                                           ladder, config 4 on one GPU, the PMC passes (tools/pmc_collect.sh), the CLI end to end
 #

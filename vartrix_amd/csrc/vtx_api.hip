@@ -1424,9 +1424,8 @@ static int ingest_inflate_crc(vtx_ctx* c, IngestState& is) {
     HIP_TRY(c, hipEventRecord(c->ev[EV_INGEST_START], s));
     HIP_TRY(c, vtxg_inflate(c->d_bam_comp.as<uint8_t>(), c->d_bam_blocks.as<vtxg_block>(), nb, c->d_bam_data.as<uint8_t>(), is.d_cnt.err, nullptr, 0, s));
     HIP_TRY(c, hipEventRecord(c->ev[EV_INFLATE_END], s));
-    static const bool no_crc = VTX_DEV_ENV("VTX_NO_CRC") != nullptr;                                   // A/B timing only: the check off
     HIP_TRY(c, hipEventRecord(c->ev_crc[0], s));
-    if (!no_crc) HIP_TRY(c, vtxg_crc32(c->d_bam_comp.as<uint8_t>(), c->d_bam_blocks.as<vtxg_block>(), nb, c->d_bam_data.as<uint8_t>(), is.d_cnt.err, nullptr, 0, crc_width(), s));
+    HIP_TRY(c, vtxg_crc32(c->d_bam_comp.as<uint8_t>(), c->d_bam_blocks.as<vtxg_block>(), nb, c->d_bam_data.as<uint8_t>(), is.d_cnt.err, nullptr, 0, crc_width(), s));
     HIP_TRY(c, hipEventRecord(c->ev_crc[1], s));
     c->crc_ms = 0;
     return VTX_OK;
@@ -1678,14 +1677,10 @@ namespace {
 // The developer hooks of vtx_run that hold for the life of the process (libvtx_dev.so; in libvtx.so every VTX_DEV_ENV is the constant
 // nullptr and the members are their defaults), and whether VTX_DEBUG asked for the kernels' statistics.  Read once, by band_knobs().
 inline bool env_is(const char* v, const char* what) { return v && !strcmp(v, what); }
-inline uint32_t env_atoi(const char* v, uint32_t dflt) { return v ? (uint32_t)atoi(v) : dflt; }
 inline uint32_t env_u32(const char* v, int base, uint32_t dflt) { return v ? (uint32_t)strtoul(v, nullptr, base) : dflt; }
 struct BandKnobs {
     bool no_duo = env_is(VTX_DEV_ENV("VTX_DP_KERNEL"), "lut"), no_pair = env_is(VTX_DEV_ENV("VTX_DP_KERNEL"), "duo2");   // (duo2: two-lookup prefix phase)
-    uint32_t lds_tasks = env_atoi(VTX_DEV_ENV("VTX_BAND_LDS_TASKS"), 4096u);    // experiment knob
     bool no_coop = VTX_DEV_ENV("VTX_BAND_NO_COOP") != nullptr;                  // experiment / test hook
-    bool sweep_v1 = VTX_DEV_ENV("VTX_SWEEP_V1") != nullptr;                     // round 4's band_sweep_kernel: the A/B reference of tests/test_gpu_sweep.py and tools/gpu_campaign.sh
-    bool no_diag2 = VTX_DEV_ENV("VTX_BAND_NO_DIAG2") != nullptr;                // everything to the sweep, as round 4 did
     uint32_t diag2_min = env_u32(VTX_DEV_ENV("VTX_BAND_DIAG2_MIN"), 10, 700000u);   // the shortest list the second stage takes (see second_stage_on)
     bool no_stream = VTX_DEV_ENV("VTX_BAND_NO_STREAM") != nullptr;              // what exceeds the second stage's list goes to the sweep
     bool no_diag = VTX_DEV_ENV("VTX_BAND_NO_DIAG") != nullptr;                  // experiment / test hook: stage 1 off
@@ -1716,7 +1711,7 @@ template <class T> hipError_t read_back(T& host, const T& member, hipStream_t st
 // Tasks [t_begin, t_end) whose locus has its longer haplotype in (mh_min, mh] (the others are left alone); chunk_tables: the tables are built per chunk for the loci the chunk spans, whatever the
 // buffer would hold. Per chunk of tasks (task = 2*record + hap), round 4 (the stages are described in vtx_band.hip's header): tables -> band_diag_kernel (+ band_refine_kernel): scores of the
 // certified tasks, and three lists — tasks whose band is one diagonal stretch (masked DP straight from one word), repeats (band_sweep_kernel + masked DP), the others (band_run_kernel: seeds,
-// chain, general certificate; its hard list -> expand -> masked DP).  What overflows band_run_kernel's lists joins the repeats after the last chunk; what band_sweep_kernel declines twice takes
+// chain, general certificate; its hard list -> expand -> masked DP).  What overflows band_run_kernel's lists joins the repeats after the last chunk; what band_sweep_kernel declines takes
 // the general band kernel (side stream). The counters are vtx_band_counters (vtx_device.h), what is read back through pinned memory PinnedCounters, the events EvSlot.
 struct BandPass {
     vtx_ctx* const c;
@@ -1737,7 +1732,7 @@ struct BandPass {
     vtx_diag_routes routes{};
     vtx_band_out run_out{};
     vtx_band_counters::run_t cnt{};             // host copy of band_run_kernel's counters
-    uint32_t pending_total = 0, over_before = 0, resweep_total = 0;
+    uint32_t pending_total = 0, over_before = 0;
     uint64_t diag_total = 0, diag_left = 0, refined_total = 0, checked_total = 0, swept_total = 0, diag2_total = 0, diag2_scored = 0, tight2_total = 0, stream_total = 0;
     float diag_ms = 0, check_ms = 0, sweep_ms = 0;
     bool sweep_used = false;                    // some chunk took the round-4 path
@@ -1809,7 +1804,7 @@ struct BandPass {
         int launch() {
             // A few overflow tasks (shallow data: some hundreds per run) first try the in-LDS variant of the general kernel
             // with a slab for kLdsMatches k-mer matches: their ~2 ms of serial HBM latency were a third of a shallow step.
-            const uint32_t kLdsMatches = 512, mh = sh.max_hap;
+            const uint32_t kLdsMatches = 512, kLdsTasks = 4096, mh = sh.max_hap;       // (kLdsTasks: the longest list the in-LDS variant takes)
             const uint64_t worst = (uint64_t)c->max_read_len * mh;
             if (cap2 >= worst && cap2 >= 512) return fail(c, VTX_E_STATE, "vtx_run: band kernel overflow with a worst-case slab");
             // first three rounds: the cooperative kernel, everything in LDS (band_coop_kernel: a wavefront per task, up to 512 matches,
@@ -1826,7 +1821,7 @@ struct BandPass {
                 HIP_TRY(c, zero(cnt.overflow, s2));
                 HIP_TRY(c, vtxk_launch_band_coop(a, tier, tasks, todo, sh, out, s2));
             } else {
-                const bool in_lds = cap2 < 512 && todo <= kn.lds_tasks && !VTX_DEV_ENV("VTX_BAND_NO_LDS_FALLBACK") && vtxk_band_lds_stride(kLdsMatches, mh, c->max_read_len) <= 160 * 1024 - 512;
+                const bool in_lds = cap2 < 512 && todo <= kLdsTasks && vtxk_band_lds_stride(kLdsMatches, mh, c->max_read_len) <= 160 * 1024 - 512;
                 cap2 = in_lds ? kLdsMatches : (uint32_t)std::max<uint64_t>(std::min<uint64_t>((uint64_t)cap2 * 16, worst), 512);
                 const size_t stride2 = vtxk_band_ws_stride(cap2, mh);
                 if (!in_lds) {                                                  // whole wavefronts: the 64 slabs are interleaved, vtxk_band_lanes() of them in use
@@ -1872,19 +1867,14 @@ struct BandPass {
         }
     } fb{*this};
     // the band of every listed task (band_sweep_kernel), one slice of band slots at a time, then the masked DP over the slice (its length — the tasks the sweep did not decline — is read on the
-    // device: counters[0]; declined: counters[1]) (libvtx_dev.so, VTX_SWEEP_V1=1: round 4's kernel instead — 256 sections per task (tier 0), then a second pass with 1 024 (tier 1) over what the
-    // first declined.  tier means nothing to band_sweep_kernel: the production build ignores it; the parameter stays so that the callers read the same in both builds.)
-    int sweep_slices([[maybe_unused]] int tier, const uint32_t* list, uint32_t n, uint32_t* over_out, vtx_cnt_pair* counters) {
+    // device: counters[0]; declined: counters[1])
+    int sweep_slices(const uint32_t* list, uint32_t n, uint32_t* over_out, vtx_cnt_pair* counters) {
         uint32_t* why = kn.sweep_stats ? d_cnt->sweep_why : nullptr;
         HIP_TRY(c, c->d_sweep_log.reserve(vtxk_band_sweep_log_bytes()));
         const vtx_band_out out{c->d_band.as<uint16_t>(), bp.band_stride, c->d_hard.as<uint32_t>(), over_out, counters};
         for (uint32_t off = 0; off < n; off += bp.slots) {
             const uint32_t cnt_s = std::min(bp.slots, n - off);
             HIP_TRY(c, zero(counters->hard, s));
-#ifdef VTX_DEVTOOLS
-            if (kn.sweep_v1) HIP_TRY(c, vtxk_launch_band_sweep_v1(a, tier, list + off, cnt_s, nullptr, out, why, rs.stage, nullptr, s));
-            else
-#endif
             HIP_TRY(c, vtxk_launch_band_sweep(a, list + off, cnt_s, nullptr, out, why, rs.stage, nullptr, c->d_sweep_log.as<uint32_t>(), s));
             HIP_TRY(c, vtxk_launch_sw_banded_dev(a, shape[0], shape[1], cnt_s, out.hard_list, &counters->hard, out.band, out.band_stride, mh, s));
             rs.launches += 2;
@@ -1894,7 +1884,7 @@ struct BandPass {
     // Second stage (round 5; DESIGN.md 4.3.3b, where its threshold of 700 k tasks is measured): band_diag2_kernel, band_stream_kernel for what exceeds its list, the full-matrix check + masked DP
     // over the one-diagonal bands they prove; what they leave — out[0, *n_out) — takes the sweep.  One host round trip for the counts. The tables of the tasks' loci have to be resident (tb:
     // the table buffer as the stage that built them was handed it).
-    bool second_stage_on(uint32_t n) const { return !kn.no_diag2 && n >= kn.diag2_min && mh <= 255; }
+    bool second_stage_on(uint32_t n) const { return n >= kn.diag2_min && mh <= 255; }
     int second_stage(const uint32_t* list, uint32_t n, const vtx_band_tables& tb, uint32_t* out, uint32_t* n_out) {
         HIP_TRY(c, zero(d_cnt->diag2, s));
         HIP_TRY(c, zero(d_cnt->streamed, s));
@@ -2076,7 +2066,7 @@ struct BandPass {
         ++rs.launches;
         return VTX_OK;
     }
-    // repeats: band_sweep_kernel (the band of ANY task) + masked DP, sorted by task; what it declines waits in d_over[2 n_tasks ..) for the second pass after the last chunk (a short list of the
+    // repeats: band_sweep_kernel (the band of ANY task) + masked DP, sorted by task; what it declines waits in d_over[2 n_tasks ..) for the general band kernel after the last chunk (a short list of the
     // other tasks is not worth band_run_kernel's launch — a persistent grid: ~1 ms whatever the count — and the two host round trips behind it: it joins the repeats, ~25 ns per task)
     int repeats(Chunk& ch, uint32_t n_dense) {
         if (ch.n_fail && ch.n_fail < kn.run_min && (uint64_t)n_dense + ch.n_fail <= ch.nt) {
@@ -2095,7 +2085,7 @@ struct BandPass {
             if (int rc = second_stage(dl, n_dense, ch.tb, sweep2, &n_sweep)) return rc;
             sl = sweep2;
         }
-        if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, c->d_over.as<uint32_t>() + 2 * bp.n_tasks, &d_cnt->sweep)) return rc; }
+        if (n_sweep) { if (int rc = sweep_slices(sl, n_sweep, c->d_over.as<uint32_t>() + 2 * bp.n_tasks, &d_cnt->sweep)) return rc; }
         swept_total += n_sweep;
         return VTX_OK;
     }
@@ -2190,8 +2180,7 @@ struct BandPass {
         return VTX_OK;
     }
     // After the last chunk of a pass with a sweep.  What overflowed band_run_kernel's lists (d_over[0, nA)) takes band_sweep_kernel too; then everything the sweep declined — here and in the
-    // chunks' own sweeps: d_over[2 n_tasks, + nB), counted on the device — takes the general band kernel (round 4's kernel, libvtx_dev.so: first its second pass, [2 n_tasks + nB, + nC) is what
-    // is left).
+    // chunks' own sweeps: d_over[2 n_tasks, + nB), counted on the device — takes the general band kernel.
     int last_chunk() {
         uint32_t *over = c->d_over.as<uint32_t>(), *declined = over + 2 * bp.n_tasks;
         const uint32_t nA = cnt.overflow;
@@ -2205,23 +2194,15 @@ struct BandPass {
                 if (int rc = second_stage(over, nA, every_locus, c->d_dense.as<uint32_t>(), &n_sweep)) return rc;
                 sl = c->d_dense.as<uint32_t>();
             }
-            if (n_sweep) { if (int rc = sweep_slices(0, sl, n_sweep, declined, &d_cnt->sweep)) return rc; }
+            if (n_sweep) { if (int rc = sweep_slices(sl, n_sweep, declined, &d_cnt->sweep)) return rc; }
             swept_total += n_sweep;
         }
-        uint32_t nB = 0, nC = 0;
+        uint32_t nB = 0;                            // what band_sweep_kernel declines (bytes outside ACGTN, > 255 bases, > 1 024 sections, a full stash bucket)
         HIP_TRY(c, read_back(nB, d_cnt->sweep.overflow, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         if (int rc = collect_sweep_times()) return rc;
-        if (nB && kn.sweep_v1) {                    // (round 4's kernel only: its second pass with the larger log)
-            resweep_total = nB;
-            if (int rc = sweep_slices(1, declined, nB, declined + nB, &d_cnt->sweep2)) return rc;
-            HIP_TRY(c, read_back(nC, d_cnt->sweep2.overflow, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-        } else if (nB) {                            // what band_sweep_kernel declines (bytes outside ACGTN, > 255 bases, > 1 024 sections, a
-            nC = nB; nB = 0;                        // full stash bucket) takes the general band kernel
-        }
-        cnt.overflow = nC;
-        if (nC) { if (int rc = fb.start((uint32_t)(2 * bp.n_tasks) + nB, (uint32_t)(2 * bp.n_tasks) + nB + nC)) return rc; }
+        cnt.overflow = nB;
+        if (nB) { if (int rc = fb.start((uint32_t)(2 * bp.n_tasks), (uint32_t)(2 * bp.n_tasks) + nB)) return rc; }
         return VTX_OK;
     }
     // the general kernel's end; the pass's times and task counts ADDED to the run's; the VTX_DEBUG lines
@@ -2239,7 +2220,6 @@ struct BandPass {
         c->timing.diag_ms += diag_ms; c->timing.diag_left += (uint32_t)std::min<uint64_t>(diag_left, 0xffffffffull);
         c->timing.check_ms += check_ms; c->timing.sweep_ms += sweep_ms;
         c->timing.swept_tasks += (uint32_t)std::min<uint64_t>(swept_total, 0xffffffffull);
-        c->timing.resweep_tasks += resweep_total;
         c->timing.diag2_tasks += (uint32_t)std::min<uint64_t>(diag2_total, 0xffffffffull);
         c->timing.diag2_scored += (uint32_t)std::min<uint64_t>(diag2_scored, 0xffffffffull);
         c->timing.diag2_streamed += (uint32_t)std::min<uint64_t>(stream_total, 0xffffffffull);
@@ -2274,7 +2254,7 @@ int run_prologue(vtx_ctx* c, RunState& rs) {
     c->ran = false;
     c->fast_overflow = 0;
     c->timing.diag_ms = c->timing.check_ms = c->timing.sweep_ms = 0;
-    c->timing.diag_left = c->timing.checked_tasks = c->timing.swept_tasks = c->timing.resweep_tasks = 0;
+    c->timing.diag_left = c->timing.checked_tasks = c->timing.swept_tasks = 0;     // (resweep_tasks: never set, see vtx.h)
     c->timing.diag2_tasks = c->timing.diag2_scored = c->timing.diag2_streamed = 0;
     rs.a = vtx_task_arrays{c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), c->d_ref.as<int32_t>(), c->d_alt.as<int32_t>()};
     if (c->stage_trace && nr) {
@@ -2527,12 +2507,6 @@ int vtx_debug_bands(vtx_ctx* c, const uint32_t* tasks, uint32_t n_tasks, uint32_
     const vtx_task_arrays a{c->d_records.as<vtx_record>(), c->d_rec_locus.as<uint32_t>(), c->d_loci.as<vtx_locus>(), c->d_read.as<uint8_t>(), c->d_hap.as<uint8_t>(), nullptr, nullptr};
     const vtx_band_out out{d_b.as<uint16_t>(), bs, d_h.as<uint32_t>(), d_o.as<uint32_t>(), d_c.as<vtx_cnt_pair>()};
     uint32_t* dbg = dbg_on ? d_d.as<uint32_t>() : nullptr;
-#ifdef VTX_DEVTOOLS
-    // (libvtx_dev.so: VTX_SWEEP_V1=1 asks round 4's kernel instead; VTX_SWEEP_TIER=1 its 1024-section variant)
-    if (VTX_DEV_ENV("VTX_SWEEP_V1"))
-        DBG_TRY(vtxk_launch_band_sweep_v1(a, VTX_DEV_ENV("VTX_SWEEP_TIER") ? atoi(VTX_DEV_ENV("VTX_SWEEP_TIER")) : 0, d_t.as<uint32_t>(), n_tasks, nullptr, out, nullptr, nullptr, dbg, s));
-    else
-#endif
     DBG_TRY(vtxk_launch_band_sweep(a, d_t.as<uint32_t>(), n_tasks, nullptr, out, nullptr, nullptr, dbg, c->d_sweep_log.as<uint32_t>(), s));
     vtx_cnt_pair swept{};                    // band_sweep_kernel's two counters: band slots, declined tasks
     DBG_TRY(hipMemcpyAsync(&swept, d_c.p, sizeof swept, hipMemcpyDeviceToHost, s));

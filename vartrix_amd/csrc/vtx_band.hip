@@ -710,13 +710,7 @@ extern "C" hipError_t vtxk_launch_band_coop(const vtx_task_arrays& a, int tier, 
 
 // active lanes per wavefront of band_kernel<false> for a list of n_tasks (the workspace holds 64 slabs per wavefront either way)
 extern "C" uint32_t vtxk_band_lanes(uint32_t n_tasks) {
-    static const int forced = VTX_DEV_ENV("VTX_BAND_LANES") ? atoi(VTX_DEV_ENV("VTX_BAND_LANES")) : 0;       // experiment knob
-    if (forced > 0) {                                         // a power of two in [4, 64]: anything else would leave tasks unscored
-        uint32_t lanes = 4;
-        while (lanes < 64 && lanes < (uint32_t)forced) lanes <<= 1;
-        return lanes;
-    }
-    uint32_t lanes = 64;
+    uint32_t lanes = 64;                                      // (a power of two in [4, 64]: anything else would leave tasks unscored)
     while (lanes > 4 && (n_tasks + lanes - 1) / lanes < 4096u) lanes >>= 1;        // >= 4096 wavefronts: 16 per CU
     return lanes;
 }
@@ -820,7 +814,7 @@ __device__ __forceinline__ void build_t3_wave(uint8_t* tb, uint32_t hn, uint32_t
     const uint2* ent = TB_ENT(tb);
     uint32_t* t3 = TB_T3(tb);
     const int nk = hn >= (uint32_t)KMER ? (int)hn - KMER + 1 : 0;
-    for (int y = tid; y < nk && vtxf::T3_BYTES != 0; y += 64) {
+    for (int y = tid; y < nk; y += 64) {
         const uint32_t c = vtxf::kw_code(ent[y].x, ent[y].y & 0xffffu);
         atomicOr(&t3[vtxf::t3_word_a(c)], 1u << vtxf::t3_bit_a(c));
         atomicOr(&t3[vtxf::t3_word_b(c)], 1u << vtxf::t3_bit_b(c));
@@ -2039,7 +2033,7 @@ __global__ __launch_bounds__(64) void band_tables_kernel(const vtx_locus* __rest
                 }
                 const uint32_t code = vtxf::kw_code(klo, khi);
                 atomicOr(&pb[code >> 5], 1u << (code & 31u));
-                if (vtxf::T3_BYTES != 0 && with_t3) {
+                if (with_t3) {
                     atomicOr(&t3[vtxf::t3_word_a(code)], 1u << vtxf::t3_bit_a(code));
                     atomicOr(&t3[vtxf::t3_word_b(code)], 1u << vtxf::t3_bit_b(code));
                     atomicOr(&t3[vtxf::t3_word_c(code)], 1u << vtxf::t3_bit_c(code));
@@ -2524,7 +2518,7 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
     // all three with one 8-byte load (vtx_fast_core.h).  The rows are cut into blocks that END at rows e = m - K (mod 3) (so no block
     // reaches beyond the read's last k-mer; the first may start before row 0: those rows are skipped); a queue entry is
     // pair << 11 | the block's three membership bits << 8 | e, the blocks go to the pair's two lanes in turn.  (Off for shallow batches — band_use_t3 —: a queue entry per row, even rows from the even lane, and pb[] — rounds 3 - 5.)
-    const bool t3_mode = vtxf::T3_BYTES != 0 && !(stats & 0x40000u);                // (per batch: vtxk_launch_band_diag, band_use_t3)
+    const bool t3_mode = !(stats & 0x40000u);                // (per batch: vtxk_launch_band_diag, band_use_t3)
     vtxf::M192 nrows = live ? fr.need : vtxf::m_zero();             // (t3_mode: the pair's rows, kept for the membership bits)
     vtxf::M192 nd;
     {
@@ -3122,14 +3116,16 @@ __global__ __launch_bounds__(256) void band_corridor_kernel(
     }
   }
 }
-// workgroups of band_corridor_kernel the device holds at once (65 536 when the runtime cannot say)
-static uint32_t corridor_resident_grid() {
-    static const uint32_t n = [] {
+// Workgroups of KERNEL (BLOCK threads, no dynamic LDS) the device holds at once: the occupancy query times the CU count; `fallback` when the
+// runtime cannot say.  Asked once per instantiation, that is per kernel (each has one caller, so one fallback).
+template <auto KERNEL, int BLOCK>
+static uint32_t resident_workgroups(uint32_t fallback) {
+    static const uint32_t n = [fallback] {
         int dev = 0, cus = 0, per_cu = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, band_corridor_kernel, 256, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, BLOCK, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
             (void)hipGetLastError();
-            return 65536u;
+            return fallback;
         }
         return (uint32_t)cus * (uint32_t)per_cu;
     }();
@@ -3139,9 +3135,9 @@ extern "C" hipError_t vtxk_launch_band_corridor(const vtx_task_arrays& a, const 
                                                 const uint32_t* n_dev, hipStream_t s) {
     if (!n_recs) return hipSuccess;
     // (n_dev != nullptr: n_recs is a bound — 3.5 M lanes for the headline's 43 k records — and a workgroup past the device's count costs its
-    //  dispatch: at most a resident grid then.  libvtx_dev.so, VTX_CORRIDOR_FULL_GRID=1: the grid over the bound, for the A/B.)
+    //  dispatch: at most a resident grid then.)
     const uint32_t blocks = (n_recs + 255) / 256;
-    const uint32_t grid = n_dev && !VTX_DEV_ENV("VTX_CORRIDOR_FULL_GRID") ? std::min(blocks, corridor_resident_grid()) : blocks;
+    const uint32_t grid = n_dev ? std::min(blocks, resident_workgroups<band_corridor_kernel, 256>(65536u)) : blocks;
     hipLaunchKernelGGL(band_corridor_kernel, dim3(grid), dim3(256), 0, s, recs, n_recs, a.records, a.rec_locus, a.loci, a.read,
                        a.hap, a.ref, a.alt, routes.counters, (uint32_t)routes.stats, routes.tight_list, routes.tight_pack, routes.stage, n_dev);
     return hipGetLastError();
@@ -3182,7 +3178,7 @@ static void launch_band_tables(const vtx_locus* loci, uint32_t gt_l0, uint32_t n
 // reads 16.9 -> 15.7; at four reads per locus, where the tables are a third of the step, 1.57 ms without against 1.67 with, level at
 // sixteen.  Per batch: on from 16 tasks per locus.  (libvtx_dev.so: VTX_DIAG_T3=1 / VTX_DIAG_NO_T3=1 force it on / off.)
 static bool band_use_t3(uint32_t tasks_per_locus) {
-    if (vtxf::T3_BYTES == 0 || VTX_DEV_ENV("VTX_DIAG_NO_T3")) return false;
+    if (VTX_DEV_ENV("VTX_DIAG_NO_T3")) return false;
     if (VTX_DEV_ENV("VTX_DIAG_T3")) return true;
     return tasks_per_locus >= 16;
 }
@@ -3217,12 +3213,13 @@ extern "C" size_t vtxk_band_gtables_bytes(uint32_t n_loci, uint32_t max_hap, uin
     return hold * per_locus;
 }
 
+// tasks per locus from which vtxk_launch_band_run picks the six-wavefront / 12-entry variant (the crossover lies between 32 and 48 reads per locus)
+constexpr uint32_t W6_MIN_TPL = 80;
 // 1: vtxk_launch_band_run picks the six-wavefront / 12-entry variant for this shape — its overflow list deserves a second
 // chance in the 15-entry variant (task_list mode) before the general kernel
 extern "C" int vtxk_band_second_chance(uint32_t tasks_per_locus, int long_lists) {
     if (long_lists) return 0;
-    const uint32_t w6 = VTX_DEV_ENV("VTX_BAND_W6_MIN_TPL") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_BAND_W6_MIN_TPL")) : 80u;
-    return tasks_per_locus >= w6 && tasks_per_locus < gt_max_tpl() && !VTX_DEV_ENV("VTX_BAND_NO_SECOND_CHANCE");
+    return tasks_per_locus >= W6_MIN_TPL && tasks_per_locus < gt_max_tpl();
 }
 
 // persistent grid of band_run_kernel<nt, ., wpe>: what the chip holds (wavefronts per SIMD x 4 SIMDs x 256 CUs)
@@ -3264,8 +3261,7 @@ extern "C" hipError_t vtxk_launch_band_run(const vtx_task_arrays& a, uint32_t n_
     // only the lists — 6 x 12 for deeper loci (config 3: band_run 45.0 -> 39.9 ms; the shorter lists send 2.7x the
     // tasks to the general kernel, still -2.5 ms per step), 5 x 15 for shallower ones (16 reads per locus: 6.9 vs 7.7 ms),
     // 4 x 15 when the grid does not fill the chip anyway.
-    static const uint32_t w6_min_tpl = VTX_DEV_ENV("VTX_BAND_W6_MIN_TPL") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_BAND_W6_MIN_TPL")) : 80u;   // experiment knob (crossover between 32 and 48 reads per locus)
-    const int variant = !global_tables ? 0 : ((task_list || long_lists) ? (tasks_per_locus < 16 && !task_list ? 1 : 2) : (tasks_per_locus < 16 ? 1 : (tasks_per_locus < w6_min_tpl ? 2 : 3)));
+    const int variant = !global_tables ? 0 : ((task_list || long_lists) ? (tasks_per_locus < 16 && !task_list ? 1 : 2) : (tasks_per_locus < 16 ? 1 : (tasks_per_locus < W6_MIN_TPL ? 2 : 3)));
     const uint32_t psv = variant == 3 ? 12u : (uint32_t)VTX_PS;
     const size_t lane_bytes = (size_t)(2 * psv) * nt * 4;
     uint32_t tables;
@@ -3288,7 +3284,8 @@ extern "C" hipError_t vtxk_launch_band_run(const vtx_task_arrays& a, uint32_t n_
     if (global_tables && !task_list)
         launch_band_tables(a.loci, tb.gt_l0, tb.n_loci, a.hap, sh.max_hap, sh.min_hap, tstride, n_heads, tb.gtables, false, s);
     const uint32_t ablate = (uint32_t)(VTX_DEV_ENV("VTX_BAND_ABLATE") ? atoi(VTX_DEV_ENV("VTX_BAND_ABLATE")) : 0);
-    const uint32_t xcd_claim = ((tasks_per_locus >= 24 || VTX_DEV_ENV("VTX_BAND_XCD")) && !VTX_DEV_ENV("VTX_BAND_NO_XCD")) ? 1u : 0u;   // (measured: config 3 -3 %, 64 / 32 reads per locus -4.5 %, 16: -1 %, 4: +2 %)
+    constexpr uint32_t XCD_MIN_TPL = 24;                      // the workgroups claim their blocks per XCD from this many tasks per locus
+    const uint32_t xcd_claim = tasks_per_locus >= XCD_MIN_TPL ? 1u : 0u;   // (measured: config 3 -3 %, 64 / 32 reads per locus -4.5 %, 16: -1 %, 4: +2 %)
 #define LAUNCH_RUN(NTV, GTV, WV, PV)                                                                                 \
     {                                                                                                                \
         if (shmem > 48 * 1024) {                                                                                     \
@@ -3321,7 +3318,7 @@ static bool diag_narrow(uint32_t max_hap) {
 }
 static bool diag_three_words(uint32_t max_read) {
     static const bool force_four = VTX_DEV_ENV("VTX_DIAG_FOUR_WORDS") != nullptr;      // (tests: the four-word build on short reads)
-    return max_read <= 192 && !force_four && vtxf::NW >= 3;
+    return max_read <= 192 && !force_four;
 }
 static uint32_t diag_stats_word(const vtx_diag_routes& routes, const vtx_band_shape& sh) {
     return (uint32_t)routes.stats |(VTX_DEV_ENV("VTX_DIAG_ABLATE") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_ABLATE")) << 8 : 0u) |
@@ -3343,19 +3340,6 @@ extern "C" int vtxk_band_tail_on(vtx_rec_buf tail) {
 // of the records.  With the 65 536 of the launch that has the device to itself a workgroup that ends hands its 8.7 KB of LDS to the
 // next one of this kernel, and a neighbour's workgroup (band_sweep_kernel: 19.1 KB in one piece) finds no room until the last record
 // is taken (DESIGN.md 4.3.7 has the measurement).
-template <class ST, int A, bool RECHECK = false>
-static uint32_t tail_resident_grid() {
-    static const uint32_t n = [] {
-        int dev = 0, cus = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, band_tail_kernel<ST, A, RECHECK>, 64, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
-            (void)hipGetLastError();
-            return 65536u;
-        }
-        return (uint32_t)cus * (uint32_t)per_cu;
-    }();
-    return n;
-}
 extern "C" hipError_t vtxk_launch_band_tail(const vtx_task_arrays& a, const vtx_band_shape& sh, const vtx_diag_routes& routes, vtx_rec_buf tail,
                                             int resident_grid, hipStream_t s) {
     if (!vtxk_band_tail_on(tail)) return hipErrorInvalidValue;
@@ -3365,7 +3349,7 @@ extern "C" hipError_t vtxk_launch_band_tail(const vtx_task_arrays& a, const vtx_
     const uint32_t grid_hook = VTX_DEV_ENV("VTX_DIAG_TAIL_GRID") ? std::max(1u, (uint32_t)atoi(VTX_DEV_ENV("VTX_DIAG_TAIL_GRID"))) : 65536u;
 #define LAUNCH_TAIL(STV, AV)                                                                                                              \
     hipLaunchKernelGGL((band_tail_kernel<STV, AV>),                                                                                         \
-                       dim3(std::min({(tail.cap + 63u) / 64u, 65536u, grid_hook, resident_grid ? tail_resident_grid<STV, AV>() : 65536u})), \
+                       dim3(std::min({(tail.cap + 63u) / 64u, 65536u, grid_hook, resident_grid ? resident_workgroups<band_tail_kernel<STV, AV>, 64>(65536u) : 65536u})), \
                        dim3(64), 0, s, tail.rec, tail.cap,                                                                                  \
                        &routes.counters->tail, a.ref, a.alt, routes.fail_list, routes.refine_rec, routes.refine_cap,                \
                        routes.counters, st, routes.tight_list, routes.tight_pack, routes.stage, routes.dense_list, routes.dense_mask)
@@ -3391,7 +3375,7 @@ extern "C" hipError_t vtxk_launch_band_recheck(const vtx_task_arrays& a, const v
     const uint32_t st = diag_stats_word(routes, sh);
 #define LAUNCH_RECHECK(AV)                                                                                                               \
     hipLaunchKernelGGL((band_tail_kernel<uint16_t, AV, true>),                                                                             \
-                       dim3(std::min({(recheck.cap + 63u) / 64u, 65536u, tail_resident_grid<uint16_t, AV, true>()})), dim3(64), 0, s,      \
+                       dim3(std::min({(recheck.cap + 63u) / 64u, 65536u, resident_workgroups<band_tail_kernel<uint16_t, AV, true>, 64>(65536u)})), dim3(64), 0, s,      \
                        recheck.rec, recheck.cap, &routes.counters->recheck, a.ref, a.alt, routes.fail_list, routes.refine_rec,     \
                        routes.refine_cap, routes.counters, st, routes.tight_list, routes.tight_pack, routes.stage, routes.dense_list,      \
                        routes.dense_mask)
@@ -3407,16 +3391,7 @@ constexpr bool DIAG_CLAIM = false;
 template <int WG, bool CLAIM, class ST, int A>
 static uint32_t diag_grid(uint32_t n_wgb, uint32_t grid_hook) {
     if constexpr (!CLAIM) return ((n_wgb + 7) / 8) * 8;                  // (no loop: a workgroup per WG tasks, in eighths)
-    static const uint32_t n = [] {
-        int dev = 0, cus = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, band_diag_kernel<WG, CLAIM, ST, A>, WG, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
-            (void)hipGetLastError();
-            return 0xffffffffu;
-        }
-        return (uint32_t)cus * (uint32_t)per_cu;
-    }();
-    return std::min({n_wgb, grid_hook, n});
+    return std::min({n_wgb, grid_hook, resident_workgroups<band_diag_kernel<WG, CLAIM, ST, A>, WG>(0xffffffffu)});
 }
 // Tables of loci [tb.gt_l0, tb.gt_l0 + tb.n_loci) into tb.gtables (table_geom: the layout and bucket count vtxk_launch_band_run picks
 // for this shape of data), then band_diag_kernel over tasks [task_base, task_base + n_tasks).  Returns hipErrorInvalidValue when the

@@ -49,8 +49,8 @@ static __host__ __device__ inline bool vtx_bytes_equal(const uint8_t* a, const u
 // say what zeroes them more often.  A group is what the host zeroes or copies as a unit, by its name and sizeof.  A kernel or launcher
 // that is handed the BASE of the block (vtx_diag_routes::counters, vtx_band_out::run_counters) names the members; a kernel
 // that is handed the address of a MEMBER counts from it: a vtx_cnt_pair as counters[0], counters[1] (band_kernel / band_coop_kernel:
-// general; the sweeps: sweep, sweep2; band_diag2_kernel: diag2, from left), a single word as *count (the full-matrix check: check, check2;
-// band_diag2_kernel: streamed; slow_align_kernel: slow; band_tail_kernel: tail, recheck), the sweeps' reasons as stat_counters[].
+// general; band_sweep_kernel: sweep; band_diag2_kernel: diag2, from left), a single word as *count (the full-matrix check: check, check2;
+// band_diag2_kernel: streamed; slow_align_kernel: slow; band_tail_kernel: tail, recheck), the sweep's reasons as stat_counters[].
 struct vtx_cnt_pair { uint32_t hard, overflow; };   // the entries of a kernel's hard list (its band slots in use) and of its overflow list (the tasks it hands on)
 constexpr uint32_t VTX_DIAG_WHY_COUNT = 10;         // vtxf::W_COUNT (vtx_fast_core.h, which not every user of this header can include; vtx_band.hip asserts that the reasons fit)
 struct vtx_band_counters {
@@ -69,8 +69,9 @@ struct vtx_band_counters {
     uint32_t block[8];
     // what the full-matrix check in front of the one-diagonal bands leaves, of the first stage and of the second: zeroed per launch
     uint32_t check, check2;
-    // band_sweep_kernel: band slots of the slice (zeroed per slice) and declined tasks (per pass); sweep2: the second pass of round 4's kernel (libvtx_dev.so)
-    vtx_cnt_pair sweep, sweep2;
+    // band_sweep_kernel: band slots of the slice (zeroed per slice) and declined tasks (per pass).  sweep_spare: two spare words — the second pass of round 4's kernel counted here; the kernel
+    // is gone (vtx_sweep_v1.hip, last in commit 5c0dd06), the words stay so that no member behind them moves (see VTX_COUNTER_AT)
+    vtx_cnt_pair sweep; uint32_t sweep_spare[2];
     struct diag2_t { uint32_t left, tight; } diag2;   // band_diag2_kernel / band_stream_kernel: tasks left for the sweep, tasks with a one-diagonal band; zeroed per call of the second stage
     uint32_t diag_why[VTX_DIAG_WHY_COUNT];   // band_diag_kernel's reasons, by vtxf::Why (statistics)
     uint32_t diag_dummy;                // where band_diag_kernel's profiling aids leave their dummy store
@@ -145,11 +146,6 @@ hipError_t vtxk_launch_band_sweep(const vtx_task_arrays& a, const uint32_t* task
                                   uint32_t* stat_counters, uint8_t* stage, uint32_t* dbg, uint32_t* glog, hipStream_t s);
 size_t vtxk_band_sweep_log_bytes(void);            // glog: the section logs of the resident workgroups
 uint32_t vtxk_band_sweep_grid(uint32_t n_tasks);
-#ifdef VTX_DEVTOOLS
-// round 4's kernel (vtx_sweep_v1.hip, libvtx_dev.so only: VTX_SWEEP_V1=1), the reference of the A/B tests
-hipError_t vtxk_launch_band_sweep_v1(const vtx_task_arrays& a, int tier, const uint32_t* tasks, uint32_t n_tasks, const uint32_t* n_dev, const vtx_band_out& out,
-                                     uint32_t* stat_counters, uint8_t* stage, uint32_t* dbg, hipStream_t s);
-#endif
 uint32_t vtxk_band_sweep_max_len(void);
 hipError_t vtxk_launch_sw_banded_dev(const vtx_task_arrays& a, int R, int GL, uint32_t n_cap, const uint32_t* hard, const uint32_t* n_dev, const uint16_t* band,
                                      uint32_t band_stride, uint32_t max_hap_len, hipStream_t stream);

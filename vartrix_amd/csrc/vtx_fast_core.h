@@ -83,16 +83,14 @@ constexpr int W = VTX_REF_W;
 static_assert(K == 6 && W == 20 && VTX_REF_MATCH == 1 && VTX_REF_MISMATCH == -5 && VTX_REF_GAP_OPEN == -5 && VTX_REF_GAP_EXTEND == -1,
               "the closed forms below (piece dp, join_same, the far-piece lemma, the +1 / -5 scan) are derived for the reference's scoring only");
 constexpr int LAZY = VTX_BAND_LAZY_EXT(6);
-#ifndef VTXF_NW
-#define VTXF_NW 4
-#endif
 // Mutation testing (tests/test_mutants.py, tests/fastcore/Makefile): VTXF_MUTANT = n > 0 makes ONE bound of the certificate stages
 // unsound on purpose, so that the tests can show they catch it.  Only the host mirror's mutant builds define it; libvtx.so never does.
 #ifndef VTXF_MUTANT
 #define VTXF_MUTANT 0
 #endif
-constexpr int NW = VTXF_NW;     // 64-bit words of a diagonal's match mask (3: rounds 3 - 5; the A/B build of tools/gpu_campaign.sh)
-static_assert(NW == 3 || NW == 4, "rows, columns and piece ends are bytes: 256 bases at most");
+constexpr int NW = 4;           // 64-bit words of a diagonal's match mask (rounds 3 - 5 had three; band_diag_kernel is also instantiated for three, picked per batch.
+                                // The compile-time switch -DVTXF_NW=3 and its build libvtx_nw3.so are gone, last in commit 5c0dd06)
+static_assert(64 * NW <= 256, "rows, columns and piece ends are bytes: 256 bases at most");
 constexpr int MAX_READ = 64 * NW;   // mask capacity
 constexpr int RM = 8;           // main-diagonal pieces
 #ifndef VTXF_S_WORDS
@@ -139,10 +137,7 @@ VTXF_HD uint32_t tab_tw_off(uint32_t max_hap, uint32_t n_heads) { return tab_pb_
 // bits 16-31: the (b1, b6) around S, bits 32-47: the (b6, b7) behind it.  band_diag_kernel's pooled probes test a block of three rows
 // with one 8-byte load per haplotype instead of one 4-byte load per row (the rows a task probes come in runs: the bases that hang over
 // the haplotype's window, the six rows around an error).  Like pb[], a filter: bytes outside ACGT alias, the walk compares the bytes.
-#ifndef VTXF_T3
-#define VTXF_T3 1          // (0: tables without t3[], a queue entry per row — the A/B build libvtx_not3.so of tools/gpu_campaign.sh variants)
-#endif
-constexpr uint32_t T3_BYTES = VTXF_T3 ? 2048 : 0;
+constexpr uint32_t T3_BYTES = 2048;   // (tables without t3[]: chosen per batch, band_use_t3.  The compile-time switch -DVTXF_T3=0 and its build libvtx_not3.so are gone, last in commit 5c0dd06)
 VTXF_HD uint32_t tab_t3_off(uint32_t max_hap, uint32_t n_heads) { return tab_tw_off(max_hap, n_heads) + TW_BYTES; }
 VTXF_HD uint32_t tab_stride(uint32_t max_hap, uint32_t n_heads) { return (tab_t3_off(max_hap, n_heads) + T3_BYTES + 15u) & ~15u; }
 // (a table in LDS — band_run_kernel without a global table buffer — ends behind pb[]: only band_diag_kernel reads tw[] and t3[])

@@ -567,8 +567,7 @@ __global__ __launch_bounds__(64) void band_sweep_kernel(
 }
 
 extern "C" uint32_t vtxk_band_sweep_grid(uint32_t n_tasks) {
-    static const uint32_t cap = VTX_DEV_ENV("VTX_SWEEP_GRID") ? (uint32_t)std::min(std::max(atoi(VTX_DEV_ENV("VTX_SWEEP_GRID")), 1), GRID_MAX) : (uint32_t)GRID_MAX;   // experiment knob (libvtx_dev.so)
-    return (uint32_t)std::min<uint64_t>(((uint64_t)n_tasks + 7) / 8, (uint64_t)cap);
+    return (uint32_t)std::min<uint64_t>(((uint64_t)n_tasks + 7) / 8, (uint64_t)GRID_MAX);
 }
 // the log slices of the largest grid (one buffer for the life of the context)
 extern "C" size_t vtxk_band_sweep_log_bytes(void) { return (size_t)GRID_MAX * 8 * LOGCAP * sizeof(uint32_t); }

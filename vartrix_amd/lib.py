@@ -19,6 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 #   dev    -DVTX_DEVTOOLS: the experiment / test hooks (stage switches, ablations, buffer caps, the socket transport standing in for
 #          RCCL) exist only there; the production libvtx.so reads VTX_DEBUG and nothing else
 #   lazy0, lazy40, anchor5, noseed0   one recollected detail of the crate's band switched (tests/test_gpu_variants.py)
+#   (the compile-time A/B builds nw3 and not3 are gone, last in commit 5c0dd06: mask words and t3[] are picked at run time)
 # VTX_LIB_VARIANT=<name> makes a variant the process default; load(variant) / Context(cfg, variant=...) pick one explicitly.
 DEFAULT_VARIANT = os.environ.get("VTX_LIB_VARIANT", "")
 
