@@ -53,6 +53,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <tuple>
 #include <type_traits>
 
 #include "vtx_device.h"
@@ -2312,6 +2313,30 @@ __device__ __forceinline__ void diag_route(int tid, uint32_t task, bool fail, ui
 // the batch has <= 255 bases, else uint32_t (20 entries).
 // A: mask words in use — 3 when no read of the batch exceeds 192 bases (the instruction count of rounds 3 - 5), else vtxf::NW = 4.
 // WG: threads of a workgroup, 64 or 256.  CLAIM: the wavefront loops over blocks of tasks it claims (DIAG_WG, DIAG_CLAIM below: what the launch uses).
+// Where argument I of a kernel void(Ts...) lies in its kernel-argument segment: the arguments in order, each at its natural alignment
+// (scalars and pointers, which is all band_diag_kernel takes) — and a load of it from there, for an argument that is read once, late.
+template <class F> struct KernSig;
+template <class... Ts> struct KernSig<void (*)(Ts...)> {
+    template <int I> using Arg = typename std::tuple_element<I, std::tuple<Ts...>>::type;
+    static constexpr uint32_t off(int idx) {
+        constexpr uint32_t sz[] = {(uint32_t)sizeof(Ts)...}, al[] = {(uint32_t)alignof(Ts)...};
+        uint32_t o = 0;
+        for (int i = 0; i <= idx; ++i) { o = (o + al[i] - 1u) & ~(al[i] - 1u); if (i < idx) o += sz[i]; }
+        return o;
+    }
+};
+// band_diag_kernel's late arguments by position (checked against the signature's types where they are read: diag_late)
+enum DiagArg { DA_fail_list = 14, DA_refine_rec = 15, DA_refine_cap = 16, DA_counters = 17, DA_tight_list = 19, DA_tight_pack = 20,
+               DA_dense_list = 22, DA_dense_mask = 23, DA_tail_rec = 25, DA_tail_cap = 26, DA_recheck_rec = 27, DA_recheck_cap = 28 };
+template <class Sig, int I, bool LATE, class T> __device__ __forceinline__ T diag_late(T arg) {
+    typedef typename Sig::template Arg<I> AT;
+    static_assert(sizeof(AT) == sizeof(T) && std::is_pointer<AT>::value == std::is_pointer<T>::value, "the argument at this position is of another kind");
+    if constexpr (!LATE) return arg;
+    else {
+        typedef const char __attribute__((address_space(4))) KA;
+        return *(T const __attribute__((address_space(4)))*)((KA*)__builtin_amdgcn_kernarg_segment_ptr() + Sig::off(I));
+    }
+}
 __device__ __forceinline__ int per_trip_v(int v) { asm volatile("" : "+v"(v)); return v; }
 __device__ __forceinline__ uint32_t per_trip_s(uint32_t v) { asm volatile("" : "+s"(v)); return v; }
 template <int WG, bool CLAIM, class ST, int A>
@@ -2394,7 +2419,13 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
     tb.gt = gtables; tb.ent = tb.head = tb.bytes = tb.uq = tb.pb = 0; tb.hmask = n_heads - 1;
     s_cnt[tid] = 0;
     o_read[tid] = 0;
-    const uint8_t* x = read_arena;
+    // Round 24: the read is (arena, offset) and every table access tb.gt + ONE 32-bit offset (vtx_fast_core.h, the loaders) — the
+    // arena and the table buffer stay in scalar registers, a lane's address is one VGPR.  Why no sum below wraps:
+    //   reads   an access starts at read_off + i, i < m: below read_off + read_len <= read_bytes <= 0xffffffff, checked by every submit
+    //           path (vtx_prep.hip) — also for a read that ends at the arena's last byte, so no access is kept in 64 bits for it
+    //   tables  tb.ent = the table's start <= gt_bytes - table_stride, gt_bytes <= 4 GiB - 64 KiB (vtxk_band_gtables_bytes); every
+    //           array offset + index stays below table_stride (vtxf::tab_stride is the end of the last array, t3[])
+    vtxf::ReadAt x{read_arena, 0u};
     int m = 0, n = 0;
     if (have) {
         const uint32_t rid = task >> 1, hap = task & 1;
@@ -2403,7 +2434,7 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
         const vtx_locus loc = loci[my_locus];
         m = (int)rec.read_len; n = (int)(hap ? loc.alt_len : loc.ref_len);
         o_read[tid] = rec.read_off;                                      // (also where this lane drops out: its partner may probe the read)
-        x = read_arena + rec.read_off;                                   // (... and takes half of the read's words from this lane, below)
+        x.off = rec.read_off;                                            // (... and takes half of the read's words from this lane, below)
         // one of the pair's two lanes gets as far as its table (the tests below, with the longer haplotype for n): BOTH load their
         // half of the read.  (A haplotype below six bases beside an ordinary one — a deletion at a padding of one or two bases: the
         // short one's lane drops out, and the other lane's read ended at base 8 HW when the halves were loaded by live lanes only.)
@@ -2442,10 +2473,11 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
 #pragma unroll
         for (int k = 0; k < HW / 2; ++k) {                             // words [HW half + 2k, + 2): bytes [8 HW half + 16 k, + 16)
             const int off = 8 * HW * half + 16 * k;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (load && off < m) __builtin_memcpy(&v, x + off, 16);    // (the arena is padded by 16 bytes)
-            mine[2 * k] = (uint64_t)v.x | ((uint64_t)v.y << 32);
-            mine[2 * k + 1] = (uint64_t)v.z | ((uint64_t)v.w << 32);
+            vtxf::W16 v{0ull, 0ull};
+            // (the arena is padded by 16 bytes.  32 bits: loaded only for off < m)
+            if (load && off < m) v = vtxf::ld16(read_arena, x.off + (uint32_t)off);
+            mine[2 * k] = v.a;
+            mine[2 * k + 1] = v.b;
         }
         pair_gather<HW>(mine, half, rw.w);
     }
@@ -2484,7 +2516,7 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
         if (live) {
             vtxf::TwinHead th{};
             if (twins) th = vtxf::twin_head(tb);
-            fr = vtxf::front_rest<LaneT, A>(x, m, tb, n, ln, d, M, twins);
+            fr = vtxf::front_rest<LaneT, A>(read_arena, m, tb, n, ln, d, M, twins);       // (it does not look at the read)
             if (fr.why != vtxf::W_OK) { live = false; fail = true; why = fr.why; }
             else if (VTX_ABLATE((stats >> 8) & 0xffu) != 10 && vtxf::whole_read(fr, m)) {      // (developer build, VTX_DIAG_ABLATE=10: the shortcut off — the A/B switch of include/vtx_band_semantics.h's fifth item; results stay right)
                 // the read matches base for base: full <= m = cert, and the reference's chain is a perfect diagonal whatever else
@@ -2567,7 +2599,7 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
                 const uint32_t e = i < n_walk ? q_walk[i] : 0xffffu;
                 go[u] = e != 0xffffu;
                 own[u] = go[u] ? e >> 8 : 0u; row[u] = go[u] ? e & 0xffu : 0u;       // (an idle slot reads lane 0's first bytes: inside the arena whatever its padding)
-                w8[u] = vtxf::ld8(read_arena + o_read[own[u]] + row[u]);
+                w8[u] = vtxf::ld8(read_arena, o_read[own[u]] + row[u]);        // (32 bits: row <= m - K of the owner's read)
                 tent[u] = o_tab[own[u]];
                 go[u] = go[u] && tent[u] != NO_TAB;
                 if (!go[u]) tent[u] = 0;
@@ -2578,19 +2610,19 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
                 const int ym = (int)row[u] + od[u];
                 chk[u] = go[u] && (tent[u] & 1u) && ym >= 0 && ym + vtxf::K <= (int)(dn >> 16);
                 tent[u] &= ~1u;
-                ym8[u] = vtxf::ld8(gtables + tent[u] + bytes_rel + (uint32_t)(chk[u] ? ym : 0));
+                ym8[u] = vtxf::ld8(gtables, tent[u] + bytes_rel + (uint32_t)(chk[u] ? ym : 0));      // (32 bits, here and below: table + array + index, 0 <= ym <= n - K)
             }
 #pragma unroll
             for (int u = 0; u < WPL; ++u) {
                 hh[u] = vtxf::kw_mix((uint32_t)w8[u], (uint32_t)(w8[u] >> 32) & 0xffffu);
-                raw[u] = vtxf::ld2(gtables + tent[u] + head_rel + 2u * vtxf::kw_bucket(hh[u], n_heads - 1));
+                raw[u] = vtxf::ld2(gtables, tent[u] + head_rel + 2u * vtxf::kw_bucket(hh[u], n_heads - 1));
             }
 #pragma unroll
             for (int u = 0; u < WPL; ++u) {
                 const uint32_t tag = raw[u] >> 12;
                 go[u] = go[u] && raw[u] != vtxf::HEAD_END && (tag == vtxf::HEAD_MULTI || tag == vtxf::kw_tag(hh[u]));   // (else: the bucket's only k-mer is another one)
                 if (chk[u] && ((ym8[u] ^ w8[u]) & 0xffffffffffffull) == 0) go[u] = false;
-                e0[u] = vtxf::ld8(gtables + tent[u] + 8u * (go[u] ? raw[u] & 0xfffu : 0u));
+                e0[u] = vtxf::ld8(gtables, tent[u] + 8u * (go[u] ? raw[u] & 0xfffu : 0u));
             }
 #pragma unroll
             for (int u = 0; u < WPL; ++u) {
@@ -2605,7 +2637,7 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
                     }
                     yc = (uint32_t)(e >> 48);
                     if (yc == vtxf::HEAD_END) break;
-                    e = vtxf::ld8(gtables + tent[u] + 8u * yc);
+                    e = vtxf::ld8(gtables, tent[u] + 8u * yc);
                 }
             }
         }
@@ -2668,7 +2700,7 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
                 on[u] = i < total;
                 ent2[u] = q_ent[on[u] ? i : 0];
                 const int s0 = (int)(ent2[u] & 0xffu) - 2;              // the block's first row (below 0: the read's first bytes, shifted)
-                const uint64_t raw8 = vtxf::ld8(read_arena + o_read[(ent2[u] >> 11) * 2u] + (uint32_t)max(s0, 0));
+                const uint64_t raw8 = vtxf::ld8(read_arena, o_read[(ent2[u] >> 11) * 2u] + (uint32_t)max(s0, 0));   // (32 bits: s0 <= m - K - 2)
                 w8[u] = s0 < 0 ? raw8 << (8 * -s0) : raw8;
             }
 #pragma unroll
@@ -2676,8 +2708,8 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
                 c16[u] = vtxf::kw_code8(w8[u]);
                 const uint32_t ta = o_tab[(ent2[u] >> 11) * 2u], tb_ = o_tab[(ent2[u] >> 11) * 2u + 1u];   // (NO_TAB: a lane without a table)
                 const uint32_t so = t3_rel + 8u * ((c16[u] >> 4) & 0xffu);
-                ea[u] = ta == NO_TAB ? 0ull : vtxf::ld8(gtables + (ta & ~1u) + so);
-                eb[u] = tb_ == NO_TAB ? 0ull : vtxf::ld8(gtables + (tb_ & ~1u) + so);
+                ea[u] = ta == NO_TAB ? 0ull : vtxf::ld8(gtables, (ta & ~1u) + so);      // (32 bits: table + t3[] + an entry of its 256)
+                eb[u] = tb_ == NO_TAB ? 0ull : vtxf::ld8(gtables, (tb_ & ~1u) + so);
             }
             uint32_t nh = 0, hits[EPL];                                 // hits: bits 0-2 rows of the block in the even lane's haplotype, 3-5 in the odd lane's
 #pragma unroll
@@ -2723,14 +2755,14 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
                 const uint32_t i = i0 + 64u * u + tid;
                 on[u] = i < total;
                 ent2[u] = q_ent[on[u] ? i : 0];
-                w8[u] = vtxf::ld8(read_arena + o_read[(ent2[u] >> 8) * 2u] + (ent2[u] & 0xffu));
+                w8[u] = vtxf::ld8(read_arena, o_read[(ent2[u] >> 8) * 2u] + (ent2[u] & 0xffu));     // (32 bits: a row <= m - K)
             }
 #pragma unroll
             for (int u = 0; u < EPL; ++u) {
                 code[u] = vtxf::kw_code((uint32_t)w8[u], (uint32_t)(w8[u] >> 32) & 0xffffu);
                 const uint32_t ta = o_tab[(ent2[u] >> 8) * 2u], tb_ = o_tab[(ent2[u] >> 8) * 2u + 1u];   // (NO_TAB: a lane without a table)
-                bits_a[u] = ta == NO_TAB ? 0u : *(const uint32_t*)(gtables + (ta & ~1u) + pb_rel + 4u * (code[u] >> 5));
-                bits_b[u] = tb_ == NO_TAB ? 0u : *(const uint32_t*)(gtables + (tb_ & ~1u) + pb_rel + 4u * (code[u] >> 5));
+                bits_a[u] = ta == NO_TAB ? 0u : vtxf::ld4(gtables, (ta & ~1u) + pb_rel + 4u * (code[u] >> 5));     // (32 bits: table + pb[] + a word of its 128)
+                bits_b[u] = tb_ == NO_TAB ? 0u : vtxf::ld4(gtables, (tb_ & ~1u) + pb_rel + 4u * (code[u] >> 5));
             }
             // the survivors (5 % of the probes) join the walk list: one LDS add per lane that has any, no ballots.  The list is
             // short (WALK_CAP entries — the LDS this kernel has left): a lane that does not fit marks what it reserved inside the
@@ -2775,6 +2807,17 @@ __global__ __launch_bounds__(WG, 4) void band_diag_kernel(
     wave_sync();
     PH(7);                                                              // the walks
     if (VTX_ABLATE((stats >> 8) & 0xffu) == 2) { if (live && s_cnt[tid] == 0x7fffffffu) counters->diag_dummy = 1; return; }   // (profiling aid) front + probes
+    // Round 24: the lists, their capacities and the counters are read from the kernel-argument segment HERE, behind the walks, where
+    // their first reader is — as kernel arguments they are live from the kernel's first instruction, 19 scalar registers through a
+    // body that keeps its wavefront masks in what is left and spills them to lanes (the three-word builds: EPL = 6 entries in flight
+    // in pass 1).  The four-word builds spill nothing and would only grow by the loads: they keep the arguments.  (The names below
+    // shadow the arguments of the same name; a test hook that reads one in front of this line reads the argument.)
+    typedef KernSig<decltype(&band_diag_kernel<WG, CLAIM, ST, A>)> Sig;
+    constexpr bool LATE = A <= 3;
+#define DIAG_LATE(name) const auto name##_arg = name; const auto name = diag_late<Sig, DA_##name, LATE>(name##_arg)
+    DIAG_LATE(fail_list); DIAG_LATE(refine_rec); DIAG_LATE(refine_cap); DIAG_LATE(counters); DIAG_LATE(tight_list); DIAG_LATE(tight_pack);
+    DIAG_LATE(dense_list); DIAG_LATE(dense_mask); DIAG_LATE(tail_rec); DIAG_LATE(tail_cap); DIAG_LATE(recheck_rec); DIAG_LATE(recheck_cap);
+#undef DIAG_LATE
     uint32_t aux = 0xffffffffu;
     bool tight = false;
     // ---- the last phase, every lane for itself: sort, harmless tests, closure, run bound (vtx_fast_core.h).  (Pooling the harmless

@@ -193,6 +193,28 @@ VTXF_HD uint32_t kw_tag(uint32_t h) { const uint32_t t = h >> 28; return t == HE
 
 VTXF_FN uint64_t ld8(const uint8_t* p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
 VTXF_FN uint32_t ld2(const uint8_t* p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
+// ---- loads at ONE 32-bit byte offset of a buffer (round 24): base + off (+ disp).  The tables and the read arena are addressed with
+//      32-bit offsets by the library's own rules (vtxk_band_gtables_bytes: a table buffer is at most 4 GiB - 64 KiB; vtx_submit: an
+//      arena at most 0xffffffff bytes), and their bases are kernel arguments.  A caller sums its offset in 32 bits FIRST — table +
+//      array + index — and says at the call why that sum cannot wrap; the device then loads with the base in scalar registers and the
+//      sum in one VGPR, where pointer + offset + offset, each addend widened on its own, is a chain of 64-bit adds on a VGPR pair.
+//      disp: a small constant displacement (the instruction's immediate field), added in 64 bits behind the widening, so it takes no
+//      part in the wrap argument.  On the host — the unit tests of this header — these are the plain pointer arithmetic.
+//      ld8 / ld2 / ld16: any alignment; ld4: a dword-aligned address; ld1: a byte. ----
+struct W16 { uint64_t a, b; };
+VTXF_FN uint64_t ld8(const uint8_t* base, uint32_t off, int disp = 0) { uint64_t v; __builtin_memcpy(&v, base + off + disp, 8); return v; }
+VTXF_FN uint32_t ld4(const uint8_t* base, uint32_t off, int disp = 0) { return *(const uint32_t*)(base + off + disp); }
+VTXF_FN uint32_t ld2(const uint8_t* base, uint32_t off, int disp = 0) { uint16_t v; __builtin_memcpy(&v, base + off + disp, 2); return v; }
+VTXF_FN uint32_t ld1(const uint8_t* base, uint32_t off, int disp = 0) { return (base + off + disp)[0]; }
+VTXF_FN W16 ld16(const uint8_t* base, uint32_t off, int disp = 0) { W16 v; __builtin_memcpy(&v, base + off + disp, 16); return v; }
+// A read as the functions below take it, X: a pointer to its first base (the host, and the kernels that hold one), or the arena and the
+// read's offset in it (band_diag_kernel) — byte i of the read is then byte off + i of the arena, one 32-bit sum.  It cannot wrap for
+// i < the read's length m: every submit path checks read_off + read_len <= read_bytes <= 0xffffffff (vtx_prep.hip), so off + i names a
+// byte of the arena itself.  Every load below STARTS at such an i — a row <= m - K, a word that holds a base of the read — and the
+// bytes it takes beyond base m (the arena's 16 bytes of padding, which may lie beyond 2^32 for the arena's last read) follow the start in the
+// 64-bit address: only the start is summed in 32 bits.
+struct ReadAt { const uint8_t* base; uint32_t off; };
+VTXF_FN uint64_t ld8(ReadAt x, uint32_t i, int disp = 0) { return ld8(x.base, x.off + i, disp); }
 VTXF_FN int imin(int a, int b) { return a < b ? a : b; }
 VTXF_FN int imax(int a, int b) { return a > b ? a : b; }
 VTXF_FN int iabs(int a) { return a < 0 ? -a : a; }
@@ -504,12 +526,12 @@ VTXF_FN ReadWords read_words(const uint8_t* x, int m) {
 // unit does not depend on its width — four loads per mask word instead of eight.  Words that do not overlap the haplotype are
 // masked, not skipped: their bytes lie inside the same table (the head words in front of bytes[], the flag bytes behind it),
 // readable and ignored.
-struct W16 { uint64_t a, b; };
-VTXF_FN W16 ld16(const uint8_t* p) { W16 v; __builtin_memcpy(&v, p, 16); return v; }
-template <int C> VTXF_FN uint64_t diag_mask_word(const ReadWords& rw, const uint8_t* x, const uint8_t* yb, int d, int wa, int wb) {
+// (yo: the offset of haplotype base d in the table buffer gt — diag_mask sums it once, the words' loads differ by constants)
+template <int C, class X> VTXF_FN uint64_t diag_mask_word(const ReadWords& rw, X x, const uint8_t* gt, uint32_t yo, int wa, int wb) {
     W16 h[4];
 VTXF_UNROLL
-    for (int k = 0; k < 4; ++k) h[k] = ld16(yb + (8 * (8 * C + 2 * k) + d));
+    for (int k = 0; k < 4; ++k) h[k] = ld16(gt, yo + 64u * C, 16 * k);      // (the word's own 32-bit sum: words 1 .. run under a branch, and the
+                                                                             //  scalar-base form needs base + offset in the block that loads)
     // The MISMATCH flags, assembled as two 32-bit halves with compile-time shifts and complemented once.  An 8-base word outside
     // [wa, wb) is not zeroed here: all of its bits lie outside [max(0, -d), min(m, n - d)) — 8 wa <= -d, 8 wb >= min(m, n - d) — and
     // diag_mask ANDs with exactly that range.  (The word test stays where it guards an ADDRESS: the read's bytes beyond RW words.)
@@ -517,24 +539,26 @@ VTXF_UNROLL
 VTXF_UNROLL
     for (int k = 0; k < 8; ++k) {
         const int w = 8 * C + k;
-        const uint64_t xw = w < RW ? rw.w[w < RW ? w : 0] : ld8(x + 8 * (w >= wa && w < wb ? w : 0));        // (compile-time choice: C is)
+        const uint64_t xw = w < RW ? rw.w[w < RW ? w : 0] : ld8(x, w >= wa && w < wb ? 8u * (uint32_t)w : 0u);        // (compile-time choice: C is)
         const uint32_t ne = ne8_raw(xw, (k & 1) ? h[k >> 1].b : h[k >> 1].a);
         const int s = 8 * (k & 3) - NE8_SH;                      // (a constant once the loop is unrolled)
         half[k >> 2] |= s < 0 ? ne >> (s < 0 ? -s : 0) : ne << (s < 0 ? 0 : s);
     }
     return ~((uint64_t)half[0] | ((uint64_t)half[1] << 32));
 }
-template <int A = NW> VTXF_FN M192 diag_mask(const ReadWords& rw, const uint8_t* x, int m, const Tab& tb, int n, int d) {
-    const uint8_t* yb = tb.gt + tb.bytes;
+template <int A = NW, class X> VTXF_FN M192 diag_mask(const ReadWords& rw, X x, int m, const Tab& tb, int n, int d) {
+    // 32 bits: bytes[] lies max_hap * 8 bytes or more behind the table's start and -d <= m - K <= 250, so tb.bytes + d names a byte of
+    // the table for a negative d too, and d <= n - K keeps it below the table's end (tab_stride: fb[], uq[], ... follow bytes[])
+    const uint32_t yo = tb.bytes + (uint32_t)d;
     // only the 8-base words that overlap the haplotype: the 8-byte loads stay within 7 bytes of bytes[0, n)
     const int wa = d < 0 ? (-d) >> 3 : 0;
     const int wb = imin((m + 7) >> 3, (n - d + 7) >> 3);
     if (wa >= wb) return m_zero();
     M192 M;
-    M.w[0] = diag_mask_word<0>(rw, x, yb, d, wa, wb);
-    M.w[1] = wb > 8 ? diag_mask_word<1>(rw, x, yb, d, wa, wb) : 0ull;
-    M.w[2] = wb > 16 ? diag_mask_word<2>(rw, x, yb, d, wa, wb) : 0ull;
-    if constexpr (NW > 3) M.w[NW - 1] = (A > 3 && wb > 24) ? diag_mask_word<NW - 1>(rw, x, yb, d, wa, wb) : 0ull;
+    M.w[0] = diag_mask_word<0>(rw, x, tb.gt, yo, wa, wb);
+    M.w[1] = wb > 8 ? diag_mask_word<1>(rw, x, tb.gt, yo, wa, wb) : 0ull;
+    M.w[2] = wb > 16 ? diag_mask_word<2>(rw, x, tb.gt, yo, wa, wb) : 0ull;
+    if constexpr (NW > 3) M.w[NW - 1] = (A > 3 && wb > 24) ? diag_mask_word<NW - 1>(rw, x, tb.gt, yo, wa, wb) : 0ull;
     return m_and(M, m_range<A>(imax(0, -d), imin(m, n - d)));
 }
 
@@ -545,10 +569,9 @@ template <class F> VTXF_FN void walk_bucket(const Tab& tb, uint64_t w8, uint32_t
     const uint32_t tag = raw >> 12;
     if (tag != HEAD_MULTI && tag != kw_tag(h)) return;     // the bucket's only k-mer is another one
     const uint32_t lo = (uint32_t)w8, hi = (uint32_t)(w8 >> 32) & 0xffffu;
-    const uint8_t* ent = tb.gt + tb.ent;
     uint32_t yc = raw & 0xfffu;
     do {
-        const uint64_t e = ld8(ent + 8u * yc);
+        const uint64_t e = ld8(tb.gt, tb.ent + 8u * yc);       // (32 bits: yc < max_hap, an entry of this table)
         if ((uint32_t)e == lo && ((uint32_t)(e >> 32) & 0xffffu) == hi) f(yc);
         yc = (uint32_t)(e >> 48);
     } while (yc != HEAD_END);
@@ -570,10 +593,10 @@ VTXF_FN int sample_row(int t, int m) {
 // the haplotype holds it exactly once.  (Until round 6 the bucket's entry was loaded and compared: one more dependent load per
 // round of the search.  A candidate is only ever a candidate — verify_diag looks at eight bases of its diagonal, the mask must hold
 // twenty matching ones — so a bucket whose k-mer merely shares the tag costs a wasted check, nothing else.)
-VTXF_FN int cand_diag(const uint8_t* x, int row, const Tab& tb) {
-    const uint64_t w8 = ld8(x + row);
+template <class X> VTXF_FN int cand_diag(X x, int row, const Tab& tb) {
+    const uint64_t w8 = ld8(x, (uint32_t)row);                 // (0 <= row <= m - K)
     const uint32_t hh = kw_mix((uint32_t)w8, (uint32_t)(w8 >> 32) & 0xffffu);
-    const uint32_t raw = ld2(tb.gt + tb.head + 2u * kw_bucket(hh, tb.hmask));
+    const uint32_t raw = ld2(tb.gt, tb.head + 2u * kw_bucket(hh, tb.hmask));      // (32 bits: a bucket of this table's head[n_heads])
     // (Measured and not kept: the first entry of a bucket with SEVERAL k-mers as a candidate too, checked on all eight bases — fewer second
     //  rounds of the search, headline 13.61 -> 13.55 ms, but in repeats it names diagonals a unit off: real sequence 152 -> 158 ms, the
     //  config-5 shape 32.0 -> 33.3.)
@@ -582,11 +605,12 @@ VTXF_FN int cand_diag(const uint8_t* x, int row, const Tab& tb) {
 }
 // cheap check of a candidate diagonal before its whole mask is computed: 8 bases in the middle of the overlap, at least 6 of
 // them equal (a chance k-mer match elsewhere in the haplotype passes with probability ~1e-3)
-VTXF_FN bool verify_diag(const uint8_t* x, int m, const Tab& tb, int n, int dc) {
+template <class X> VTXF_FN bool verify_diag(X x, int m, const Tab& tb, int n, int dc) {
     const int vlo = imax(0, -dc), vhi = imin(m, n - dc);
     if (vhi - vlo < 20) return false;                     // (the mask must hold >= 20 matching bases anyway)
     const int p = vlo + ((vhi - vlo - 8) >> 1);
-    return __builtin_popcount(ne8_raw(ld8(x + p), ld8(tb.gt + tb.bytes + (p + dc)))) <= 2;      // (at most two of the eight differ)
+    // (32 bits: vlo <= p <= vhi - 8, so p + 8 <= m and 0 <= p + dc <= n - 8 — inside the read and inside bytes[])
+    return __builtin_popcount(ne8_raw(ld8(x, (uint32_t)p), ld8(tb.gt, tb.bytes + (uint32_t)(p + dc)))) <= 2;      // (at most two of the eight differ)
 }
 template <class LN, int A = NW> VTXF_FN Front front_rest(const uint8_t* x, int m, const Tab& tb, int n, const LN& ln, int d, M192 M, bool tw = false);
 
@@ -685,12 +709,11 @@ template <class LN, int A> VTXF_FN Front front_rest(const uint8_t* x, int m, con
         const M192 I6 = m_and(P4, m_shr<4>(P2));            // bit i: bases i .. i + 5 all match
         // unique-k-mer bits of haplotype positions [d, d + MAX_READ): the array carries 32 * UQ_PAD_WORDS zero bits in front
         static_assert(32 * (int)UQ_PAD_WORDS >= MAX_READ, "d >= -(m - K)");
-        const uint32_t* uq = (const uint32_t*)(tb.gt + tb.uq);
         const uint32_t bo = (uint32_t)(d + 32 * (int)UQ_PAD_WORDS);
         const uint32_t wi = bo >> 5, sh = bo & 31u;
         uint32_t q[2 * NW + 1];
         VTXF_UNROLL
-        for (int k = 0; k < 2 * NW + 1; ++k) q[k] = (k < 2 * A + 1 && !tw) ? uq[wi + k] : 0u;
+        for (int k = 0; k < 2 * NW + 1; ++k) q[k] = (k < 2 * A + 1 && !tw) ? ld4(tb.gt, tb.uq + 4u * wi, 4 * k) : 0u;    // (32 bits: wi + k < tab_uq_words, inside the table)
         M192 U;
         VTXF_UNROLL
         for (int k = 0; k < NW; ++k) {
@@ -707,18 +730,16 @@ template <class LN, int A> VTXF_FN Front front_rest(const uint8_t* x, int m, con
 //      that front_rest(.., tw = true) did NOT put into fr.need — are (i, y') for the twins y' of haplotype position i + d.  Appended
 //      to ln[0 ..) in (x, y) order (the list's own); returns their number (entries beyond the lane's capacity are counted, not stored).
 //      Precondition: the list exists (tw[0] != TW_NONE). ----
-VTXF_FN bool tab_has_twins(const Tab& tb) { return tb.gt[tb.pb + 512u] != TW_NONE; }
+VTXF_FN bool tab_has_twins(const Tab& tb) { return ld1(tb.gt, tb.pb, 512) != TW_NONE; }
 // (the list's first 32 bytes — its length and twelve pairs: band_diag_kernel asks for them before front_rest, they arrive under it)
 struct TwinHead { W16 h0, h1; };
 VTXF_FN TwinHead twin_head(const Tab& tb) {
     TwinHead t;
-    const uint8_t* tw = tb.gt + tb.pb + 512u;
-    __builtin_memcpy(&t.h0, tw, 16);
-    __builtin_memcpy(&t.h1, tw + 16, 16);
+    t.h0 = ld16(tb.gt, tb.pb, 512);
+    t.h1 = ld16(tb.gt, tb.pb, 512 + 16);
     return t;
 }
 template <class LN> VTXF_FN int twin_matches(const Tab& tb, const Front& fr, int m, const LN& ln, const TwinHead& th) {
-    const uint8_t* tw = tb.gt + tb.pb + 512u;
     int ns = 0;
     auto four = [&](uint64_t w, int i0, int cnt) {                            // pairs i0 .. i0 + 3 of the list
 VTXF_UNROLL
@@ -736,7 +757,7 @@ VTXF_UNROLL
     four(th.h0.b, 0, cnt);
     four(th.h1.a, 4, cnt);
     four(th.h1.b, 8, cnt);
-    for (int i0 = 12; i0 < cnt; i0 += 4) four(ld8(tw + 8 + 2 * i0), i0, cnt);
+    for (int i0 = 12; i0 < cnt; i0 += 4) four(ld8(tb.gt, tb.pb + 2u * (uint32_t)i0, 512 + 8), i0, cnt);      // (32 bits: 8 + 2 i0 < TW_BYTES, inside tw[])
     return ns;
 }
 template <class LN> VTXF_FN int twin_matches(const Tab& tb, const Front& fr, int m, const LN& ln) { return twin_matches(tb, fr, m, ln, twin_head(tb)); }
