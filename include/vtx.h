@@ -644,13 +644,48 @@ int vtx_csr_geno_tally(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_
                        const uint32_t* d_alt, const uint32_t* d_ref,
                        const uint8_t* d_geno, uint32_t n_donors, const vtx_geno_tally* out);
 
+/* ---- doublet tally: a cell's reads by the dosage class of pairs of pooled donors (vartrix_amd/csrc/vtx_csr_geno_pair.hip) ---------------
+ * The two-donor hypotheses beside vtx_csr_geno_tally's one-donor ones.  A droplet that holds cells of the donors a and b in EQUAL parts
+ * shows an alt read at a variant with a probability that depends only on the dosage g_a + g_b in 0 .. 4; unequal mixtures are out of
+ * scope.  The CSR and d_geno[n_minor * n_donors] are exactly vtx_csr_geno_tally's.  d_pairs[2 * n_pairs], in device memory, holds the
+ * donors (a, b) of pair p at [2 p], [2 p + 1]; any list is allowed: duplicates, both orders, a == b.  For every (row r, pair p, class
+ * c), at element (r * n_pairs + p) * VTX_GENO_PAIR_CLASSES + c of each array of `out`:
+ *   sum_alt / sum_ref   the alt / ref counts summed over the entries of row r whose variant has class c under pair p: c = g_a + g_b when
+ *                       both donors have a call there, c = 5 when either byte is VTX_GENO_NONE
+ *   n_obs               how many of those entries have alt + ref > 0
+ * A pair (a, a) therefore carries donor a's one-donor tally on the classes 0, 2, 4, its missing class on 5 and zeros on 1 and 3.  The
+ * result is not a function of the one-donor tallies: it needs the joint class of each entry.  The arrays have n_major * n_pairs * 6
+ * elements; any pointer may be NULL and is then not written; every element of the others is written, zeros for rows without entries.
+ * The contract is vtx_csr_geno_tally's: a context but no run, synchronous on the context's stream, and three checks on the device BEFORE
+ * anything is written: the CSR, the table (every byte 0, 1, 2 or VTX_GENO_NONE), and the pairs (a < n_donors and b < n_donors).  A
+ * violation returns VTX_E_INVAL (the reason in vtx_strerror; for a pair it names the lowest offending pair index and its two donors),
+ * no output byte is written and the context stays usable.  VTX_E_INVAL also for n_donors == 0, n_pairs == 0, a null `out`, a null
+ * d_pairs and a null array that is needed (d_geno unless n_minor == 0); VTX_E_UNSUPPORTED for nnz >= 2^32, n_donors >
+ * vtx_csr_geno_max() and n_pairs > vtx_csr_geno_pair_max().  Outputs must not overlap inputs.  One GPU.
+ * One wavefront walks a row with up to 64 pairs on its lanes and keeps the eighteen numbers of a pair in registers; with more pairs it
+ * repeats the row once per 64, which vtx_csr_geno_pair_max() = 64 passes bounds.  No atomics, no zeroing pass, integer additions only:
+ * the result is a function of the input alone.  Work space: the checks' flag words only.                                              */
+#define VTX_GENO_PAIR_CLASSES 6u       /* dosage 0..4, and 5: either donor without a call */
+typedef struct vtx_geno_pair_tally {
+    uint64_t *sum_alt, *sum_ref;       /* n_major * n_pairs * 6 elements each */
+    uint32_t *n_obs;
+} vtx_geno_pair_tally;
+uint32_t vtx_csr_geno_pair_max(void);       /* the largest n_pairs accepted: 4096 (64 passes of a wavefront) */
+uint32_t vtx_sizeof_geno_pair_tally(void);  /* sizeof(vtx_geno_pair_tally) as the library was built: 24 (the table of vtx_abi_sizes is unchanged) */
+int vtx_csr_geno_pair_tally(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
+                            const uint64_t* d_indptr, const uint32_t* d_indices,
+                            const uint32_t* d_alt, const uint32_t* d_ref,
+                            const uint8_t* d_geno, uint32_t n_donors,
+                            const uint32_t* d_pairs, uint32_t n_pairs, const vtx_geno_pair_tally* out);
+
 /* Device time of the context's last CSR call that succeeded, in milliseconds, from events on the context's own stream.
  * vtx_device_csr / vtx_csr_transpose: ms[0] the check of the inputs, ms[1] the sort of the positions by column, ms[2] the offsets,
  * ms[3] the placement of the indices and payloads (vtx_device_csr: 1 and 3 are 0).  vtx_csr_row_stats: ms[0] the check, ms[3] the
  * reduction (1 and 2 are 0).  vtx_csr_select_plan / vtx_csr_select: ms[0] the check, ms[1] the scans, ms[2] the offsets and ids, ms[3]
  * the placement (the plan: 2 and 3 are 0).  vtx_csr_group_plan / vtx_csr_group_sum: ms[0] the checks of the CSR and of the labels,
  * ms[1] the count and its scan, ms[3] the fill (2 is 0; the plan: 3 is 0 too).  vtx_csr_geno_tally: ms[0] the checks of the CSR and
- * of the genotype table, ms[3] the tally (1 and 2 are 0).  Writes the first n of the four, at most four.                              */
+ * of the genotype table, ms[3] the tally (1 and 2 are 0).  vtx_csr_geno_pair_tally: ms[0] the checks of the CSR, the table and the
+ * pairs, ms[3] the tally (1 and 2 are 0).  Writes the first n of the four, at most four.                                              */
 int vtx_last_csr_ms(vtx_ctx* ctx, float* ms, uint32_t n);
 
 /* ---- Multi-GPU: one process (one ctx) per GPU, loci sharded over the ranks (src/main.rs:284-291: chunks of loci

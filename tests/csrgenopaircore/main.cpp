@@ -1,0 +1,96 @@
+// Host build of vartrix_amd/csrc/vtx_csr_geno_pair_core.h as a stand-alone program for tests/test_csr_geno_pair_core.py: what the lanes
+// TOUCH.
+//   csr_geno_pair_host IN OUT
+//   IN:  u32 n_cases, then per case { u32 n_major, n_minor, nnz, n_donors, n_pairs; (n_major + 1) x u64 indptr; nnz x u32 each of
+//        indices, alt, ref; n_minor * n_donors x u8 geno; 2 * n_pairs x u32 pairs }.
+//   OUT per case: u64 first_bad, u64 first_pair (all ones: every byte / pair is fine; otherwise the case ends here, as the call does);
+//        n_major * n_pairs * 6 x u64 each of sum_alt, sum_ref; as many x u32 n_obs.
+// Every array is an allocation of exactly the size the device gives it — the genotype table exactly n_minor * n_donors bytes, the
+// pairs exactly 2 * n_pairs words — filled with a pattern first: under the sanitizer build (`make csr_geno_pair_host_san`) a store or
+// load outside it, such as a dead lane's read past the pairs or the table, is an error, and an element the rules do not write keeps the
+// pattern and fails the comparison in the test.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "lanes.h"
+
+namespace {
+bool read_file(const char* path, std::vector<uint8_t>& out) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return false;
+    uint8_t buf[1 << 16];
+    size_t k;
+    while ((k = fread(buf, 1, sizeof buf, f)) > 0) out.insert(out.end(), buf, buf + k);
+    fclose(f);
+    return true;
+}
+
+// exactly `bytes` bytes (one when 0, so that the pointer is a real allocation), every byte 0xA5
+template <typename T> T* pattern(size_t count) {
+    const size_t bytes = count * sizeof(T);
+    T* p = (T*)malloc(bytes ? bytes : 1);
+    if (!p) { fprintf(stderr, "out of memory\n"); exit(2); }
+    memset(p, 0xA5, bytes ? bytes : 1);
+    return p;
+}
+
+template <typename T> T* take(const std::vector<uint8_t>& in, size_t& p, size_t count) {
+    if (p + count * sizeof(T) > in.size()) { fprintf(stderr, "truncated input\n"); exit(2); }
+    T* a = pattern<T>(count);
+    if (count) memcpy(a, in.data() + p, count * sizeof(T));
+    p += count * sizeof(T);
+    return a;
+}
+
+template <typename T> void put(FILE* f, const T* a, size_t count) {
+    if (fwrite(a, sizeof(T), count, f) != count) { fprintf(stderr, "cannot write the output\n"); exit(2); }
+}
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc != 3) { fprintf(stderr, "usage: csr_geno_pair_host IN OUT\n"); return 2; }
+    std::vector<uint8_t> in;
+    if (!read_file(argv[1], in) || in.size() < 4) { fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }
+    FILE* f = fopen(argv[2], "wb");
+    if (!f) { fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
+    uint32_t n_cases;
+    memcpy(&n_cases, in.data(), 4);
+    size_t p = 4;
+    for (uint32_t c = 0; c < n_cases; ++c) {
+        uint32_t* h = take<uint32_t>(in, p, 5);
+        const uint32_t n_major = h[0], n_minor = h[1], nnz = h[2], n_donors = h[3], n_pairs = h[4];
+        free(h);
+        uint64_t* indptr = take<uint64_t>(in, p, (size_t)n_major + 1);
+        uint32_t *indices = take<uint32_t>(in, p, nnz), *alt = take<uint32_t>(in, p, nnz), *ref = take<uint32_t>(in, p, nnz);
+        const uint64_t n_bytes = (uint64_t)n_minor * n_donors;
+        uint8_t* geno = take<uint8_t>(in, p, n_bytes);
+        uint32_t* pairs = take<uint32_t>(in, p, 2 * (size_t)n_pairs);
+        uint32_t bad = 0;                                                        // csr_check_kernel: a refused CSR never reaches the lanes below
+        for (uint64_t i = 0; i <= n_major; ++i) bad |= vtxr::indptr_bad(i, n_major, nnz, indptr[i], i < n_major ? indptr[i + 1] : 0ull);
+        for (uint64_t i = 0; i < nnz; ++i) bad |= vtxr::index_bad(indices[i], n_minor);
+        if (bad || !n_donors || n_donors > vtxr::GENO_MAX || !n_pairs || n_pairs > vtxr::PAIR_MAX) {
+            fprintf(stderr, "case %u: not an input the call takes (%u)\n", c, bad);
+            return 2;
+        }
+        uint64_t first_bad = csrgenopair::NO_BAD;                                // csr_geno_check_kernel
+        for (uint64_t i = 0; i < n_bytes; ++i)
+            if (vtxr::geno_bad(geno[i])) { first_bad = i; break; }
+        const uint64_t first_pair = csrgenopair::first_bad(pairs, n_pairs, n_donors);
+        put(f, &first_bad, 1);
+        put(f, &first_pair, 1);
+        if (first_bad == csrgenopair::NO_BAD && first_pair == csrgenopair::NO_BAD) {
+            const size_t n = (size_t)n_major * n_pairs * vtxr::PAIR_CLASSES;
+            uint64_t *sum_alt = pattern<uint64_t>(n), *sum_ref = pattern<uint64_t>(n);
+            uint32_t* n_obs = pattern<uint32_t>(n);
+            csrgenopair::tally(indptr, n_major, indices, alt, ref, geno, n_donors, pairs, n_pairs, csrgenopair::TallyOut{sum_alt, sum_ref, n_obs}, nullptr);
+            put(f, sum_alt, n); put(f, sum_ref, n); put(f, n_obs, n);
+            free(sum_alt); free(sum_ref); free(n_obs);
+        }
+        free(indptr); free(indices); free(alt); free(ref); free(geno); free(pairs);
+    }
+    if (fclose(f) != 0) { fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
+    return 0;
+}

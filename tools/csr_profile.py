@@ -32,7 +32,13 @@ GPU box:   python tools/csr_profile.py --group --json profiles/r14_csr_group.jso
 a random genotype table of 8 and of 64 donors, each result compared with a numpy model before it is timed, next to (a) vtx_csr_row_stats
 on the same CSR — the same bytes without the gather — and (b) torch on the device (rows by repeat_interleave, a gather of the genotype
 rows, three index_add_ into a dense buffer).
-GPU box:   python tools/csr_profile.py --geno --json profiles/r22_csr_geno.json"""
+GPU box:   python tools/csr_profile.py --geno --json profiles/r22_csr_geno.json
+
+--pairs measures the doublet tally (vtx_csr_geno_pair_tally) on --geno's CSR and table at 8 donors (all 28 pairs), 16 donors (all 120) and
+64 donors (a list of 64 pairs), each result compared with a numpy model before it is timed, next to (a) vtx_csr_geno_tally on the same CSR
+and table — the cost of a (entry, donor) slot against that of a (entry, pair) slot — and (b) torch on the device (rows by
+repeat_interleave, per pair two gathered genotype columns, the dosage, three index_add_ into a dense buffer of the output's size).
+GPU box:   python tools/csr_profile.py --pairs --json profiles/r25_csr_geno_pair.json"""
 import argparse
 import json
 import os
@@ -63,6 +69,7 @@ ap.add_argument("--ops", action="store_true", help="measure vtx_csr_row_stats / 
 ap.add_argument("--sweep", action="store_true", help="time csr_row_stats_kernel at every group size (developer library), no batch")
 ap.add_argument("--group", action="store_true", help="measure vtx_csr_group_plan / vtx_csr_group_sum on synthetic CSRs, no batch")
 ap.add_argument("--geno", action="store_true", help="measure vtx_csr_geno_tally on a synthetic cell-major CSR, no batch")
+ap.add_argument("--pairs", action="store_true", help="measure vtx_csr_geno_pair_tally on --geno's synthetic cell-major CSR, no batch")
 args = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -332,6 +339,114 @@ if args.geno:
             print(n_donors, "tally", E["geno_tally"]["device_ms_by_phase_median"], "wall", E["geno_tally"]["host_wall_ms_median"], "torch",
                   E["torch_gather_index_add_dense"].get("host_wall_ms_median", E["torch_gather_index_add_dense"].get("error")), flush=True)
             del out, table, cls
+    finish(res)
+    sys.exit(0)
+
+if args.pairs:
+    from concurrent.futures import ThreadPoolExecutor
+    from vartrix_amd import abi
+    C6 = abi.GENO_PAIR_CLASSES
+    n_major, n_minor, mean = args.barcodes, args.loci, 2392.3 * args.loci / 100_000
+    res = {"what": "vtx_csr_geno_pair_tally (tools/csr_profile.py --pairs): median of %d after one warm-up, one process; --geno's synthetic "
+                   "cell-major CSR (Poisson row lengths, uniform random columns) and random genotype table (classes 0 / 1 / 2 / missing at 35 / "
+                   "30 / 20 / 15 %%); device ms by phase from vtx_last_csr_ms" % args.runs, "geno_pair_max": lib.load().vtx_csr_geno_pair_max(),
+           "sizes": {}}
+    gen = torch.Generator(device=dev).manual_seed(11)
+    byte_of = torch.tensor([0, 1, 2, abi.VTX_GENO_NONE], dtype=torch.uint8, device=dev)
+    with lib.Context(default_config(n_barcodes=4)) as ctx:
+        lens = torch.poisson(torch.full((n_major,), mean, device=dev), generator=gen).clamp_(max=n_minor).to(torch.int64)
+        indptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(lens, 0)])
+        nnz = int(indptr[-1])
+        csr = {"indptr": indptr, "indices": torch.randint(0, n_minor, (nnz,), dtype=torch.int32, device=dev, generator=gen)}
+        for k in ("alt", "ref", "unk"):
+            csr[k] = torch.randint(0, 3, (nnz,), dtype=torch.int32, device=dev, generator=gen)
+        host = {k: v.cpu().numpy() for k, v in csr.items()}
+        rows_host = np.repeat(np.arange(n_major, dtype=np.int64), np.diff(host["indptr"]))
+        # the three numbers of an entry in one float64 weight: every (row, class) sum of each stays below 2^17, the whole below 2^53
+        assert int(np.diff(host["indptr"]).max()) * 2 < 1 << 17
+        packed = (host["alt"].astype(np.int64) + (host["ref"].astype(np.int64) << 17)
+                  + (((host["alt"] + host["ref"]) > 0).astype(np.int64) << 34)).astype(np.float64)
+        res.update({"n_major": n_major, "n_minor": n_minor, "nnz": nnz})
+        for n_donors, listed in ((8, None), (16, None), (64, 64)):
+            cls = torch.multinomial(torch.tensor([0.35, 0.3, 0.2, 0.15], device=dev), n_minor * n_donors, replacement=True, generator=gen)
+            table = byte_of[cls].reshape(n_minor, n_donors).contiguous()
+            if listed is None:
+                pairs_host = np.stack(np.triu_indices(n_donors, 1), axis=1).astype(np.int64)
+            else:
+                pairs_host = torch.randint(0, n_donors, (listed, 2), device=dev, generator=gen).cpu().numpy().astype(np.int64)
+            n_pairs = len(pairs_host)
+            pairs = torch.from_numpy(pairs_host.astype(np.int32).reshape(-1).copy()).to(dev)
+            n = n_major * n_pairs * C6
+            out = {"sum_alt": torch.empty(n, dtype=torch.int64, device=dev), "sum_ref": torch.empty(n, dtype=torch.int64, device=dev),
+                   "n_obs": torch.empty(n, dtype=torch.int32, device=dev)}
+            torch.cuda.synchronize(dev)
+
+            def pair_call():
+                return ctx.csr_geno_pair_tally(n_major, n_minor, nnz, csr["indptr"].data_ptr(), csr["indices"].data_ptr(), csr["alt"].data_ptr(),
+                                               csr["ref"].data_ptr(), table.data_ptr(), n_donors, pairs.data_ptr(), n_pairs,
+                                               {k: v.data_ptr() for k, v in out.items()})
+            pair_call()
+            # ---- correctness first: per pair, numpy's bincount over (row, class) with the packed counts as weights (exact) ----
+            got = {k: v.cpu().numpy().reshape(n_major, n_pairs, C6).astype(np.int64) for k, v in out.items()}
+            dosage = np.array([0, 1, 2, 50], np.int8)[cls.reshape(n_minor, n_donors).cpu().numpy()]
+            per_entry = [np.ascontiguousarray(dosage[:, d])[host["indices"]] for d in range(n_donors)]      # one gather per donor, shared by its pairs
+
+            def check_pair(p):
+                two = per_entry[pairs_host[p, 0]] + per_entry[pairs_host[p, 1]]
+                key = rows_host * C6 + np.where(two > 4, 5, two)
+                want = np.bincount(key, weights=packed, minlength=n_major * C6).astype(np.int64).reshape(n_major, C6)
+                for k, shift in (("sum_alt", 0), ("sum_ref", 17), ("n_obs", 34)):
+                    assert np.array_equal(got[k][:, p], (want >> shift) & 0x1FFFF), (n_donors, p, k)
+            with ThreadPoolExecutor(8) as pool:
+                list(pool.map(check_pair, range(n_pairs)))
+            del per_entry, dosage, got
+            print("%d donors, %d pairs: equals the numpy model" % (n_donors, n_pairs), flush=True)
+            E = {"n_pairs": n_pairs, "geno_pair_tally": series(pair_call, ctx.csr_ms)}
+            # (a) the one-donor tally on the same CSR and table: the cost of a (entry, donor) slot
+            n1 = n_major * n_donors * 4
+            out1 = {"sum_alt": torch.empty(n1, dtype=torch.int64, device=dev), "sum_ref": torch.empty(n1, dtype=torch.int64, device=dev),
+                    "n_obs": torch.empty(n1, dtype=torch.int32, device=dev)}
+            torch.cuda.synchronize(dev)
+
+            def tally_call():
+                return ctx.csr_geno_tally(n_major, n_minor, nnz, csr["indptr"].data_ptr(), csr["indices"].data_ptr(), csr["alt"].data_ptr(),
+                                          csr["ref"].data_ptr(), table.data_ptr(), n_donors, {k: v.data_ptr() for k, v in out1.items()})
+            E["geno_tally"] = series(tally_call, ctx.csr_ms)
+            del out1
+            pair_ms, one_ms = (E[k]["device_ms_by_phase_median"]["place"] for k in ("geno_pair_tally", "geno_tally"))
+            E["ns_per_entry_pair"] = round(pair_ms * 1e6 / (nnz * n_pairs), 5)
+            E["ns_per_entry_donor"] = round(one_ms * 1e6 / (nnz * n_donors), 5)
+
+            # (b) torch on the device: per pair two gathered genotype columns, the dosage, three index_add_ into the dense buffer
+            def torch_tally():
+                rows = torch.repeat_interleave(torch.arange(n_major, device=dev), csr["indptr"][1:] - csr["indptr"][:-1])
+                cols = csr["indices"].to(torch.int64)
+                a, r = csr["alt"].to(torch.int64), csr["ref"].to(torch.int64)
+                w = (a, r, ((a + r) > 0).to(torch.int64))
+                o = [torch.zeros(n, dtype=torch.int64, device=dev) for _ in w]
+                for p in range(n_pairs):
+                    ga, gb = (table[:, int(pairs_host[p, s])][cols].to(torch.int64) for s in (0, 1))
+                    c = torch.where((ga == abi.VTX_GENO_NONE) | (gb == abi.VTX_GENO_NONE), 5, ga + gb)
+                    key = (rows * n_pairs + p) * C6 + c
+                    for dst, src in zip(o, w):
+                        dst.index_add_(0, key, src)
+                torch.cuda.synchronize(dev)
+                return o
+            try:
+                dense = torch_tally()
+                for d, k in zip(dense, abi.GENO_TALLY_NAMES):
+                    assert torch.equal(d, out[k].to(torch.int64)), k
+                del dense
+                E["torch_gather_index_add_dense"] = series(torch_tally)
+                E["torch_over_call"] = round(E["torch_gather_index_add_dense"]["host_wall_ms_median"] / E["geno_pair_tally"]["host_wall_ms_median"], 2)
+            except Exception as e:                               # noqa: BLE001  (the record IS the error)
+                E["torch_gather_index_add_dense"] = {"error": "%s: %s" % (type(e).__name__, str(e).splitlines()[0][:200] if str(e) else "")}
+            res["sizes"]["%d_donors_%d_pairs" % (n_donors, n_pairs)] = E
+            print(n_donors, n_pairs, "pair tally", E["geno_pair_tally"]["device_ms_by_phase_median"], "wall", E["geno_pair_tally"]["host_wall_ms_median"],
+                  "donor tally", E["geno_tally"]["device_ms_by_phase_median"], "ns per (entry, pair)", E["ns_per_entry_pair"], "per (entry, donor)",
+                  E["ns_per_entry_donor"], "torch", E["torch_gather_index_add_dense"].get("host_wall_ms_median", E["torch_gather_index_add_dense"].get("error")),
+                  flush=True)
+            del out, table, cls, pairs
     finish(res)
     sys.exit(0)
 

@@ -142,6 +142,15 @@ class VtxGenoTally(C.Structure):
     _fields_ = [("sum_alt", C.POINTER(C.c_uint64)), ("sum_ref", C.POINTER(C.c_uint64)), ("n_obs", C.POINTER(C.c_uint32))]
 
 
+GENO_PAIR_CLASSES = 6               # VTX_GENO_PAIR_CLASSES: the dosage g_a + g_b of a pair of donors, 0 .. 4, and 5: either donor without a call
+
+
+class VtxGenoPairTally(C.Structure):
+    """vtx_geno_pair_tally: where vtx_csr_geno_pair_tally stores the eighteen numbers of every (row, pair); a NULL pointer is not
+    written.  The names are ``GENO_TALLY_NAMES``; the arrays have n_major * n_pairs * 6 elements."""
+    _fields_ = [("sum_alt", C.POINTER(C.c_uint64)), ("sum_ref", C.POINTER(C.c_uint64)), ("n_obs", C.POINTER(C.c_uint32))]
+
+
 class VtxCsrStats(C.Structure):
     """vtx_csr_stats: where vtx_csr_row_stats stores the seven statistics of every row; a NULL pointer is not written."""
     _fields_ = [(k, C.POINTER(C.c_uint32)) for k in CSR_STAT_COUNTS] + [(k, C.POINTER(C.c_uint64)) for k in CSR_STAT_SUMS]

@@ -20,6 +20,8 @@ of the run, and ``read_groups()`` reads the labels from a two-column file such a
 ``donor_tally()`` produces what the donor label is made from when samples are pooled: per (cell, donor) pair the cell's alt and ref reads
 by the class of the donor's known genotype at each variant (``vtx_csr_geno_tally`` on the device for a torch result, scipy on the host
 for a scipy one; ``read_genotypes()`` reads the table from a VCF), and ``assign_donors()`` is the plain likelihood on top, in numpy.
+``doublet_tally()`` is the same for droplets of two donors: per (cell, pair of donors) the reads by the dosage of the pair's genotypes
+(``vtx_csr_geno_pair_tally``), and ``assign_doublets()`` scores the two-donor hypotheses next to the one-donor ones (50 : 50 mixtures).
 
 There is no CPU path: the scores, the calls, the offsets and the transpose are computed on the GPU; torch carries the device arrays
 (``__cuda_array_interface__``) and, for ``to="scipy"``, copies the finished arrays to the host.
@@ -737,7 +739,8 @@ def assign_donors(tally_or_result, genotypes=None, *, error=0.01) -> DonorAssign
     donor with the highest ``ll``, the lowest index on a tie, and -1 for a cell whose ``n_obs`` over the classes 0 - 2 is zero for every
     donor; ``margin`` is the best minus the second best, ``+inf`` with one donor.  ``error`` must lie in (0, 0.5).
 
-    Out of scope: doublets, ambient RNA, and clustering without genotypes (souporcell's and vireo's other modes)."""
+    Out of scope: ambient RNA, and clustering without genotypes (souporcell's and vireo's other modes).  Droplets of two donors are
+    ``doublet_tally``'s and ``assign_doublets``'."""
     if not 0.0 < float(error) < 0.5:
         raise ValueError("assign_donors: error %r: a probability in (0, 0.5)" % (error,))
     tally = tally_or_result
@@ -761,3 +764,183 @@ def assign_donors(tally_or_result, genotypes=None, *, error=0.01) -> DonorAssign
     else:
         margin = np.full(n_cell, np.inf)
     return DonorAssignment(best=best, margin=margin, log_lik=ll, donors=list(tally.donors), barcodes=list(tally.barcodes))
+
+
+@dataclass
+class DoubletTally:
+    """Every cell's reads by the dosage class of pairs of donors: arrays of cells x pairs x 6, int64 (numpy, or torch tensors on the
+    result's device).  The last axis is the class of the pair (a, b) at the variant of an entry: the dosage ``g_a + g_b`` in 0 .. 4,
+    and 5 where either donor has no call."""
+    alt: object               # alt reads of the cell at the variants where the pair has that class
+    ref: object               # ref reads
+    n_obs: object             # entries of the cell with alt + ref > 0 at those variants
+    pairs: object             # int64, n_pairs x 2 (numpy): indices into ``donors``
+    donors: list
+    barcodes: list
+
+
+@dataclass
+class DoubletAssignment:
+    kind: object              # int8 per cell: 1 doublet, 0 singlet, -1 for a cell without a read at a genotyped variant
+    best: object              # int64 per cell: the singlet donor, ``assign_donors``' ``best``
+    best_pair: object         # int64 per cell: the pair (an index into ``pairs``) with the highest likelihood; -1 without pairs
+    log_odds: object          # float64 per cell: the best doublet hypothesis against the best singlet one, priors included
+    log_lik_pairs: object     # float64, cells x pairs
+    pairs: object
+    donors: list
+    barcodes: list
+
+
+def _pairs(pairs, n_donors):
+    """The list of pairs as an int64 array of n_pairs x 2: the caller's, or every a < b in ``np.triu_indices(n_donors, 1)`` order."""
+    raw = None if pairs is None else np.asarray(pairs.cpu() if _is_torch(pairs) else pairs)
+    if (raw is None and n_donors < 2) or (raw is not None and raw.size == 0):
+        return np.zeros((0, 2), np.int64)                     # no list: no library call either
+    most = int(lib.load().vtx_csr_geno_pair_max())
+    if raw is None:
+        if n_donors * (n_donors - 1) // 2 > most:
+            raise ValueError("doublet_tally: %d donors have %d pairs, more than the %d of one call: pass `pairs` (the candidates, such as the "
+                             "pairs of every cell's best few donors)" % (n_donors, n_donors * (n_donors - 1) // 2, most))
+        a, b = np.triu_indices(n_donors, 1)
+        return np.stack([a, b], axis=1).astype(np.int64)
+    if raw.ndim != 2 or raw.shape[1] != 2 or raw.dtype.kind not in "iu":
+        raise ValueError("doublet_tally: pairs of shape %s, dtype %s: integers, one row (a, b) per pair" % (raw.shape, raw.dtype))
+    out = np.ascontiguousarray(raw.astype(np.int64))
+    bad = np.flatnonzero(((out < 0) | (out >= n_donors)).any(axis=1))
+    if len(bad):
+        raise ValueError("doublet_tally: pair %d is (%d, %d): donors are 0 .. %d" % (bad[0], out[bad[0], 0], out[bad[0], 1], n_donors - 1))
+    if len(out) > most:
+        raise ValueError("doublet_tally: %d pairs: at most %d in one call" % (len(out), most))
+    return out
+
+
+def _geno_pair_tally(ctx, torch, dev, csr, n_major, n_minor, geno, n_donors, pairs):
+    """A CELL-major CSR with ``alt`` / ``ref`` arrays against the table and the pairs on the device (``vtx_csr_geno_pair_tally``) -> the
+    three arrays of ``abi.GENO_TALLY_NAMES`` as int64 tensors of n_major x n_pairs x 6."""
+    nnz, n_pairs = int(csr["indices"].shape[0]), len(pairs)
+    src = {k: csr[k].contiguous() for k in ("indptr", "indices", "alt", "ref")}
+    table = torch.from_numpy(np.ascontiguousarray(geno, np.uint8).reshape(-1).copy()).to(dev)
+    plist = torch.from_numpy(pairs.astype(np.int32).reshape(-1).copy()).to(dev)     # < n_donors <= vtx_csr_geno_max(): the bits of the uint32
+    n = n_major * n_pairs * abi.GENO_PAIR_CLASSES
+    raw = {"sum_alt": torch.empty(n, dtype=torch.int64, device=dev), "sum_ref": torch.empty(n, dtype=torch.int64, device=dev),
+           "n_obs": torch.empty(n, dtype=torch.int32, device=dev)}
+    torch.cuda.synchronize(dev)
+    ctx.csr_geno_pair_tally(n_major, n_minor, nnz, src["indptr"].data_ptr(), src["indices"].data_ptr(), src["alt"].data_ptr(), src["ref"].data_ptr(),
+                            table.data_ptr(), n_donors, plist.data_ptr(), n_pairs, {k: v.data_ptr() for k, v in raw.items()})
+    raw["n_obs"] = raw["n_obs"].to(torch.int64) & 0xFFFFFFFF
+    return {k: v.reshape(n_major, n_pairs, abi.GENO_PAIR_CLASSES) for k, v in raw.items()}
+
+
+def _doublet_tally_host(result, geno, pairs, orient):
+    """The tally of a scipy result on the host: per class ``A^T @ (cls == c)`` for a variant-major ``A``, ``A @ (cls == c)`` for a
+    cell-major one; ``cls`` the class of every (variant, pair), ``A`` the alt counts, the ref counts, and the indicator of alt + ref > 0."""
+    import scipy.sparse as sp
+    alt, ref = (sp.csr_matrix(m).astype(np.int64) for m in (result.alt_counts, result.ref_counts))
+    obs = sp.csr_matrix((alt + ref) > 0).astype(np.int64)
+    n_cell, n_pairs = len(result.barcodes), len(pairs)
+    ga, gb = geno[:, pairs[:, 0]].astype(np.int64), geno[:, pairs[:, 1]].astype(np.int64)
+    cls = np.where((ga == abi.VTX_GENO_NONE) | (gb == abi.VTX_GENO_NONE), abi.GENO_PAIR_CLASSES - 1, ga + gb)
+    out = {k: np.zeros((n_cell, n_pairs, abi.GENO_PAIR_CLASSES), np.int64) for k in ("sum_alt", "sum_ref", "n_obs")}
+    for c in range(abi.GENO_PAIR_CLASSES):
+        has = (cls == c).astype(np.int64)
+        for k, m in (("sum_alt", alt), ("sum_ref", ref), ("n_obs", obs)):
+            out[k][:, :, c] = np.asarray((m.T if orient == "variants" else m) @ has).reshape(n_cell, n_pairs)
+    return out
+
+
+def doublet_tally(result: Result, genotypes, pairs=None, donors=None, *, to=None) -> DoubletTally:
+    """Every cell's reads tallied against PAIRS of pooled donors: per (cell, pair) the alt reads, the ref reads and the informative
+    entries of the cell, by the dosage ``g_a + g_b`` (0 .. 4) of the pair's known genotypes at the entry's variant, and in class 5 where
+    either donor has no call — the integer part of scoring the two-donor hypotheses, and what ``assign_doublets`` takes beside a
+    ``DonorTally``.  The six classes assume the two cells of a droplet contribute reads in equal parts (50 : 50); other proportions
+    are out of scope, as are ambient RNA and clustering without genotypes.
+
+    ``genotypes``, ``donors``: as for ``donor_tally``.  ``pairs``: integers of n_pairs x 2, indices into the donors; any list is
+    allowed — duplicates, both orders, ``(a, a)``, which carries donor a's one-donor tally on the classes 0, 2, 4.  ``None`` means every
+    ``a < b`` in ``np.triu_indices(n_donors, 1)`` order; beyond ``vtx_csr_geno_pair_max()`` = 4 096 pairs (91 donors and more) that is a
+    ``ValueError``: pass the candidate pairs.
+
+    A torch result is tallied on its device — one ``vtx_csr_geno_pair_tally`` on a bare context for that device (one GPU, fewer than
+    2^32 entries), after one transpose of the alt and ref counts if the result is variant-major — into int64 tensors, or into numpy
+    arrays with ``to="scipy"``; a scipy result is tallied on the host with scipy into numpy arrays.  Zero donors or zero pairs give
+    empty arrays without a library call."""
+    n_var, n_cell = len(result.variants), len(result.barcodes)
+    orient = result.orient or ("cells" if tuple(result.shape) == (n_cell, n_var) != (n_var, n_cell) else "variants")
+    if to not in (None, "scipy", "torch"):
+        raise ValueError("to %r: scipy, torch, or None for the container of the result" % (to,))
+    geno, names = _genotypes(genotypes, donors, result.variants)
+    n_donors = geno.shape[1]
+    plist = _pairs(pairs, n_donors)
+    n_pairs = len(plist)
+    on_device = _is_torch(result.alt_counts)
+    if not on_device and to == "torch":
+        raise ValueError("doublet_tally: a scipy result is tallied on the host; to=\"torch\" needs a torch result (run(to=\"torch\"))")
+    if not on_device:
+        if n_pairs:
+            out = _doublet_tally_host(result, geno, plist, orient)
+        else:
+            out = {k: np.zeros((n_cell, 0, abi.GENO_PAIR_CLASSES), np.int64) for k in abi.GENO_TALLY_NAMES}
+    else:
+        import torch
+        first = result.alt_counts
+        dev = first.device
+        if first.values().shape[0] != result.ref_counts.values().shape[0]:
+            raise ValueError("doublet_tally: the count matrices do not have one sparsity")
+        if not n_pairs:                          # nothing to tally against, and the library takes no empty list
+            out = {k: torch.zeros((n_cell, 0, abi.GENO_PAIR_CLASSES), dtype=torch.int64, device=dev) for k in abi.GENO_TALLY_NAMES}
+        else:
+            csr = {"indptr": first.crow_indices(), "indices": first.col_indices().to(torch.int32), "alt": first.values().to(torch.int32),
+                   "ref": result.ref_counts.values().to(torch.int32)}
+            index = torch.cuda.current_device() if dev.index is None else dev.index
+            with lib.Context(abi.default_config(n_barcodes=max(n_cell, 1), device=index)) as ctx:    # no batch, no run: device, stream, work space
+                if orient == "variants":         # to cell-major: a wavefront tallies the row of a cell
+                    csr = _transpose(ctx, torch, dev, csr, n_var, n_cell, ("alt", "ref"))
+                out = _geno_pair_tally(ctx, torch, dev, csr, n_cell, n_var, geno, n_donors, plist)
+        if to == "scipy":
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+    return DoubletTally(alt=out["sum_alt"], ref=out["sum_ref"], n_obs=out["n_obs"], pairs=plist, donors=names, barcodes=list(result.barcodes))
+
+
+def assign_doublets(singlets: DonorTally, doublets: DoubletTally, *, error=0.01, doublet_prior=0.5) -> DoubletAssignment:
+    """Singlet or doublet, per cell, under the plain genotype model with the two cells of a doublet mixed 50 : 50: a read of a droplet
+    of the donors (a, b) shows the alt allele with probability ``q = (error, 0.25, 0.5, 0.75, 1 - error)`` at the dosage ``g_a + g_b``
+    = 0 .. 4.  Takes ``donor_tally``'s and ``doublet_tally``'s outputs for the same cells.  In numpy float64, from the integer tallies,
+    in exactly this order:
+
+        ll2 = alt[..., 0] * log(q[0]) + ref[..., 0] * log1p(-q[0]) + alt[..., 1] * log(q[1]) + ref[..., 1] * log1p(-q[1])
+              + alt[..., 2] * log(q[2]) + ref[..., 2] * log1p(-q[2]) + alt[..., 3] * log(q[3]) + ref[..., 3] * log1p(-q[3])
+              + alt[..., 4] * log(q[4]) + ref[..., 4] * log1p(-q[4])
+        ll1 = assign_donors(singlets, error=error).log_lik
+        log_odds = (max(ll2) + log(doublet_prior) - log(n_pairs)) - (max(ll1) + log1p(-doublet_prior) - log(n_donors))
+
+    so that the same tallies give the same bits wherever they were counted.  Class 5 (a donor without a call) contributes nothing.
+    ``kind`` is 1 (doublet) where ``log_odds > 0``, 0 (singlet) otherwise, and -1 where ``assign_donors`` gives -1; ``best`` is
+    ``assign_donors``' donor; ``best_pair`` the pair with the highest ``ll2``, the lowest index on a tie.  Without pairs ``best_pair``
+    is -1 and ``log_odds`` is -inf: no doublet hypothesis was scored.  ``error`` must lie in (0, 0.5), ``doublet_prior`` in (0, 1).
+
+    Out of scope: mixtures other than 50 : 50, ambient RNA, and clustering without genotypes."""
+    if not 0.0 < float(error) < 0.5:
+        raise ValueError("assign_doublets: error %r: a probability in (0, 0.5)" % (error,))
+    if not 0.0 < float(doublet_prior) < 1.0:
+        raise ValueError("assign_doublets: doublet_prior %r: a probability in (0, 1)" % (doublet_prior,))
+    if list(singlets.barcodes) != list(doublets.barcodes):
+        raise ValueError("assign_doublets: the two tallies are not of the same cells")
+    one = assign_donors(singlets, error=error)
+    alt, ref = (np.asarray(a.cpu() if _is_torch(a) else a).astype(np.float64) for a in (doublets.alt, doublets.ref))
+    q = (float(error), 0.25, 0.5, 0.75, 1.0 - float(error))
+    ll2 = (alt[..., 0] * np.log(q[0]) + ref[..., 0] * np.log1p(-q[0]) + alt[..., 1] * np.log(q[1]) + ref[..., 1] * np.log1p(-q[1])
+           + alt[..., 2] * np.log(q[2]) + ref[..., 2] * np.log1p(-q[2]) + alt[..., 3] * np.log(q[3]) + ref[..., 3] * np.log1p(-q[3])
+           + alt[..., 4] * np.log(q[4]) + ref[..., 4] * np.log1p(-q[4]))
+    n_cell, n_pairs = ll2.shape
+    n_donors = one.log_lik.shape[1]
+    if n_pairs and n_donors:
+        best_pair = np.argmax(ll2, axis=1).astype(np.int64)
+        log_odds = ((np.max(ll2, axis=1) + np.log(float(doublet_prior)) - np.log(float(n_pairs)))
+                    - (np.max(one.log_lik, axis=1) + np.log1p(-float(doublet_prior)) - np.log(float(n_donors))))
+    else:
+        best_pair = np.argmax(ll2, axis=1).astype(np.int64) if n_pairs else np.full(n_cell, -1, np.int64)
+        log_odds = np.full(n_cell, np.inf if n_pairs else -np.inf)
+    kind = (log_odds > 0).astype(np.int8)
+    kind[one.best < 0] = -1
+    return DoubletAssignment(kind=kind, best=one.best, best_pair=best_pair, log_odds=log_odds, log_lik_pairs=ll2,
+                             pairs=np.asarray(doublets.pairs), donors=list(doublets.donors), barcodes=list(doublets.barcodes))

@@ -35,6 +35,7 @@
 #include "vtx_csr_ops_core.h"
 #include "vtx_csr_group_core.h"
 #include "vtx_csr_geno_core.h"
+#include "vtx_csr_geno_pair_core.h"
 #include "../../include/vtx_band_semantics.h"
 
 extern "C" hipError_t vtxk_inclusive_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, void* temp,
@@ -166,6 +167,7 @@ struct vtx_ctx {
     DevBuf d_sel_pos, d_sel_major, d_sel_minor, d_sel_tmp;   // vtx_csr_select_plan / vtx_csr_select: pos[nnz + 1], major_map[n_major + 1], minor_map[n_minor + 1], the scan's work space
     DevBuf d_grp_flag, d_grp_pos, d_grp_tmp;   // vtx_csr_group_plan / vtx_csr_group_sum: the lowest column with a bad label, pos[n_major + 1], the scan's work space
     DevBuf d_geno_flag;                      // vtx_csr_geno_tally: the lowest flat index of a bad genotype byte (one 64-bit word)
+    DevBuf d_pair_flag;                      // vtx_csr_geno_pair_tally: the lowest index of a pair with a donor out of range (one 64-bit word)
     bool band_long_lists = false;      // (performance feedback between runs: see vtx_run)
     int read_format = VTX_READS_BYTES;     // vtx_set_read_format
     DevBuf d_read_packed;                  // VTX_READS_NIBBLES: the arena as uploaded, unpacked into d_read
@@ -730,6 +732,7 @@ int vtx_abi_sizes(uint32_t* out, uint32_t n) {
 
 uint32_t vtx_sizeof_csr_stats(void) { return (uint32_t)sizeof(vtx_csr_stats); }
 uint32_t vtx_sizeof_geno_tally(void) { return (uint32_t)sizeof(vtx_geno_tally); }
+uint32_t vtx_sizeof_geno_pair_tally(void) { return (uint32_t)sizeof(vtx_geno_pair_tally); }
 
 const char* vtx_status_name(int status) {
     switch (status) {
@@ -812,6 +815,7 @@ void vtx_destroy(vtx_ctx* c) {
     c->d_sel_pos.release(); c->d_sel_major.release(); c->d_sel_minor.release(); c->d_sel_tmp.release();
     c->d_grp_flag.release(); c->d_grp_pos.release(); c->d_grp_tmp.release();
     c->d_geno_flag.release();
+    c->d_pair_flag.release();
     DevBuf* ib[] = {&c->d_bam_comp, &c->d_bam_data, &c->d_bam_blocks, &c->d_bam_seeds, &c->d_bam_seed_cnt, &c->d_bam_seed_scan, &c->d_bam_iv, &c->d_bam_cnt,
                     &c->d_bam_rec, &c->d_bam_nhit, &c->d_bam_rsz, &c->d_bam_tsz, &c->d_bam_hscan, &c->d_bam_rscan, &c->d_bam_tscan, &c->d_bam_info, &c->d_bam_segs};
     for (DevBuf* b : ib) b->release();
@@ -3120,6 +3124,62 @@ int vtx_csr_geno_tally(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t 
     HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = csr_times(c, true, false, true, false)) return rc;      // the two checks and the tally: no sort, no offsets here
+    return VTX_OK;
+}
+
+// ---- doublet tally: the same CSR and table against a list of donor pairs (include/vtx.h, vtx_csr_geno_pair.hip) ----
+uint32_t vtx_csr_geno_pair_max(void) { return vtxr::PAIR_MAX; }
+static_assert(VTX_GENO_PAIR_CLASSES == vtxr::PAIR_CLASSES, "the header's and the kernels' classes of a pair");
+static_assert(sizeof(vtx_geno_pair_tally) == 24, "three pointers");
+
+int vtx_csr_geno_pair_tally(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
+                            const uint32_t* d_alt, const uint32_t* d_ref, const uint8_t* d_geno, uint32_t n_donors, const uint32_t* d_pairs,
+                            uint32_t n_pairs, const vtx_geno_pair_tally* out) {
+    const char* who = "vtx_csr_geno_pair_tally";
+    if (!c) return VTX_E_INVAL;
+    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "%s: %llu entries: positions are 32-bit", who, (unsigned long long)nnz);
+    if (!n_donors) return fail(c, VTX_E_INVAL, "%s: no donors", who);
+    if (!n_pairs) return fail(c, VTX_E_INVAL, "%s: no pairs", who);
+    if (n_donors > vtxr::GENO_MAX)
+        return fail(c, VTX_E_UNSUPPORTED, "%s: %u donors: at most %u (%u passes of %u)", who, n_donors, vtxr::GENO_MAX, vtxr::GENO_MAX_PASSES, vtxr::GENO_WAVE);
+    if (n_pairs > vtxr::PAIR_MAX)
+        return fail(c, VTX_E_UNSUPPORTED, "%s: %u pairs: at most %u (%u passes of %u)", who, n_pairs, vtxr::PAIR_MAX, vtxr::PAIR_MAX_PASSES, vtxr::GENO_WAVE);
+    if (!out || !d_indptr || !d_pairs || (nnz && (!d_indices || !d_alt || !d_ref)) || (n_minor && !d_geno)) return fail(c, VTX_E_INVAL, "%s: null array", who);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    // the caller's arrays are read, and judged, before a single byte is written through `out`
+    if (int rc = csr_events(c)) return rc;
+    if (int rc = csr_flag_zero(c)) return rc;
+    HIP_TRY(c, c->d_geno_flag.reserve(sizeof(uint64_t)));
+    HIP_TRY(c, c->d_pair_flag.reserve(sizeof(uint64_t)));
+    HIP_TRY(c, hipMemsetAsync(c->d_geno_flag.p, 0xFF, sizeof(uint64_t), s));      // no byte yet
+    HIP_TRY(c, hipMemsetAsync(c->d_pair_flag.p, 0xFF, sizeof(uint64_t), s));      // no pair yet
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK0], s));
+    HIP_TRY(c, vtxr_check(d_indptr, n_major, nnz, d_indices, n_minor, c->d_csr_flag.as<uint32_t>(), s));
+    HIP_TRY(c, vtxr_geno_check(d_geno, (uint64_t)n_minor * n_donors, c->d_geno_flag.as<uint64_t>(), s));      // each check reads its own array only, whatever the others hold
+    HIP_TRY(c, vtxr_geno_pair_check(d_pairs, n_pairs, n_donors, c->d_pair_flag.as<uint64_t>(), s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK1], s));
+    uint32_t flag = 0;
+    uint64_t first_bad = 0, first_pair = 0;
+    HIP_TRY(c, hipMemcpyAsync(&first_bad, c->d_geno_flag.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&first_pair, c->d_pair_flag.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (int rc = csr_flag_read(c, &flag)) return rc;
+    if (flag) return fail(c, VTX_E_INVAL, "%s: %s", who, csr_bad_reason(flag));
+    if (first_bad != ~0ull)
+        return fail(c, VTX_E_INVAL, "%s: the genotype of variant %llu, donor %llu is neither 0, 1, 2 nor VTX_GENO_NONE", who,
+                    (unsigned long long)(first_bad / n_donors), (unsigned long long)(first_bad % n_donors));
+    if (first_pair != ~0ull) {      // < n_pairs: the check's lanes are the pairs
+        uint32_t ab[2] = {0, 0};
+        HIP_TRY(c, hipMemcpyAsync(ab, d_pairs + 2 * first_pair, sizeof(ab), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        return fail(c, VTX_E_INVAL, "%s: pair %llu is (%u, %u): a donor is not below n_donors = %u", who, (unsigned long long)first_pair, ab[0], ab[1], n_donors);
+    }
+    const vtx_geno_pair_in in{d_indptr, n_major, d_indices, d_alt, d_ref, d_geno, n_donors, d_pairs, n_pairs};
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, vtxr_geno_pair_tally(in, out, s));
+    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = csr_times(c, true, false, true, false)) return rc;      // the three checks and the tally: no sort, no offsets here
     return VTX_OK;
 }
 

@@ -43,6 +43,7 @@ SYMBOLS = (
     "vtx_csr_row_stats", "vtx_csr_select_plan", "vtx_csr_select", "vtx_sizeof_csr_stats",
     "vtx_csr_group_window", "vtx_csr_group_max", "vtx_csr_group_plan", "vtx_csr_group_sum",
     "vtx_csr_geno_max", "vtx_sizeof_geno_tally", "vtx_csr_geno_tally",
+    "vtx_csr_geno_pair_max", "vtx_sizeof_geno_pair_tally", "vtx_csr_geno_pair_tally",
 )
 # (entry points with a digit in their name: tests/test_abi.py finds the header's declarations with [a-z_]+ and compares them with SYMBOLS,
 # so these are listed — and checked against the header and every build of the library, tests/test_abi_f64.py — on their own)
@@ -120,6 +121,12 @@ def load(variant=None):
     L.vtx_sizeof_geno_tally.argtypes = []
     L.vtx_csr_geno_tally.restype = C.c_int
     L.vtx_csr_geno_tally.argtypes = csr_in + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(abi.VtxGenoTally)]
+    L.vtx_csr_geno_pair_max.restype = C.c_uint32
+    L.vtx_csr_geno_pair_max.argtypes = []
+    L.vtx_sizeof_geno_pair_tally.restype = C.c_uint32
+    L.vtx_sizeof_geno_pair_tally.argtypes = []
+    L.vtx_csr_geno_pair_tally.restype = C.c_int
+    L.vtx_csr_geno_pair_tally.argtypes = csr_in + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(abi.VtxGenoPairTally)]
     L.vtx_sizeof_csr_stats.restype = C.c_uint32
     L.vtx_sizeof_csr_stats.argtypes = []
     L.vtx_last_csr_ms.restype = C.c_int
@@ -496,6 +503,22 @@ class Context:
             setattr(st, k, C.cast(C.c_void_p(int(out.get(k) or 0) or None), typ))
         self._check(self._L.vtx_csr_geno_tally(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
                                                ref or None, geno or None, int(n_donors), C.byref(st)))
+
+    def csr_geno_pair_tally(self, n_major: int, n_minor: int, nnz: int, indptr: int, indices: int, alt: int, ref: int, geno: int, n_donors: int,
+                            pairs: int, n_pairs: int, out: dict):
+        """Every row of a CSR in device memory (rows = cells, indices = variants) tallied against ``n_pairs`` pairs of donors
+        (vtx_csr_geno_pair_tally).  ``geno``: as for ``csr_geno_tally``.  ``pairs``: the address of 2 * n_pairs uint32 in device memory,
+        the donors (a, b) of pair p at [2 p], [2 p + 1], both below ``n_donors``.  ``out``: name (``abi.GENO_TALLY_NAMES``) -> address of
+        n_major * n_pairs * 6 uint64 (``sum_alt``, ``sum_ref``) / uint32 (``n_obs``), by the dosage g_a + g_b (5: either donor without a
+        call); a name that is missing or 0 is not written."""
+        unknown = set(out) - set(abi.GENO_TALLY_NAMES)
+        if unknown:
+            raise ValueError("csr_geno_pair_tally: unknown outputs %s" % sorted(unknown))
+        st = abi.VtxGenoPairTally()
+        for k, typ in st._fields_:
+            setattr(st, k, C.cast(C.c_void_p(int(out.get(k) or 0) or None), typ))
+        self._check(self._L.vtx_csr_geno_pair_tally(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
+                                                    ref or None, geno or None, int(n_donors), pairs or None, int(n_pairs), C.byref(st)))
 
     def comm_init(self, ident: bytes, rank: int, world: int):
         """Join the RCCL communicator of the sharded run (collective; vtx_comm_init)."""
