@@ -140,6 +140,66 @@ def test_authored_indel_bam_end_to_end(tmp_path, mode, umi, aligner, prep):
     assert len(coo["row"]) > 50
 
 
+def assert_cli_equals_refpipe(tmp_path, bam, aligner, prep, padding=None):
+    """One run of the command line in coverage mode with --umi against the oracle pipeline: both .mtx byte for byte, the nine counters
+    of the log line for line -> the packed batch of the restatement."""
+    vcfp, fap, bcp = (os.path.join(G, n) for n in ("test_dna.vcf", "test_dna.fa", "dna_barcodes.tsv"))
+    out, ref = str(tmp_path / "out.mtx"), str(tmp_path / "ref.mtx")
+    args = ["-v", vcfp, "-b", bam, "-f", fap, "-c", bcp, "-o", out, "-s", "coverage", "--ref-matrix", ref, "--threads", "4",
+            "--aligner", aligner, "--log-level", "info", "--umi"] + PATHS[prep] + (["--padding", str(padding)] if padding else [])
+    r = run_cli(args, tmp_path)
+    assert ("ingest on the device" in r.stderr) == (prep == "ingest")
+    bcs = refpipe.load_barcodes(bcp)
+    vcf = refpipe.read_vcf(vcfp)
+    batch, wm = refpipe.pack(vcf, refpipe.read_fasta(fap), refpipe.read_bam(bam), bcs,
+                             refpipe.Args(use_umi=True, padding=padding or 100))
+    log = r.stdout + r.stderr
+    names = ["Number of alignments evaluated", "Number of alignments skipped due to low mapping quality",
+             "Number of alignments skipped due to not being primary", "Number of alignments skipped due to being duplicates",
+             "Number of alignments skipped due to not being associated with a cell barcode",
+             "Number of alignments skipped due to not intersecting variant", "Number of alignments skipped due to not having a UMI",
+             "Number of VCF records skipped due to having invalid characters in the alternative haplotype",
+             "Number of VCF records skipped due to being multi-allelic"]
+    for name, key in zip(names, refpipe.METRIC_NAMES):
+        assert "%s: %d\n" % (name, wm[key]) in log, name
+    cfg = default_config(aligner=aligner, scoring_mode="coverage", use_umi=1, n_barcodes=len(bcs))
+    sr, sa = oracle.batch_scores(batch, cfg, threads=8)
+    coo = oracle.batch_reduce(batch, cfg, sr, sa)
+    assert open(out).read() == refpipe.mtx_text(len(vcf), len(bcs), coo["row"], coo["col"], coo["value"])
+    assert open(ref).read() == refpipe.mtx_text(len(vcf), len(bcs), coo["row"], coo["col"], coo["ref_value"])
+    assert len(coo["row"]) > 50
+    return batch
+
+
+@pytest.mark.parametrize("prep", ["host", "device", "ingest"])
+@pytest.mark.parametrize("aligner", ["banded", "full"])
+def test_long_read_bam_end_to_end(tmp_path, aligner, prep):
+    """Long reads (400 - 3 000 bases, insertions, deletions and soft clips in their CIGARs) over test_dna.vcf at the default padding:
+    the records above 1 024 bases take the exact slow path, the others the fast kernels, in one batch — through the host packer, the
+    device prep and the device ingest (nibble arena), both aligners, equal to the oracle pipeline."""
+    from tests.test_host import make_long_read_bam
+    bam = make_long_read_bam(tmp_path)
+    batch = assert_cli_equals_refpipe(tmp_path, bam, aligner, prep)
+    rl = batch.records["read_len"]
+    assert int((rl > 1024).sum()) >= 20 and int((rl <= 1024).sum()) >= 20          # slow and fast records survived the filters
+    assert int(rl.max()) > 2500 and int(batch.loci["ref_len"].max()) <= 2400
+
+
+@pytest.mark.parametrize("prep", ["host", "device", "ingest"])
+@pytest.mark.parametrize("aligner", ["banded", "full"])
+def test_wide_padding_end_to_end(tmp_path, aligner, prep):
+    """--padding 1300 over the authored indel BAM: every haplotype whose window fits the contig is above 2 400 bases (the last locus,
+    853 bases from the contig's end, keeps 2 154), so the records of the run — reads of 60 - 150 bases — are scored by the exact
+    slow path; equal to the oracle pipeline through all three preparation paths."""
+    from tests.test_host import make_dna_bam
+    bam = make_dna_bam(tmp_path, seed=3, n_reads=300)
+    batch = assert_cli_equals_refpipe(tmp_path, bam, aligner, prep, padding=1300)
+    hmin = np.minimum(batch.loci["ref_len"], batch.loci["alt_len"])
+    assert int((hmin > 2400).sum()) >= batch.n_loci - 1 and batch.n_records > 150
+    slow = np.repeat(np.maximum(batch.loci["ref_len"], batch.loci["alt_len"]) > 2400, batch.loci["rec_count"])
+    assert slow.mean() > 0.9
+
+
 @pytest.mark.parametrize("umi", [False, True])
 def test_reference_fixtures_with_device_prep(tmp_path, umi):
     """The reference's coverage fixtures (src/main.rs:1266-1339) with barcode lookup / UMI grouping / sort on the GPU."""

@@ -163,6 +163,101 @@ def make_dna_bam(tmp_path, seed=1, n_reads=600, block=20000, index="linear"):
     return bam
 
 
+def make_long_read_bam(tmp_path, seed=1, n_reads=120, block=20000):
+    """Author a coordinate-sorted BAM of LONG reads over test_dna.fa: 400 - 3 000 bases, half of them above the fast kernels' 1 024,
+    most over the dense loci of test_dna.vcf at 55 299 - 63 697 and some over the indel loci at 49 514 / 66 487 / 98 921.  A read
+    carries, at random, the ALT allele of every variant it spans — an SNV as a mismatch inside M, an insertion as I, a deletion as D —
+    plus 1 % substitutions and soft clips at either end.  Flags, MAPQs and the CB / UB tags as in make_dna_bam."""
+    from oracle import bamwriter
+    rng = np.random.default_rng(seed)
+    fa = refpipe.read_fasta(os.path.join(G, "test_dna.fa"))["1"].upper()
+    vcf = sorted(refpipe.read_vcf(os.path.join(G, "test_dna.vcf")), key=lambda v: v.pos)
+    bcs = list(refpipe.load_barcodes(os.path.join(G, "dna_barcodes.tsv")).keys())
+    acgt = b"ACGT"
+    recs = []
+    for k in range(n_reads):
+        span = int(rng.integers(1025, 2900)) if k % 2 else int(rng.integers(400, 1025))
+        anchor = int(rng.choice([49514, 66487, 66521, 98921, 98999])) if k % 5 == 0 else int(rng.integers(55299, 63698))
+        start = max(0, anchor - int(rng.integers(10, span - 10)))
+        end = start + span
+        seq, ops, cur = bytearray(), [], start
+
+        def add(op, n):
+            if n <= 0:
+                return
+            if ops and ops[-1][0] == op:
+                ops[-1][1] += n
+            else:
+                ops.append([op, n])
+
+        for v in vcf:
+            refa, alta = v.alleles[0].upper(), v.alleles[1].upper()
+            if v.pos < cur or v.pos + len(refa) >= end or rng.random() < 0.5:
+                continue
+            seq += fa[cur:v.pos]
+            add("M", v.pos - cur)
+            seq += alta                                    # (the first base of an indel allele is the anchor base: M)
+            add("M", 1)
+            if len(alta) > len(refa):
+                add("I", len(alta) - 1)
+            elif len(refa) > len(alta):
+                add("D", len(refa) - 1)
+            cur = v.pos + len(refa)
+        seq += fa[cur:end]
+        add("M", end - cur)
+        for e in np.nonzero(rng.random(len(seq)) < 0.01)[0]:
+            seq[e] = acgt[int(rng.integers(0, 4))]
+        if rng.random() < 0.4:
+            clip = int(rng.integers(5, 50))
+            seq = bytearray(rng.choice(list(acgt), clip).tolist()) + seq
+            ops.insert(0, ["S", clip])
+        if rng.random() < 0.4:
+            clip = int(rng.integers(5, 50))
+            seq += bytearray(rng.choice(list(acgt), clip).tolist())
+            ops.append(["S", clip])
+        cigar = "".join("%d%s" % (n, op) for op, n in ops)
+        flag = 0
+        u = rng.random()
+        if u < 0.04:
+            flag |= 0x400
+        elif u < 0.08:
+            flag |= 0x100
+        tags = []
+        if rng.random() < 0.95:
+            tags.append(("CB", "Z", bcs[int(rng.integers(0, 40))] if rng.random() < 0.92 else b"NOTLISTED-1"))
+        if rng.random() < 0.9:
+            tags.append(("UB", "Z", "UMI%02d" % int(rng.integers(0, 12))))
+        tags.append(("NM", "i", 0))
+        mapq = int(rng.choice([3, 30, 60, 255]))
+        recs.append((start, bamwriter.record(0, start, "long%04d" % k, bytes(seq).decode(), cigar, flag=flag, mapq=mapq, tags=tags)))
+    recs.sort(key=lambda t: t[0])
+    bam = str(tmp_path / "long.bam")
+    bamwriter.write_bam(bam, [("1", len(fa))], [r for _, r in recs], block=block, index="linear")
+    return bam
+
+
+def test_long_read_bam_is_what_it_says(tmp_path):
+    """make_long_read_bam: read lengths of 400 - 3 000 bases, CIGARs with I, D and S whose lengths add up to the read's, and records
+    above 1 024 bases that survive the packer's filters; C++ packer == Python restatement on it."""
+    bam = make_long_read_bam(tmp_path)
+    vcfp, fap, bcp = (os.path.join(G, n) for n in ("test_dna.vcf", "test_dna.fa", "dna_barcodes.tsv"))
+    recs = refpipe.read_bam(bam).recs
+    lens = np.array([len(r.seq) for r in recs])
+    assert len(recs) == 120 and lens.min() >= 400 and lens.max() <= 3000 and (lens > 1024).sum() >= 20
+    seen = set()
+    for r in recs:
+        ops = ["MIDNSHP=X"[int(c) & 15] for c in r.cigar]
+        seen.update(ops)
+        assert sum(int(c) >> 4 for c, op in zip(r.cigar, ops) if op in "MIS=X") == len(r.seq)
+    assert {"M", "I", "D", "S"} <= seen
+    for use_umi in (False, True):
+        want, wm = refpipe.pack(refpipe.read_vcf(vcfp), refpipe.read_fasta(fap), refpipe.read_bam(bam), refpipe.load_barcodes(bcp),
+                                refpipe.Args(use_umi=use_umi))
+        assert int((want.records["read_len"] > 1024).sum()) >= 20 and int(want.loci["ref_len"].max()) <= 2400
+        batch, metrics, nv, barcodes, variants = hostlib.pack_files(vcfp, bam, fap, bcp, threads=2, use_umi=use_umi)
+        assert metrics == wm and same_batch(batch, want)
+
+
 @pytest.mark.parametrize("window_blocks", [0, 1, 2])
 @pytest.mark.parametrize("kw", [dict(), dict(use_umi=True), dict(mapq=30), dict(primary_only=True, no_duplicates=True),
                                 dict(padding=20), dict(use_umi=True, padding=150)])
