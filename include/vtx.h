@@ -644,7 +644,7 @@ int vtx_csr_geno_tally(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_
                        const uint32_t* d_alt, const uint32_t* d_ref,
                        const uint8_t* d_geno, uint32_t n_donors, const vtx_geno_tally* out);
 
-/* ---- doublet tally: a cell's reads by the dosage class of pairs of pooled donors (vartrix_amd/csrc/vtx_csr_geno_pair.hip) ---------------
+/* ---- doublet tally: a cell's reads by the dosage class of pairs of pooled donors (vartrix_amd/csrc/vtx_csr_geno.hip) --------------------
  * The two-donor hypotheses beside vtx_csr_geno_tally's one-donor ones.  A droplet that holds cells of the donors a and b in EQUAL parts
  * shows an alt read at a variant with a probability that depends only on the dosage g_a + g_b in 0 .. 4; unequal mixtures are out of
  * scope.  The CSR and d_geno[n_minor * n_donors] are exactly vtx_csr_geno_tally's.  d_pairs[2 * n_pairs], in device memory, holds the

@@ -32,7 +32,7 @@ uint64_t csrgeno_first_bad(const uint8_t* geno, uint64_t n_bytes) { return csrge
 // vtx_csr_geno_tally; stores: n_major * n_donors * 4 zeroed bytes that count the lanes that store each element
 void csrgeno_tally(const uint64_t* indptr, uint32_t n_major, const uint32_t* indices, const uint32_t* alt, const uint32_t* ref,
                    const uint8_t* geno, uint32_t n_donors, uint64_t* sum_alt, uint64_t* sum_ref, uint32_t* n_obs, uint8_t* stores) {
-    csrgeno::tally(indptr, n_major, indices, alt, ref, geno, n_donors, csrgeno::TallyOut{sum_alt, sum_ref, n_obs}, stores);
+    csrgeno::tally<vtxr::DonorHyp>(csrgeno::TallyIn{indptr, n_major, indices, alt, ref, geno, n_donors, nullptr, 0}, csrgeno::TallyOut{sum_alt, sum_ref, n_obs}, stores);
 }
 
 }

@@ -75,7 +75,7 @@ int main(int argc, char** argv) {
             const size_t n = (size_t)n_major * n_donors * vtxr::GENO_CLASSES;
             uint64_t *sum_alt = pattern<uint64_t>(n), *sum_ref = pattern<uint64_t>(n);
             uint32_t* n_obs = pattern<uint32_t>(n);
-            csrgeno::tally(indptr, n_major, indices, alt, ref, geno, n_donors, csrgeno::TallyOut{sum_alt, sum_ref, n_obs}, nullptr);
+            csrgeno::tally<vtxr::DonorHyp>(csrgeno::TallyIn{indptr, n_major, indices, alt, ref, geno, n_donors, nullptr, 0}, csrgeno::TallyOut{sum_alt, sum_ref, n_obs}, nullptr);
             put(f, sum_alt, n); put(f, sum_ref, n); put(f, n_obs, n);
             free(sum_alt); free(sum_ref); free(n_obs);
         }

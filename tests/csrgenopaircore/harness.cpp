@@ -1,5 +1,5 @@
 // Host build of vartrix_amd/csrc/vtx_csr_geno_pair_core.h for tests/test_csr_geno_pair_core.py: the functions one lane of the doublet
-// tally kernels (vtx_csr_geno_pair.hip) runs alone, with the lanes as loops and the exchange between lanes as array reads (lanes.h).
+// tally kernels (vtx_csr_geno.hip) runs alone, with the lanes as loops and the exchange between lanes as array reads (lanes.h).
 // No device code, no sanitizer: a shared object ctypes loads.
 #include "lanes.h"
 
@@ -19,7 +19,7 @@ uint64_t csrgenopair_first_bad(const uint32_t* pairs, uint32_t n_pairs, uint32_t
 void csrgenopair_tally(const uint64_t* indptr, uint32_t n_major, const uint32_t* indices, const uint32_t* alt, const uint32_t* ref,
                        const uint8_t* geno, uint32_t n_donors, const uint32_t* pairs, uint32_t n_pairs, uint64_t* sum_alt, uint64_t* sum_ref,
                        uint32_t* n_obs, uint8_t* stores) {
-    csrgenopair::tally(indptr, n_major, indices, alt, ref, geno, n_donors, pairs, n_pairs, csrgenopair::TallyOut{sum_alt, sum_ref, n_obs}, stores);
+    csrgenopair::tally(csrgenopair::TallyIn{indptr, n_major, indices, alt, ref, geno, n_donors, pairs, n_pairs}, csrgenopair::TallyOut{sum_alt, sum_ref, n_obs}, stores);
 }
 
 }

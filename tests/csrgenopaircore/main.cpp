@@ -85,7 +85,7 @@ int main(int argc, char** argv) {
             const size_t n = (size_t)n_major * n_pairs * vtxr::PAIR_CLASSES;
             uint64_t *sum_alt = pattern<uint64_t>(n), *sum_ref = pattern<uint64_t>(n);
             uint32_t* n_obs = pattern<uint32_t>(n);
-            csrgenopair::tally(indptr, n_major, indices, alt, ref, geno, n_donors, pairs, n_pairs, csrgenopair::TallyOut{sum_alt, sum_ref, n_obs}, nullptr);
+            csrgenopair::tally(csrgenopair::TallyIn{indptr, n_major, indices, alt, ref, geno, n_donors, pairs, n_pairs}, csrgenopair::TallyOut{sum_alt, sum_ref, n_obs}, nullptr);
             put(f, sum_alt, n); put(f, sum_ref, n); put(f, n_obs, n);
             free(sum_alt); free(sum_ref); free(n_obs);
         }

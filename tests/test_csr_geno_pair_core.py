@@ -1,4 +1,4 @@
-"""vtx_csr_geno_pair_core.h on the CPU: what one lane of the doublet tally kernels (vartrix_amd/csrc/vtx_csr_geno_pair.hip) does alone —
+"""vtx_csr_geno_pair_core.h on the CPU: what one lane of the doublet tally kernel (vartrix_amd/csrc/vtx_csr_geno.hip) does alone —
 the check of a pair, the class of an entry under a pair, an entry's contribution by predicated additions, the fold over the sub-groups,
 the place of a number in the output — compiled for the host by tests/csrgenopaircore/Makefile with the lanes as loops and the exchange
 between lanes as array reads, against the numpy model of tests/csr_geno_pair_util.py.  The device runs the same source

@@ -11,8 +11,11 @@ import pytest
 import torch
 
 from tests.csr_geno_pair_util import CLASSES, NAMES, cases, model_pair_tally, random_pairs
-from tests.csr_geno_util import random_counts, random_table
+from tests.csr_geno_util import model_geno_tally, random_counts, random_table
+from tests.csr_group_util import model_group_sum
+from tests.csr_ops_util import model_stats
 from tests.test_gpu_csr_geno import tally as donor_tally
+from tests.test_gpu_csr_group import fold
 from tests.test_gpu_csr_ops import dev, filled, row_stats, untouched, words
 from tests.test_gpu_csr_transpose import random_csr
 from vartrix_amd import abi, lib
@@ -159,6 +162,55 @@ def test_refusals_write_nothing_and_leave_the_context_usable(ctx, CASES):
                                         len(pairs), None)      # no outputs
     assert rc == INVAL
     after()
+
+
+def test_the_csr_is_judged_first_then_the_table_then_the_pairs(ctx, CASES):
+    """One call with all three inputs bad names the CSR; with the CSR repaired, the genotype byte; with the table repaired, the pair.
+    Nothing is written each time (tally checks the outputs).  The pseudobulk calls judge the CSR before the labels in the same way."""
+    (name, indptr, indices, n_minor, counts, geno, n_donors, pairs), want = by_name(CASES, "same_donor_both_orders_and_repeats")
+    INVAL = abi.VTX_E_INVAL
+    order = indptr.copy()
+    order[3] = order[4] + np.uint64(1)
+    byte = geno.copy()
+    byte[7, 3] = 254
+    off = pairs.copy()
+    off[4] = (5, 0)
+    said = [tally(ctx, ptr, indices, n_minor, counts, gen, n_donors, off, expect=INVAL) for ptr, gen in ((order, byte), (indptr, byte), (indptr, geno))]
+    for msg, reason in zip(said, ("indptr decreases", "variant 7, donor 3", "pair 4 is (5, 0)")):
+        assert reason in msg and sum(r in msg for r in ("indptr", "variant", "pair 4")) == 1, msg
+    same(tally(ctx, indptr, indices, n_minor, counts, geno, n_donors, pairs), want)
+    three = (*counts, np.zeros(len(indices), np.uint32))
+    label = np.zeros(n_minor, np.uint32)
+    label[9] = 2                                           # two groups: neither a group nor VTX_GROUP_NONE
+    msg = fold(ctx, order, indices, n_minor, three, label, 2, n_alloc=8, expect=INVAL, plan_expect=INVAL)      # plan and sum
+    assert "indptr decreases" in msg and "label" not in msg, msg
+    assert "the label of column 9" in fold(ctx, indptr, indices, n_minor, three, label, 2, n_alloc=8, expect=INVAL, plan_expect=INVAL)
+
+
+def test_no_verdict_of_a_check_survives_its_call():
+    """Refused and accepted calls of the three kinds of check (pairs, genotype bytes, labels) interleaved on one context: a call that
+    follows a refusal is judged by its own input alone."""
+    name, indptr, indices, n_minor, counts, geno, n_donors, pairs = next(c for c in cases() if c[0] == "same_donor_both_orders_and_repeats")
+    INVAL = abi.VTX_E_INVAL
+    off = pairs.copy()
+    off[2] = (1, 0xFFFFFFFF)
+    byte = geno.copy()
+    byte[7, 3] = 254
+    three = (*counts, np.zeros(len(indices), np.uint32))
+    label = np.arange(n_minor, dtype=np.uint32) % 3
+    bad_label = label.copy()
+    bad_label[9] = 3
+    with lib.Context(default_config(n_barcodes=4)) as c:
+        assert "pair 2 is (1, 4294967295)" in tally(c, indptr, indices, n_minor, counts, geno, n_donors, off, expect=INVAL)
+        same(donor_tally(c, indptr, indices, n_minor, counts, geno, n_donors), model_geno_tally(indptr, indices, *counts, geno, n_donors))
+        assert "the label of column 9" in fold(c, indptr, indices, n_minor, three, bad_label, 3, n_alloc=8, expect=INVAL, plan_expect=INVAL)
+        same(tally(c, indptr, indices, n_minor, counts, geno, n_donors, pairs), model_pair_tally(indptr, indices, *counts, geno, n_donors, pairs))
+        assert "variant 7, donor 3" in donor_tally(c, indptr, indices, n_minor, counts, byte, n_donors, expect=INVAL)
+        want = model_group_sum(indptr, indices, *three, label, 3)
+        n_out, got = fold(c, indptr, indices, n_minor, three, label, 3)
+        assert n_out == len(want["indices"])
+        same(got, want, tuple(want))
+        same(row_stats(c, indptr, indices, n_minor, *three), model_stats(indptr, *three), tuple(model_stats(indptr, *three)))
 
 
 def test_phase_times_are_reported(ctx):

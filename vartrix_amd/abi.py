@@ -145,10 +145,9 @@ class VtxGenoTally(C.Structure):
 GENO_PAIR_CLASSES = 6               # VTX_GENO_PAIR_CLASSES: the dosage g_a + g_b of a pair of donors, 0 .. 4, and 5: either donor without a call
 
 
-class VtxGenoPairTally(C.Structure):
-    """vtx_geno_pair_tally: where vtx_csr_geno_pair_tally stores the eighteen numbers of every (row, pair); a NULL pointer is not
-    written.  The names are ``GENO_TALLY_NAMES``; the arrays have n_major * n_pairs * 6 elements."""
-    _fields_ = [("sum_alt", C.POINTER(C.c_uint64)), ("sum_ref", C.POINTER(C.c_uint64)), ("n_obs", C.POINTER(C.c_uint32))]
+# vtx_geno_pair_tally: where vtx_csr_geno_pair_tally stores the eighteen numbers of every (row, pair): vtx_geno_tally's three pointers,
+# to arrays of n_major * n_pairs * 6 elements
+VtxGenoPairTally = VtxGenoTally
 
 
 class VtxCsrStats(C.Structure):

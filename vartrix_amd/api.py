@@ -653,35 +653,71 @@ def _genotypes(genotypes, donors, variants):
     return geno, names
 
 
-def _geno_tally(ctx, torch, dev, csr, n_major, n_minor, geno, n_donors):
-    """A CELL-major CSR with ``alt`` / ``ref`` arrays against the table on the device (``vtx_csr_geno_tally``) -> the three arrays of
-    ``abi.GENO_TALLY_NAMES`` as int64 tensors of n_major x n_donors x 4."""
+def _class_tally(call, torch, dev, csr, n_major, n_minor, geno, n_donors, n_hyp, n_classes, pairs=None):
+    """A CELL-major CSR with ``alt`` / ``ref`` arrays against the table, and the ``pairs`` if any, on the device: ``call`` is
+    ``ctx.csr_geno_tally`` or ``ctx.csr_geno_pair_tally`` -> the three arrays of ``abi.GENO_TALLY_NAMES`` as int64 tensors of
+    n_major x n_hyp x n_classes."""
     nnz = int(csr["indices"].shape[0])
     src = {k: csr[k].contiguous() for k in ("indptr", "indices", "alt", "ref")}
     table = torch.from_numpy(np.ascontiguousarray(geno, np.uint8).reshape(-1).copy()).to(dev)
-    n = n_major * n_donors * 4
+    hyp = ()
+    if pairs is not None:
+        plist = torch.from_numpy(pairs.astype(np.int32).reshape(-1).copy()).to(dev)     # < n_donors <= vtx_csr_geno_max(): the bits of the uint32
+        hyp = (plist.data_ptr(), n_hyp)
+    n = n_major * n_hyp * n_classes
     raw = {"sum_alt": torch.empty(n, dtype=torch.int64, device=dev), "sum_ref": torch.empty(n, dtype=torch.int64, device=dev),
            "n_obs": torch.empty(n, dtype=torch.int32, device=dev)}
     torch.cuda.synchronize(dev)
-    ctx.csr_geno_tally(n_major, n_minor, nnz, src["indptr"].data_ptr(), src["indices"].data_ptr(), src["alt"].data_ptr(), src["ref"].data_ptr(),
-                       table.data_ptr(), n_donors, {k: v.data_ptr() for k, v in raw.items()})
+    call(n_major, n_minor, nnz, src["indptr"].data_ptr(), src["indices"].data_ptr(), src["alt"].data_ptr(), src["ref"].data_ptr(),
+         table.data_ptr(), n_donors, *hyp, {k: v.data_ptr() for k, v in raw.items()})
     raw["n_obs"] = raw["n_obs"].to(torch.int64) & 0xFFFFFFFF
-    return {k: v.reshape(n_major, n_donors, 4) for k, v in raw.items()}
+    return {k: v.reshape(n_major, n_hyp, n_classes) for k, v in raw.items()}
 
 
-def _donor_tally_host(result, geno, orient):
-    """The tally of a scipy result on the host: per class ``A^T @ (geno == g)`` for a variant-major ``A``, ``A @ (geno == g)`` for a
-    cell-major one; ``A`` the alt counts, the ref counts, and the indicator of alt + ref > 0."""
+def _geno_tally(ctx, torch, dev, csr, n_major, n_minor, geno, n_donors):
+    """``vtx_csr_geno_tally`` -> int64 tensors of n_major x n_donors x 4."""
+    return _class_tally(ctx.csr_geno_tally, torch, dev, csr, n_major, n_minor, geno, n_donors, n_donors, 4)
+
+
+def _class_tally_host(result, cls, n_classes, orient):
+    """The tally of a scipy result on the host from ``cls``, the class of every (variant, hypothesis): per class ``A^T @ (cls == c)``
+    for a variant-major ``A``, ``A @ (cls == c)`` for a cell-major one; ``A`` the alt counts, the ref counts, and the indicator of
+    alt + ref > 0.  -> the three arrays of ``abi.GENO_TALLY_NAMES``, int64, cells x hypotheses x n_classes."""
     import scipy.sparse as sp
     alt, ref = (sp.csr_matrix(m).astype(np.int64) for m in (result.alt_counts, result.ref_counts))
     obs = sp.csr_matrix((alt + ref) > 0).astype(np.int64)
-    n_cell, n_donors = len(result.barcodes), geno.shape[1]
-    out = {k: np.zeros((n_cell, n_donors, 4), np.int64) for k in ("alt", "ref", "n_obs")}
-    for g, byte in enumerate((0, 1, 2, abi.VTX_GENO_NONE)):
-        has = (geno == byte).astype(np.int64)
-        for k, m in (("alt", alt), ("ref", ref), ("n_obs", obs)):
-            out[k][:, :, g] = np.asarray((m.T if orient == "variants" else m) @ has).reshape(n_cell, n_donors)
+    n_cell, n_hyp = len(result.barcodes), cls.shape[1]
+    out = {k: np.zeros((n_cell, n_hyp, n_classes), np.int64) for k in abi.GENO_TALLY_NAMES}
+    for c in range(n_classes):
+        has = (cls == c).astype(np.int64)
+        for k, m in (("sum_alt", alt), ("sum_ref", ref), ("n_obs", obs)):
+            out[k][:, :, c] = np.asarray((m.T if orient == "variants" else m) @ has).reshape(n_cell, n_hyp)
     return out
+
+
+def _donor_tally_host(result, geno, orient):
+    """The class of (variant, donor) is the donor's genotype, 3 where it has no call."""
+    wide = geno.astype(np.int64)
+    return _class_tally_host(result, np.where(wide == abi.VTX_GENO_NONE, 3, wide), 4, orient)
+
+
+def _tally_head(result, genotypes, donors, to):
+    """What ``donor_tally`` and ``doublet_tally`` begin with -> (orient, n_var, n_cell, the table, the donor names)."""
+    n_var, n_cell = len(result.variants), len(result.barcodes)
+    orient = result.orient or ("cells" if tuple(result.shape) == (n_cell, n_var) != (n_var, n_cell) else "variants")
+    if to not in (None, "scipy", "torch"):
+        raise ValueError("to %r: scipy, torch, or None for the container of the result" % (to,))
+    geno, names = _genotypes(genotypes, donors, result.variants)
+    return orient, n_var, n_cell, geno, names
+
+
+def _tally_csr(who, result, torch):
+    """The alt and ref counts of a torch result as the CSR arrays the tallies take -> (csr, device)."""
+    first = result.alt_counts
+    if first.values().shape[0] != result.ref_counts.values().shape[0]:
+        raise ValueError("%s: the count matrices do not have one sparsity" % who)
+    return {"indptr": first.crow_indices(), "indices": first.col_indices().to(torch.int32), "alt": first.values().to(torch.int32),
+            "ref": result.ref_counts.values().to(torch.int32)}, first.device
 
 
 def donor_tally(result: Result, genotypes, donors=None, *, to=None) -> DonorTally:
@@ -696,24 +732,15 @@ def donor_tally(result: Result, genotypes, donors=None, *, to=None) -> DonorTall
     A torch result is tallied on its device — one ``vtx_csr_geno_tally`` on a bare context for that device (at most
     ``vtx_csr_geno_max()`` donors), after one transpose of the alt and ref counts if the result is variant-major — into int64
     tensors, or into numpy arrays with ``to="scipy"``; a scipy result is tallied on the host with scipy into numpy arrays."""
-    n_var, n_cell = len(result.variants), len(result.barcodes)
-    orient = result.orient or ("cells" if tuple(result.shape) == (n_cell, n_var) != (n_var, n_cell) else "variants")
-    if to not in (None, "scipy", "torch"):
-        raise ValueError("to %r: scipy, torch, or None for the container of the result" % (to,))
-    geno, names = _genotypes(genotypes, donors, result.variants)
+    orient, n_var, n_cell, geno, names = _tally_head(result, genotypes, donors, to)
     n_donors = geno.shape[1]
     if not _is_torch(result.alt_counts):
         if to == "torch":
             raise ValueError("donor_tally: a scipy result is tallied on the host; to=\"torch\" needs a torch result (run(to=\"torch\"))")
         out = _donor_tally_host(result, geno, orient)
-        return DonorTally(alt=out["alt"], ref=out["ref"], n_obs=out["n_obs"], donors=names, barcodes=list(result.barcodes))
+        return DonorTally(alt=out["sum_alt"], ref=out["sum_ref"], n_obs=out["n_obs"], donors=names, barcodes=list(result.barcodes))
     import torch
-    first = result.alt_counts
-    dev = first.device
-    if first.values().shape[0] != result.ref_counts.values().shape[0]:
-        raise ValueError("donor_tally: the count matrices do not have one sparsity")
-    csr = {"indptr": first.crow_indices(), "indices": first.col_indices().to(torch.int32), "alt": first.values().to(torch.int32),
-           "ref": result.ref_counts.values().to(torch.int32)}
+    csr, dev = _tally_csr("donor_tally", result, torch)
     if not n_donors:                             # nothing to tally against, and the library takes no table without donors
         out = {k: torch.zeros((n_cell, 0, 4), dtype=torch.int64, device=dev) for k in abi.GENO_TALLY_NAMES}
     else:
@@ -815,37 +842,15 @@ def _pairs(pairs, n_donors):
 
 
 def _geno_pair_tally(ctx, torch, dev, csr, n_major, n_minor, geno, n_donors, pairs):
-    """A CELL-major CSR with ``alt`` / ``ref`` arrays against the table and the pairs on the device (``vtx_csr_geno_pair_tally``) -> the
-    three arrays of ``abi.GENO_TALLY_NAMES`` as int64 tensors of n_major x n_pairs x 6."""
-    nnz, n_pairs = int(csr["indices"].shape[0]), len(pairs)
-    src = {k: csr[k].contiguous() for k in ("indptr", "indices", "alt", "ref")}
-    table = torch.from_numpy(np.ascontiguousarray(geno, np.uint8).reshape(-1).copy()).to(dev)
-    plist = torch.from_numpy(pairs.astype(np.int32).reshape(-1).copy()).to(dev)     # < n_donors <= vtx_csr_geno_max(): the bits of the uint32
-    n = n_major * n_pairs * abi.GENO_PAIR_CLASSES
-    raw = {"sum_alt": torch.empty(n, dtype=torch.int64, device=dev), "sum_ref": torch.empty(n, dtype=torch.int64, device=dev),
-           "n_obs": torch.empty(n, dtype=torch.int32, device=dev)}
-    torch.cuda.synchronize(dev)
-    ctx.csr_geno_pair_tally(n_major, n_minor, nnz, src["indptr"].data_ptr(), src["indices"].data_ptr(), src["alt"].data_ptr(), src["ref"].data_ptr(),
-                            table.data_ptr(), n_donors, plist.data_ptr(), n_pairs, {k: v.data_ptr() for k, v in raw.items()})
-    raw["n_obs"] = raw["n_obs"].to(torch.int64) & 0xFFFFFFFF
-    return {k: v.reshape(n_major, n_pairs, abi.GENO_PAIR_CLASSES) for k, v in raw.items()}
+    """``vtx_csr_geno_pair_tally`` -> int64 tensors of n_major x n_pairs x 6."""
+    return _class_tally(ctx.csr_geno_pair_tally, torch, dev, csr, n_major, n_minor, geno, n_donors, len(pairs), abi.GENO_PAIR_CLASSES, pairs)
 
 
 def _doublet_tally_host(result, geno, pairs, orient):
-    """The tally of a scipy result on the host: per class ``A^T @ (cls == c)`` for a variant-major ``A``, ``A @ (cls == c)`` for a
-    cell-major one; ``cls`` the class of every (variant, pair), ``A`` the alt counts, the ref counts, and the indicator of alt + ref > 0."""
-    import scipy.sparse as sp
-    alt, ref = (sp.csr_matrix(m).astype(np.int64) for m in (result.alt_counts, result.ref_counts))
-    obs = sp.csr_matrix((alt + ref) > 0).astype(np.int64)
-    n_cell, n_pairs = len(result.barcodes), len(pairs)
+    """The class of (variant, pair) is the dosage of the two donors, 5 where either has no call."""
     ga, gb = geno[:, pairs[:, 0]].astype(np.int64), geno[:, pairs[:, 1]].astype(np.int64)
     cls = np.where((ga == abi.VTX_GENO_NONE) | (gb == abi.VTX_GENO_NONE), abi.GENO_PAIR_CLASSES - 1, ga + gb)
-    out = {k: np.zeros((n_cell, n_pairs, abi.GENO_PAIR_CLASSES), np.int64) for k in ("sum_alt", "sum_ref", "n_obs")}
-    for c in range(abi.GENO_PAIR_CLASSES):
-        has = (cls == c).astype(np.int64)
-        for k, m in (("sum_alt", alt), ("sum_ref", ref), ("n_obs", obs)):
-            out[k][:, :, c] = np.asarray((m.T if orient == "variants" else m) @ has).reshape(n_cell, n_pairs)
-    return out
+    return _class_tally_host(result, cls, abi.GENO_PAIR_CLASSES, orient)
 
 
 def doublet_tally(result: Result, genotypes, pairs=None, donors=None, *, to=None) -> DoubletTally:
@@ -864,11 +869,7 @@ def doublet_tally(result: Result, genotypes, pairs=None, donors=None, *, to=None
     2^32 entries), after one transpose of the alt and ref counts if the result is variant-major — into int64 tensors, or into numpy
     arrays with ``to="scipy"``; a scipy result is tallied on the host with scipy into numpy arrays.  Zero donors or zero pairs give
     empty arrays without a library call."""
-    n_var, n_cell = len(result.variants), len(result.barcodes)
-    orient = result.orient or ("cells" if tuple(result.shape) == (n_cell, n_var) != (n_var, n_cell) else "variants")
-    if to not in (None, "scipy", "torch"):
-        raise ValueError("to %r: scipy, torch, or None for the container of the result" % (to,))
-    geno, names = _genotypes(genotypes, donors, result.variants)
+    orient, n_var, n_cell, geno, names = _tally_head(result, genotypes, donors, to)
     n_donors = geno.shape[1]
     plist = _pairs(pairs, n_donors)
     n_pairs = len(plist)
@@ -882,15 +883,10 @@ def doublet_tally(result: Result, genotypes, pairs=None, donors=None, *, to=None
             out = {k: np.zeros((n_cell, 0, abi.GENO_PAIR_CLASSES), np.int64) for k in abi.GENO_TALLY_NAMES}
     else:
         import torch
-        first = result.alt_counts
-        dev = first.device
-        if first.values().shape[0] != result.ref_counts.values().shape[0]:
-            raise ValueError("doublet_tally: the count matrices do not have one sparsity")
+        csr, dev = _tally_csr("doublet_tally", result, torch)
         if not n_pairs:                          # nothing to tally against, and the library takes no empty list
             out = {k: torch.zeros((n_cell, 0, abi.GENO_PAIR_CLASSES), dtype=torch.int64, device=dev) for k in abi.GENO_TALLY_NAMES}
         else:
-            csr = {"indptr": first.crow_indices(), "indices": first.col_indices().to(torch.int32), "alt": first.values().to(torch.int32),
-                   "ref": result.ref_counts.values().to(torch.int32)}
             index = torch.cuda.current_device() if dev.index is None else dev.index
             with lib.Context(abi.default_config(n_barcodes=max(n_cell, 1), device=index)) as ctx:    # no batch, no run: device, stream, work space
                 if orient == "variants":         # to cell-major: a wavefront tallies the row of a cell

@@ -133,6 +133,33 @@ struct HostArr {
     T* data() { return p; }
 };
 
+// ---- what the CSR calls keep in the context (vtx_device_csr, vtx_csr_*: "the matrices as CSR on the device" below) ----
+// Device times: events on the context's stream.  enum CsrEv names what lies between two of them.
+enum CsrEv { EV_CSR_CHECK0 = 0, EV_CSR_CHECK1, EV_CSR_SORT0, EV_CSR_SORT1, EV_CSR_OFFSETS1, EV_CSR_PLACE1, EV_CSR_COUNT };
+// The verdicts of a call's check kernels: one 64-bit word each in ONE buffer, set by one copy in front of the checks (kCsrVerdictInit)
+// and read by one copy behind them (csr_judged).  A word is the OR of bad bits (from zero) or the minimum over the offenders (from all ones).
+enum CsrVerdict {
+    V_CSR_BAD = 0,         // vtxr_check / vtxr_window_check: the OR of vtxr::Bad bits, in the low 32 bits
+    V_LABEL,               // vtxr_group_check: the lowest column with a bad label (a 32-bit atomicMin on the low 32 bits)
+    V_GENO,                // vtxr_geno_check: the lowest flat index of a bad genotype byte
+    V_PAIR,                // vtxr_geno_pair_check: the lowest pair with a donor out of range
+    V_COUNT
+};
+struct CsrWork {
+    hipEvent_t ev[EV_CSR_COUNT] = {};        // created on first use (csr_events)
+    float ms[4] = {};                        // vtx_last_csr_ms: check, sort, offsets, place
+    DevBuf d_verdict;                        // V_COUNT words
+    DevBuf d_indptr;                         // vtx_device_csr: the row offsets of d_o_row (a buffer of its own: no other call works in it)
+    DevBuf d_keys, d_iota, d_perm, d_tmp;    // vtx_csr_transpose: sorted columns, positions, perm (when the caller wants none), the sort's work space
+    DevBuf d_sel_pos, d_sel_major, d_sel_minor, d_sel_tmp;   // vtx_csr_select_plan / vtx_csr_select: pos[nnz + 1], major_map[n_major + 1], minor_map[n_minor + 1], the scan's work space
+    DevBuf d_grp_pos, d_grp_tmp;             // vtx_csr_group_plan / vtx_csr_group_sum: pos[n_major + 1], the scan's work space
+    template <typename T> T* verdict(CsrVerdict v) const { return (T*)(d_verdict.as<uint64_t>() + v); }
+    void release() {
+        for (DevBuf* b : {&d_verdict, &d_indptr, &d_keys, &d_iota, &d_perm, &d_tmp, &d_sel_pos, &d_sel_major, &d_sel_minor, &d_sel_tmp, &d_grp_pos, &d_grp_tmp}) b->release();
+    }
+    void destroy_events() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } }
+};
+
 struct vtx_ctx {
     vtx_config cfg{};
     hipStream_t stream = nullptr;
@@ -148,8 +175,7 @@ struct vtx_ctx {
     hipEvent_t ev[EV_COUNT] = {};
     hipEvent_t ev_crc[2] = {};               // around bgzf_crc32_kernel (vtx_submit_bam, vtx_debug_crc32)
     float crc_ms = 0;                        // vtx_last_crc_ms
-    hipEvent_t ev_csr[6] = {};               // vtx_device_csr / vtx_csr_transpose: around the check, the sort, the offsets, the placement (created on first use)
-    float csr_ms[4] = {};                    // vtx_last_csr_ms
+    CsrWork csr;                             // vtx_device_csr and the vtx_csr_* calls: events, phase times, verdict words, work space
     std::string err;
     bool submitted = false, ran = false;
     uint32_t n_loci = 0, n_records = 0, n_cell_groups = 0, n_umi_groups = 0, max_hap_len = 0;
@@ -162,12 +188,6 @@ struct vtx_ctx {
     int reduce_path = 0;                     // the last vtx_run's call reduction: 1 = histogram kernels (atomics), 2 = one pass per group
     DevBuf d_cell_cnt, d_umi_cnt, d_keep, d_keep_scan, d_scan_tmp;
     DevBuf d_o_row, d_o_col, d_o_alt, d_o_ref, d_o_unk, d_o_val, d_o_refval;
-    DevBuf d_csr_indptr;                     // vtx_device_csr: the row offsets of d_o_row (a buffer of its own: no other call works in it)
-    DevBuf d_csr_flag, d_csr_keys, d_csr_iota, d_csr_perm, d_csr_tmp;   // vtx_csr_transpose: flag word, sorted columns, positions, perm (when the caller wants none), the sort's work space
-    DevBuf d_sel_pos, d_sel_major, d_sel_minor, d_sel_tmp;   // vtx_csr_select_plan / vtx_csr_select: pos[nnz + 1], major_map[n_major + 1], minor_map[n_minor + 1], the scan's work space
-    DevBuf d_grp_flag, d_grp_pos, d_grp_tmp;   // vtx_csr_group_plan / vtx_csr_group_sum: the lowest column with a bad label, pos[n_major + 1], the scan's work space
-    DevBuf d_geno_flag;                      // vtx_csr_geno_tally: the lowest flat index of a bad genotype byte (one 64-bit word)
-    DevBuf d_pair_flag;                      // vtx_csr_geno_pair_tally: the lowest index of a pair with a donor out of range (one 64-bit word)
     bool band_long_lists = false;      // (performance feedback between runs: see vtx_run)
     int read_format = VTX_READS_BYTES;     // vtx_set_read_format
     DevBuf d_read_packed;                  // VTX_READS_NIBBLES: the arena as uploaded, unpacked into d_read
@@ -811,11 +831,7 @@ void vtx_destroy(vtx_ctx* c) {
                       &c->d_prep_cnt, &c->d_sort_tmp, &c->d_fail, &c->d_fail_tmp, &c->d_refine, &c->d_tail, &c->d_recheck, &c->d_tight, &c->d_tight_pack, &c->d_dband, &c->d_dband_pack, &c->d_dense, &c->d_stage, &c->d_sweep_log, &c->d_tight2, &c->d_tight2_pack, &c->d_recheck2, &c->d_recheck2_pack};
     for (DevBuf* b : bufs) b->release();
     c->d_slow_ws.release(); c->d_slow_retry.release(); c->d_read_packed.release();
-    c->d_csr_indptr.release(); c->d_csr_flag.release(); c->d_csr_keys.release(); c->d_csr_iota.release(); c->d_csr_perm.release(); c->d_csr_tmp.release();
-    c->d_sel_pos.release(); c->d_sel_major.release(); c->d_sel_minor.release(); c->d_sel_tmp.release();
-    c->d_grp_flag.release(); c->d_grp_pos.release(); c->d_grp_tmp.release();
-    c->d_geno_flag.release();
-    c->d_pair_flag.release();
+    c->csr.release();
     DevBuf* ib[] = {&c->d_bam_comp, &c->d_bam_data, &c->d_bam_blocks, &c->d_bam_seeds, &c->d_bam_seed_cnt, &c->d_bam_seed_scan, &c->d_bam_iv, &c->d_bam_cnt,
                     &c->d_bam_rec, &c->d_bam_nhit, &c->d_bam_rsz, &c->d_bam_tsz, &c->d_bam_hscan, &c->d_bam_rscan, &c->d_bam_tscan, &c->d_bam_info, &c->d_bam_segs};
     for (DevBuf* b : ib) b->release();
@@ -825,7 +841,7 @@ void vtx_destroy(vtx_ctx* c) {
     upload_release(c);
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : c->ev_crc) if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : c->ev_csr) if (ev) (void)hipEventDestroy(ev);
+    c->csr.destroy_events();
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -2782,30 +2798,16 @@ static const char* csr_bad_reason(uint32_t flag) {
     return "a triplet's row outside [row_begin, row_end)";
 }
 
-// the flag word of a check: zeroed on the stream in front of the check, read back behind it
-static int csr_flag_zero(vtx_ctx* c) {
-    HIP_TRY(c, c->d_csr_flag.reserve(sizeof(uint32_t)));
-    HIP_TRY(c, hipMemsetAsync(c->d_csr_flag.p, 0, sizeof(uint32_t), c->stream));
-    return VTX_OK;
-}
-static int csr_flag_read(vtx_ctx* c, uint32_t* flag) {
-    HIP_TRY(c, hipMemcpyAsync(flag, c->d_csr_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return VTX_OK;
-}
-
-// Device times of the CSR calls: events on the context's stream.  enum CsrEv names what lies between two of them.
-enum CsrEv { EV_CSR_CHECK0 = 0, EV_CSR_CHECK1 = 1, EV_CSR_SORT0 = 2, EV_CSR_SORT1 = 3, EV_CSR_OFFSETS1 = 4, EV_CSR_PLACE1 = 5 };
 static int csr_events(vtx_ctx* c) {
-    for (auto& ev : c->ev_csr) if (!ev) HIP_TRY(c, hipEventCreate(&ev));
+    for (auto& ev : c->csr.ev) if (!ev) HIP_TRY(c, hipEventCreate(&ev));
     return VTX_OK;
 }
 static int csr_times(vtx_ctx* c, bool checked, bool sorted, bool placed, bool offsets = true) {        // after the stream is synchronised
     const int pair[4][2] = {{EV_CSR_CHECK0, EV_CSR_CHECK1}, {EV_CSR_SORT0, EV_CSR_SORT1}, {EV_CSR_SORT1, EV_CSR_OFFSETS1}, {EV_CSR_OFFSETS1, EV_CSR_PLACE1}};
     const bool on[4] = {checked, sorted, offsets, placed};
     for (int i = 0; i < 4; ++i) {
-        c->csr_ms[i] = 0.f;
-        if (on[i]) HIP_TRY(c, hipEventElapsedTime(&c->csr_ms[i], c->ev_csr[pair[i][0]], c->ev_csr[pair[i][1]]));
+        c->csr.ms[i] = 0.f;
+        if (on[i]) HIP_TRY(c, hipEventElapsedTime(&c->csr.ms[i], c->csr.ev[pair[i][0]], c->csr.ev[pair[i][1]]));
     }
     return VTX_OK;
 }
@@ -2813,7 +2815,60 @@ static int csr_times(vtx_ctx* c, bool checked, bool sorted, bool placed, bool of
 int vtx_last_csr_ms(vtx_ctx* c, float* ms, uint32_t n) {
     if (!c) return VTX_E_INVAL;
     if (!ms) return fail(c, VTX_E_INVAL, "vtx_last_csr_ms: null output");
-    for (uint32_t i = 0; i < n && i < 4; ++i) ms[i] = c->csr_ms[i];
+    for (uint32_t i = 0; i < n && i < 4; ++i) ms[i] = c->csr.ms[i];
+    return VTX_OK;
+}
+
+// The preamble of every call that takes arrays from outside: they are read, and judged, before a single byte is written through them.
+// The verdict words are set on the stream, `launch(s)` issues the call's check kernels between the events of the check phase, and the
+// words come back to `verdict` with the stream synchronised.  Every call sets all the words: none survives into the next call.
+static const uint64_t kCsrVerdictInit[V_COUNT] = {0ull, ~0ull, ~0ull, ~0ull};      // (static: the copy is asynchronous)
+extern "C++" {      // (templates over the callables: this part of the file has C linkage)
+template <class Launch> static int csr_judged(vtx_ctx* c, uint64_t verdict[V_COUNT], Launch launch) {
+    hipStream_t s = c->stream;
+    if (int rc = csr_events(c)) return rc;
+    HIP_TRY(c, c->csr.d_verdict.reserve(sizeof kCsrVerdictInit));
+    HIP_TRY(c, hipMemcpyAsync(c->csr.d_verdict.p, kCsrVerdictInit, sizeof kCsrVerdictInit, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_CHECK0], s));
+    if (int rc = launch(s)) return rc;
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_CHECK1], s));
+    HIP_TRY(c, hipMemcpyAsync(verdict, c->csr.d_verdict.p, sizeof kCsrVerdictInit, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return VTX_OK;
+}
+
+// ... of a caller's CSR: vtxr_check and the call's own checks (`extra(s)`; each reads its own array only, whatever the others hold).  A
+// bad CSR is refused here, first; the caller judges the words of its own checks in `verdict` next.
+template <class Extra> static int csr_checked(vtx_ctx* c, const char* who, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr,
+                                              const uint32_t* d_indices, uint64_t verdict[V_COUNT], Extra extra) {
+    if (int rc = csr_judged(c, verdict, [&](hipStream_t s) -> int {
+            HIP_TRY(c, vtxr_check(d_indptr, n_major, nnz, d_indices, n_minor, c->csr.verdict<uint32_t>(V_CSR_BAD), s));
+            return extra(s);
+        })) return rc;
+    if (const uint32_t flag = (uint32_t)verdict[V_CSR_BAD]) return fail(c, VTX_E_INVAL, "%s: %s", who, csr_bad_reason(flag));
+    return VTX_OK;
+}
+}
+static int csr_checked(vtx_ctx* c, const char* who, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr,
+                       const uint32_t* d_indices) {
+    uint64_t verdict[V_COUNT];
+    return csr_checked(c, who, n_major, n_minor, nnz, d_indptr, d_indices, verdict, [](hipStream_t) { return (int)VTX_OK; });
+}
+
+// what the calls refuse on the host, before the device is touched
+static int csr_positions_fit(vtx_ctx* c, const char* who, uint64_t nnz) {
+    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "%s: %llu entries: positions are 32-bit", who, (unsigned long long)nnz);
+    return VTX_OK;
+}
+// the arrays that move with the entries; need_in / need_out: the input / output side has elements, so that its arrays must exist
+static int csr_payload_args(vtx_ctx* c, const char* who, const void* const* d_payload_in, void* const* d_payload_out, const uint32_t* payload_elem_bytes,
+                            uint32_t n_payload, bool need_in, bool need_out) {
+    if (n_payload && (!d_payload_in || !d_payload_out || !payload_elem_bytes)) return fail(c, VTX_E_INVAL, "%s: null payload list", who);
+    for (uint32_t a = 0; a < n_payload; ++a) {
+        if (payload_elem_bytes[a] != 4 && payload_elem_bytes[a] != 8)
+            return fail(c, VTX_E_INVAL, "%s: payload %u has elements of %u bytes (4 or 8)", who, a, payload_elem_bytes[a]);
+        if ((need_in && !d_payload_in[a]) || (need_out && !d_payload_out[a])) return fail(c, VTX_E_INVAL, "%s: payload %u is null", who, a);
+    }
     return VTX_OK;
 }
 
@@ -2829,21 +2884,20 @@ int vtx_device_csr(vtx_ctx* c, uint32_t row_begin, uint32_t row_end, vtx_csr* ou
     const uint32_t* d_row = c->d_o_row.as<uint32_t>();
     if (int rc = csr_events(c)) return rc;
     if (nnz) {
-        if (int rc = csr_flag_zero(c)) return rc;
-        HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK0], s));
-        HIP_TRY(c, vtxr_window_check(d_row, nnz, row_begin, row_end, c->d_csr_flag.as<uint32_t>(), s));
-        HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK1], s));
-        uint32_t flag = 0;
-        if (int rc = csr_flag_read(c, &flag)) return rc;
-        if (flag) return fail(c, VTX_E_INVAL, "vtx_device_csr: %s [%u, %u)", csr_bad_reason(flag), row_begin, row_end);
+        uint64_t verdict[V_COUNT];
+        if (int rc = csr_judged(c, verdict, [&](hipStream_t st) -> int {
+                HIP_TRY(c, vtxr_window_check(d_row, nnz, row_begin, row_end, c->csr.verdict<uint32_t>(V_CSR_BAD), st));
+                return VTX_OK;
+            })) return rc;
+        if (const uint32_t flag = (uint32_t)verdict[V_CSR_BAD]) return fail(c, VTX_E_INVAL, "vtx_device_csr: %s [%u, %u)", csr_bad_reason(flag), row_begin, row_end);
     }
-    HIP_TRY(c, c->d_csr_indptr.reserve(((size_t)(row_end - row_begin) + 1) * sizeof(uint64_t)));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT1], s));
-    HIP_TRY(c, vtxr_offsets(d_row, nnz, row_begin, row_end, c->d_csr_indptr.as<uint64_t>(), s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, c->csr.d_indptr.reserve(((size_t)(row_end - row_begin) + 1) * sizeof(uint64_t)));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_SORT1], s));
+    HIP_TRY(c, vtxr_offsets(d_row, nnz, row_begin, row_end, c->csr.d_indptr.as<uint64_t>(), s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_OFFSETS1], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = csr_times(c, nnz != 0, false, false)) return rc;
-    out->indptr = c->d_csr_indptr.as<uint64_t>();
+    out->indptr = c->csr.d_indptr.as<uint64_t>();
     out->indices = c->d_o_col.as<uint32_t>();
     out->alt = c->d_o_alt.as<uint32_t>(); out->ref = c->d_o_ref.as<uint32_t>(); out->unk = c->d_o_unk.as<uint32_t>();
     out->value = c->d_o_val.as<double>(); out->ref_value = c->d_o_refval.as<double>();
@@ -2855,76 +2909,49 @@ int vtx_device_csr(vtx_ctx* c, uint32_t row_begin, uint32_t row_end, vtx_csr* ou
 int vtx_csr_transpose(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
                       uint64_t* d_indptr_t, uint32_t* d_indices_t, uint32_t* d_perm, const void* const* d_payload_in, void* const* d_payload_out,
                       const uint32_t* payload_elem_bytes, uint32_t n_payload) {
+    const char* who = "vtx_csr_transpose";
     if (!c) return VTX_E_INVAL;
-    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "vtx_csr_transpose: %llu entries: positions are 32-bit", (unsigned long long)nnz);
-    if (!d_indptr || !d_indptr_t || (nnz && (!d_indices || !d_indices_t))) return fail(c, VTX_E_INVAL, "vtx_csr_transpose: null array");
-    if (n_payload && (!d_payload_in || !d_payload_out || !payload_elem_bytes)) return fail(c, VTX_E_INVAL, "vtx_csr_transpose: null payload list");
-    for (uint32_t a = 0; a < n_payload; ++a) {
-        if (payload_elem_bytes[a] != 4 && payload_elem_bytes[a] != 8)
-            return fail(c, VTX_E_INVAL, "vtx_csr_transpose: payload %u has elements of %u bytes (4 or 8)", a, payload_elem_bytes[a]);
-        if (nnz && (!d_payload_in[a] || !d_payload_out[a])) return fail(c, VTX_E_INVAL, "vtx_csr_transpose: payload %u is null", a);
-    }
+    if (int rc = csr_positions_fit(c, who, nnz)) return rc;
+    if (!d_indptr || !d_indptr_t || (nnz && (!d_indices || !d_indices_t))) return fail(c, VTX_E_INVAL, "%s: null array", who);
+    if (int rc = csr_payload_args(c, who, d_payload_in, d_payload_out, payload_elem_bytes, n_payload, nnz != 0, nnz != 0)) return rc;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
-    // the caller's arrays are read, and judged, before a single byte is written through them
-    if (int rc = csr_events(c)) return rc;
-    if (int rc = csr_flag_zero(c)) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK0], s));
-    HIP_TRY(c, vtxr_check(d_indptr, n_major, nnz, d_indices, n_minor, c->d_csr_flag.as<uint32_t>(), s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK1], s));
-    uint32_t flag = 0;
-    if (int rc = csr_flag_read(c, &flag)) return rc;
-    if (flag) return fail(c, VTX_E_INVAL, "vtx_csr_transpose: %s", csr_bad_reason(flag));
+    if (int rc = csr_checked(c, who, n_major, n_minor, nnz, d_indptr, d_indices)) return rc;
     uint32_t* perm = d_perm;
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT0], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_SORT0], s));
     if (nnz) {
         const int end_bit = (int)bits_for(n_minor - 1);
         const size_t tmp = vtxr_sort_temp_bytes(nnz, end_bit);
-        HIP_TRY(c, c->d_csr_keys.reserve((size_t)nnz * sizeof(uint32_t)));
-        HIP_TRY(c, c->d_csr_iota.reserve((size_t)nnz * sizeof(uint32_t)));
-        HIP_TRY(c, c->d_csr_tmp.reserve(tmp));
-        if (!perm) { HIP_TRY(c, c->d_csr_perm.reserve((size_t)nnz * sizeof(uint32_t))); perm = c->d_csr_perm.as<uint32_t>(); }
-        HIP_TRY(c, vtxr_sort_positions(d_indices, c->d_csr_keys.as<uint32_t>(), c->d_csr_iota.as<uint32_t>(), perm, nnz, end_bit, c->d_csr_tmp.p, tmp, s));
+        HIP_TRY(c, c->csr.d_keys.reserve((size_t)nnz * sizeof(uint32_t)));
+        HIP_TRY(c, c->csr.d_iota.reserve((size_t)nnz * sizeof(uint32_t)));
+        HIP_TRY(c, c->csr.d_tmp.reserve(tmp));
+        if (!perm) { HIP_TRY(c, c->csr.d_perm.reserve((size_t)nnz * sizeof(uint32_t))); perm = c->csr.d_perm.as<uint32_t>(); }
+        HIP_TRY(c, vtxr_sort_positions(d_indices, c->csr.d_keys.as<uint32_t>(), c->csr.d_iota.as<uint32_t>(), perm, nnz, end_bit, c->csr.d_tmp.p, tmp, s));
     }
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT1], s));
-    HIP_TRY(c, vtxr_offsets(c->d_csr_keys.as<uint32_t>(), nnz, 0, n_minor, d_indptr_t, s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_SORT1], s));
+    HIP_TRY(c, vtxr_offsets(c->csr.d_keys.as<uint32_t>(), nnz, 0, n_minor, d_indptr_t, s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_OFFSETS1], s));
     HIP_TRY(c, vtxr_place(d_indptr, n_major, perm, nnz, d_indices_t, d_payload_in, d_payload_out, payload_elem_bytes, n_payload, s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_PLACE1], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = csr_times(c, true, true, true)) return rc;
     return VTX_OK;
 }
 
 // ---- summaries and selections of a caller's CSR (include/vtx.h, vtx_csr_ops.hip) ----
-// the check every one of these calls begins with: the caller's arrays are read, and judged, before a single byte is written
-static int csr_checked(vtx_ctx* c, const char* who, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr,
-                       const uint32_t* d_indices) {
-    hipStream_t s = c->stream;
-    if (int rc = csr_events(c)) return rc;
-    if (int rc = csr_flag_zero(c)) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK0], s));
-    HIP_TRY(c, vtxr_check(d_indptr, n_major, nnz, d_indices, n_minor, c->d_csr_flag.as<uint32_t>(), s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK1], s));
-    uint32_t flag = 0;
-    if (int rc = csr_flag_read(c, &flag)) return rc;
-    if (flag) return fail(c, VTX_E_INVAL, "%s: %s", who, csr_bad_reason(flag));
-    return VTX_OK;
-}
-
 int vtx_csr_row_stats(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
                       const uint32_t* d_alt, const uint32_t* d_ref, const uint32_t* d_unk, const vtx_csr_stats* out) {
     if (!c) return VTX_E_INVAL;
-    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "vtx_csr_row_stats: %llu entries: positions are 32-bit", (unsigned long long)nnz);
+    if (int rc = csr_positions_fit(c, "vtx_csr_row_stats", nnz)) return rc;
     if (!out || !d_indptr || (nnz && (!d_indices || !d_alt || !d_ref || !d_unk))) return fail(c, VTX_E_INVAL, "vtx_csr_row_stats: null array");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
     if (int rc = csr_checked(c, "vtx_csr_row_stats", n_major, n_minor, nnz, d_indptr, d_indices)) return rc;
     uint32_t G = vtxr::group_lanes(nnz, n_major);
     if (const char* e = VTX_DEV_ENV("VTX_CSR_STATS_G")) G = (uint32_t)atoi(e);    // developer library: the sweep behind the rule (tools/csr_profile.py)
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_OFFSETS1], s));
     HIP_TRY(c, vtxr_row_stats(d_indptr, n_major, d_alt, d_ref, d_unk, out, G, s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_PLACE1], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = csr_times(c, true, false, true, false)) return rc;      // no sort, no offsets here
     return VTX_OK;
@@ -2936,16 +2963,16 @@ static int csr_select_scans(vtx_ctx* c, const char* who, uint32_t n_major, uint3
     hipStream_t s = c->stream;
     if (int rc = csr_checked(c, who, n_major, n_minor, nnz, d_indptr, d_indices)) return rc;
     const size_t tmp = std::max(vtxr_scan_temp_bytes(nnz + 1), std::max(vtxr_scan_temp_bytes((uint64_t)n_major + 1), vtxr_scan_temp_bytes((uint64_t)n_minor + 1)));
-    HIP_TRY(c, c->d_sel_pos.reserve(((size_t)nnz + 1) * sizeof(uint32_t)));
-    HIP_TRY(c, c->d_sel_major.reserve(((size_t)n_major + 1) * sizeof(uint32_t)));
-    HIP_TRY(c, c->d_sel_minor.reserve(((size_t)n_minor + 1) * sizeof(uint32_t)));
-    HIP_TRY(c, c->d_sel_tmp.reserve(std::max<size_t>(tmp, 1)));      // never a null work space: with one the scan only reports its size
-    uint32_t *pos = c->d_sel_pos.as<uint32_t>(), *major_map = c->d_sel_major.as<uint32_t>(), *minor_map = c->d_sel_minor.as<uint32_t>();
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT0], s));
-    HIP_TRY(c, vtxr_mask_map(d_keep_minor, n_minor, minor_map, c->d_sel_tmp.p, tmp, s));
-    HIP_TRY(c, vtxr_keep_positions(d_indptr, n_major, d_indices, nnz, d_keep_major, d_keep_minor, pos, c->d_sel_tmp.p, tmp, s));
-    HIP_TRY(c, vtxr_mask_map(d_keep_major, n_major, major_map, c->d_sel_tmp.p, tmp, s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT1], s));
+    HIP_TRY(c, c->csr.d_sel_pos.reserve(((size_t)nnz + 1) * sizeof(uint32_t)));
+    HIP_TRY(c, c->csr.d_sel_major.reserve(((size_t)n_major + 1) * sizeof(uint32_t)));
+    HIP_TRY(c, c->csr.d_sel_minor.reserve(((size_t)n_minor + 1) * sizeof(uint32_t)));
+    HIP_TRY(c, c->csr.d_sel_tmp.reserve(std::max<size_t>(tmp, 1)));      // never a null work space: with one the scan only reports its size
+    uint32_t *pos = c->csr.d_sel_pos.as<uint32_t>(), *major_map = c->csr.d_sel_major.as<uint32_t>(), *minor_map = c->csr.d_sel_minor.as<uint32_t>();
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_SORT0], s));
+    HIP_TRY(c, vtxr_mask_map(d_keep_minor, n_minor, minor_map, c->csr.d_sel_tmp.p, tmp, s));
+    HIP_TRY(c, vtxr_keep_positions(d_indptr, n_major, d_indices, nnz, d_keep_major, d_keep_minor, pos, c->csr.d_sel_tmp.p, tmp, s));
+    HIP_TRY(c, vtxr_mask_map(d_keep_major, n_major, major_map, c->csr.d_sel_tmp.p, tmp, s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_SORT1], s));
     HIP_TRY(c, hipMemcpyAsync(&sizes[0], major_map + n_major, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(&sizes[1], minor_map + n_minor, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(&sizes[2], pos + nnz, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -2957,7 +2984,7 @@ int vtx_csr_select_plan(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t
                         const uint8_t* d_keep_major, const uint8_t* d_keep_minor, uint32_t* n_major_out, uint32_t* n_minor_out,
                         uint64_t* nnz_out) {
     if (!c) return VTX_E_INVAL;
-    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "vtx_csr_select_plan: %llu entries: positions are 32-bit", (unsigned long long)nnz);
+    if (int rc = csr_positions_fit(c, "vtx_csr_select_plan", nnz)) return rc;
     if (!d_indptr || (nnz && !d_indices) || !n_major_out || !n_minor_out || !nnz_out) return fail(c, VTX_E_INVAL, "vtx_csr_select_plan: null array");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     uint32_t sizes[3] = {0, 0, 0};
@@ -2972,14 +2999,9 @@ int vtx_csr_select(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
                    uint64_t* d_indptr_out, uint32_t* d_indices_out, uint32_t* d_major_ids, uint32_t* d_minor_ids,
                    const void* const* d_payload_in, void* const* d_payload_out, const uint32_t* payload_elem_bytes, uint32_t n_payload) {
     if (!c) return VTX_E_INVAL;
-    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "vtx_csr_select: %llu entries: positions are 32-bit", (unsigned long long)nnz);
+    if (int rc = csr_positions_fit(c, "vtx_csr_select", nnz)) return rc;
     if (!d_indptr || !d_indptr_out || (nnz && !d_indices) || (nnz_out && !d_indices_out)) return fail(c, VTX_E_INVAL, "vtx_csr_select: null array");
-    if (n_payload && (!d_payload_in || !d_payload_out || !payload_elem_bytes)) return fail(c, VTX_E_INVAL, "vtx_csr_select: null payload list");
-    for (uint32_t a = 0; a < n_payload; ++a) {
-        if (payload_elem_bytes[a] != 4 && payload_elem_bytes[a] != 8)
-            return fail(c, VTX_E_INVAL, "vtx_csr_select: payload %u has elements of %u bytes (4 or 8)", a, payload_elem_bytes[a]);
-        if ((nnz && !d_payload_in[a]) || (nnz_out && !d_payload_out[a])) return fail(c, VTX_E_INVAL, "vtx_csr_select: payload %u is null", a);
-    }
+    if (int rc = csr_payload_args(c, "vtx_csr_select", d_payload_in, d_payload_out, payload_elem_bytes, n_payload, nnz != 0, nnz_out != 0)) return rc;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
     uint32_t sizes[3] = {0, 0, 0};
@@ -2988,19 +3010,19 @@ int vtx_csr_select(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
     if (sizes[0] != n_major_out || sizes[1] != n_minor_out || sizes[2] != nnz_out)
         return fail(c, VTX_E_INVAL, "vtx_csr_select: the selection has %u rows, %u columns and %u entries, the caller said %u, %u and %llu (vtx_csr_select_plan)",
                     sizes[0], sizes[1], sizes[2], n_major_out, n_minor_out, (unsigned long long)nnz_out);
-    const uint32_t *pos = c->d_sel_pos.as<uint32_t>(), *major_map = c->d_sel_major.as<uint32_t>(), *minor_map = c->d_sel_minor.as<uint32_t>();
+    const uint32_t *pos = c->csr.d_sel_pos.as<uint32_t>(), *major_map = c->csr.d_sel_major.as<uint32_t>(), *minor_map = c->csr.d_sel_minor.as<uint32_t>();
     float scan_ms = 0.f;                                      // the stream was idle while the sizes came back: the offsets' time starts anew
-    HIP_TRY(c, hipEventElapsedTime(&scan_ms, c->ev_csr[EV_CSR_SORT0], c->ev_csr[EV_CSR_SORT1]));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT1], s));
+    HIP_TRY(c, hipEventElapsedTime(&scan_ms, c->csr.ev[EV_CSR_SORT0], c->csr.ev[EV_CSR_SORT1]));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_SORT1], s));
     HIP_TRY(c, vtxr_select_offsets(d_indptr, n_major, d_keep_major, major_map, pos, d_indptr_out, s));
     HIP_TRY(c, vtxr_select_ids(d_keep_major, n_major, major_map, d_major_ids, s));
     HIP_TRY(c, vtxr_select_ids(d_keep_minor, n_minor, minor_map, d_minor_ids, s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_OFFSETS1], s));
     if (nnz_out) HIP_TRY(c, vtxr_select_place(d_indices, nnz, pos, minor_map, d_indices_out, d_payload_in, d_payload_out, payload_elem_bytes, n_payload, s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_PLACE1], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = csr_times(c, true, false, true)) return rc;
-    c->csr_ms[1] = scan_ms;
+    c->csr.ms[1] = scan_ms;
     return VTX_OK;
 }
 
@@ -3012,7 +3034,7 @@ static_assert(VTX_GROUP_NONE == vtxr::GROUP_NONE, "the header's and the kernels'
 // what both calls refuse on the host, before the device is touched
 static int csr_group_args(vtx_ctx* c, const char* who, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
                           const uint32_t* d_group, uint32_t n_groups) {
-    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "%s: %llu entries: positions are 32-bit", who, (unsigned long long)nnz);
+    if (int rc = csr_positions_fit(c, who, nnz)) return rc;
     if (!n_groups) return fail(c, VTX_E_INVAL, "%s: no groups", who);
     if (n_groups > vtxr::GROUP_MAX)
         return fail(c, VTX_E_UNSUPPORTED, "%s: %u groups: at most %u (%u windows of %u)", who, n_groups, vtxr::GROUP_MAX, vtxr::GROUP_MAX_WINDOWS, vtxr::GROUP_WINDOW);
@@ -3023,27 +3045,20 @@ static int csr_group_args(vtx_ctx* c, const char* who, uint32_t n_minor, uint64_
 // The checks of the CSR and of the labels, the count and its scan; nnz_out comes back to the host.  Writes into the context's work space only.
 static int csr_group_counts(vtx_ctx* c, const char* who, uint32_t n_minor, uint64_t nnz, const vtx_group_in& in, uint32_t* nnz_out) {
     hipStream_t s = c->stream;
-    if (int rc = csr_events(c)) return rc;
-    if (int rc = csr_flag_zero(c)) return rc;
-    HIP_TRY(c, c->d_grp_flag.reserve(sizeof(uint32_t)));
-    HIP_TRY(c, hipMemsetAsync(c->d_grp_flag.p, 0xFF, sizeof(uint32_t), s));      // no column yet
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK0], s));
-    HIP_TRY(c, vtxr_check(in.indptr, in.n_major, nnz, in.indices, n_minor, c->d_csr_flag.as<uint32_t>(), s));
-    HIP_TRY(c, vtxr_group_check(in.group, n_minor, in.n_groups, c->d_grp_flag.as<uint32_t>(), s));      // reads group[0 .. n_minor) only, whatever the CSR is
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK1], s));
-    uint32_t flag = 0, first_bad = 0;
-    HIP_TRY(c, hipMemcpyAsync(&first_bad, c->d_grp_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (int rc = csr_flag_read(c, &flag)) return rc;
-    if (flag) return fail(c, VTX_E_INVAL, "%s: %s", who, csr_bad_reason(flag));
-    if (first_bad != 0xFFFFFFFFu)
+    uint64_t verdict[V_COUNT];
+    if (int rc = csr_checked(c, who, in.n_major, n_minor, nnz, in.indptr, in.indices, verdict, [&](hipStream_t st) -> int {
+            HIP_TRY(c, vtxr_group_check(in.group, n_minor, in.n_groups, c->csr.verdict<uint32_t>(V_LABEL), st));      // reads group[0 .. n_minor) only, whatever the CSR is
+            return VTX_OK;
+        })) return rc;
+    if (const uint32_t first_bad = (uint32_t)verdict[V_LABEL]; first_bad != 0xFFFFFFFFu)
         return fail(c, VTX_E_INVAL, "%s: the label of column %u is neither below n_groups = %u nor VTX_GROUP_NONE", who, first_bad, in.n_groups);
     const size_t tmp = vtxr_scan_temp_bytes((uint64_t)in.n_major + 1);
-    HIP_TRY(c, c->d_grp_pos.reserve(((size_t)in.n_major + 1) * sizeof(uint32_t)));
-    HIP_TRY(c, c->d_grp_tmp.reserve(std::max<size_t>(tmp, 1)));      // never a null work space: with one the scan only reports its size
-    uint32_t* pos = c->d_grp_pos.as<uint32_t>();
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT0], s));
-    HIP_TRY(c, vtxr_group_count(in, pos, c->d_grp_tmp.p, tmp, s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_SORT1], s));
+    HIP_TRY(c, c->csr.d_grp_pos.reserve(((size_t)in.n_major + 1) * sizeof(uint32_t)));
+    HIP_TRY(c, c->csr.d_grp_tmp.reserve(std::max<size_t>(tmp, 1)));      // never a null work space: with one the scan only reports its size
+    uint32_t* pos = c->csr.d_grp_pos.as<uint32_t>();
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_SORT0], s));
+    HIP_TRY(c, vtxr_group_count(in, pos, c->csr.d_grp_tmp.p, tmp, s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_SORT1], s));
     HIP_TRY(c, hipMemcpyAsync(nnz_out, pos + in.n_major, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     return VTX_OK;
@@ -3077,107 +3092,91 @@ int vtx_csr_group_sum(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t n
     // stateless: the size is this call's own; a caller whose arrays were made for another fold is refused before a byte is written
     if (n != nnz_out)
         return fail(c, VTX_E_INVAL, "vtx_csr_group_sum: the result has %u entries, the caller said %llu (vtx_csr_group_plan)", n, (unsigned long long)nnz_out);
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
-    HIP_TRY(c, vtxr_group_fill(in, c->d_grp_pos.as<uint32_t>(), d_indptr_out, d_indices_out, out, s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, vtxr_group_fill(in, c->csr.d_grp_pos.as<uint32_t>(), d_indptr_out, d_indices_out, out, s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_PLACE1], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = csr_times(c, true, true, true, false)) return rc;      // checks, count + scan, no offsets phase, fill
     return VTX_OK;
 }
 
-// ---- donor tally: a caller's cells x variants CSR against a table of donor genotypes (include/vtx.h, vtx_csr_geno.hip) ----
+// ---- donor and doublet tally: a caller's cells x variants CSR against a table of donor genotypes, by donor or by pair of donors
+// (include/vtx.h, vtx_csr_geno.hip) ----
 uint32_t vtx_csr_geno_max(void) { return vtxr::GENO_MAX; }
+uint32_t vtx_csr_geno_pair_max(void) { return vtxr::PAIR_MAX; }
 static_assert(VTX_GENO_NONE == vtxr::GENO_NONE, "the header's and the kernels' byte of no call");
-static_assert(sizeof(vtx_geno_tally) == 24, "three pointers");
+static_assert(VTX_GENO_PAIR_CLASSES == vtxr::PAIR_CLASSES, "the header's and the kernels' classes of a pair");
+static_assert(sizeof(vtx_geno_tally) == 24 && sizeof(vtx_geno_pair_tally) == 24, "three pointers");
+
+// what both tallies refuse on the host, before the device is touched.  n_pairs: the doublet call's (nullptr: the donor call);
+// null_array: one of the arrays the call needs is missing
+static int csr_geno_args(vtx_ctx* c, const char* who, uint64_t nnz, uint32_t n_donors, const uint32_t* n_pairs, bool null_array) {
+    if (int rc = csr_positions_fit(c, who, nnz)) return rc;
+    if (!n_donors) return fail(c, VTX_E_INVAL, "%s: no donors", who);
+    if (n_pairs && !*n_pairs) return fail(c, VTX_E_INVAL, "%s: no pairs", who);
+    if (n_donors > vtxr::GENO_MAX)
+        return fail(c, VTX_E_UNSUPPORTED, "%s: %u donors: at most %u (%u passes of %u)", who, n_donors, vtxr::GENO_MAX, vtxr::GENO_MAX_PASSES, vtxr::GENO_WAVE);
+    if (n_pairs && *n_pairs > vtxr::PAIR_MAX)
+        return fail(c, VTX_E_UNSUPPORTED, "%s: %u pairs: at most %u (%u passes of %u)", who, *n_pairs, vtxr::PAIR_MAX, vtxr::PAIR_MAX_PASSES, vtxr::GENO_WAVE);
+    if (null_array) return fail(c, VTX_E_INVAL, "%s: null array", who);
+    return VTX_OK;
+}
+
+// the verdict of vtxr_geno_check
+static int csr_geno_judged(vtx_ctx* c, const char* who, uint64_t first_bad, uint32_t n_donors) {
+    if (first_bad == ~0ull) return VTX_OK;
+    return fail(c, VTX_E_INVAL, "%s: the genotype of variant %llu, donor %llu is neither 0, 1, 2 nor VTX_GENO_NONE", who,
+                (unsigned long long)(first_bad / n_donors), (unsigned long long)(first_bad % n_donors));
+}
 
 int vtx_csr_geno_tally(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
                        const uint32_t* d_alt, const uint32_t* d_ref, const uint8_t* d_geno, uint32_t n_donors, const vtx_geno_tally* out) {
     const char* who = "vtx_csr_geno_tally";
     if (!c) return VTX_E_INVAL;
-    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "%s: %llu entries: positions are 32-bit", who, (unsigned long long)nnz);
-    if (!n_donors) return fail(c, VTX_E_INVAL, "%s: no donors", who);
-    if (n_donors > vtxr::GENO_MAX)
-        return fail(c, VTX_E_UNSUPPORTED, "%s: %u donors: at most %u (%u passes of %u)", who, n_donors, vtxr::GENO_MAX, vtxr::GENO_MAX_PASSES, vtxr::GENO_WAVE);
-    if (!out || !d_indptr || (nnz && (!d_indices || !d_alt || !d_ref)) || (n_minor && !d_geno)) return fail(c, VTX_E_INVAL, "%s: null array", who);
+    if (int rc = csr_geno_args(c, who, nnz, n_donors, nullptr, !out || !d_indptr || (nnz && (!d_indices || !d_alt || !d_ref)) || (n_minor && !d_geno))) return rc;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
-    // the caller's arrays are read, and judged, before a single byte is written through `out`
-    if (int rc = csr_events(c)) return rc;
-    if (int rc = csr_flag_zero(c)) return rc;
-    HIP_TRY(c, c->d_geno_flag.reserve(sizeof(uint64_t)));
-    HIP_TRY(c, hipMemsetAsync(c->d_geno_flag.p, 0xFF, sizeof(uint64_t), s));      // no byte yet
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK0], s));
-    HIP_TRY(c, vtxr_check(d_indptr, n_major, nnz, d_indices, n_minor, c->d_csr_flag.as<uint32_t>(), s));
-    HIP_TRY(c, vtxr_geno_check(d_geno, (uint64_t)n_minor * n_donors, c->d_geno_flag.as<uint64_t>(), s));      // reads the table's own bytes only, whatever the CSR is
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK1], s));
-    uint32_t flag = 0;
-    uint64_t first_bad = 0;
-    HIP_TRY(c, hipMemcpyAsync(&first_bad, c->d_geno_flag.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    if (int rc = csr_flag_read(c, &flag)) return rc;
-    if (flag) return fail(c, VTX_E_INVAL, "%s: %s", who, csr_bad_reason(flag));
-    if (first_bad != ~0ull)
-        return fail(c, VTX_E_INVAL, "%s: the genotype of variant %llu, donor %llu is neither 0, 1, 2 nor VTX_GENO_NONE", who,
-                    (unsigned long long)(first_bad / n_donors), (unsigned long long)(first_bad % n_donors));
+    uint64_t verdict[V_COUNT];
+    if (int rc = csr_checked(c, who, n_major, n_minor, nnz, d_indptr, d_indices, verdict, [&](hipStream_t st) -> int {
+            HIP_TRY(c, vtxr_geno_check(d_geno, (uint64_t)n_minor * n_donors, c->csr.verdict<uint64_t>(V_GENO), st));
+            return VTX_OK;
+        })) return rc;
+    if (int rc = csr_geno_judged(c, who, verdict[V_GENO], n_donors)) return rc;
     const vtx_geno_in in{d_indptr, n_major, d_indices, d_alt, d_ref, d_geno, n_donors};
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_OFFSETS1], s));
     HIP_TRY(c, vtxr_geno_tally(in, out, s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_PLACE1], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = csr_times(c, true, false, true, false)) return rc;      // the two checks and the tally: no sort, no offsets here
     return VTX_OK;
 }
-
-// ---- doublet tally: the same CSR and table against a list of donor pairs (include/vtx.h, vtx_csr_geno_pair.hip) ----
-uint32_t vtx_csr_geno_pair_max(void) { return vtxr::PAIR_MAX; }
-static_assert(VTX_GENO_PAIR_CLASSES == vtxr::PAIR_CLASSES, "the header's and the kernels' classes of a pair");
-static_assert(sizeof(vtx_geno_pair_tally) == 24, "three pointers");
 
 int vtx_csr_geno_pair_tally(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
                             const uint32_t* d_alt, const uint32_t* d_ref, const uint8_t* d_geno, uint32_t n_donors, const uint32_t* d_pairs,
                             uint32_t n_pairs, const vtx_geno_pair_tally* out) {
     const char* who = "vtx_csr_geno_pair_tally";
     if (!c) return VTX_E_INVAL;
-    if (nnz >= (1ull << 32)) return fail(c, VTX_E_UNSUPPORTED, "%s: %llu entries: positions are 32-bit", who, (unsigned long long)nnz);
-    if (!n_donors) return fail(c, VTX_E_INVAL, "%s: no donors", who);
-    if (!n_pairs) return fail(c, VTX_E_INVAL, "%s: no pairs", who);
-    if (n_donors > vtxr::GENO_MAX)
-        return fail(c, VTX_E_UNSUPPORTED, "%s: %u donors: at most %u (%u passes of %u)", who, n_donors, vtxr::GENO_MAX, vtxr::GENO_MAX_PASSES, vtxr::GENO_WAVE);
-    if (n_pairs > vtxr::PAIR_MAX)
-        return fail(c, VTX_E_UNSUPPORTED, "%s: %u pairs: at most %u (%u passes of %u)", who, n_pairs, vtxr::PAIR_MAX, vtxr::PAIR_MAX_PASSES, vtxr::GENO_WAVE);
-    if (!out || !d_indptr || !d_pairs || (nnz && (!d_indices || !d_alt || !d_ref)) || (n_minor && !d_geno)) return fail(c, VTX_E_INVAL, "%s: null array", who);
+    if (int rc = csr_geno_args(c, who, nnz, n_donors, &n_pairs,
+                               !out || !d_indptr || !d_pairs || (nnz && (!d_indices || !d_alt || !d_ref)) || (n_minor && !d_geno))) return rc;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
-    // the caller's arrays are read, and judged, before a single byte is written through `out`
-    if (int rc = csr_events(c)) return rc;
-    if (int rc = csr_flag_zero(c)) return rc;
-    HIP_TRY(c, c->d_geno_flag.reserve(sizeof(uint64_t)));
-    HIP_TRY(c, c->d_pair_flag.reserve(sizeof(uint64_t)));
-    HIP_TRY(c, hipMemsetAsync(c->d_geno_flag.p, 0xFF, sizeof(uint64_t), s));      // no byte yet
-    HIP_TRY(c, hipMemsetAsync(c->d_pair_flag.p, 0xFF, sizeof(uint64_t), s));      // no pair yet
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK0], s));
-    HIP_TRY(c, vtxr_check(d_indptr, n_major, nnz, d_indices, n_minor, c->d_csr_flag.as<uint32_t>(), s));
-    HIP_TRY(c, vtxr_geno_check(d_geno, (uint64_t)n_minor * n_donors, c->d_geno_flag.as<uint64_t>(), s));      // each check reads its own array only, whatever the others hold
-    HIP_TRY(c, vtxr_geno_pair_check(d_pairs, n_pairs, n_donors, c->d_pair_flag.as<uint64_t>(), s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_CHECK1], s));
-    uint32_t flag = 0;
-    uint64_t first_bad = 0, first_pair = 0;
-    HIP_TRY(c, hipMemcpyAsync(&first_bad, c->d_geno_flag.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&first_pair, c->d_pair_flag.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    if (int rc = csr_flag_read(c, &flag)) return rc;
-    if (flag) return fail(c, VTX_E_INVAL, "%s: %s", who, csr_bad_reason(flag));
-    if (first_bad != ~0ull)
-        return fail(c, VTX_E_INVAL, "%s: the genotype of variant %llu, donor %llu is neither 0, 1, 2 nor VTX_GENO_NONE", who,
-                    (unsigned long long)(first_bad / n_donors), (unsigned long long)(first_bad % n_donors));
-    if (first_pair != ~0ull) {      // < n_pairs: the check's lanes are the pairs
+    uint64_t verdict[V_COUNT];
+    if (int rc = csr_checked(c, who, n_major, n_minor, nnz, d_indptr, d_indices, verdict, [&](hipStream_t st) -> int {
+            HIP_TRY(c, vtxr_geno_check(d_geno, (uint64_t)n_minor * n_donors, c->csr.verdict<uint64_t>(V_GENO), st));
+            HIP_TRY(c, vtxr_geno_pair_check(d_pairs, n_pairs, n_donors, c->csr.verdict<uint64_t>(V_PAIR), st));
+            return VTX_OK;
+        })) return rc;
+    if (int rc = csr_geno_judged(c, who, verdict[V_GENO], n_donors)) return rc;
+    if (const uint64_t first_pair = verdict[V_PAIR]; first_pair != ~0ull) {      // < n_pairs: the check's lanes are the pairs
         uint32_t ab[2] = {0, 0};
         HIP_TRY(c, hipMemcpyAsync(ab, d_pairs + 2 * first_pair, sizeof(ab), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         return fail(c, VTX_E_INVAL, "%s: pair %llu is (%u, %u): a donor is not below n_donors = %u", who, (unsigned long long)first_pair, ab[0], ab[1], n_donors);
     }
     const vtx_geno_pair_in in{d_indptr, n_major, d_indices, d_alt, d_ref, d_geno, n_donors, d_pairs, n_pairs};
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_OFFSETS1], s));
     HIP_TRY(c, vtxr_geno_pair_tally(in, out, s));
-    HIP_TRY(c, hipEventRecord(c->ev_csr[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_PLACE1], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = csr_times(c, true, false, true, false)) return rc;      // the three checks and the tally: no sort, no offsets here
     return VTX_OK;

@@ -1,6 +1,7 @@
-// vtx_csr_geno_pair_core.h — what ONE LANE does alone in the doublet tally kernels (vtx_csr_geno_pair.hip): the check of a pair of donors,
-// the class of an entry under a pair, an entry's contribution to the lane's eighteen numbers, the merge of the lanes that share a pair,
-// and the place of a number in the output.  The lane's place in the wavefront is vtx_csr_geno_core.h's, with a pair in a donor's place.
+// vtx_csr_geno_pair_core.h — what is particular to a PAIR of donors in the tally kernel (vtx_csr_geno.hip): the check of a pair, the
+// class of an entry under a pair, and the policy PairHyp that hands both to the kernel.  The lane's place in the wavefront, the tally
+// (ClassTally<PAIR_CLASSES>: eighteen numbers), its fold and its place in the output are vtx_csr_geno_core.h's, with a pair in a
+// donor's place.
 //
 // What it serves: the two-donor hypotheses next to the one-donor ones of vtx_csr_geno_core.h.  A droplet that holds cells of the donors
 // a and b in equal parts shows, at a variant, an alt read with a probability that depends only on the DOSAGE g_a + g_b in 0 .. 4.  So per
@@ -15,8 +16,7 @@
 // The lane map.  pass_lanes, lane_map, lane_live, sub_groups and the fold distances of vtx_csr_geno_core.h with n_pairs for n_donors: one
 // wavefront owns a row and, per pass, the pairs [base, base + count), count <= 64; lane (sub, d) is live when base + d < n_pairs, loads
 // its (a, b) once per pass and tallies over the entries begin + sub, + 64 / Dp, ...  Per entry it loads two bytes of the table, both
-// inside it (pair_geno_index).  The tally lives in registers: pair_tally_add selects the class by six predicated additions, never by an
-// index into the arrays.  n_pairs > 64: the wavefront repeats the row once per 64 pairs, at most PAIR_MAX_PASSES times.
+// inside it (pair_geno_index).  n_pairs > 64: the wavefront repeats the row once per 64 pairs, at most PAIR_MAX_PASSES times.
 //
 // Compiles for the host too (tests/csrgenopaircore/: the same functions, the lanes as loops, the exchange as array reads, against numpy).
 #ifndef VTX_CSR_GENO_PAIR_CORE_H
@@ -31,10 +31,7 @@ constexpr uint32_t PAIR_NONE_CLASS = 5;
 constexpr uint32_t PAIR_MAX_PASSES = 64;                                  // passes over a row, at most
 constexpr uint32_t PAIR_MAX = GENO_WAVE * PAIR_MAX_PASSES;                // the largest n_pairs
 
-struct PairTally {
-    uint64_t sum_alt[PAIR_CLASSES], sum_ref[PAIR_CLASSES];
-    uint32_t n_obs[PAIR_CLASSES];                                         // entries of the class with alt + ref > 0
-};
+using PairTally = ClassTally<PAIR_CLASSES>;
 
 // a pair the call refuses: a donor the table has no column for
 VTXR_FN bool pair_bad(uint32_t a, uint32_t b, uint32_t n_donors) { return a >= n_donors || b >= n_donors; }
@@ -45,33 +42,17 @@ VTXR_FN uint32_t pair_class(uint8_t ga, uint8_t gb) { return (ga == GENO_NONE ||
 // where the byte of a donor is: < n_minor * n_donors, since v < n_minor (the CSR check) and donor < n_donors (the pair check)
 VTXR_FN uint64_t pair_geno_index(uint32_t v, uint32_t n_donors, uint32_t donor) { return (uint64_t)v * n_donors + donor; }
 
-VTXR_FN PairTally pair_tally_zero() {
-    return PairTally{{0ull, 0ull, 0ull, 0ull, 0ull, 0ull}, {0ull, 0ull, 0ull, 0ull, 0ull, 0ull}, {0u, 0u, 0u, 0u, 0u, 0u}};
-}
-
-// one entry into the tally of a pair whose class at the entry's variant is `cls`: every class takes an addition, five of them of zero
-VTXR_FN void pair_tally_add_class(PairTally& t, uint32_t c, bool on, uint32_t alt, uint32_t ref, uint32_t seen) {      // c: a literal at every call
-    t.sum_alt[c] += on ? alt : 0u;
-    t.sum_ref[c] += on ? ref : 0u;
-    t.n_obs[c] += on ? seen : 0u;
-}
-VTXR_FN void pair_tally_add(PairTally& t, uint32_t cls, uint32_t alt, uint32_t ref) {
-    const uint32_t seen = (alt | ref) != 0u;                              // alt + ref > 0 without the carry
-    pair_tally_add_class(t, 0, cls == 0u, alt, ref, seen);
-    pair_tally_add_class(t, 1, cls == 1u, alt, ref, seen);
-    pair_tally_add_class(t, 2, cls == 2u, alt, ref, seen);
-    pair_tally_add_class(t, 3, cls == 3u, alt, ref, seen);
-    pair_tally_add_class(t, 4, cls == 4u, alt, ref, seen);
-    pair_tally_add_class(t, 5, cls == 5u, alt, ref, seen);
-}
-
-// the partial tally of another lane of the same pair
-VTXR_FN void pair_tally_merge(PairTally& a, const PairTally& b) {
-    for (uint32_t c = 0; c < PAIR_CLASSES; ++c) { a.sum_alt[c] += b.sum_alt[c]; a.sum_ref[c] += b.sum_ref[c]; a.n_obs[c] += b.n_obs[c]; }
-}
-
-// the element of (row r, pair p, class c) in each of the three output arrays
-VTXR_FN uint64_t pair_tally_index(uint64_t r, uint32_t n_pairs, uint32_t p, uint32_t c) { return (r * n_pairs + p) * PAIR_CLASSES + c; }
+// The two-donor hypotheses as the tally kernel takes them (DonorHyp's counterpart).  `In`: the fields of vtx_geno_pair_in (vtx_device.h).
+struct PairHyp {
+    static constexpr uint32_t CLASSES = PAIR_CLASSES;
+    struct Lane { uint32_t a, b; };                                       // a live lane loads its pair once per pass
+    template <class In> VTXR_STATIC_FN uint32_t count(const In& in) { return in.n_pairs; }
+    template <class In> VTXR_STATIC_FN Lane load(const In& in, uint32_t h) { return Lane{in.pairs[2 * h], in.pairs[2 * h + 1]}; }
+    // the class of the entry at variant v under the pair, a live lane's
+    template <class In> VTXR_STATIC_FN uint32_t cls(const In& in, const Lane& me, uint32_t v, uint32_t) {
+        return pair_class(in.geno[pair_geno_index(v, in.n_donors, me.a)], in.geno[pair_geno_index(v, in.n_donors, me.b)]);
+    }
+};
 
 }  // namespace vtxr
 #endif

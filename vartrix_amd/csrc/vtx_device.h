@@ -285,8 +285,8 @@ hipError_t vtxr_geno_check(const uint8_t* geno, uint64_t n_bytes, uint64_t* firs
 // the arrays of `out` (any of them NULL: not written) have n_major * n_donors * 4 elements, each stored once
 hipError_t vtxr_geno_tally(const vtx_geno_in& in, const vtx_geno_tally* out, hipStream_t s);
 }
-// ---- vtx_csr_geno_pair.hip: a cell's reads tallied against pairs of donors.  The CSR has passed vtxr_check, the table vtxr_geno_check,
-// the pairs vtxr_geno_pair_check ----
+// ---- vtx_csr_geno.hip too (the same kernel over pairs): a cell's reads tallied against pairs of donors.  The CSR has passed vtxr_check,
+// the table vtxr_geno_check, the pairs vtxr_geno_pair_check ----
 // vtx_geno_in's matrix and table, and pairs[2 * n_pairs]: the donors (a, b) of pair p at [2 p], [2 p + 1], both < n_donors
 struct vtx_geno_pair_in {
     const uint64_t* indptr; uint32_t n_major; const uint32_t* indices; const uint32_t *alt, *ref; const uint8_t* geno; uint32_t n_donors;

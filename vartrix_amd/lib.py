@@ -241,6 +241,27 @@ def mtx_join(path: str, n_rows: int, n_cols: int, parts, gz: bool = False, varia
     return int(t.value)
 
 
+def _out_struct(cls, out: dict, names, who: str, what: str):
+    """A struct of output pointers from a dict name -> device address; a name that is missing or 0 stays NULL, a name the struct does
+    not have is a ValueError."""
+    unknown = set(out) - set(names)
+    if unknown:
+        raise ValueError("%s: unknown %s %s" % (who, what, sorted(unknown)))
+    st = cls()
+    for k, typ in st._fields_:
+        setattr(st, k, C.cast(C.c_void_p(int(out.get(k) or 0) or None), typ))
+    return st
+
+
+def _payload_arrays(payloads):
+    """(address in, address out, element bytes) per array that moves with the entries -> the three C arrays and their length."""
+    n = len(payloads)
+    p_in = (C.c_void_p * max(n, 1))(*[int(p[0]) or None for p in payloads])
+    p_out = (C.c_void_p * max(n, 1))(*[int(p[1]) or None for p in payloads])
+    p_sz = (C.c_uint32 * max(n, 1))(*[int(p[2]) for p in payloads])
+    return p_in, p_out, p_sz, n
+
+
 class Context:
     """One vtx_ctx: bound to one GPU, holds one resident batch."""
 
@@ -417,10 +438,7 @@ class Context:
                       payloads=()):
         """Stable transpose of a CSR in device memory (vtx_csr_transpose); every array is a raw device ADDRESS.  ``payloads``: a list
         of (address in, address out, element bytes 4 | 8) that move with the entries.  ``perm`` = 0: not wanted."""
-        n = len(payloads)
-        p_in = (C.c_void_p * max(n, 1))(*[int(p[0]) or None for p in payloads])
-        p_out = (C.c_void_p * max(n, 1))(*[int(p[1]) or None for p in payloads])
-        p_sz = (C.c_uint32 * max(n, 1))(*[int(p[2]) for p in payloads])
+        p_in, p_out, p_sz, n = _payload_arrays(payloads)
         self._check(self._L.vtx_csr_transpose(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, indptr_t or None,
                                               indices_t or None, perm or None, p_in, p_out, p_sz, n))
 
@@ -435,12 +453,7 @@ class Context:
         """The statistics of every row of a CSR in device memory (vtx_csr_row_stats); every array is a raw device ADDRESS.  ``out``:
         name (``abi.CSR_STAT_NAMES``) -> address of n_major uint32 (the four counts) / uint64 (the three sums); a name that is missing
         or 0 is not computed into memory."""
-        unknown = set(out) - set(abi.CSR_STAT_NAMES)
-        if unknown:
-            raise ValueError("csr_row_stats: unknown statistics %s" % sorted(unknown))
-        st = abi.VtxCsrStats()
-        for k, typ in st._fields_:
-            setattr(st, k, C.cast(C.c_void_p(int(out.get(k) or 0) or None), typ))
+        st = _out_struct(abi.VtxCsrStats, out, abi.CSR_STAT_NAMES, "csr_row_stats", "statistics")
         self._check(self._L.vtx_csr_row_stats(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
                                               ref or None, unk or None, C.byref(st)))
 
@@ -457,10 +470,7 @@ class Context:
         """Stable selection of rows and columns of a CSR in device memory (vtx_csr_select).  ``sizes``: what ``csr_select_plan`` returned
         for the same inputs, the sizes the outputs were allocated for — any other selection is refused with nothing written.
         ``payloads``: (address in, address out, element bytes 4 | 8) per array that moves with the entries."""
-        n = len(payloads)
-        p_in = (C.c_void_p * max(n, 1))(*[int(p[0]) or None for p in payloads])
-        p_out = (C.c_void_p * max(n, 1))(*[int(p[1]) or None for p in payloads])
-        p_sz = (C.c_uint32 * max(n, 1))(*[int(p[2]) for p in payloads])
+        p_in, p_out, p_sz, n = _payload_arrays(payloads)
         self._check(self._L.vtx_csr_select(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, keep_major or None,
                                            keep_minor or None, int(sizes[0]), int(sizes[1]), int(sizes[2]), indptr_out or None, indices_out or None,
                                            major_ids or None, minor_ids or None, p_in, p_out, p_sz, n))
@@ -479,12 +489,7 @@ class Context:
         ``csr_group_plan`` returned for the same inputs, the size the outputs were allocated for — any other fold is refused with
         nothing written.  ``out``: name (``abi.CSR_STAT_NAMES``) -> address of nnz_out uint32 (the four counts) / uint64 (the three
         sums); a name that is missing or 0 is not written."""
-        unknown = set(out) - set(abi.CSR_STAT_NAMES)
-        if unknown:
-            raise ValueError("csr_group_sum: unknown statistics %s" % sorted(unknown))
-        st = abi.VtxCsrStats()
-        for k, typ in st._fields_:
-            setattr(st, k, C.cast(C.c_void_p(int(out.get(k) or 0) or None), typ))
+        st = _out_struct(abi.VtxCsrStats, out, abi.CSR_STAT_NAMES, "csr_group_sum", "statistics")
         self._check(self._L.vtx_csr_group_sum(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
                                               ref or None, unk or None, group or None, int(n_groups), int(nnz_out), indptr_out or None,
                                               indices_out or None, C.byref(st)))
@@ -495,12 +500,7 @@ class Context:
         (vtx_csr_geno_tally).  ``geno``: the address of n_minor * n_donors bytes, variant-major, each 0, 1, 2 or ``abi.VTX_GENO_NONE``.
         ``out``: name (``abi.GENO_TALLY_NAMES``) -> address of n_major * n_donors * 4 uint64 (``sum_alt``, ``sum_ref``) / uint32
         (``n_obs``); a name that is missing or 0 is not written."""
-        unknown = set(out) - set(abi.GENO_TALLY_NAMES)
-        if unknown:
-            raise ValueError("csr_geno_tally: unknown outputs %s" % sorted(unknown))
-        st = abi.VtxGenoTally()
-        for k, typ in st._fields_:
-            setattr(st, k, C.cast(C.c_void_p(int(out.get(k) or 0) or None), typ))
+        st = _out_struct(abi.VtxGenoTally, out, abi.GENO_TALLY_NAMES, "csr_geno_tally", "outputs")
         self._check(self._L.vtx_csr_geno_tally(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
                                                ref or None, geno or None, int(n_donors), C.byref(st)))
 
@@ -511,12 +511,7 @@ class Context:
         the donors (a, b) of pair p at [2 p], [2 p + 1], both below ``n_donors``.  ``out``: name (``abi.GENO_TALLY_NAMES``) -> address of
         n_major * n_pairs * 6 uint64 (``sum_alt``, ``sum_ref``) / uint32 (``n_obs``), by the dosage g_a + g_b (5: either donor without a
         call); a name that is missing or 0 is not written."""
-        unknown = set(out) - set(abi.GENO_TALLY_NAMES)
-        if unknown:
-            raise ValueError("csr_geno_pair_tally: unknown outputs %s" % sorted(unknown))
-        st = abi.VtxGenoPairTally()
-        for k, typ in st._fields_:
-            setattr(st, k, C.cast(C.c_void_p(int(out.get(k) or 0) or None), typ))
+        st = _out_struct(abi.VtxGenoPairTally, out, abi.GENO_TALLY_NAMES, "csr_geno_pair_tally", "outputs")
         self._check(self._L.vtx_csr_geno_pair_tally(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
                                                     ref or None, geno or None, int(n_donors), pairs or None, int(n_pairs), C.byref(st)))
 
