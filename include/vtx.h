@@ -678,6 +678,31 @@ int vtx_csr_geno_pair_tally(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, ui
                             const uint8_t* d_geno, uint32_t n_donors,
                             const uint32_t* d_pairs, uint32_t n_pairs, const vtx_geno_pair_tally* out);
 
+/* ---- CSR x integer tables: the integer part of the models without genotype classes (vartrix_amd/csrc/vtx_csr_dense.hip) ------------------
+ * Where the alt probability at a variant is a free parameter per (variant, hypothesis) — clustering without genotypes, an ambient
+ * profile, an unequal mixture — the integer part of a likelihood is no tally by class but a sparse-times-dense product:
+ *   out[r * n_cols + h] = sum over the entries k of row r of  alt[k] * w_alt[indices[k] * n_cols + h] + ref[k] * w_ref[indices[k] * n_cols + h]
+ * d_w_alt and d_w_ref are int32_t[n_minor * n_cols] in device memory, minor-major: element (uint64_t)v * n_cols + h, the columns of one
+ * minor index consecutive.  Either table may be NULL and its term is then absent (the same table may so serve as w_alt in one call and
+ * as w_ref in the next, without a copy); both NULL is VTX_E_INVAL unless n_minor == 0, where no table has an element.  The sum is
+ * COMPUTED MODULO 2^64 and read as two's complement: the counts are zero-extended, the weights sign-extended, the products added in
+ * uint64_t.  Wrapping is defined behaviour; the sum is the true sum whenever that fits int64_t.  Any int32_t is a valid weight: the
+ * tables are not checked.  d_out has n_major * n_cols elements; every one is written, zeros for rows without entries.
+ * The contract is vtx_csr_geno_tally's: ANY CSR in caller-owned device memory (rows in any order inside, duplicate indices allowed:
+ * every entry counts), a context but no run, synchronous on the context's stream, and the CSR is checked on the device BEFORE anything
+ * is written.  A violation returns VTX_E_INVAL (the reason in vtx_strerror), no output byte is written and the context stays usable.
+ * VTX_E_INVAL also for n_cols == 0, a null d_out and a null array that is needed; VTX_E_UNSUPPORTED for nnz >= 2^32 and for n_cols >
+ * vtx_csr_dense_max().  Outputs must not overlap inputs.  One GPU.
+ * One wavefront walks a row with up to 64 columns on its lanes, one 64-bit sum a lane; with more columns it repeats the row once per
+ * 64, which vtx_csr_dense_max() = 16 passes bounds.  No atomics, no zeroing pass, integer arithmetic only: the result is a function of
+ * the input alone.  Work space: the check's flag words only.  The call takes no struct: VTX_ABI_VERSION and vtx_abi_sizes are unchanged. */
+uint32_t vtx_csr_dense_max(void);    /* the largest n_cols accepted: 1024 (16 passes of a wavefront) */
+int vtx_csr_dense_sum(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, uint64_t nnz,
+                      const uint64_t* d_indptr, const uint32_t* d_indices,
+                      const uint32_t* d_alt, const uint32_t* d_ref,
+                      const int32_t* d_w_alt, const int32_t* d_w_ref, uint32_t n_cols,
+                      int64_t* d_out);
+
 /* Device time of the context's last CSR call that succeeded, in milliseconds, from events on the context's own stream.
  * vtx_device_csr / vtx_csr_transpose: ms[0] the check of the inputs, ms[1] the sort of the positions by column, ms[2] the offsets,
  * ms[3] the placement of the indices and payloads (vtx_device_csr: 1 and 3 are 0).  vtx_csr_row_stats: ms[0] the check, ms[3] the
@@ -685,7 +710,8 @@ int vtx_csr_geno_pair_tally(vtx_ctx* ctx, uint32_t n_major, uint32_t n_minor, ui
  * the placement (the plan: 2 and 3 are 0).  vtx_csr_group_plan / vtx_csr_group_sum: ms[0] the checks of the CSR and of the labels,
  * ms[1] the count and its scan, ms[3] the fill (2 is 0; the plan: 3 is 0 too).  vtx_csr_geno_tally: ms[0] the checks of the CSR and
  * of the genotype table, ms[3] the tally (1 and 2 are 0).  vtx_csr_geno_pair_tally: ms[0] the checks of the CSR, the table and the
- * pairs, ms[3] the tally (1 and 2 are 0).  Writes the first n of the four, at most four.                                              */
+ * pairs, ms[3] the tally (1 and 2 are 0).  vtx_csr_dense_sum: ms[0] the check of the CSR, ms[3] the sum (1 and 2 are 0).  Writes the
+ * first n of the four, at most four.                                                                                                  */
 int vtx_last_csr_ms(vtx_ctx* ctx, float* ms, uint32_t n);
 
 /* ---- Multi-GPU: one process (one ctx) per GPU, loci sharded over the ranks (src/main.rs:284-291: chunks of loci

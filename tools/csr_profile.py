@@ -38,7 +38,14 @@ GPU box:   python tools/csr_profile.py --geno --json profiles/r22_csr_geno.json
 64 donors (a list of 64 pairs), each result compared with a numpy model before it is timed, next to (a) vtx_csr_geno_tally on the same CSR
 and table — the cost of a (entry, donor) slot against that of a (entry, pair) slot — and (b) torch on the device (rows by
 repeat_interleave, per pair two gathered genotype columns, the dosage, three index_add_ into a dense buffer of the output's size).
-GPU box:   python tools/csr_profile.py --pairs --json profiles/r25_csr_geno_pair.json"""
+GPU box:   python tools/csr_profile.py --pairs --json profiles/r25_csr_geno_pair.json
+
+--dense measures the CSR x integer-table sum (vtx_csr_dense_sum) on --geno's CSR and on its transpose at 8, 16 and 64 columns — the call
+with both tables (the E-step's shape) and the two single-table calls (the M-step's) — each result compared with a float64 matmul on the
+host before it is timed, next to (b) torch on the device: two torch.sparse.mm of float64 CSR copies against float64 tables (or, where this
+build has no device CSR x dense product, --geno's gather + index_add_ form; the record says which).  It ends with one whole
+api.cluster_donors at that shape with k = 8 and one restart.
+GPU box:   python tools/csr_profile.py --dense --json profiles/r27_csr_dense.json"""
 import argparse
 import json
 import os
@@ -70,6 +77,7 @@ ap.add_argument("--sweep", action="store_true", help="time csr_row_stats_kernel 
 ap.add_argument("--group", action="store_true", help="measure vtx_csr_group_plan / vtx_csr_group_sum on synthetic CSRs, no batch")
 ap.add_argument("--geno", action="store_true", help="measure vtx_csr_geno_tally on a synthetic cell-major CSR, no batch")
 ap.add_argument("--pairs", action="store_true", help="measure vtx_csr_geno_pair_tally on --geno's synthetic cell-major CSR, no batch")
+ap.add_argument("--dense", action="store_true", help="measure vtx_csr_dense_sum on --geno's synthetic CSR in both orientations, no batch")
 args = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -447,6 +455,120 @@ if args.pairs:
                   E["ns_per_entry_donor"], "torch", E["torch_gather_index_add_dense"].get("host_wall_ms_median", E["torch_gather_index_add_dense"].get("error")),
                   flush=True)
             del out, table, cls, pairs
+    finish(res)
+    sys.exit(0)
+
+if args.dense:
+    n_cell, n_var, mean = args.barcodes, args.loci, 2392.3 * args.loci / 100_000
+    res = {"what": "vtx_csr_dense_sum (tools/csr_profile.py --dense): median of %d after one warm-up, one process; --geno's synthetic cell-major "
+                   "CSR (Poisson row lengths, uniform random columns, counts 0 - 2) and its transpose, int32 tables uniform in [-2^20, 2^20); every "
+                   "result compared with a float64 matmul on the host (the sums stay below 2^53) before it is timed; device ms by phase from "
+                   "vtx_last_csr_ms" % args.runs, "dense_max": lib.load().vtx_csr_dense_max(), "library": os.path.basename(lib.LIB_PATH), "shapes": {}}
+    gen = torch.Generator(device=dev).manual_seed(11)
+    with lib.Context(default_config(n_barcodes=4)) as ctx:
+        lens = torch.poisson(torch.full((n_cell,), mean, device=dev), generator=gen).clamp_(max=n_var).to(torch.int64)
+        indptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(lens, 0)])
+        nnz = int(indptr[-1])
+        cells = {"indptr": indptr, "indices": torch.randint(0, n_var, (nnz,), dtype=torch.int32, device=dev, generator=gen)}
+        for k in ("alt", "ref"):
+            cells[k] = torch.randint(0, 3, (nnz,), dtype=torch.int32, device=dev, generator=gen)
+        variants = api._transpose(ctx, torch, dev, cells, n_cell, n_var, ("alt", "ref"))
+        res.update({"n_cells": n_cell, "n_variants": n_var, "nnz": nnz})
+        for name, csr, n_major, n_minor in (("cells_x_variants", cells, n_cell, n_var), ("variants_x_cells", variants, n_var, n_cell)):
+            host = {k: v.cpu().numpy() for k, v in csr.items()}
+            mats = [sp.csr_matrix((host[k].astype(np.float64), host["indices"], host["indptr"]), shape=(n_major, n_minor)) for k in ("alt", "ref")]
+            rows = torch.repeat_interleave(torch.arange(n_major, device=dev), csr["indptr"][1:] - csr["indptr"][:-1])
+            cols = csr["indices"].to(torch.int64)
+            one = {"n_major": n_major, "n_minor": n_minor, "n_cols": {}}
+            for n_cols in (8, 16, 64):
+                w = [torch.randint(-(1 << 20), 1 << 20, (n_minor, n_cols), dtype=torch.int32, device=dev, generator=gen) for _ in range(2)]
+                out = torch.empty((n_major, n_cols), dtype=torch.int64, device=dev)
+                torch.cuda.synchronize(dev)
+
+                def call(w_alt, w_ref):
+                    return lambda: ctx.csr_dense_sum(n_major, n_minor, nnz, csr["indptr"].data_ptr(), csr["indices"].data_ptr(), csr["alt"].data_ptr(),
+                                                     csr["ref"].data_ptr(), w_alt.data_ptr() if w_alt is not None else 0,
+                                                     w_ref.data_ptr() if w_ref is not None else 0, n_cols, out.data_ptr())
+                calls = {"both_tables": call(*w), "w_alt_only": call(w[0], None), "w_ref_only": call(None, w[1])}
+                # ---- correctness first: float64 matmuls on the host, exact below 2^53 ----
+                want = [m @ t.cpu().numpy().astype(np.float64) for m, t in zip(mats, w)]
+                assert max(float(np.abs(x).max()) for x in want) * 2 < 1 << 53
+                for key, model in (("both_tables", want[0] + want[1]), ("w_alt_only", want[0]), ("w_ref_only", want[1])):
+                    out.fill_(-1)
+                    torch.cuda.synchronize(dev)
+                    calls[key]()
+                    assert np.array_equal(out.cpu().numpy(), model.astype(np.int64)), (name, n_cols, key)
+                print("%s, %d columns: equals the float64 matmul on the host" % (name, n_cols), flush=True)
+                E = {key: series(fn, ctx.csr_ms) for key, fn in calls.items()}
+                for key in calls:
+                    tables = 2 if key == "both_tables" else 1
+                    E[key]["ps_per_entry_column"] = round(E[key]["device_ms_by_phase_median"]["place"] * 1e9 / (nnz * n_cols), 3)
+                    E[key]["ps_per_entry_column_table"] = round(E[key]["ps_per_entry_column"] / tables, 3)
+                # (b) torch on the device: two torch.sparse.mm of float64 CSR copies against float64 tables; where this build has no device
+                # CSR x dense product, --geno's form: rows by repeat_interleave, a gather of the table rows, index_add_ into a dense buffer
+                wf = [t.to(torch.float64) for t in w]
+                both = calls["both_tables"]
+                both()
+                mine = out.to(torch.float64)
+
+                def torch_spmm():
+                    o = torch.sparse.mm(spm[0], wf[0]) + torch.sparse.mm(spm[1], wf[1])
+                    torch.cuda.synchronize(dev)
+                    return o
+
+                def torch_index_add():
+                    o = torch.zeros((n_major, n_cols), dtype=torch.float64, device=dev)
+                    for counts, t in zip((csr["alt"], csr["ref"]), wf):
+                        o.index_add_(0, rows, counts.to(torch.float64)[:, None] * t[cols])
+                    torch.cuda.synchronize(dev)
+                    return o
+                try:
+                    spm = [torch.sparse_csr_tensor(csr["indptr"], cols, csr[k].to(torch.float64), size=(n_major, n_minor)) for k in ("alt", "ref")]
+                    assert torch.equal(torch_spmm(), mine)
+                    E["torch_sparse_mm_f64"] = series(torch_spmm)
+                    baseline = "torch_sparse_mm_f64"
+                    del spm
+                except Exception as e:                           # noqa: BLE001  (the record IS the error)
+                    E["torch_sparse_mm_f64"] = {"error": "%s: %s" % (type(e).__name__, str(e).splitlines()[0][:200] if str(e) else "")}
+                    baseline = "torch_gather_index_add_f64"
+                    try:
+                        assert torch.equal(torch_index_add(), mine)
+                        E[baseline] = series(torch_index_add)
+                    except Exception as e2:                      # noqa: BLE001
+                        E[baseline] = {"error": "%s: %s" % (type(e2).__name__, str(e2).splitlines()[0][:200] if str(e2) else "")}
+                E["torch_baseline"] = baseline
+                if "host_wall_ms_median" in E[baseline]:
+                    E["torch_over_call"] = round(E[baseline]["host_wall_ms_median"] / E["both_tables"]["host_wall_ms_median"], 2)
+                one["n_cols"][str(n_cols)] = E
+                print(name, n_cols, {key: (E[key]["host_wall_ms_median"], E[key]["device_ms_by_phase_median"]["place"], E[key]["ps_per_entry_column"])
+                                     for key in calls}, baseline, E[baseline].get("host_wall_ms_median", E[baseline].get("error")), flush=True)
+                del w, wf, out, mine, want
+            res["shapes"][name] = one
+            del host, mats, rows, cols
+        del variants
+    # one whole clustering at this shape, of the torch result run(to="torch") would hand over.  The uniform counts above carry no donors
+    # (at 2 400 entries a cell a random start is a fixed point of the EM at once: a cell's own reads dominate its cluster's theta), so
+    # eight donors are planted on the same sparsity: genotypes uniform in {0, 1, 2}, depth 1 - 3, alt reads binomial at 0.01 / 0.5 / 0.99
+    k = 8
+    donor = torch.arange(n_cell, device=dev) % k
+    rows = torch.repeat_interleave(torch.arange(n_cell, device=dev), cells["indptr"][1:] - cells["indptr"][:-1])
+    geno = torch.randint(0, 3, (n_var, k), device=dev, generator=gen)
+    p_alt = torch.tensor([0.01, 0.5, 0.99], dtype=torch.float64, device=dev)[geno[cells["indices"].to(torch.int64), donor[rows]]]
+    depth = torch.randint(1, 4, (nnz,), device=dev, generator=gen)
+    alt = torch.binomial(depth.to(torch.float64), p_alt, generator=gen).to(torch.int32)
+    counts = {"alt": alt, "ref": depth.to(torch.int32) - alt}
+    del rows, geno, p_alt
+    as_csr = [torch.sparse_csr_tensor(cells["indptr"], cells["indices"].to(torch.int64), counts[f], size=(n_cell, n_var)) for f in ("alt", "ref")]
+    result = api.Result(matrix=None, ref_matrix=None, alt_counts=as_csr[0], ref_counts=as_csr[1], unknown_counts=None, variants=[""] * n_var,
+                        barcodes=[""] * n_cell, metrics={}, shape=(n_cell, n_var), orient="cells")
+    timed(lambda: api.cluster_donors(result, k, n_init=1, max_iter=1))      # warm-up: torch's kernels, the allocator
+    wall, c = timed(lambda: api.cluster_donors(result, k, n_init=1))
+    pairs = set(zip(donor.cpu().tolist(), c.labels.cpu().tolist()))
+    res["cluster_donors"] = {"k": k, "n_init": 1, "rounds": c.n_iter, "converged": c.converged, "total_ms": round(wall, 1),
+                             "ms_per_round": round(wall / c.n_iter, 2), "plant_recovered": len(pairs) == k and len({b for _, b in pairs}) == k,
+                             "note": "one restart, after a warm-up call of one round; the total includes the bare context, one vtx_csr_transpose "
+                             "and the row sums of the guard; eight planted donors on the sparsity of the sums above"}
+    print("cluster_donors", res["cluster_donors"], flush=True)
     finish(res)
     sys.exit(0)
 

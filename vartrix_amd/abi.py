@@ -150,6 +150,16 @@ GENO_PAIR_CLASSES = 6               # VTX_GENO_PAIR_CLASSES: the dosage g_a + g_
 VtxGenoPairTally = VtxGenoTally
 
 
+def __getattr__(name):
+    """``abi.CSR_DENSE_MAX``: the largest column count vtx_csr_dense_sum takes, read from the library when first asked for (the
+    library is not loaded to import this module)."""
+    if name == "CSR_DENSE_MAX":
+        from . import lib
+        value = globals()[name] = int(lib.load().vtx_csr_dense_max())
+        return value
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 class VtxCsrStats(C.Structure):
     """vtx_csr_stats: where vtx_csr_row_stats stores the seven statistics of every row; a NULL pointer is not written."""
     _fields_ = [(k, C.POINTER(C.c_uint32)) for k in CSR_STAT_COUNTS] + [(k, C.POINTER(C.c_uint64)) for k in CSR_STAT_SUMS]

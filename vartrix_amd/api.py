@@ -23,6 +23,11 @@ for a scipy one; ``read_genotypes()`` reads the table from a VCF), and ``assign_
 ``doublet_tally()`` is the same for droplets of two donors: per (cell, pair of donors) the reads by the dosage of the pair's genotypes
 (``vtx_csr_geno_pair_tally``), and ``assign_doublets()`` scores the two-donor hypotheses next to the one-donor ones (50 : 50 mixtures).
 
+``weighted_sum()`` is the integer part of the models that know no genotype classes: the CSR times one or two tables of int32 weights per
+(variant, hypothesis), exact in int64 (``vtx_csr_dense_sum`` on the device for a torch result, scipy on the host for a scipy one), and
+``cluster_donors()`` is genotype-free clustering on top of it: a soft EM whose two halves are that sum in the two orientations, with
+the floating point between them in torch on the device (numpy for a scipy result).
+
 There is no CPU path: the scores, the calls, the offsets and the transpose are computed on the GPU; torch carries the device arrays
 (``__cuda_array_interface__``) and, for ``to="scipy"``, copies the finished arrays to the host.
 """
@@ -225,7 +230,7 @@ def _labels(groups, barcodes):
         n_unmatched = len(set(by_name) - set(barcodes))
         per_cell = [by_name.get(b) for b in barcodes]
     else:
-        per_cell = list(groups)
+        per_cell = groups.cpu().tolist() if _is_torch(groups) else list(groups)      # (a tensor: cluster_donors' labels of a torch result)
         if len(per_cell) != len(barcodes):
             raise ValueError("pseudobulk: %d labels for %d barcodes: one label per cell (None leaves the cell out)" % (len(per_cell), len(barcodes)))
     names = list({g for g in per_cell if g is not None})
@@ -766,8 +771,8 @@ def assign_donors(tally_or_result, genotypes=None, *, error=0.01) -> DonorAssign
     donor with the highest ``ll``, the lowest index on a tie, and -1 for a cell whose ``n_obs`` over the classes 0 - 2 is zero for every
     donor; ``margin`` is the best minus the second best, ``+inf`` with one donor.  ``error`` must lie in (0, 0.5).
 
-    Out of scope: ambient RNA, and clustering without genotypes (souporcell's and vireo's other modes).  Droplets of two donors are
-    ``doublet_tally``'s and ``assign_doublets``'."""
+    Droplets of two donors are ``doublet_tally``'s and ``assign_doublets``'; pools without genotypes (souporcell's and vireo's other
+    modes) are ``cluster_donors``'.  Out of scope: ambient RNA (a matter of other tables for ``weighted_sum``)."""
     if not 0.0 < float(error) < 0.5:
         raise ValueError("assign_donors: error %r: a probability in (0, 0.5)" % (error,))
     tally = tally_or_result
@@ -858,7 +863,8 @@ def doublet_tally(result: Result, genotypes, pairs=None, donors=None, *, to=None
     entries of the cell, by the dosage ``g_a + g_b`` (0 .. 4) of the pair's known genotypes at the entry's variant, and in class 5 where
     either donor has no call — the integer part of scoring the two-donor hypotheses, and what ``assign_doublets`` takes beside a
     ``DonorTally``.  The six classes assume the two cells of a droplet contribute reads in equal parts (50 : 50); other proportions
-    are out of scope, as are ambient RNA and clustering without genotypes.
+    are out of scope, as is ambient RNA (both are a matter of other tables for ``weighted_sum``); clustering without genotypes is
+    ``cluster_donors``'.
 
     ``genotypes``, ``donors``: as for ``donor_tally``.  ``pairs``: integers of n_pairs x 2, indices into the donors; any list is
     allowed — duplicates, both orders, ``(a, a)``, which carries donor a's one-donor tally on the classes 0, 2, 4.  ``None`` means every
@@ -914,7 +920,8 @@ def assign_doublets(singlets: DonorTally, doublets: DoubletTally, *, error=0.01,
     ``assign_donors``' donor; ``best_pair`` the pair with the highest ``ll2``, the lowest index on a tie.  Without pairs ``best_pair``
     is -1 and ``log_odds`` is -inf: no doublet hypothesis was scored.  ``error`` must lie in (0, 0.5), ``doublet_prior`` in (0, 1).
 
-    Out of scope: mixtures other than 50 : 50, ambient RNA, and clustering without genotypes."""
+    Out of scope: mixtures other than 50 : 50 and ambient RNA (both a matter of other tables for ``weighted_sum``).  Clustering without
+    genotypes is ``cluster_donors``'."""
     if not 0.0 < float(error) < 0.5:
         raise ValueError("assign_doublets: error %r: a probability in (0, 0.5)" % (error,))
     if not 0.0 < float(doublet_prior) < 1.0:
@@ -940,3 +947,304 @@ def assign_doublets(singlets: DonorTally, doublets: DoubletTally, *, error=0.01,
     kind[one.best < 0] = -1
     return DoubletAssignment(kind=kind, best=one.best, best_pair=best_pair, log_odds=log_odds, log_lik_pairs=ll2,
                              pairs=np.asarray(doublets.pairs), donors=list(doublets.donors), barcodes=list(doublets.barcodes))
+
+
+SCORE_SCALE = 2 ** 20          # S: a log-probability as an int32 weight is rint(S * log p)
+RESP_SCALE = 2 ** 15           # Q: a responsibility as an int32 weight is rint(Q * r), r in [0, 1]
+CLUSTER_MAX = 64               # the dense theta table of cluster_donors is the limit, not the kernel (abi.CSR_DENSE_MAX columns)
+
+
+@dataclass
+class DonorClusters:
+    """Cells clustered by donor without genotypes (``cluster_donors``): numpy arrays, or torch tensors on the result's device."""
+    labels: object            # int64 per cell: the cluster with the highest score, the lowest index on a tie; -1 for a cell without a read
+    resp: object              # float64, cells x k: the responsibilities rq / RESP_SCALE; rows of cells without a read are 0
+    score: object             # int64, cells x k: the last round's fixed-point log-likelihoods, weighted_sum(w_alt, w_ref)
+    theta: object             # float64, variants x k: the alt probability of every variant in every cluster
+    w_alt: object             # int32, variants x k: rint(SCORE_SCALE * log(theta)), the table ``score`` was summed with
+    w_ref: object             # int32, variants x k: rint(SCORE_SCALE * log1p(-theta))
+    log_lik: float            # the sum over the cells with a read of logsumexp(score / SCORE_SCALE)
+    n_iter: int               # rounds of the winning restart
+    converged: bool           # ... which ended below ``tol``
+    restart: int              # the winning restart
+    barcodes: list
+    variants: list
+
+
+def _orient(result):
+    n_var, n_cell = len(result.variants), len(result.barcodes)
+    return result.orient or ("cells" if tuple(result.shape) == (n_cell, n_var) != (n_var, n_cell) else "variants")
+
+
+def _dense_table(w, n_rows, what, torch=None, dev=None):
+    """A table of weights as a C-contiguous int32 array of ``n_rows`` x columns: numpy, or a tensor on ``dev`` when ``torch`` is given."""
+    if w is None:
+        return None
+    if _is_torch(w):
+        if str(w.dtype) != "torch.int32":
+            raise ValueError("weighted_sum: %s is %s: the tables are int32" % (what, w.dtype))
+        w = w.to(dev).contiguous() if torch is not None else np.ascontiguousarray(w.cpu().numpy())
+    else:
+        w = np.asarray(w)
+        if w.dtype != np.int32:
+            raise ValueError("weighted_sum: %s is %s: the tables are int32" % (what, w.dtype))
+        w = torch.from_numpy(np.ascontiguousarray(w)).to(dev) if torch is not None else np.ascontiguousarray(w)
+    if w.ndim != 2 or w.shape[0] != n_rows:
+        raise ValueError("weighted_sum: %s of shape %s: %d rows (one per variant for over=\"cells\", per cell for over=\"variants\"), one column per hypothesis"
+                         % (what, tuple(w.shape), n_rows))
+    return w
+
+
+def _dense_guard(w_alt, w_ref, max_row):
+    """The guard against a wrapped sum: no |sum| can reach 2^63 when max|w| * (the largest row's alt + ref reads) stays below it."""
+    most = 0
+    for w in (w_alt, w_ref):
+        if w is not None and w.shape[0] and w.shape[1]:
+            most = max(most, -int(w.min()), int(w.max()))
+    if most * max_row >= 1 << 63:
+        raise ValueError("weighted_sum: max|w| = %d times the %d reads of the largest row reaches 2^63: the 64-bit sum could wrap" % (most, max_row))
+
+
+def _dense_operand_host(result, over):
+    """The alt and ref counts of a scipy result as int64 matrices whose rows are what ``over`` names, and the largest row's reads."""
+    import scipy.sparse as sp
+    alt, ref = (sp.csr_matrix(m).astype(np.int64) for m in (result.alt_counts, result.ref_counts))
+    if _orient(result) != over:
+        alt, ref = sp.csr_matrix(alt.T), sp.csr_matrix(ref.T)
+    rows = np.asarray(alt.sum(axis=1)).reshape(-1) + np.asarray(ref.sum(axis=1)).reshape(-1)
+    return (alt, ref), rows
+
+
+def _dense_sum_host(op, w_alt, w_ref, n_cols):
+    """scipy's sparse x dense product in int64: exact wherever the guard held."""
+    out = np.zeros((op[0].shape[0], n_cols), np.int64)
+    for m, w in zip(op, (w_alt, w_ref)):
+        if w is not None:
+            out += np.asarray(m @ w.astype(np.int64)).reshape(out.shape)
+    return out
+
+
+def _dense_operands_device(ctx, torch, dev, result, overs):
+    """The alt and ref counts of a torch result as the CSR arrays vtx_csr_dense_sum takes, in each orientation of ``overs`` (one
+    ``vtx_csr_transpose`` for the orientation the result does not have) -> {over: (csr, n_major, n_minor, reads per row (int64))}."""
+    csr, _ = _tally_csr("weighted_sum", result, torch)
+    csr = {k: v.contiguous() for k, v in csr.items()}
+    n_var, n_cell = len(result.variants), len(result.barcodes)
+    have = _orient(result)
+    size = {"variants": (n_var, n_cell), "cells": (n_cell, n_var)}
+    out = {}
+    for over in overs:
+        c = csr if over == have else _transpose(ctx, torch, dev, csr, *size[have], ("alt", "ref"))
+        reads = (c["alt"].to(torch.int64) & 0xFFFFFFFF) + (c["ref"].to(torch.int64) & 0xFFFFFFFF)
+        upto = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(reads, 0)])
+        out[over] = (c, size[over][0], size[over][1], upto[c["indptr"][1:]] - upto[c["indptr"][:-1]])
+    return out
+
+
+def _dense_sum_device(ctx, torch, dev, op, w_alt, w_ref, n_cols):
+    """One ``vtx_csr_dense_sum`` -> an int64 tensor of n_major x n_cols.  The tables are int32 tensors on ``dev``, C-contiguous."""
+    csr, n_major, n_minor, _ = op
+    out = torch.empty((n_major, n_cols), dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)              # the library works on its own stream: torch's writes to the tables have to be done
+    ctx.csr_dense_sum(n_major, n_minor, int(csr["indices"].shape[0]), csr["indptr"].data_ptr(), csr["indices"].data_ptr(), csr["alt"].data_ptr(),
+                      csr["ref"].data_ptr(), 0 if w_alt is None else w_alt.data_ptr(), 0 if w_ref is None else w_ref.data_ptr(), n_cols, out.data_ptr())
+    return out
+
+
+def _bare_context(torch, dev, n_cell):
+    index = torch.cuda.current_device() if dev.index is None else dev.index
+    return lib.Context(abi.default_config(n_barcodes=max(n_cell, 1), device=index))      # no batch, no run: device, stream, work space
+
+
+def weighted_sum(result: Result, w_alt=None, w_ref=None, *, over="cells", to=None):
+    """The integer part of every likelihood that depends on the variant through more than a genotype class — a free alt probability
+    per (variant, cluster), an ambient profile, an unequal mixture: with ``over="cells"``, per cell c and column h,
+
+        out[c, h] = sum over the cell's entries (c, v) of  alt[c, v] * w_alt[v, h] + ref[c, v] * w_ref[v, h]
+
+    from tables of ``len(result.variants)`` x n_cols; with ``over="variants"`` the same per variant, from tables of
+    ``len(result.barcodes)`` x n_cols.  The tables are int32 (fixed-point: ``rint(SCORE_SCALE * log p)``, say), numpy or torch; one
+    of them may be ``None`` and its term is then absent.  -> int64, cells (variants) x n_cols.
+
+    A torch result is summed on its device — one ``vtx_csr_dense_sum`` on a bare context for that device (at most
+    ``abi.CSR_DENSE_MAX`` columns, fewer than 2^32 entries), after one ``vtx_csr_transpose`` of the alt and ref counts when the result's
+    rows are not what ``over`` names — into a tensor, or into a numpy array with ``to="scipy"``; a scipy result is summed on the host
+    in int64.  Zero columns give an empty array without a library call.  The library's sum wraps modulo 2^64; this raises
+    ``ValueError`` when ``max|w|`` times the alt + ref reads of the largest row reaches 2^63, so what it returns never wrapped.
+
+    ``cluster_donors`` is built from this; ambient RNA and unequal mixtures are a matter of other tables and are not built here."""
+    if over not in ("cells", "variants"):
+        raise ValueError("weighted_sum: over %r: cells or variants" % (over,))
+    if to not in (None, "scipy", "torch"):
+        raise ValueError("to %r: scipy, torch, or None for the container of the result" % (to,))
+    if w_alt is None and w_ref is None:
+        raise ValueError("weighted_sum: w_alt, w_ref or both")
+    n_var, n_cell = len(result.variants), len(result.barcodes)
+    n_rows, n_table = (n_cell, n_var) if over == "cells" else (n_var, n_cell)
+    on_device = _is_torch(result.alt_counts)
+    if not on_device and to == "torch":
+        raise ValueError("weighted_sum: a scipy result is summed on the host; to=\"torch\" needs a torch result (run(to=\"torch\"))")
+    torch = dev = None
+    if on_device:
+        import torch
+        dev = result.alt_counts.device
+    w_alt, w_ref = _dense_table(w_alt, n_table, "w_alt", torch, dev), _dense_table(w_ref, n_table, "w_ref", torch, dev)
+    n_cols = int((w_alt if w_alt is not None else w_ref).shape[1])
+    if w_alt is not None and w_ref is not None and tuple(w_alt.shape) != tuple(w_ref.shape):
+        raise ValueError("weighted_sum: w_alt of shape %s and w_ref of shape %s" % (tuple(w_alt.shape), tuple(w_ref.shape)))
+    if not on_device:
+        if not n_cols:
+            return np.zeros((n_rows, 0), np.int64)
+        op, rows = _dense_operand_host(result, over)
+        _dense_guard(w_alt, w_ref, int(rows.max()) if len(rows) else 0)
+        return _dense_sum_host(op, w_alt, w_ref, n_cols)
+    if not n_cols:                               # nothing to sum, and the library takes no table without columns
+        out = torch.zeros((n_rows, 0), dtype=torch.int64, device=dev)
+    else:
+        if n_cols > abi.CSR_DENSE_MAX:
+            raise ValueError("weighted_sum: %d columns: at most %d" % (n_cols, abi.CSR_DENSE_MAX))
+        with _bare_context(torch, dev, n_cell) as ctx:
+            op = _dense_operands_device(ctx, torch, dev, result, (over,))[over]
+            _dense_guard(w_alt, w_ref, int(op[3].max()) if n_rows else 0)
+            out = _dense_sum_device(ctx, torch, dev, op, w_alt, w_ref, n_cols)
+    return out.cpu().numpy() if to == "scipy" else out
+
+
+def _m_step_tables(A, R, prior):
+    """The M-step's floating point, float64 in numpy or in torch (on the tensors' device), from the exact weighted reads A and R (int64,
+    variants x k): theta = (A / Q + prior[0]) / ((A + R) / Q + prior[0] + prior[1]), and the int32 tables rint(S log theta), rint(S
+    log1p(-theta)).  -> (theta, w_alt, w_ref)"""
+    q, s = float(RESP_SCALE), float(SCORE_SCALE)
+    if _is_torch(A):
+        import torch
+        theta = (A.to(torch.float64) / q + prior[0]) / ((A + R).to(torch.float64) / q + (prior[0] + prior[1]))
+        return theta, torch.round(s * torch.log(theta)).to(torch.int32), torch.round(s * torch.log1p(-theta)).to(torch.int32)
+    theta = (A.astype(np.float64) / q + prior[0]) / ((A + R).astype(np.float64) / q + (prior[0] + prior[1]))
+    return theta, np.rint(s * np.log(theta)).astype(np.int32), np.rint(s * np.log1p(-theta)).astype(np.int32)
+
+
+def _e_step_resp(score, live):
+    """The E-step's floating point: rq' = rint(Q softmax(score / S)) per live cell (the row maximum subtracted first), 0 for the
+    others, and the log-likelihood sum over the live cells of logsumexp(score / S).  -> (rq' int32, log_lik float)"""
+    q, s = float(RESP_SCALE), float(SCORE_SCALE)
+    if _is_torch(score):
+        import torch
+        x = score.to(torch.float64) / s
+        top = x.max(dim=1, keepdim=True).values
+        e = torch.exp(x - top)
+        total = e.sum(dim=1, keepdim=True)
+        rq = torch.round(q * (e / total)).to(torch.int32) * live.to(torch.int32)[:, None]
+        return rq, float(((top + torch.log(total))[:, 0] * live.to(torch.float64)).sum())
+    x = score.astype(np.float64) / s
+    top = x.max(axis=1, keepdims=True)
+    e = np.exp(x - top)
+    total = e.sum(axis=1, keepdims=True)
+    rq = np.rint(q * (e / total)).astype(np.int32) * live.astype(np.int32)[:, None]
+    return rq, float(((top + np.log(total))[:, 0] * live.astype(np.float64)).sum())
+
+
+def cluster_donors(result: Result, k, *, n_init=8, max_iter=100, tol=2 ** -10, prior=(1.0, 1.0), seed=0, to=None) -> DonorClusters:
+    """Cluster the cells of a pool by donor WITHOUT genotypes (souporcell's and vireo's default mode): a soft EM over a free alt
+    probability ``theta`` per (variant, cluster), whose integer parts are two ``weighted_sum``s.  With ``S = SCORE_SCALE`` and ``Q =
+    RESP_SCALE``:
+
+    A cell is live when it has an entry with ``alt + ref > 0``; the others keep responsibilities 0 and the label -1.  Restart ``t`` of
+    ``n_init`` draws ``lab = np.random.default_rng([seed, t]).integers(0, k, n_cells)`` for all cells in barcode order and sets ``rq[c,
+    lab[c]] = Q`` for the live ones (``rq``: int32, cells x k).  A round is
+
+        A = weighted_sum(w_alt=rq, over="variants");  R = weighted_sum(w_ref=rq, over="variants")              exact int64
+        theta = (A / Q + prior[0]) / ((A + R) / Q + prior[0] + prior[1])                                      float64
+        w_alt = rint(S * log(theta));  w_ref = rint(S * log1p(-theta))                                        int32
+        score = weighted_sum(w_alt, w_ref, over="cells")                                                      exact int64
+        rq' = rint(Q * softmax(score / S)) per live cell, the row maximum subtracted first                    int32
+
+    and the restart stops when ``max |rq' - rq| <= tol * Q``, or after ``max_iter`` rounds.  ``log_lik`` is the sum over the live
+    cells of ``logsumexp(score / S)``; the restart with the highest wins, the lowest ``t`` on a tie.  ``labels`` is the argmax of the
+    winner's ``score``, the lowest cluster on a tie, and is accepted as ``groups`` by ``pseudobulk`` (the cells without a read form
+    the group -1).
+
+    On a torch result the sums are ``vtx_csr_dense_sum`` calls on one bare context, after one ``vtx_csr_transpose``, and the floating
+    point between them is torch float64 on the device: the CSR, the tables and the scores never leave it between rounds (one number,
+    the convergence test, does).  On a scipy result everything is numpy.  The integer sums are exact either way; the float64 steps of
+    the two may differ in the last bit, and with them a table entry by one unit.  -> ``DonorClusters`` of tensors, or of numpy arrays
+    for a scipy result and with ``to="scipy"``.
+
+    ``k`` must lie in 1 .. 64.  Out of scope: ambient RNA and unequal mixtures (other tables for ``weighted_sum``), more than 64
+    clusters, several GPUs."""
+    if int(k) != k or k < 1:
+        raise ValueError("cluster_donors: k %r: at least one cluster" % (k,))
+    if k > CLUSTER_MAX:
+        raise ValueError("cluster_donors: %d clusters: at most %d (theta is a dense variants x k table)" % (k, CLUSTER_MAX))
+    k = int(k)
+    if n_init < 1 or max_iter < 1:
+        raise ValueError("cluster_donors: n_init %r, max_iter %r: at least one restart and one round" % (n_init, max_iter))
+    prior = (float(prior[0]), float(prior[1]))
+    if not (prior[0] > 0.0 and prior[1] > 0.0):
+        raise ValueError("cluster_donors: prior %r: two positive pseudo-counts" % (prior,))
+    if to not in (None, "scipy", "torch"):
+        raise ValueError("to %r: scipy, torch, or None for the container of the result" % (to,))
+    on_device = _is_torch(result.alt_counts)
+    if not on_device and to == "torch":
+        raise ValueError("cluster_donors: a scipy result is clustered on the host; to=\"torch\" needs a torch result (run(to=\"torch\"))")
+    n_var, n_cell = len(result.variants), len(result.barcodes)
+
+    def em(sum_over, as_table, live):
+        """Every restart: sum_over(over, w_alt, w_ref) is the guarded sum, as_table(numpy int32) an array where the sums run, ``live``
+        the live cells there.  -> the winner's state"""
+        live_host = np.asarray(live.cpu() if _is_torch(live) else live)
+        best = None
+        for t in range(int(n_init)):
+            lab = np.random.default_rng([seed, t]).integers(0, k, n_cell)
+            first = np.zeros((n_cell, k), np.int32)
+            first[np.arange(n_cell), lab] = RESP_SCALE
+            rq = as_table(first * live_host.astype(np.int32)[:, None])
+            converged = False
+            for n_iter in range(1, int(max_iter) + 1):
+                A, R = sum_over("variants", rq, None), sum_over("variants", None, rq)
+                theta, w_alt, w_ref = _m_step_tables(A, R, prior)
+                score = sum_over("cells", w_alt, w_ref)
+                new, log_lik = _e_step_resp(score, live)
+                delta = int(abs(new - rq).max()) if n_cell else 0
+                rq = new
+                if delta <= tol * RESP_SCALE:
+                    converged = True
+                    break
+            if best is None or log_lik > best["log_lik"]:
+                best = dict(rq=rq, score=score, theta=theta, w_alt=w_alt, w_ref=w_ref, log_lik=log_lik, n_iter=n_iter, converged=converged, restart=t)
+        return best
+
+    if on_device:
+        import torch
+        dev = result.alt_counts.device
+        with _bare_context(torch, dev, n_cell) as ctx:
+            ops = _dense_operands_device(ctx, torch, dev, result, ("cells", "variants"))
+            most = {over: int(op[3].max()) if op[1] else 0 for over, op in ops.items()}
+            live = ops["cells"][3] > 0
+
+            def sum_over(over, w_alt, w_ref):
+                _dense_guard(w_alt, w_ref, most[over])
+                w_alt, w_ref = (None if w is None else w.contiguous() for w in (w_alt, w_ref))
+                return _dense_sum_device(ctx, torch, dev, ops[over], w_alt, w_ref, k)
+            best = em(sum_over, lambda a: torch.from_numpy(a).to(dev), live)
+        score = best["score"]
+        ranks = torch.arange(k, dtype=torch.int64, device=dev)[None, :].expand(n_cell, k)
+        labels = torch.where(score == score.max(dim=1, keepdim=True).values, ranks, k).min(dim=1).values      # the lowest index on a tie
+        labels = torch.where(live, labels, -1)
+        resp = best["rq"].to(torch.float64) / float(RESP_SCALE)
+        fields = dict(labels=labels, resp=resp, score=score, theta=best["theta"], w_alt=best["w_alt"], w_ref=best["w_ref"])
+        if to == "scipy":
+            fields = {f: v.cpu().numpy() for f, v in fields.items()}
+    else:
+        ops = {over: _dense_operand_host(result, over) for over in ("cells", "variants")}
+        most = {over: int(rows.max()) if len(rows) else 0 for over, (_, rows) in ops.items()}
+        live = ops["cells"][1] > 0
+
+        def sum_over(over, w_alt, w_ref):
+            _dense_guard(w_alt, w_ref, most[over])
+            return _dense_sum_host(ops[over][0], w_alt, w_ref, k)
+        best = em(sum_over, lambda a: a, live)
+        labels = np.where(live, np.argmax(best["score"], axis=1), -1).astype(np.int64)
+        fields = dict(labels=labels, resp=best["rq"].astype(np.float64) / float(RESP_SCALE), score=best["score"], theta=best["theta"],
+                      w_alt=best["w_alt"], w_ref=best["w_ref"])
+    return DonorClusters(**fields, log_lik=best["log_lik"], n_iter=best["n_iter"], converged=best["converged"], restart=best["restart"],
+                         barcodes=list(result.barcodes), variants=list(result.variants))

@@ -36,6 +36,7 @@
 #include "vtx_csr_group_core.h"
 #include "vtx_csr_geno_core.h"
 #include "vtx_csr_geno_pair_core.h"
+#include "vtx_csr_dense_core.h"
 #include "../../include/vtx_band_semantics.h"
 
 extern "C" hipError_t vtxk_inclusive_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, void* temp,
@@ -3179,6 +3180,32 @@ int vtx_csr_geno_pair_tally(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint
     HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_PLACE1], s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = csr_times(c, true, false, true, false)) return rc;      // the three checks and the tally: no sort, no offsets here
+    return VTX_OK;
+}
+
+// ---- CSR x integer tables: a caller's CSR against one or two tables of int32 weights per (minor, column), summed modulo 2^64
+// (include/vtx.h, vtx_csr_dense.hip) ----
+uint32_t vtx_csr_dense_max(void) { return vtxr::DENSE_MAX; }
+
+int vtx_csr_dense_sum(vtx_ctx* c, uint32_t n_major, uint32_t n_minor, uint64_t nnz, const uint64_t* d_indptr, const uint32_t* d_indices,
+                      const uint32_t* d_alt, const uint32_t* d_ref, const int32_t* d_w_alt, const int32_t* d_w_ref, uint32_t n_cols, int64_t* d_out) {
+    const char* who = "vtx_csr_dense_sum";
+    if (!c) return VTX_E_INVAL;
+    if (int rc = csr_positions_fit(c, who, nnz)) return rc;
+    if (!n_cols) return fail(c, VTX_E_INVAL, "%s: no columns", who);
+    if (n_cols > vtxr::DENSE_MAX)
+        return fail(c, VTX_E_UNSUPPORTED, "%s: %u columns: at most %u (%u passes of %u)", who, n_cols, vtxr::DENSE_MAX, vtxr::DENSE_MAX_PASSES, vtxr::GENO_WAVE);
+    if (!d_out || !d_indptr || (nnz && (!d_indices || !d_alt || !d_ref))) return fail(c, VTX_E_INVAL, "%s: null array", who);
+    if (n_minor && !d_w_alt && !d_w_ref) return fail(c, VTX_E_INVAL, "%s: null tables: w_alt, w_ref or both", who);
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    if (int rc = csr_checked(c, who, n_major, n_minor, nnz, d_indptr, d_indices)) return rc;
+    const vtx_dense_in in{d_indptr, n_major, d_indices, d_alt, d_ref, d_w_alt, d_w_ref, n_cols};
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_OFFSETS1], s));
+    HIP_TRY(c, vtxr_dense_sum(in, d_out, s));
+    HIP_TRY(c, hipEventRecord(c->csr.ev[EV_CSR_PLACE1], s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = csr_times(c, true, false, true, false)) return rc;      // the check and the sum: no sort, no offsets here
     return VTX_OK;
 }
 

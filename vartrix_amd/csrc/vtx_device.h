@@ -298,4 +298,12 @@ hipError_t vtxr_geno_pair_check(const uint32_t* pairs, uint32_t n_pairs, uint32_
 // the arrays of `out` (any of them NULL: not written) have n_major * n_pairs * 6 elements, each stored once
 hipError_t vtxr_geno_pair_tally(const vtx_geno_pair_in& in, const vtx_geno_pair_tally* out, hipStream_t s);
 }
+// ---- vtx_csr_dense.hip: a CSR times integer tables, summed modulo 2^64.  The CSR has passed vtxr_check; any int32 is a weight ----
+// the matrix and the tables as the kernel reads them: w_alt / w_ref[n_minor * n_cols], minor-major; either may be NULL (its term is
+// absent), both only where no row has an entry
+struct vtx_dense_in { const uint64_t* indptr; uint32_t n_major; const uint32_t* indices; const uint32_t *alt, *ref; const int32_t *w_alt, *w_ref; uint32_t n_cols; };
+extern "C" {
+// out has n_major * n_cols elements, each stored once
+hipError_t vtxr_dense_sum(const vtx_dense_in& in, int64_t* out, hipStream_t s);
+}
 #endif

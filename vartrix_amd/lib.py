@@ -44,6 +44,7 @@ SYMBOLS = (
     "vtx_csr_group_window", "vtx_csr_group_max", "vtx_csr_group_plan", "vtx_csr_group_sum",
     "vtx_csr_geno_max", "vtx_sizeof_geno_tally", "vtx_csr_geno_tally",
     "vtx_csr_geno_pair_max", "vtx_sizeof_geno_pair_tally", "vtx_csr_geno_pair_tally",
+    "vtx_csr_dense_max", "vtx_csr_dense_sum",
 )
 # (entry points with a digit in their name: tests/test_abi.py finds the header's declarations with [a-z_]+ and compares them with SYMBOLS,
 # so these are listed — and checked against the header and every build of the library, tests/test_abi_f64.py — on their own)
@@ -127,6 +128,10 @@ def load(variant=None):
     L.vtx_sizeof_geno_pair_tally.argtypes = []
     L.vtx_csr_geno_pair_tally.restype = C.c_int
     L.vtx_csr_geno_pair_tally.argtypes = csr_in + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(abi.VtxGenoPairTally)]
+    L.vtx_csr_dense_max.restype = C.c_uint32
+    L.vtx_csr_dense_max.argtypes = []
+    L.vtx_csr_dense_sum.restype = C.c_int
+    L.vtx_csr_dense_sum.argtypes = csr_in + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.vtx_sizeof_csr_stats.restype = C.c_uint32
     L.vtx_sizeof_csr_stats.argtypes = []
     L.vtx_last_csr_ms.restype = C.c_int
@@ -514,6 +519,15 @@ class Context:
         st = _out_struct(abi.VtxGenoPairTally, out, abi.GENO_TALLY_NAMES, "csr_geno_pair_tally", "outputs")
         self._check(self._L.vtx_csr_geno_pair_tally(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
                                                     ref or None, geno or None, int(n_donors), pairs or None, int(n_pairs), C.byref(st)))
+
+    def csr_dense_sum(self, n_major: int, n_minor: int, nnz: int, indptr: int, indices: int, alt: int, ref: int, w_alt: int, w_ref: int,
+                      n_cols: int, out: int):
+        """Every row of a CSR in device memory times one or two tables of int32 weights (vtx_csr_dense_sum): ``out[r * n_cols + h]`` =
+        the sum over the row's entries of ``alt * w_alt[index * n_cols + h] + ref * w_ref[index * n_cols + h]``, modulo 2^64.  ``w_alt``,
+        ``w_ref``: the addresses of n_minor * n_cols int32, minor-major; 0 leaves the term out (not both, unless n_minor is 0).  ``out``:
+        the address of n_major * n_cols int64, each written once.  At most ``abi.CSR_DENSE_MAX`` columns."""
+        self._check(self._L.vtx_csr_dense_sum(self._h, int(n_major), int(n_minor), int(nnz), indptr or None, indices or None, alt or None,
+                                              ref or None, w_alt or None, w_ref or None, int(n_cols), out or None))
 
     def comm_init(self, ident: bytes, rank: int, world: int):
         """Join the RCCL communicator of the sharded run (collective; vtx_comm_init)."""
