@@ -41,15 +41,16 @@ void build_table(uint8_t* tb, const uint8_t* hy, uint32_t hn, uint32_t max_hap, 
     // tags: a bucket with one entry carries 4 hash bits of its k-mer, a bucket with more HEAD_MULTI
     for (uint32_t h = 0; h < n_heads; ++h)
         if (count[h]) head[h] = (uint16_t)(head[h] | ((count[h] == 1 ? tag[h] : HEAD_MULTI) << 12));
-    for (uint32_t y = 0; y + 6 <= hn; ++y) {
+    // uniqueness flags; a haplotype with a byte >= 0x80 gets none (vtx_band.hip, build_tables: bit 7 of fb[] is the flag)
+    bool hib = false;
+    for (uint32_t y = 0; y < hn; ++y) hib |= (hy[y] & 0x80) != 0;
+    for (uint32_t y = 0; !hib && y + 6 <= hn; ++y) {
         uint32_t same = 0;
         for (uint32_t z = 0; z + 6 <= hn; ++z) same += memcmp(hy + y, hy + z, 6) == 0;
         if (same == 1) { uq[y >> 5] |= 1u << (y & 31); fb[y + 5] |= 0x80; }
     }
     // the twin list (vtx_fast_core.h: tab_tw_off): pairs (y, y') of positions with the same k-mer, in (y, y') order
     uint8_t* tw = tb + tab_tw_off(max_hap, n_heads);
-    bool hib = false;
-    for (uint32_t y = 0; y < hn; ++y) hib |= (hy[y] & 0x80) != 0;
     uint32_t cnt = 0;
     bool ok = !hib && hn <= 256;
     for (uint32_t y = 0; ok && y + 6 <= hn; ++y)
@@ -64,6 +65,43 @@ void build_table(uint8_t* tb, const uint8_t* hy, uint32_t hn, uint32_t max_hap, 
 }  // namespace
 
 extern "C" {
+// The mirror's tables themselves (tests/test_tables_model.py, tests/test_gpu_tables_model.py): build_table for REF and ALT of every
+// locus, table 2 * locus + hap at out + (2 * locus + hap) * stride — what vtx_debug_tables hands out for the device's, without t3[]
+// (the mirror builds none).  stride: at least tab_stride(max_hap, n_heads); max_hap: at least the batch's longest haplotype.
+int vtxt_build_tables(const vtx_batch* b, uint32_t n_heads, uint32_t max_hap, uint8_t* out, uint64_t stride) {
+    if (!n_heads || (n_heads & (n_heads - 1)) || stride < vtxf::tab_stride(max_hap, n_heads)) return -1;
+    for (uint32_t l = 0; l < b->n_loci; ++l)
+        if (std::max(b->loci[l].ref_len, b->loci[l].alt_len) > max_hap) return -2;
+    for (uint32_t l = 0; l < b->n_loci; ++l) {
+        const vtx_locus& L = b->loci[l];
+        build_table(out + (size_t)(2 * l) * stride, b->hap_arena + L.ref_off, L.ref_len, max_hap, n_heads);
+        build_table(out + (size_t)(2 * l + 1) * stride, b->hap_arena + L.alt_off, L.alt_len, max_hap, n_heads);
+    }
+    return 0;
+}
+// the header's own hash and code of the k-mer (bytes 0-3 in lo, bytes 4-5 in hi): out = kw_mix, kw_bucket, kw_tag, kw_code
+void vtxt_kw(uint32_t lo, uint32_t hi, uint32_t n_heads, uint32_t* out) {
+    out[0] = vtxf::kw_mix(lo, hi); out[1] = vtxf::kw_bucket(out[0], n_heads - 1); out[2] = vtxf::kw_tag(out[0]); out[3] = vtxf::kw_code(lo, hi);
+}
+// ... of n k-mers at once, and where each code sits in t3[]: out[10 * i ..] = the four above, then t3_word_a, t3_bit_a, .. t3_bit_c
+void vtxt_kw_many(const uint32_t* lo, const uint32_t* hi, uint32_t n, uint32_t n_heads, uint32_t* out) {
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t* o = out + 10 * (size_t)i;
+        vtxt_kw(lo[i], hi[i], n_heads, o);
+        const uint32_t c = o[3];
+        o[4] = vtxf::t3_word_a(c); o[5] = vtxf::t3_bit_a(c); o[6] = vtxf::t3_word_b(c); o[7] = vtxf::t3_bit_b(c);
+        o[8] = vtxf::t3_word_c(c); o[9] = vtxf::t3_bit_c(c);
+    }
+}
+// the header's layout: out = tab_bytes_off, tab_fb_off, tab_uq_off, tab_pb_off, tab_tw_off, tab_t3_off, tab_stride, then the constants
+// UQ_PAD_WORDS, HEAD_END, HEAD_MULTI, TW_MAX, TW_BYTES, TW_NONE, T3_BYTES
+void vtxt_tab_layout(uint32_t max_hap, uint32_t n_heads, uint32_t* out) {
+    using namespace vtxf;
+    const uint32_t v[14] = {tab_bytes_off(max_hap, n_heads), tab_fb_off(max_hap, n_heads), tab_uq_off(max_hap, n_heads), tab_pb_off(max_hap, n_heads),
+                            tab_tw_off(max_hap, n_heads), tab_t3_off(max_hap, n_heads), tab_stride(max_hap, n_heads),
+                            UQ_PAD_WORDS, HEAD_END, HEAD_MULTI, TW_MAX, TW_BYTES, TW_NONE, T3_BYTES};
+    memcpy(out, v, sizeof v);
+}
 // the closed forms and the corridor DP of the run bound, for unit tests against brute force (tests/test_fastcore.py)
 int vtxt_join_free(int D) { return vtxf::join_free(D); }
 int vtxt_join_same(int D, int e) { return vtxf::join_same(D, e); }

@@ -22,6 +22,7 @@ from vartrix_amd.abi import default_config
 
 import stress_batches as SB
 from audit_util import assert_stage_invariant, stage_report
+from tables_model import _defined_bytes, _table_layout, _uses_t3        # (their home since the tables have a model of their own)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -217,41 +218,6 @@ def _tables_and_scores(batch, nb, variant=None):
         ctx.submit(batch)
         ctx.run()
         return ctx.debug_tables(), ctx.fetch_scores()
-
-
-def _table_layout(max_hap, n_heads):
-    """vtx_fast_core.h: tab_bytes_off .. tab_stride."""
-    bytes_off = max_hap * 8 + n_heads * 2
-    fb_off = bytes_off + max_hap + 8
-    uq_off = (fb_off + max_hap + 8 + 3) & ~3
-    pb_off = uq_off + 4 * (8 + (max_hap + 31) // 32 + 8)
-    return bytes_off, fb_off, uq_off, pb_off, (pb_off + 512 + 128 + 2048 + 15) & ~15        # (round 6: tw[128], the twin list, and t3[2048], the three-row sets, behind pb[])
-
-
-def _defined_bytes(tables, batch, n_heads=1024):
-    """The bytes of the tables that MEAN something (entries of existing k-mers, head words, haplotype and flag bytes, the two
-    bitmaps), table by table; the gaps between them are whatever the LDS held."""
-    nl = batch.n_loci
-    stride = len(tables) // (2 * nl)
-    longest = int(max(batch.loci["ref_len"].max(), batch.loci["alt_len"].max()))
-    max_hap = next(m for m in range(longest, longest + 64) if _table_layout(m, n_heads)[4] == stride)
-    bytes_off, fb_off, uq_off, pb_off, _ = _table_layout(max_hap, n_heads)
-    out = []
-    for t in range(2 * nl):
-        tb = tables[t * stride:(t + 1) * stride]
-        hn = int(batch.loci["alt_len" if t & 1 else "ref_len"][t >> 1])
-        nk = max(hn - 5, 0)
-        out += [tb[:8 * nk], tb[max_hap * 8:bytes_off], tb[bytes_off:bytes_off + hn], tb[fb_off:fb_off + hn], tb[uq_off:pb_off + 512]]
-        tw = tb[pb_off + 512:pb_off + 640]
-        out += [tw[:1], tw[8:8 + 2 * (0 if tw[0] == 0xff else int(tw[0]))]]          # the twin list: its length, its pairs
-        if _uses_t3(batch):
-            out += [tb[pb_off + 640:pb_off + 640 + 2048]]                             # the three-row sets
-    return np.concatenate(out)
-
-
-def _uses_t3(batch):
-    """vtx_band.hip, band_use_t3: t3[] is built for batches of at least 16 tasks (8 reads) per locus on average."""
-    return (2 * batch.n_records) // max(batch.n_loci, 1) >= 16
 
 
 def _expected_t3_and_twins(hap):
