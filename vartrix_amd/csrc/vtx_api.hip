@@ -713,11 +713,7 @@ int make_buckets(vtx_ctx* c, const uint32_t* shape_cnt, uint32_t max_hap, uint32
     return VTX_OK;
 }
 
-uint32_t bits_for(uint64_t max_value) {   // bits needed to represent values 0..max_value
-    uint32_t b = 1;
-    while (b < 64 && (max_value >> b)) ++b;
-    return b;
-}
+using vtxp::bits_for;   // bits needed to represent values 0..max_value (vtx_prep_core.h)
 
 }  // namespace
 
@@ -1069,23 +1065,10 @@ int vtx_set_barcodes(vtx_ctx* c, const uint8_t* bytes, const uint64_t* offsets, 
         if (offsets[j + 1] - offsets[j] >= VTX_TAG_MISSING) return fail(c, VTX_E_UNSUPPORTED, "vtx_set_barcodes: barcode %u longer than 65534 bytes", j);
     }
     // open addressing, load <= 1/2; slot = index + 1, 0 = empty.  Duplicated byte strings keep the first index (:704-710).
-    uint32_t cap = 16;
-    while (cap < 2ull * n) cap <<= 1;
+    const uint32_t cap = vtxp::table_capacity(n);
     std::vector<uint32_t> slots(cap, 0);
     std::vector<uint64_t> hashes(std::max(n, 1u));
-    for (uint32_t j = 0; j < n; ++j) {
-        const uint8_t* b = bytes + offsets[j];
-        const uint32_t len = (uint32_t)(offsets[j + 1] - offsets[j]);
-        const uint64_t h = vtx_hash_bytes(b, len, 0);
-        hashes[j] = h;
-        bool dup = false;
-        uint32_t sidx = (uint32_t)h & (cap - 1);
-        for (; slots[sidx]; sidx = (sidx + 1) & (cap - 1)) {
-            const uint32_t k = slots[sidx] - 1;
-            if (hashes[k] == h && offsets[k + 1] - offsets[k] == len && memcmp(bytes + offsets[k], b, len) == 0) { dup = true; break; }
-        }
-        if (!dup) slots[sidx] = j + 1;
-    }
+    vtxp::table_build(bytes, offsets, n, cap, slots.data(), hashes.data());
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     const uint64_t nbytes = n ? offsets[n] : 0;
     HIP_TRY(c, c->d_bc_slots.reserve(cap * sizeof(uint32_t)));
@@ -1144,8 +1127,8 @@ static int raw_prepare(vtx_ctx* c, uint32_t nl, uint32_t nr, uint64_t read_bytes
     uint32_t* d_shape_cnt = (uint32_t*)(d_counters + 8);
     uint32_t* d_lut_flag = d_shape_cnt + 16;
     HIP_TRY(c, hipEventRecord(c->ev[EV_PREP_START], s));
-    const uint32_t cell_bits = bits_for(c->cfg.n_barcodes ? c->cfg.n_barcodes - 1 : 0);
-    const int end_bit = (int)(cell_bits + bits_for(nl));
+    const uint32_t cell_bits = vtxp::cell_bits_of(c->cfg.n_barcodes);
+    const int end_bit = (int)vtxp::end_bit_of(cell_bits, nl);
     if (end_bit > 64) return fail(c, VTX_E_UNSUPPORTED, "raw batch: loci x barcodes exceed a 64-bit sort key");
     const int use_umi = c->cfg.use_umi ? 1 : 0;
     unsigned long long cnt[8] = {0};
@@ -1153,7 +1136,7 @@ static int raw_prepare(vtx_ctx* c, uint32_t nl, uint32_t nr, uint64_t read_bytes
     // test hook: the first N rounds hash every UMI to 0, so that the collision check and the re-seed are exercised
     const uint32_t weak_rounds = VTX_DEV_ENV("VTX_PREP_WEAK_ROUNDS") ? (uint32_t)atoi(VTX_DEV_ENV("VTX_PREP_WEAK_ROUNDS")) : 0;
     if (nr && locus_from_loci) HIP_TRY(c, vtxk_prep_rec_locus(c->d_loci.as<vtx_locus>(), nl, c->d_raw_locus.as<uint32_t>(), s));
-    for (uint64_t seed = 0x9e3779b97f4a7c15ull;; seed = seed * 0xd1342543de82ef95ull + 1) {
+    for (uint64_t seed = vtxp::UMI_SEED0;; seed = vtxp::next_seed(seed)) {
         ++rounds;
         HIP_TRY(c, hipMemsetAsync(c->d_prep_cnt.p, 0, 8 * u64 + 64 * u32, s));
         HIP_TRY(c, hipMemsetAsync(c->d_locus_cnt.p, 0, ((size_t)nl + 1) * u32, s));      // first record of each locus
@@ -1190,7 +1173,7 @@ static int raw_prepare(vtx_ctx* c, uint32_t nl, uint32_t nr, uint64_t read_bytes
         HIP_TRY(c, hipMemcpyAsync(cnt, d_counters, 8 * u64, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         if (!cnt[4]) break;                  // no UMI hash collision inside a (locus, cell) group
-        if (rounds == 8) return fail(c, VTX_E_STATE, "raw batch: UMI hash collisions with 8 different seeds");
+        if (rounds == vtxp::UMI_MAX_ROUNDS) return fail(c, VTX_E_STATE, "raw batch: UMI hash collisions with 8 different seeds");
     }
     const size_t scan_tmp = vtxk_scan_temp_bytes(std::max(nr, nl));
     // dense UMI group numbers; per-locus record ranges of the kept, sorted records

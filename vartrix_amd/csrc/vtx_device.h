@@ -24,26 +24,9 @@
 // a kernel's profiling-ablation selector: the constant 0 in the production build (the early exits compile out of the hot bodies)
 #define VTX_ABLATE(x) (VTX_DEVTOOLS_ON ? (uint32_t)(x) : 0u)
 
-// 64-bit hash of a tag byte string (FNV-1a style over little-endian 8-byte words + fmix64), identical on the
-// host (barcode table build) and the device.  The words are read with memcpy: gfx950 global memory takes
-// unaligned dwordx2 loads, so a lane hashes an 18-byte barcode with 3 loads instead of 18.
-static __host__ __device__ inline uint64_t vtx_load_le(const uint8_t* p, uint32_t n) {   // n <= 8 bytes, zero-extended
-    uint64_t w = 0;
-    if (n == 8) { __builtin_memcpy(&w, p, 8); return w; }
-    for (uint32_t i = 0; i < n; ++i) w |= (uint64_t)p[i] << (8 * i);
-    return w;
-}
-static __host__ __device__ inline uint64_t vtx_hash_bytes(const uint8_t* p, uint32_t n, uint64_t seed) {
-    uint64_t h = (0xcbf29ce484222325ull ^ seed) + n;
-    for (uint32_t i = 0; i < n; i += 8) { h ^= vtx_load_le(p + i, n - i < 8 ? n - i : 8); h *= 0x100000001b3ull; h ^= h >> 29; }
-    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
-    return h;
-}
-static __host__ __device__ inline bool vtx_bytes_equal(const uint8_t* a, const uint8_t* b, uint32_t n) {
-    bool eq = true;
-    for (uint32_t i = 0; i < n; i += 8) { const uint32_t m = n - i < 8 ? n - i : 8; eq &= vtx_load_le(a + i, m) == vtx_load_le(b + i, m); }
-    return eq;
-}
+// vtx_load_le, vtx_hash_bytes, vtx_bytes_equal (the tag bytes' hash and compare, identical on the host and the device) and the rules of the
+// raw-batch preparation: vtx_prep_core.h, which the host can compile on its own (tests/prepcore/)
+#include "vtx_prep_core.h"
 
 // The banded stage's counter block (vtx_ctx::d_cnt): 64 words, all of them zeroed once per pass of the stage (BandPass::run); the groups
 // say what zeroes them more often.  A group is what the host zeroes or copies as a unit, by its name and sizeof.  A kernel or launcher

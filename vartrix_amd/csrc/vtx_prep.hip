@@ -11,6 +11,10 @@
 //             (a collision between two UMIs of one cell is detected, never silently merged: the caller
 //             re-runs with another seed), per-locus counts, kernel-shape histogram
 //
+// The decisions themselves — table probe, record validity, barcode test before UB test, key packing, heads and the collision flag,
+// vtx_submit's record codes — are the functions of vtx_prep_core.h (vtxp::), which the host compiles too: tests/prepcore/ runs the
+// whole preparation from them on the CPU.
+//
 // All of it is HBM-bound integer/byte work: one pass over the records per step, coalesced except the
 // tag-byte and table probes (L2-resident: the barcode table of 10^4..10^6 entries is a few MB).
 #include <hip/hip_runtime.h>
@@ -50,29 +54,16 @@ __global__ __launch_bounds__(256) void prep_resolve_kernel(
     const uint32_t max_read_len = max_read_len_fmt & 0x7fffffffu, odd_mask = max_read_len_fmt >> 31;
     uint32_t n_not_bc = 0, n_no_umi = 0, n_bad = 0;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        uint64_t klc = (uint64_t)n_loci << cell_bits, ku = 0;
+        uint64_t klc = vtxp::dropped_key(n_loci, cell_bits), ku = 0;
         const vtx_raw_record r = raw[i];
-        const bool umi_missing = r.umi_len == VTX_TAG_MISSING;
-        const bool bad = (uint64_t)r.bc_off + r.bc_len > tag_bytes || (uint64_t)r.read_off + r.read_len > read_bytes ||
-                         r.read_len > max_read_len || (r.read_off & odd_mask) || (use_umi && !umi_missing && (uint64_t)r.umi_off + r.umi_len > tag_bytes);
-        if (bad) ++n_bad;
+        if (vtxp::raw_record_bad(r, tag_bytes, read_bytes, max_read_len, odd_mask, use_umi)) ++n_bad;
         else {
-            const uint8_t* b = tags + r.bc_off;
-            const uint64_t h = vtx_hash_bytes(b, r.bc_len, 0);
-            uint32_t cell = 0xffffffffu;
-            for (uint32_t s = (uint32_t)h & bc_mask;; s = (s + 1) & bc_mask) {
-                const uint32_t e = bc_slots[s];
-                if (!e) break;
-                const uint32_t j = e - 1;
-                if (bc_hash[j] != h) continue;
-                const uint64_t o = bc_off[j];
-                if (bc_off[j + 1] - o != r.bc_len) continue;
-                if (vtx_bytes_equal(bc_bytes + o, b, r.bc_len)) { cell = j; break; }
-            }
-            if (cell == 0xffffffffu) ++n_not_bc;                     // :870-876
-            else if (use_umi && umi_missing) ++n_no_umi;             // :879-888
+            const uint32_t cell = vtxp::table_probe(bc_slots, bc_mask, bc_hash, bc_off, bc_bytes, tags + r.bc_off, r.bc_len);
+            const vtxp::Class cls = vtxp::classify(cell, use_umi, r.umi_len == VTX_TAG_MISSING);
+            if (cls == vtxp::NOT_CELL_BC) ++n_not_bc;                // :870-876
+            else if (cls == vtxp::NON_UMI) ++n_no_umi;               // :879-888
             else {
-                klc = ((uint64_t)rec_locus[i] << cell_bits) | cell;
+                klc = vtxp::kept_key(rec_locus[i], cell, cell_bits);
                 if (use_umi) ku = vtx_hash_bytes(tags + r.umi_off, r.umi_len, seed) & hash_mask;
             }
         }
@@ -116,27 +107,18 @@ __global__ __launch_bounds__(256) void prep_finalize_kernel(
     bool collide = false;
     for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < n_kept; j += gridDim.x * 256) {
         const uint32_t i = perm[j];
-        const uint64_t k = key_lc_sorted[j];
-        const uint32_t locus = (uint32_t)(k >> cell_bits), cell = (uint32_t)(k & ((1ull << cell_bits) - 1));
         const vtx_raw_record r = raw[i];
-        const uint64_t kprev = j ? key_lc_sorted[j - 1] : ~0ull;
-        bool head = kprev != k;
-        if (use_umi && !head) {
-            const uint32_t ip = perm[j - 1];
-            if (key_umi[ip] != key_umi[i]) head = true;
-            else {
-                // equal hashes inside one (locus, cell): must be the same bytes, else this seed collides
-                const vtx_raw_record q = raw[ip];
-                if (q.umi_len != r.umi_len || !vtx_bytes_equal(tags + q.umi_off, tags + r.umi_off, r.umi_len)) collide = true;
-            }
-        }
-        records[j] = vtx_record{r.read_off, r.read_len, cell, 0};
+        // group head, UMI head (equal hashes inside one (locus, cell) must be the same bytes, else this seed collides), locus run
+        const vtxp::Decision d = vtxp::finalize_decide(j, n_kept, perm, key_lc_sorted, key_umi, raw, r, tags, cell_bits, use_umi);
+        const uint32_t locus = d.locus;
+        collide |= d.collide;
+        records[j] = vtx_record{r.read_off, r.read_len, d.cell, 0};
         rec_locus[j] = locus;
-        umi_head[j] = head ? 1u : 0u;
+        umi_head[j] = d.head ? 1u : 0u;
         seq[j] = j;
         // records are sorted by locus: the run boundaries give every locus its record range without atomics
-        if (j == 0 || (uint32_t)(kprev >> cell_bits) != locus) locus_first[locus] = j;
-        if (j + 1 == n_kept || (uint32_t)(key_lc_sorted[j + 1] >> cell_bits) != locus) locus_end[locus] = j + 1;
+        if (d.locus_first) locus_first[locus] = j;
+        if (d.locus_last) locus_end[locus] = j + 1;
         const uint32_t rl = r.read_len;
         const bool slow = rl > c_fast_limit[0] || max(loci[locus].ref_len, loci[locus].alt_len) > c_fast_limit[1];
         uint32_t my_shape = 0;
@@ -181,7 +163,7 @@ __global__ __launch_bounds__(256) void prep_locus_ranges_kernel(vtx_locus* __res
 // length limit, cell index range, order (cell_index, umi_id) inside the locus (cell_index alone when !use_umi: umi_id may then hold
 // any value, include/vtx.h, and nothing reads it); plus what the host loop used to derive —
 // kernel shape per record, shape histogram, DP-cell count, longest read.  counters[6] = min over offending records of
-// (record << 3 | code): 1 read outside the arena, 2 read too long, 3 cell_index >= n_barcodes, 4 order.
+// (record << 3 | code): vtxp::check_code — 1 read outside the arena, 2 read too long, 3 cell_index >= n_barcodes, 5 odd read_off, 4 order.
 __global__ __launch_bounds__(256) void prep_check_kernel(
     const vtx_record* __restrict__ records, uint32_t n, const uint32_t* __restrict__ rec_locus,
     const vtx_locus* __restrict__ loci, uint64_t read_bytes, uint32_t max_read_len_fmt, uint32_t n_barcodes, int use_umi, uint32_t n_shapes,
@@ -199,16 +181,8 @@ __global__ __launch_bounds__(256) void prep_check_kernel(
     for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
         const vtx_record r = records[j];
         const uint32_t locus = rec_locus[j];
-        uint32_t code = 0;
-        if ((uint64_t)r.read_off + r.read_len > read_bytes) code = 1;
-        else if (r.read_len > max_read_len) code = 2;
-        else if (r.cell_index >= n_barcodes) code = 3;
-        else if (r.read_off & odd_mask) code = 5;
-        else if (j > 0 && rec_locus[j - 1] == locus) {
-            const vtx_record q = records[j - 1];
-            if (q.cell_index > r.cell_index || (use_umi && q.cell_index == r.cell_index && q.umi_id > r.umi_id)) code = 4;
-        }
-        if (code) bad = min(bad, ((unsigned long long)j << 3) | code);
+        const uint32_t code = vtxp::check_code(records, rec_locus, j, r, locus, read_bytes, max_read_len, odd_mask, n_barcodes, use_umi);
+        if (code) bad = min(bad, vtxp::check_word(j, code));
         const uint32_t rl = min(r.read_len, max_read_len);
         const bool slow = rl > c_fast_limit[0] || max(loci[locus].ref_len, loci[locus].alt_len) > c_fast_limit[1];
         uint32_t my_shape = 0;
